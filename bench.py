@@ -1,15 +1,27 @@
 #!/usr/bin/env python3
 """Benchmark of the single-variant SPA scan (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one pass of the hot path -- rows -> result table: the pass that lists the missing genotypes, the score
 stage and the SPA stage, through sgx_scan_2bit_dev -- over one block of 50 000 variants (the reference's
 seqParallel block size, R/assoc_single.r:204) of synthetic ROW-MAJOR 2-bit genotypes that are already resident in
 this GPU's HBM ("sgx_scan_* on HBM-resident packed genotypes").  Every step scans a different block
-of rows.  Beside the headline: `resident_block` (sgx_scan_block on blocks loaded once -- what a second, third ...
-phenotype over the same genotypes costs per block) and `block_load` (what loading such a block costs).
+of rows.
+
+A plain run sets up, warms up, times the K steps and prints the JSON line: the headline `value` / `ms_per_step` and the
+`roofline` worked out from the stage times of those steps.  `--full` adds everything beside the headline, each in runs
+of its own: `resident_block` (sgx_scan_block on blocks loaded once -- what a second, third ... phenotype over the same
+genotypes costs per block), `block_load` (what loading such a block costs), `roofline.alone` (the stages on one lane),
+`cpu_baseline` (the CPU oracle on the same rows, with its parity check), `host_path`, `from_file` and `secondary`
+(other configurations, the null-model operator).  Without `--full` those keys are null.
+
+`--dump-outputs DIR` writes, after the timed steps, the result table of the last timed step as its caller receives
+it: DIR/table.npy (float64 [variants, 8]: AF, mac, num, beta, SE, pval, p.norm, converged; NaN rows where the filter
+drops a variant) and DIR/valid.npy (the valid bytes as float64).  With several GPUs: rank 0's gathered table, the
+last block of every rank in rank order.  Beyond DUMP_CAP bytes a fixed, seeded sample of rows is written, with the
+row numbers in DIR/rows.npy.  The inputs are a function of the arguments alone (counter-based generator, --seed).
 
 Workloads; variants shard across ranks, per-GPU work is
 fixed (weak scaling); with 8 GPUs and 25 steps the job is BASELINE config [2]:
@@ -38,6 +50,7 @@ MFMA_CYCLES, MFMA_ISSUE, VALU_ISSUE = 16, 8, 4
 UNPACK_OPS = 9              # vector instructions per (16 variants x 16 samples) dword of score3_kernel (kern_score3.h)
 UNPACK_OPS_3 = 15           # ... of its three-plane form (s3_unpack3_op), which also has 2 nbf - 1 MFMAs per dword instead of nbf
 BOUND_NAME = {"hbm": "hbm", "mfma": "mfma", "valu_issue": "valu issue"}
+DUMP_CAP = 64 << 20          # bytes of --dump-outputs at most
 
 WORKLOADS = {
     "c3": dict(n=430_000, trait="binary", prevalence=0.01, desc="configs[2] shard"),
@@ -170,11 +183,13 @@ class Case:
         }
 
 
-def measure(case, steps, warmup, lanes, world=1, dist=None, rehearse=False, resident=False):
+def measure(case, steps, warmup, lanes, world=1, dist=None, rehearse=False, resident=False, alone=True, keep=False):
     """warmup + K timed steps -> dict(elapsed, stage stats ...).  resident: the steps scan loaded blocks
     (sgx_scan_block) instead of row-major rows.  world > 1: the timed region is the product's own sharded scan
     (saigegds_amd.dist.scan_sharded: the rank's blocks through sgx_scan_2bit_dev on two lanes, then the one
-    exchange of the path, the gather of the result table on rank 0)."""
+    exchange of the path, the gather of the result table on rank 0).  alone: with several lanes, also the stage
+    times of a few one-lane steps after the timed region.  keep: the table of the last timed step, on the host
+    (rank 0; world > 1: the last block of every rank)."""
     torch = case.torch
     sc = case.sc
     lanes = max(1, min(lanes, case.pool))             # L steps in flight need L result buffers
@@ -212,9 +227,16 @@ def measure(case, steps, warmup, lanes, world=1, dist=None, rehearse=False, resi
     else:
         sdist.scan_shard(sc, chunks, case.bpv, out_r, valid_r, case.block)
         so, sv = (out_r.cpu(), valid_r.cpu()) if rehearse else (out_r, valid_r)
-        sdist.gather_table(so, sv, m_r * world, recv=recv)
+        tab = sdist.gather_table(so, sv, m_r * world, recv=recv)
     barrier()
     elapsed = time.perf_counter() - t0
+    last = None
+    if keep and world == 1:
+        b = (warmup + steps - 1) % case.pool
+        last = (case.out[b].cpu().numpy(), case.valid[b].cpu().numpy())
+    elif keep and tab[0] is not None:
+        idx = torch.cat([torch.arange((r + 1) * m_r - case.block, (r + 1) * m_r) for r in range(world)]).to(tab[0].device)
+        last = (tab[0].index_select(0, idx).cpu().numpy(), tab[1].index_select(0, idx).cpu().numpy())
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else case.dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -223,7 +245,7 @@ def measure(case, steps, warmup, lanes, world=1, dist=None, rehearse=False, resi
     assert ncalls == steps, (ncalls, steps)
     # the stages with nothing running beside them (one lane, a few extra steps outside the timed region)
     iso = None
-    if lanes > 1:
+    if alone and lanes > 1:
         sc.set_option("lanes", 1)
         for i in range(2):                 # (the first steps after the switch still see the other lane's tail)
             step(i)
@@ -238,7 +260,20 @@ def measure(case, steps, warmup, lanes, world=1, dist=None, rehearse=False, resi
         # which now and then is hundreds of microseconds
         iso = tuple(float(np.median([p[k] for p in per])) for k in range(4))
         sc.set_option("lanes", lanes)
-    return dict(elapsed=elapsed, tot=tot, iso=iso, lanes=lanes)
+    return dict(elapsed=elapsed, tot=tot, iso=iso, lanes=lanes, last=last)
+
+
+def dump_outputs(d, arrays, seed):
+    """arrays (equal numbers of rows) -> d/<name>.npy in float64; beyond DUMP_CAP bytes a sample of rows drawn
+    with `seed`, their numbers in d/rows.npy"""
+    os.makedirs(d, exist_ok=True)
+    m = len(next(iter(arrays.values())))
+    row_bytes = sum(8 * (a.size // max(1, m)) for a in arrays.values())
+    if m * row_bytes > DUMP_CAP:
+        rows = np.sort(np.random.default_rng(seed).choice(m, DUMP_CAP // (row_bytes + 8), replace=False))
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, rows=rows)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def main():
@@ -267,7 +302,13 @@ def main():
     ap.add_argument("--grm-markers", type=int, default=100_000, help="markers of the null-model operator's figures in `secondary.grm`; 0 = skip")
     ap.add_argument("--secondary", type=int, default=1,
                     help="1: after the main measurement (rank 0, one GPU) a few steps of K = 13, c2 and c4 into `secondary`")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline (resident_block, block_load, roofline.alone, cpu_baseline, host_path, "
+                         "from_file, secondary; the options above say how much of each); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result table of the last timed step to DIR/*.npy (float64)")
     args = ap.parse_args()
+    full = args.full
 
     import torch
     import torch.distributed as dist
@@ -305,12 +346,14 @@ def main():
                       "world_size": dist.get_world_size(), "devices": devs}
 
     block, steps, warmup = args.block, args.steps, args.warmup
-    do_res = rank == 0 and world == 1 and args.resident_steps > 0
+    do_res = full and rank == 0 and world == 1 and args.resident_steps > 0
     case = Case(args.workload, args.k, block, args.seed, args.pool_gb, steps + warmup, rank, local, args.n_samp,
                 miss_rate=args.missing, n_resident=4 if do_res else 0)
     n, wl, sc, pool = case.n, case.wl, case.sc, case.pool
-    r = measure(case, steps, warmup, args.lanes, world, dist, rehearse)
+    r = measure(case, steps, warmup, args.lanes, world, dist, rehearse, alone=full, keep=args.dump_outputs is not None)
     elapsed, tot, lanes = r["elapsed"], r["tot"], r["lanes"]
+    if args.dump_outputs is not None and r["last"] is not None:
+        dump_outputs(args.dump_outputs, {"table": r["last"][0], "valid": r["last"][1]}, args.seed)
     # ---- beside the headline: blocks loaded once, scanned again (a further phenotype over the same genotypes) ----
     resident_block, block_load = None, None
     if do_res and case.blocks:
@@ -421,7 +464,7 @@ def main():
     b0 = warmup % pool
     out, valid, bpv, sm = case.out, case.valid, case.bpv, case.sm
     rows = case.rows[b0]             # the rows of a timed block (resident: the generator is not run again)
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         from concurrent.futures import ThreadPoolExecutor
         from oracle import Oracle
         cores, cpu_model = _physical_cores()
@@ -486,7 +529,7 @@ def main():
 
     # ---- PCIe-inclusive rate of the host-buffer entry point (rank 0, N=1 only; never `value`) -------
     host_path = None
-    if rank == 0 and world == 1 and args.host_variants > 0:
+    if full and rank == 0 and world == 1 and args.host_variants > 0:
         from saigegds_amd._lib import PinnedBuffer
         nh = min(block, args.host_variants)
         sc.set_option("lanes", 1)
@@ -508,7 +551,7 @@ def main():
 
     # ---- file -> table: seqAssocGLMM_SPA on a GDS file (rank 0, N=1 only; never `value`) -----------------
     from_file = None
-    if rank == 0 and world == 1 and args.file_variants > 0:
+    if full and rank == 0 and world == 1 and args.file_variants > 0:
         import tempfile
         from saigegds_amd import assoc as assoc_mod
         from saigegds_amd import synth as synth_mod
@@ -569,7 +612,7 @@ def main():
 
     # ---- other configurations, a few steps each (rank 0, N=1 only) -----------------------------------
     secondary = None
-    if rank == 0 and world == 1 and args.secondary and args.workload == "c3" and args.k == 3 and not args.n_samp:
+    if full and rank == 0 and world == 1 and args.secondary and args.workload == "c3" and args.k == 3 and not args.n_samp:
         secondary = {}
         for name, w2, k2, miss2 in (("k13", "c3", 13, 1e-3), ("c2", "c2", 3, 1e-3), ("c4", "c4", 3, 1e-3),
                                     ("c3_missing_1e-2", "c3", 3, 1e-2), ("c3_missing_2e-2", "c3", 3, 2e-2)):

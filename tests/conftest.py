@@ -9,20 +9,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference"
 
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-    config.addinivalue_line("markers", "reference: reads /root/reference (build container only)")
-
-
-def pytest_collection_modifyitems(config, items):
-    have_ref = os.path.isdir(REFERENCE)
-    skip_ref = pytest.mark.skip(reason="/root/reference not present on this machine")
-    for it in items:
-        if "reference" in it.keywords and not have_ref:
-            it.add_marker(skip_ref)
 
 
 def load_null_model(name):

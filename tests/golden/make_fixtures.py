@@ -13,6 +13,9 @@ Inputs (data files of the reference's test-suite, inst/unitTests/test_SAIGE.R:79
   inst/unitTests/saige_pval_quant.rds   golden result table, quantitative
   inst/extdata/pheno.txt.gz             phenotypes + covariates (input of test.saige_fit_null_model)
 Outputs are data only (decoded arrays); no reference source is copied.
+The host tests that check the decoders against those raw files read copies of
+three of them stored here as they are: grm1k_10k_snp.gds, assoc_100snp.gds and
+saige_model_quant.rds.
 """
 import os
 import sys

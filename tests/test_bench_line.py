@@ -41,3 +41,26 @@ def test_other_configurations_name_their_form(name):
     d = _line(name)
     assert d["roofline"]["bounds"]["form"] in ("two planes", "three planes")
     assert d["value"] > 0 and d["roofline"]["frac"] > 0
+
+
+def test_dump_outputs_writes_float64_and_caps_by_a_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as float64 .npy; beyond the cap the same seeded rows on every run."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    table = np.random.default_rng(0).random((5000, 8))
+    valid = (np.arange(5000) % 3 > 0).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "all"), {"table": table, "valid": valid}, 1)
+    assert np.array_equal(np.load(tmp_path / "all" / "table.npy"), table)
+    v = np.load(tmp_path / "all" / "valid.npy")
+    assert v.dtype == np.float64 and np.array_equal(v, valid)
+    assert not (tmp_path / "all" / "rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_CAP", 100_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"table": table, "valid": valid}, 1)
+    got = {k: [np.load(tmp_path / d / f"{k}.npy") for d in ("a", "b")] for k in ("table", "valid", "rows")}
+    assert sum(a.nbytes for a, _ in got.values()) <= 100_000
+    rows = got["rows"][0].astype(np.int64)
+    assert np.array_equal(got["rows"][0], got["rows"][1]) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["table"][0], table[rows]) and np.array_equal(got["valid"][0], valid[rows])

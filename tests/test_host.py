@@ -6,7 +6,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE, ROOT, load_null_model
+from conftest import GOLDEN, ROOT, load_null_model
 
 
 def test_abi_exports_every_declared_symbol():
@@ -149,14 +149,13 @@ def test_result_writers_roundtrip(tmp_path):
         assert b"\tR.logical\x00" in g.stream(g.node("converged").block_id)
 
 
-@pytest.mark.reference
 def test_gds_writer_emits_the_reference_files_records():
     """A node written by GdsWriter with the data of a node of the reference's own file is that node's
     stream byte for byte (up to the stream id, the stored size and SeqArray's md5 attribute)."""
     import tempfile
     from saigegds_amd.gds import GdsFile
     from saigegds_amd.gds_write import GdsWriter
-    g = GdsFile(REFERENCE + "/inst/extdata/assoc_100snp.gds")
+    g = GdsFile(os.path.join(GOLDEN, "assoc_100snp.gds"))
     with tempfile.TemporaryDirectory() as d:
         w = GdsWriter(os.path.join(d, "t.gds"))
         w.put_attr("FileFormat", "SEQ_ARRAY")
@@ -186,31 +185,29 @@ def test_synthetic_generator_is_counter_based():
     assert a.shape[1] % 16 == 0 and not a[:, 195:].any()   # padding beyond ceil(N/4) is zero
 
 
-@pytest.mark.reference
 def test_formats_against_reference_files():
     """RDS + GDS decoders reproduce the committed fixtures from the raw files."""
     from saigegds_amd.gds import GdsFile
     from saigegds_amd.nullmod import load_modobj
-    g = GdsFile(REFERENCE + "/inst/extdata/grm1k_10k_snp.gds")
+    g = GdsFile(os.path.join(GOLDEN, "grm1k_10k_snp.gds"))
     packed, n, m = g.dosage_alt_packed()
     z = np.load(os.path.join(GOLDEN, "grm1k_10k_snp.npz"))
     assert (n, m) == (1000, 10000) and np.array_equal(packed, z["packed"])
     assert g.sample_id()[:2] == ["s1", "s2"] and g.read("annotation/id")[0] == "rs1"
-    mod = load_modobj(REFERENCE + "/inst/unitTests/saige_model_quant.rds")
+    mod = load_modobj(os.path.join(GOLDEN, "saige_model_quant.rds"))
     ref = load_null_model("saige_model_quant.npz")
     assert mod.trait_type == "quantitative" and np.array_equal(mod.y, ref.y)
-    g2 = GdsFile(REFERENCE + "/inst/extdata/assoc_100snp.gds")
+    g2 = GdsFile(os.path.join(GOLDEN, "assoc_100snp.gds"))
     assert not g2.has_genotype()
     ds = g2.dosage_real()
     assert ds.shape == (100, 1000) and set(np.unique(ds)) == {0.0, 1.0, 2.0}
 
 
-@pytest.mark.reference
 def test_gds_row_ranges_equal_whole_reads():
     """Ranged reads through the LZMA_RA block index (what the streaming driver uses) give the same
     bytes as decoding the whole node, across block borders and for sample subsets."""
     from saigegds_amd.gds import GdsFile, unpack_dosage_2bit
-    g = GdsFile(REFERENCE + "/inst/extdata/grm1k_10k_snp.gds")
+    g = GdsFile(os.path.join(GOLDEN, "grm1k_10k_snp.gds"))
     z = np.load(os.path.join(GOLDEN, "grm1k_10k_snp.npz"))
     for lo, hi in ((0, 1), (4700, 4800), (4718, 4719), (9437, 9440), (9990, 10000), (0, 10000)):
         assert np.array_equal(g.dosage_alt_packed_range(lo, hi), z["packed"][lo:hi]), (lo, hi)
@@ -218,7 +215,7 @@ def test_gds_row_ranges_equal_whole_reads():
     got = unpack_dosage_2bit(g.dosage_alt_packed_range(4000, 5000, sel), 5)
     assert np.array_equal(got, unpack_dosage_2bit(z["packed"][4000:5000], 1000)[:, sel])
     assert np.array_equal(g.read_rows("position", 100, 250), np.asarray(g.read("position"))[100:250])
-    g2 = GdsFile(REFERENCE + "/inst/extdata/assoc_100snp.gds")
+    g2 = GdsFile(os.path.join(GOLDEN, "assoc_100snp.gds"))
     assert np.array_equal(g2.dosage_real_range("annotation/format/DS", 10, 37), g2.dosage_real()[10:37])
 
 
