@@ -115,8 +115,12 @@ typedef struct sgx_stats {
 	                          made when the block was loaded                                             */
 	uint32_t three_plane;  /* 1: the call took the three-plane form of the contraction kernel (the sums over the
 	                          missing samples from a third MFMA plane: no lists, no sparse pass; chosen for
-	                          few score columns or many missing genotypes); totals: number of such calls     */
-	uint32_t n_unlisted;   /* variants whose missing genotypes found the pool of the lists full (FP64 kernel)  */
+	                          few score columns or many missing genotypes); totals: number of such calls.
+	                          0 for a call of the FP64 kernels (score_v1, or a model outside the fixed-point form) */
+	uint32_t n_unlisted;   /* variants of a two-plane call whose missing genotypes are not listed, scored by the FP64
+	                          kernel instead (same results): a row-major call lists at most 256 missing genotypes of a
+	                          (variant, sample range) segment, a resident block what the pool of its lists has room
+	                          for; 0 in the three-plane form and for the FP64 kernels                               */
 	uint32_t n_guarded;    /* variants whose a-posteriori bound on the fixed-point columns' quantisation (its
 	                          effect on the z-score) exceeded the guard: scored by the FP64 kernel  */
 } sgx_stats;

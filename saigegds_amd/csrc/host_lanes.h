@@ -62,8 +62,9 @@ static int sync_lane(sgx_handle *h)
 		h->stats.three_plane = h->used_miss ? 1u : 0u;
 		h->stats.n_guarded = (uint32_t)h->h_counters[21];
 		h->stats.n_unlisted = (uint32_t)h->h_counters[23] - h->stats.n_guarded;
-		{
+		if (h->chain_ran) {
 			// the step's missing genotypes (census of the epilogue, units of 64) decide the form of the NEXT row-major calls
+			// (a call of the FP64 kernels counted none: it leaves the choice as it was)
 			sgx_handle *p = h->owner ? h->owner : h;
 			const double frac = 64.0 * (double)h->h_counters[22] / ((double)std::max<uint64_t>(1, h->stats.n_variants) * (double)h->md.N);
 			const bool over = (uint64_t)h->stats.n_unlisted * 32 > h->stats.n_variants;

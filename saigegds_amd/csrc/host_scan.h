@@ -34,7 +34,7 @@ static int launch_block_scan(sgx_handle *h, const sgx_block *b, size_t M, double
 	S3Plan pl{};
 	int NCW = 0, NAFW = 0;
 	const int slots = miss ? 2 * NBF - 1 : NBF;      // fragment slots of a variant's row of limb sums
-	h->used_miss = miss;
+	h->used_miss = miss; h->chain_ran = true;
 	HIPCHK(hipStreamWaitEvent(st, b->ready, 0));
 	HIPCHK(hipEventRecord(h->ev[0], st));            // (counters and queue cursors: zeroed by s3_reduce_kernel)
 	int rc = ensure_buf(h, &h->s3_t3, &h->s3_t3_cap, (size_t)b->nr * M * md.P * 2);            // per-range sums over the missing samples (the epilogue adds them up)
@@ -204,6 +204,7 @@ extern "C" int sgx_scan_block(sgx_handle *h, const sgx_block *b, double *out8_de
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(lane->ev[1], st));
 		lane->stats.score_launches = 1;
+		lane->used_miss = false; lane->chain_ran = false;
 		rc = launch_spa<IN_2BIT>(lane, rr, b->M, out8_dev);
 		if (rc) return rc;
 		HIPCHK(hipEventRecord(lane->ev[2], st));

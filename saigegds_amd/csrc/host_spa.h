@@ -205,6 +205,7 @@ static int launch_scan(sgx_handle *h, const void *rows, size_t row_bytes, size_t
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(h->ev[1], st));
 	h->stats.score_launches = 1;
+	h->used_miss = false; h->chain_ran = false;
 	int rc = launch_spa<INPUT>(h, rr, M, out8);
 	if (rc) return rc;
 	HIPCHK(hipEventRecord(h->ev[2], st));

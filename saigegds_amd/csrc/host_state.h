@@ -125,7 +125,11 @@ struct sgx_handle {
 	// bound on the z-score's move by the fixed-point columns' quantisation beyond which a variant is scored by the FP64
 	// kernel (score3_epilogue): 2e-11 keeps the p-value inside 1e-10 relative with room; "guard_exp" option: 10^-x
 	double guard_tol = 2e-11;
-	bool used_miss = false;           // this lane's call in flight took the three-plane form
+	// the form of this lane's call in flight, set by every launch path: used_miss -- it took the three-plane form;
+	// chain_ran -- it ran the fixed-point chain (contraction kernel + epilogue), whose census of the missing genotypes
+	// steers dense_mode (the FP64 kernels count none: their calls leave dense_mode as it is)
+	bool used_miss = false;
+	bool chain_ran = false;
 	int next_lane = 0;                // primary: which lane takes the next _dev call
 	sgx_handle *last_issued = nullptr;// primary: lane of the most recent call
 	sgx_stats total{};                // primary: sums over harvested calls (sgx_get_stats_total)

@@ -137,6 +137,17 @@ __device__ __forceinline__ void spa_write_row(const SpaRec &r, double Tstat, dou
 	o[7] = converged ? 1.0 : 0.0;
 }
 
+// log(1 - m + m e^{gt}) = g t + log((1-m) e^{-gt} + m) given d = (1-m) e^{-gt} + m: reuses the exponential; when
+// e^{-gt} overflows the reference's own form is evaluated instead.  Where e^{gt} overflows (g t > log DBL_MAX, the
+// bound of fast_exp) the reference's term is +inf (SPATest.cpp:49): its Korg, and so its saddle-point p-value, then
+// gives 0 and the row falls back to p.norm, not converged (saige_main.cpp:390-391).  The rewritten form would stay
+// finite there and report a converged row: the reference's infinity is kept.
+__device__ __forceinline__ double cgf_korg_term(double g, double m, double t, double d, double om)
+{
+	if (g * t > 709.782712893384) return INFINITY;
+	return isfinite(d) ? fma(g, t, fast_log(d)) : fast_log(fma(m, fast_exp(g * t), om));
+}
+
 // K1, K2 (SPATest.cpp:64,79-80) and Korg (:49) terms of one carrier at t
 template <bool WITH_K>
 __device__ __forceinline__ void cgf_terms(double g, double m, double t, double &k1, double &k2, double &k0)
@@ -148,9 +159,7 @@ __device__ __forceinline__ void cgf_terms(double g, double m, double t, double &
 	k1 = fma(mg, rr, k1);
 	const double tt = c2 * e * rr * rr;
 	if (isfinite(tt)) k2 += tt;
-	// log(1 - m + m e^{gt}) = g t + log((1-m) e^{-gt} + m): reuses the exponential;
-	// when e^{-gt} overflows the reference's own form is evaluated instead
-	if (WITH_K) k0 += isfinite(d) ? fma(g, t, fast_log(d)) : fast_log(fma(m, fast_exp(g * t), om));
+	if (WITH_K) k0 += cgf_korg_term(g, m, t, d, om);
 }
 
 

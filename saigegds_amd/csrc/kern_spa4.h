@@ -702,7 +702,7 @@ __device__ __forceinline__ void cgf_terms_rt(double g, double m, double t, bool 
 	k1 = fma(mg, rr, k1);
 	const double tt = c2 * e * rr * rr;
 	if (isfinite(tt)) k2 += tt;
-	if (with_k) k0 += isfinite(d) ? fma(g, t, fast_log(d)) : fast_log(fma(m, fast_exp(g * t), om));
+	if (with_k) k0 += cgf_korg_term(g, m, t, d, om);
 }
 
 // bytes of scratch per workgroup: (adj, mu) list + index list, N entries each
