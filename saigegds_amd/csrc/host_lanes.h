@@ -40,6 +40,16 @@ extern "C" int sgx_set_option(sgx_handle *h, const char *name, long long value)
 	return SGX_OK;
 }
 
+static void stats_add(sgx_stats &into, const sgx_stats &x)
+{
+	into.n_variants += x.n_variants; into.n_valid += x.n_valid; into.n_spa += x.n_spa;
+	into.n_spa_dense += x.n_spa_dense; into.n_spa_slow += x.n_spa_slow;
+	into.ms_score += x.ms_score; into.ms_spa += x.ms_spa; into.ms_total += x.ms_total;
+	into.ms_kernel += x.ms_kernel; into.ms_lists += x.ms_lists;
+	into.score_launches += x.score_launches; into.spa_launches += x.spa_launches;
+	into.three_plane += x.three_plane; into.n_unlisted += x.n_unlisted; into.n_guarded += x.n_guarded;
+}
+
 // wait for this lane's work and turn its events / counters into stats
 static int sync_lane(sgx_handle *h)
 {
@@ -59,17 +69,17 @@ static int sync_lane(sgx_handle *h)
 		h->stats.n_valid = (uint64_t)h->h_counters[1];
 		h->stats.n_spa_dense = (uint64_t)h->h_counters[2];
 		h->stats.n_spa_slow = (uint64_t)h->h_counters[4];
-		h->stats.three_plane = h->used_miss ? 1u : 0u;
+		h->stats.three_plane = h->form == FORM_THREE ? 1u : 0u;
 		h->stats.n_guarded = (uint32_t)h->h_counters[21];
 		h->stats.n_unlisted = (uint32_t)h->h_counters[23] - h->stats.n_guarded;
-		if (h->chain_ran) {
+		if (h->form != FORM_FP64) {
 			// the step's missing genotypes (census of the epilogue, units of 64) decide the form of the NEXT row-major calls
 			// (a call of the FP64 kernels counted none: it leaves the choice as it was)
 			sgx_handle *p = h->owner ? h->owner : h;
 			const double frac = 64.0 * (double)h->h_counters[22] / ((double)std::max<uint64_t>(1, h->stats.n_variants) * (double)h->md.N);
 			const bool over = (uint64_t)h->stats.n_unlisted * 32 > h->stats.n_variants;
-			if (!h->used_miss && (frac > SGX_DENSE_ON || over)) p->dense_mode = true;
-			else if (h->used_miss && frac < SGX_DENSE_OFF) p->dense_mode = false;
+			if (h->form != FORM_THREE && (frac > SGX_DENSE_ON || over)) p->dense_mode = true;
+			else if (h->form == FORM_THREE && frac < SGX_DENSE_OFF) p->dense_mode = false;
 		}
 #ifdef SPA5_PROF
 		fprintf(stderr, "routing: tier A %d, tier B %d (of them handed on by A: %d), per-variant kernels %d (series list %d, exact list %d), dense %d\n",
@@ -91,13 +101,7 @@ static int sync_lane(sgx_handle *h)
 		h->stats.ms_lists = l; h->lists_timed = false;
 		h->stats_pending = false;
 		sgx_handle *p = h->owner ? h->owner : h;
-		const sgx_stats &x = h->stats;
-		p->total.n_variants += x.n_variants; p->total.n_valid += x.n_valid; p->total.n_spa += x.n_spa;
-		p->total.n_spa_dense += x.n_spa_dense; p->total.n_spa_slow += x.n_spa_slow;
-		p->total.ms_score += x.ms_score; p->total.ms_spa += x.ms_spa; p->total.ms_total += x.ms_total; p->total.ms_kernel += x.ms_kernel;
-		p->total.ms_lists += x.ms_lists;
-		p->total.score_launches += x.score_launches; p->total.spa_launches += x.spa_launches;
-		p->total.three_plane += x.three_plane; p->total.n_unlisted += x.n_unlisted; p->total.n_guarded += x.n_guarded;
+		stats_add(p->total, h->stats);
 		p->total_calls++;
 	}
 	return SGX_OK;

@@ -105,13 +105,9 @@ static int scan_host(sgx_handle *h, const void *rows, size_t src_row_bytes, size
 		if (r2) return r2;
 		memcpy(out8 + off * 8, h->pin_out[b], m * 8 * sizeof(double));
 		memcpy(valid + off, h->pin_valid[b], m);
-		const sgx_stats &x = h->stats;
-		total.n_variants += x.n_variants; total.n_valid += x.n_valid; total.n_spa += x.n_spa;
-		total.n_spa_dense += x.n_spa_dense; total.n_spa_slow += x.n_spa_slow;
-		total.ms_score += x.ms_score; total.ms_spa += x.ms_spa; total.ms_total += x.ms_total;
-		total.ms_kernel += x.ms_kernel; total.ms_lists += x.ms_lists;
-		total.score_launches += x.score_launches; total.spa_launches += x.spa_launches;
-		total.three_plane = std::max(total.three_plane, x.three_plane); total.n_unlisted += x.n_unlisted; total.n_guarded += x.n_guarded;   // (any chunk)
+		const uint32_t three_plane = std::max(total.three_plane, h->stats.three_plane);   // (any chunk)
+		stats_add(total, h->stats);
+		total.three_plane = three_plane;
 		return SGX_OK;
 	};
 	size_t prev_off = 0, prev_m = 0;
@@ -334,10 +330,7 @@ extern "C" int sgx_burden_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv,
 		HIPCHK(hipMemcpyAsync(valid + off, h->stage_valid, m, hipMemcpyDeviceToHost, h->stream));
 		rc = sgx_sync(h);
 		if (rc) return rc;
-		total.n_variants += h->stats.n_variants; total.n_valid += h->stats.n_valid;
-		total.n_spa += h->stats.n_spa; total.n_spa_dense += h->stats.n_spa_dense; total.n_spa_slow += h->stats.n_spa_slow;
-		total.ms_score += h->stats.ms_score; total.ms_spa += h->stats.ms_spa; total.ms_total += h->stats.ms_total;
-		total.score_launches += h->stats.score_launches; total.spa_launches += h->stats.spa_launches;
+		stats_add(total, h->stats);
 	}
 	h->stats = total;
 	return SGX_OK;

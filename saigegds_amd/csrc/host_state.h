@@ -39,6 +39,14 @@ struct sgx_block {
 	bool info_read = false, dense = false;
 };
 
+// The forms of the single-variant scan; scan_form picks the form of a call.
+enum ScanForm {
+	FORM_FP64,    // FP64 kernels: dosage rows, models the fixed-point form cannot hold, the "score_v1" hook
+	FORM_LISTS,   // two planes on a resident block's lists of the missing genotypes
+	FORM_ROWS,    // two planes on row-major rows, behind the fused list + T3 pass
+	FORM_THREE,   // three planes: the sums over the missing samples come out of the contraction kernel, no lists
+};
+
 struct sgx_handle {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -125,18 +133,14 @@ struct sgx_handle {
 	// bound on the z-score's move by the fixed-point columns' quantisation beyond which a variant is scored by the FP64
 	// kernel (score3_epilogue): 2e-11 keeps the p-value inside 1e-10 relative with room; "guard_exp" option: 10^-x
 	double guard_tol = 2e-11;
-	// the form of this lane's call in flight, set by every launch path: used_miss -- it took the three-plane form;
-	// chain_ran -- it ran the fixed-point chain (contraction kernel + epilogue), whose census of the missing genotypes
-	// steers dense_mode (the FP64 kernels count none: their calls leave dense_mode as it is)
-	bool used_miss = false;
-	bool chain_ran = false;
+	ScanForm form = FORM_FP64;        // the form of this lane's call in flight (scan_begin; read by sync_lane)
 	int next_lane = 0;                // primary: which lane takes the next _dev call
 	sgx_handle *last_issued = nullptr;// primary: lane of the most recent call
 	sgx_stats total{};                // primary: sums over harvested calls (sgx_get_stats_total)
 	uint64_t total_calls = 0;
 };
 
-#define SGX_DENSE_ON  0.005       /* see rows_take_three_planes */
+#define SGX_DENSE_ON  0.005       /* see scan_form */
 #define SGX_DENSE_OFF 0.003
 
 static int set_dev(sgx_handle *h)
