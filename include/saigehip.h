@@ -301,6 +301,24 @@ int  sgx_grm_crossprod(sgx_grm *g, const double *b, double *out);
 int  sgx_grm_pcg(sgx_grm *g, const double *w, const double *tau, const double *b,
 	int maxiter, double tol, double *x_out, int *iters_out);
 
+/* Several right-hand sides at once: the solves of one AI-REML step that share (w, tau) -- the nrun
+ * Hutchinson vectors of get_trace (:627-668), Y and the columns of X in get_coeff_w (:739-758), Sigma_iX
+ * and Sigma_iG of saige_GxG_snp_bin (:1477-1558) -- stream the genotypes once per iteration for all k
+ * instead of once per vector.  B and Out hold k columns of N doubles, column j at B + j*ldb (a
+ * row-major [k][ldb] array); Out / X use the same ldb.  1 <= k <= SGX_GRM_MAX_RHS, ldb >= N.
+ *   sgx_grm_crossprod_multi(_dev)  column j = sgx_grm_crossprod(B[:, j]), bit for bit (host / device
+ *                                  pointers; the _dev form is asynchronous until sgx_grm_sync)
+ *   sgx_grm_pcg_multi              column j = sgx_grm_pcg(w, tau, B[:, j]): the same iterations (iters[j])
+ *                                  and the same x, bit for bit; a column that meets rr <= tol or maxiter
+ *                                  stops and leaves the later products; tau[1] == 0 skips the GRM
+ * Scratch is allocated by the first batched call on a handle and grown to the largest k seen
+ * (about 8 k N doubles, plus 96 ints per sample and per marker). */
+#define SGX_GRM_MAX_RHS 64
+int  sgx_grm_crossprod_multi(sgx_grm *g, const double *B, size_t ldb, int k, double *Out);
+int  sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size_t ldb, int k, double *Out_dev);
+int  sgx_grm_pcg_multi(sgx_grm *g, const double *w, const double *tau, const double *B, size_t ldb, int k,
+	int maxiter, double tol, double *X, int *iters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,10 @@ EXPORTS = (
     "sgx_block_bytes", "sgx_block_create", "sgx_block_create_ex", "sgx_block_free", "sgx_block_load_dev", "sgx_block_load", "sgx_block_variants", "sgx_scan_block",
     "sgx_sync", "sgx_get_stats", "sgx_get_stats_total", "sgx_row_stride", "sgx_synth_2bit_dev", "sgx_selftest", "sgx_set_option",
     "sgx_grm_init", "sgx_grm_init_dev", "sgx_grm_crossprod_dev", "sgx_grm_sync", "sgx_grm_free", "sgx_grm_diag", "sgx_grm_crossprod", "sgx_grm_pcg",
+    "sgx_grm_crossprod_multi", "sgx_grm_crossprod_multi_dev", "sgx_grm_pcg_multi",
 )
+
+GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
 
 
 class SgxError(RuntimeError):
@@ -163,6 +166,12 @@ def load():
     L.sgx_grm_crossprod.argtypes = [vp, vp, vp]
     L.sgx_grm_pcg.restype = C.c_int
     L.sgx_grm_pcg.argtypes = [vp, vp, vp, vp, C.c_int, dp, vp, C.POINTER(C.c_int)]
+    L.sgx_grm_crossprod_multi.restype = C.c_int
+    L.sgx_grm_crossprod_multi.argtypes = [vp, vp, sz, C.c_int, vp]
+    L.sgx_grm_crossprod_multi_dev.restype = C.c_int
+    L.sgx_grm_crossprod_multi_dev.argtypes = [vp, vp, sz, C.c_int, vp]
+    L.sgx_grm_pcg_multi.restype = C.c_int
+    L.sgx_grm_pcg_multi.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int, dp, vp, vp]
     _lib = L
     return L
 
@@ -499,3 +508,37 @@ class GrmOperator:
         check(self._L.sgx_grm_pcg(self._h, w.ctypes.data, tau.ctypes.data, b.ctypes.data, int(maxiter),
                                   float(tol), x.ctypes.data, C.byref(it)))
         return x, int(it.value)
+
+    # -- several right-hand sides: B is [k, N] (row j = vector j), k of any size (batches of GRM_MAX_RHS)
+    def _rhs(self, B) -> np.ndarray:
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[1] != self.n:
+            raise ValueError("B must be [k, N]: one right-hand side of N samples per row")
+        return B
+
+    def crossprod_many(self, B: np.ndarray) -> np.ndarray:
+        """GRM b_j for every row b_j of B ([k, N] -> [k, N]); row j equals crossprod(B[j]) bit for bit."""
+        B = self._rhs(B)
+        out = np.empty_like(B)
+        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
+            k = min(GRM_MAX_RHS, B.shape[0] - j0)
+            check(self._L.sgx_grm_crossprod_multi(self._h, B[j0].ctypes.data, self.n, k, out[j0].ctypes.data))
+        return out
+
+    def crossprod_many_dev(self, b_ptr: int, ldb: int, k: int, out_ptr: int):
+        """Device form: k vectors at b_ptr + j * ldb doubles (asynchronous until sync())."""
+        check(self._L.sgx_grm_crossprod_multi_dev(self._h, b_ptr, int(ldb), int(k), out_ptr))
+
+    def pcg_many(self, w: np.ndarray, tau, B: np.ndarray, maxiter: int = 500, tol: float = 1e-5):
+        """pcg on every row of B in lockstep -> (X [k, N], iters [k]); row j equals pcg(w, tau, B[j])
+        bit for bit, with the same iteration count."""
+        B = self._rhs(B)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        X = np.empty_like(B)
+        iters = np.zeros(B.shape[0], dtype=np.int32)
+        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
+            k = min(GRM_MAX_RHS, B.shape[0] - j0)
+            check(self._L.sgx_grm_pcg_multi(self._h, w.ctypes.data, tau.ctypes.data, B[j0].ctypes.data, self.n, k,
+                                            int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
+        return X, iters

@@ -20,7 +20,10 @@ struct sgx_grm {
 	double *vb = nullptr, *vout = nullptr; // [N] staging for host-pointer calls
 	double *r = nullptr, *z = nullptr, *p = nullptr, *x = nullptr, *Ap = nullptr, *minv = nullptr, *w = nullptr;
 	int n_cu = 256;
+	struct GrmMulti *multi = nullptr;      // scratch of the batched calls (allocated by the first one)
 };
+
+static void grm_multi_release(sgx_grm *g);
 
 #define GRM_RED_BLOCKS 256
 
@@ -84,6 +87,7 @@ extern "C" void sgx_grm_free(sgx_grm *g)
 	if (!g) return;
 	(void)hipSetDevice(g->device);
 	if (g->stream) (void)hipStreamSynchronize(g->stream);
+	grm_multi_release(g);
 	void *ptrs[] = {g->G, g->Gt, g->af, g->inv, g->l0, g->diag, g->FlN, g->FlM, g->accV, g->accS, g->xv, g->gv,
 		g->maxb, g->part, g->vb, g->vout, g->r, g->z, g->p, g->x, g->Ap, g->minv, g->w};
 	for (void *p : ptrs) (void)hipFree(p);
@@ -255,5 +259,276 @@ extern "C" int sgx_grm_sync(sgx_grm *g)
 	if (!g) return fail(SGX_EINVAL, "sgx_grm_sync: NULL handle");
 	HIPCHK(hipSetDevice(g->device));
 	HIPCHK(hipStreamSynchronize(g->stream));
+	return SGX_OK;
+}
+
+// ===========================================================================
+// Several right-hand sides at once: sgx_grm_crossprod_multi(_dev), sgx_grm_pcg_multi.
+// Pass 1 puts two columns' limbs side by side in each 16-column B fragment (7 + 7 limbs) and runs
+// the contraction kernel with up to GRM_MAXF = 3 value fragments (GRM_GROUP = 6 columns); pass 2 needs
+// x and gam limbs of a column (7 + 7) in one fragment and runs with up to 3 (GRM_GROUP2).  A group of 6
+// columns thus streams the genotypes three times (G once, Gt twice) where 6 single products stream
+// them 12 times.
+// Scratch is allocated on the first batched call; the PCG vectors are sized for the largest k seen.
+
+struct GrmMulti {
+	int kcap = 0;                          // columns the [k][N] vectors below have room for
+	uint8_t *FlN = nullptr, *FlM = nullptr;          // limb tile images, 16 GRM_MAXF columns wide
+	int *accV = nullptr, *accS = nullptr;            // [M][32 GRM_MAXF], [N][32 GRM_MAXF]
+	double *xv = nullptr, *gv = nullptr;             // [GRM_GROUP][M]
+	unsigned long long *maxb = nullptr;              // [GRM_MAX_RHS][3]
+	double *part = nullptr, *h_part = nullptr;       // [2 * GRM_MAX_RHS][GRM_RED_BLOCKS]
+	double *B = nullptr, *O = nullptr;               // [k][N] staging of host-pointer calls
+	double *R = nullptr, *Z = nullptr, *P = nullptr, *X = nullptr, *AP = nullptr, *GP = nullptr;   // [k][N]
+};
+static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
+
+static void grm_multi_release(sgx_grm *g)
+{
+	GrmMulti *s = g->multi;
+	if (!s) return;
+	g->multi = nullptr;
+	void *ptrs[] = {s->FlN, s->FlM, s->accV, s->accS, s->xv, s->gv, s->maxb, s->part, s->B, s->O,
+		s->R, s->Z, s->P, s->X, s->AP, s->GP};
+	for (void *p : ptrs) (void)hipFree(p);
+	if (s->h_part) (void)hipHostFree(s->h_part);
+	delete s;
+}
+
+// scratch for k columns (k <= GRM_MAX_RHS); vecs: also the [k][N] vectors
+static int grm_multi_scratch(sgx_grm *g, int k, bool vecs, GrmMulti **out)
+{
+	if (!g->multi) g->multi = new GrmMulti();
+	GrmMulti *s = g->multi;
+	const size_t N = (size_t)g->N, M = g->M;
+	if (!s->FlN) {
+		const size_t bN = (size_t)g->tbN.ntile * 16 * (16 * GRM_MAXF) * 16, bM = (size_t)g->tbM.ntile * 16 * (16 * GRM_MAXF) * 16;
+		HIPCHK(hipMalloc((void **)&s->FlN, bN));
+		HIPCHK(hipMalloc((void **)&s->FlM, bM));
+		HIPCHK(hipMalloc((void **)&s->accV, M * 32 * GRM_MAXF * sizeof(int)));
+		HIPCHK(hipMalloc((void **)&s->accS, N * 32 * GRM_MAXF * sizeof(int)));
+		HIPCHK(hipMalloc((void **)&s->xv, GRM_GROUP * M * sizeof(double)));
+		HIPCHK(hipMalloc((void **)&s->gv, GRM_GROUP * M * sizeof(double)));
+		HIPCHK(hipMalloc((void **)&s->maxb, GRM_MAX_RHS * 3 * sizeof(unsigned long long)));
+		HIPCHK(hipMalloc((void **)&s->part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double)));
+		HIPCHK(hipHostMalloc((void **)&s->h_part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double), hipHostMallocDefault));
+	}
+	if (vecs && k > s->kcap) {
+		for (double **p : {&s->B, &s->O, &s->R, &s->Z, &s->P, &s->X, &s->AP, &s->GP}) {
+			if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
+		}
+		s->kcap = 0;
+		for (double **p : {&s->B, &s->O, &s->R, &s->Z, &s->P, &s->X, &s->AP, &s->GP})
+			HIPCHK(hipMalloc((void **)p, (size_t)k * N * sizeof(double)));
+		s->kcap = k;
+	}
+	*out = s;
+	return SGX_OK;
+}
+
+// per column y of cols: out[y] = sum a (* b), partitioned and summed exactly as grm_sum; one host sync
+// for up to two sets (a1/b1 over cols1, then a2/b2 over cols2; a2 == NULL: none)
+static int grm_sum_multi(sgx_grm *g, GrmMulti *s, const double *a1, const double *b1, size_t ld1, const GrmCols &c1,
+	double *out1, const double *a2 = nullptr, const double *b2 = nullptr, size_t ld2 = 0, const GrmCols *c2 = nullptr,
+	double *out2 = nullptr)
+{
+	hipStream_t st = g->stream;
+	const size_t n = (size_t)g->N;
+	auto launch = [&](const double *a, const double *b, size_t ld, const GrmCols &c, double *part) {
+		if (b) hipLaunchKernelGGL((dot_partial_multi_kernel<true>), dim3(GRM_RED_BLOCKS, c.n), dim3(256), 0, st, a, b, ld, c, n, part);
+		else hipLaunchKernelGGL((dot_partial_multi_kernel<false>), dim3(GRM_RED_BLOCKS, c.n), dim3(256), 0, st, a, b, ld, c, n, part);
+	};
+	const int n1 = c1.n, n2 = a2 ? c2->n : 0;
+	if (n1 + n2 == 0) return SGX_OK;
+	if (n1) launch(a1, b1, ld1, c1, s->part);
+	if (n2) launch(a2, b2, ld2, *c2, s->part + (size_t)n1 * GRM_RED_BLOCKS);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(s->h_part, s->part, (size_t)(n1 + n2) * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	for (int y = 0; y < n1 + n2; y++) {
+		double v = 0;
+		for (int i = 0; i < GRM_RED_BLOCKS; i++) v += s->h_part[(size_t)y * GRM_RED_BLOCKS + i];   // fixed order
+		if (y < n1) out1[y] = v; else out2[y - n1] = v;
+	}
+	return SGX_OK;
+}
+
+template <int NBFV>
+static void grm_mfma_launch(sgx_grm *g, const uint8_t *packed, size_t bpv, int rows, const uint8_t *Fl, int ntile, int *acc)
+{
+	MfTab tb{};
+	tb.Fl = Fl; tb.ntile = ntile;
+	int tps = 0;
+	const dim3 grid = grm_mfma_grid(g, (size_t)rows, ntile, &tps);
+	const size_t lds = (size_t)2 * 16 * (16 * NBFV) * 16;
+	hipLaunchKernelGGL((score_mfma_kernel<NBFV, false, true>), grid, dim3(WAVE * MF_WAVES), lds, g->stream, packed, bpv, rows, tb, tps, acc, 32 * NBFV);
+}
+
+static void grm_mfma_dispatch(sgx_grm *g, int nbfv, const uint8_t *packed, size_t bpv, int rows, const uint8_t *Fl, int ntile, int *acc)
+{
+	switch (nbfv) {
+	case 1: grm_mfma_launch<1>(g, packed, bpv, rows, Fl, ntile, acc); break;
+	case 2: grm_mfma_launch<2>(g, packed, bpv, rows, Fl, ntile, acc); break;
+	default: grm_mfma_launch<GRM_MAXF>(g, packed, bpv, rows, Fl, ntile, acc); break;
+	}
+}
+
+// Out[:, c] = G'(G B[:, c])/M for c in cols (columns at base + c * ld), device vectors; each column
+// bit-identical to grm_matvec_dev on it
+static int grm_matvec_multi_dev(sgx_grm *g, GrmMulti *s, const double *B, size_t ldb, const GrmCols &cols,
+	double *Out, size_t ldo)
+{
+	hipStream_t st = g->stream;
+	const size_t N = (size_t)g->N, M = g->M;
+	const dim3 bl(256);
+	double sum_b[GRM_MAX_RHS];
+	int rc = grm_sum_multi(g, s, B, nullptr, ldb, cols, sum_b);
+	if (rc) return rc;
+	for (int g0 = 0; g0 < cols.n; g0 += GRM_GROUP) {
+		GrmCols gc{};
+		gc.n = std::min(GRM_GROUP, cols.n - g0);
+		GrmScal sb{};
+		for (int y = 0; y < gc.n; y++) { gc.c[y] = cols.c[g0 + y]; sb.v[y] = sum_b[g0 + y]; }
+		// ---- pass 1: per marker, over samples; column y in fragment y / 2, limbs 7 (y % 2) ..
+		const int nb1 = (gc.n + 1) / 2;
+		HIPCHK(hipMemsetAsync(s->maxb, 0, (size_t)gc.n * 3 * sizeof(unsigned long long), st));
+		hipLaunchKernelGGL(absmax_multi_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, B, ldb, gc, N, 0, s->maxb);
+		HIPCHK(hipMemsetAsync(s->FlN, 0, (size_t)g->tbN.ntile * 16 * (16 * nb1) * 16, st));
+		hipLaunchKernelGGL(limbs_multi_kernel, dim3(512, gc.n), bl, 0, st, B, ldb, gc, N, (size_t)g->tbN.ntile * 256,
+			16 * nb1, 2, 0, s->maxb, 0, s->FlN);
+		HIPCHK(hipMemsetAsync(s->accV, 0, M * 32 * nb1 * sizeof(int), st));
+		grm_mfma_dispatch(g, nb1, g->G, g->bpvN, (int)M, s->FlN, g->tbN.ntile, s->accV);
+		hipLaunchKernelGGL(grm_dot_epilogue_multi, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, s->accV, s->maxb, sb,
+			g->af, g->inv, g->l0, s->xv, s->gv, s->part);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(s->h_part, s->part, (size_t)gc.n * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+		GrmScal C0{};
+		for (int y = 0; y < gc.n; y++) {
+			double c0 = 0;
+			for (int i = 0; i < GRM_RED_BLOCKS; i++) c0 += s->h_part[(size_t)y * GRM_RED_BLOCKS + i];
+			C0.v[y] = c0;
+		}
+		// ---- pass 2: per sample, over markers; column y of a sub-group in fragment y (x limbs 0.., gam limbs 7..)
+		GrmCols all{};
+		all.n = gc.n;
+		for (int y = 0; y < gc.n; y++) all.c[y] = y;
+		hipLaunchKernelGGL(absmax_multi_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, s->xv, M, all, M, 1, s->maxb);
+		hipLaunchKernelGGL(absmax_multi_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, s->gv, M, all, M, 2, s->maxb);
+		for (int s0 = 0; s0 < gc.n; s0 += GRM_GROUP2) {
+			GrmCols sc{}, oc{};
+			sc.n = oc.n = std::min(GRM_GROUP2, gc.n - s0);
+			GrmScal c0s{};
+			for (int y = 0; y < sc.n; y++) { sc.c[y] = s0 + y; oc.c[y] = gc.c[s0 + y]; c0s.v[y] = C0.v[s0 + y]; }
+			const int nb2 = sc.n;
+			const unsigned long long *mb = s->maxb + 3 * s0;
+			HIPCHK(hipMemsetAsync(s->FlM, 0, (size_t)g->tbM.ntile * 16 * (16 * nb2) * 16, st));
+			hipLaunchKernelGGL(limbs_multi_kernel, dim3(512, sc.n), bl, 0, st, s->xv, M, sc, M, (size_t)g->tbM.ntile * 256,
+				16 * nb2, 1, 0, mb, 1, s->FlM);
+			hipLaunchKernelGGL(limbs_multi_kernel, dim3(512, sc.n), bl, 0, st, s->gv, M, sc, M, (size_t)g->tbM.ntile * 256,
+				16 * nb2, 1, MF_NLIMB, mb, 2, s->FlM);
+			HIPCHK(hipMemsetAsync(s->accS, 0, N * 32 * nb2 * sizeof(int), st));
+			grm_mfma_dispatch(g, nb2, g->Gt, g->bpvM, g->N, s->FlM, g->tbM.ntile, s->accS);
+			hipLaunchKernelGGL(grm_out_epilogue_multi, dim3((unsigned)((N + 255) / 256), sc.n), bl, 0, st, g->N, M, nb2,
+				s->accS, mb, c0s, Out, ldo, oc);
+			HIPCHK(hipGetLastError());
+		}
+	}
+	return SGX_OK;
+}
+
+static int grm_multi_args(const char *fn, sgx_grm *g, const void *B, size_t ldb, int k, const void *Out)
+{
+	if (!g || !B || !Out) return fail(SGX_EINVAL, "%s: NULL argument", fn);
+	if (k < 1 || k > SGX_GRM_MAX_RHS) return fail(SGX_EINVAL, "%s: k=%d outside 1..%d", fn, k, SGX_GRM_MAX_RHS);
+	if (ldb < (size_t)g->N) return fail(SGX_EINVAL, "%s: ldb=%zu < N=%d", fn, ldb, g->N);
+	return SGX_OK;
+}
+
+static GrmCols grm_cols_iota(int k)
+{
+	GrmCols c{};
+	c.n = k;
+	for (int j = 0; j < k; j++) c.c[j] = j;
+	return c;
+}
+
+extern "C" int sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size_t ldb, int k, double *Out_dev)
+{
+	int rc = grm_multi_args("sgx_grm_crossprod_multi_dev", g, B_dev, ldb, k, Out_dev);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(g->device));
+	GrmMulti *s = nullptr;
+	if ((rc = grm_multi_scratch(g, k, false, &s))) return rc;
+	return grm_matvec_multi_dev(g, s, B_dev, ldb, grm_cols_iota(k), Out_dev, ldb);
+}
+
+extern "C" int sgx_grm_crossprod_multi(sgx_grm *g, const double *B, size_t ldb, int k, double *Out)
+{
+	int rc = grm_multi_args("sgx_grm_crossprod_multi", g, B, ldb, k, Out);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(g->device));
+	GrmMulti *s = nullptr;
+	if ((rc = grm_multi_scratch(g, k, true, &s))) return rc;
+	const size_t N = (size_t)g->N, nb = N * sizeof(double);
+	HIPCHK(hipMemcpy2DAsync(s->B, nb, B, ldb * sizeof(double), nb, (size_t)k, hipMemcpyHostToDevice, g->stream));
+	if ((rc = grm_matvec_multi_dev(g, s, s->B, N, grm_cols_iota(k), s->O, N))) return rc;
+	HIPCHK(hipMemcpy2DAsync(Out, ldb * sizeof(double), s->O, nb, nb, (size_t)k, hipMemcpyDeviceToHost, g->stream));
+	HIPCHK(hipStreamSynchronize(g->stream));
+	return SGX_OK;
+}
+
+// PCG_diag_sigma (saige_fitnull.cpp:581-614) on k right-hand sides in lockstep: column j follows exactly
+// the steps of sgx_grm_pcg on B[:, j]; a column stops (and leaves the products) once rr <= tol or
+// maxiter is reached.  Each reduction step is one host sync for all columns.
+extern "C" int sgx_grm_pcg_multi(sgx_grm *g, const double *w, const double *tau, const double *B, size_t ldb, int k,
+	int maxiter, double tol, double *X_out, int *iters)
+{
+	if (!w || !tau || !iters) return fail(SGX_EINVAL, "sgx_grm_pcg_multi: NULL argument");
+	int rc = grm_multi_args("sgx_grm_pcg_multi", g, B, ldb, k, X_out);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(g->device));
+	GrmMulti *s = nullptr;
+	if ((rc = grm_multi_scratch(g, k, true, &s))) return rc;
+	hipStream_t st = g->stream;
+	const int n = g->N;
+	const size_t N = (size_t)n, nb = N * sizeof(double);
+	const dim3 bl(256);
+	const unsigned gx = (unsigned)((n + 255) / 256);
+	const double tau0 = tau[0], tau1 = tau[1];
+	HIPCHK(hipMemcpyAsync(g->w, w, nb, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpy2DAsync(s->B, nb, B, ldb * sizeof(double), nb, (size_t)k, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(pcg_minv_kernel, dim3(gx), bl, 0, st, n, g->w, g->diag, tau0, tau1, g->minv);
+	const GrmCols all = grm_cols_iota(k);
+	hipLaunchKernelGGL(pcg_init_multi_kernel, dim3(gx, k), bl, 0, st, n, s->B, N, g->minv, s->R, s->Z, s->P, s->X, all);
+	double rr[GRM_MAX_RHS], rz[GRM_MAX_RHS];
+	if ((rc = grm_sum_multi(g, s, s->R, s->R, N, all, rr, s->R, s->Z, N, &all, rz))) return rc;
+	for (int j = 0; j < k; j++) iters[j] = 0;
+	for (;;) {
+		GrmCols act{};
+		for (int j = 0; j < k; j++)
+			if (iters[j] < maxiter && rr[j] > tol) act.c[act.n++] = j;
+		if (act.n == 0) break;
+		for (int y = 0; y < act.n; y++) iters[act.c[y]]++;
+		const double *gp = nullptr;
+		if (tau1 != 0) {                       // get_crossprod :569-575
+			if ((rc = grm_matvec_multi_dev(g, s, s->P, N, act, s->GP, N))) return rc;
+			gp = s->GP;
+		}
+		hipLaunchKernelGGL(pcg_ap_multi_kernel, dim3(gx, act.n), bl, 0, st, n, s->P, g->w, gp, tau0, tau1, s->AP, act);
+		double pAp[GRM_MAX_RHS], rz1[GRM_MAX_RHS], rrn[GRM_MAX_RHS];
+		if ((rc = grm_sum_multi(g, s, s->P, s->AP, N, act, pAp))) return rc;
+		GrmScal a{};
+		for (int y = 0; y < act.n; y++) a.v[y] = rz[act.c[y]] / pAp[y];
+		hipLaunchKernelGGL(pcg_update_multi_kernel, dim3(gx, act.n), bl, 0, st, n, a, s->P, s->AP, g->minv, s->X, s->R, s->Z, act);
+		if ((rc = grm_sum_multi(g, s, s->Z, s->R, N, act, rz1, s->R, s->R, N, &act, rrn))) return rc;
+		GrmScal bet{};
+		for (int y = 0; y < act.n; y++) bet.v[y] = rz1[y] / rz[act.c[y]];
+		hipLaunchKernelGGL(pcg_dir_multi_kernel, dim3(gx, act.n), bl, 0, st, n, bet, s->Z, s->P, act);
+		for (int y = 0; y < act.n; y++) { rz[act.c[y]] = rz1[y]; rr[act.c[y]] = rrn[y]; }
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpy2DAsync(X_out, ldb * sizeof(double), s->X, nb, nb, (size_t)k, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
 	return SGX_OK;
 }

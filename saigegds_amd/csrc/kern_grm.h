@@ -261,3 +261,174 @@ __global__ void pcg_dir_kernel(int n, double bet, const double *z, double *p)
 	if (i >= n) return;
 	p[i] = z[i] + bet * p[i];
 }
+
+// ===========================================================================
+// Several right-hand sides at once (sgx_grm_*_multi, host_grm.h).  Each kernel below restates one
+// kernel above for a set of columns: blockIdx.y picks the column, the grid-stride partition over
+// blockIdx.x and every expression are those of the single-vector kernel, so a column's result is
+// bit-identical to the single call on it.  Column c of a set lives at base + c * ld.
+
+#define GRM_MAX_RHS 64        /* SGX_GRM_MAX_RHS                                     */
+#define GRM_MAXF 3            /* value fragments of a batched contraction launch (4 spill: DESIGN.md) */
+#define GRM_GROUP (2 * GRM_MAXF)   /* columns per pass-1 launch: two per 16-column fragment         */
+#define GRM_GROUP2 GRM_MAXF        /* columns per pass-2 launch: one per fragment (x and gam limbs) */
+
+struct GrmCols {              // the columns of a set a launch works on (kernel argument, by value)
+	int n;
+	int c[GRM_MAX_RHS];
+};
+
+struct GrmScal {              // one double per column of a launch (by value)
+	double v[GRM_MAX_RHS];
+};
+
+// dot_partial_kernel per column: out[y * GRM_RED_BLOCKS-sized row + blockIdx.x]
+template <bool WITH_B>
+__global__ void __launch_bounds__(256)
+dot_partial_multi_kernel(const double *__restrict__ A, const double *__restrict__ B, size_t ld, GrmCols cols,
+	size_t n, double *__restrict__ out)
+{
+	__shared__ double sh[4];
+	const size_t c = (size_t)cols.c[blockIdx.y];
+	const double *__restrict__ a = A + c * ld;
+	const double *__restrict__ b = WITH_B ? B + c * ld : nullptr;
+	double s[1] = {0};
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+		s[0] = WITH_B ? fma(a[i], b[i], s[0]) : s[0] + a[i];
+	block_sum<1, 256>(s, sh);
+	if (threadIdx.x == 0) out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
+}
+
+// absmax_kernel per column: out[3 * y + slot]
+__global__ void __launch_bounds__(256)
+absmax_multi_kernel(const double *__restrict__ X, size_t ld, GrmCols cols, size_t n, int slot,
+	unsigned long long *__restrict__ out)
+{
+	const double *__restrict__ x = X + (size_t)cols.c[blockIdx.y] * ld;
+	double m = 0;
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+		const double a = fabs(x[i]);
+		m = (a > m) ? a : m;
+	}
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) { const double t = __shfl_xor(m, o, WAVE); m = (t > m) ? t : m; }
+	if ((threadIdx.x & (WAVE - 1)) == 0) atomicMax(out + 3 * blockIdx.y + slot, (unsigned long long)__double_as_longlong(m));
+}
+
+// limbs_kernel per column y into a tile image of ncol columns: first limb column
+// 16 * (y / per_frag) + 7 * (y % per_frag) + off; the columns nobody writes must be zero beforehand
+__global__ void __launch_bounds__(256)
+limbs_multi_kernel(const double *__restrict__ X, size_t ld, GrmCols cols, size_t n, size_t n_pad, int ncol,
+	int per_frag, int off, const unsigned long long *__restrict__ maxbits, int slot, uint8_t *__restrict__ Fl)
+{
+	const int y = blockIdx.y;
+	const double *__restrict__ x = X + (size_t)cols.c[y] * ld;
+	const int col0 = 16 * (y / per_frag) + MF_NLIMB * (y % per_frag) + off;
+	const int e = limb_scale(maxbits[3 * y + slot]);
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_pad; i += (size_t)gridDim.x * blockDim.x) {
+		long long q = 0;
+		if (i < n) {
+			const double v = x[i];
+			q = isfinite(v) ? __double2ll_rn(ldexp(v, e)) : 0;
+		}
+		uint8_t *base = Fl + ((i >> 4) * ncol + col0) * 16 + mf_pos((int)(i & 15));
+		long long rem = q;
+#pragma unroll
+		for (int l = 0; l < MF_NLIMB; l++) {
+			const long long d = (l < MF_NLIMB - 1) ? (((rem + 128) & 255) - 128) : rem;
+			rem = (rem - d) >> 8;
+			base[l * 16] = (uint8_t)(int8_t)d;
+		}
+	}
+}
+
+// grm_dot_epilogue per column y of a pass-1 launch with nbfv fragments (two columns per fragment);
+// x_v, gam_v -> XV / GV row y (stride M), C0 partials -> c0_partial[y * gridDim.x + blockIdx.x]
+__global__ void __launch_bounds__(256)
+grm_dot_epilogue_multi(size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
+	GrmScal sum_b, const double *__restrict__ af, const double *__restrict__ inv,
+	const double *__restrict__ l0, double *__restrict__ XV, double *__restrict__ GV,
+	double *__restrict__ c0_partial)
+{
+	__shared__ double sh[4];
+	const int y = blockIdx.y;
+	const int stride = 32 * nbfv, col = 16 * (y >> 1) + MF_NLIMB * (y & 1);
+	const int e = limb_scale(maxb[3 * y]);
+	const double sb = sum_b.v[y];
+	double *__restrict__ xv = XV + (size_t)y * M;
+	double *__restrict__ gv = GV + (size_t)y * M;
+	double c0[1] = {0};
+	for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < M; v += (size_t)gridDim.x * blockDim.x) {
+		const int *a = acc + v * stride + col;
+		const HiLo V = mf_limbs(a), T3 = mf_limbs(a + 16 * nbfv);
+		const double t3 = ldexp(hl_to_double(T3), -e);
+		const double vw = ldexp(hl_to_double(hl_axpy(-3, T3, V)), -e);
+		const double dot = l0[v] * (sb - t3) + inv[v] * vw;
+		const double x = dot * inv[v];
+		xv[v] = x;
+		gv[v] = (3 - 2 * af[v]) * x;
+		c0[0] = fma(dot, l0[v], c0[0]);
+	}
+	block_sum<1, 256>(c0, sh);
+	if (threadIdx.x == 0) c0_partial[(size_t)y * gridDim.x + blockIdx.x] = c0[0];
+}
+
+// grm_out_epilogue per column y of a pass-2 launch with nbfv fragments (one column per fragment)
+__global__ void __launch_bounds__(256)
+grm_out_epilogue_multi(int N, size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
+	GrmScal C0, double *__restrict__ Out, size_t ldo, GrmCols cols)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	const int y = blockIdx.y;
+	if (i >= N) return;
+	const int ex = limb_scale(maxb[3 * y + 1]), eg = limb_scale(maxb[3 * y + 2]);
+	const int *a = acc + (size_t)i * (32 * nbfv) + 16 * y;
+	const double X = ldexp(hl_to_double(mf_limbs(a)), -ex);
+	const double G = ldexp(hl_to_double(mf_limbs(a + 16 * nbfv + MF_NLIMB)), -eg);
+	Out[(size_t)cols.c[y] * ldo + i] = (C0.v[y] + X - G) / (double)M;
+}
+
+// ---- PCG_diag_sigma vector kernels per column (blockIdx.y); w and minv are shared
+// r = b, z = minv*r, p = z, x = 0
+__global__ void pcg_init_multi_kernel(int n, const double *B, size_t ldb, const double *minv,
+	double *R, double *Z, double *P, double *X, GrmCols cols)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const size_t c = (size_t)cols.c[blockIdx.y], o = c * n + i;
+	const double ri = B[c * ldb + i];
+	R[o] = ri; Z[o] = minv[i] * ri; P[o] = Z[o]; X[o] = 0;
+}
+
+// Ap = tau0 * p / w + tau1 * gp; GP may be NULL when tau1 == 0
+__global__ void pcg_ap_multi_kernel(int n, const double *P, const double *w, const double *GP, double tau0, double tau1,
+	double *AP, GrmCols cols)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const size_t o = (size_t)cols.c[blockIdx.y] * n + i;
+	const double base = tau0 * (P[o] * (1 / w[i]));
+	AP[o] = GP ? base + tau1 * GP[o] : base;
+}
+
+// x += a p; r -= a Ap; z = minv r   (a per column)
+__global__ void pcg_update_multi_kernel(int n, GrmScal a, const double *P, const double *AP, const double *minv,
+	double *X, double *R, double *Z, GrmCols cols)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const size_t o = (size_t)cols.c[blockIdx.y] * n + i;
+	const double ai = a.v[blockIdx.y];
+	X[o] += ai * P[o];
+	const double ri = R[o] - ai * AP[o];
+	R[o] = ri; Z[o] = minv[i] * ri;
+}
+
+// p = z + bet p   (bet per column)
+__global__ void pcg_dir_multi_kernel(int n, GrmScal bet, const double *Z, double *P, GrmCols cols)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const size_t o = (size_t)cols.c[blockIdx.y] * n + i;
+	P[o] = Z[o] + bet.v[blockIdx.y] * P[o];
+}

@@ -182,20 +182,41 @@ class _Param:
 
 
 class _Fitter:
-    def __init__(self, op, X: np.ndarray, y: np.ndarray, fit0: GlmFit, param: _Param, rng: RRandom):
+    """``batched``: the solves that share (w, tau) -- Y and the columns of X, the trace vectors -- go to
+    the operator's ``pcg_many`` / ``crossprod_many`` in one call (each column bit-identical to the
+    single solve); an operator without them is called column by column."""
+
+    def __init__(self, op, X: np.ndarray, y: np.ndarray, fit0: GlmFit, param: _Param, rng: RRandom,
+                 batched: bool = False):
         self.op, self.X, self.y, self.fit0, self.p, self.rng = op, X, y, fit0, param, rng
         self.fam = fit0.family
         self.offset = np.zeros_like(y) if fit0.offset is None else fit0.offset
+        self.batched = batched
 
     def pcg(self, w, tau, b):
         x, _ = self.op.pcg(w, tau, b, self.p.maxiterPCG, self.p.tolPCG)
         return x
 
+    def pcg_many(self, w, tau, B):
+        """Solves of the rows of B ([k, N]) -> [k, N]."""
+        if hasattr(self.op, "pcg_many"):
+            return self.op.pcg_many(w, tau, B, self.p.maxiterPCG, self.p.tolPCG)[0]
+        return np.stack([self.pcg(w, tau, np.ascontiguousarray(b)) for b in B])
+
+    def crossprod_many(self, B):
+        if hasattr(self.op, "crossprod_many"):
+            return self.op.crossprod_many(B)
+        return np.stack([self.op.crossprod(np.ascontiguousarray(b)) for b in B])
+
     # get_coeff_w (:739-758)
     def get_coeff_w(self, Y, w, tau):
         X = self.X
-        Sigma_iY = self.pcg(w, tau, Y)
-        Sigma_iX = np.column_stack([self.pcg(w, tau, np.ascontiguousarray(X[:, i])) for i in range(X.shape[1])])
+        if self.batched:
+            S = self.pcg_many(w, tau, np.vstack([Y[None, :], X.T]))
+            Sigma_iY, Sigma_iX = S[0], np.ascontiguousarray(S[1:].T)
+        else:
+            Sigma_iY = self.pcg(w, tau, Y)
+            Sigma_iX = np.column_stack([self.pcg(w, tau, np.ascontiguousarray(X[:, i])) for i in range(X.shape[1])])
         cov = _mat_inv(X.T @ Sigma_iX)
         alpha = cov @ (Sigma_iX.T @ Y)
         eta = Y - tau[0] * (Sigma_iY - Sigma_iX @ alpha) / w
@@ -229,13 +250,23 @@ class _Fitter:
         nrun_start, nrun_end = 0, p.nrun
         buf, buf0 = np.zeros(p.nrun), np.zeros(p.nrun)
         while True:
-            for i in range(nrun_start, nrun_end):
-                u = 2 * self.rng.rbinom1_half(n) - 1
-                Sigma_iu = self.pcg(w, tau, u)
-                Pu = Sigma_iu - Sigma_iX @ (cov @ (Sigma_iX.T @ u))
-                Au = self.op.crossprod(u)
-                buf[i] = float(Au @ Pu)
-                buf0[i] = float(u @ Pu)
+            if self.batched:
+                # the vectors in the reference's draw order, then all solves and products at once
+                U = np.stack([2 * self.rng.rbinom1_half(n) - 1 for _ in range(nrun_start, nrun_end)])
+                SU, AU = self.pcg_many(w, tau, U), self.crossprod_many(U)
+                for i in range(nrun_start, nrun_end):
+                    u, Sigma_iu, Au = U[i - nrun_start], SU[i - nrun_start], AU[i - nrun_start]
+                    Pu = Sigma_iu - Sigma_iX @ (cov @ (Sigma_iX.T @ u))
+                    buf[i] = float(Au @ Pu)
+                    buf0[i] = float(u @ Pu)
+            else:
+                for i in range(nrun_start, nrun_end):
+                    u = 2 * self.rng.rbinom1_half(n) - 1
+                    Sigma_iu = self.pcg(w, tau, u)
+                    Pu = Sigma_iu - Sigma_iX @ (cov @ (Sigma_iX.T @ u))
+                    Au = self.op.crossprod(u)
+                    buf[i] = float(Au @ Pu)
+                    buf0[i] = float(u @ Pu)
             cv = _calc_cv(buf)
             cv0 = _calc_cv(buf0) if quant else 0.0
             if cv > p.traceCVcutoff or cv0 > p.traceCVcutoff:
@@ -312,7 +343,8 @@ class _Fitter:
         return tau
 
     # saige_fit_AI_PCG_binary (:949-1099) / _quant (:1103-1248)
-    def fit(self, tau_in, quant: bool):
+    def fit(self, tau_in, quant: bool, no_iteration: bool = False):
+        """``no_iteration``: the coefficients at the given tau only (:1004-1014)."""
         p, fit0, y = self.p, self.fit0, self.y
         tol, n = p.tol, len(y)
         tol_inv_2 = 1 / (tol * tol)
@@ -322,10 +354,13 @@ class _Fitter:
         alpha = alpha0.copy()
         tau = np.asarray(tau_in, dtype=np.float64).copy()
         tau0 = tau.copy()
-        if p.verbose:
+        if p.verbose and not no_iteration:
             print("Initial variance component estimates, tau:")
             print(f"    Sigma_E: {tau[0]:g}, Sigma_G: {tau[1]:g}")
         c = self.get_coeff(tau, alpha0, eta0)
+        if no_iteration:
+            return dict(coefficients=c["alpha"], tau=tau, linear_predictors=c["eta"], fitted_values=c["mu"],
+                        residuals=y - c["mu"], cov=c["cov"], converged=True)
         if quant:
             YPAPY, trace, _ = self.get_AI_score_q(c["Y"], c["W"], tau, c["Sigma_iY"], c["Sigma_iX"], c["cov"])
             tau[0] = max(0.0, tau0[0] + tau0[0] * tau0[0] * (YPAPY[1] - trace[0]) / n)
@@ -446,40 +481,12 @@ class FittedNullModel(NullModel):
     res_noK: Optional[np.ndarray] = None
 
 
-def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: str = "binary",
-                       sample_col: str = "sample.id", maf: float = 0.005, missing_rate: float = 0.01,
-                       max_num_snp: int = 1000000, variant_id: Optional[Sequence[int]] = None,
-                       inv_norm: bool = True, X_transform: bool = True, tol: float = 0.02, maxiter: int = 20,
-                       nrun: int = 30, tolPCG: float = 1e-5, maxiterPCG: int = 500, num_marker: int = 30,
-                       tau_init=(0, 0), traceCVcutoff: float = 0.0025, ratioCVcutoff: float = 0.001,
-                       geno_sparse: bool = True, num_thread: int = 1, model_savefn: str = "", seed: int = 200,
-                       fork_loading: bool = False, verbose: bool = True, operator_factory=None) -> FittedNullModel:
-    """Fit the SAIGE null model ``formula + var(GRM)`` on MI355X.
-
-    ``data``: mapping column -> sequence (a pandas DataFrame works);
-    ``gdsfile``: SeqArray GDS path / ``GdsFile`` / ``GenotypeSource``.
-    ``operator_factory(packed, n_samp)`` builds the GRM operator; the default is
-    the GPU one (``GrmOperator``) -- tests inject the CPU oracle to exercise
-    this host logic without a GPU.  ``geno_sparse``, ``num_thread`` and
-    ``fork_loading`` only select storage/threads in the reference and are
-    accepted for signature compatibility.
-    """
-    if trait_type not in ("binary", "quantitative"):
-        raise ValueError("'arg' should be one of \"binary\", \"quantitative\"")
-    phenovar, covars = _parse_formula(formula)
-    cols = {k: np.asarray(v) for k, v in dict(data).items()}
-    if phenovar not in cols:
-        raise ValueError(f"There is no '{phenovar}' in the input data frame.")
-    if sample_col in [phenovar] + covars:
-        raise ValueError(f"'{sample_col}' should not be in the formula.")
-    if sample_col not in cols:
-        raise ValueError(f"'{sample_col}' should be one of the columns in 'data'.")
-    sids = [str(s) for s in cols[sample_col]]
-    if len(set(sids)) != len(sids):
-        raise ValueError(f"'{sample_col}' in data should be unique.")
-    if verbose:
-        print("SAIGE association analysis:")
-
+def _load_grm_markers(phenovar: str, covars: List[str], cols: Dict[str, np.ndarray], sids: List[str], gdsfile, maf: float,
+                      missing_rate: float, max_num_snp: int, variant_id, seed: int, verbose: bool,
+                      use_gpu_counts: bool) -> Dict[str, Any]:
+    """Samples and GRM markers of a null-model fit (R/saige_main.r:299-333, R/saige_interaction.r:160-200):
+    complete cases in the GDS sample order, the maf / missing-rate filter (or ``variant_id``), then
+    ``max_num_snp`` markers drawn by R's ``sample()`` after ``set.seed(seed)``."""
     # complete cases, then the GDS sample order (R/saige_main.r:299-311)
     num = np.column_stack([np.asarray(cols[c], dtype=np.float64) for c in [phenovar] + covars])
     keep = ~np.isnan(num).any(axis=1)
@@ -506,7 +513,7 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
     packed_all = np.asarray(packed_all)
     want = None if variant_id is None else set(int(v) for v in variant_id)
     gpu_counts = None
-    if want is None and n_samp == n_all and operator_factory is None:
+    if want is None and n_samp == n_all and use_gpu_counts:
         # all samples selected: the per-variant counts of the filter come from the GPU
         from ._lib import geno_stats_2bit
         gpu_counts = geno_stats_2bit(packed_all, n_all)
@@ -557,6 +564,48 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
         rng.set_seed(seed)
         pick = np.sort(rng.sample_int(idx.size)[:max_num_snp] - 1)     # sample(which(v), max.num.snp)
         idx, packed = idx[pick], np.ascontiguousarray(packed[pick])
+    return dict(y=yv, Xc=Xc, rows=rows, sample_id=sample_ids, n_samp=n_samp, packed=packed, idx=idx,
+                var_ids=var_ids, n_before=n_before, rng=rng, src=src)
+
+
+def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: str = "binary",
+                       sample_col: str = "sample.id", maf: float = 0.005, missing_rate: float = 0.01,
+                       max_num_snp: int = 1000000, variant_id: Optional[Sequence[int]] = None,
+                       inv_norm: bool = True, X_transform: bool = True, tol: float = 0.02, maxiter: int = 20,
+                       nrun: int = 30, tolPCG: float = 1e-5, maxiterPCG: int = 500, num_marker: int = 30,
+                       tau_init=(0, 0), traceCVcutoff: float = 0.0025, ratioCVcutoff: float = 0.001,
+                       geno_sparse: bool = True, num_thread: int = 1, model_savefn: str = "", seed: int = 200,
+                       fork_loading: bool = False, verbose: bool = True, operator_factory=None) -> FittedNullModel:
+    """Fit the SAIGE null model ``formula + var(GRM)`` on MI355X.
+
+    ``data``: mapping column -> sequence (a pandas DataFrame works);
+    ``gdsfile``: SeqArray GDS path / ``GdsFile`` / ``GenotypeSource``.
+    ``operator_factory(packed, n_samp)`` builds the GRM operator; the default is
+    the GPU one (``GrmOperator``) -- tests inject the CPU oracle to exercise
+    this host logic without a GPU.  ``geno_sparse``, ``num_thread`` and
+    ``fork_loading`` only select storage/threads in the reference and are
+    accepted for signature compatibility.
+    """
+    if trait_type not in ("binary", "quantitative"):
+        raise ValueError("'arg' should be one of \"binary\", \"quantitative\"")
+    phenovar, covars = _parse_formula(formula)
+    cols = {k: np.asarray(v) for k, v in dict(data).items()}
+    if phenovar not in cols:
+        raise ValueError(f"There is no '{phenovar}' in the input data frame.")
+    if sample_col in [phenovar] + covars:
+        raise ValueError(f"'{sample_col}' should not be in the formula.")
+    if sample_col not in cols:
+        raise ValueError(f"'{sample_col}' should be one of the columns in 'data'.")
+    sids = [str(s) for s in cols[sample_col]]
+    if len(set(sids)) != len(sids):
+        raise ValueError(f"'{sample_col}' in data should be unique.")
+    if verbose:
+        print("SAIGE association analysis:")
+
+    g = _load_grm_markers(phenovar, covars, cols, sids, gdsfile, maf, missing_rate, max_num_snp, variant_id,
+                          seed, verbose, use_gpu_counts=operator_factory is None)
+    yv, Xc, sample_ids, n_samp = g["y"], g["Xc"], g["sample_id"], g["n_samp"]
+    packed, idx, var_ids, n_before, rng = g["packed"], g["idx"], g["var_ids"], g["n_before"], g["rng"]
     n_var = idx.size
     if verbose:
         print(f"Fit the null model: {formula} + var(GRM)")

@@ -58,7 +58,8 @@ def _pairlist(items) -> bytes:
     return out + _i(254)
 
 
-def _data_frame(cols: Dict[str, Any]) -> bytes:
+def _data_frame(cols: Dict[str, Any], extra_attrs=()) -> bytes:
+    """``extra_attrs``: (name, serialised value) pairs after the data frame's own attributes."""
     names = list(cols)
     n = len(next(iter(cols.values()))) if cols else 0
     body = b"".join(_vector(cols[k]) for k in names)
@@ -66,6 +67,7 @@ def _data_frame(cols: Dict[str, Any]) -> bytes:
         ("names", _strsxp(names)),
         ("class", _strsxp(["data.frame"])),
         ("row.names", _i(13) + _i(2) + _i(NA_INT) + _i(-n)),
+        *extra_attrs,
     ])
     return _i(19 | 0x100 | 0x200) + _i(len(names)) + body + attr
 
