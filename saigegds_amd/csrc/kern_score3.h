@@ -91,6 +91,70 @@ __device__ __forceinline__ void s3_unpack3_op(uint32_t w, uint32_t &w4, uint32_t
 	else if constexpr (OP == 14) mis[3] = (int)(w4 & t4 & 0x04040404u);
 }
 
+// The three-plane consumer with ONE set of plane registers (4 B fragments: 3 value + bit-1, NAF row pieces).
+// A dword step's 7 NAF MFMAs, in the order
+//   m <  NAF        chunk {3, 0}: bit-1 planes x fragment 3, piece f = m
+//   m <  3 NAF                    value / missing planes of piece (m - NAF) / 2 x fragment 0
+//   m <  7 NAF      chunk {1, 2}: piece-major, piece (m - 3 NAF) / 4: value x 1, missing x 1, value x 2, missing x 2
+// frees the bit-1 planes of piece f behind MFMA f and its value / missing planes behind MFMA 3 NAF + 4 f + 2 / + 3.
+// The 15 NAF operations that make a dword's planes run as one stream per dword -- per piece the three shifts and the
+// four bit-1 operations, then per piece the four value and four missing-plane operations -- and the streams of dwords
+// 1 .. 3 of a tile are dealt out evenly over the tile's 4 x 7 NAF MFMA slots, DL slots late and never in front of the
+// MFMA that frees their register (slot g = u 7 NAF + m: behind MFMA m of dword step u).  ok(): every operation is
+// in place before the MFMA that reads what it makes.
+template <int NAF>
+struct s3_one {
+	static constexpr int NM = 7 * NAF, NOPT = S3_UNPACK3_OPS * NAF, DL = 2, NK = 3 * NOPT;
+	static constexpr int piece_of(int m) { return m < NAF ? m : m < 3 * NAF ? (m - NAF) / 2 : (m - 3 * NAF) / 4; }
+	static constexpr int frag_of(int m) { return m < NAF ? 3 : m < 3 * NAF ? 0 : 1 + ((m - 3 * NAF) & 3) / 2; }
+	static constexpr int plane_of(int m) { return m < NAF ? 2 : m < 3 * NAF ? (m - NAF) & 1 : (m - 3 * NAF) & 1; }
+	static constexpr int chunk_of(int m) { return m < 3 * NAF ? 0 : 1; }
+	static constexpr int slot_of(int m) { return m < NAF ? 0 : m < 3 * NAF ? 1 : ((m - 3 * NAF) & 3) / 2; }   // place in its chunk
+	static constexpr int frag(int ch, int j) { return ch == 0 ? (j == 0 ? 3 : 0) : 1 + j; }
+	static constexpr bool enters(int m) { return m == 0 || m == 3 * NAF; }
+	// operation i of a dword's stream: its row piece and its s3_unpack3_op
+	static constexpr int piece(int i) { return i < 7 * NAF ? i / 7 : (i - 7 * NAF) / 8; }
+	static constexpr int op(int i)
+	{
+		const int head[7] = {0, 9, 10, 5, 6, 7, 8}, tail[8] = {1, 2, 3, 4, 11, 12, 13, 14};
+		return i < 7 * NAF ? head[i % 7] : tail[(i - 7 * NAF) % 8];
+	}
+	// first slot that may carry operation i of dword d (behind the MFMA of step d - 1 that last reads its register),
+	// and the slot of the MFMA of step d that reads it (operations in slots below it only)
+	static constexpr int earliest(int d, int i)
+	{
+		const int base = NM * (d - 1);
+		if (i < 7 * NAF) return base + (i % 7 >= 3 ? i / 7 : 0);
+		const int q = i - 7 * NAF;
+		return base + 3 * NAF + 4 * (q / 8) + (q % 8 < 4 ? 2 : 3);
+	}
+	static constexpr int deadline(int d, int i)
+	{
+		const int base = NM * d;
+		if (i < 7 * NAF) return i % 7 >= 3 ? base + i / 7 : 1 << 30;     // (the shifts: only the stream's order)
+		const int q = i - 7 * NAF;
+		return base + NAF + 2 * (q / 8) + (q % 8 < 4 ? 0 : 1);
+	}
+	// slot of operation k of the tile (dword 1 + k / NOPT): the even share, not before its register is free
+	static constexpr int slot(int k)
+	{
+		int s = 0;
+		for (int j = 0; j <= k; j++) {
+			const int d = 1 + j / NOPT, i = j % NOPT, t = NM * (d - 1) + i * NM / NOPT + DL, e = earliest(d, i);
+			s = s > t ? s : t;
+			s = s > e ? s : e;
+		}
+		return s;
+	}
+	static constexpr int first(int g) { int k = 0; while (k < NK && slot(k) < g) k++; return k; }
+	static constexpr bool ok()
+	{
+		for (int k = 0; k < NK; k++)
+			if (slot(k) >= deadline(1 + k / NOPT, k % NOPT) || slot(k) >= 4 * NM) return false;
+		return true;
+	}
+};
+
 // NBF: B fragments per tile (value fragments + the bit-1 fragment, the LAST one).  NAF: A fragments (16
 // variants) per consumer wave.  NC consumer waves + NLA row-loader waves + NLB B-loader waves per workgroup
 // (one workgroup per CU).
@@ -474,6 +538,10 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 	// ---- the three-plane consumer (MISS): per dword step the MFMAs run (fragment, plane)-major -- B fragment b feeds the
 	// NAF value MFMAs, then the NAF missing-plane MFMAs, the bit-1 fragment its NAF -- and the 15 NAF operations that
 	// make the NEXT dword's planes (a second set of plane registers) are dealt out evenly behind them.
+	// ONE (4 B fragments, NAF >= 3: 4 NAF x 7 accumulators leave no room for a second set of planes in the 168
+	// registers of three waves per SIMD): ONE set of planes, B fragments in chunks {3, 0}, {1, 2}, and the MFMAs of
+	// a dword step in the order of s3_one (bit-1 planes first, the last chunk piece-major), so that every plane of a
+	// row piece is free early and its next dword's operations are dealt out evenly behind the MFMAs (s3_one::slot).
 	auto consume3 = [&]() {
 		static_assert(!MISS || NCB == 1, "the three-plane form has one column group");
 		constexpr int NBUF = NBUF_;                           // chunk buffers: the B reads run NBUF - 1 chunks ahead of their MFMAs
@@ -481,7 +549,11 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 		constexpr int NVF = 2 * NBV + 1;                      // (fragment, plane) pairs of a dword step
 		constexpr int NM = NAF * NVF;                         // MFMAs per dword step
 		constexpr int NOPT = S3_UNPACK3_OPS * NAF;            // operations per dword
-		constexpr int BCH = NBF <= 4 ? NBF : 2, NCH = (NBF + BCH - 1) / BCH;
+		constexpr bool ONE = NBF == 4 && NAF >= 3;
+		using S1 = s3_one<NAF>;
+		static_assert(!ONE || S1::ok(), "an unpack operation of the one-set schedule lands behind the MFMA that needs it");
+		constexpr int BCH = ONE ? 2 : NBF <= 4 ? NBF : 2, NCH = (NBF + BCH - 1) / BCH;
+		constexpr int NPS = ONE ? 1 : 2;                      // sets of plane registers
 		const uint32_t bt_lds = smem_lds + (4 * kg * NCOL + r) * 16;
 		s3_v4i acc[NAF][NBF], accm[NAF][NBV > 0 ? NBV : 1];
 #pragma unroll
@@ -506,7 +578,8 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 				constexpr int ci = decltype(CI)::value, u = ci / NCH, b0 = (ci % NCH) * BCH;
 				s3_static_for<0, BCH>([&](auto J) {
 					constexpr int j = decltype(J)::value;
-					if constexpr (b0 + j < NBF) S3_DS_READ(bf[ci % NBUF][j], b_addr, u * NCOL * 16 + (b0 + j) * 256);
+					constexpr int b = ONE ? S1::frag(ci % NCH, j) : b0 + j;
+					if constexpr (b0 + j < NBF) S3_DS_READ(bf[ci % NBUF][j], b_addr, u * NCOL * 16 + b * 256);
 				});
 			};
 			constexpr int nread_last = NBF - (NCH - 1) * BCH;
@@ -515,7 +588,7 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 			S3_LGKM_WAIT(nreads(0, NBUF - 1), aw[0]);
 #pragma unroll
 			for (int f = 1; f < NAF; f++) S3_TIE(aw[f]);
-			s3_v4i val[2][NAF], b1[2][NAF], mis[2][NAF];
+			s3_v4i val[NPS][NAF], b1[NPS][NAF], mis[NPS][NAF];
 			uint32_t w4[NAF], tt[NAF], m4[NAF];
 			s3_static_for<0, NOPT>([&](auto O) {
 				constexpr int o = decltype(O)::value, f = o / S3_UNPACK3_OPS, op = o % S3_UNPACK3_OPS;
@@ -523,13 +596,14 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 			});
 			__builtin_amdgcn_sched_barrier(0);
 			s3_static_for<0, 4>([&](auto U) {
-				constexpr int u = decltype(U)::value, vb = u & 1, vn = (u + 1) & 1;
+				constexpr int u = decltype(U)::value, vb = ONE ? 0 : u & 1, vn = ONE ? 0 : (u + 1) & 1;
 				s3_static_for<0, NM>([&](auto MI) {
-					constexpr int m = decltype(MI)::value, vf = m / NAF, f = m % NAF;
-					constexpr int b = vf < 2 * NBV ? vf / 2 : NBV;            // B fragment
-					constexpr int plane = vf < 2 * NBV ? (vf & 1) : 2;        // 0 value, 1 missing, 2 bit-1
-					constexpr int ch = b / BCH, ci = u * NCH + ch, j = b % BCH;
-					if constexpr (f == 0 && plane != 1 && b % BCH == 0) {
+					constexpr int m = decltype(MI)::value, vf = m / NAF;
+					constexpr int f = ONE ? S1::piece_of(m) : m % NAF;                                // row piece
+					constexpr int b = ONE ? S1::frag_of(m) : vf < 2 * NBV ? vf / 2 : NBV;             // B fragment
+					constexpr int plane = ONE ? S1::plane_of(m) : vf < 2 * NBV ? (vf & 1) : 2;        // 0 value, 1 missing, 2 bit-1
+					constexpr int ch = ONE ? S1::chunk_of(m) : b / BCH, ci = u * NCH + ch, j = ONE ? S1::slot_of(m) : b % BCH;
+					if constexpr (ONE ? S1::enters(m) : f == 0 && plane != 1 && b % BCH == 0) {
 						// entering a chunk: start the next one, then wait for this one
 						if constexpr (ci + NBUF - 1 < 4 * NCH) read_chunk(std::integral_constant<int, ci + NBUF - 1>());
 						constexpr int inflight = nreads(ci + 1, ci + NBUF);
@@ -541,7 +615,14 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 					if constexpr (plane == 0) acc[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(val[vb][f], bf[ci % NBUF][j], acc[f][b], 0, 0, 0);
 					else if constexpr (plane == 1) accm[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(mis[vb][f], bf[ci % NBUF][j], accm[f][b], 0, 0, 0);
 					else acc[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(b1[vb][f], bf[ci % NBUF][j], acc[f][b], 0, 0, 0);
-					if constexpr (u < 3) {
+					if constexpr (ONE) {
+						// the operations whose slot is this MFMA (of dwords u + 1 and, late ones, u)
+						constexpr int g = u * NM + m;
+						s3_static_for<S1::first(g), S1::first(g + 1)>([&](auto K) {
+							constexpr int k = decltype(K)::value, d = 1 + k / NOPT, i = k % NOPT, ff = S1::piece(i), op = S1::op(i);
+							s3_unpack3_op<op>((uint32_t)aw[ff][d], w4[ff], tt[ff], m4[ff], val[0][ff], b1[0][ff], mis[0][ff]);
+						});
+					} else if constexpr (u < 3) {
 						s3_static_for<m * NOPT / NM, (m + 1) * NOPT / NM>([&](auto O) {
 							constexpr int o = decltype(O)::value, ff = o / S3_UNPACK3_OPS, op = o % S3_UNPACK3_OPS;
 							s3_unpack3_op<op>((uint32_t)aw[ff][u + 1], w4[ff], tt[ff], m4[ff], val[vn][ff], b1[vn][ff], mis[vn][ff]);
@@ -589,9 +670,12 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 	X(2, 4, 8, 3, 1, 1, 2) X(3, 4, 8, 3, 1, 1, 1) X(4, 4, 8, 3, 1, 1, 1) X(5, 3, 8, 3, 1, 1, 2) X(6, 3, 8, 3, 1, 1, 1) \
 	X(7, 4, 4, 2, 2, 2, 1) X(8, 4, 4, 2, 2, 2, 1) X(9, 4, 4, 2, 2, 1, 1) X(10, 4, 4, 2, 2, 1, 1) X(11, 4, 4, 2, 2, 1, 1) \
 	X(12, 3, 4, 2, 2, 1, 1) X(13, 3, 4, 2, 2, 1, 1) X(14, 2, 4, 2, 2, 2, 1) X(15, 2, 4, 2, 2, 1, 1) X(16, 2, 4, 2, 2, 1, 1)
-// ... and of the three-plane form (MISS: no lists of the missing genotypes; 4 NAF (2 NBF - 1) accumulators per wave)
+// ... and of the three-plane form (MISS: no lists of the missing genotypes; 4 NAF (2 NBF - 1) accumulators per wave).
+// 4 B fragments (K = 3 binary, the headline): NAF = 3 with one set of planes (s3_one, 168 registers, no scratch), one
+// pair of row tiles ahead (2 x 48 KiB) and two B tiles (3 x 16 KiB): each wave's read of a B tile from LDS feeds 48
+// variants instead of 32 (NAF = 2: LDS-bound, tools/README.md)
 #define S3_FOR_EACH_NBF_MISS(X) \
-	X(2, 4, 8, 3, 1, 1, 2) X(3, 3, 8, 3, 1, 1, 2) X(4, 2, 8, 3, 1, 2, 2) X(5, 2, 8, 3, 1, 2, 2) X(6, 3, 4, 2, 2, 2, 1) \
+	X(2, 4, 8, 3, 1, 1, 2) X(3, 3, 8, 3, 1, 1, 2) X(4, 3, 8, 3, 1, 1, 2) X(5, 2, 8, 3, 1, 2, 2) X(6, 3, 4, 2, 2, 2, 1) \
 	X(7, 2, 4, 2, 2, 2, 1) X(8, 2, 4, 2, 2, 2, 1) X(9, 2, 4, 2, 2, 2, 1) X(10, 2, 4, 2, 2, 2, 1) X(11, 1, 4, 2, 2, 2, 1) \
 	X(12, 1, 4, 2, 2, 2, 1) X(13, 1, 4, 2, 2, 2, 1) X(14, 1, 4, 2, 2, 2, 1) X(15, 1, 4, 2, 2, 2, 1) X(16, 1, 4, 2, 2, 2, 1)
 static inline size_t s3_lds_bytes(int NBF, int NAF, int NC, int DA, int DB) { return ((size_t)(DB + 1) * 4 * NBF + (size_t)(DA + 1) * 2 * NC * NAF) * 1024; }

@@ -410,6 +410,15 @@ int main(int argc, char **argv)
 		bad += check<4, 2, 8, 3, 1, 2, 2, 1, 2, 1, true>("three planes, 1 missing code in 65536", 5000, 700, 1, 8, 0, 1);
 		bad += check<4, 2, 8, 3, 1, 2, 2, 1, 2, 1, true>("three planes, no missing code", 3000, 300, 1, 8, 64, 0);
 		bad += check<4, 2, 8, 3, 1, 2, 2, 1, 2, 1, true>("three planes, 5 % missing", 3000, 300, 1, 8, 0, 3277);
+		// the one-set form (NAF = 3, 384-variant tiles): around one tile, leftover tiles cut into pieces, both B rings
+		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, 1 missing code in 65536", 5000, 700, 1, 8, 0, 1);
+		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, no missing code", 3000, 300, 1, 8, 64, 0);
+		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, 5 % missing", 3000, 300, 1, 8, 0, 3277);
+		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, M = 383", 4099, 383, 1, 8);
+		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, M = 384", 4099, 384, 1, 8, 64);
+		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, M = 385", 4099, 385, 1, 8);
+		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, M = 3 tiles + 7, big grid", 9000, 3 * 384 + 7, 1, n_cu);
+		bad += check<4, 3, 8, 3, 1, 1, 1, 1, 2, 1, true>("naf3 d1/1, M = 2 tiles + 1", 7001, 769, 1, 16, 0, 2600);
 		return bad ? 1 : 0;
 	}
 	const int N = argc > 1 ? atoi(argv[1]) : 430000;
@@ -575,6 +584,18 @@ int main(int argc, char **argv)
 			R3M(4, 4, 4, 3, 1, 2, 1, 0, "k3 three planes naf4 4+3+1 d2/1");
 			R3M(4, 2, 8, 2, 2, 2, 1, 0, "k3 three planes naf2 8+2+2 d2/1");
 			R3M(4, 2, 8, 2, 2, 3, 1, 0, "k3 three planes naf2 8+2+2 d3/1");
+			return 0;
+		}
+		if (getenv("SWEEP6")) {
+			// NAF = 3 with one set of planes (s3_one) against the NAF = 2 form it replaced, alternating; the other narrow forms
+			for (int rep = 0; rep < 3; rep++) {
+				R3M(4, 2, 8, 3, 1, 2, 2, 0, "k3 three planes naf2 8+3+1 d2/2");
+				R3M(4, 3, 8, 3, 1, 1, 2, 0, "k3 three planes naf3 one set d1/2");
+				R3M(4, 3, 8, 3, 1, 1, 1, 0, "k3 three planes naf3 one set d1/1");
+			}
+			R3M(4, 3, 8, 2, 2, 1, 2, 0, "k3 three planes naf3 one set 8+2+2");
+			R3M(2, 4, 8, 3, 1, 1, 2, 0, "nbf2 three planes naf4 (table)");
+			R3M(5, 2, 8, 3, 1, 2, 2, 0, "nbf5 three planes naf2 (table)");
 			return 0;
 		}
 #endif
