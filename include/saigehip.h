@@ -229,6 +229,51 @@ int sgx_burden_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_varia
 	size_t n_variants, size_t n_rows, const int64_t *row_ptr, const int32_t *var_idx,
 	const double *lut, double *out8, uint8_t *valid);
 
+/* Aggregate tests on dosage input: the INTSXP / REALSXP branches of ds_mat_mafmac and ds_mat_burden
+ * (src/saige_main.cpp:485-610), which the R drivers reach with .dsnode(gdsfile, dsnode) for imputed
+ * data (R/assoc_aggregate.r:89,351,606).  A batch of dosage rows (u8: 0xFF = missing; i32: INT_MIN =
+ * missing; f64: NaN / Inf = missing; one row of n_samp values per variant) crosses PCIe ONCE and stays
+ * on the device for the three things a driver needs from it:
+ *   sgx_dsblock_create  storage for up to max_variants rows (u8: n_samp bytes a row; i32 and f64:
+ *                       8 n_samp -- i32 rows are kept as doubles, as sgx_scan_i32 converts them)
+ *   sgx_dsblock_load    rows in host memory -> block, in chunks of the host-buffer pipeline; returns per
+ *                       variant n_valid, sum (ds_mat_mafmac's s: exact for u8 / i32, a double sum for
+ *                       f64) and sum_trunc, the `int sum` of ds_mat_burden.  The reference declares that
+ *                       sum `int` in the REALSXP branch too (:589-591), so it truncates after every
+ *                       addition; the device returns the sum of floor(dosage), which is the same number
+ *                       for finite dosages in [0, 2] with a fractional part below 1 - 2^-20.  Agreement
+ *                       with the reference is claimed for dosages in that range only, and for i32 sums
+ *                       (64-bit here) wherever the reference's `int` does not overflow.
+ *   sgx_dsblock_scan    single-variant test of every resident row: the kernels of sgx_scan_u8 / _f64,
+ *                       launched on the chunks sgx_scan_* would cut the same rows into, so rows that take
+ *                       the dosage kernels there give the same results bit for bit.  Hard-call u8 / i32
+ *                       rows are not packed to 2-bit here; they agree with sgx_scan_u8 / _i32 within the
+ *                       scan's tolerance (integer columns exactly).
+ *   sgx_dsblock_burden  n_groups units; group g has the entries [grp_ptr[g], grp_ptr[g+1]) = rows
+ *                       var_idx[e] of the block, in the unit's order; n_cols weight columns per group
+ *                       (1 .. SGX_DS_MAX_COLS; each pass over a group's rows feeds 8 of them).  Burden
+ *                       row g * n_cols + c = sum over the group's entries with finite w[e*n_cols+c] of
+ *                           present ? (flip[e] ? 2 - x : x) * w[e*n_cols+c] : mw[e*n_cols+c]
+ *                       per sample, the product rounded and then added as ds_mat_burden does; the caller
+ *                       forms flip (sum_trunc > n_valid) and mw = m * w, m = sum_trunc / n_valid or
+ *                       2 - that (saigegds_amd/aggregate.py).  Then the single-variant test on every
+ *                       row; out8 / valid: n_groups * n_cols rows.  A row of hard calls equals the row
+ *                       sgx_burden_2bit makes from the packed form of the same data bit for bit.
+ * All four are synchronous; block and handle must be on the same device and have the same n_samp. */
+#define SGX_DS_U8  0
+#define SGX_DS_I32 1
+#define SGX_DS_F64 2
+#define SGX_DS_MAX_COLS 64
+typedef struct sgx_dsblock sgx_dsblock;
+int  sgx_dsblock_create(int32_t n_samp, int dtype, size_t max_variants, int device, sgx_dsblock **out);
+void sgx_dsblock_free(sgx_dsblock *b);
+int  sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosage, size_t n_variants,
+	int32_t *n_valid, double *sum, int64_t *sum_trunc);
+int  sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out8, uint8_t *valid);
+int  sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_groups, const int64_t *grp_ptr,
+	const int32_t *var_idx, const uint8_t *flip, int n_cols, const double *w, const double *mw,
+	double *out8, uint8_t *valid);
+
 /* Host-side decoder of SeqArray's genotype/data node (dBit2 [variant][sample][ploidy]) into the 2-bit dosage
  * rows of sgx_scan_2bit / sgx_block_load: code = number of non-reference alleles, 3 = missing -- SeqArray's
  * "$dosage_alt", what seqApply(.useraw=NA) hands saige_score_test_bin as RAW (R/assoc_single.r:202-221).

@@ -20,9 +20,12 @@ EXPORTS = (
     "sgx_sync", "sgx_get_stats", "sgx_get_stats_total", "sgx_row_stride", "sgx_synth_2bit_dev", "sgx_selftest", "sgx_set_option",
     "sgx_grm_init", "sgx_grm_init_dev", "sgx_grm_crossprod_dev", "sgx_grm_sync", "sgx_grm_free", "sgx_grm_diag", "sgx_grm_crossprod", "sgx_grm_pcg",
     "sgx_grm_crossprod_multi", "sgx_grm_crossprod_multi_dev", "sgx_grm_pcg_multi",
+    "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
+DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
+DS_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float64): 2}   # SGX_DS_U8 / _I32 / _F64
 
 
 class SgxError(RuntimeError):
@@ -134,6 +137,16 @@ def load():
     L.sgx_scan_i32.argtypes = [vp, vp, sz, vp, vp]
     L.sgx_burden_2bit.restype = C.c_int
     L.sgx_burden_2bit.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
+    L.sgx_dsblock_create.restype = C.c_int
+    L.sgx_dsblock_create.argtypes = [C.c_int32, C.c_int, sz, C.c_int, C.POINTER(vp)]
+    L.sgx_dsblock_free.restype = None
+    L.sgx_dsblock_free.argtypes = [vp]
+    L.sgx_dsblock_load.restype = C.c_int
+    L.sgx_dsblock_load.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    L.sgx_dsblock_scan.restype = C.c_int
+    L.sgx_dsblock_scan.argtypes = [vp, vp, vp, vp]
+    L.sgx_dsblock_burden.restype = C.c_int
+    L.sgx_dsblock_burden.argtypes = [vp, vp, sz, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.sgx_decode_dbit2.restype = C.c_int
     L.sgx_decode_dbit2.argtypes = [vp, sz, C.c_int32, sz, vp, C.c_int32, vp, sz, C.c_int]
     L.sgx_geno_stats_2bit.restype = C.c_int
@@ -281,6 +294,10 @@ class Scanner:
                                       out.ctypes.data, valid.ctypes.data))
         return out, valid
 
+    def dosage_block(self, dtype, max_variants: int) -> "DosageBlock":
+        """Device storage for a batch of dosage rows of the aggregate tests (``DosageBlock`` below)."""
+        return DosageBlock(self, dtype, max_variants)
+
     # -- device-resident scans (pointers are raw device addresses) ---------
     def row_stride(self) -> int:
         return int(self._L.sgx_row_stride(self.n))
@@ -365,6 +382,77 @@ class Block:
     def close(self):
         if getattr(self, "_b", None):
             self._L.sgx_block_free(self._b)
+            self._b = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class DosageBlock:
+    """A batch of dosage rows resident on the device (``sgx_dsblock``) for the aggregate tests: loaded once, it
+    serves the per-variant counts, the single-variant test of every row and the burden rows of all units.
+    ``dtype``: uint8 (0xFF = missing), int32 (INT_MIN = missing) or float64 (NaN / Inf = missing)."""
+
+    def __init__(self, sc: Scanner, dtype, max_variants: int):
+        self._L = load()
+        dt = np.dtype(dtype)
+        if dt not in DS_DTYPES:
+            raise TypeError("the dosages should be uint8, int32 or float64")
+        self.dtype, self._sc = dt, sc
+        self.n, self.cap, self.n_variants = sc.n, int(max_variants), 0
+        b = C.c_void_p()
+        check(self._L.sgx_dsblock_create(sc.n, DS_DTYPES[dt], self.cap, int(sc.device), C.byref(b)))
+        self._b = b
+
+    def load(self, dosage: np.ndarray):
+        """Rows [m, N] in host memory -> block; returns (n_valid int32, sum float64, sum_trunc int64) per variant."""
+        dosage = np.ascontiguousarray(dosage, dtype=self.dtype)
+        if dosage.ndim != 2 or dosage.shape[1] != self.n:
+            raise ValueError(f"Invalid length of dosages: {dosage.shape[-1]}.")
+        m = dosage.shape[0]
+        nv, sm, st = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float64), np.empty(m, dtype=np.int64)
+        check(self._L.sgx_dsblock_load(self._sc._h, self._b, dosage.ctypes.data, m, nv.ctypes.data, sm.ctypes.data,
+                                       st.ctypes.data))
+        self.n_variants = m
+        return nv, sm, st
+
+    def scan(self):
+        """Single-variant test of every resident row -> (out [m, 8], valid [m])."""
+        out, valid = self._sc._out(self.n_variants)
+        check(self._L.sgx_dsblock_scan(self._sc._h, self._b, out.ctypes.data, valid.ctypes.data))
+        return out, valid
+
+    def burden(self, grp_ptr, var_idx, flip, w, mw):
+        """Burden rows of the groups (CSR over the block's rows) x the columns of ``w`` / ``mw`` ([entries, n_cols],
+        NaN weight = entry not in that column), then the single-variant test -> (out [groups * n_cols, 8], valid)."""
+        grp_ptr = np.ascontiguousarray(grp_ptr, dtype=np.int64)
+        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        mw = np.ascontiguousarray(mw, dtype=np.float64)
+        ng = grp_ptr.size - 1
+        if w.ndim != 2 or w.shape != mw.shape or w.shape[0] != var_idx.size or flip.shape != var_idx.shape or ng < 0 \
+                or grp_ptr[-1] != var_idx.size:
+            raise ValueError("DosageBlock.burden: inconsistent group / weight shapes")
+        nc = w.shape[1]
+        out, valid = self._sc._out(ng * nc)
+        check(self._L.sgx_dsblock_burden(self._sc._h, self._b, ng, grp_ptr.ctypes.data, var_idx.ctypes.data,
+                                         flip.ctypes.data, nc, w.ctypes.data, mw.ctypes.data, out.ctypes.data,
+                                         valid.ctypes.data))
+        return out, valid
+
+    def close(self):
+        if getattr(self, "_b", None):
+            self._L.sgx_dsblock_free(self._b)
             self._b = None
 
     def __del__(self):

@@ -14,7 +14,11 @@ unit; here the work of ALL units goes through the scan library in three batches:
    device by the same single-variant test;
 3. the Cauchy combination (``acat_pval``) on the host.
 
-Only 2-bit genotype input (the RAW branch of the reference routines) is supported.
+That is the flow of 2-bit genotypes (``$dosage_alt``, the RAW branch of the reference routines).  Dosage
+input -- a format node such as ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` of uint8, int32 or
+float64 (the INTSXP / REALSXP branches) -- goes through ``DosageBlock`` in batches of consecutive units whose
+distinct variants fit a byte budget on the device: the rows of a batch are uploaded once, and counts, single-variant
+tests and the burden rows of every column of the driver are made from the resident rows (``_run_dosage``).
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from ._lib import Scanner
-from .assoc import GenotypeSource, _is_num, _open_source
+from .assoc import GenotypeSource, _dsnode, _is_num, _open_source
 from .gds import GdsFile, pack_dosage_2bit, unpack_dosage_2bit
 from .nullmod import ModelError, NullModel, init_nullmod, load_modobj
 
@@ -139,41 +143,8 @@ class _Prepared:
     pass
 
 
-def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, scanner_factory=None) -> _Prepared:
-    """Common head of the three drivers (R/assoc_aggregate.r:55-150): checks, sample matching,
-    model, and the per-variant scan of every variant that occurs in a unit."""
-    if verbose:
-        print(what)
-    pr = _Prepared()
-    pr.units = _Units(units)
-    pr.wbeta = _check_beta(wbeta)
-    for nm, v in (("spa.pval", spa_pval), ("var.ratio", var_ratio)):
-        if not _is_num(v):
-            raise TypeError(f"is.numeric({nm}) is not TRUE")
-    mod: NullModel = load_modobj(modobj, verbose)
-    src = _open_source(gdsfile, verbose)
-    gsid = [str(s) for s in src.sample_id()]
-    pos = {str(s): i for i, s in enumerate(mod.sample_id)}
-    sel = [i for i, s in enumerate(gsid) if s in pos]
-    if len(sel) != len(mod.sample_id):
-        raise ModelError("Some of sample IDs are not available in the GDS file.")
-    ii = np.array([pos[gsid[i]] for i in sel], dtype=np.int64)
-    if isinstance(src, GenotypeSource):
-        if src.packed is None:
-            raise NotImplementedError("aggregate tests take 2-bit genotypes ($dosage_alt)")
-        packed_all, n_all = src.packed, len(gsid)
-    else:
-        packed_all, n_all, _ = src.dosage_alt_packed()
-    n_var_all = packed_all.shape[0]
-    used = np.unique(np.concatenate(pr.units.index))
-    if used.size == 0 or used.min() < 1 or used.max() > n_var_all:
-        raise ValueError("No variant in the genotypic data set!")
-    if len(sel) == n_all and np.array_equal(sel, np.arange(n_all)):
-        packed = np.ascontiguousarray(packed_all[used - 1])
-    else:
-        packed = pack_dosage_2bit(unpack_dosage_2bit(packed_all[used - 1], n_all)[:, sel])
-    pr.local = {int(v): k for k, v in enumerate(used)}        # 1-based variant index -> row of `packed`
-    pr.packed = packed
+def _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner_factory):
+    """The model and the scanner of a driver call (and what the reference prints about the units)."""
     if not math.isfinite(var_ratio):
         var_ratio = float(np.nanmean(mod.var_ratio))
     sizes = np.array([len(ix) for ix in pr.units.index])
@@ -195,6 +166,174 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
     pr.sc = Scanner(pr.sm) if scanner_factory is None else scanner_factory(pr.sm)   # tests inject the CPU oracle
     if verbose:
         print("Calculating p-values:")
+
+
+DS_BUDGET = 1 << 30      # bytes of dosage rows resident on the device per batch of units
+
+
+def _sets_all(pr, r):
+    """Weights of a unit's burden row per weight set: dbeta(maf)."""
+    return [_dbeta(pr.maf[r], a, b) for a, b in pr.wbeta.T]
+
+
+def _sets_rare(pr, r, burden_mac):
+    """... of ACAT-V's burden of the rare variants: mac >= threshold -> single-variant test, not in the burden."""
+    rare = pr.mac[r] < burden_mac
+    return [np.where(rare, _dbeta(pr.maf[r], a, b), np.nan) for a, b in pr.wbeta.T]
+
+
+def _hard_calls(ds: np.ndarray) -> bool:
+    """An integer matrix that holds 0, 1, 2 and the missing code only: the RAW branch's meaning."""
+    miss = 0xFF if ds.dtype == np.uint8 else np.iinfo(np.int32).min
+    return bool(np.all((ds == miss) | ((ds >= 0) & (ds <= 2))))
+
+
+def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
+    """Dosage flow: the units in batches of consecutive units whose distinct variants fit ``budget`` bytes of
+    resident rows (a unit larger than that is a batch of its own).  Per batch: rows -> block (one upload), counts and
+    single-variant tests into the per-variant arrays, weights, one burden call with every column of the driver.
+    A variant that two batches share (sliding windows) is loaded in both.  Fills pr.n / s / maf / mac / pval and
+    pr.ds_out[kind] = (rows [n_units, n_weights, 8], valid)."""
+    if "rare" in kinds and not pr.binary:
+        return                                    # ACAT-V / ACAT-O of a quantitative trait: the driver raises, as the reference does
+    n_samp = pr.sm.n
+    row_bytes = n_samp * (1 if np.dtype(dtype) == np.uint8 else 8)
+    index = [np.array([pr.local[int(v)] for v in ix], dtype=np.int64) for ix in pr.units.index]
+    batches, cur, seen = [], [], set()
+    for u, r in enumerate(index):
+        new = set(r.tolist()) - seen
+        if cur and (len(seen) + len(new)) * row_bytes > budget:
+            batches.append(cur)
+            cur, seen, new = [], set(), set(r.tolist())
+        cur.append(u)
+        seen |= new
+    batches.append(cur)
+    pr.n_batches = len(batches)
+    nv_used, nu, nw, nk = used.size, len(index), pr.wbeta.shape[1], len(kinds)
+    pr.n, pr.s, pr.st = np.zeros(nv_used), np.zeros(nv_used), np.zeros(nv_used, dtype=np.int64)
+    pr.maf, pr.mac, pr.pval = np.full(nv_used, np.nan), np.full(nv_used, np.nan), np.full(nv_used, np.nan)
+    out_all, valid_all = np.full((nu, nk * nw, 8), np.nan), np.zeros((nu, nk * nw), dtype=np.uint8)
+    cap = max(np.unique(np.concatenate([index[u] for u in bt])).size for bt in batches)
+    with pr.sc.dosage_block(dtype, cap) as blk:
+        for bt in batches:
+            bv = np.unique(np.concatenate([index[u] for u in bt]))          # rows of the per-variant arrays
+            n, s, st = blk.load(read_rows(used[bv] - 1))
+            out, valid = blk.scan()
+            n = n.astype(np.float64)
+            # ds_mat_mafmac (src/saige_main.cpp:485-524): n non-missing, s their sum (a double sum for REAL dosages)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                af = s / (2 * n)
+            pr.n[bv], pr.s[bv], pr.st[bv] = n, s, st
+            pr.maf[bv] = np.where(n > 0, np.minimum(af, 1 - af), np.nan)
+            pr.mac[bv] = np.minimum(s, 2 * n - s)
+            pr.pval[bv] = np.where(valid != 0, out[:, 5], np.nan)          # single_test_*: NaN when the filter rejects
+            # ds_mat_burden (:526-610): the mean and the flip from its `int sum` (st), weights normalised per column
+            loc = {int(v): k for k, v in enumerate(bv)}
+            grp_ptr, var_idx, flip, ws, mws = [0], [], [], [], []
+            for u in bt:
+                r = index[u]
+                cols = []
+                for kind in kinds:
+                    cols += _sets_all(pr, r) if kind == "all" else _sets_rare(pr, r, burden_mac)
+                W = np.array(cols, dtype=np.float64).reshape(nk * nw, len(r)).T.copy()
+                for c in range(W.shape[1]):
+                    fin = np.isfinite(W[:, c])
+                    sm = W[fin, c].sum()
+                    if sm > 0:
+                        W[fin, c] = W[fin, c] * (1 / sm)                   # f64_normalize
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    m = pr.st[r] / pr.n[r]                                 # (double)sum / n
+                fl = pr.st[r] > pr.n[r]
+                m = np.where(fl, 2 - m, m)
+                keep = np.isfinite(W).any(axis=1)
+                var_idx += [loc[int(v)] for v in r[keep]]
+                flip += list(fl[keep])
+                ws.append(W[keep])
+                with np.errstate(invalid="ignore"):
+                    mws.append(m[keep, None] * W[keep])
+                grp_ptr.append(len(var_idx))
+            ob, vb = blk.burden(grp_ptr, np.asarray(var_idx, dtype=np.int32), np.asarray(flip, dtype=np.uint8),
+                                np.concatenate(ws).reshape(-1, nk * nw), np.concatenate(mws).reshape(-1, nk * nw))
+            out_all[bt] = ob.reshape(len(bt), nk * nw, 8)
+            valid_all[bt] = vb.reshape(len(bt), nk * nw)
+    pr.ds_out = {kind: (out_all[:, k * nw:(k + 1) * nw], valid_all[:, k * nw:(k + 1) * nw]) for k, kind in enumerate(kinds)}
+
+
+def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, scanner_factory=None, dsnode="",
+             kinds=("all",), burden_mac=float("nan"), ds_budget=None) -> _Prepared:
+    """Common head of the three drivers (R/assoc_aggregate.r:55-150): checks, sample matching,
+    model, and the per-variant scan of every variant that occurs in a unit.  Dosage input: the whole
+    device side, the burden rows of the driver's column ``kinds`` included (``_run_dosage``)."""
+    if verbose:
+        print(what)
+    pr = _Prepared()
+    pr.units = _Units(units)
+    pr.wbeta = _check_beta(wbeta)
+    for nm, v in (("spa.pval", spa_pval), ("var.ratio", var_ratio)):
+        if not _is_num(v):
+            raise TypeError(f"is.numeric({nm}) is not TRUE")
+    mod: NullModel = load_modobj(modobj, verbose)
+    src = _open_source(gdsfile, verbose)
+    gsid = [str(s) for s in src.sample_id()]
+    pos = {str(s): i for i, s in enumerate(mod.sample_id)}
+    sel = [i for i, s in enumerate(gsid) if s in pos]
+    if len(sel) != len(mod.sample_id):
+        raise ModelError("Some of sample IDs are not available in the GDS file.")
+    ii = np.array([pos[gsid[i]] for i in sel], dtype=np.int64)
+    if not isinstance(dsnode, str):
+        raise TypeError("is.character(dsnode) is not TRUE")
+    node = _dsnode(src, dsnode)
+    ds_all, ds_dtype = None, None                 # dosage input: the matrix in memory (else read from `node`), its type
+    if isinstance(src, GenotypeSource):
+        packed_all, n_all = src.packed, len(gsid)
+        if packed_all is None:
+            ds_all = np.asarray(src.dosage)
+            if ds_all.ndim != 2 or ds_all.shape[1] != n_all or ds_all.dtype not in (np.uint8, np.int32, np.float64):
+                raise TypeError("the dosages should be a [variant, sample] matrix of uint8, int32 or float64")
+            ds_dtype = ds_all.dtype
+            if ds_dtype != np.float64 and _hard_calls(ds_all):
+                # hard calls: the reference's RAW branch has the same meaning -> the 2-bit path
+                packed_all, ds_all = pack_dosage_2bit(np.where((ds_all < 0) | (ds_all > 2), 3, ds_all).astype(np.uint8)), None
+    elif node == "$dosage_alt":
+        packed_all, n_all, _ = src.dosage_alt_packed()
+    else:
+        packed_all, ds_dtype = None, np.dtype(np.float64)
+        n_var_ds, n_all = src.node(node + "/data").dims[:2]
+    pr.ds_out = None
+    if packed_all is None:
+        n_var_all = ds_all.shape[0] if ds_all is not None else n_var_ds
+        used = np.unique(np.concatenate(pr.units.index))
+        if used.size == 0 or used.min() < 1 or used.max() > n_var_all:
+            raise ValueError("No variant in the genotypic data set!")
+        pr.local = {int(v): k for k, v in enumerate(used)}
+        sel_a = np.asarray(sel, dtype=np.int64)
+        whole = len(sel) == n_all and np.array_equal(sel_a, np.arange(n_all))
+
+        def read_rows(v0):           # 0-based variant indices, ascending -> [len, n_samp], the model's samples only
+            if ds_all is not None:
+                rows = ds_all[v0]
+            else:
+                lo = int(v0[0])
+                rows = src.dosage_real_range(node, lo, int(v0[-1]) + 1)[v0 - lo]
+            return np.ascontiguousarray(rows if whole else rows[:, sel_a], dtype=ds_dtype)
+        _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner_factory)
+        try:
+            _run_dosage(pr, read_rows, ds_dtype, used, kinds, burden_mac, DS_BUDGET if ds_budget is None else ds_budget)
+        except BaseException:
+            pr.sc.close()
+            raise
+        return pr
+    n_var_all = packed_all.shape[0]
+    used = np.unique(np.concatenate(pr.units.index))
+    if used.size == 0 or used.min() < 1 or used.max() > n_var_all:
+        raise ValueError("No variant in the genotypic data set!")
+    if len(sel) == n_all and np.array_equal(sel, np.arange(n_all)):
+        packed = np.ascontiguousarray(packed_all[used - 1])
+    else:
+        packed = pack_dosage_2bit(unpack_dosage_2bit(packed_all[used - 1], n_all)[:, sel])
+    pr.local = {int(v): k for k, v in enumerate(used)}        # 1-based variant index -> row of `packed`
+    pr.packed = packed
+    _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner_factory)
     out, valid = pr.sc.scan_2bit(packed)
     # ds_mat_mafmac (src/saige_main.cpp:466-524), RAW branch: n non-missing, s = sum of codes
     num = out[:, 2]
@@ -231,10 +370,13 @@ def _summary_cols(pr: _Prepared) -> Dict[str, Any]:
     return ans
 
 
-def _burden_rows(pr: _Prepared, weight_sets: List[List[np.ndarray]]):
+def _burden_rows(pr: _Prepared, weight_sets: List[List[np.ndarray]], kind: str = "all"):
     """weight_sets[u][k] = per-variant weights (NaN = not in the burden) of unit u, row kind k.
     Returns the scan rows [n_units, n_kinds, 8] and validity; ``f64_normalize`` and the tables of
-    ``ds_mat_burden`` (RAW branch) are formed here."""
+    ``ds_mat_burden`` (RAW branch) are formed here.  Dosage input: the rows of column kind ``kind`` were
+    made while their batch was resident (``_run_dosage``, from the same weights)."""
+    if pr.ds_out is not None:
+        return pr.ds_out[kind]
     row_ptr, var_idx, lut = [0], [], []
     for u, sets in enumerate(weight_sets):
         r = np.asarray(pr.rows[u])
@@ -272,14 +414,16 @@ def _row_result(o, ok, n_snp, summac_thr):
 def seqAssocGLMM_spaBurden(gdsfile, modobj, units, wbeta=AggrParamBeta, summac: float = 3, dsnode: str = "",
                            spa_pval: float = 0.05, var_ratio: float = float("nan"), res_savefn: str = "",
                            res_compress: str = "LZMA", parallel=False, verbose: bool = True,
-                           verbose_maf: bool = True, scanner_factory=None) -> Dict[str, Any]:
+                           verbose_maf: bool = True, scanner_factory=None,
+                           ds_budget: Optional[int] = None) -> Dict[str, Any]:
     """Burden tests per unit and weight set (R/assoc_aggregate.r:51-302)."""
     if not (_is_num(summac) and math.isfinite(summac)):
         raise TypeError("is.finite(summac) is not TRUE")
-    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE burden analysis:", scanner_factory)
+    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE burden analysis:", scanner_factory,
+                  dsnode, ("all",), ds_budget=ds_budget)
     try:
         ans = _summary_cols(pr)
-        sets = [[_dbeta(pr.maf[r], a, b) for a, b in pr.wbeta.T] for r in pr.rows]
+        sets = [_sets_all(pr, r) for r in pr.rows]
         out, valid = _burden_rows(pr, sets)
     finally:
         pr.sc.close()
@@ -298,12 +442,9 @@ def _acatv(pr: _Prepared, burden_mac: float, burden_summac: float):
     """ACAT-V per unit and weight set (saige_acatv_test_bin, src/saige_main.cpp:720-830):
     returns p [n_units, n_w], and (n.single, n.burden, median/min/max of the combined p-values)."""
     nu, nw = len(pr.rows), pr.wbeta.shape[1]
-    sets = []
-    for r in pr.rows:
-        rare = pr.mac[r] < burden_mac            # mac >= threshold -> single-variant test
-        sets.append([np.where(rare, _dbeta(pr.maf[r], a, b), np.nan) for a, b in pr.wbeta.T])
+    sets = [_sets_rare(pr, r, burden_mac) for r in pr.rows]
     has_b = [bool(np.isfinite(s[0]).any()) for s in sets]
-    out, valid = _burden_rows(pr, sets)
+    out, valid = _burden_rows(pr, sets, "rare")
     p = np.full((nu, nw), np.nan)
     extra = np.full((nu, 2 + 3 * nw), np.nan)
     for u, r in enumerate(pr.rows):
@@ -334,9 +475,11 @@ def _acatv(pr: _Prepared, burden_mac: float, burden_summac: float):
 def seqAssocGLMM_spaACAT_V(gdsfile, modobj, units, wbeta=AggrParamBeta, burden_mac: float = 10,
                            burden_summac: float = 3, dsnode: str = "", spa_pval: float = 0.05,
                            var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
-                           parallel=False, verbose: bool = True, verbose_maf: bool = True, scanner_factory=None) -> Dict[str, Any]:
+                           parallel=False, verbose: bool = True, verbose_maf: bool = True, scanner_factory=None,
+                           ds_budget: Optional[int] = None) -> Dict[str, Any]:
     """ACAT-V tests (R/assoc_aggregate.r:309-557); binary outcomes only, as in the reference."""
-    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE ACAT-V analysis:", scanner_factory)
+    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE ACAT-V analysis:", scanner_factory,
+                  dsnode, ("rare",), burden_mac, ds_budget)
     try:
         if not pr.binary:
             raise NotImplementedError("'saige_acatv_test_quant' not implemented.")
@@ -356,15 +499,17 @@ def seqAssocGLMM_spaACAT_V(gdsfile, modobj, units, wbeta=AggrParamBeta, burden_m
 def seqAssocGLMM_spaACAT_O(gdsfile, modobj, units, wbeta=AggrParamBeta, burden_mac: float = 10,
                            burden_summac: float = 3, dsnode: str = "", spa_pval: float = 0.05,
                            var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
-                           parallel=False, verbose: bool = True, verbose_maf: bool = True, scanner_factory=None) -> Dict[str, Any]:
+                           parallel=False, verbose: bool = True, verbose_maf: bool = True, scanner_factory=None,
+                           ds_budget: Optional[int] = None) -> Dict[str, Any]:
     """ACAT-O: burden and ACAT-V p-values of every weight set combined by ACAT
     (R/assoc_aggregate.r:564-797, saige_acato_test_bin src/saige_main.cpp:845-976)."""
-    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE ACAT-O analysis:", scanner_factory)
+    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE ACAT-O analysis:", scanner_factory,
+                  dsnode, ("all", "rare"), burden_mac, ds_budget)
     try:
         if not pr.binary:
             raise NotImplementedError("'saige_acato_test_quant' not implemented.")
         ans = _summary_cols(pr)
-        sets = [[_dbeta(pr.maf[r], a, b) for a, b in pr.wbeta.T] for r in pr.rows]
+        sets = [_sets_all(pr, r) for r in pr.rows]
         out, valid = _burden_rows(pr, sets)
         pb = np.array([[_row_result(out[u, i], valid[u, i], len(pr.rows[u]), burden_summac)[3]
                         for i in range(pr.wbeta.shape[1])] for u in range(len(pr.rows))])

@@ -1,0 +1,261 @@
+// host_burden_ds.h -- aggregate tests on dosage input: a batch of dosage rows resident on the device
+// (sgx_dsblock) for the three things the drivers need from it -- per-variant counts, the single-variant
+// test of every row, and the burden rows of all units and weight columns.
+// Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
+
+// Rows as the dosage score kernels read them: row-major, stride N elements.  u8 rows stay u8; i32 rows are
+// stored as doubles (NaN = NA_INTEGER), as sgx_scan_i32 converts them; f64 rows as they come.
+struct sgx_dsblock {
+	int device = 0;
+	int N = 0, dtype = 0;
+	size_t cap = 0, M = 0;
+	uint8_t *rows = nullptr;
+	size_t row_bytes = 0;            // of a resident row: N (u8) or 8 N
+	int *d_nv = nullptr; double *d_sum = nullptr; long long *d_trunc = nullptr;   // [cap] ds_stats_kernel
+	uint8_t *tabs = nullptr; size_t tabs_cap = 0;    // sgx_dsblock_burden: groups, entries, weights
+};
+
+extern "C" int sgx_dsblock_create(int32_t n_samp, int dtype, size_t max_variants, int device, sgx_dsblock **out)
+{
+	if (!out) return fail(SGX_EINVAL, "sgx_dsblock_create: NULL argument");
+	*out = nullptr;
+	if (n_samp <= 0 || max_variants == 0) return fail(SGX_EINVAL, "sgx_dsblock_create: no samples or no variants");
+	if (dtype != SGX_DS_U8 && dtype != SGX_DS_I32 && dtype != SGX_DS_F64)
+		return fail(SGX_EINVAL, "sgx_dsblock_create: unknown dtype %d", dtype);
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+		return fail(SGX_ENODEV, "sgx_dsblock_create: no device %d", device);
+	HIPCHK(hipSetDevice(device));
+	sgx_dsblock *b = new sgx_dsblock();
+	b->device = device; b->N = n_samp; b->dtype = dtype; b->cap = max_variants;
+	b->row_bytes = (size_t)n_samp * (dtype == SGX_DS_U8 ? 1 : sizeof(double));
+	hipError_t e = hipMalloc((void **)&b->rows, b->cap * b->row_bytes + 16);
+	if (e == hipSuccess) e = hipMalloc((void **)&b->d_nv, b->cap * sizeof(int));
+	if (e == hipSuccess) e = hipMalloc((void **)&b->d_sum, b->cap * sizeof(double));
+	if (e == hipSuccess) e = hipMalloc((void **)&b->d_trunc, b->cap * sizeof(long long));
+	if (e != hipSuccess) {
+		const size_t rb = b->row_bytes;
+		sgx_dsblock_free(b);
+		return fail(SGX_ENOMEM, "sgx_dsblock_create: %zu rows of %zu bytes: %s", max_variants, rb, hipGetErrorString(e));
+	}
+	*out = b;
+	return SGX_OK;
+}
+
+extern "C" void sgx_dsblock_free(sgx_dsblock *b)
+{
+	if (!b) return;
+	(void)hipSetDevice(b->device);
+	if (b->rows) (void)hipFree(b->rows);
+	if (b->d_nv) (void)hipFree(b->d_nv);
+	if (b->d_sum) (void)hipFree(b->d_sum);
+	if (b->d_trunc) (void)hipFree(b->d_trunc);
+	if (b->tabs) (void)hipFree(b->tabs);
+	delete b;
+}
+
+static int dsblock_check(sgx_handle *h, const sgx_dsblock *b, const char *who)
+{
+	if (!h || !b) return fail(SGX_EINVAL, "%s: NULL argument", who);
+	if (b->device != h->device) return fail(SGX_EINVAL, "%s: block and handle are on different devices", who);
+	if (b->N != h->md.N) return fail(SGX_EINVAL, "Invalid length of dosages: %d.", b->N);
+	return SGX_OK;
+}
+
+// Rows in host memory into the block -- the one crossing of PCIe of a batch -- and their counts back.
+// u8 / f64 rows are copied to where they stay, in chunks of the pipeline's size; i32 chunks land in the
+// pipeline's two input buffers on the copy stream and are converted on the handle's stream meanwhile.
+extern "C" int sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosage, size_t M,
+	int32_t *n_valid, double *sum, int64_t *sum_trunc)
+{
+	int rc = dsblock_check(h, b, "sgx_dsblock_load");
+	if (rc) return rc;
+	if (!dosage || !n_valid || !sum || !sum_trunc) return fail(SGX_EINVAL, "sgx_dsblock_load: NULL buffer");
+	if (M == 0 || M > b->cap) return fail(SGX_EINVAL, "sgx_dsblock_load: %zu variants, the block holds up to %zu", M, b->cap);
+	rc = sync_lane(h);                        // anything that still reads the block through this handle is done
+	if (rc) return rc;
+	b->M = 0;
+	const int N = b->N;
+	const size_t src_row = (size_t)N * (b->dtype == SGX_DS_U8 ? 1 : b->dtype == SGX_DS_I32 ? sizeof(int32_t) : sizeof(double));
+	const size_t chunk = std::min(M, std::max<size_t>(1, (h->pipe_bytes ? h->pipe_bytes : PIPE_BYTES) / src_row));
+	const uint8_t *src = reinterpret_cast<const uint8_t *>(dosage);
+	if (b->dtype != SGX_DS_I32) {
+		for (size_t off = 0; off < M; off += chunk)
+			HIPCHK(hipMemcpyAsync(b->rows + off * b->row_bytes, src + off * src_row, std::min(chunk, M - off) * src_row,
+				hipMemcpyHostToDevice, h->stream));
+	} else {
+		rc = ensure_pipe(h, chunk * src_row, 0, 1);
+		if (rc) return rc;
+		int i = 0;
+		for (size_t off = 0; off < M; off += chunk, i++) {
+			const size_t m = std::min(chunk, M - off);
+			const int k = i & 1;
+			if (i >= 2) HIPCHK(hipStreamWaitEvent(h->cstream, h->ev_done[k], 0));      // the buffer's previous chunk has been read
+			HIPCHK(hipMemcpyAsync(h->pipe_in[k], src + off * src_row, m * src_row, hipMemcpyHostToDevice, h->cstream));
+			HIPCHK(hipEventRecord(h->ev_copy[k], h->cstream));
+			HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy[k], 0));
+			hipLaunchKernelGGL(i32_rows_to_f64, dim3(1024), dim3(256), 0, h->stream,
+				(const int *)h->pipe_in[k], m * (size_t)N, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
+			HIPCHK(hipGetLastError());
+			HIPCHK(hipEventRecord(h->ev_done[k], h->stream));
+		}
+		HIPCHK(hipStreamSynchronize(h->cstream));
+	}
+	if (b->dtype == SGX_DS_U8)
+		hipLaunchKernelGGL((ds_stats_kernel<uint8_t>), dim3((unsigned)M), dim3(256), 0, h->stream,
+			(const uint8_t *)b->rows, N, b->d_nv, b->d_sum, b->d_trunc);
+	else
+		hipLaunchKernelGGL((ds_stats_kernel<double>), dim3((unsigned)M), dim3(256), 0, h->stream,
+			(const double *)b->rows, N, b->d_nv, b->d_sum, b->d_trunc);
+	HIPCHK(hipGetLastError());
+	static_assert(sizeof(long long) == sizeof(int64_t), "sum_trunc");
+	HIPCHK(hipMemcpyAsync(n_valid, b->d_nv, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(sum, b->d_sum, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(sum_trunc, b->d_trunc, M * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
+	b->M = M;
+	return SGX_OK;
+}
+
+// Single-variant test of every resident row.  The rows go to the dosage kernels in the chunks scan_host would cut
+// the same host buffer into (the tiled score kernel splits the samples by the number of rows of a launch, so the
+// same chunks give the same sums): results equal sgx_scan_u8 / _i32 / _f64 on rows that take the dosage kernels
+// there bit for bit.  Hard-call u8 / i32 rows are NOT packed to 2-bit here (the host-buffer scans do that): they
+// take the dosage kernels too, and agree with the fixed-point kernels within the scan's tolerance.
+extern "C" int sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out8, uint8_t *valid)
+{
+	int rc = dsblock_check(h, b, "sgx_dsblock_scan");
+	if (rc) return rc;
+	if (!out8 || !valid) return fail(SGX_EINVAL, "sgx_dsblock_scan: NULL buffer");
+	if (b->M == 0) return fail(SGX_EINVAL, "sgx_dsblock_scan: nothing loaded");
+	rc = sync_lane(h);
+	if (rc) return rc;
+	h->last_issued = h;
+	const size_t N = (size_t)b->N, M = b->M;
+	const size_t per_row = b->dtype == SGX_DS_U8 ? N : b->dtype == SGX_DS_I32 ? N * (sizeof(int32_t) + sizeof(double)) : N * sizeof(double);
+	const size_t chunk = std::min(M, std::max<size_t>(1, (h->pipe_bytes ? h->pipe_bytes : PIPE_BYTES) / per_row));
+	rc = ensure_stage(h, 0, chunk);
+	if (rc) return rc;
+	rc = ensure_recs(h, chunk);
+	if (rc) return rc;
+	sgx_stats total{};
+	for (size_t off = 0; off < M; off += chunk) {
+		const size_t m = std::min(chunk, M - off);
+		const uint8_t *rows = b->rows + off * b->row_bytes;
+		if (b->dtype == SGX_DS_U8) rc = launch_scan<IN_U8>(h, rows, b->row_bytes, m, h->stage_out, h->stage_valid);
+		else rc = launch_scan<IN_F64>(h, rows, b->row_bytes, m, h->stage_out, h->stage_valid);
+		if (rc) return rc;
+		HIPCHK(hipMemcpyAsync(out8 + off * 8, h->stage_out, m * 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipMemcpyAsync(valid + off, h->stage_valid, m, hipMemcpyDeviceToHost, h->stream));
+		rc = sgx_sync(h);
+		if (rc) return rc;
+		stats_add(total, h->stats);
+	}
+	h->stats = total;
+	return SGX_OK;
+}
+
+template <typename T>
+static void launch_collapse_ds(hipStream_t st, const T *rows, int N, size_t n_groups, const long long *grp_ptr,
+	const int *var_idx, const uint8_t *flip, int n_cols, int c0, int nc, const double *w, const double *mw, double *out)
+{
+	auto go = [&](auto nct, auto spt) {
+		constexpr int NC = decltype(nct)::value, SPT = decltype(spt)::value;
+		const dim3 grid((unsigned)((N + 256 * SPT - 1) / (256 * SPT)), (unsigned)n_groups);
+		hipLaunchKernelGGL((burden_collapse_ds_kernel<T, NC, SPT>), grid, dim3(256), 0, st,
+			rows, N, grp_ptr, var_idx, flip, n_cols, c0, nc, w, mw, out);
+	};
+	using std::integral_constant;
+	constexpr bool U8 = sizeof(T) == 1;
+	if (nc <= 1) go(integral_constant<int, 1>{}, integral_constant<int, U8 ? 16 : 4>{});
+	else if (nc <= 2) go(integral_constant<int, 2>{}, integral_constant<int, U8 ? 16 : 4>{});
+	else if (nc <= 4) go(integral_constant<int, 4>{}, integral_constant<int, U8 ? 8 : 4>{});
+	else go(integral_constant<int, 8>{}, integral_constant<int, 4>{});
+}
+
+// Burden rows of n_groups units x n_cols weight columns from the resident rows, then the single-variant test on
+// each (ds_mat_burden + single_test_bin/quant of saige_burden_test_*, saige_acatv_test_bin, saige_acato_test_bin,
+// src/saige_main.cpp:526-976, for INTSXP / REALSXP dosages).  Whole groups per chunk of STAGE_BYTES of collapsed rows;
+// the collapse kernel takes up to SGX_DS_COLS_PER_PASS columns per pass over a group's rows.
+#define SGX_DS_COLS_PER_PASS 8
+extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_groups, const int64_t *grp_ptr,
+	const int32_t *var_idx, const uint8_t *flip, int n_cols, const double *w, const double *mw,
+	double *out8, uint8_t *valid)
+{
+	int rc = dsblock_check(h, b, "sgx_dsblock_burden");
+	if (rc) return rc;
+	if (n_groups == 0) return SGX_OK;
+	if (!grp_ptr || !var_idx || !flip || !w || !mw || !out8 || !valid)
+		return fail(SGX_EINVAL, "sgx_dsblock_burden: NULL buffer");
+	if (n_cols < 1 || n_cols > SGX_DS_MAX_COLS)
+		return fail(SGX_EINVAL, "sgx_dsblock_burden: n_cols = %d, 1 .. %d are supported", n_cols, SGX_DS_MAX_COLS);
+	if (b->M == 0) return fail(SGX_EINVAL, "sgx_dsblock_burden: nothing loaded");
+	const int64_t nnz = grp_ptr[n_groups];
+	if (grp_ptr[0] != 0 || nnz < 0) return fail(SGX_EINVAL, "sgx_dsblock_burden: bad grp_ptr");
+	for (size_t g = 0; g < n_groups; g++)
+		if (grp_ptr[g + 1] < grp_ptr[g]) return fail(SGX_EINVAL, "sgx_dsblock_burden: grp_ptr not ascending");
+	for (int64_t e = 0; e < nnz; e++)
+		if (var_idx[e] < 0 || (size_t)var_idx[e] >= b->M)
+			return fail(SGX_EINVAL, "sgx_dsblock_burden: variant index %d outside the block's %zu rows", var_idx[e], b->M);
+	rc = sync_lane(h);
+	if (rc) return rc;
+	h->last_issued = h;
+	// device copies of the tables
+	sgx_dsblock *bm = const_cast<sgx_dsblock *>(b);
+	const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
+	const size_t o_idx = ((n_groups + 1) * sizeof(long long) + 15) & ~(size_t)15;
+	const size_t o_w = (o_idx + ne * sizeof(int) + 15) & ~(size_t)15;
+	const size_t o_mw = o_w + ne * (size_t)n_cols * sizeof(double);
+	const size_t o_flip = o_mw + ne * (size_t)n_cols * sizeof(double);
+	const size_t need = o_flip + ne;
+	if (need > bm->tabs_cap) {
+		if (bm->tabs) HIPCHK(hipFree(bm->tabs));
+		bm->tabs = nullptr; bm->tabs_cap = 0;
+		HIPCHK(hipMalloc((void **)&bm->tabs, need));
+		bm->tabs_cap = need;
+	}
+	std::vector<long long> gp(grp_ptr, grp_ptr + n_groups + 1);
+	HIPCHK(hipMemcpyAsync(b->tabs, gp.data(), gp.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+	if (nnz > 0) {
+		HIPCHK(hipMemcpyAsync(b->tabs + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(hipMemcpyAsync(b->tabs + o_w, w, (size_t)nnz * n_cols * sizeof(double), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(hipMemcpyAsync(b->tabs + o_mw, mw, (size_t)nnz * n_cols * sizeof(double), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(hipMemcpyAsync(b->tabs + o_flip, flip, (size_t)nnz, hipMemcpyHostToDevice, h->stream));
+	}
+	HIPCHK(hipStreamSynchronize(h->stream));      // gp is a local
+	const int N = b->N;
+	const size_t row_bytes = (size_t)N * sizeof(double);
+	size_t gchunk = std::max<size_t>(1, STAGE_BYTES / (row_bytes * (size_t)n_cols));
+	gchunk = std::min<size_t>(std::min(gchunk, n_groups), 65535);       // grid.y of the collapse kernel
+	rc = ensure_stage(h, gchunk * n_cols * row_bytes, gchunk * n_cols);
+	if (rc) return rc;
+	rc = ensure_recs(h, gchunk * n_cols);
+	if (rc) return rc;
+	sgx_stats total{};
+	const long long *d_gp = reinterpret_cast<const long long *>(b->tabs);
+	const int *d_idx = reinterpret_cast<const int *>(b->tabs + o_idx);
+	const double *d_w = reinterpret_cast<const double *>(b->tabs + o_w), *d_mw = reinterpret_cast<const double *>(b->tabs + o_mw);
+	const uint8_t *d_flip = b->tabs + o_flip;
+	for (size_t off = 0; off < n_groups; off += gchunk) {
+		const size_t ng = std::min(gchunk, n_groups - off), m = ng * (size_t)n_cols;
+		for (int c0 = 0; c0 < n_cols; c0 += SGX_DS_COLS_PER_PASS) {
+			const int nc = std::min(SGX_DS_COLS_PER_PASS, n_cols - c0);
+			if (b->dtype == SGX_DS_U8)
+				launch_collapse_ds<uint8_t>(h->stream, (const uint8_t *)b->rows, N, ng, d_gp + off, d_idx, d_flip, n_cols, c0, nc,
+					d_w, d_mw, reinterpret_cast<double *>(h->stage_in));
+			else
+				launch_collapse_ds<double>(h->stream, (const double *)b->rows, N, ng, d_gp + off, d_idx, d_flip, n_cols, c0, nc,
+					d_w, d_mw, reinterpret_cast<double *>(h->stage_in));
+			HIPCHK(hipGetLastError());
+		}
+		rc = launch_scan<IN_F64>(h, h->stage_in, row_bytes, m, h->stage_out, h->stage_valid);
+		if (rc) return rc;
+		HIPCHK(hipMemcpyAsync(out8 + off * n_cols * 8, h->stage_out, m * 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipMemcpyAsync(valid + off * n_cols, h->stage_valid, m, hipMemcpyDeviceToHost, h->stream));
+		rc = sgx_sync(h);
+		if (rc) return rc;
+		stats_add(total, h->stats);
+	}
+	h->stats = total;
+	return SGX_OK;
+}

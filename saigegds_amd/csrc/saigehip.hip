@@ -69,6 +69,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_synth.h"
 #include "kern_grm.h"
 #include "kern_burden.h"
+#include "kern_burden_ds.h"
 #include "kern_pack.h"
 
 // ---------------------------------------------------------------------------
@@ -80,5 +81,6 @@ static int fail(int code, const char *fmt, ...)
 #include "host_blocks.h"
 #include "host_scan.h"
 #include "host_pipeline.h"
+#include "host_burden_ds.h"
 #include "host_util.h"
 #include "host_grm.h"
