@@ -218,6 +218,27 @@ int sgx_scan_i32(sgx_handle *h, const int32_t *dosage, size_t n_variants,
 int sgx_scan_f64(sgx_handle *h, const double *dosage, size_t n_variants,
 	double *out8, uint8_t *valid);
 
+/* Packed-real dosage rows in HOST memory, as a SeqArray file stores annotation/format/DS/data: one row of
+ * n_file_samp values per variant, the FILE's samples in the file's order,
+ *   SGX_PR_U8 / _I8   1 byte a value,  0xFF   / -128   = missing (dPackedReal8U / dPackedReal8)
+ *   SGX_PR_U16 / _I16 2 bytes a value, 0xFFFF / -32768 = missing (dPackedReal16U / dPackedReal16)
+ *   SGX_PR_F32        float, NaN / Inf = missing; scale and offset are not applied (dFloat32)
+ * with the node's scale and offset: dosage = raw * scale + offset, the product rounded and then the sum (what
+ * gdsfmt's reader and saigegds_amd/gds.py compute).  The rows cross PCIe as they are stored -- 1/8, 1/4 or 1/2
+ * of the bytes of the float64 rows seqApply hands get_ds (REALSXP, src/saige_main.cpp:173-174) -- and are decoded
+ * and sample-selected on the device.  sel: NULL (then n_file_samp must equal the model's n_samp) or n_samp
+ * indices into the file's samples in the MODEL's order, each checked against [0, n_file_samp).  Chunks are
+ * those of sgx_scan_f64 (rows of 8 n_samp bytes per "pipe_mb"), so out8 / valid equal sgx_scan_f64 on the
+ * host-decoded, sample-selected rows bit for bit.  A bad argument (unknown cls, NULL buffer, n_file_samp <
+ * n_samp, no sel with n_file_samp != n_samp, an index out of range) returns SGX_EINVAL and launches nothing. */
+#define SGX_PR_U8 0   /* dPackedReal8U  */
+#define SGX_PR_I8 1   /* dPackedReal8   */
+#define SGX_PR_U16 2  /* dPackedReal16U */
+#define SGX_PR_I16 3  /* dPackedReal16  */
+#define SGX_PR_F32 4  /* dFloat32       */
+int sgx_scan_packed(sgx_handle *h, const void *raw, int cls, size_t n_file_samp, double scale, double offset,
+	const int32_t *sel, size_t n_variants, double *out8, uint8_t *valid);
+
 /* Aggregate tests: n_rows burden rows from 2-bit genotypes in HOST memory, then the
  * single-variant test on every row (replaces ds_mat_burden + single_test_bin/quant inside
  * saige_burden_test_*, saige_acatv_test_bin and saige_acato_test_bin, src/saige_main.cpp:526-976).
@@ -259,7 +280,13 @@ int sgx_burden_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_varia
  *                       2 - that (saigegds_amd/aggregate.py).  Then the single-variant test on every
  *                       row; out8 / valid: n_groups * n_cols rows.  A row of hard calls equals the row
  *                       sgx_burden_2bit makes from the packed form of the same data bit for bit.
- * All four are synchronous; block and handle must be on the same device and have the same n_samp. */
+ *   sgx_ds_block_load_packed  the load of an SGX_DS_F64 block (SGX_EINVAL for the other types) from packed-real
+ *                       rows as the file stores them (raw, cls, n_file_samp, scale, offset, sel: as for
+ *                       sgx_scan_packed, same checks): decoded and sample-selected on the device.  n_valid, sum,
+ *                       sum_trunc and everything sgx_dsblock_scan / _burden then give equal sgx_dsblock_load of
+ *                       the host-decoded rows bit for bit.  (Its name stands apart from the sgx_dsblock_* five on
+ *                       purpose: that set is pinned as it is by tests/test_aggregate_dosage.py.)
+ * All five are synchronous; block and handle must be on the same device and have the same n_samp. */
 #define SGX_DS_U8  0
 #define SGX_DS_I32 1
 #define SGX_DS_F64 2
@@ -268,6 +295,9 @@ typedef struct sgx_dsblock sgx_dsblock;
 int  sgx_dsblock_create(int32_t n_samp, int dtype, size_t max_variants, int device, sgx_dsblock **out);
 void sgx_dsblock_free(sgx_dsblock *b);
 int  sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosage, size_t n_variants,
+	int32_t *n_valid, double *sum, int64_t *sum_trunc);
+int  sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const void *raw, int cls, size_t n_file_samp,
+	double scale, double offset, const int32_t *sel, size_t n_variants,
 	int32_t *n_valid, double *sum, int64_t *sum_trunc);
 int  sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out8, uint8_t *valid);
 int  sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_groups, const int64_t *grp_ptr,

@@ -21,11 +21,34 @@ EXPORTS = (
     "sgx_grm_init", "sgx_grm_init_dev", "sgx_grm_crossprod_dev", "sgx_grm_sync", "sgx_grm_free", "sgx_grm_diag", "sgx_grm_crossprod", "sgx_grm_pcg",
     "sgx_grm_crossprod_multi", "sgx_grm_crossprod_multi_dev", "sgx_grm_pcg_multi",
     "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
+    "sgx_scan_packed", "sgx_ds_block_load_packed",
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
 DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
 DS_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float64): 2}   # SGX_DS_U8 / _I32 / _F64
+# SGX_PR_*: the GDS classes whose rows cross PCIe as stored (sgx_scan_packed) and the numpy type of their values
+PACKED_CLASSES = {"dPackedReal8U": 0, "dPackedReal8": 1, "dPackedReal16U": 2, "dPackedReal16": 3, "dFloat32": 4}
+PACKED_DTYPES = (np.dtype(np.uint8), np.dtype(np.int8), np.dtype("<u2"), np.dtype("<i2"), np.dtype("<f4"))
+
+
+def _packed_args(raw, cls, n, sel):
+    """Checks of the shapes ctypes cannot see -> (raw, SGX_PR_* code, sel or None); the values are checked in C."""
+    if isinstance(cls, str) and cls not in PACKED_CLASSES:
+        raise ValueError(f"unknown packed-real class {cls!r}")
+    code = PACKED_CLASSES[cls] if isinstance(cls, str) else int(cls)
+    if 0 <= code < len(PACKED_DTYPES):
+        raw = np.ascontiguousarray(raw, dtype=PACKED_DTYPES[code])
+    else:
+        raw = np.ascontiguousarray(raw)                # (an unknown code: the library refuses it)
+    if raw.ndim != 2:
+        raise ValueError("packed-real rows must be [n_variants, n_file_samp]")
+    if sel is not None:
+        sel = np.ascontiguousarray(sel)
+        if sel.shape != (n,):
+            raise ValueError(f"Invalid length of dosages: {sel.size}.")
+        sel = np.clip(sel, -1, np.iinfo(np.int32).max).astype(np.int32)     # (out of int32's range stays out of range)
+    return raw, code, sel
 
 
 class SgxError(RuntimeError):
@@ -143,6 +166,10 @@ def load():
     L.sgx_dsblock_free.argtypes = [vp]
     L.sgx_dsblock_load.restype = C.c_int
     L.sgx_dsblock_load.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    L.sgx_scan_packed.restype = C.c_int
+    L.sgx_scan_packed.argtypes = [vp, vp, C.c_int, sz, dp, dp, vp, sz, vp, vp]
+    L.sgx_ds_block_load_packed.restype = C.c_int
+    L.sgx_ds_block_load_packed.argtypes = [vp, vp, vp, C.c_int, sz, dp, dp, vp, sz, vp, vp, vp]
     L.sgx_dsblock_scan.restype = C.c_int
     L.sgx_dsblock_scan.argtypes = [vp, vp, vp, vp]
     L.sgx_dsblock_burden.restype = C.c_int
@@ -276,6 +303,18 @@ class Scanner:
         out, valid = self._out(dosage.shape[0])
         check(self._L.sgx_scan_f64(self._h, dosage.ctypes.data, dosage.shape[0], out.ctypes.data,
                                    valid.ctypes.data))
+        return out, valid
+
+    def scan_packed(self, raw: np.ndarray, cls, scale: float, offset: float, sel=None):
+        """Packed-real dosage rows as the file stores them (``sgx_scan_packed``): ``raw`` [m, n_file_samp] integers
+        (or float32) of class ``cls`` (a GDS class name or an SGX_PR_* code), dosage = raw * scale + offset, decoded
+        on the device.  ``sel``: None (the file's samples are the model's) or the model's samples as indices into
+        the file's.  Equals ``scan_f64`` of the decoded, selected rows bit for bit."""
+        raw, code, sel = _packed_args(raw, cls, self.n, sel)
+        out, valid = self._out(raw.shape[0])
+        check(self._L.sgx_scan_packed(self._h, raw.ctypes.data, code, raw.shape[1], float(scale), float(offset),
+                                      None if sel is None else sel.ctypes.data, raw.shape[0], out.ctypes.data,
+                                      valid.ctypes.data))
         return out, valid
 
     def burden_2bit(self, packed: np.ndarray, row_ptr, var_idx, lut):
@@ -422,6 +461,19 @@ class DosageBlock:
         nv, sm, st = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float64), np.empty(m, dtype=np.int64)
         check(self._L.sgx_dsblock_load(self._sc._h, self._b, dosage.ctypes.data, m, nv.ctypes.data, sm.ctypes.data,
                                        st.ctypes.data))
+        self.n_variants = m
+        return nv, sm, st
+
+    def load_packed(self, raw: np.ndarray, cls, scale: float, offset: float, sel=None):
+        """Packed-real rows as the file stores them -> a float64 block, decoded and sample-selected on the device
+        (``sgx_ds_block_load_packed``; arguments as ``Scanner.scan_packed``); returns what ``load`` of the decoded
+        rows returns."""
+        raw, code, sel = _packed_args(raw, cls, self.n, sel)
+        m = raw.shape[0]
+        nv, sm, st = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.float64), np.empty(m, dtype=np.int64)
+        check(self._L.sgx_ds_block_load_packed(self._sc._h, self._b, raw.ctypes.data, code, raw.shape[1], float(scale),
+                                              float(offset), None if sel is None else sel.ctypes.data, m,
+                                              nv.ctypes.data, sm.ctypes.data, st.ctypes.data))
         self.n_variants = m
         return nv, sm, st
 

@@ -28,7 +28,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from ._lib import Scanner
-from .assoc import GenotypeSource, _dsnode, _is_num, _open_source
+from .assoc import GenotypeSource, PackedRows, _dsnode, _is_num, _open_source, packed_block_size
 from .gds import GdsFile, pack_dosage_2bit, unpack_dosage_2bit
 from .nullmod import ModelError, NullModel, init_nullmod, load_modobj
 
@@ -217,7 +217,8 @@ def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
     with pr.sc.dosage_block(dtype, cap) as blk:
         for bt in batches:
             bv = np.unique(np.concatenate([index[u] for u in bt]))          # rows of the per-variant arrays
-            n, s, st = blk.load(read_rows(used[bv] - 1))
+            rows = read_rows(used[bv] - 1)
+            n, s, st = blk.load_packed(*rows.args()) if isinstance(rows, PackedRows) else blk.load(rows)
             out, valid = blk.scan()
             n = n.astype(np.float64)
             # ds_mat_mafmac (src/saige_main.cpp:485-524): n non-missing, s their sum (a double sum for REAL dosages)
@@ -309,7 +310,23 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
         sel_a = np.asarray(sel, dtype=np.int64)
         whole = len(sel) == n_all and np.array_equal(sel_a, np.arange(n_all))
 
+        # a packed-real or float32 node goes to the device as stored: the variants are picked here, the samples
+        # there.  (An injected scanner -- the tests' CPU stand-in for the device -- has no such load: decoded rows.)
+        stored = ds_all is None and scanner_factory is None and src.dosage_raw_class(node) is not None
+
+        def read_stored(v0):         # ... -> PackedRows [len, n_all], the file's samples
+            step = packed_block_size(src.dosage_raw_row_bytes(node))
+            parts, meta = [], None
+            for a in range(int(v0[0]), int(v0[-1]) + 1, step):          # the range in pieces of a bounded size
+                pick = v0[(v0 >= a) & (v0 < a + step)]
+                if pick.size:
+                    raw, *meta = src.dosage_raw_range(node, int(pick[0]), int(pick[-1]) + 1)
+                    parts.append(raw[pick - pick[0]])
+            return PackedRows(np.concatenate(parts), *meta, None if whole else sel_a)
+
         def read_rows(v0):           # 0-based variant indices, ascending -> [len, n_samp], the model's samples only
+            if stored:
+                return read_stored(v0)
             if ds_all is not None:
                 rows = ds_all[v0]
             else:

@@ -20,6 +20,32 @@ from .nullmod import ModelError, NullModel, ScanModel, init_nullmod, load_modobj
 BLOCK_SIZE = 50_000   # .bl_size=50000L, R/assoc_single.r:204
 
 
+PACKED_BLOCK_BYTES = 1 << 30   # host bytes of one block of packed-real rows as the file stores them
+
+
+def packed_block_size(raw_row_bytes: int) -> int:
+    """Variants per block on the packed-real route: .bl_size, but no more than a GiB of stored rows -- a block is
+    read and held whole on the host, and at N = 430 000 a 16-bit row is 0.86 MB (50 000 of them: 43 GB)."""
+    return min(BLOCK_SIZE, max(1, PACKED_BLOCK_BYTES // int(raw_row_bytes)))
+
+
+class PackedRows:
+    """Rows of a packed-real (or float32) dosage node as stored (``GdsFile.dosage_raw_range``) with what the device
+    needs to decode them: the node's class, scale and offset, and the model's samples as indices into the file's
+    (None: the file's samples are the model's, in order).  What ``Scanner.scan_packed`` / ``DosageBlock.load_packed``
+    take."""
+
+    def __init__(self, raw: np.ndarray, cls: str, scale: float, offset: float, sel: Optional[np.ndarray]):
+        self.raw, self.cls, self.scale, self.offset, self.sel = raw, cls, scale, offset, sel
+
+    @property
+    def nbytes(self) -> int:
+        return self.raw.nbytes
+
+    def args(self):
+        return self.raw, self.cls, self.scale, self.offset, self.sel
+
+
 class GenotypeSource:
     """In-memory stand-in for an opened SeqArray GDS file (synthetic data,
     tests): 2-bit packed ``$dosage_alt`` rows or real-valued dosages."""
@@ -127,7 +153,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         kind = "packed"
         n_var, n_all = src.genotype_dims()
     else:
-        kind = "dosage"
+        # packed-real and float32 nodes go to the device as stored; dFloat64 / integer nodes are decoded here
+        kind = "dosage" if src.dosage_raw_class(node) is None else "stored"
         n_var, n_all = src.node(node + "/data").dims[:2]
     if verbose:
         print(f"    # of samples: {_pretty(n_samp)}")
@@ -158,6 +185,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
             return blk if all_samples else np.ascontiguousarray(blk[:, sel])
         if kind == "packed":
             return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
+        if kind == "stored":
+            return PackedRows(*src.dosage_raw_range(node, off, end), None if all_samples else sel)
         blk = src.dosage_real_range(node, off, end)
         return blk if all_samples else np.ascontiguousarray(blk[:, sel])
 
@@ -180,7 +209,10 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     # offsets, so the table keeps the file's order whatever GPU finishes first (:226-227)
     out = np.empty((n_var, 8), dtype=np.float64)
     valid = np.zeros(n_var, dtype=np.uint8)
-    blocks = [(off, min(n_var, off + BLOCK_SIZE)) for off in range(0, n_var, BLOCK_SIZE)]
+    bl_size = BLOCK_SIZE
+    if kind == "stored":
+        bl_size = packed_block_size(src.dosage_raw_row_bytes(node))
+    blocks = [(off, min(n_var, off + bl_size)) for off in range(0, n_var, bl_size)]
     t_loop = time.perf_counter()
     scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, read_block, kind == "packed", out, valid, timing)
     if timing is not None:
@@ -253,6 +285,8 @@ def scan_blocks(make_scanner, ngpu: int, blocks, read_block, packed_rows: bool, 
                     t = time.perf_counter()
                     if packed_rows:
                         o, v = sc.scan_2bit(blk)            # 2-bit packed rows
+                    elif isinstance(blk, PackedRows):
+                        o, v = sc.scan_packed(*blk.args())  # packed-real rows as stored: decoded on the device
                     elif blk.dtype == np.uint8:
                         o, v = sc.scan_u8(blk)
                     elif np.issubdtype(blk.dtype, np.integer):

@@ -62,6 +62,25 @@ static int dsblock_check(sgx_handle *h, const sgx_dsblock *b, const char *who)
 	return SGX_OK;
 }
 
+// ds_stats_kernel on the M rows just put into the block, the counts to the caller; the block is loaded when they are back
+static int dsblock_counts(sgx_handle *h, sgx_dsblock *b, size_t M, int32_t *n_valid, double *sum, int64_t *sum_trunc)
+{
+	if (b->dtype == SGX_DS_U8)
+		hipLaunchKernelGGL((ds_stats_kernel<uint8_t>), dim3((unsigned)M), dim3(256), 0, h->stream,
+			(const uint8_t *)b->rows, b->N, b->d_nv, b->d_sum, b->d_trunc);
+	else
+		hipLaunchKernelGGL((ds_stats_kernel<double>), dim3((unsigned)M), dim3(256), 0, h->stream,
+			(const double *)b->rows, b->N, b->d_nv, b->d_sum, b->d_trunc);
+	HIPCHK(hipGetLastError());
+	static_assert(sizeof(long long) == sizeof(int64_t), "sum_trunc");
+	HIPCHK(hipMemcpyAsync(n_valid, b->d_nv, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(sum, b->d_sum, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(sum_trunc, b->d_trunc, M * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
+	b->M = M;
+	return SGX_OK;
+}
+
 // Rows in host memory into the block -- the one crossing of PCIe of a batch -- and their counts back.
 // u8 / f64 rows are copied to where they stay, in chunks of the pipeline's size; i32 chunks land in the
 // pipeline's two input buffers on the copy stream and are converted on the handle's stream meanwhile.
@@ -101,20 +120,48 @@ extern "C" int sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosag
 		}
 		HIPCHK(hipStreamSynchronize(h->cstream));
 	}
-	if (b->dtype == SGX_DS_U8)
-		hipLaunchKernelGGL((ds_stats_kernel<uint8_t>), dim3((unsigned)M), dim3(256), 0, h->stream,
-			(const uint8_t *)b->rows, N, b->d_nv, b->d_sum, b->d_trunc);
-	else
-		hipLaunchKernelGGL((ds_stats_kernel<double>), dim3((unsigned)M), dim3(256), 0, h->stream,
-			(const double *)b->rows, N, b->d_nv, b->d_sum, b->d_trunc);
-	HIPCHK(hipGetLastError());
-	static_assert(sizeof(long long) == sizeof(int64_t), "sum_trunc");
-	HIPCHK(hipMemcpyAsync(n_valid, b->d_nv, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(hipMemcpyAsync(sum, b->d_sum, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(hipMemcpyAsync(sum_trunc, b->d_trunc, M * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(hipStreamSynchronize(h->stream));
-	b->M = M;
-	return SGX_OK;
+	return dsblock_counts(h, b, M, n_valid, sum, sum_trunc);
+}
+
+// The same block from packed-real rows as the file stores them (kern_unpack.h): raw chunks land in the pipeline's two
+// input buffers on the copy stream and are decoded and sample-selected into the block's float64 rows on the handle's
+// stream meanwhile.  The counts are those of sgx_dsblock_load on the decoded rows.
+extern "C" int sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const void *raw, int cls, size_t n_file_samp,
+	double scale, double offset, const int32_t *sel, size_t M, int32_t *n_valid, double *sum, int64_t *sum_trunc)
+{
+	int rc = dsblock_check(h, b, "sgx_ds_block_load_packed");
+	if (rc) return rc;
+	if (b->dtype != SGX_DS_F64) return fail(SGX_EINVAL, "sgx_ds_block_load_packed: packed-real rows need a float64 block");
+	rc = packed_check("sgx_ds_block_load_packed", b->N, raw, cls, n_file_samp, sel);
+	if (rc) return rc;
+	if (!n_valid || !sum || !sum_trunc) return fail(SGX_EINVAL, "sgx_ds_block_load_packed: NULL buffer");
+	if (M == 0 || M > b->cap) return fail(SGX_EINVAL, "sgx_ds_block_load_packed: %zu variants, the block holds up to %zu", M, b->cap);
+	rc = sync_lane(h);                        // anything that still reads the block through this handle is done
+	if (rc) return rc;
+	b->M = 0;
+	PackedSrc pk;
+	pk.cls = cls; pk.esz = packed_esz(cls); pk.nfs = n_file_samp; pk.scale = scale; pk.offset = offset;
+	const size_t src_row = n_file_samp * pk.esz;
+	const size_t chunk = std::min(M, std::max<size_t>(1, (h->pipe_bytes ? h->pipe_bytes : PIPE_BYTES) / src_row));
+	rc = ensure_pipe(h, 0, 0, 1);
+	if (rc) return rc;
+	rc = ensure_packed(h, pk, sel, chunk * src_row);
+	if (rc) return rc;
+	const uint8_t *src = reinterpret_cast<const uint8_t *>(raw);
+	int i = 0;
+	for (size_t off = 0; off < M; off += chunk, i++) {
+		const size_t m = std::min(chunk, M - off);
+		const int k = i & 1;
+		if (i >= 2) HIPCHK(hipStreamWaitEvent(h->cstream, h->ev_done[k], 0));      // the buffer's previous chunk has been read
+		HIPCHK(hipMemcpyAsync(h->pipe_raw[k], src + off * src_row, m * src_row, hipMemcpyHostToDevice, h->cstream));
+		HIPCHK(hipEventRecord(h->ev_copy[k], h->cstream));
+		HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy[k], 0));      // (the selection went first on the same stream)
+		rc = launch_unpack(h->stream, pk, h->pipe_raw[k], b->N, m, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
+		if (rc) return rc;
+		HIPCHK(hipEventRecord(h->ev_done[k], h->stream));
+	}
+	HIPCHK(hipStreamSynchronize(h->cstream));
+	return dsblock_counts(h, b, M, n_valid, sum, sum_trunc);
 }
 
 // Single-variant test of every resident row.  The rows go to the dosage kernels in the chunks scan_host would cut

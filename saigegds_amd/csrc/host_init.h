@@ -392,11 +392,11 @@ extern "C" void sgx_free(sgx_handle *h)
 	(void)hipFree(h->mf_acc); (void)hipFree(h->seg4); (void)hipFree(h->scr5); (void)hipFree(h->cur5);
 	(void)hipFree(h->recs); (void)hipFree(h->counters); (void)hipFree(h->scratch);
 	for (int b = 0; b < 2; b++) {
-		(void)hipFree(h->pipe_in[b]); (void)hipFree(h->pipe_pk[b]); (void)hipFree(h->pipe_out[b]); (void)hipFree(h->pipe_valid[b]);
+		(void)hipFree(h->pipe_in[b]); (void)hipFree(h->pipe_pk[b]); (void)hipFree(h->pipe_raw[b]); (void)hipFree(h->pipe_out[b]); (void)hipFree(h->pipe_valid[b]);
 		if (h->pin_out[b]) (void)hipHostFree(h->pin_out[b]);
 		if (h->pin_valid[b]) (void)hipHostFree(h->pin_valid[b]);
 	}
-	(void)hipFree(h->pipe_flag);
+	(void)hipFree(h->pipe_flag); (void)hipFree(h->pk_sel);
 	if (h->h_pipe_flag) (void)hipHostFree(h->h_pipe_flag);
 	if (h->ev_h2d) (void)hipEventDestroy(h->ev_h2d);
 	for (int k = 0; k < 2; k++) { if (h->ev_copy[k]) (void)hipEventDestroy(h->ev_copy[k]); if (h->ev_done[k]) (void)hipEventDestroy(h->ev_done[k]); }

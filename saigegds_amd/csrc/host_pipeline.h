@@ -72,9 +72,83 @@ static int ensure_pipe(sgx_handle *h, size_t in_bytes, size_t pk_bytes, size_t M
 	return SGX_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Packed-real rows (kern_unpack.h): they cross PCIe as the file stores them -- 1, 2 or 4 bytes a sample, the file's
+// samples in the file's order -- and are decoded and sample-selected on the device into the float64 rows the dosage
+// kernels read.
+struct PackedSrc {
+	int cls = 0;                      // SGX_PR_*
+	size_t esz = 0, nfs = 0;          // bytes per value, samples per row of the file
+	double scale = 1, offset = 0;
+	const int *sel = nullptr;         // device copy of the selection (h->pk_sel) or nullptr
+};
+
+static size_t packed_esz(int cls)
+{
+	return cls == SGX_PR_U8 || cls == SGX_PR_I8 ? 1 : cls == SGX_PR_U16 || cls == SGX_PR_I16 ? 2 : cls == SGX_PR_F32 ? 4 : 0;
+}
+
+// the argument checks of sgx_scan_packed / sgx_ds_block_load_packed: nothing is launched on a bad argument
+static int packed_check(const char *who, int N, const void *raw, int cls, size_t nfs, const int32_t *sel)
+{
+	if (!packed_esz(cls)) return fail(SGX_EINVAL, "%s: unknown class %d", who, cls);
+	if (!raw) return fail(SGX_EINVAL, "%s: NULL buffer", who);
+	if (nfs < (size_t)N) return fail(SGX_EINVAL, "%s: n_file_samp = %zu < %d samples of the model", who, nfs, N);
+	if (!sel && nfs != (size_t)N)
+		return fail(SGX_EINVAL, "%s: n_file_samp = %zu but the model has %d samples and there is no selection", who, nfs, N);
+	if (sel) for (int i = 0; i < N; i++)
+		if (sel[i] < 0 || (size_t)sel[i] >= nfs)
+			return fail(SGX_EINVAL, "%s: sample index %d outside the file's %zu samples", who, sel[i], nfs);
+	return SGX_OK;
+}
+
+// the call's selection to the device (copy stream), the raw buffers of `bytes` each
+static int ensure_packed(sgx_handle *h, PackedSrc &pk, const int32_t *sel, size_t bytes)
+{
+	const size_t N = (size_t)h->md.N;
+	if (bytes > h->pipe_raw_cap) {
+		for (int b = 0; b < 2; b++) { if (h->pipe_raw[b]) HIPCHK(hipFree(h->pipe_raw[b])); h->pipe_raw[b] = nullptr; }
+		h->pipe_raw_cap = 0;
+		for (int b = 0; b < 2; b++) HIPCHK(hipMalloc((void **)&h->pipe_raw[b], bytes));
+		h->pipe_raw_cap = bytes;
+	}
+	pk.sel = nullptr;
+	if (!sel) return SGX_OK;
+	if (N > h->pk_sel_cap) {
+		if (h->pk_sel) HIPCHK(hipFree(h->pk_sel));
+		h->pk_sel = nullptr; h->pk_sel_cap = 0;
+		HIPCHK(hipMalloc((void **)&h->pk_sel, N * sizeof(int)));
+		h->pk_sel_cap = N;
+	}
+	static_assert(sizeof(int) == sizeof(int32_t), "sel");
+	HIPCHK(hipMemcpyAsync(h->pk_sel, sel, N * sizeof(int), hipMemcpyHostToDevice, h->cstream));
+	pk.sel = h->pk_sel;
+	return SGX_OK;
+}
+
+static int launch_unpack(hipStream_t st, const PackedSrc &pk, const void *raw_dev, int N, size_t m, double *out)
+{
+	// a thread: one sample of up to 4 rows (selection) or one 16-byte load of up to 4 rows
+	const size_t per_thread = pk.sel ? 1 : 16 / pk.esz, items = ((size_t)N + per_thread - 1) / per_thread + 1;
+	const dim3 g((unsigned)std::min<size_t>((items + 255) / 256, 4096), (unsigned)std::min<size_t>((m + 3) / 4, 65535));
+#define SGX_UNPACK(T) hipLaunchKernelGGL((unpack_real_rows<T>), g, dim3(256), 0, st, \
+		(const T *)raw_dev, pk.nfs, pk.sel, N, m, pk.scale, pk.offset, out)
+	switch (pk.cls) {
+	case SGX_PR_U8: SGX_UNPACK(uint8_t); break;
+	case SGX_PR_I8: SGX_UNPACK(int8_t); break;
+	case SGX_PR_U16: SGX_UNPACK(uint16_t); break;
+	case SGX_PR_I16: SGX_UNPACK(int16_t); break;
+	default: SGX_UNPACK(float); break;
+	}
+#undef SGX_UNPACK
+	HIPCHK(hipGetLastError());
+	return SGX_OK;
+}
+
+// pk: the rows are packed-real rows of src_row_bytes; dev_row_bytes is that of the float64 rows they become
 template <int INPUT>
 static int scan_host(sgx_handle *h, const void *rows, size_t src_row_bytes, size_t dev_row_bytes,
-	size_t M, double *out8, uint8_t *valid)
+	size_t M, double *out8, uint8_t *valid, PackedSrc *pk = nullptr, const int32_t *sel = nullptr)
 {
 	if (!h) return fail(SGX_EINVAL, "scan: NULL handle");
 	if (M == 0) return SGX_OK;
@@ -96,6 +170,7 @@ static int scan_host(sgx_handle *h, const void *rows, size_t src_row_bytes, size
 	if (rc) return rc;
 	rc = ensure_recs(h, chunk);
 	if (rc) return rc;
+	if (pk) { rc = ensure_packed(h, *pk, sel, chunk * src_row_bytes); if (rc) return rc; }
 	// 2-bit rows (as they come, or packed from hard calls) take the MFMA path, the lists of a chunk per pipeline buffer
 	const bool blocks = (INPUT == IN_2BIT || can_pack) && h->mf_ok && !h->force_v1;
 	if (blocks) for (int b = 0; b < 2; b++) { rc = ensure_tmp_block(h, b, chunk); if (rc) return rc; }
@@ -117,7 +192,11 @@ static int scan_host(sgx_handle *h, const void *rows, size_t src_row_bytes, size
 		const int b = i & 1;
 		// ---- chunk i over PCIe on the copy stream (buffer b was last used by chunk i - 2: done)
 		const uint8_t *src = reinterpret_cast<const uint8_t *>(rows) + off * src_row_bytes;
-		if (src_row_bytes == dev_row_bytes) {
+		if (pk) {
+			HIPCHK(hipMemcpyAsync(h->pipe_raw[b], src, m * src_row_bytes, hipMemcpyHostToDevice, h->cstream));
+			rc = launch_unpack(h->cstream, *pk, h->pipe_raw[b], N, m, reinterpret_cast<double *>(h->pipe_in[b]));
+			if (rc) return rc;
+		} else if (src_row_bytes == dev_row_bytes) {
 			HIPCHK(hipMemcpyAsync(h->pipe_in[b], src, m * dev_row_bytes, hipMemcpyHostToDevice, h->cstream));
 		} else {
 			if (dev_row_bytes > src_row_bytes) HIPCHK(hipMemsetAsync(h->pipe_in[b], 0, m * dev_row_bytes, h->cstream));
@@ -261,6 +340,17 @@ extern "C" int sgx_scan_f64(sgx_handle *h, const double *dosage, size_t M, doubl
 {
 	const size_t rb = h ? (size_t)h->md.N * sizeof(double) : 0;
 	return scan_host<IN_F64>(h, dosage, rb, rb, M, out8, valid);
+}
+
+extern "C" int sgx_scan_packed(sgx_handle *h, const void *raw, int cls, size_t n_file_samp, double scale, double offset,
+	const int32_t *sel, size_t M, double *out8, uint8_t *valid)
+{
+	if (!h) return fail(SGX_EINVAL, "sgx_scan_packed: NULL handle");
+	int rc = packed_check("sgx_scan_packed", h->md.N, raw, cls, n_file_samp, sel);
+	if (rc) return rc;
+	PackedSrc pk;
+	pk.cls = cls; pk.esz = packed_esz(cls); pk.nfs = n_file_samp; pk.scale = scale; pk.offset = offset;
+	return scan_host<IN_F64>(h, raw, n_file_samp * pk.esz, (size_t)h->md.N * sizeof(double), M, out8, valid, &pk, sel);
 }
 
 // Burden rows from 2-bit genotypes, then the single-variant test on each row

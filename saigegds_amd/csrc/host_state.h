@@ -97,6 +97,8 @@ struct sgx_handle {
 	size_t pipe_bytes = 0;            // test hook: chunk size of the pipeline (0 = PIPE_BYTES)
 	uint8_t *pipe_in[2] = {nullptr, nullptr}; size_t pipe_in_cap = 0;
 	uint8_t *pipe_pk[2] = {nullptr, nullptr}; size_t pipe_pk_cap = 0;       // packed 2-bit rows made on the device
+	uint8_t *pipe_raw[2] = {nullptr, nullptr}; size_t pipe_raw_cap = 0;     // packed-real rows as the file stores them (sgx_scan_packed)
+	int *pk_sel = nullptr; size_t pk_sel_cap = 0;                           // ... and the sample selection of the call
 	double *pipe_out[2] = {nullptr, nullptr}; uint8_t *pipe_valid[2] = {nullptr, nullptr}; size_t pipe_out_cap = 0;
 	double *pin_out[2] = {nullptr, nullptr}; uint8_t *pin_valid[2] = {nullptr, nullptr};   // pinned host
 	int *pipe_flag = nullptr, *h_pipe_flag = nullptr;

@@ -71,6 +71,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_burden.h"
 #include "kern_burden_ds.h"
 #include "kern_pack.h"
+#include "kern_unpack.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files

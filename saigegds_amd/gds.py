@@ -533,13 +533,49 @@ class GdsFile:
     def dosage_real_range(self, path: str, v0: int, v1: int) -> np.ndarray:
         """Rows [v0, v1) of a real-valued dosage node [M, N] (NaN = missing)."""
         nd = self.node(path + "/data")
+        self._check_one_value_per_variant(path, nd)
+        return np.asarray(self.read_rows(path + "/data", v0, v1), dtype=np.float64)
+
+    def _check_one_value_per_variant(self, path: str, nd):
+        """``@data`` of a format node holds the values per variant: a dosage node has one (checked once per node)."""
         if not getattr(nd, "_reps_ok", False):
             if self.node(path + "/@data", silent=True) is not None:
                 reps = np.asarray(self.read(path + "/@data")).reshape(-1)
                 if reps.size and not np.all(reps == 1):
                     raise GdsError(f"{path}: more than one value per variant")
             nd._reps_ok = True
-        return np.asarray(self.read_rows(path + "/data", v0, v1), dtype=np.float64)
+
+    RAW_DOSAGE_DTYPES = {"dPackedReal8U": np.uint8, "dPackedReal8": np.int8, "dPackedReal16U": "<u2", "dPackedReal16": "<i2",
+                   "dFloat32": "<f4"}
+
+    def dosage_raw_class(self, path: str) -> Optional[str]:
+        """The class of a dosage node if its rows can go to the device as stored (``dosage_raw_range``), else None."""
+        cls = self.node(path + "/data").cls or ""
+        return cls if cls in self.RAW_DOSAGE_DTYPES else None
+
+    def dosage_raw_row_bytes(self, path: str) -> int:
+        """Bytes of one stored row of such a node."""
+        nd = self.node(path + "/data")
+        return int(np.prod(nd.dims[1:])) * np.dtype(self.RAW_DOSAGE_DTYPES[nd.cls]).itemsize
+
+    def dosage_raw_range(self, path: str, v0: int, v1: int) -> Tuple[np.ndarray, str, float, float]:
+        """Rows [v0, v1) of a packed-real (or dFloat32) dosage node [M, N] AS STORED -> (raw, class, scale, offset):
+        the integers of dPackedReal8[U] / dPackedReal16[U] (the all-ones / most negative code = missing), nothing
+        decoded.  dosage = raw * scale + offset (two roundings) gives ``dosage_real_range`` bit for bit; float32 rows
+        are widened as they are (scale 1, offset 0 are returned and not to be applied)."""
+        nd = self.node(path + "/data")
+        cls = nd.cls or ""
+        if cls not in self.RAW_DOSAGE_DTYPES:
+            raise GdsError(f"{path}: {cls!r} is not a packed-real or float32 node")
+        self._check_one_value_per_variant(path, nd)
+        dims = tuple(nd.dims or ())
+        dt = np.dtype(self.RAW_DOSAGE_DTYPES[cls])
+        per = int(np.prod(dims[1:])) if len(dims) > 1 else 1
+        data = self.raw_range(path + "/data", v0 * per * dt.itemsize, v1 * per * dt.itemsize)
+        raw = np.frombuffer(data, dtype=dt).reshape((v1 - v0,) + dims[1:])
+        if cls == "dFloat32":
+            return raw, cls, 1.0, 0.0
+        return raw, cls, float(nd.scale), float(nd.offset)
 
     def dosage_real(self, path: str = "annotation/format/DS") -> np.ndarray:
         """Real-valued dosages [M, N] (NaN = missing) from a format node."""
