@@ -239,6 +239,29 @@ int sgx_scan_f64(sgx_handle *h, const double *dosage, size_t n_variants,
 int sgx_scan_packed(sgx_handle *h, const void *raw, int cls, size_t n_file_samp, double scale, double offset,
 	const int32_t *sel, size_t n_variants, double *out8, uint8_t *valid);
 
+/* Hard calls in HOST memory as a SeqArray file stores genotype/data (dBit2 [row][sample][ploidy]): per sample one
+ * nibble, allele a0 in bits 0-1 and a1 in bits 2-3, n_file_samp samples a row -- the FILE's samples in the file's
+ * order -- and the rows back to back in one bit stream, so with an odd n_file_samp every other row starts in the
+ * middle of a byte.  alleles: the bytes that hold the variants' rows; the first row starts at bit `bit0` (0 or 4) of
+ * the first byte.  n_rows: NULL (one row per variant) or the rows of each variant (genotype/@data; 1 to 16: a site of
+ * more than three alleles takes several rows, the base-4 digits of the allele index, least significant first; an
+ * allele is missing when all its digits are 3 and non-reference when any digit is non-zero and it is not missing).
+ * sel: NULL (then n_file_samp must equal the model's n_samp) or n_samp indices into the file's samples in the
+ * MODEL's order, each checked against [0, n_file_samp).  The rows cross PCIe as stored, 4 bits a sample, and are
+ * folded into the 2-bit rows of sgx_scan_2bit on the device, by the rule of sgx_decode_dbit2: code 3 if an allele is
+ * missing, else the number of non-reference alleles.
+ *   sgx_scan_dbit2        chunks of as many variants as sgx_scan_2bit's (2-bit rows of the device stride per
+ *                         "pipe_mb"); the raw chunk i + 1 crosses the link while chunk i is decoded and scanned.
+ *                         out8 / valid equal sgx_scan_2bit on sgx_decode_dbit2's rows bit for bit.
+ *   sgx_block_load_dbit2  sgx_block_load of the same rows: the loaded block gives the same sgx_scan_block tables
+ *                         bit for bit, with the same readiness guarantee.
+ * A bad argument (NULL buffer, bit0 other than 0 and 4, n_file_samp < n_samp, no sel with n_file_samp != n_samp, an
+ * index out of range, n_rows[j] < 1 or > 16) returns SGX_EINVAL and launches nothing; the handle stays usable. */
+int sgx_scan_dbit2(sgx_handle *h, const uint8_t *alleles, size_t bit0, size_t n_file_samp,
+	const int32_t *n_rows, const int32_t *sel, size_t n_variants, double *out8, uint8_t *valid);
+int sgx_block_load_dbit2(sgx_handle *h, sgx_block *b, const uint8_t *alleles, size_t bit0, size_t n_file_samp,
+	const int32_t *n_rows, const int32_t *sel, size_t n_variants);
+
 /* Aggregate tests: n_rows burden rows from 2-bit genotypes in HOST memory, then the
  * single-variant test on every row (replaces ds_mat_burden + single_test_bin/quant inside
  * saige_burden_test_*, saige_acatv_test_bin and saige_acato_test_bin, src/saige_main.cpp:526-976).

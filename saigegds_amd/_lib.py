@@ -22,6 +22,7 @@ EXPORTS = (
     "sgx_grm_crossprod_multi", "sgx_grm_crossprod_multi_dev", "sgx_grm_pcg_multi",
     "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
     "sgx_scan_packed", "sgx_ds_block_load_packed",
+    "sgx_scan_dbit2", "sgx_block_load_dbit2",
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
@@ -49,6 +50,29 @@ def _packed_args(raw, cls, n, sel):
             raise ValueError(f"Invalid length of dosages: {sel.size}.")
         sel = np.clip(sel, -1, np.iinfo(np.int32).max).astype(np.int32)     # (out of int32's range stays out of range)
     return raw, code, sel
+
+
+def _dbit2_args(alleles, bit0, n_file_samp, n_rows, sel, n, n_variants):
+    """Checks of the sizes ctypes cannot see -> (alleles, n_rows or None, sel or None, m); the values are checked in C."""
+    a = np.frombuffer(alleles, dtype=np.uint8) if not isinstance(alleles, np.ndarray) else alleles
+    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    if n_rows is not None:
+        n_rows = np.ascontiguousarray(np.clip(n_rows, -1, np.iinfo(np.int32).max), dtype=np.int32).reshape(-1)
+        if n_variants is not None and int(n_variants) != n_rows.size:
+            raise ValueError("n_rows must hold one count per variant")
+        m, rows = n_rows.size, int(np.clip(n_rows, 0, None).sum(dtype=np.int64))
+    else:
+        if n_variants is None:
+            raise ValueError("give n_variants or n_rows")
+        m = rows = int(n_variants)
+    if a.size < (int(bit0) + rows * int(n_file_samp) * 4 + 7) // 8:
+        raise ValueError("allele buffer too short")
+    if sel is not None:
+        sel = np.ascontiguousarray(sel)
+        if sel.shape != (n,):
+            raise ValueError(f"Invalid length of dosages: {sel.size}.")
+        sel = np.clip(sel, -1, np.iinfo(np.int32).max).astype(np.int32)     # (out of int32's range stays out of range)
+    return a, n_rows, sel, m
 
 
 class SgxError(RuntimeError):
@@ -168,6 +192,10 @@ def load():
     L.sgx_dsblock_load.argtypes = [vp, vp, vp, sz, vp, vp, vp]
     L.sgx_scan_packed.restype = C.c_int
     L.sgx_scan_packed.argtypes = [vp, vp, C.c_int, sz, dp, dp, vp, sz, vp, vp]
+    L.sgx_scan_dbit2.restype = C.c_int
+    L.sgx_scan_dbit2.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp]
+    L.sgx_block_load_dbit2.restype = C.c_int
+    L.sgx_block_load_dbit2.argtypes = [vp, vp, vp, sz, sz, vp, vp, sz]
     L.sgx_ds_block_load_packed.restype = C.c_int
     L.sgx_ds_block_load_packed.argtypes = [vp, vp, vp, C.c_int, sz, dp, dp, vp, sz, vp, vp, vp]
     L.sgx_dsblock_scan.restype = C.c_int
@@ -317,6 +345,19 @@ class Scanner:
                                       valid.ctypes.data))
         return out, valid
 
+    def scan_dbit2(self, alleles, bit0: int, n_file_samp: int, n_rows=None, sel=None, n_variants: int = None):
+        """``genotype/data`` rows as the file stores them (``sgx_scan_dbit2``; ``GdsFile.genotype_raw_range``): the
+        bytes that hold the variants' dBit2 rows from bit ``bit0`` of the first byte on, ``n_file_samp`` samples a row.
+        ``n_rows``: None (one row per variant, ``n_variants`` of them) or the rows of each variant.  ``sel``: None (the
+        file's samples are the model's) or the model's samples as indices into the file's.  Decoded on the device;
+        equals ``scan_2bit`` of ``decode_dbit2``'s rows bit for bit."""
+        a, n_rows, sel, m = _dbit2_args(alleles, bit0, n_file_samp, n_rows, sel, self.n, n_variants)
+        out, valid = self._out(m)
+        check(self._L.sgx_scan_dbit2(self._h, a.ctypes.data, int(bit0), int(n_file_samp),
+                                     None if n_rows is None else n_rows.ctypes.data, None if sel is None else sel.ctypes.data,
+                                     m, out.ctypes.data, valid.ctypes.data))
+        return out, valid
+
     def burden_2bit(self, packed: np.ndarray, row_ptr, var_idx, lut):
         """Burden rows (CSR over the rows of ``packed``, one 4-entry table per entry), then the
         single-variant test on each row (``sgx_burden_2bit``)."""
@@ -409,6 +450,14 @@ class Block:
             check(self._L.sgx_block_create_ex(int(n_samp), int(max_variants), int(device), int(clist_avg), C.byref(b)))
         self._b = b
         self.n, self.cap = int(n_samp), int(max_variants)
+
+    def load_dbit2(self, sc: "Scanner", alleles, bit0: int, n_file_samp: int, n_rows=None, sel=None, n_variants: int = None):
+        """``genotype/data`` rows as the file stores them -> block, decoded on the device (``sgx_block_load_dbit2``;
+        arguments as ``Scanner.scan_dbit2``): the block ``Scanner.load_block`` makes of the host-decoded rows."""
+        a, n_rows, sel, m = _dbit2_args(alleles, bit0, n_file_samp, n_rows, sel, self.n, n_variants)
+        check(self._L.sgx_block_load_dbit2(sc._h, self._b, a.ctypes.data, int(bit0), int(n_file_samp),
+                                           None if n_rows is None else n_rows.ctypes.data,
+                                           None if sel is None else sel.ctypes.data, m))
 
     @staticmethod
     def nbytes(n_samp: int, max_variants: int) -> int:

@@ -24,8 +24,9 @@ PACKED_BLOCK_BYTES = 1 << 30   # host bytes of one block of packed-real rows as 
 
 
 def packed_block_size(raw_row_bytes: int) -> int:
-    """Variants per block on the packed-real route: .bl_size, but no more than a GiB of stored rows -- a block is
-    read and held whole on the host, and at N = 430 000 a 16-bit row is 0.86 MB (50 000 of them: 43 GB)."""
+    """Variants per block on the stored-rows routes (packed-real dosages, genotype/data): .bl_size, but no more than a
+    GiB of stored rows -- a block is read and held whole on the host, and at N = 430 000 a 16-bit row is 0.86 MB
+    (50 000 of them: 43 GB), a row of allele codes 215 kB (10.75 GB)."""
     return min(BLOCK_SIZE, max(1, PACKED_BLOCK_BYTES // int(raw_row_bytes)))
 
 
@@ -44,6 +45,31 @@ class PackedRows:
 
     def args(self):
         return self.raw, self.cls, self.scale, self.offset, self.sel
+
+
+# Where the allele codes of genotype/data become 2-bit dosage rows: "device" -- the stored rows cross PCIe as they are
+# and sgx_scan_dbit2 decodes and sample-selects them; "host" -- dosage_alt_packed_range (sgx_decode_dbit2 on the host's
+# threads), then sgx_scan_2bit.  Same table either way, bit for bit.
+GENOTYPE_DECODE = "device"
+MAX_STORED_ROWS = 16      # SGX_DBIT2_MAX_ROWS: stored rows of one variant sgx_scan_dbit2 takes; a block with a wider site is decoded on the host
+
+
+class StoredGenotypes:
+    """Rows of genotype/data as stored (``GdsFile.genotype_raw_range``) with what the device needs to decode them: the
+    bit the first row starts at, the file's samples per row, the rows per variant (None: one each) and the model's
+    samples as indices into the file's (None: the file's samples are the model's, in order).  What
+    ``Scanner.scan_dbit2`` / ``Block.load_dbit2`` take."""
+
+    def __init__(self, raw: np.ndarray, bit0: int, n_file_samp: int, n_rows: Optional[np.ndarray], sel: Optional[np.ndarray],
+                 n_variants: int):
+        self.raw, self.bit0, self.n_file_samp, self.n_rows, self.sel, self.n_variants = raw, bit0, n_file_samp, n_rows, sel, n_variants
+
+    @property
+    def nbytes(self) -> int:
+        return self.raw.nbytes
+
+    def args(self):
+        return self.raw, self.bit0, self.n_file_samp, self.n_rows, self.sel, self.n_variants
 
 
 class GenotypeSource:
@@ -129,6 +155,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     if verbose:
         print("SAIGE association analysis:")
 
+    if GENOTYPE_DECODE not in ("device", "host"):
+        raise ValueError("saigegds_amd.assoc.GENOTYPE_DECODE should be 'device' or 'host'.")
     mod: NullModel = load_modobj(modobj, verbose)
     src = _open_source(gdsfile, verbose)
     node = _dsnode(src, dsnode)
@@ -183,6 +211,11 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
                 return blk
             blk = src.dosage[off:end]
             return blk if all_samples else np.ascontiguousarray(blk[:, sel])
+        if kind == "packed" and GENOTYPE_DECODE == "device":
+            raw, bit0, reps = src.genotype_raw_range(off, end)
+            if reps is not None and int(reps.max()) > MAX_STORED_ROWS:      # (the host decoder has no such limit)
+                return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
+            return StoredGenotypes(raw, bit0, n_all, reps, None if all_samples else sel, end - off)
         if kind == "packed":
             return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
         if kind == "stored":
@@ -212,6 +245,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     bl_size = BLOCK_SIZE
     if kind == "stored":
         bl_size = packed_block_size(src.dosage_raw_row_bytes(node))
+    elif kind == "packed" and not isinstance(src, GenotypeSource) and GENOTYPE_DECODE == "device":
+        bl_size = packed_block_size(src.genotype_raw_row_bytes())      # a stored row is twice a 2-bit row
     blocks = [(off, min(n_var, off + bl_size)) for off in range(0, n_var, bl_size)]
     t_loop = time.perf_counter()
     scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, read_block, kind == "packed", out, valid, timing)
@@ -283,7 +318,9 @@ def scan_blocks(make_scanner, ngpu: int, blocks, read_block, packed_rows: bool, 
                     rng = take()                                       # the next block decodes while this one is scanned
                     fut = ex.submit(decode, rng) if rng is not None else None
                     t = time.perf_counter()
-                    if packed_rows:
+                    if isinstance(blk, StoredGenotypes):
+                        o, v = sc.scan_dbit2(*blk.args())   # genotype/data rows as stored: decoded on the device
+                    elif packed_rows:
                         o, v = sc.scan_2bit(blk)            # 2-bit packed rows
                     elif isinstance(blk, PackedRows):
                         o, v = sc.scan_packed(*blk.args())  # packed-real rows as stored: decoded on the device

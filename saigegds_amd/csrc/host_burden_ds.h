@@ -145,7 +145,7 @@ extern "C" int sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const voi
 	const size_t chunk = std::min(M, std::max<size_t>(1, (h->pipe_bytes ? h->pipe_bytes : PIPE_BYTES) / src_row));
 	rc = ensure_pipe(h, 0, 0, 1);
 	if (rc) return rc;
-	rc = ensure_packed(h, pk, sel, chunk * src_row);
+	rc = ensure_packed(h, pk.sel, sel, chunk * src_row);
 	if (rc) return rc;
 	const uint8_t *src = reinterpret_cast<const uint8_t *>(raw);
 	int i = 0;

@@ -396,7 +396,7 @@ extern "C" void sgx_free(sgx_handle *h)
 		if (h->pin_out[b]) (void)hipHostFree(h->pin_out[b]);
 		if (h->pin_valid[b]) (void)hipHostFree(h->pin_valid[b]);
 	}
-	(void)hipFree(h->pipe_flag); (void)hipFree(h->pk_sel);
+	(void)hipFree(h->pipe_flag); (void)hipFree(h->pk_sel); (void)hipFree(h->db2_row0);
 	if (h->h_pipe_flag) (void)hipHostFree(h->h_pipe_flag);
 	if (h->ev_h2d) (void)hipEventDestroy(h->ev_h2d);
 	for (int k = 0; k < 2; k++) { if (h->ev_copy[k]) (void)hipEventDestroy(h->ev_copy[k]); if (h->ev_done[k]) (void)hipEventDestroy(h->ev_done[k]); }

@@ -103,7 +103,7 @@ static int packed_check(const char *who, int N, const void *raw, int cls, size_t
 }
 
 // the call's selection to the device (copy stream), the raw buffers of `bytes` each
-static int ensure_packed(sgx_handle *h, PackedSrc &pk, const int32_t *sel, size_t bytes)
+static int ensure_packed(sgx_handle *h, const int *&sel_dev, const int32_t *sel, size_t bytes)
 {
 	const size_t N = (size_t)h->md.N;
 	if (bytes > h->pipe_raw_cap) {
@@ -112,7 +112,7 @@ static int ensure_packed(sgx_handle *h, PackedSrc &pk, const int32_t *sel, size_
 		for (int b = 0; b < 2; b++) HIPCHK(hipMalloc((void **)&h->pipe_raw[b], bytes));
 		h->pipe_raw_cap = bytes;
 	}
-	pk.sel = nullptr;
+	sel_dev = nullptr;
 	if (!sel) return SGX_OK;
 	if (N > h->pk_sel_cap) {
 		if (h->pk_sel) HIPCHK(hipFree(h->pk_sel));
@@ -122,7 +122,7 @@ static int ensure_packed(sgx_handle *h, PackedSrc &pk, const int32_t *sel, size_
 	}
 	static_assert(sizeof(int) == sizeof(int32_t), "sel");
 	HIPCHK(hipMemcpyAsync(h->pk_sel, sel, N * sizeof(int), hipMemcpyHostToDevice, h->cstream));
-	pk.sel = h->pk_sel;
+	sel_dev = h->pk_sel;
 	return SGX_OK;
 }
 
@@ -145,14 +145,104 @@ static int launch_unpack(hipStream_t st, const PackedSrc &pk, const void *raw_de
 	return SGX_OK;
 }
 
+// ---------------------------------------------------------------------------
+// genotype/data rows (kern_dbit2.h): the dBit2 allele codes cross PCIe as the file stores them -- 4 bits a sample, the
+// file's samples in the file's order, rows back to back in one bit stream -- and are folded into 2-bit dosage rows and
+// sample-selected on the device.
+struct Dbit2Src {
+	const uint8_t *alleles = nullptr;
+	size_t nib0 = 0, nfs = 0;         // nibble of the first byte the first row starts at; samples per row of the file
+	std::vector<unsigned> row0;       // [M + 1] row offsets where a variant of the call has more than one row, else empty
+	const int *sel = nullptr;         // device copies (h->pk_sel, h->db2_row0) or nullptr
+	const unsigned *row0_dev = nullptr;
+	size_t row_of(size_t j) const { return row0.empty() ? j : row0[j]; }
+	// variants [off, off + m): the bytes that hold them, the nibble of the first byte they start at
+	void span(size_t off, size_t m, size_t &byte0, size_t &bytes, unsigned &nib) const
+	{
+		const size_t a = nib0 + row_of(off) * nfs, b = nib0 + row_of(off + m) * nfs;
+		byte0 = a >> 1; bytes = ((b + 1) >> 1) - byte0; nib = (unsigned)(a & 1);
+	}
+};
+
+#define SGX_DBIT2_MAX_ROWS 16     /* rows of one variant: allele indices below 4^16 */
+
+// the argument checks of sgx_scan_dbit2 / sgx_block_load_dbit2 (as packed_check: nothing is launched on a bad argument)
+static int dbit2_check(const char *who, int N, const uint8_t *alleles, size_t bit0, size_t nfs, const int32_t *n_rows,
+	const int32_t *sel, size_t M, Dbit2Src &db)
+{
+	if (!alleles) return fail(SGX_EINVAL, "%s: NULL buffer", who);
+	if (bit0 != 0 && bit0 != 4) return fail(SGX_EINVAL, "%s: bit0 = %zu, must be 0 or 4", who, bit0);
+	if (nfs < (size_t)N) return fail(SGX_EINVAL, "%s: n_file_samp = %zu < %d samples of the model", who, nfs, N);
+	if (!sel && nfs != (size_t)N)
+		return fail(SGX_EINVAL, "%s: n_file_samp = %zu but the model has %d samples and there is no selection", who, nfs, N);
+	if (sel) for (int i = 0; i < N; i++)
+		if (sel[i] < 0 || (size_t)sel[i] >= nfs)
+			return fail(SGX_EINVAL, "%s: sample index %d outside the file's %zu samples", who, sel[i], nfs);
+	if (M > 0xFFFFFFFFu / SGX_DBIT2_MAX_ROWS) return fail(SGX_EINVAL, "%s: too many variants in one call", who);
+	bool multi = false;
+	if (n_rows) for (size_t j = 0; j < M; j++) {
+		if (n_rows[j] < 1 || n_rows[j] > SGX_DBIT2_MAX_ROWS)
+			return fail(SGX_EINVAL, "%s: n_rows[%zu] = %d, a variant has 1 to %d rows", who, j, n_rows[j], SGX_DBIT2_MAX_ROWS);
+		multi |= n_rows[j] > 1;
+	}
+	db.alleles = alleles; db.nib0 = bit0 / 4; db.nfs = nfs;
+	db.row0.clear();
+	if (multi) {
+		db.row0.resize(M + 1);
+		db.row0[0] = 0;
+		for (size_t j = 0; j < M; j++) db.row0[j + 1] = db.row0[j] + (unsigned)n_rows[j];
+	}
+	return SGX_OK;
+}
+
+// the call's selection and row offsets to the device (copy stream), the raw buffers for chunks of `chunk` variants
+static int dbit2_prepare(sgx_handle *h, Dbit2Src &db, const int32_t *sel, size_t M, size_t chunk)
+{
+	size_t need = 0;
+	for (size_t off = 0; off < M; off += chunk) {
+		size_t byte0, bytes; unsigned nib;
+		db.span(off, std::min(chunk, M - off), byte0, bytes, nib);
+		need = std::max(need, bytes);
+	}
+	int rc = ensure_packed(h, db.sel, sel, need);
+	if (rc) return rc;
+	db.row0_dev = nullptr;
+	if (db.row0.empty()) return SGX_OK;
+	if (M + 1 > h->db2_row0_cap) {
+		if (h->db2_row0) HIPCHK(hipFree(h->db2_row0));
+		h->db2_row0 = nullptr; h->db2_row0_cap = 0;
+		HIPCHK(hipMalloc((void **)&h->db2_row0, (M + 1) * sizeof(unsigned)));
+		h->db2_row0_cap = M + 1;
+	}
+	HIPCHK(hipMemcpyAsync(h->db2_row0, db.row0.data(), (M + 1) * sizeof(unsigned), hipMemcpyHostToDevice, h->cstream));   // (db outlives the call's chunks)
+	db.row0_dev = h->db2_row0;
+	return SGX_OK;
+}
+
+// variants [off, off + m) of the call from their raw bytes on the device -> m rows of out_stride bytes
+static int launch_dbit2(hipStream_t st, const Dbit2Src &db, const uint8_t *raw_dev, size_t off, size_t m, int N, uint8_t *out, size_t out_stride)
+{
+	size_t byte0, bytes; unsigned nib;
+	db.span(off, m, byte0, bytes, nib);
+	// a thread: one output dword of the variants of its stride (selection) or 8 output bytes of one variant
+	const size_t items = out_stride / (db.sel ? 4 : 8);
+	const dim3 g((unsigned)std::min<size_t>((items + 255) / 256, 4096), (unsigned)std::min<size_t>(m, db.sel ? 64 : 65535));
+	hipLaunchKernelGGL(decode_dbit2_rows, g, dim3(256), 0, st, raw_dev, bytes, nib, db.nfs,
+		db.row0_dev ? db.row0_dev + off : (const unsigned *)nullptr, (unsigned)db.row_of(off), db.sel, N, m, out, out_stride);
+	HIPCHK(hipGetLastError());
+	return SGX_OK;
+}
+
 // pk: the rows are packed-real rows of src_row_bytes; dev_row_bytes is that of the float64 rows they become
+// db: the rows are genotype/data rows (src_row_bytes unused); dev_row_bytes is that of the 2-bit rows they become
 template <int INPUT>
 static int scan_host(sgx_handle *h, const void *rows, size_t src_row_bytes, size_t dev_row_bytes,
-	size_t M, double *out8, uint8_t *valid, PackedSrc *pk = nullptr, const int32_t *sel = nullptr)
+	size_t M, double *out8, uint8_t *valid, PackedSrc *pk = nullptr, const int32_t *sel = nullptr, Dbit2Src *db = nullptr)
 {
 	if (!h) return fail(SGX_EINVAL, "scan: NULL handle");
 	if (M == 0) return SGX_OK;
 	if (!rows || !out8 || !valid) return fail(SGX_EINVAL, "scan: NULL buffer");
+	if (db && dev_row_bytes % 8 != 0) return fail(SGX_EINVAL, "scan: row stride %zu", dev_row_bytes);
 	int rc = set_dev(h);
 	if (rc) return rc;
 	rc = sync_lane(h);                        // anything queued on this handle before is done
@@ -170,7 +260,8 @@ static int scan_host(sgx_handle *h, const void *rows, size_t src_row_bytes, size
 	if (rc) return rc;
 	rc = ensure_recs(h, chunk);
 	if (rc) return rc;
-	if (pk) { rc = ensure_packed(h, *pk, sel, chunk * src_row_bytes); if (rc) return rc; }
+	if (pk) { rc = ensure_packed(h, pk->sel, sel, chunk * src_row_bytes); if (rc) return rc; }
+	if (db) { rc = dbit2_prepare(h, *db, sel, M, chunk); if (rc) return rc; }
 	// 2-bit rows (as they come, or packed from hard calls) take the MFMA path, the lists of a chunk per pipeline buffer
 	const bool blocks = (INPUT == IN_2BIT || can_pack) && h->mf_ok && !h->force_v1;
 	if (blocks) for (int b = 0; b < 2; b++) { rc = ensure_tmp_block(h, b, chunk); if (rc) return rc; }
@@ -192,7 +283,14 @@ static int scan_host(sgx_handle *h, const void *rows, size_t src_row_bytes, size
 		const int b = i & 1;
 		// ---- chunk i over PCIe on the copy stream (buffer b was last used by chunk i - 2: done)
 		const uint8_t *src = reinterpret_cast<const uint8_t *>(rows) + off * src_row_bytes;
-		if (pk) {
+		if (db) {
+			size_t byte0, bytes; unsigned nib;
+			db->span(off, m, byte0, bytes, nib);
+			// (belt and braces: harvest() of chunk i - 1 has synchronised the lane, so the decoder of chunk i - 2, the last
+			// reader of this raw buffer, is done already; the wait keeps the reuse safe should the harvest ever move)
+			if (i >= 2) HIPCHK(hipStreamWaitEvent(h->cstream, h->ev_done[b], 0));
+			HIPCHK(hipMemcpyAsync(h->pipe_raw[b], db->alleles + byte0, bytes, hipMemcpyHostToDevice, h->cstream));
+		} else if (pk) {
 			HIPCHK(hipMemcpyAsync(h->pipe_raw[b], src, m * src_row_bytes, hipMemcpyHostToDevice, h->cstream));
 			rc = launch_unpack(h->cstream, *pk, h->pipe_raw[b], N, m, reinterpret_cast<double *>(h->pipe_in[b]));
 			if (rc) return rc;
@@ -234,6 +332,14 @@ static int scan_host(sgx_handle *h, const void *rows, size_t src_row_bytes, size
 		// link idled a fifth of the time (43 GB/s; the next copy now starts as this one ends).
 		HIPCHK(hipStreamWaitEvent(h->stream, h->ev_h2d, 0));
 		HIPCHK(hipStreamWaitEvent(h->hstream, h->ev_h2d, 0));
+		if (db) {
+			// the raw chunk -> 2-bit rows, on the compute stream too (the link goes on with chunk i + 1 meanwhile); the
+			// score chain of a block scan runs on the lane's other stream and waits for the rows
+			rc = launch_dbit2(h->stream, *db, h->pipe_raw[b], off, m, N, h->pipe_in[b], dev_row_bytes);
+			if (rc) return rc;
+			HIPCHK(hipEventRecord(h->ev_done[b], h->stream));
+			HIPCHK(hipStreamWaitEvent(h->hstream, h->ev_done[b], 0));
+		}
 		if (as_block) rc = scan_rows_dev(h, b, INPUT == IN_2BIT ? h->pipe_in[b] : h->pipe_pk[b], INPUT == IN_2BIT ? dev_row_bytes : pk_row, m,
 			h->pipe_out[b], h->pipe_valid[b], false);
 		else if (INPUT == IN_2BIT) rc = launch_scan<IN_2BIT>(h, h->pipe_in[b], dev_row_bytes, m, h->pipe_out[b], h->pipe_valid[b]);
@@ -315,6 +421,53 @@ extern "C" int sgx_block_load(sgx_handle *h, sgx_block *b, const uint8_t *packed
 	return SGX_OK;
 }
 
+// The same block from genotype/data rows as the file stores them (kern_dbit2.h): raw chunks cross PCIe on the copy
+// stream and are decoded on the handle's stream into the rows block_put_rows reads, in sgx_block_load's chunks.
+extern "C" int sgx_block_load_dbit2(sgx_handle *h, sgx_block *b, const uint8_t *alleles, size_t bit0, size_t n_file_samp,
+	const int32_t *n_rows, const int32_t *sel, size_t M)
+{
+	if (!h || !b) return fail(SGX_EINVAL, "sgx_block_load_dbit2: NULL argument");
+	if (b->lists_only) return fail(SGX_EINVAL, "sgx_block_load_dbit2: not a resident block");
+	if (b->device != h->device) return fail(SGX_EINVAL, "sgx_block_load_dbit2: block and handle are on different devices");
+	if (b->N != h->md.N) return fail(SGX_EINVAL, "sgx_block_load_dbit2: the block holds rows of %d samples, the model has %d", b->N, h->md.N);
+	if (M == 0 || M > b->cap) return fail(SGX_EINVAL, "sgx_block_load_dbit2: %zu variants, the block holds up to %zu", M, b->cap);
+	Dbit2Src db;
+	int rc = dbit2_check("sgx_block_load_dbit2", b->N, alleles, bit0, n_file_samp, n_rows, sel, M, db);
+	if (rc) return rc;
+	rc = set_dev(h);
+	if (rc) return rc;
+	const size_t dev_row = (size_t)b->ntile * 64;
+	size_t chunk = std::max<size_t>(16, ((h->pipe_bytes ? h->pipe_bytes : PIPE_BYTES) / dev_row) & ~(size_t)15);
+	chunk = std::min(chunk, (M + 15) & ~(size_t)15);
+	rc = ensure_pipe(h, chunk * dev_row, 0, 1);
+	if (rc) return rc;
+	rc = dbit2_prepare(h, db, sel, M, chunk);
+	if (rc) return rc;
+	rc = block_begin_load(h, b, h->stream);
+	if (rc) return rc;
+	int i = 0;
+	for (size_t off = 0; off < M; off += chunk, i++) {
+		const size_t m = std::min(chunk, M - off);
+		const int k = i & 1;
+		size_t byte0, bytes; unsigned nib;
+		db.span(off, m, byte0, bytes, nib);
+		if (i >= 2) HIPCHK(hipStreamWaitEvent(h->cstream, h->ev_done[k], 0));      // the buffers' previous chunk has been read
+		HIPCHK(hipMemcpyAsync(h->pipe_raw[k], alleles + byte0, bytes, hipMemcpyHostToDevice, h->cstream));
+		HIPCHK(hipEventRecord(h->ev_copy[k], h->cstream));
+		HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy[k], 0));      // (the selection and the row offsets went first on the same stream)
+		rc = launch_dbit2(h->stream, db, h->pipe_raw[k], off, m, b->N, h->pipe_in[k], dev_row);
+		if (rc) return rc;
+		rc = block_put_rows(b, h->pipe_in[k], dev_row, off, m, h->stream);
+		if (rc) return rc;
+		HIPCHK(hipEventRecord(h->ev_done[k], h->stream));
+	}
+	rc = block_finish(b, M, h->stream);
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(h->cstream));      // the caller's buffers are free
+	HIPCHK(hipStreamSynchronize(h->stream));
+	return SGX_OK;
+}
+
 extern "C" int sgx_scan_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t M,
 	double *out8, uint8_t *valid)
 {
@@ -351,6 +504,16 @@ extern "C" int sgx_scan_packed(sgx_handle *h, const void *raw, int cls, size_t n
 	PackedSrc pk;
 	pk.cls = cls; pk.esz = packed_esz(cls); pk.nfs = n_file_samp; pk.scale = scale; pk.offset = offset;
 	return scan_host<IN_F64>(h, raw, n_file_samp * pk.esz, (size_t)h->md.N * sizeof(double), M, out8, valid, &pk, sel);
+}
+
+extern "C" int sgx_scan_dbit2(sgx_handle *h, const uint8_t *alleles, size_t bit0, size_t n_file_samp, const int32_t *n_rows,
+	const int32_t *sel, size_t M, double *out8, uint8_t *valid)
+{
+	if (!h) return fail(SGX_EINVAL, "sgx_scan_dbit2: NULL handle");
+	Dbit2Src db;
+	int rc = dbit2_check("sgx_scan_dbit2", h->md.N, alleles, bit0, n_file_samp, n_rows, sel, M, db);
+	if (rc) return rc;
+	return scan_host<IN_2BIT>(h, alleles, 0, sgx_row_stride(h->md.N), M, out8, valid, nullptr, sel, &db);
 }
 
 // Burden rows from 2-bit genotypes, then the single-variant test on each row

@@ -97,8 +97,9 @@ struct sgx_handle {
 	size_t pipe_bytes = 0;            // test hook: chunk size of the pipeline (0 = PIPE_BYTES)
 	uint8_t *pipe_in[2] = {nullptr, nullptr}; size_t pipe_in_cap = 0;
 	uint8_t *pipe_pk[2] = {nullptr, nullptr}; size_t pipe_pk_cap = 0;       // packed 2-bit rows made on the device
-	uint8_t *pipe_raw[2] = {nullptr, nullptr}; size_t pipe_raw_cap = 0;     // packed-real rows as the file stores them (sgx_scan_packed)
+	uint8_t *pipe_raw[2] = {nullptr, nullptr}; size_t pipe_raw_cap = 0;     // rows as the file stores them (sgx_scan_packed, sgx_scan_dbit2)
 	int *pk_sel = nullptr; size_t pk_sel_cap = 0;                           // ... and the sample selection of the call
+	unsigned *db2_row0 = nullptr; size_t db2_row0_cap = 0;                  // sgx_scan_dbit2: row offsets of the call's variants (multi-row sites)
 	double *pipe_out[2] = {nullptr, nullptr}; uint8_t *pipe_valid[2] = {nullptr, nullptr}; size_t pipe_out_cap = 0;
 	double *pin_out[2] = {nullptr, nullptr}; uint8_t *pin_valid[2] = {nullptr, nullptr};   // pinned host
 	int *pipe_flag = nullptr, *h_pipe_flag = nullptr;

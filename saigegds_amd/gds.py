@@ -481,6 +481,26 @@ class GdsFile:
             res[a:b, :nb] = pack_dosage_2bit(codes)
         return res if res.shape[1] == nb else res
 
+    def genotype_raw_row_bytes(self) -> int:
+        """Bytes of one stored row of genotype/data (4 bits a sample; rows of an odd number of samples share a byte)."""
+        return (self.genotype_dims()[1] * 4 + 7) // 8
+
+    def genotype_raw_range(self, v0: int, v1: int):
+        """The rows of variants [v0, v1) of genotype/data AS STORED -> (bytes uint8, bit0, n_rows): the bytes that hold
+        them, the bit of the first byte the first row starts at (0 or 4), and the rows per variant (None: one each).
+        Nothing is decoded: ``sgx_decode_dbit2`` on the host or ``sgx_scan_dbit2`` on the device fold the allele codes
+        into ``dosage_alt_packed_range``'s rows."""
+        M, N = self.genotype_dims()
+        v0, v1 = max(0, v0), min(M, v1)
+        nd = self.node("genotype/data")
+        if v1 <= v0:
+            return np.zeros(0, dtype=np.uint8), 0, None
+        ra, rb = int(nd._row0[v0]), int(nd._row0[v1])
+        bits0, bits1 = ra * N * 4, rb * N * 4
+        data = np.frombuffer(self.raw_range("genotype/data", bits0 // 8, (bits1 + 7) // 8), dtype=np.uint8)
+        reps = None if rb - ra == v1 - v0 else np.diff(nd._row0[v0:v1 + 1]).astype(np.int32)
+        return data, bits0 % 8, reps
+
     def _dosage_alt_multirow(self, v0, v1, sample_sel, out, chunk_bytes):
         """The range holds sites of more than three alleles: through the allele indices (numpy; such sites are
         rare, so this path is not tuned).  Runs of single-row variants inside the range take the fast path."""
