@@ -77,7 +77,7 @@ static int grm_matvec_dev(sgx_grm *g, const double *b, double *out)
 	grid = grm_mfma_grid(g, N, g->tbM.ntile, &tps);
 	hipLaunchKernelGGL((score_mfma_kernel<1, false, true>), grid, dim3(WAVE * MF_WAVES), lds, st, g->Gt, g->bpvM, g->N, g->tbM, tps, g->accS, GRM_NACC);
 	hipLaunchKernelGGL(grm_out_epilogue, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g->N, M, g->accS,
-		g->maxb + 1, g->maxb + 2, C0, out);
+		g->maxb + 1, g->maxb + 2, C0, g->diag, out);
 	HIPCHK(hipGetLastError());
 	return SGX_OK;
 }
@@ -430,7 +430,7 @@ static int grm_matvec_multi_dev(sgx_grm *g, GrmMulti *s, const double *B, size_t
 			HIPCHK(hipMemsetAsync(s->accS, 0, N * 32 * nb2 * sizeof(int), st));
 			grm_mfma_dispatch(g, nb2, g->Gt, g->bpvM, g->N, s->FlM, g->tbM.ntile, s->accS);
 			hipLaunchKernelGGL(grm_out_epilogue_multi, dim3((unsigned)((N + 255) / 256), sc.n), bl, 0, st, g->N, M, nb2,
-				s->accS, mb, c0s, Out, ldo, oc);
+				s->accS, mb, c0s, g->diag, Out, ldo, oc);
 			HIPCHK(hipGetLastError());
 		}
 	}

@@ -201,9 +201,19 @@ grm_dot_epilogue(size_t M, const int *__restrict__ acc, const unsigned long long
 }
 
 // ---- pass-2 epilogue: out_i = (C0 + X_i - Gam_i) / M
+// A sample without a single non-zero standardised genotype (every code missing or on a monomorphic
+// marker: diag_i == 0, a sum of squares) has out_i = 0 as a sum of zero terms, and the reference's
+// loop gives exactly that; C0 + X_i - Gam_i only cancels to rounding level there.  0 * v keeps a
+// NaN or infinity of b visible, as 0 * dot does in the reference (:507-519).
+__device__ __forceinline__ double grm_out_value(double C0, double X, double G, size_t M, double diag_i)
+{
+	const double v = (C0 + X - G) / (double)M;
+	return (diag_i == 0) ? 0 * v : v;
+}
+
 __global__ void __launch_bounds__(256)
 grm_out_epilogue(int N, size_t M, const int *__restrict__ acc, const unsigned long long *__restrict__ maxx,
-	const unsigned long long *__restrict__ maxg, double C0, double *__restrict__ out)
+	const unsigned long long *__restrict__ maxg, double C0, const double *__restrict__ diag, double *__restrict__ out)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= N) return;
@@ -211,7 +221,7 @@ grm_out_epilogue(int N, size_t M, const int *__restrict__ acc, const unsigned lo
 	const int *a = acc + (size_t)i * GRM_NACC;
 	const double X = ldexp(hl_to_double(mf_limbs(a)), -ex);                       // code plane x x limbs
 	const double G = ldexp(hl_to_double(mf_limbs(a + GRM_NCOL + MF_NLIMB)), -eg);  // missing plane x gam limbs
-	out[i] = (C0 + X - G) / (double)M;
+	out[i] = grm_out_value(C0, X, G, M, diag[i]);
 }
 
 // ---- vector kernels of PCG_diag_sigma (:581-614)
@@ -376,7 +386,7 @@ grm_dot_epilogue_multi(size_t M, int nbfv, const int *__restrict__ acc, const un
 // grm_out_epilogue per column y of a pass-2 launch with nbfv fragments (one column per fragment)
 __global__ void __launch_bounds__(256)
 grm_out_epilogue_multi(int N, size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
-	GrmScal C0, double *__restrict__ Out, size_t ldo, GrmCols cols)
+	GrmScal C0, const double *__restrict__ diag, double *__restrict__ Out, size_t ldo, GrmCols cols)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	const int y = blockIdx.y;
@@ -385,7 +395,7 @@ grm_out_epilogue_multi(int N, size_t M, int nbfv, const int *__restrict__ acc, c
 	const int *a = acc + (size_t)i * (32 * nbfv) + 16 * y;
 	const double X = ldexp(hl_to_double(mf_limbs(a)), -ex);
 	const double G = ldexp(hl_to_double(mf_limbs(a + 16 * nbfv + MF_NLIMB)), -eg);
-	Out[(size_t)cols.c[y] * ldo + i] = (C0.v[y] + X - G) / (double)M;
+	Out[(size_t)cols.c[y] * ldo + i] = grm_out_value(C0.v[y], X, G, M, diag[i]);
 }
 
 // ---- PCG_diag_sigma vector kernels per column (blockIdx.y); w and minv are shared
