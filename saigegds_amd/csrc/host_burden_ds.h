@@ -95,36 +95,30 @@ extern "C" int sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosag
 	if (rc) return rc;
 	b->M = 0;
 	const int N = b->N;
-	const size_t src_row = (size_t)N * (b->dtype == SGX_DS_U8 ? 1 : b->dtype == SGX_DS_I32 ? sizeof(int32_t) : sizeof(double));
-	const size_t chunk = std::min(M, std::max<size_t>(1, (h->pipe_bytes ? h->pipe_bytes : PIPE_BYTES) / src_row));
-	const uint8_t *src = reinterpret_cast<const uint8_t *>(dosage);
+	RowSrc src = plain_rows(dosage, (size_t)N * (b->dtype == SGX_DS_U8 ? 1 : b->dtype == SGX_DS_I32 ? sizeof(int32_t) : sizeof(double)));
+	const size_t chunk = scan_chunk(h, src.row_bytes, M);
 	if (b->dtype != SGX_DS_I32) {
 		for (size_t off = 0; off < M; off += chunk)
-			HIPCHK(hipMemcpyAsync(b->rows + off * b->row_bytes, src + off * src_row, std::min(chunk, M - off) * src_row,
+			HIPCHK(hipMemcpyAsync(b->rows + off * b->row_bytes, src.rows + off * src.row_bytes, std::min(chunk, M - off) * src.row_bytes,
 				hipMemcpyHostToDevice, h->stream));
 	} else {
-		rc = ensure_pipe(h, chunk * src_row, 0, 1);
+		rc = ensure_pipe(h, chunk * src.row_bytes, 0, 1);
 		if (rc) return rc;
-		int i = 0;
-		for (size_t off = 0; off < M; off += chunk, i++) {
-			const size_t m = std::min(chunk, M - off);
-			const int k = i & 1;
-			if (i >= 2) HIPCHK(hipStreamWaitEvent(h->cstream, h->ev_done[k], 0));      // the buffer's previous chunk has been read
-			HIPCHK(hipMemcpyAsync(h->pipe_in[k], src + off * src_row, m * src_row, hipMemcpyHostToDevice, h->cstream));
-			HIPCHK(hipEventRecord(h->ev_copy[k], h->cstream));
-			HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy[k], 0));
-			hipLaunchKernelGGL(i32_rows_to_f64, dim3(1024), dim3(256), 0, h->stream,
-				(const int *)h->pipe_in[k], m * (size_t)N, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipEventRecord(h->ev_done[k], h->stream));
-		}
-		HIPCHK(hipStreamSynchronize(h->cstream));
+		rc = ingest(h, M, chunk,
+			[&](int k, size_t off, size_t m) -> int { return src_upload(h, src, k, off, m, src.row_bytes); },
+			[&](int k, size_t off, size_t m) -> int {
+				hipLaunchKernelGGL(i32_rows_to_f64, dim3(1024), dim3(256), 0, h->stream,
+					(const int *)h->pipe_in[k], m * (size_t)N, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
+				HIPCHK(hipGetLastError());
+				return SGX_OK;
+			});
+		if (rc) return rc;
 	}
 	return dsblock_counts(h, b, M, n_valid, sum, sum_trunc);
 }
 
 // The same block from packed-real rows as the file stores them (kern_unpack.h): raw chunks land in the pipeline's two
-// input buffers on the copy stream and are decoded and sample-selected into the block's float64 rows on the handle's
+// raw buffers on the copy stream and are decoded and sample-selected into the block's float64 rows on the handle's
 // stream meanwhile.  The counts are those of sgx_dsblock_load on the decoded rows.
 extern "C" int sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const void *raw, int cls, size_t n_file_samp,
 	double scale, double offset, const int32_t *sel, size_t M, int32_t *n_valid, double *sum, int64_t *sum_trunc)
@@ -132,43 +126,32 @@ extern "C" int sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const voi
 	int rc = dsblock_check(h, b, "sgx_ds_block_load_packed");
 	if (rc) return rc;
 	if (b->dtype != SGX_DS_F64) return fail(SGX_EINVAL, "sgx_ds_block_load_packed: packed-real rows need a float64 block");
-	rc = packed_check("sgx_ds_block_load_packed", b->N, raw, cls, n_file_samp, sel);
+	RowSrc src;
+	rc = packed_check("sgx_ds_block_load_packed", b->N, raw, cls, n_file_samp, scale, offset, sel, src);
 	if (rc) return rc;
 	if (!n_valid || !sum || !sum_trunc) return fail(SGX_EINVAL, "sgx_ds_block_load_packed: NULL buffer");
 	if (M == 0 || M > b->cap) return fail(SGX_EINVAL, "sgx_ds_block_load_packed: %zu variants, the block holds up to %zu", M, b->cap);
 	rc = sync_lane(h);                        // anything that still reads the block through this handle is done
 	if (rc) return rc;
 	b->M = 0;
-	PackedSrc pk;
-	pk.cls = cls; pk.esz = packed_esz(cls); pk.nfs = n_file_samp; pk.scale = scale; pk.offset = offset;
-	const size_t src_row = n_file_samp * pk.esz;
-	const size_t chunk = std::min(M, std::max<size_t>(1, (h->pipe_bytes ? h->pipe_bytes : PIPE_BYTES) / src_row));
+	const size_t chunk = scan_chunk(h, src.row_bytes, M);
 	rc = ensure_pipe(h, 0, 0, 1);
 	if (rc) return rc;
-	rc = ensure_packed(h, pk.sel, sel, chunk * src_row);
+	rc = src_prepare(h, src, M, chunk);
 	if (rc) return rc;
-	const uint8_t *src = reinterpret_cast<const uint8_t *>(raw);
-	int i = 0;
-	for (size_t off = 0; off < M; off += chunk, i++) {
-		const size_t m = std::min(chunk, M - off);
-		const int k = i & 1;
-		if (i >= 2) HIPCHK(hipStreamWaitEvent(h->cstream, h->ev_done[k], 0));      // the buffer's previous chunk has been read
-		HIPCHK(hipMemcpyAsync(h->pipe_raw[k], src + off * src_row, m * src_row, hipMemcpyHostToDevice, h->cstream));
-		HIPCHK(hipEventRecord(h->ev_copy[k], h->cstream));
-		HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy[k], 0));      // (the selection went first on the same stream)
-		rc = launch_unpack(h->stream, pk, h->pipe_raw[k], b->N, m, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
-		if (rc) return rc;
-		HIPCHK(hipEventRecord(h->ev_done[k], h->stream));
-	}
-	HIPCHK(hipStreamSynchronize(h->cstream));
+	rc = ingest(h, M, chunk,
+		[&](int k, size_t off, size_t m) -> int { return copy_raw(h, src, k, off, m); },
+		[&](int k, size_t off, size_t m) -> int {
+			return launch_unpack(h->stream, src, h->pipe_raw[k], b->N, m, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
+		});
+	if (rc) return rc;
 	return dsblock_counts(h, b, M, n_valid, sum, sum_trunc);
 }
 
-// Single-variant test of every resident row.  The rows go to the dosage kernels in the chunks scan_host would cut
-// the same host buffer into (the tiled score kernel splits the samples by the number of rows of a launch, so the
-// same chunks give the same sums): results equal sgx_scan_u8 / _i32 / _f64 on rows that take the dosage kernels
-// there bit for bit.  Hard-call u8 / i32 rows are NOT packed to 2-bit here (the host-buffer scans do that): they
-// take the dosage kernels too, and agree with the fixed-point kernels within the scan's tolerance.
+// Single-variant test of every resident row, in scan_chunk's chunks: results equal sgx_scan_u8 / _i32 / _f64 on rows
+// that take the dosage kernels there bit for bit.  Hard-call u8 / i32 rows are NOT packed to 2-bit here (the
+// host-buffer scans do that): they take the dosage kernels too, and agree with the fixed-point kernels within the
+// scan's tolerance.
 extern "C" int sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out8, uint8_t *valid)
 {
 	int rc = dsblock_check(h, b, "sgx_dsblock_scan");
@@ -180,7 +163,7 @@ extern "C" int sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out
 	h->last_issued = h;
 	const size_t N = (size_t)b->N, M = b->M;
 	const size_t per_row = b->dtype == SGX_DS_U8 ? N : b->dtype == SGX_DS_I32 ? N * (sizeof(int32_t) + sizeof(double)) : N * sizeof(double);
-	const size_t chunk = std::min(M, std::max<size_t>(1, (h->pipe_bytes ? h->pipe_bytes : PIPE_BYTES) / per_row));
+	const size_t chunk = scan_chunk(h, per_row, M);
 	rc = ensure_stage(h, 0, chunk);
 	if (rc) return rc;
 	rc = ensure_recs(h, chunk);
@@ -189,14 +172,9 @@ extern "C" int sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out
 	for (size_t off = 0; off < M; off += chunk) {
 		const size_t m = std::min(chunk, M - off);
 		const uint8_t *rows = b->rows + off * b->row_bytes;
-		if (b->dtype == SGX_DS_U8) rc = launch_scan<IN_U8>(h, rows, b->row_bytes, m, h->stage_out, h->stage_valid);
-		else rc = launch_scan<IN_F64>(h, rows, b->row_bytes, m, h->stage_out, h->stage_valid);
+		if (b->dtype == SGX_DS_U8) rc = scan_staged<IN_U8>(h, rows, b->row_bytes, m, out8 + off * 8, valid + off, total);
+		else rc = scan_staged<IN_F64>(h, rows, b->row_bytes, m, out8 + off * 8, valid + off, total);
 		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(out8 + off * 8, h->stage_out, m * 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipMemcpyAsync(valid + off, h->stage_valid, m, hipMemcpyDeviceToHost, h->stream));
-		rc = sgx_sync(h);
-		if (rc) return rc;
-		stats_add(total, h->stats);
 	}
 	h->stats = total;
 	return SGX_OK;
@@ -237,13 +215,11 @@ extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_
 	if (n_cols < 1 || n_cols > SGX_DS_MAX_COLS)
 		return fail(SGX_EINVAL, "sgx_dsblock_burden: n_cols = %d, 1 .. %d are supported", n_cols, SGX_DS_MAX_COLS);
 	if (b->M == 0) return fail(SGX_EINVAL, "sgx_dsblock_burden: nothing loaded");
+	const int32_t *bad;
+	rc = csr_check("sgx_dsblock_burden", "grp_ptr", n_groups, grp_ptr, var_idx, b->M, &bad);
+	if (rc) return rc;
+	if (bad) return fail(SGX_EINVAL, "sgx_dsblock_burden: variant index %d outside the block's %zu rows", *bad, b->M);
 	const int64_t nnz = grp_ptr[n_groups];
-	if (grp_ptr[0] != 0 || nnz < 0) return fail(SGX_EINVAL, "sgx_dsblock_burden: bad grp_ptr");
-	for (size_t g = 0; g < n_groups; g++)
-		if (grp_ptr[g + 1] < grp_ptr[g]) return fail(SGX_EINVAL, "sgx_dsblock_burden: grp_ptr not ascending");
-	for (int64_t e = 0; e < nnz; e++)
-		if (var_idx[e] < 0 || (size_t)var_idx[e] >= b->M)
-			return fail(SGX_EINVAL, "sgx_dsblock_burden: variant index %d outside the block's %zu rows", var_idx[e], b->M);
 	rc = sync_lane(h);
 	if (rc) return rc;
 	h->last_issued = h;
@@ -254,13 +230,8 @@ extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_
 	const size_t o_w = (o_idx + ne * sizeof(int) + 15) & ~(size_t)15;
 	const size_t o_mw = o_w + ne * (size_t)n_cols * sizeof(double);
 	const size_t o_flip = o_mw + ne * (size_t)n_cols * sizeof(double);
-	const size_t need = o_flip + ne;
-	if (need > bm->tabs_cap) {
-		if (bm->tabs) HIPCHK(hipFree(bm->tabs));
-		bm->tabs = nullptr; bm->tabs_cap = 0;
-		HIPCHK(hipMalloc((void **)&bm->tabs, need));
-		bm->tabs_cap = need;
-	}
+	rc = grow(bm->tabs, bm->tabs_cap, o_flip + ne);
+	if (rc) return rc;
 	std::vector<long long> gp(grp_ptr, grp_ptr + n_groups + 1);
 	HIPCHK(hipMemcpyAsync(b->tabs, gp.data(), gp.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
 	if (nnz > 0) {
@@ -295,13 +266,8 @@ extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_
 					d_w, d_mw, reinterpret_cast<double *>(h->stage_in));
 			HIPCHK(hipGetLastError());
 		}
-		rc = launch_scan<IN_F64>(h, h->stage_in, row_bytes, m, h->stage_out, h->stage_valid);
+		rc = scan_staged<IN_F64>(h, h->stage_in, row_bytes, m, out8 + off * n_cols * 8, valid + off * n_cols, total);
 		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(out8 + off * n_cols * 8, h->stage_out, m * 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipMemcpyAsync(valid + off * n_cols, h->stage_valid, m, hipMemcpyDeviceToHost, h->stream));
-		rc = sgx_sync(h);
-		if (rc) return rc;
-		stats_add(total, h->stats);
 	}
 	h->stats = total;
 	return SGX_OK;

@@ -418,32 +418,21 @@ static int ensure_recs(sgx_handle *h, size_t n)
 {
 	if (n <= h->recs_cap) return SGX_OK;
 	HIPCHK(hipStreamSynchronize(h->stream));
-	if (h->recs) HIPCHK(hipFree(h->recs));
-	if (h->fallback) HIPCHK(hipFree(h->fallback));
-	h->recs = nullptr; h->fallback = nullptr; h->recs_cap = 0;
-	HIPCHK(hipMalloc((void **)&h->recs, 3 * n * sizeof(SpaRec)));   // tier ranges A and B (+ handed-on copies), exact range (dev_common.h)
-	HIPCHK(hipMalloc((void **)&h->fallback, n * sizeof(int)));
-	if (!h->md.quant) {
-		if (h->fb_spa2) HIPCHK(hipFree(h->fb_spa2));
-		h->fb_spa2 = nullptr;
+	h->recs_cap = 0;
+	int rc = renew(h->recs, 3 * n);          // tier ranges A and B (+ handed-on copies), exact range (dev_common.h)
+	if (!rc) rc = renew(h->fallback, n);
+	if (!rc && !h->md.quant) {
 		h->nseg = (h->md.N + spa_seg(h->md.K) - 1) / spa_seg(h->md.K);
-		HIPCHK(hipMalloc((void **)&h->fb_spa2, n * sizeof(int)));
-		if (h->fb_x2) HIPCHK(hipFree(h->fb_x2));
-		h->fb_x2 = nullptr;
-		HIPCHK(hipMalloc((void **)&h->fb_x2, n * sizeof(int)));
-		if (h->seg4) HIPCHK(hipFree(h->seg4));
-		h->seg4 = nullptr;
+		rc = renew(h->fb_spa2, n);
+		if (!rc) rc = renew(h->fb_x2, n);
 		// flagged variants per round of the series SPA stage: a block of the usual 50 000 variants in one
 		// round (a second, normally empty round costs four kernel launches per step)
 		h->vcap4 = (int)std::min<size_t>(n, 65536);
 		h->nround4 = (int)((n + h->vcap4 - 1) / h->vcap4);
-		HIPCHK(hipMalloc((void **)&h->seg4, (size_t)h->nseg * SPA4_NSMAX * h->vcap4 * sizeof(double)));
+		if (!rc) rc = renew(h->seg4, (size_t)h->nseg * SPA4_NSMAX * h->vcap4);
 	}
-	if (h->mf_ok) {
-		if (h->mf_acc) HIPCHK(hipFree(h->mf_acc));
-		h->mf_acc = nullptr;
-		HIPCHK(hipMalloc((void **)&h->mf_acc, n * (size_t)(2 * h->mfe.acc_stride - 16) * sizeof(int)));   // (three-plane form: 2 NBF - 1 fragment slots)
-	}
+	if (!rc && h->mf_ok) rc = renew(h->mf_acc, n * (size_t)(2 * h->mfe.acc_stride - 16));   // (three-plane form: 2 NBF - 1 fragment slots)
+	if (rc) return rc;
 	h->recs_cap = n;
 	return SGX_OK;
 }

@@ -8,11 +8,7 @@ static int ensure_buf(sgx_handle *h, T **p, size_t *cap, size_t need)
 	HIPCHK(hipStreamSynchronize(h->stream));
 	if (h->hstream) HIPCHK(hipStreamSynchronize(h->hstream));
 	if (h->s3_side) HIPCHK(hipStreamSynchronize(h->s3_side));
-	if (*p) HIPCHK(hipFree(*p));
-	*p = nullptr; *cap = 0;
-	HIPCHK(hipMalloc((void **)p, need * sizeof(T)));
-	*cap = need;
-	return SGX_OK;
+	return grow(*p, *cap, need);
 }
 
 // The shapes of the contraction kernel's forms (kern_score3.h): [0] two planes, [1] three planes; entries in table order

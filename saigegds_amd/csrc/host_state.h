@@ -92,19 +92,25 @@ struct sgx_handle {
 	double *scratch = nullptr; size_t scratch_stride = 0; int spa_grid = 0;
 	// host-pointer staging
 	uint8_t *stage_in = nullptr; size_t stage_in_cap = 0;
-	// pipelined host-buffer scans (scan_host): two input buffers, results through pinned memory
-	hipStream_t cstream = nullptr;    // copies of the block that is NOT being computed
-	size_t pipe_bytes = 0;            // test hook: chunk size of the pipeline (0 = PIPE_BYTES)
-	uint8_t *pipe_in[2] = {nullptr, nullptr}; size_t pipe_in_cap = 0;
-	uint8_t *pipe_pk[2] = {nullptr, nullptr}; size_t pipe_pk_cap = 0;       // packed 2-bit rows made on the device
-	uint8_t *pipe_raw[2] = {nullptr, nullptr}; size_t pipe_raw_cap = 0;     // rows as the file stores them (sgx_scan_packed, sgx_scan_dbit2)
-	int *pk_sel = nullptr; size_t pk_sel_cap = 0;                           // ... and the sample selection of the call
-	unsigned *db2_row0 = nullptr; size_t db2_row0_cap = 0;                  // sgx_scan_dbit2: row offsets of the call's variants (multi-row sites)
+	// Host rows to the device (host_pipeline.h; created by ensure_pipe on first use): chunk i + 1 crosses PCIe on the
+	// copy stream into one buffer of each pair while chunk i, in the other, is read on this handle's streams.
+	hipStream_t cstream = nullptr;    // the copy stream: what brings a chunk into its buffers (RowSrc: src_upload)
+	size_t pipe_bytes = 0;            // "pipe_mb" option: device bytes of a chunk's rows (0 = PIPE_BYTES)
+	//  the chunk's rows, by pipeline buffer
+	uint8_t *pipe_in[2] = {nullptr, nullptr}; size_t pipe_in_cap = 0;       // as the kernels read them (copied, or decoded from pipe_raw)
+	uint8_t *pipe_raw[2] = {nullptr, nullptr}; size_t pipe_raw_cap = 0;     // as the file stores them (SRC_PACKED, SRC_DBIT2)
+	uint8_t *pipe_pk[2] = {nullptr, nullptr}; size_t pipe_pk_cap = 0;       // scans: 2-bit rows packed from hard-call u8 / i32 rows
+	int *pipe_flag = nullptr, *h_pipe_flag = nullptr;                       // ... and whether every row of the chunk was one (pinned copy)
+	//  of a call with a stored source (src_prepare)
+	int *pk_sel = nullptr; size_t pk_sel_cap = 0;                           // the sample selection
+	unsigned *db2_row0 = nullptr; size_t db2_row0_cap = 0;                  // SRC_DBIT2: row offsets of the variants (multi-row sites)
+	//  scans: a chunk's results on the device and in pinned host memory, one cap
 	double *pipe_out[2] = {nullptr, nullptr}; uint8_t *pipe_valid[2] = {nullptr, nullptr}; size_t pipe_out_cap = 0;
-	double *pin_out[2] = {nullptr, nullptr}; uint8_t *pin_valid[2] = {nullptr, nullptr};   // pinned host
-	int *pipe_flag = nullptr, *h_pipe_flag = nullptr;
-	hipEvent_t ev_h2d = nullptr;
-	hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};   // sgx_block_load: chunk copied / chunk read
+	double *pin_out[2] = {nullptr, nullptr}; uint8_t *pin_valid[2] = {nullptr, nullptr};
+	//  events
+	hipEvent_t ev_h2d = nullptr;      // scans: the chunk is in its buffers; this handle's two streams wait for it
+	hipEvent_t ev_copy[2] = {nullptr, nullptr};   // loaders (ingest): the same per buffer; the handle's stream waits for it
+	hipEvent_t ev_done[2] = {nullptr, nullptr};   // behind what reads a buffer on the handle's stream: the copy of the chunk after next waits for it
 	uint8_t *stage_pk = nullptr; size_t stage_pk_cap = 0;   // burden: packed rows, CSR and tables
 	double *ds_part = nullptr; size_t ds_part_cap = 0;       // dosage score kernels: per-split partial sums
 	double *stage_out = nullptr; uint8_t *stage_valid = nullptr; size_t stage_out_cap = 0;
@@ -149,5 +155,39 @@ struct sgx_handle {
 static int set_dev(sgx_handle *h)
 {
 	HIPCHK(hipSetDevice(h->device));
+	return SGX_OK;
+}
+
+// Workspace buffers grow and never shrink; what they held is not kept.  The caller sees to it that nothing queued
+// still uses the old buffer (hipFree itself waits for the device).
+// renew: p -> a fresh device buffer of n elements.  grow: the same where its cap elements do not hold n.
+template <class T>
+static int renew(T *&p, size_t n)
+{
+	if (p) HIPCHK(hipFree(p));
+	p = nullptr;
+	HIPCHK(hipMalloc((void **)&p, n * sizeof(T)));
+	return SGX_OK;
+}
+
+template <class T>
+static int grow(T *&p, size_t &cap, size_t n)
+{
+	if (n <= cap) return SGX_OK;
+	cap = 0;
+	int rc = renew(p, n);
+	if (rc) return rc;
+	cap = n;
+	return SGX_OK;
+}
+
+// the two buffers of the pipeline's pairs, one cap
+template <class T>
+static int grow2(T *(&p)[2], size_t &cap, size_t n)
+{
+	if (n <= cap) return SGX_OK;
+	cap = 0;
+	for (T *&q : p) { int rc = renew(q, n); if (rc) return rc; }
+	cap = n;
 	return SGX_OK;
 }

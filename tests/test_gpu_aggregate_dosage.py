@@ -124,6 +124,35 @@ def test_g2_block_scan_equals_host_buffer_scans(n):
             assert_table_close(out, valid, ref, ref_valid, what=f"N={n} hard calls {np.dtype(dtype)}")
 
 
+def test_g2_i32_block_loads_in_three_chunks():
+    """N = 1000, 600 int32 rows that are not all hard calls: pipe_mb = 1 is 262 rows of 4000 bytes, so the load cuts
+    chunks of 262, 262 and 76, the third into the pipeline buffer of the first.  Counts and table equal those of the
+    one-chunk load, and the table equals sgx_scan_i32 of the same rows at the same pipe_mb, all bit for bit."""
+    import torch  # noqa: F401
+    from saigegds_amd._lib import Scanner
+    n, m = 1000, 600
+    i32 = _as(_hard_calls(n, m, 6), np.int32)
+    i32[:, 0] = 5
+    assert m > 2 * ((1 << 20) // (4 * n))
+    got = {}
+    with Scanner(_model(n)) as sc:
+        try:
+            for pipe_mb in (0, 1):
+                sc.set_option("pipe_mb", pipe_mb)
+                with sc.dosage_block(np.int32, m) as blk:
+                    nv, sm, st = blk.load(i32)
+                    out, valid = blk.scan()
+                ref, ref_valid = sc.scan_i32(i32)
+                print("pipe_mb", pipe_mb, "valid", int(valid.sum()))
+                assert np.array_equal(valid, ref_valid) and np.array_equal(out, ref, equal_nan=True), pipe_mb
+                got[pipe_mb] = (nv, sm, st, out, valid)
+        finally:
+            sc.set_option("pipe_mb", 0)
+    assert got[0][4].sum() > m // 2
+    for a, b, what in zip(got[1], got[0], ("n_valid", "sum", "sum_trunc", "table", "valid")):
+        assert np.array_equal(a, b, equal_nan=(what in ("sum", "table"))), what
+
+
 def test_g3_c1_gds_file_on_the_device():
     import torch  # noqa: F401
     mod = R.golden_model()

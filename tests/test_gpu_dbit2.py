@@ -193,6 +193,43 @@ def test_d5_block(files):
                     assert np.array_equal(rm_valid, tabs["dev"][1])
 
 
+def test_d5_block_loads_in_three_chunks(files):
+    """pipe_mb = 1 is 4096 rows of the block's 256-byte stride: the 8400 variants of test_d4_chunks are loaded in three
+    chunks, the third into the pipeline buffer of the first.  load_block of the host-decoded rows and load_dbit2 of the
+    stored bytes then give, through scan_block, the table of the one-chunk load_block; each load is made twice in a row,
+    so that a call finds both buffers used by the one before."""
+    from saigegds_amd._lib import Block, Scanner
+    sm = scan_model("saige_model.npz")
+    with Scanner(sm, device=0) as sc:
+        try:
+            for n_file in (1000, 1037):
+                raw, bit0, n_rows, sel, ref_rows = _case(files, n_file, 1)
+                big, reps, m = D.tile(raw, bit0, n_file, n_rows, M, 28)
+                ref_big = np.ascontiguousarray(np.tile(ref_rows, (28, 1)))
+                assert m == 8400 > 2 * ((1 << 20) // sc.row_stride())
+                tabs = {}
+                for key, pipe_mb in (("host rows, one chunk", 0), ("host rows", 1), ("stored bytes", 1)):
+                    sc.set_option("pipe_mb", pipe_mb)
+                    with Block(1000, m) as blk:
+                        for _ in range(2):
+                            if key == "stored bytes":
+                                blk.load_dbit2(sc, big, 0, n_file, reps, sel, m)
+                            else:
+                                sc.load_block(blk, ref_big)
+                        assert blk.n_variants == 8400
+                        o, v = _dev_out(m)
+                        sc.scan_block(blk, o.data_ptr(), v.data_ptr())
+                        sc.sync()
+                    tabs[key] = (o.cpu().numpy(), v.cpu().numpy())
+                    print(n_file, key, "valid", int(tabs[key][1].sum()))
+                one = tabs["host rows, one chunk"]
+                assert one[1].sum() > 100
+                assert _same(*tabs["host rows"], *one), n_file
+                assert _same(*tabs["stored bytes"], *one), n_file
+        finally:
+            sc.set_option("pipe_mb", 0)
+
+
 def test_d6_golden_file_through_the_driver(golden_bin, monkeypatch):
     """seqAssocGLMM_SPA on grm1k_10k_snp.gds with GENOTYPE_DECODE = "device": the first 2 000 variants reproduce
     saige_pval.npz, and the table equals the "host" run bit for bit."""

@@ -154,10 +154,13 @@ def test_p3_assoc_100snp_through_the_stored_rows(monkeypatch):
 
 
 def test_p4_dosage_block_from_stored_rows():
-    """load_packed == load of the decoded rows: the three arrays, then scan() and burden() bit for bit."""
+    """load_packed == load of the decoded rows: the three arrays, then scan() and burden() bit for bit.  600 rows at
+    pipe_mb = 1: the float32 rows (4000 and 4412 bytes) are loaded in three chunks, 262 + 262 + 76 and 237 + 237 + 126,
+    the third into the pipeline buffer of the first; the 2-byte classes in two chunks, the 1-byte ones in one."""
     from saigegds_amd._lib import Scanner
     sm = scan_model("saige_model.npz", mac=0.0, maf=0.0, missing=1.0)
-    m, per = 300, 10
+    m, per = 600, 10
+    assert m > 2 * ((1 << 20) // (4 * 1103))
     codes, _ = P.golden_codes(m)
     x = P.dosages(m, 1000, 12, codes)
     rng = np.random.default_rng(3)
