@@ -343,6 +343,31 @@ int sgx_decode_dbit2(const uint8_t *alleles, size_t bit0, int32_t n_samp, size_t
 int sgx_geno_stats_2bit(const uint8_t *packed, size_t bytes_per_variant, int32_t n_samp,
 	size_t n_variants, int device, int32_t *n_valid, int32_t *allele_sum);
 
+/* GRM markers of the null-model fit from a file that holds only imputed dosages: the reference's default mode falls
+ * back to annotation/format/DS and rounds every dosage to a hard call (saige_get_sparse, src/saige_fitnull.cpp:273-288;
+ * R/saige_main.r:395-417).  raw: n_rows stored rows of n_file_samp values in HOST memory, cls / scale / offset / sel as
+ * for sgx_scan_packed (the five SGX_PR_* classes, dosage v = raw * scale + offset in two roundings, float32 widened as
+ * it is; sel: NULL or n_samp indices into the file's samples).  Per row, on GPU `device`:
+ *   packed_out  ceil(n_samp/4) bytes at packed_out + row * out_stride, four samples a byte LSB first, the codes of the
+ *               last byte's samples beyond n_samp 0 (bytes from ceil(n_samp/4) up to out_stride are left as they are):
+ *               code 3 where v is not finite, else r = round(v) (C's round: halves away from zero) if r is 0, 1 or 2,
+ *               else 3.  The range is decided in double (1e30f -> 3; -0.4 and -0.0 -> 0).  No flip to the minor allele:
+ *               the orientation stays the alt allele's, as for $dosage_alt rows.
+ *   n_valid, allele_sum   the codes other than 3 and their sum (the counts of sgx_geno_stats_2bit on the row)
+ *   ds_valid, ds_sum      the finite dosages before rounding and their sum: for the four integer classes
+ *               (double)(sum of the non-missing stored values, exact in 64 bits) * scale + ds_valid * offset, each
+ *               operation rounded once; for float32 a double sum in a fixed order (a thread's 16 samples in index order,
+ *               the lanes of a wave pairwise, then waves and blocks in index order).
+ * All five are the same bit for bit from run to run and do not depend on chunk_bytes: the rows cross PCIe as stored in
+ * chunks of chunk_bytes of raw rows (0 = 512 MiB; at least one row), chunk i + 1 uploading while chunk i is quantised
+ * and its rows come back.  Needs no model handle; synchronous.  n_rows == 0 succeeds and does nothing.  A bad argument
+ * (unknown cls, a NULL buffer, n_samp < 1, n_file_samp < n_samp, no sel with n_file_samp != n_samp, an index outside
+ * [0, n_file_samp), out_stride < ceil(n_samp/4)) returns SGX_EINVAL, launches nothing and writes nothing. */
+int sgx_quantize_packed(const void *raw, int cls, size_t n_file_samp, double scale, double offset,
+	const int32_t *sel, int32_t n_samp, size_t n_rows, int device, size_t chunk_bytes,
+	uint8_t *packed_out, size_t out_stride,
+	int32_t *n_valid, int32_t *allele_sum, int32_t *ds_valid, double *ds_sum);
+
 /* Tuning / test hooks (per handle; there are no process-wide switches): "spa_exact" (every flagged variant
  * through the exact exp/log SPA kernel instead of the cumulant series), "force_dense" (exact g_pos/g_neg
  * pass for every SPA variant), "score_v1" (FP64 gather score kernel instead of the MFMA path), "lanes"

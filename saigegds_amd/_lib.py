@@ -23,6 +23,7 @@ EXPORTS = (
     "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
     "sgx_scan_packed", "sgx_ds_block_load_packed",
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
+    "sgx_quantize_packed",
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
@@ -206,6 +207,8 @@ def load():
     L.sgx_decode_dbit2.argtypes = [vp, sz, C.c_int32, sz, vp, C.c_int32, vp, sz, C.c_int]
     L.sgx_geno_stats_2bit.restype = C.c_int
     L.sgx_geno_stats_2bit.argtypes = [vp, sz, C.c_int32, sz, C.c_int, vp, vp]
+    L.sgx_quantize_packed.restype = C.c_int
+    L.sgx_quantize_packed.argtypes = [vp, C.c_int, sz, dp, dp, vp, C.c_int32, sz, C.c_int, sz, vp, sz, vp, vp, vp, vp]
     L.sgx_set_option.restype = C.c_int
     L.sgx_set_option.argtypes = [vp, C.c_char_p, C.c_longlong]
     L.sgx_sync.restype = C.c_int
@@ -626,6 +629,25 @@ def geno_stats_2bit(packed: np.ndarray, n_samp: int, device: int = 0):
     check(L.sgx_geno_stats_2bit(packed.ctypes.data, packed.shape[1], int(n_samp), m, int(device),
                                 nv.ctypes.data, sm.ctypes.data))
     return nv, sm
+
+
+def quantize_packed(raw, cls, scale, offset, n_samp: int, sel=None, device: int = 0, chunk_bytes: int = 0):
+    """Stored dosage rows -> the 2-bit hard-call rows of the null-model fit and the marker filter's counts, on the GPU
+    (``sgx_quantize_packed``): ``raw`` [m, n_file_samp] of class ``cls`` as for ``Scanner.scan_packed``, ``sel``: the
+    ``n_samp`` samples wanted as indices into the file's, or None (all, in the file's order).  Returns (packed
+    [m, ceil(n_samp / 4)], n_valid, allele_sum, ds_valid, ds_sum): what ``gds.quantize_dosage_2bit`` states in numpy."""
+    L = load()
+    n_samp = int(n_samp)
+    raw, code, sel = _packed_args(raw, cls, n_samp, sel)
+    m = raw.shape[0]
+    packed = np.zeros((m, (max(n_samp, 0) + 3) // 4), dtype=np.uint8)
+    nv, sm, dv = (np.zeros(m, dtype=np.int32) for _ in range(3))
+    dsum = np.zeros(m, dtype=np.float64)
+    check(L.sgx_quantize_packed(raw.ctypes.data, code, raw.shape[1], float(scale), float(offset),
+                                None if sel is None else sel.ctypes.data, n_samp, m, int(device), int(chunk_bytes),
+                                packed.ctypes.data, packed.shape[1], nv.ctypes.data, sm.ctypes.data, dv.ctypes.data,
+                                dsum.ctypes.data))
+    return packed, nv, sm, dv, dsum
 
 
 class GrmOperator:

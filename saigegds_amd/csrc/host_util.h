@@ -104,6 +104,106 @@ extern "C" int sgx_geno_stats_2bit(const uint8_t *packed, size_t bpv, int32_t n_
 	return rc;
 }
 
+// What sgx_quantize_packed holds on the device, released on every way out
+struct QuantDev {
+	hipStream_t cstream = nullptr, stream = nullptr;
+	hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+	uint8_t *raw[2] = {nullptr, nullptr}, *out = nullptr;
+	int *sel = nullptr, *part = nullptr, *cnt = nullptr;
+	double *part_s = nullptr, *sum = nullptr;
+	~QuantDev()
+	{
+		if (cstream) (void)hipStreamSynchronize(cstream);
+		if (stream) (void)hipStreamSynchronize(stream);
+		for (int k = 0; k < 2; k++) {
+			if (ev_copy[k]) (void)hipEventDestroy(ev_copy[k]);
+			if (ev_done[k]) (void)hipEventDestroy(ev_done[k]);
+			(void)hipFree(raw[k]);
+		}
+		(void)hipFree(out); (void)hipFree(sel); (void)hipFree(part); (void)hipFree(cnt); (void)hipFree(part_s); (void)hipFree(sum);
+		if (cstream) (void)hipStreamDestroy(cstream);
+		if (stream) (void)hipStreamDestroy(stream);
+	}
+};
+
+// Stored dosage rows of a host buffer -> 2-bit hard-call rows and the marker filter's counts (kern_quant.h), no model
+// handle needed.  The raw rows go through two device buffers: chunk i + 1 crosses the link on the copy stream while
+// chunk i is quantised and its rows and counts go back on the other.
+extern "C" int sgx_quantize_packed(const void *raw, int cls, size_t n_file_samp, double scale, double offset,
+	const int32_t *sel, int32_t n_samp, size_t n_rows, int device, size_t chunk_bytes,
+	uint8_t *packed_out, size_t out_stride, int32_t *n_valid, int32_t *allele_sum, int32_t *ds_valid, double *ds_sum)
+{
+	const char *who = "sgx_quantize_packed";
+	if (n_rows == 0) return SGX_OK;
+	if (n_samp < 1) return fail(SGX_EINVAL, "%s: n_samp = %d", who, n_samp);
+	if (!packed_out || !n_valid || !allele_sum || !ds_valid || !ds_sum) return fail(SGX_EINVAL, "%s: NULL buffer", who);
+	RowSrc src;
+	int rc = packed_check(who, n_samp, raw, cls, n_file_samp, scale, offset, sel, src);
+	if (rc) return rc;
+	const size_t nb = ((size_t)n_samp + 3) / 4, dstride = (((size_t)n_samp + 15) / 16) * 4;
+	if (out_stride < nb) return fail(SGX_EINVAL, "%s: out_stride %zu < ceil(n_samp/4) = %zu", who, out_stride, nb);
+	HIPCHK(hipSetDevice(device));
+	if (chunk_bytes == 0) chunk_bytes = (size_t)512 << 20;
+	const size_t chunk = std::max<size_t>(1, std::min(n_rows, chunk_bytes / src.row_bytes));
+	const unsigned nbx = (unsigned)((dstride / 4 + 255) / 256);      // blocks of a row: quantize_rows has no stride in x
+	QuantDev d;
+	HIPCHK(hipStreamCreateWithFlags(&d.cstream, hipStreamNonBlocking));
+	HIPCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+	for (int k = 0; k < 2; k++) {
+		HIPCHK(hipEventCreateWithFlags(&d.ev_copy[k], hipEventDisableTiming));
+		HIPCHK(hipEventCreateWithFlags(&d.ev_done[k], hipEventDisableTiming));
+		if (k == 0 || chunk < n_rows) HIPCHK(hipMalloc((void **)&d.raw[k], chunk * src.row_bytes));
+	}
+	HIPCHK(hipMalloc((void **)&d.out, chunk * dstride));
+	HIPCHK(hipMalloc((void **)&d.part, 3 * (size_t)nbx * chunk * sizeof(int)));
+	HIPCHK(hipMalloc((void **)&d.part_s, (size_t)nbx * chunk * sizeof(double)));
+	HIPCHK(hipMalloc((void **)&d.cnt, 3 * chunk * sizeof(int)));
+	HIPCHK(hipMalloc((void **)&d.sum, chunk * sizeof(double)));
+	if (sel) {
+		static_assert(sizeof(int) == sizeof(int32_t), "sel");
+		HIPCHK(hipMalloc((void **)&d.sel, (size_t)n_samp * sizeof(int)));
+		HIPCHK(hipMemcpyAsync(d.sel, sel, (size_t)n_samp * sizeof(int), hipMemcpyHostToDevice, d.cstream));   // ahead of the chunks
+	}
+	int *p_nv = d.part, *p_as = d.part + (size_t)nbx * chunk, *p_dv = d.part + 2 * (size_t)nbx * chunk;
+	int *c_nv = d.cnt, *c_as = d.cnt + chunk, *c_dv = d.cnt + 2 * chunk;
+	int i = 0;
+	for (size_t off = 0; off < n_rows; off += chunk, i++) {
+		const size_t m = std::min(chunk, n_rows - off);
+		const int k = i & 1;
+		if (i >= 2) HIPCHK(hipStreamWaitEvent(d.cstream, d.ev_done[k], 0));      // the buffer's previous chunk has been read
+		HIPCHK(hipMemcpyAsync(d.raw[k], src.rows + off * src.row_bytes, m * src.row_bytes, hipMemcpyHostToDevice, d.cstream));
+		HIPCHK(hipEventRecord(d.ev_copy[k], d.cstream));
+		HIPCHK(hipStreamWaitEvent(d.stream, d.ev_copy[k], 0));
+		// with a selection a thread keeps its 16 indices for the rows of its stride: fewer, longer strides
+		const dim3 g(nbx, (unsigned)std::min<size_t>(m, sel ? 64 : 65535));
+#define SGX_QUANT(T, S) do { \
+		hipLaunchKernelGGL((quantize_rows<T>), g, dim3(256), 0, d.stream, (const T *)d.raw[k], n_file_samp, (const int *)d.sel, \
+			(int)n_samp, m, scale, offset, d.out, dstride, p_nv, p_as, p_dv, (S *)d.part_s); \
+		HIPCHK(hipGetLastError()); \
+		hipLaunchKernelGGL((quantize_finish<S>), dim3((unsigned)std::min<size_t>((m + 255) / 256, 1024)), dim3(256), 0, d.stream, \
+			p_nv, p_as, p_dv, (const S *)d.part_s, nbx, m, scale, offset, c_nv, c_as, c_dv, d.sum); \
+		HIPCHK(hipGetLastError()); } while (0)
+		static_assert(sizeof(long long) == sizeof(double), "the partial sums share a buffer");
+		switch (cls) {
+		case SGX_PR_U8: SGX_QUANT(uint8_t, long long); break;
+		case SGX_PR_I8: SGX_QUANT(int8_t, long long); break;
+		case SGX_PR_U16: SGX_QUANT(uint16_t, long long); break;
+		case SGX_PR_I16: SGX_QUANT(int16_t, long long); break;
+		default: SGX_QUANT(float, double); break;
+		}
+#undef SGX_QUANT
+		HIPCHK(hipEventRecord(d.ev_done[k], d.stream));                          // raw[k] is free again
+		HIPCHK(hipMemcpy2DAsync(packed_out + off * out_stride, out_stride, d.out, dstride, nb, m, hipMemcpyDeviceToHost, d.stream));
+		HIPCHK(hipMemcpyAsync(n_valid + off, c_nv, m * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+		HIPCHK(hipMemcpyAsync(allele_sum + off, c_as, m * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+		HIPCHK(hipMemcpyAsync(ds_valid + off, c_dv, m * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+		HIPCHK(hipMemcpyAsync(ds_sum + off, d.sum, m * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+	}
+	HIPCHK(hipStreamSynchronize(d.cstream));
+	HIPCHK(hipStreamSynchronize(d.stream));
+	return SGX_OK;
+}
+
 extern "C" int sgx_synth_2bit_dev(sgx_handle *h, uint8_t *packed_dev, size_t bpv, int32_t n_samp,
 	size_t M, uint64_t first_variant, uint64_t seed, const uint32_t *thr_dev)
 {

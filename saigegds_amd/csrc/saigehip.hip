@@ -73,6 +73,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_pack.h"
 #include "kern_unpack.h"
 #include "kern_dbit2.h"
+#include "kern_quant.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files

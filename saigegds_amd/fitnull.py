@@ -481,6 +481,59 @@ class FittedNullModel(NullModel):
     res_noK: Optional[np.ndarray] = None
 
 
+_DS_NODE = "annotation/format/DS"
+_MARKER_PASS = 4096                            # markers per pass: bounded host memory at any M x N
+
+
+def _ds_grm_markers(src: GdsFile, sel: np.ndarray, n_all: int, want, var_ids: np.ndarray, maf: float,
+                    missing_rate: float, on_gpu: bool):
+    """GRM markers of a file without genotypes: the rows of ``annotation/format/DS`` rounded to hard calls
+    (``gds.round_dosage_codes``), in passes of ``_MARKER_PASS`` variants.  The stored rows go to the device as they
+    are (``sgx_quantize_packed``) when ``on_gpu``, else -- an injected operator, or a node of a class the device
+    does not take -- through the numpy statement of the same rule.  ``sel``: the model's samples as indices into
+    the file's ``n_all``.  The variant filter takes the REAL dosages (SeqArray's allele frequency on a file without
+    genotypes): af = ds_sum / (2 ds_valid), min(af, 1 - af) >= maf, (n_samp - ds_valid) / n_samp <= missing_rate;
+    with ``want`` (a set of variant ids) there is no filter and only those rows are quantised.
+    -> (keep_idx, keep_packed): per pass the kept row numbers and their 2-bit rows."""
+    from .gds import quantize_dosage_2bit
+    nd = src.node(_DS_NODE + "/data")
+    dims = tuple(nd.dims or ())
+    if len(dims) != 2 or int(dims[1]) != n_all:
+        raise ValueError(f"'{_DS_NODE}' should be a [variant, sample] matrix of the file's samples.")
+    n_samp = int(sel.size)
+    sel_q = None if n_samp == n_all else sel       # (indices in increasing order: all of them = the file's order)
+    cls = src.dosage_raw_class(_DS_NODE)
+    keep_idx: List[np.ndarray] = []
+    keep_packed: List[np.ndarray] = []
+    for s0 in range(0, int(dims[0]), _MARKER_PASS):
+        s1 = min(s0 + _MARKER_PASS, int(dims[0]))
+        loc = None
+        if want is not None:
+            loc = np.flatnonzero(np.fromiter((int(x) in want for x in var_ids[s0:s1]), dtype=bool, count=s1 - s0))
+            if loc.size == 0:
+                continue
+        if cls is None:                            # (dFloat64, say: decoded by the reader)
+            raw, scale, offset = src.dosage_real_range(_DS_NODE, s0, s1), 1.0, 0.0
+        else:
+            raw, _, scale, offset = src.dosage_raw_range(_DS_NODE, s0, s1)
+        if loc is not None:
+            raw = raw[loc]
+        if on_gpu and cls is not None:
+            from ._lib import quantize_packed
+            pk, _, _, dv, dsum = quantize_packed(raw, cls, scale, offset, n_samp, sel=sel_q)
+        else:
+            pk, _, _, dv, dsum = quantize_dosage_2bit(raw, cls, scale, offset, sel=sel_q)
+        if loc is None:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                af = dsum / (2.0 * dv)
+            v = (np.minimum(af, 1 - af) >= maf) & ((n_samp - dv.astype(np.int64)) / n_samp <= missing_rate)
+            loc = np.flatnonzero(v)
+            pk = np.ascontiguousarray(pk[loc])
+        keep_idx.append(loc + s0)
+        keep_packed.append(pk)
+    return keep_idx, keep_packed
+
+
 def _load_grm_markers(phenovar: str, covars: List[str], cols: Dict[str, np.ndarray], sids: List[str], gdsfile, maf: float,
                       missing_rate: float, max_num_snp: int, variant_id, seed: int, verbose: bool,
                       use_gpu_counts: bool) -> Dict[str, Any]:
@@ -504,26 +557,39 @@ def _load_grm_markers(phenovar: str, covars: List[str], cols: Dict[str, np.ndarr
     n_samp = len(sel)
 
     # genotypes of the selected samples; variant filter (seqSetFilterCond, :314-321)
+    want = None if variant_id is None else set(int(v) for v in variant_id)
+    ds_route = False
+    keep_idx: List[np.ndarray] = []
+    keep_packed: List[np.ndarray] = []
     if isinstance(src, GenotypeSource):
         packed_all, n_all = src.packed, len(gsid)
         var_ids = np.asarray(src.variant_id)
-    else:
+    elif src.has_genotype():                       # (also when a DS node is present: the reference's order)
         packed_all, n_all, _ = src.dosage_alt_packed()
         var_ids = np.asarray(src.read("variant.id"))
+    elif src.node(_DS_NODE + "/data", silent=True) is not None:
+        # no genotypes: the dosages, rounded to hard calls (R/saige_main.r:395-417, saige_get_sparse)
+        if verbose:
+            print(f"    using '{_DS_NODE}'")
+        var_ids = np.asarray(src.read("variant.id"))
+        if variant_id is None and verbose:
+            print("Filtering variants:")
+        keep_idx, keep_packed = _ds_grm_markers(src, np.asarray(sel), len(gsid), want, var_ids, maf, missing_rate,
+                                                use_gpu_counts)
+        packed_all, n_all, ds_route = np.zeros((0, 0), dtype=np.uint8), len(gsid), True
+    else:
+        raise ValueError("'genotype' and 'annotation/format/DS' are not available.")
     packed_all = np.asarray(packed_all)
-    want = None if variant_id is None else set(int(v) for v in variant_id)
     gpu_counts = None
-    if want is None and n_samp == n_all and use_gpu_counts:
+    if want is None and n_samp == n_all and use_gpu_counts and not ds_route:
         # all samples selected: the per-variant counts of the filter come from the GPU
         from ._lib import geno_stats_2bit
         gpu_counts = geno_stats_2bit(packed_all, n_all)
-    if variant_id is None and verbose:
+    if variant_id is None and verbose and not ds_route:
         print("Filtering variants:")
     same_samples = (n_samp == n_all)
     sel_a = np.asarray(sel)
-    keep_idx: List[np.ndarray] = []
-    keep_packed: List[np.ndarray] = []
-    CH = 4096                                  # markers per pass: bounded host memory at any M x N
+    CH = _MARKER_PASS
     for s0 in range(0, packed_all.shape[0], CH):
         blk = packed_all[s0:s0 + CH]
         codes = None
@@ -582,9 +648,12 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
     ``gdsfile``: SeqArray GDS path / ``GdsFile`` / ``GenotypeSource``.
     ``operator_factory(packed, n_samp)`` builds the GRM operator; the default is
     the GPU one (``GrmOperator``) -- tests inject the CPU oracle to exercise
-    this host logic without a GPU.  ``geno_sparse``, ``num_thread`` and
-    ``fork_loading`` only select storage/threads in the reference and are
-    accepted for signature compatibility.
+    this host logic without a GPU.  A file without ``genotype/data`` gives
+    its GRM markers from ``annotation/format/DS``, every dosage rounded to a
+    hard call: the reference's default mode (``geno_sparse=TRUE``), which is the
+    one implemented -- ``geno_sparse=FALSE`` is not, and the argument is
+    accepted for signature compatibility, as are ``num_thread`` and
+    ``fork_loading`` (threads only).
     """
     if trait_type not in ("binary", "quantitative"):
         raise ValueError("'arg' should be one of \"binary\", \"quantitative\"")

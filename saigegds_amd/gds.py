@@ -830,3 +830,68 @@ def unpack_dosage_2bit(packed: np.ndarray, n_samp: int) -> np.ndarray:
     for k in range(4):
         out[:, :, k] = (packed >> (2 * k)) & 3
     return out.reshape(M, nb * 4)[:, :n_samp]
+
+
+def round_dosage_codes(v: np.ndarray) -> np.ndarray:
+    """Dosages -> the hard-call codes of the null-model fit on a dosage-only file (the reference's ``saige_get_sparse``,
+    src/saige_fitnull.cpp:273-288): 3 where the value is not finite, else r = round(v) with C's ``round`` (halves away
+    from zero) if r is 0, 1 or 2, else 3.  round(v) is 0 exactly on (-0.5, 0.5), 1 on [0.5, 1.5) and 2 on [1.5, 2.5),
+    so the code is decided by comparisons in float64 (1e30 -> 3; -0.4 and -0.0 -> 0; a NaN fails every comparison).
+    No flip to the minor allele."""
+    v = np.asarray(v, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        c = np.full(v.shape, 3, dtype=np.uint8)
+        c[(v > -0.5) & (v < 0.5)] = 0
+        c[(v >= 0.5) & (v < 1.5)] = 1
+        c[(v >= 1.5) & (v < 2.5)] = 2
+    return c
+
+
+def quantize_dosage_2bit(raw: np.ndarray, cls: Optional[str], scale: float = 1.0, offset: float = 0.0, sel=None,
+                         block_bytes: int = 64 << 20):
+    """The numpy statement of ``sgx_quantize_packed``: stored dosage rows ``raw`` [m, n_file_samp] of a packed-real
+    class (``GdsFile.dosage_raw_range``; dosage = raw * scale + offset in two roundings, the class's all-ones / most
+    negative code = missing) or, ``cls`` "dFloat32" / None, real values taken as they are; ``sel``: the samples wanted
+    as indices into the file's.  -> (packed [m, ceil(n / 4)] as ``pack_dosage_2bit`` of ``round_dosage_codes``,
+    n_valid, allele_sum of the codes other than 3, ds_valid, ds_sum of the finite dosages before rounding).  ds_sum of
+    an integer class is (float64)(exact integer sum of the stored values) * scale + ds_valid * offset, as on the
+    device; of real values a float64 sum (numpy's pairwise order: within rounding of the device's).  Rows are decoded
+    ``block_bytes`` of float64 at a time."""
+    raw = np.asarray(raw)
+    if raw.ndim != 2:
+        raise ValueError("dosage rows must be [n_variants, n_file_samp]")
+    integer = cls in ("dPackedReal8U", "dPackedReal8", "dPackedReal16U", "dPackedReal16")
+    if integer:
+        dt = np.dtype(GdsFile.RAW_DOSAGE_DTYPES[cls])
+        raw = raw.astype(dt, copy=False)
+        miss = {"dPackedReal8U": 0xFF, "dPackedReal8": -128, "dPackedReal16U": 0xFFFF, "dPackedReal16": -32768}[cls]
+    elif cls not in ("dFloat32", None):
+        raise ValueError(f"unknown packed-real class {cls!r}")
+    sel = None if sel is None else np.asarray(sel, dtype=np.int64)
+    m, n = raw.shape[0], (raw.shape[1] if sel is None else sel.size)
+    packed = np.zeros((m, (n + 3) // 4), dtype=np.uint8)
+    nv, sm, dv = (np.zeros(m, dtype=np.int32) for _ in range(3))
+    dsum = np.zeros(m, dtype=np.float64)
+    step = max(1, int(block_bytes) // (8 * max(n, 1)))
+    for r0 in range(0, m, step):
+        x = raw[r0:r0 + step] if sel is None else raw[r0:r0 + step][:, sel]
+        if integer:
+            v = x.astype(np.float64) * np.float64(scale)
+            v = v + np.float64(offset)
+            v[x == miss] = np.nan
+        else:
+            v = x.astype(np.float64)
+        fin = np.isfinite(v)
+        codes = round_dosage_codes(v)
+        packed[r0:r0 + step] = pack_dosage_2bit(codes)
+        ok = codes != 3
+        nv[r0:r0 + step] = ok.sum(axis=1)
+        sm[r0:r0 + step] = np.where(ok, codes, 0).sum(axis=1, dtype=np.int64)
+        cnt = fin.sum(axis=1)
+        dv[r0:r0 + step] = cnt
+        if integer:
+            tot = np.where(fin, x, 0).sum(axis=1, dtype=np.int64)
+            dsum[r0:r0 + step] = tot.astype(np.float64) * np.float64(scale) + cnt.astype(np.float64) * np.float64(offset)
+        else:
+            dsum[r0:r0 + step] = np.where(fin, v, 0.0).sum(axis=1)
+    return packed, nv, sm, dv, dsum

@@ -431,9 +431,12 @@ def seqGLMM_GxG_spa(formula: str, data: Dict[str, Any], gds_grm, gds_assoc, snp_
     pandas DataFrame works), the first two the variant ids of a pair, further columns are appended to
     the result.  ``operator_factory(packed, n_samp)`` builds the GRM operator (default: the GPU
     ``GrmOperator``); ``batch_solves=False`` solves one vector at a time (same results).  ``inv_norm``,
-    ``X_transform`` (for the pairs), ``ratioCVcutoff``, ``geno_sparse``, ``num_thread`` and
-    ``fork_loading`` do not change what the reference computes for binary traits and are accepted for
-    signature compatibility.  Returns a ``GxGTable`` (column -> values, R's column order)."""
+    ``X_transform`` (for the pairs), ``ratioCVcutoff``, ``num_thread`` and ``fork_loading`` do not change
+    what the reference computes for binary traits and are accepted for signature compatibility.  A
+    ``gds_grm`` file without ``genotype/data`` gives its markers from ``annotation/format/DS``, every dosage
+    rounded to a hard call: the reference's default mode (``geno_sparse=TRUE``,
+    R/saige_interaction.r:223-236), the one implemented; ``geno_sparse`` itself is accepted and not read.
+    Returns a ``GxGTable`` (column -> values, R's column order)."""
     if trait_type not in ("binary", "quantitative"):
         raise ValueError("'arg' should be one of \"binary\", \"quantitative\"")
     if not verbose:
