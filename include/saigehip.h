@@ -273,6 +273,26 @@ int sgx_burden_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_varia
 	size_t n_variants, size_t n_rows, const int64_t *row_ptr, const int32_t *var_idx,
 	const double *lut, double *out8, uint8_t *valid);
 
+/* SKAT set test: per unit the score statistics of its variants and their covariance, from 2-bit genotypes in HOST
+ * memory (nothing of this is in the reference, which has no variance-component test).  Unit u has the
+ * entries e in [unit_ptr[u], unit_ptr[u+1]) = rows var_idx[e] of `packed`, each with a 4-entry dosage table
+ * lut[4e + code] that holds mean imputation and the flip to the minor allele as for sgx_burden_2bit (no weight).  With
+ * G_e the dosage vector that table gives and adj_e = G_e - X (X'VX)^-1 X'V G_e as in the single-variant test:
+ *   score[e]                 S_e = sum_i (y - mu)_i adj_ei                    (quantitative traits: divided by tau[0])
+ *   cov, unit u: m_u x m_u doubles, row-major, at the sum of m_v^2 over the units v < u, exactly symmetric:
+ *                            Phi_ef = var_ratio * sum_i mu2_i adj_ei adj_fi   (quantitative traits: mu2 = 1)
+ * so that S_e^2 / Phi_ee is the chi-square behind the p.norm column of the scan of that variant.  The sums are made in
+ * FP64 on the matrix cores in a fixed order: no atomics, the same bits from call to call, and what a unit gets does
+ * not depend on the other units of the call or on their order.  An entry whose table holds a non-finite value gets
+ * non-finite results and leaves the other entries of its unit alone.  The rows cross PCIe once per call in the chunks
+ * of the host-buffer scans.  A unit of 0 entries is legal and writes nothing; a unit of more than
+ * SGX_SKAT_MAX_VARIANTS entries, a variant index outside [0, n_variants) or a NULL buffer returns SGX_EINVAL and
+ * launches nothing; the handle stays usable.  Synchronous. */
+#define SGX_SKAT_MAX_VARIANTS 4096
+int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant, size_t n_variants,
+	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut,
+	double *score, double *cov);
+
 /* Aggregate tests on dosage input: the INTSXP / REALSXP branches of ds_mat_mafmac and ds_mat_burden
  * (src/saige_main.cpp:485-610), which the R drivers reach with .dsnode(gdsfile, dsnode) for imputed
  * data (R/assoc_aggregate.r:89,351,606).  A batch of dosage rows (u8: 0xFF = missing; i32: INT_MIN =

@@ -24,9 +24,11 @@ EXPORTS = (
     "sgx_scan_packed", "sgx_ds_block_load_packed",
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
     "sgx_quantize_packed",
+    "sgx_skat_2bit",
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
+SKAT_MAX_VARIANTS = 4096   # SGX_SKAT_MAX_VARIANTS: entries of one unit of sgx_skat_2bit
 DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
 DS_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float64): 2}   # SGX_DS_U8 / _I32 / _F64
 # SGX_PR_*: the GDS classes whose rows cross PCIe as stored (sgx_scan_packed) and the numpy type of their values
@@ -185,6 +187,8 @@ def load():
     L.sgx_scan_i32.argtypes = [vp, vp, sz, vp, vp]
     L.sgx_burden_2bit.restype = C.c_int
     L.sgx_burden_2bit.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
+    L.sgx_skat_2bit.restype = C.c_int
+    L.sgx_skat_2bit.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
     L.sgx_dsblock_create.restype = C.c_int
     L.sgx_dsblock_create.argtypes = [C.c_int32, C.c_int, sz, C.c_int, C.POINTER(vp)]
     L.sgx_dsblock_free.restype = None
@@ -376,6 +380,27 @@ class Scanner:
                                       row_ptr.ctypes.data, var_idx.ctypes.data, lut.ctypes.data,
                                       out.ctypes.data, valid.ctypes.data))
         return out, valid
+
+    def skat_2bit(self, packed: np.ndarray, unit_ptr, var_idx, lut):
+        """Score statistics and their covariance per unit (CSR over the rows of ``packed``, one 4-entry dosage table
+        per entry; ``sgx_skat_2bit``) -> (score [entries], cov: per unit an [m, m] symmetric matrix)."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        unit_ptr = np.ascontiguousarray(unit_ptr, dtype=np.int64)
+        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+        lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
+        n_units = unit_ptr.size - 1
+        if packed.ndim != 2 or lut.shape[0] != var_idx.size or n_units < 0 or unit_ptr[-1] != var_idx.size:
+            raise ValueError("skat_2bit: inconsistent CSR / table shapes")
+        sizes = np.diff(unit_ptr)
+        if (sizes < 0).any():
+            raise ValueError("skat_2bit: unit_ptr not ascending")
+        offs = np.concatenate([[0], np.cumsum(sizes * sizes)])
+        score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
+        if var_idx.size:
+            check(self._L.sgx_skat_2bit(self._h, packed.ctypes.data, packed.shape[1], packed.shape[0], n_units,
+                                        unit_ptr.ctypes.data, var_idx.ctypes.data, lut.ctypes.data,
+                                        score.ctypes.data, cov.ctypes.data))
+        return score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)]
 
     def dosage_block(self, dtype, max_variants: int) -> "DosageBlock":
         """Device storage for a batch of dosage rows of the aggregate tests (``DosageBlock`` below)."""

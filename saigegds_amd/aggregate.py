@@ -373,6 +373,7 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
     pr.maf = np.where(n > 0, np.minimum(af, 1 - af), np.nan)
     pr.mac = np.minimum(s, 2 * n - s)
     pr.pval = np.where(valid != 0, out[:, 5], np.nan)          # single_test_*: NaN when the filter rejects
+    pr.out, pr.valid = out, valid                               # the whole table: the SKAT driver's SPA adjustment
     return pr
 
 

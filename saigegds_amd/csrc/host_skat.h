@@ -1,0 +1,157 @@
+// host_skat.h -- the SKAT set test's score vector and covariance matrix per unit from 2-bit rows in host
+// memory: the rows and tables go to the device once, kern_skat.h makes the Gram tiles and the dense sums, the host
+// turns them into S and Phi by the scan's own algebra in double.
+// Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
+
+static const int SKAT_SLAB_DW = 256;                        // dwords (of 16 samples) per sample slab: cut by N alone
+static const size_t SKAT_PART_BYTES = (size_t)256 << 20;    // per-slab partial tiles of one launch
+
+extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t n_variants,
+	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut,
+	double *score, double *cov)
+{
+	if (!h) return fail(SGX_EINVAL, "sgx_skat_2bit: NULL handle");
+	if (n_units == 0) return SGX_OK;
+	if (!packed || !unit_ptr || !var_idx || !lut || !score || !cov)
+		return fail(SGX_EINVAL, "sgx_skat_2bit: NULL buffer");
+	const int N = h->md.N, K = h->md.K, P = h->md.P, C = 2 * K + 1;
+	if (bpv < (size_t)(N + 3) / 4)
+		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
+	// the units' sizes first: nothing is read through a unit_ptr that is out of bounds
+	if (unit_ptr[0] != 0) return fail(SGX_EINVAL, "sgx_skat_2bit: bad unit_ptr");
+	for (size_t u = 0; u < n_units; u++) {
+		const int64_t m = unit_ptr[u + 1] - unit_ptr[u];
+		if (m < 0) return fail(SGX_EINVAL, "sgx_skat_2bit: unit_ptr not ascending");
+		if (m > SGX_SKAT_MAX_VARIANTS)
+			return fail(SGX_EINVAL, "sgx_skat_2bit: unit %zu has %lld variants, at most %d are supported", u, (long long)m, SGX_SKAT_MAX_VARIANTS);
+	}
+	const int32_t *bad;
+	int rc = csr_check("sgx_skat_2bit", "unit_ptr", n_units, unit_ptr, var_idx, n_variants, &bad);
+	if (rc) return rc;
+	if (bad) return fail(SGX_EINVAL, "sgx_skat_2bit: variant index %d out of range", *bad);
+	const int64_t nnz = unit_ptr[n_units];
+	if (nnz == 0) return SGX_OK;
+	rc = set_dev(h);
+	if (rc) return rc;
+	rc = sync_lane(h);
+	if (rc) return rc;
+	h->last_issued = h;
+
+	// the tiles: per unit the variant tiles with tile_col >= tile_row, then the row tile against the 2K+1 columns of F
+	std::vector<SkatTile> tiles;
+	std::vector<uint32_t> tile_unit;
+	const int n_dt = (C + 15) / 16;
+	for (size_t u = 0; u < n_units; u++) {
+		const int64_t e0 = unit_ptr[u], m = unit_ptr[u + 1] - e0;
+		const int n_vt = (int)((m + 15) / 16);
+		for (int tr = 0; tr < n_vt; tr++) {
+			SkatTile t{};
+			t.row_e0 = e0 + 16 * tr; t.nrow = (int)std::min<int64_t>(16, m - 16 * tr);
+			for (int tc = tr; tc < n_vt; tc++) {
+				t.col_e0 = e0 + 16 * tc; t.ncol = (int)std::min<int64_t>(16, m - 16 * tc); t.dense = 0;
+				tiles.push_back(t); tile_unit.push_back((uint32_t)u);
+			}
+			for (int dt = 0; dt < n_dt; dt++) {
+				t.col_e0 = 16 * dt; t.ncol = std::min(16, C - 16 * dt); t.dense = 1;
+				tiles.push_back(t); tile_unit.push_back((uint32_t)u);
+			}
+		}
+	}
+	const size_t T = tiles.size();
+	const int ndw = (N + 15) >> 4, nslab = (ndw + SKAT_SLAB_DW - 1) / SKAT_SLAB_DW;
+	const size_t tchunk = std::min(T, std::max<size_t>(1, SKAT_PART_BYTES / ((size_t)nslab * 256 * sizeof(double))));
+
+	// device copies: the rows (dword stride) in the host-row pipeline's chunks, then entries, tables, tiles
+	const size_t dbpv = (size_t)ndw * 4;
+	const size_t o_idx = (n_variants * dbpv + 15) & ~(size_t)15;
+	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
+	const size_t o_til = o_lut + (size_t)nnz * 4 * sizeof(double);
+	const size_t need = o_til + T * sizeof(SkatTile);
+	rc = grow(h->stage_pk, h->stage_pk_cap, need);
+	if (rc) return rc;
+	rc = grow(h->skat_part, h->skat_part_cap, tchunk * (size_t)nslab * 256);
+	if (rc) return rc;
+	rc = grow(h->skat_fin, h->skat_fin_cap, tchunk * 256);
+	if (rc) return rc;
+	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
+	for (size_t off = 0; off < n_variants; off += rchunk) {
+		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), h->stream);
+		if (rc) return rc;
+	}
+	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut, (size_t)nnz * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_til, tiles.data(), T * sizeof(SkatTile), hipMemcpyHostToDevice, h->stream));
+
+	// W into cov (upper triangle, unit by unit), the dense sums into `dense` [entry][2K+1]
+	std::vector<size_t> cov_off(n_units + 1, 0);
+	for (size_t u = 0; u < n_units; u++) {
+		const size_t m = (size_t)(unit_ptr[u + 1] - unit_ptr[u]);
+		cov_off[u + 1] = cov_off[u] + m * m;
+	}
+	std::vector<double> dense((size_t)nnz * C), fin(tchunk * 256);
+	for (size_t t0 = 0; t0 < T; t0 += tchunk) {
+		const size_t nt = std::min(tchunk, T - t0);
+		hipLaunchKernelGGL(skat_gram_kernel, dim3((unsigned)nt, (unsigned)nslab), dim3(64), 0, h->stream,
+			h->stage_pk, dbpv, N, reinterpret_cast<const int *>(h->stage_pk + o_idx),
+			reinterpret_cast<const double *>(h->stage_pk + o_lut), h->dF, P,
+			reinterpret_cast<const SkatTile *>(h->stage_pk + o_til) + t0, nt, SKAT_SLAB_DW, h->skat_part);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(skat_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream,
+			h->skat_part, nt * 256, nslab, h->skat_fin);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(fin.data(), h->skat_fin, nt * 256 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
+		for (size_t k = 0; k < nt; k++) {
+			const SkatTile &t = tiles[t0 + k];
+			const double *f = &fin[k * 256];
+			const size_t u = tile_unit[t0 + k];
+			const int64_t e0 = unit_ptr[u];
+			const size_t m = (size_t)(unit_ptr[u + 1] - e0), r0 = (size_t)(t.row_e0 - e0);
+			if (t.dense) {
+				for (int i = 0; i < t.nrow; i++)
+					for (int j = 0; j < t.ncol; j++) dense[(size_t)(t.row_e0 + i) * C + t.col_e0 + j] = f[i * 16 + j];
+			} else {
+				const size_t c0 = (size_t)(t.col_e0 - e0);
+				double *w = cov + cov_off[u];
+				for (int i = 0; i < t.nrow; i++)
+					for (int j = (c0 == r0 ? i : 0); j < t.ncol; j++) w[(r0 + i) * m + c0 + j] = f[i * 16 + j];
+			}
+		}
+	}
+
+	// S_j = s_j - S_a c'_j;  Phi_jl = r (c'_j XVX c'_l + W_jl - e_j c'_l - e_l c'_j), j <= l, mirrored
+	const DevModel &md = h->md;
+	std::vector<double> q;
+	for (size_t u = 0; u < n_units; u++) {
+		const int64_t e0 = unit_ptr[u];
+		const size_t m = (size_t)(unit_ptr[u + 1] - e0);
+		if (m == 0) continue;
+		double *phi = cov + cov_off[u];
+		q.assign(m * K, 0.0);
+		for (size_t j = 0; j < m; j++) {
+			const double *cj = &dense[(size_t)(e0 + j) * C];
+			double sa = 0;
+			for (int a = 0; a < K; a++) {
+				double x = 0;
+				for (int b = 0; b < K; b++) x += md.XVX[a * K + b] * cj[b];
+				q[j * K + a] = x;
+				sa += md.S_a[a] * cj[a];
+			}
+			const double S = cj[2 * K] - sa;
+			score[e0 + j] = md.quant ? S / md.tau0 : S;
+		}
+		for (size_t j = 0; j < m; j++) {
+			const double *cj = &dense[(size_t)(e0 + j) * C], *ej = cj + K;
+			for (size_t l = j; l < m; l++) {
+				const double *cl = &dense[(size_t)(e0 + l) * C], *el = cl + K, *ql = &q[l * K];
+				double cq = 0, ec = 0;
+				for (int a = 0; a < K; a++) { cq += cj[a] * ql[a]; ec += ej[a] * cl[a] + el[a] * cj[a]; }
+				const double v = md.r * (cq + phi[j * m + l] - ec);
+				phi[j * m + l] = v;
+				phi[l * m + j] = v;
+			}
+		}
+	}
+	return SGX_OK;
+}

@@ -113,6 +113,8 @@ struct sgx_handle {
 	hipEvent_t ev_done[2] = {nullptr, nullptr};   // behind what reads a buffer on the handle's stream: the copy of the chunk after next waits for it
 	uint8_t *stage_pk = nullptr; size_t stage_pk_cap = 0;   // burden: packed rows, CSR and tables
 	double *ds_part = nullptr; size_t ds_part_cap = 0;       // dosage score kernels: per-split partial sums
+	double *skat_part = nullptr; size_t skat_part_cap = 0;   // sgx_skat_2bit: per-slab partial tiles of a launch
+	double *skat_fin = nullptr; size_t skat_fin_cap = 0;     // ... and its tiles summed over the slabs
 	double *stage_out = nullptr; uint8_t *stage_valid = nullptr; size_t stage_out_cap = 0;
 	hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
 	hipEvent_t evk[2] = {nullptr, nullptr};    // around the contraction kernel alone (stats.ms_kernel)

@@ -1,0 +1,186 @@
+"""SKAT, the variance-component set test, on MI355X: ``seqAssocGLMM_spaSKAT`` and the mixture p-value
+``pchisq_mix``.
+
+The reference has no SKAT (its set tests collapse a unit to one dosage row: burden, ACAT-V, ACAT-O), so nothing here
+mirrors reference code and no reference vector pins it: the definition is tied to the project's pinned scan and
+burden paths by identities (tests/test_gpu_skat.py).  The flow of a call:
+
+1. ``_prepare`` of the aggregate drivers: one ``sgx_scan_2bit`` over every variant that occurs in a unit (thresholds
+   0 / 0 / 1) for maf, mac and the single-variant p-values;
+2. one ``sgx_skat_2bit`` for all units: score statistics ``S`` and their covariance ``Phi`` per unit, the weighted Gram
+   matrix of the unit's 2-bit rows on the device's matrix cores;
+3. on the host, per unit and weight column: the SPA adjustment of ``Phi`` (binary traits), ``Q = sum w_j^2 S_j^2`` and
+   its p-value under the mixture of chi-squares with the eigenvalues of ``diag(w) Phi diag(w)``.
+"""
+from __future__ import annotations
+
+import math
+from typing import Any, Dict
+
+import numpy as np
+
+from .aggregate import AggrParamBeta, _dbeta, _prepare, _save, _summary_cols
+
+LAMBDA_DROP = 1e-10      # eigenvalues at or below this fraction of the largest one are dropped
+SERIES_X = 0.05          # |2 t lambda_k| below which a term's functions are summed as power series
+LIMIT_T = 1e-150         # |2 t lambda_max| below which the saddlepoint is taken to BE the mean (w -> 0 limit)
+_NSER = 24               # terms of those series: 0.05^24 is far below a double's resolution
+
+
+def _h_u(x: np.ndarray):
+    """For x = 2 t lambda (x < 1), without cancellation near x = 0:
+         h(x) = [x / (1 - x) + log(1 - x)] / x^2       = sum_{n>=0} (n + 1) / (n + 2) x^n
+         u(x) = 1 / (1 - x)^2 - 2 h(x)                 = sum_{n>=1} n (n + 1) / (n + 2) x^n
+    so that t q - K(t) = 2 t^2 sum lambda^2 h(x) at the saddlepoint and K''(t) = 2 sum lambda^2 / (1 - x)^2."""
+    h, u = np.empty_like(x), np.empty_like(x)
+    small = np.abs(x) < SERIES_X
+    xs = x[small]
+    if xs.size:
+        hs, us, p = np.zeros_like(xs), np.zeros_like(xs), np.ones_like(xs)
+        for n in range(_NSER):
+            hs += (n + 1) / (n + 2) * p
+            us += n * (n + 1) / (n + 2) * p
+            p = p * xs
+        h[small], u[small] = hs, us
+    xl = x[~small]
+    if xl.size:
+        hl = (xl / (1 - xl) + np.log1p(-xl)) / (xl * xl)
+        h[~small], u[~small] = hl, 1 / ((1 - xl) * (1 - xl)) - 2 * hl
+    return h, u
+
+
+def pchisq_mix(q: float, lam) -> float:
+    """P(sum_k lam_k chi2_1 > q) for lam_k > 0.
+
+    Eigenvalues ``<= 1e-10 * max(lam)`` are dropped.  One eigenvalue left: exact, ``chdtrc(1, q / lam)``.  Otherwise the
+    saddlepoint approximation with the cumulant generating function ``K(t) = -1/2 sum log(1 - 2 t lam_k)``:
+    ``K'(t^) = q`` is solved on ``t < 1 / (2 max lam)`` by Newton steps kept inside a bracket (bisection when a step
+    leaves it), then ``w = sign(t^) sqrt(2 (t^ q - K))``, ``v = t^ sqrt(K'')`` and ``p = 1 - Phi(w + log(v / w) / w)``.
+
+    Near the mean ``q = sum lam`` both ``w`` and ``v`` go to 0 with ``t^``.  They are therefore formed from ``t^`` alone
+    (``_h_u``): ``w = 2 t^ sqrt(sum lam^2 h)``, ``v / w`` with ``t^`` cancelled, ``log(v / w) = 1/2 log1p(R)``,
+    ``R = sum lam^2 u / (2 sum lam^2 h)`` -- sums of terms of one sign, so the formula keeps its precision down to
+    any ``t^ != 0``; terms with ``|2 t^ lam_k| < 0.05`` take the power series of ``h`` and ``u``.  Only where
+    ``|2 t^ max lam| < 1e-150`` (in practice: ``q`` equal to the mean) the limit ``log(v / w) / w -> K'''(0) / (6 K''(0)^1.5)``
+    is used, ``w = 0``.  The result is continuous and non-increasing in ``q`` through the mean.
+
+    ``q <= 0`` gives 1, an empty ``lam`` (or none positive) NaN.  Accuracy against the exact distribution: DESIGN.md 8b.
+    """
+    from scipy.special import chdtrc, ndtr
+    lam = np.asarray(lam, dtype=np.float64).ravel()
+    if lam.size == 0 or not np.all(np.isfinite(lam)) or not math.isfinite(q):
+        return float("nan")
+    lmax = float(lam.max())
+    if not lmax > 0:
+        return float("nan")
+    if q <= 0:
+        return 1.0
+    lam = lam[lam > LAMBDA_DROP * lmax]
+    if lam.size == 1:
+        return float(chdtrc(1.0, q / lam[0]))
+    q = float(q)
+    mean = float(lam.sum())
+    # bracket of the root of K'(t) = sum lam / (1 - 2 t lam) - q: K' is increasing; below the mean every term is
+    # under 1 / (2 |t|), so K'(-n / (2 q)) < q; above it the largest term alone reaches q at (1 - lmax / q) / (2 lmax)
+    if q > mean:
+        lo, hi = 0.0, (1 - lmax / q) / (2 * lmax)
+    elif q < mean:
+        lo, hi = -lam.size / (2 * q), 0.0
+    else:
+        lo = hi = 0.0
+    t = 0.0
+    if lo < hi:
+        for _ in range(200):
+            d = 1 - 2 * t * lam
+            f = float((lam / d).sum()) - q
+            if f == 0:
+                break
+            if f > 0:
+                hi = t
+            else:
+                lo = t
+            k2 = 2 * float((lam * lam / (d * d)).sum())
+            tn = t - f / k2
+            if not (lo < tn < hi):
+                tn = 0.5 * (lo + hi)
+            if tn == t or abs(tn - t) <= 1e-16 * abs(tn):
+                t = tn
+                break
+            t = tn
+    x = 2 * t * lam
+    l2 = lam * lam
+    if abs(2 * t * lmax) < LIMIT_T:
+        k2 = 2 * float(l2.sum())
+        z = 8 * float((l2 * lam).sum()) / (6 * k2 ** 1.5)
+        return float(ndtr(-z))
+    h, u = _h_u(x)
+    sh = float((l2 * h).sum())
+    w = 2 * t * math.sqrt(sh)
+    z = w + 0.5 * math.log1p(float((l2 * u).sum()) / (2 * sh)) / w
+    return float(ndtr(-z))
+
+
+def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: str = "", spa_pval: float = 0.05,
+                         var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
+                         parallel=False, verbose: bool = True, verbose_maf: bool = True,
+                         scanner_factory=None) -> Dict[str, Any]:
+    """SKAT per unit and weight set on hard calls (not in the reference; arguments as ``seqAssocGLMM_spaBurden``).
+
+    Per unit: the variants that pass the scan at thresholds 0 / 0 / 1 with mac > 0; their score statistics ``S`` and
+    covariance ``Phi`` (``sgx_skat_2bit``, one call for all units).  Binary traits: where a variant went through the
+    SPA stage (p.norm <= spa.pval) and it converged with 0 < pval != p.norm and S_j != 0, row and column j of ``Phi``
+    are scaled by the square root of ``d_j = S_j^2 / (Phi_jj qchisq(pval_j, 1, upper))``, so that the variant's own
+    chi-square under the scaled variance gives its SPA p-value.  Per weight column (a, b): ``w_j = dbeta(maf_j, a, b)``,
+    ``Q = sum w_j^2 S_j^2``, ``pval = pchisq_mix(Q, eigvalsh(diag(w) Phi diag(w)))``.  Columns: those of the burden
+    driver's summary, ``n.var`` (variants in the test), ``Q`` and ``pval`` (suffix ``.b<a>_<b>`` with more than one
+    weight set).  A unit with no variant left gives NaN."""
+    from scipy.special import chdtri
+    if not isinstance(dsnode, str):
+        raise TypeError("is.character(dsnode) is not TRUE")
+    if dsnode != "":
+        raise NotImplementedError("SKAT on dosage input is not implemented.")
+    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT analysis:", scanner_factory)
+    try:
+        if pr.ds_out is not None:
+            raise NotImplementedError("SKAT on dosage input is not implemented.")
+        ans = _summary_cols(pr)
+        ok = (pr.valid != 0) & (pr.mac > 0)
+        kept = [np.asarray(r, dtype=np.int64)[ok[np.asarray(r, dtype=np.int64)]] for r in pr.rows]
+        var_idx = np.concatenate(kept).astype(np.int32) if kept else np.zeros(0, dtype=np.int32)
+        unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])]).astype(np.int64)
+        n, s = pr.n[var_idx], pr.s[var_idx]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = s / n                                               # (double)sum / n, as _burden_rows
+        flip = s > n
+        lut = np.where(flip[:, None], np.stack([2 + 0 * m, 1 + 0 * m, 0 * m, 2 - m], axis=1),
+                       np.stack([0 * m, 1 + 0 * m, 2 + 0 * m, m], axis=1))
+        score, cov = pr.sc.skat_2bit(pr.packed, unit_ptr, var_idx, lut)
+    finally:
+        pr.sc.close()
+    nu, nw = len(kept), pr.wbeta.shape[1]
+    Q, P = np.full((nu, nw), np.nan), np.full((nu, nw), np.nan)
+    for u, r in enumerate(kept):
+        if r.size == 0:
+            continue
+        S = np.asarray(score[unit_ptr[u]:unit_ptr[u + 1]], dtype=np.float64)
+        phi = np.array(cov[u], dtype=np.float64)
+        if pr.binary:
+            o = pr.out[r]
+            pv, pn, cvg = o[:, 5], o[:, 6], o[:, 7]
+            adj = (pn <= pr.sm.spa_pval) & (cvg != 0) & (pv > 0) & (pv != pn) & (S != 0)
+            d = np.ones(r.size)
+            d[adj] = S[adj] ** 2 / (np.diag(phi)[adj] * chdtri(1.0, pv[adj]))
+            sd = np.sqrt(d)
+            phi = phi * sd[:, None] * sd[None, :]
+        for i, (a, b) in enumerate(pr.wbeta.T):
+            w = _dbeta(pr.maf[r], a, b)
+            Q[u, i] = float(np.sum(w * w * S * S))
+            wp = phi * w[:, None] * w[None, :]
+            if np.all(np.isfinite(wp)) and math.isfinite(Q[u, i]):
+                P[u, i] = pchisq_mix(Q[u, i], np.linalg.eigvalsh(wp))
+    ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
+    for i, nm in enumerate(pr.wb_colnm):
+        sfx = f".{nm}" if len(pr.wb_colnm) > 1 else ""
+        ans["Q" + sfx], ans["pval" + sfx] = Q[:, i], P[:, i]
+    _save(ans, res_savefn, res_compress, verbose)
+    return ans
