@@ -329,7 +329,21 @@ int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant
  *                       sum_trunc and everything sgx_dsblock_scan / _burden then give equal sgx_dsblock_load of
  *                       the host-decoded rows bit for bit.  (Its name stands apart from the sgx_dsblock_* five on
  *                       purpose: that set is pinned as it is by tests/test_aggregate_dosage.py.)
- * All five are synchronous; block and handle must be on the same device and have the same n_samp. */
+ *   sgx_ds_block_skat   the SKAT sums of sgx_skat_2bit from the resident rows (named as the entry above, for the same
+ *                       reason).  Unit u has the entries [unit_ptr[u], unit_ptr[u+1]) = rows var_idx[e] of the block,
+ *                       in [0, rows loaded); entry e has the dosage vector
+ *                           G_e(i) = present ? (flip[e] ? 2 - x : x) : mean[e],    x = row var_idx[e] at sample i
+ *                       with mean[e] already flipped by the caller (the drivers: flip = sum > n_valid, mean =
+ *                       sum / n_valid or 2 - that, from the double `sum` -- what the scan itself imputes and flips by;
+ *                       DESIGN.md 8b).  score, cov: as sgx_skat_2bit lays them out, every unit's matrix exactly
+ *                       symmetric; the same FP64 matrix-core sums in a fixed order -- no atomics, sample slabs cut by
+ *                       n_samp alone, the same bits from call to call and whatever the other units of the call are.  An
+ *                       entry whose mean is not finite and is used gets non-finite results and leaves the other entries
+ *                       of its unit alone.  Nothing crosses PCIe but the tables and the results.  A unit of 0 entries
+ *                       is legal; a unit of more than SGX_SKAT_MAX_VARIANTS entries, an index outside the loaded rows,
+ *                       a NULL buffer or a block / handle mismatch returns SGX_EINVAL and launches nothing; the handle
+ *                       stays usable.
+ * All of them are synchronous; block and handle must be on the same device and have the same n_samp. */
 #define SGX_DS_U8  0
 #define SGX_DS_I32 1
 #define SGX_DS_F64 2
@@ -342,6 +356,8 @@ int  sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosage, size_t 
 int  sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const void *raw, int cls, size_t n_file_samp,
 	double scale, double offset, const int32_t *sel, size_t n_variants,
 	int32_t *n_valid, double *sum, int64_t *sum_trunc);
+int  sgx_ds_block_skat(sgx_handle *h, const sgx_dsblock *b, size_t n_units, const int64_t *unit_ptr,
+	const int32_t *var_idx, const uint8_t *flip, const double *mean, double *score, double *cov);
 int  sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out8, uint8_t *valid);
 int  sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_groups, const int64_t *grp_ptr,
 	const int32_t *var_idx, const uint8_t *flip, int n_cols, const double *w, const double *mw,

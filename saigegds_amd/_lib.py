@@ -24,7 +24,7 @@ EXPORTS = (
     "sgx_scan_packed", "sgx_ds_block_load_packed",
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
     "sgx_quantize_packed",
-    "sgx_skat_2bit",
+    "sgx_skat_2bit", "sgx_ds_block_skat",
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
@@ -207,6 +207,8 @@ def load():
     L.sgx_dsblock_scan.argtypes = [vp, vp, vp, vp]
     L.sgx_dsblock_burden.restype = C.c_int
     L.sgx_dsblock_burden.argtypes = [vp, vp, sz, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.sgx_ds_block_skat.restype = C.c_int
+    L.sgx_ds_block_skat.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.sgx_decode_dbit2.restype = C.c_int
     L.sgx_decode_dbit2.argtypes = [vp, sz, C.c_int32, sz, vp, C.c_int32, vp, sz, C.c_int]
     L.sgx_geno_stats_2bit.restype = C.c_int
@@ -515,7 +517,8 @@ class Block:
 
 class DosageBlock:
     """A batch of dosage rows resident on the device (``sgx_dsblock``) for the aggregate tests: loaded once, it
-    serves the per-variant counts, the single-variant test of every row and the burden rows of all units.
+    serves the per-variant counts, the single-variant test of every row, the burden rows of all units and the SKAT
+    sums of all units.
     ``dtype``: uint8 (0xFF = missing), int32 (INT_MIN = missing) or float64 (NaN / Inf = missing)."""
 
     def __init__(self, sc: Scanner, dtype, max_variants: int):
@@ -578,6 +581,28 @@ class DosageBlock:
                                          flip.ctypes.data, nc, w.ctypes.data, mw.ctypes.data, out.ctypes.data,
                                          valid.ctypes.data))
         return out, valid
+
+    def skat(self, unit_ptr, var_idx, flip, mean):
+        """Score statistics and their covariance per unit (CSR over the block's rows; per entry ``flip`` and the mean
+        that stands in for a missing dosage, already flipped; ``sgx_ds_block_skat``) -> (score [entries], cov: per unit
+        an [m, m] symmetric matrix), as ``Scanner.skat_2bit``."""
+        unit_ptr = np.ascontiguousarray(unit_ptr, dtype=np.int64)
+        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        n_units = unit_ptr.size - 1
+        if var_idx.ndim != 1 or flip.shape != var_idx.shape or mean.shape != var_idx.shape or n_units < 0 \
+                or unit_ptr[-1] != var_idx.size:
+            raise ValueError("DosageBlock.skat: inconsistent CSR / table shapes")
+        sizes = np.diff(unit_ptr)
+        if (sizes < 0).any():
+            raise ValueError("DosageBlock.skat: unit_ptr not ascending")
+        offs = np.concatenate([[0], np.cumsum(sizes * sizes)])
+        score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
+        if var_idx.size:
+            check(self._L.sgx_ds_block_skat(self._sc._h, self._b, n_units, unit_ptr.ctypes.data, var_idx.ctypes.data,
+                                            flip.ctypes.data, mean.ctypes.data, score.ctypes.data, cov.ctypes.data))
+        return score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)]
 
     def close(self):
         if getattr(self, "_b", None):

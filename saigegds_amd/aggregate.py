@@ -18,7 +18,8 @@ That is the flow of 2-bit genotypes (``$dosage_alt``, the RAW branch of the refe
 input -- a format node such as ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` of uint8, int32 or
 float64 (the INTSXP / REALSXP branches) -- goes through ``DosageBlock`` in batches of consecutive units whose
 distinct variants fit a byte budget on the device: the rows of a batch are uploaded once, and counts, single-variant
-tests and the burden rows of every column of the driver are made from the resident rows (``_run_dosage``).
+tests and the burden rows of every column of the driver are made from the resident rows (``_run_dosage``); the SKAT
+driver (``skat.py``) takes its score statistics and covariance matrices from the same resident rows.
 """
 from __future__ import annotations
 
@@ -193,7 +194,13 @@ def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
     resident rows (a unit larger than that is a batch of its own).  Per batch: rows -> block (one upload), counts and
     single-variant tests into the per-variant arrays, weights, one burden call with every column of the driver.
     A variant that two batches share (sliding windows) is loaded in both.  Fills pr.n / s / maf / mac / pval and
-    pr.ds_out[kind] = (rows [n_units, n_weights, 8], valid)."""
+    pr.ds_out[kind] = (rows [n_units, n_weights, 8], valid).
+
+    Column kind ``"skat"`` (the SKAT driver's only kind) makes no burden rows: the batch's scan table is kept per
+    variant (pr.out [n, 8], pr.valid), and one ``blk.skat`` call per batch gives every unit its variants with
+    valid != 0 and mac > 0 (pr.skat_rows[u]), their score statistics and covariance (pr.skat_S[u], pr.skat_Phi[u]).
+    Its flip and mean come from the double sum ``s`` -- what the scan's own imputation 2 AF and its flip use -- not
+    from the truncated ``st``, which is a quirk of the reference's burden code only."""
     if "rare" in kinds and not pr.binary:
         return                                    # ACAT-V / ACAT-O of a quantitative trait: the driver raises, as the reference does
     n_samp = pr.sm.n
@@ -209,12 +216,19 @@ def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
         seen |= new
     batches.append(cur)
     pr.n_batches = len(batches)
+    skat = "skat" in kinds
+    kinds = tuple(k for k in kinds if k != "skat")
     nv_used, nu, nw, nk = used.size, len(index), pr.wbeta.shape[1], len(kinds)
     pr.n, pr.s, pr.st = np.zeros(nv_used), np.zeros(nv_used), np.zeros(nv_used, dtype=np.int64)
     pr.maf, pr.mac, pr.pval = np.full(nv_used, np.nan), np.full(nv_used, np.nan), np.full(nv_used, np.nan)
     out_all, valid_all = np.full((nu, nk * nw, 8), np.nan), np.zeros((nu, nk * nw), dtype=np.uint8)
     cap = max(np.unique(np.concatenate([index[u] for u in bt])).size for bt in batches)
+    if skat:
+        pr.out, pr.valid = np.full((nv_used, 8), np.nan), np.zeros(nv_used, dtype=np.uint8)
+        pr.skat_rows, pr.skat_S, pr.skat_Phi = [None] * nu, [None] * nu, [None] * nu
     with pr.sc.dosage_block(dtype, cap) as blk:
+        if skat and not hasattr(blk, "skat"):
+            raise NotImplementedError("SKAT on dosage input is not implemented.")
         for bt in batches:
             bv = np.unique(np.concatenate([index[u] for u in bt]))          # rows of the per-variant arrays
             rows = read_rows(used[bv] - 1)
@@ -230,6 +244,22 @@ def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
             pr.pval[bv] = np.where(valid != 0, out[:, 5], np.nan)          # single_test_*: NaN when the filter rejects
             # ds_mat_burden (:526-610): the mean and the flip from its `int sum` (st), weights normalised per column
             loc = {int(v): k for k, v in enumerate(bv)}
+            if skat:
+                pr.out[bv], pr.valid[bv] = out, valid
+                ok = (pr.valid != 0) & (pr.mac > 0)
+                kept = [index[u][ok[index[u]]] for u in bt]
+                rows_k = np.concatenate(kept)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    m = pr.s[rows_k] / pr.n[rows_k]
+                fl = pr.s[rows_k] > pr.n[rows_k]
+                unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])])
+                score, cov = blk.skat(unit_ptr, np.array([loc[int(v)] for v in rows_k], dtype=np.int32),
+                                      fl.astype(np.uint8), np.where(fl, 2 - m, m))
+                for k, u in enumerate(bt):
+                    pr.skat_rows[u], pr.skat_Phi[u] = kept[k], np.array(cov[k], dtype=np.float64)
+                    pr.skat_S[u] = np.array(score[unit_ptr[k]:unit_ptr[k + 1]], dtype=np.float64)
+            if not kinds:
+                continue
             grp_ptr, var_idx, flip, ws, mws = [0], [], [], [], []
             for u in bt:
                 r = index[u]

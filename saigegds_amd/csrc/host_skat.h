@@ -1,45 +1,42 @@
 // host_skat.h -- the SKAT set test's score vector and covariance matrix per unit from 2-bit rows in host
 // memory: the rows and tables go to the device once, kern_skat.h makes the Gram tiles and the dense sums, the host
-// turns them into S and Phi by the scan's own algebra in double.
+// turns them into S and Phi by the scan's own algebra in double.  The checks of the units, the tile
+// plan, the slab sum and that last step are functions of their own: sgx_ds_block_skat (host_skat_ds.h) runs the same
+// ones on the dosage rows of a resident block.
 // Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
 
 static const int SKAT_SLAB_DW = 256;                        // dwords (of 16 samples) per sample slab: cut by N alone
 static const size_t SKAT_PART_BYTES = (size_t)256 << 20;    // per-slab partial tiles of one launch
 
-extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t n_variants,
-	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut,
-	double *score, double *cov)
+// The units of a call: sizes first, so that nothing is read through a unit_ptr that is out of bounds, then the
+// indices against the n_rows rows they point into.
+static int skat_units_check(const char *who, size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, size_t n_rows)
 {
-	if (!h) return fail(SGX_EINVAL, "sgx_skat_2bit: NULL handle");
-	if (n_units == 0) return SGX_OK;
-	if (!packed || !unit_ptr || !var_idx || !lut || !score || !cov)
-		return fail(SGX_EINVAL, "sgx_skat_2bit: NULL buffer");
-	const int N = h->md.N, K = h->md.K, P = h->md.P, C = 2 * K + 1;
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	// the units' sizes first: nothing is read through a unit_ptr that is out of bounds
-	if (unit_ptr[0] != 0) return fail(SGX_EINVAL, "sgx_skat_2bit: bad unit_ptr");
+	if (unit_ptr[0] != 0) return fail(SGX_EINVAL, "%s: bad unit_ptr", who);
 	for (size_t u = 0; u < n_units; u++) {
 		const int64_t m = unit_ptr[u + 1] - unit_ptr[u];
-		if (m < 0) return fail(SGX_EINVAL, "sgx_skat_2bit: unit_ptr not ascending");
+		if (m < 0) return fail(SGX_EINVAL, "%s: unit_ptr not ascending", who);
 		if (m > SGX_SKAT_MAX_VARIANTS)
-			return fail(SGX_EINVAL, "sgx_skat_2bit: unit %zu has %lld variants, at most %d are supported", u, (long long)m, SGX_SKAT_MAX_VARIANTS);
+			return fail(SGX_EINVAL, "%s: unit %zu has %lld variants, at most %d are supported", who, u, (long long)m, SGX_SKAT_MAX_VARIANTS);
 	}
 	const int32_t *bad;
-	int rc = csr_check("sgx_skat_2bit", "unit_ptr", n_units, unit_ptr, var_idx, n_variants, &bad);
+	int rc = csr_check(who, "unit_ptr", n_units, unit_ptr, var_idx, n_rows, &bad);
 	if (rc) return rc;
-	if (bad) return fail(SGX_EINVAL, "sgx_skat_2bit: variant index %d out of range", *bad);
-	const int64_t nnz = unit_ptr[n_units];
-	if (nnz == 0) return SGX_OK;
-	rc = set_dev(h);
-	if (rc) return rc;
-	rc = sync_lane(h);
-	if (rc) return rc;
-	h->last_issued = h;
+	if (bad) return fail(SGX_EINVAL, "%s: variant index %d out of range", who, *bad);
+	return SGX_OK;
+}
 
-	// the tiles: per unit the variant tiles with tile_col >= tile_row, then the row tile against the 2K+1 columns of F
+// The tiles of a call: per unit the variant tiles with tile_col >= tile_row, then the row tile against the 2K+1
+// columns of F; tchunk of them per launch, so that their per-slab partial tiles fit SKAT_PART_BYTES.
+struct SkatPlan {
 	std::vector<SkatTile> tiles;
 	std::vector<uint32_t> tile_unit;
+	int nslab = 0;
+	size_t tchunk = 0;
+};
+
+static void skat_plan(SkatPlan &pl, size_t n_units, const int64_t *unit_ptr, int C, int nslab)
+{
 	const int n_dt = (C + 15) / 16;
 	for (size_t u = 0; u < n_units; u++) {
 		const int64_t e0 = unit_ptr[u], m = unit_ptr[u + 1] - e0;
@@ -49,53 +46,42 @@ extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 			t.row_e0 = e0 + 16 * tr; t.nrow = (int)std::min<int64_t>(16, m - 16 * tr);
 			for (int tc = tr; tc < n_vt; tc++) {
 				t.col_e0 = e0 + 16 * tc; t.ncol = (int)std::min<int64_t>(16, m - 16 * tc); t.dense = 0;
-				tiles.push_back(t); tile_unit.push_back((uint32_t)u);
+				pl.tiles.push_back(t); pl.tile_unit.push_back((uint32_t)u);
 			}
 			for (int dt = 0; dt < n_dt; dt++) {
 				t.col_e0 = 16 * dt; t.ncol = std::min(16, C - 16 * dt); t.dense = 1;
-				tiles.push_back(t); tile_unit.push_back((uint32_t)u);
+				pl.tiles.push_back(t); pl.tile_unit.push_back((uint32_t)u);
 			}
 		}
 	}
-	const size_t T = tiles.size();
-	const int ndw = (N + 15) >> 4, nslab = (ndw + SKAT_SLAB_DW - 1) / SKAT_SLAB_DW;
-	const size_t tchunk = std::min(T, std::max<size_t>(1, SKAT_PART_BYTES / ((size_t)nslab * 256 * sizeof(double))));
+	pl.nslab = nslab;
+	const size_t T = pl.tiles.size();
+	pl.tchunk = std::min(T, std::max<size_t>(1, SKAT_PART_BYTES / ((size_t)nslab * 256 * sizeof(double))));
+}
 
-	// device copies: the rows (dword stride) in the host-row pipeline's chunks, then entries, tables, tiles
-	const size_t dbpv = (size_t)ndw * 4;
-	const size_t o_idx = (n_variants * dbpv + 15) & ~(size_t)15;
-	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
-	const size_t o_til = o_lut + (size_t)nnz * 4 * sizeof(double);
-	const size_t need = o_til + T * sizeof(SkatTile);
-	rc = grow(h->stage_pk, h->stage_pk_cap, need);
-	if (rc) return rc;
-	rc = grow(h->skat_part, h->skat_part_cap, tchunk * (size_t)nslab * 256);
+// The plan's tiles, tchunk at a time: launch(t0, nt) queues the Gram kernel of tiles [t0, t0 + nt) into h->skat_part
+// (grown here, with h->skat_fin); the slabs are added in slab order and the tiles scattered: W into cov (upper
+// triangle, unit by unit), the dense sums into `dense` [entry][2K+1].
+template <class Launch>
+static int skat_run(sgx_handle *h, const SkatPlan &pl, size_t n_units, const int64_t *unit_ptr, int C, Launch launch,
+	std::vector<double> &dense, double *cov)
+{
+	const size_t T = pl.tiles.size(), tchunk = pl.tchunk;
+	const int nslab = pl.nslab;
+	int rc = grow(h->skat_part, h->skat_part_cap, tchunk * (size_t)nslab * 256);
 	if (rc) return rc;
 	rc = grow(h->skat_fin, h->skat_fin_cap, tchunk * 256);
 	if (rc) return rc;
-	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
-	for (size_t off = 0; off < n_variants; off += rchunk) {
-		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), h->stream);
-		if (rc) return rc;
-	}
-	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut, (size_t)nnz * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_til, tiles.data(), T * sizeof(SkatTile), hipMemcpyHostToDevice, h->stream));
-
-	// W into cov (upper triangle, unit by unit), the dense sums into `dense` [entry][2K+1]
 	std::vector<size_t> cov_off(n_units + 1, 0);
 	for (size_t u = 0; u < n_units; u++) {
 		const size_t m = (size_t)(unit_ptr[u + 1] - unit_ptr[u]);
 		cov_off[u + 1] = cov_off[u] + m * m;
 	}
-	std::vector<double> dense((size_t)nnz * C), fin(tchunk * 256);
+	dense.assign((size_t)unit_ptr[n_units] * C, 0.0);
+	std::vector<double> fin(tchunk * 256);
 	for (size_t t0 = 0; t0 < T; t0 += tchunk) {
 		const size_t nt = std::min(tchunk, T - t0);
-		hipLaunchKernelGGL(skat_gram_kernel, dim3((unsigned)nt, (unsigned)nslab), dim3(64), 0, h->stream,
-			h->stage_pk, dbpv, N, reinterpret_cast<const int *>(h->stage_pk + o_idx),
-			reinterpret_cast<const double *>(h->stage_pk + o_lut), h->dF, P,
-			reinterpret_cast<const SkatTile *>(h->stage_pk + o_til) + t0, nt, SKAT_SLAB_DW, h->skat_part);
+		launch(t0, nt);
 		HIPCHK(hipGetLastError());
 		hipLaunchKernelGGL(skat_reduce_kernel, dim3((unsigned)nt), dim3(256), 0, h->stream,
 			h->skat_part, nt * 256, nslab, h->skat_fin);
@@ -103,9 +89,9 @@ extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 		HIPCHK(hipMemcpyAsync(fin.data(), h->skat_fin, nt * 256 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
 		for (size_t k = 0; k < nt; k++) {
-			const SkatTile &t = tiles[t0 + k];
+			const SkatTile &t = pl.tiles[t0 + k];
 			const double *f = &fin[k * 256];
-			const size_t u = tile_unit[t0 + k];
+			const size_t u = pl.tile_unit[t0 + k];
 			const int64_t e0 = unit_ptr[u];
 			const size_t m = (size_t)(unit_ptr[u + 1] - e0), r0 = (size_t)(t.row_e0 - e0);
 			if (t.dense) {
@@ -119,15 +105,24 @@ extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 			}
 		}
 	}
+	return SGX_OK;
+}
 
-	// S_j = s_j - S_a c'_j;  Phi_jl = r (c'_j XVX c'_l + W_jl - e_j c'_l - e_l c'_j), j <= l, mirrored
-	const DevModel &md = h->md;
+// From the dense sums [entry][2K+1] (c', e, s of DESIGN.md 3.1) and W (the upper triangles in cov) to
+//     S_j = s_j - S_a c'_j;  Phi_jl = r (c'_j XVX c'_l + W_jl - e_j c'_l - e_l c'_j), j <= l, mirrored
+// -- the one place where this is done, for 2-bit rows and for dosage rows.
+static void skat_finish(const DevModel &md, size_t n_units, const int64_t *unit_ptr, const std::vector<double> &dense,
+	double *score, double *cov)
+{
+	const int K = md.K, C = 2 * K + 1;
 	std::vector<double> q;
+	size_t off = 0;
 	for (size_t u = 0; u < n_units; u++) {
 		const int64_t e0 = unit_ptr[u];
 		const size_t m = (size_t)(unit_ptr[u + 1] - e0);
 		if (m == 0) continue;
-		double *phi = cov + cov_off[u];
+		double *phi = cov + off;
+		off += m * m;
 		q.assign(m * K, 0.0);
 		for (size_t j = 0; j < m; j++) {
 			const double *cj = &dense[(size_t)(e0 + j) * C];
@@ -153,5 +148,60 @@ extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 			}
 		}
 	}
+}
+
+extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t n_variants,
+	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut,
+	double *score, double *cov)
+{
+	if (!h) return fail(SGX_EINVAL, "sgx_skat_2bit: NULL handle");
+	if (n_units == 0) return SGX_OK;
+	if (!packed || !unit_ptr || !var_idx || !lut || !score || !cov)
+		return fail(SGX_EINVAL, "sgx_skat_2bit: NULL buffer");
+	const int N = h->md.N, K = h->md.K, P = h->md.P, C = 2 * K + 1;
+	if (bpv < (size_t)(N + 3) / 4)
+		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
+	int rc = skat_units_check("sgx_skat_2bit", n_units, unit_ptr, var_idx, n_variants);
+	if (rc) return rc;
+	const int64_t nnz = unit_ptr[n_units];
+	if (nnz == 0) return SGX_OK;
+	rc = set_dev(h);
+	if (rc) return rc;
+	rc = sync_lane(h);
+	if (rc) return rc;
+	h->last_issued = h;
+
+	const int ndw = (N + 15) >> 4;
+	SkatPlan pl;
+	skat_plan(pl, n_units, unit_ptr, C, (ndw + SKAT_SLAB_DW - 1) / SKAT_SLAB_DW);
+	const size_t T = pl.tiles.size();
+
+	// device copies: the rows (dword stride) in the host-row pipeline's chunks, then entries, tables, tiles
+	const size_t dbpv = (size_t)ndw * 4;
+	const size_t o_idx = (n_variants * dbpv + 15) & ~(size_t)15;
+	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
+	const size_t o_til = o_lut + (size_t)nnz * 4 * sizeof(double);
+	const size_t need = o_til + T * sizeof(SkatTile);
+	rc = grow(h->stage_pk, h->stage_pk_cap, need);
+	if (rc) return rc;
+	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
+	for (size_t off = 0; off < n_variants; off += rchunk) {
+		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), h->stream);
+		if (rc) return rc;
+	}
+	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut, (size_t)nnz * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_til, pl.tiles.data(), T * sizeof(SkatTile), hipMemcpyHostToDevice, h->stream));
+
+	std::vector<double> dense;
+	rc = skat_run(h, pl, n_units, unit_ptr, C, [&](size_t t0, size_t nt) {
+		hipLaunchKernelGGL(skat_gram_kernel, dim3((unsigned)nt, (unsigned)pl.nslab), dim3(64), 0, h->stream,
+			h->stage_pk, dbpv, N, reinterpret_cast<const int *>(h->stage_pk + o_idx),
+			reinterpret_cast<const double *>(h->stage_pk + o_lut), h->dF, P,
+			reinterpret_cast<const SkatTile *>(h->stage_pk + o_til) + t0, nt, SKAT_SLAB_DW, h->skat_part);
+	}, dense, cov);
+	if (rc) return rc;
+	skat_finish(h->md, n_units, unit_ptr, dense, score, cov);
 	return SGX_OK;
 }

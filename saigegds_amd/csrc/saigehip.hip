@@ -75,6 +75,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_dbit2.h"
 #include "kern_quant.h"
 #include "kern_skat.h"
+#include "kern_skat_ds.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -87,5 +88,6 @@ static int fail(int code, const char *fmt, ...)
 #include "host_pipeline.h"
 #include "host_burden_ds.h"
 #include "host_skat.h"
+#include "host_skat_ds.h"
 #include "host_util.h"
 #include "host_grm.h"

@@ -11,15 +11,21 @@ burden paths by identities (tests/test_gpu_skat.py).  The flow of 
    matrix of the unit's 2-bit rows on the device's matrix cores;
 3. on the host, per unit and weight column: the SPA adjustment of ``Phi`` (binary traits), ``Q = sum w_j^2 S_j^2`` and
    its p-value under the mixture of chi-squares with the eigenvalues of ``diag(w) Phi diag(w)``.
+
+Dosage input (a format node such as ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` that does not reduce
+to hard calls) takes the aggregate drivers' dosage flow instead of 1 and 2: per batch of units the rows go to a
+resident ``DosageBlock`` once, ``blk.scan()`` gives the per-variant table and ``blk.skat()`` (``sgx_ds_block_skat``)
+``S`` and ``Phi`` of the batch's units; step 3 is the same code.
 """
 from __future__ import annotations
 
 import math
-from typing import Any, Dict
+from typing import Any, Dict, Optional
 
 import numpy as np
 
 from .aggregate import AggrParamBeta, _dbeta, _prepare, _save, _summary_cols
+from .assoc import GenotypeSource
 
 LAMBDA_DROP = 1e-10      # eigenvalues at or below this fraction of the largest one are dropped
 SERIES_X = 0.05          # |2 t lambda_k| below which a term's functions are summed as power series
@@ -120,50 +126,17 @@ def pchisq_mix(q: float, lam) -> float:
     return float(ndtr(-z))
 
 
-def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: str = "", spa_pval: float = 0.05,
-                         var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
-                         parallel=False, verbose: bool = True, verbose_maf: bool = True,
-                         scanner_factory=None) -> Dict[str, Any]:
-    """SKAT per unit and weight set on hard calls (not in the reference; arguments as ``seqAssocGLMM_spaBurden``).
-
-    Per unit: the variants that pass the scan at thresholds 0 / 0 / 1 with mac > 0; their score statistics ``S`` and
-    covariance ``Phi`` (``sgx_skat_2bit``, one call for all units).  Binary traits: where a variant went through the
-    SPA stage (p.norm <= spa.pval) and it converged with 0 < pval != p.norm and S_j != 0, row and column j of ``Phi``
-    are scaled by the square root of ``d_j = S_j^2 / (Phi_jj qchisq(pval_j, 1, upper))``, so that the variant's own
-    chi-square under the scaled variance gives its SPA p-value.  Per weight column (a, b): ``w_j = dbeta(maf_j, a, b)``,
-    ``Q = sum w_j^2 S_j^2``, ``pval = pchisq_mix(Q, eigvalsh(diag(w) Phi diag(w)))``.  Columns: those of the burden
-    driver's summary, ``n.var`` (variants in the test), ``Q`` and ``pval`` (suffix ``.b<a>_<b>`` with more than one
-    weight set).  A unit with no variant left gives NaN."""
+def _unit_tests(pr, kept, S_of, phi_of):
+    """Step 3 of the flow for every unit: ``kept[u]`` the unit's variants (rows of pr.out / pr.maf), ``S_of(u)`` and
+    ``phi_of(u)`` their score statistics and covariance -> (Q, pval), [n_units, n_weights] each."""
     from scipy.special import chdtri
-    if not isinstance(dsnode, str):
-        raise TypeError("is.character(dsnode) is not TRUE")
-    if dsnode != "":
-        raise NotImplementedError("SKAT on dosage input is not implemented.")
-    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT analysis:", scanner_factory)
-    try:
-        if pr.ds_out is not None:
-            raise NotImplementedError("SKAT on dosage input is not implemented.")
-        ans = _summary_cols(pr)
-        ok = (pr.valid != 0) & (pr.mac > 0)
-        kept = [np.asarray(r, dtype=np.int64)[ok[np.asarray(r, dtype=np.int64)]] for r in pr.rows]
-        var_idx = np.concatenate(kept).astype(np.int32) if kept else np.zeros(0, dtype=np.int32)
-        unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])]).astype(np.int64)
-        n, s = pr.n[var_idx], pr.s[var_idx]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            m = s / n                                               # (double)sum / n, as _burden_rows
-        flip = s > n
-        lut = np.where(flip[:, None], np.stack([2 + 0 * m, 1 + 0 * m, 0 * m, 2 - m], axis=1),
-                       np.stack([0 * m, 1 + 0 * m, 2 + 0 * m, m], axis=1))
-        score, cov = pr.sc.skat_2bit(pr.packed, unit_ptr, var_idx, lut)
-    finally:
-        pr.sc.close()
     nu, nw = len(kept), pr.wbeta.shape[1]
     Q, P = np.full((nu, nw), np.nan), np.full((nu, nw), np.nan)
     for u, r in enumerate(kept):
         if r.size == 0:
             continue
-        S = np.asarray(score[unit_ptr[u]:unit_ptr[u + 1]], dtype=np.float64)
-        phi = np.array(cov[u], dtype=np.float64)
+        S = np.asarray(S_of(u), dtype=np.float64)
+        phi = np.array(phi_of(u), dtype=np.float64)
         if pr.binary:
             o = pr.out[r]
             pv, pn, cvg = o[:, 5], o[:, 6], o[:, 7]
@@ -178,6 +151,58 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
             wp = phi * w[:, None] * w[None, :]
             if np.all(np.isfinite(wp)) and math.isfinite(Q[u, i]):
                 P[u, i] = pchisq_mix(Q[u, i], np.linalg.eigvalsh(wp))
+    return Q, P
+
+
+def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: str = "", spa_pval: float = 0.05,
+                         var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
+                         parallel=False, verbose: bool = True, verbose_maf: bool = True,
+                         scanner_factory=None, ds_budget: Optional[int] = None) -> Dict[str, Any]:
+    """SKAT per unit and weight set (not in the reference; arguments as ``seqAssocGLMM_spaBurden``), on hard calls or
+    on dosages (``dsnode``, or a file without ``genotype/data``, or an in-memory dosage matrix that is float64 or holds
+    more than hard calls; ``ds_budget``: bytes of resident dosage rows per batch of units).
+
+    Per unit: the variants that pass the scan at thresholds 0 / 0 / 1 with mac > 0; their score statistics ``S`` and
+    covariance ``Phi`` (``sgx_skat_2bit``, one call for all units; dosages: ``sgx_ds_block_skat``, one call per batch,
+    with the mean and the flip of the scan: ``s / n`` and ``s > n`` of the double sum ``s``).  Binary traits: where a
+    variant went through the SPA stage (p.norm <= spa.pval) and it converged with 0 < pval != p.norm and S_j != 0, row
+    and column j of ``Phi`` are scaled by the square root of ``d_j = S_j^2 / (Phi_jj qchisq(pval_j, 1, upper))``, so
+    that the variant's own chi-square under the scaled variance gives its SPA p-value.  Per weight column (a, b):
+    ``w_j = dbeta(maf_j, a, b)``, ``Q = sum w_j^2 S_j^2``, ``pval = pchisq_mix(Q, eigvalsh(diag(w) Phi diag(w)))``.
+    Columns: those of the burden driver's summary, ``n.var`` (variants in the test), ``Q`` and ``pval`` (suffix
+    ``.b<a>_<b>`` with more than one weight set).  A unit with no variant left gives NaN.
+
+    Two kinds of dosage input are refused with ``NotImplementedError`` (both pinned by
+    tests/test_skat.py::test_driver_refuses_dosage_input): a non-empty ``dsnode`` together with an in-memory source of
+    packed rows, which has no nodes; and a scanner whose ``dosage_block(...)`` object has no ``skat`` method (checked
+    right after the block is made, before any row is read; the scanner is closed)."""
+    if not isinstance(dsnode, str):
+        raise TypeError("is.character(dsnode) is not TRUE")
+    if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
+        raise NotImplementedError("SKAT on dosage input is not implemented.")
+    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT analysis:", scanner_factory,
+                  dsnode, ("skat",), ds_budget=ds_budget)
+    try:
+        ans = _summary_cols(pr)
+        if pr.ds_out is not None:
+            kept = pr.skat_rows
+            S_of, phi_of = pr.skat_S.__getitem__, pr.skat_Phi.__getitem__
+        else:
+            ok = (pr.valid != 0) & (pr.mac > 0)
+            kept = [np.asarray(r, dtype=np.int64)[ok[np.asarray(r, dtype=np.int64)]] for r in pr.rows]
+            var_idx = np.concatenate(kept).astype(np.int32) if kept else np.zeros(0, dtype=np.int32)
+            unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])]).astype(np.int64)
+            n, s = pr.n[var_idx], pr.s[var_idx]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                m = s / n                                               # (double)sum / n, as _burden_rows
+            flip = s > n
+            lut = np.where(flip[:, None], np.stack([2 + 0 * m, 1 + 0 * m, 0 * m, 2 - m], axis=1),
+                           np.stack([0 * m, 1 + 0 * m, 2 + 0 * m, m], axis=1))
+            score, cov = pr.sc.skat_2bit(pr.packed, unit_ptr, var_idx, lut)
+            S_of, phi_of = (lambda u: score[unit_ptr[u]:unit_ptr[u + 1]]), cov.__getitem__
+    finally:
+        pr.sc.close()
+    Q, P = _unit_tests(pr, kept, S_of, phi_of)
     ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
     for i, nm in enumerate(pr.wb_colnm):
         sfx = f".{nm}" if len(pr.wb_colnm) > 1 else ""
