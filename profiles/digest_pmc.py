@@ -46,7 +46,7 @@ for k in sorted(set(rd) | set(wr)):
     write_b = wr[k].get("WRITE_SIZE", 0.0) * 1024
     kern[k] = {"launches": nr[k], "read_bytes_per_step": read_b / steps, "write_bytes_per_step": write_b / steps,
                "fetch_doubled": bool(wide)}
-score = [v for k, v in kern.items() if k.startswith("score3_kernel") or k.startswith("score_mfma_kernel")]
+score = [v for k, v in kern.items() if k.startswith(("score3_kernel", "score_mfma_kernel", "grm_contract_kernel"))]
 spa = [v for k, v in kern.items() if k.startswith("spa")]
 lists = [v for k, v in kern.items() if k.startswith("s3_lists_t3_kernel") or k.startswith("s3_lists_kernel")]
 out = dict(meta)

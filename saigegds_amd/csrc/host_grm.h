@@ -3,6 +3,14 @@
 
 // ===========================================================================
 // Implicit-GRM operator of the null-model fit (kern_grm.h)
+// Products and solves work on k right-hand sides at once; the single-vector entry points are k = 1.
+// Pass 1 puts two columns' limbs side by side in each 16-column B fragment (7 + 7 limbs) and runs
+// the contraction kernel with up to GRM_MAXF = 3 value fragments (GRM_GROUP = 6 columns); pass 2 needs
+// x and gam limbs of a column (7 + 7) in one fragment and runs with up to 3 (GRM_GROUP2).  A group of 6
+// columns thus streams the genotypes three times (G once, Gt twice) where 6 single products stream
+// them 12 times.
+
+#define GRM_RED_BLOCKS 256
 
 struct sgx_grm {
 	int device = 0;
@@ -11,75 +19,33 @@ struct sgx_grm {
 	size_t bpvN = 0, bpvM = 0;             // row strides of G (marker-major) and Gt (sample-major)
 	uint8_t *G = nullptr, *Gt = nullptr;
 	double *af = nullptr, *inv = nullptr, *l0 = nullptr, *diag = nullptr;
-	MfTab tbN{}, tbM{};                    // limb tiles over samples / over markers
-	uint8_t *FlN = nullptr, *FlM = nullptr;
-	int *accV = nullptr, *accS = nullptr;  // [M][32], [N][32]
-	double *xv = nullptr, *gv = nullptr;   // [M]
-	unsigned long long *maxb = nullptr;    // [3]: b, x, gam
-	double *part = nullptr, *h_part = nullptr;   // 256 block partials (device / pinned)
-	double *vb = nullptr, *vout = nullptr; // [N] staging for host-pointer calls
-	double *r = nullptr, *z = nullptr, *p = nullptr, *x = nullptr, *Ap = nullptr, *minv = nullptr, *w = nullptr;
+	int ntileN = 0, ntileM = 0;            // 256-entry limb tiles over samples / over markers
+	uint8_t *FlN = nullptr, *FlM = nullptr;          // limb tile images, 16 GRM_MAXF columns wide
+	int *accV = nullptr, *accS = nullptr;            // [M][32 GRM_MAXF], [N][32 GRM_MAXF]
+	double *xv = nullptr, *gv = nullptr;             // [GRM_GROUP][M]
+	unsigned long long *maxb = nullptr;              // [GRM_MAX_RHS][3]: b, x, gam
+	double *part = nullptr, *h_part = nullptr;       // [2 * GRM_MAX_RHS][GRM_RED_BLOCKS] block partials (device / pinned)
+	double *minv = nullptr, *w = nullptr;            // [N]
 	int n_cu = 256;
-	struct GrmMulti *multi = nullptr;      // scratch of the batched calls (allocated by the first one)
+	int kcap = 0;                          // columns the [k][N] vectors below have room for (the largest k seen)
+	double *B = nullptr, *O = nullptr;               // [k][N] staging of host-pointer calls
+	double *R = nullptr, *Z = nullptr, *P = nullptr, *X = nullptr, *AP = nullptr, *GP = nullptr;   // [k][N]
 };
+static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
 
-static void grm_multi_release(sgx_grm *g);
-
-#define GRM_RED_BLOCKS 256
-
-static int grm_sum(sgx_grm *g, const double *a, const double *b, size_t n, double *out)
+// room for k columns (k <= GRM_MAX_RHS) in the [k][N] vectors
+static hipError_t grm_reserve(sgx_grm *g, int k)
 {
-	if (b) hipLaunchKernelGGL((dot_partial_kernel<true>), dim3(GRM_RED_BLOCKS), dim3(256), 0, g->stream, a, b, n, g->part);
-	else hipLaunchKernelGGL((dot_partial_kernel<false>), dim3(GRM_RED_BLOCKS), dim3(256), 0, g->stream, a, b, n, g->part);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(g->h_part, g->part, GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-	HIPCHK(hipStreamSynchronize(g->stream));
-	double s = 0;
-	for (int i = 0; i < GRM_RED_BLOCKS; i++) s += g->h_part[i];   // fixed order
-	*out = s;
-	return SGX_OK;
-}
-
-static dim3 grm_mfma_grid(const sgx_grm *g, size_t rows, int ntile, int *tps)
-{
-	return mf_grid(g->n_cu, rows, ntile, tps);
-}
-
-// out = G'(G b)/M, device vectors (get_crossprod_b_grm, saige_fitnull.cpp:435-536)
-static int grm_matvec_dev(sgx_grm *g, const double *b, double *out)
-{
-	hipStream_t st = g->stream;
-	const size_t N = (size_t)g->N, M = g->M;
-	const size_t lds = (size_t)2 * 16 * GRM_NCOL * 16;
-	double sum_b = 0, C0 = 0;
-	int rc = grm_sum(g, b, nullptr, N, &sum_b);
-	if (rc) return rc;
-	// ---- pass 1: per marker, over samples
-	HIPCHK(hipMemsetAsync(g->maxb, 0, 3 * sizeof(unsigned long long), st));
-	hipLaunchKernelGGL(absmax_kernel, dim3(GRM_RED_BLOCKS), dim3(256), 0, st, b, N, g->maxb);
-	hipLaunchKernelGGL(limbs_kernel, dim3(512), dim3(256), 0, st, b, N, (size_t)g->tbN.ntile * 256, 0, g->maxb, g->FlN);
-	HIPCHK(hipMemsetAsync(g->accV, 0, M * GRM_NACC * sizeof(int), st));
-	int tps = 0;
-	dim3 grid = grm_mfma_grid(g, M, g->tbN.ntile, &tps);
-	hipLaunchKernelGGL((score_mfma_kernel<1, false, true>), grid, dim3(WAVE * MF_WAVES), lds, st, g->G, g->bpvN, (int)M, g->tbN, tps, g->accV, GRM_NACC);
-	hipLaunchKernelGGL(grm_dot_epilogue, dim3(GRM_RED_BLOCKS), dim3(256), 0, st, M, g->accV, g->maxb, sum_b,
-		g->af, g->inv, g->l0, g->xv, g->gv, g->part);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(g->h_part, g->part, GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	for (int i = 0; i < GRM_RED_BLOCKS; i++) C0 += g->h_part[i];
-	// ---- pass 2: per sample, over markers
-	hipLaunchKernelGGL(absmax_kernel, dim3(GRM_RED_BLOCKS), dim3(256), 0, st, g->xv, M, g->maxb + 1);
-	hipLaunchKernelGGL(absmax_kernel, dim3(GRM_RED_BLOCKS), dim3(256), 0, st, g->gv, M, g->maxb + 2);
-	hipLaunchKernelGGL(limbs_kernel, dim3(512), dim3(256), 0, st, g->xv, M, (size_t)g->tbM.ntile * 256, 0, g->maxb + 1, g->FlM);
-	hipLaunchKernelGGL(limbs_kernel, dim3(512), dim3(256), 0, st, g->gv, M, (size_t)g->tbM.ntile * 256, MF_NLIMB, g->maxb + 2, g->FlM);
-	HIPCHK(hipMemsetAsync(g->accS, 0, N * GRM_NACC * sizeof(int), st));
-	grid = grm_mfma_grid(g, N, g->tbM.ntile, &tps);
-	hipLaunchKernelGGL((score_mfma_kernel<1, false, true>), grid, dim3(WAVE * MF_WAVES), lds, st, g->Gt, g->bpvM, g->N, g->tbM, tps, g->accS, GRM_NACC);
-	hipLaunchKernelGGL(grm_out_epilogue, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g->N, M, g->accS,
-		g->maxb + 1, g->maxb + 2, C0, g->diag, out);
-	HIPCHK(hipGetLastError());
-	return SGX_OK;
+	if (k <= g->kcap) return hipSuccess;
+	g->kcap = 0;
+	for (double **p : {&g->B, &g->O, &g->R, &g->Z, &g->P, &g->X, &g->AP, &g->GP}) {
+		hipError_t e = *p ? hipFree(*p) : hipSuccess;
+		*p = nullptr;
+		if (e == hipSuccess) e = hipMalloc((void **)p, (size_t)k * g->N * sizeof(double));
+		if (e != hipSuccess) return e;
+	}
+	g->kcap = k;
+	return hipSuccess;
 }
 
 extern "C" void sgx_grm_free(sgx_grm *g)
@@ -87,9 +53,8 @@ extern "C" void sgx_grm_free(sgx_grm *g)
 	if (!g) return;
 	(void)hipSetDevice(g->device);
 	if (g->stream) (void)hipStreamSynchronize(g->stream);
-	grm_multi_release(g);
 	void *ptrs[] = {g->G, g->Gt, g->af, g->inv, g->l0, g->diag, g->FlN, g->FlM, g->accV, g->accS, g->xv, g->gv,
-		g->maxb, g->part, g->vb, g->vout, g->r, g->z, g->p, g->x, g->Ap, g->minv, g->w};
+		g->maxb, g->part, g->minv, g->w, g->B, g->O, g->R, g->Z, g->P, g->X, g->AP, g->GP};
 	for (void *p : ptrs) (void)hipFree(p);
 	if (g->h_part) (void)hipHostFree(g->h_part);
 	if (g->stream) (void)hipStreamDestroy(g->stream);
@@ -139,6 +104,8 @@ static int grm_init_impl(const uint8_t *packed, size_t bytes_per_marker, int32_t
 	g->N = n_samp; g->M = M;
 	g->bpvN = sgx_row_stride(n_samp);
 	g->bpvM = (size_t)((M + 511) / 512) * 128;
+	g->ntileN = 2 * (int)((N + 511) / 512);
+	g->ntileM = 2 * (int)((M + 511) / 512);
 	GTRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
 	GTRY(hipMalloc((void **)&g->G, M * g->bpvN));
 	GTRY(hipMalloc((void **)&g->Gt, N * g->bpvM));
@@ -146,26 +113,19 @@ static int grm_init_impl(const uint8_t *packed, size_t bytes_per_marker, int32_t
 	GTRY(hipMemsetAsync(g->Gt, 0, N * g->bpvM, g->stream));
 	GTRY(hipMemcpy2DAsync(g->G, g->bpvN, packed, bytes_per_marker, std::min(bytes_per_marker, g->bpvN), M,
 		kind, g->stream));
-	for (double **p : {&g->af, &g->inv, &g->l0, &g->xv, &g->gv}) GTRY(hipMalloc((void **)p, M * sizeof(double)));
-	for (double **p : {&g->diag, &g->vb, &g->vout, &g->r, &g->z, &g->p, &g->x, &g->Ap, &g->minv, &g->w})
-		GTRY(hipMalloc((void **)p, N * sizeof(double)));
-	GTRY(hipMalloc((void **)&g->maxb, 3 * sizeof(unsigned long long)));
-	GTRY(hipMalloc((void **)&g->part, GRM_RED_BLOCKS * sizeof(double)));
-	GTRY(hipHostMalloc((void **)&g->h_part, GRM_RED_BLOCKS * sizeof(double), hipHostMallocDefault));
-	auto mk = [&](MfTab &tb, size_t n, uint8_t **Fl) -> hipError_t {
-		tb = MfTab{};
-		tb.ntile = 2 * (int)((n + 511) / 512);
-		const size_t bytes = (size_t)tb.ntile * 16 * GRM_NCOL * 16;
-		hipError_t ee = hipMalloc((void **)Fl, bytes);
-		if (ee != hipSuccess) return ee;
-		ee = hipMemsetAsync(*Fl, 0, bytes, g->stream);
-		tb.Fl = *Fl;
-		return ee;
-	};
-	GTRY(mk(g->tbN, N, &g->FlN));
-	GTRY(mk(g->tbM, M, &g->FlM));
-	GTRY(hipMalloc((void **)&g->accV, M * GRM_NACC * sizeof(int)));
-	GTRY(hipMalloc((void **)&g->accS, N * GRM_NACC * sizeof(int)));
+	for (double **p : {&g->af, &g->inv, &g->l0}) GTRY(hipMalloc((void **)p, M * sizeof(double)));
+	for (double **p : {&g->diag, &g->minv, &g->w}) GTRY(hipMalloc((void **)p, N * sizeof(double)));
+	// scratch of a product: every launch zeroes what it reads of it
+	GTRY(hipMalloc((void **)&g->FlN, (size_t)g->ntileN * 16 * (16 * GRM_MAXF) * 16));
+	GTRY(hipMalloc((void **)&g->FlM, (size_t)g->ntileM * 16 * (16 * GRM_MAXF) * 16));
+	GTRY(hipMalloc((void **)&g->accV, M * 32 * GRM_MAXF * sizeof(int)));
+	GTRY(hipMalloc((void **)&g->accS, N * 32 * GRM_MAXF * sizeof(int)));
+	GTRY(hipMalloc((void **)&g->xv, GRM_GROUP * M * sizeof(double)));
+	GTRY(hipMalloc((void **)&g->gv, GRM_GROUP * M * sizeof(double)));
+	GTRY(hipMalloc((void **)&g->maxb, GRM_MAX_RHS * 3 * sizeof(unsigned long long)));
+	GTRY(hipMalloc((void **)&g->part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double)));
+	GTRY(hipHostMalloc((void **)&g->h_part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double), hipHostMallocDefault));
+	GTRY(grm_reserve(g, 1));
 	// marker statistics, transpose, diag(GRM)
 	hipLaunchKernelGGL(grm_marker_stats, dim3((unsigned)M), dim3(256), 0, g->stream, g->G, g->bpvN, g->N, M, g->af, g->inv, g->l0);
 	hipLaunchKernelGGL(transpose_2bit, dim3((unsigned)((N + 255) / 256), (unsigned)((M + 63) / 64)), dim3(256), 0, g->stream,
@@ -187,73 +147,6 @@ extern "C" int sgx_grm_diag(sgx_grm *g, double *diag_out)
 	return SGX_OK;
 }
 
-// get_crossprod_b_grm: out = GRM b, host vectors of length N
-extern "C" int sgx_grm_crossprod(sgx_grm *g, const double *b, double *out)
-{
-	if (!g || !b || !out) return fail(SGX_EINVAL, "sgx_grm_crossprod: NULL argument");
-	HIPCHK(hipSetDevice(g->device));
-	const size_t nb = (size_t)g->N * sizeof(double);
-	HIPCHK(hipMemcpyAsync(g->vb, b, nb, hipMemcpyHostToDevice, g->stream));
-	int rc = grm_matvec_dev(g, g->vb, g->vout);
-	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(out, g->vout, nb, hipMemcpyDeviceToHost, g->stream));
-	HIPCHK(hipStreamSynchronize(g->stream));
-	return SGX_OK;
-}
-
-// PCG_diag_sigma (saige_fitnull.cpp:581-614): solves (tau0 diag(1/w) + tau1 GRM) x = b
-extern "C" int sgx_grm_pcg(sgx_grm *g, const double *w, const double *tau, const double *b,
-	int maxiter, double tol, double *x_out, int *iters_out)
-{
-	if (!g || !w || !tau || !b || !x_out) return fail(SGX_EINVAL, "sgx_grm_pcg: NULL argument");
-	HIPCHK(hipSetDevice(g->device));
-	hipStream_t st = g->stream;
-	const int n = g->N;
-	const size_t nb = (size_t)n * sizeof(double);
-	const dim3 gr((unsigned)((n + 255) / 256)), bl(256);
-	const double tau0 = tau[0], tau1 = tau[1];
-	HIPCHK(hipMemcpyAsync(g->w, w, nb, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(g->vb, b, nb, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(pcg_minv_kernel, gr, bl, 0, st, n, g->w, g->diag, tau0, tau1, g->minv);
-	hipLaunchKernelGGL(pcg_init_kernel, gr, bl, 0, st, n, g->vb, g->minv, g->r, g->z, g->p, g->x);
-	int iter = 0, rc;
-	double rr = 0, rz = 0;
-	if ((rc = grm_sum(g, g->r, g->r, n, &rr))) return rc;
-	if ((rc = grm_sum(g, g->r, g->z, n, &rz))) return rc;
-	while (iter < maxiter && rr > tol) {
-		iter++;
-		const double *gp = nullptr;
-		if (tau1 != 0) {                       // get_crossprod :569-575
-			if ((rc = grm_matvec_dev(g, g->p, g->vout))) return rc;
-			gp = g->vout;
-		}
-		hipLaunchKernelGGL(pcg_ap_kernel, gr, bl, 0, st, n, g->p, g->w, gp, tau0, tau1, g->Ap);
-		double pAp = 0;
-		if ((rc = grm_sum(g, g->p, g->Ap, n, &pAp))) return rc;
-		const double a = rz / pAp;
-		hipLaunchKernelGGL(pcg_update_kernel, gr, bl, 0, st, n, a, g->p, g->Ap, g->minv, g->x, g->r, g->z);
-		double rz1 = 0;
-		if ((rc = grm_sum(g, g->z, g->r, n, &rz1))) return rc;
-		const double bet = rz1 / rz;
-		hipLaunchKernelGGL(pcg_dir_kernel, gr, bl, 0, st, n, bet, g->z, g->p);
-		rz = rz1;
-		if ((rc = grm_sum(g, g->r, g->r, n, &rr))) return rc;
-	}
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(x_out, g->x, nb, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	if (iters_out) *iters_out = iter;
-	return SGX_OK;
-}
-
-// out = GRM b with b, out device vectors of N doubles (asynchronous until sgx_grm_sync)
-extern "C" int sgx_grm_crossprod_dev(sgx_grm *g, const double *b_dev, double *out_dev)
-{
-	if (!g || !b_dev || !out_dev) return fail(SGX_EINVAL, "sgx_grm_crossprod_dev: NULL argument");
-	HIPCHK(hipSetDevice(g->device));
-	return grm_matvec_dev(g, b_dev, out_dev);
-}
-
 extern "C" int sgx_grm_sync(sgx_grm *g)
 {
 	if (!g) return fail(SGX_EINVAL, "sgx_grm_sync: NULL handle");
@@ -262,127 +155,63 @@ extern "C" int sgx_grm_sync(sgx_grm *g)
 	return SGX_OK;
 }
 
-// ===========================================================================
-// Several right-hand sides at once: sgx_grm_crossprod_multi(_dev), sgx_grm_pcg_multi.
-// Pass 1 puts two columns' limbs side by side in each 16-column B fragment (7 + 7 limbs) and runs
-// the contraction kernel with up to GRM_MAXF = 3 value fragments (GRM_GROUP = 6 columns); pass 2 needs
-// x and gam limbs of a column (7 + 7) in one fragment and runs with up to 3 (GRM_GROUP2).  A group of 6
-// columns thus streams the genotypes three times (G once, Gt twice) where 6 single products stream
-// them 12 times.
-// Scratch is allocated on the first batched call; the PCG vectors are sized for the largest k seen.
-
-struct GrmMulti {
-	int kcap = 0;                          // columns the [k][N] vectors below have room for
-	uint8_t *FlN = nullptr, *FlM = nullptr;          // limb tile images, 16 GRM_MAXF columns wide
-	int *accV = nullptr, *accS = nullptr;            // [M][32 GRM_MAXF], [N][32 GRM_MAXF]
-	double *xv = nullptr, *gv = nullptr;             // [GRM_GROUP][M]
-	unsigned long long *maxb = nullptr;              // [GRM_MAX_RHS][3]
-	double *part = nullptr, *h_part = nullptr;       // [2 * GRM_MAX_RHS][GRM_RED_BLOCKS]
-	double *B = nullptr, *O = nullptr;               // [k][N] staging of host-pointer calls
-	double *R = nullptr, *Z = nullptr, *P = nullptr, *X = nullptr, *AP = nullptr, *GP = nullptr;   // [k][N]
-};
-static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
-
-static void grm_multi_release(sgx_grm *g)
-{
-	GrmMulti *s = g->multi;
-	if (!s) return;
-	g->multi = nullptr;
-	void *ptrs[] = {s->FlN, s->FlM, s->accV, s->accS, s->xv, s->gv, s->maxb, s->part, s->B, s->O,
-		s->R, s->Z, s->P, s->X, s->AP, s->GP};
-	for (void *p : ptrs) (void)hipFree(p);
-	if (s->h_part) (void)hipHostFree(s->h_part);
-	delete s;
-}
-
-// scratch for k columns (k <= GRM_MAX_RHS); vecs: also the [k][N] vectors
-static int grm_multi_scratch(sgx_grm *g, int k, bool vecs, GrmMulti **out)
-{
-	if (!g->multi) g->multi = new GrmMulti();
-	GrmMulti *s = g->multi;
-	const size_t N = (size_t)g->N, M = g->M;
-	if (!s->FlN) {
-		const size_t bN = (size_t)g->tbN.ntile * 16 * (16 * GRM_MAXF) * 16, bM = (size_t)g->tbM.ntile * 16 * (16 * GRM_MAXF) * 16;
-		HIPCHK(hipMalloc((void **)&s->FlN, bN));
-		HIPCHK(hipMalloc((void **)&s->FlM, bM));
-		HIPCHK(hipMalloc((void **)&s->accV, M * 32 * GRM_MAXF * sizeof(int)));
-		HIPCHK(hipMalloc((void **)&s->accS, N * 32 * GRM_MAXF * sizeof(int)));
-		HIPCHK(hipMalloc((void **)&s->xv, GRM_GROUP * M * sizeof(double)));
-		HIPCHK(hipMalloc((void **)&s->gv, GRM_GROUP * M * sizeof(double)));
-		HIPCHK(hipMalloc((void **)&s->maxb, GRM_MAX_RHS * 3 * sizeof(unsigned long long)));
-		HIPCHK(hipMalloc((void **)&s->part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double)));
-		HIPCHK(hipHostMalloc((void **)&s->h_part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double), hipHostMallocDefault));
-	}
-	if (vecs && k > s->kcap) {
-		for (double **p : {&s->B, &s->O, &s->R, &s->Z, &s->P, &s->X, &s->AP, &s->GP}) {
-			if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
-		}
-		s->kcap = 0;
-		for (double **p : {&s->B, &s->O, &s->R, &s->Z, &s->P, &s->X, &s->AP, &s->GP})
-			HIPCHK(hipMalloc((void **)p, (size_t)k * N * sizeof(double)));
-		s->kcap = k;
-	}
-	*out = s;
-	return SGX_OK;
-}
-
-// per column y of cols: out[y] = sum a (* b), partitioned and summed exactly as grm_sum; one host sync
-// for up to two sets (a1/b1 over cols1, then a2/b2 over cols2; a2 == NULL: none)
-static int grm_sum_multi(sgx_grm *g, GrmMulti *s, const double *a1, const double *b1, size_t ld1, const GrmCols &c1,
+// per column y of cols: out[y] = sum a (* b) as GRM_RED_BLOCKS block partials summed on the host in
+// fixed order; one host sync for up to two sets (a1/b1 over cols1, then a2/b2 over cols2; a2 == NULL: none)
+static int grm_sum(sgx_grm *g, const double *a1, const double *b1, size_t ld1, const GrmCols &c1,
 	double *out1, const double *a2 = nullptr, const double *b2 = nullptr, size_t ld2 = 0, const GrmCols *c2 = nullptr,
 	double *out2 = nullptr)
 {
 	hipStream_t st = g->stream;
 	const size_t n = (size_t)g->N;
 	auto launch = [&](const double *a, const double *b, size_t ld, const GrmCols &c, double *part) {
-		if (b) hipLaunchKernelGGL((dot_partial_multi_kernel<true>), dim3(GRM_RED_BLOCKS, c.n), dim3(256), 0, st, a, b, ld, c, n, part);
-		else hipLaunchKernelGGL((dot_partial_multi_kernel<false>), dim3(GRM_RED_BLOCKS, c.n), dim3(256), 0, st, a, b, ld, c, n, part);
+		if (b) hipLaunchKernelGGL((dot_partial_kernel<true>), dim3(GRM_RED_BLOCKS, c.n), dim3(256), 0, st, a, b, ld, c, n, part);
+		else hipLaunchKernelGGL((dot_partial_kernel<false>), dim3(GRM_RED_BLOCKS, c.n), dim3(256), 0, st, a, b, ld, c, n, part);
 	};
 	const int n1 = c1.n, n2 = a2 ? c2->n : 0;
 	if (n1 + n2 == 0) return SGX_OK;
-	if (n1) launch(a1, b1, ld1, c1, s->part);
-	if (n2) launch(a2, b2, ld2, *c2, s->part + (size_t)n1 * GRM_RED_BLOCKS);
+	if (n1) launch(a1, b1, ld1, c1, g->part);
+	if (n2) launch(a2, b2, ld2, *c2, g->part + (size_t)n1 * GRM_RED_BLOCKS);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(s->h_part, s->part, (size_t)(n1 + n2) * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(g->h_part, g->part, (size_t)(n1 + n2) * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	for (int y = 0; y < n1 + n2; y++) {
 		double v = 0;
-		for (int i = 0; i < GRM_RED_BLOCKS; i++) v += s->h_part[(size_t)y * GRM_RED_BLOCKS + i];   // fixed order
+		for (int i = 0; i < GRM_RED_BLOCKS; i++) v += g->h_part[(size_t)y * GRM_RED_BLOCKS + i];   // fixed order
 		if (y < n1) out1[y] = v; else out2[y - n1] = v;
 	}
 	return SGX_OK;
 }
 
 template <int NBFV>
-static void grm_mfma_launch(sgx_grm *g, const uint8_t *packed, size_t bpv, int rows, const uint8_t *Fl, int ntile, int *acc)
+static void grm_contract_launch(sgx_grm *g, const uint8_t *packed, size_t bpv, int rows, const uint8_t *Fl, int ntile, int *acc)
 {
 	MfTab tb{};
 	tb.Fl = Fl; tb.ntile = ntile;
 	int tps = 0;
-	const dim3 grid = grm_mfma_grid(g, (size_t)rows, ntile, &tps);
+	const dim3 grid = mf_grid(g->n_cu, (size_t)rows, ntile, &tps);
 	const size_t lds = (size_t)2 * 16 * (16 * NBFV) * 16;
-	hipLaunchKernelGGL((score_mfma_kernel<NBFV, false, true>), grid, dim3(WAVE * MF_WAVES), lds, g->stream, packed, bpv, rows, tb, tps, acc, 32 * NBFV);
+	hipLaunchKernelGGL((grm_contract_kernel<NBFV>), grid, dim3(WAVE * GRM_WAVES), lds, g->stream, packed, bpv, rows, tb, tps, acc, 32 * NBFV);
 }
 
-static void grm_mfma_dispatch(sgx_grm *g, int nbfv, const uint8_t *packed, size_t bpv, int rows, const uint8_t *Fl, int ntile, int *acc)
+static void grm_contract(sgx_grm *g, int nbfv, const uint8_t *packed, size_t bpv, int rows, const uint8_t *Fl, int ntile, int *acc)
 {
 	switch (nbfv) {
-	case 1: grm_mfma_launch<1>(g, packed, bpv, rows, Fl, ntile, acc); break;
-	case 2: grm_mfma_launch<2>(g, packed, bpv, rows, Fl, ntile, acc); break;
-	default: grm_mfma_launch<GRM_MAXF>(g, packed, bpv, rows, Fl, ntile, acc); break;
+	case 1: grm_contract_launch<1>(g, packed, bpv, rows, Fl, ntile, acc); break;
+	case 2: grm_contract_launch<2>(g, packed, bpv, rows, Fl, ntile, acc); break;
+	default: grm_contract_launch<GRM_MAXF>(g, packed, bpv, rows, Fl, ntile, acc); break;
 	}
 }
 
-// Out[:, c] = G'(G B[:, c])/M for c in cols (columns at base + c * ld), device vectors; each column
-// bit-identical to grm_matvec_dev on it
-static int grm_matvec_multi_dev(sgx_grm *g, GrmMulti *s, const double *B, size_t ldb, const GrmCols &cols,
-	double *Out, size_t ldo)
+// Out[:, c] = G'(G B[:, c])/M for c in cols (columns at base + c * ld), device vectors
+// (get_crossprod_b_grm, saige_fitnull.cpp:435-536).  A column's result does not depend on the other
+// columns of the call: its limbs, its exact integer sums and its reductions are its own.
+static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols &cols, double *Out, size_t ldo)
 {
 	hipStream_t st = g->stream;
 	const size_t N = (size_t)g->N, M = g->M;
 	const dim3 bl(256);
 	double sum_b[GRM_MAX_RHS];
-	int rc = grm_sum_multi(g, s, B, nullptr, ldb, cols, sum_b);
+	int rc = grm_sum(g, B, nullptr, ldb, cols, sum_b);
 	if (rc) return rc;
 	for (int g0 = 0; g0 < cols.n; g0 += GRM_GROUP) {
 		GrmCols gc{};
@@ -391,46 +220,46 @@ static int grm_matvec_multi_dev(sgx_grm *g, GrmMulti *s, const double *B, size_t
 		for (int y = 0; y < gc.n; y++) { gc.c[y] = cols.c[g0 + y]; sb.v[y] = sum_b[g0 + y]; }
 		// ---- pass 1: per marker, over samples; column y in fragment y / 2, limbs 7 (y % 2) ..
 		const int nb1 = (gc.n + 1) / 2;
-		HIPCHK(hipMemsetAsync(s->maxb, 0, (size_t)gc.n * 3 * sizeof(unsigned long long), st));
-		hipLaunchKernelGGL(absmax_multi_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, B, ldb, gc, N, 0, s->maxb);
-		HIPCHK(hipMemsetAsync(s->FlN, 0, (size_t)g->tbN.ntile * 16 * (16 * nb1) * 16, st));
-		hipLaunchKernelGGL(limbs_multi_kernel, dim3(512, gc.n), bl, 0, st, B, ldb, gc, N, (size_t)g->tbN.ntile * 256,
-			16 * nb1, 2, 0, s->maxb, 0, s->FlN);
-		HIPCHK(hipMemsetAsync(s->accV, 0, M * 32 * nb1 * sizeof(int), st));
-		grm_mfma_dispatch(g, nb1, g->G, g->bpvN, (int)M, s->FlN, g->tbN.ntile, s->accV);
-		hipLaunchKernelGGL(grm_dot_epilogue_multi, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, s->accV, s->maxb, sb,
-			g->af, g->inv, g->l0, s->xv, s->gv, s->part);
+		HIPCHK(hipMemsetAsync(g->maxb, 0, (size_t)gc.n * 3 * sizeof(unsigned long long), st));
+		hipLaunchKernelGGL(absmax_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, B, ldb, gc, N, 0, g->maxb);
+		HIPCHK(hipMemsetAsync(g->FlN, 0, (size_t)g->ntileN * 16 * (16 * nb1) * 16, st));
+		hipLaunchKernelGGL(limbs_kernel, dim3(512, gc.n), bl, 0, st, B, ldb, gc, N, (size_t)g->ntileN * 256,
+			16 * nb1, 2, 0, g->maxb, 0, g->FlN);
+		HIPCHK(hipMemsetAsync(g->accV, 0, M * 32 * nb1 * sizeof(int), st));
+		grm_contract(g, nb1, g->G, g->bpvN, (int)M, g->FlN, g->ntileN, g->accV);
+		hipLaunchKernelGGL(grm_dot_epilogue, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, g->accV, g->maxb, sb,
+			g->af, g->inv, g->l0, g->xv, g->gv, g->part);
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(s->h_part, s->part, (size_t)gc.n * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(g->h_part, g->part, (size_t)gc.n * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
 		GrmScal C0{};
 		for (int y = 0; y < gc.n; y++) {
 			double c0 = 0;
-			for (int i = 0; i < GRM_RED_BLOCKS; i++) c0 += s->h_part[(size_t)y * GRM_RED_BLOCKS + i];
+			for (int i = 0; i < GRM_RED_BLOCKS; i++) c0 += g->h_part[(size_t)y * GRM_RED_BLOCKS + i];   // fixed order
 			C0.v[y] = c0;
 		}
 		// ---- pass 2: per sample, over markers; column y of a sub-group in fragment y (x limbs 0.., gam limbs 7..)
 		GrmCols all{};
 		all.n = gc.n;
 		for (int y = 0; y < gc.n; y++) all.c[y] = y;
-		hipLaunchKernelGGL(absmax_multi_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, s->xv, M, all, M, 1, s->maxb);
-		hipLaunchKernelGGL(absmax_multi_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, s->gv, M, all, M, 2, s->maxb);
+		hipLaunchKernelGGL(absmax_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, g->xv, M, all, M, 1, g->maxb);
+		hipLaunchKernelGGL(absmax_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, g->gv, M, all, M, 2, g->maxb);
 		for (int s0 = 0; s0 < gc.n; s0 += GRM_GROUP2) {
 			GrmCols sc{}, oc{};
 			sc.n = oc.n = std::min(GRM_GROUP2, gc.n - s0);
 			GrmScal c0s{};
 			for (int y = 0; y < sc.n; y++) { sc.c[y] = s0 + y; oc.c[y] = gc.c[s0 + y]; c0s.v[y] = C0.v[s0 + y]; }
 			const int nb2 = sc.n;
-			const unsigned long long *mb = s->maxb + 3 * s0;
-			HIPCHK(hipMemsetAsync(s->FlM, 0, (size_t)g->tbM.ntile * 16 * (16 * nb2) * 16, st));
-			hipLaunchKernelGGL(limbs_multi_kernel, dim3(512, sc.n), bl, 0, st, s->xv, M, sc, M, (size_t)g->tbM.ntile * 256,
-				16 * nb2, 1, 0, mb, 1, s->FlM);
-			hipLaunchKernelGGL(limbs_multi_kernel, dim3(512, sc.n), bl, 0, st, s->gv, M, sc, M, (size_t)g->tbM.ntile * 256,
-				16 * nb2, 1, MF_NLIMB, mb, 2, s->FlM);
-			HIPCHK(hipMemsetAsync(s->accS, 0, N * 32 * nb2 * sizeof(int), st));
-			grm_mfma_dispatch(g, nb2, g->Gt, g->bpvM, g->N, s->FlM, g->tbM.ntile, s->accS);
-			hipLaunchKernelGGL(grm_out_epilogue_multi, dim3((unsigned)((N + 255) / 256), sc.n), bl, 0, st, g->N, M, nb2,
-				s->accS, mb, c0s, g->diag, Out, ldo, oc);
+			const unsigned long long *mb = g->maxb + 3 * s0;
+			HIPCHK(hipMemsetAsync(g->FlM, 0, (size_t)g->ntileM * 16 * (16 * nb2) * 16, st));
+			hipLaunchKernelGGL(limbs_kernel, dim3(512, sc.n), bl, 0, st, g->xv, M, sc, M, (size_t)g->ntileM * 256,
+				16 * nb2, 1, 0, mb, 1, g->FlM);
+			hipLaunchKernelGGL(limbs_kernel, dim3(512, sc.n), bl, 0, st, g->gv, M, sc, M, (size_t)g->ntileM * 256,
+				16 * nb2, 1, MF_NLIMB, mb, 2, g->FlM);
+			HIPCHK(hipMemsetAsync(g->accS, 0, N * 32 * nb2 * sizeof(int), st));
+			grm_contract(g, nb2, g->Gt, g->bpvM, g->N, g->FlM, g->ntileM, g->accS);
+			hipLaunchKernelGGL(grm_out_epilogue, dim3((unsigned)((N + 255) / 256), sc.n), bl, 0, st, g->N, M, nb2,
+				g->accS, mb, c0s, g->diag, Out, ldo, oc);
 			HIPCHK(hipGetLastError());
 		}
 	}
@@ -453,43 +282,69 @@ static GrmCols grm_cols_iota(int k)
 	return c;
 }
 
-extern "C" int sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size_t ldb, int k, double *Out_dev)
+// k columns of N doubles between a host array with columns ldh doubles apart and a packed [k][N] device array
+// (one linear copy when the host columns are packed too)
+static hipError_t grm_copy_cols(sgx_grm *g, double *dst, const double *src, size_t ldh, int k, hipMemcpyKind kind)
 {
-	int rc = grm_multi_args("sgx_grm_crossprod_multi_dev", g, B_dev, ldb, k, Out_dev);
-	if (rc) return rc;
+	const size_t nb = (size_t)g->N * sizeof(double);
+	if (ldh == (size_t)g->N || k == 1) return hipMemcpyAsync(dst, src, (size_t)k * nb, kind, g->stream);
+	const bool up = kind == hipMemcpyHostToDevice;
+	return hipMemcpy2DAsync(dst, up ? nb : ldh * sizeof(double), src, up ? ldh * sizeof(double) : nb, nb, (size_t)k, kind, g->stream);
+}
+
+// Out = GRM B for k host vectors, column j at B + j * ldb (and Out + j * ldb)
+static int grm_crossprod_run(sgx_grm *g, const double *B, size_t ldb, int k, double *Out)
+{
 	HIPCHK(hipSetDevice(g->device));
-	GrmMulti *s = nullptr;
-	if ((rc = grm_multi_scratch(g, k, false, &s))) return rc;
-	return grm_matvec_multi_dev(g, s, B_dev, ldb, grm_cols_iota(k), Out_dev, ldb);
+	HIPCHK(grm_reserve(g, k));
+	const size_t N = (size_t)g->N;
+	HIPCHK(grm_copy_cols(g, g->B, B, ldb, k, hipMemcpyHostToDevice));
+	int rc = grm_matvec_dev(g, g->B, N, grm_cols_iota(k), g->O, N);
+	if (rc) return rc;
+	HIPCHK(grm_copy_cols(g, Out, g->O, ldb, k, hipMemcpyDeviceToHost));
+	HIPCHK(hipStreamSynchronize(g->stream));
+	return SGX_OK;
+}
+
+// get_crossprod_b_grm: out = GRM b, host vectors of length N
+extern "C" int sgx_grm_crossprod(sgx_grm *g, const double *b, double *out)
+{
+	if (!g || !b || !out) return fail(SGX_EINVAL, "sgx_grm_crossprod: NULL argument");
+	return grm_crossprod_run(g, b, (size_t)g->N, 1, out);
 }
 
 extern "C" int sgx_grm_crossprod_multi(sgx_grm *g, const double *B, size_t ldb, int k, double *Out)
 {
 	int rc = grm_multi_args("sgx_grm_crossprod_multi", g, B, ldb, k, Out);
 	if (rc) return rc;
-	HIPCHK(hipSetDevice(g->device));
-	GrmMulti *s = nullptr;
-	if ((rc = grm_multi_scratch(g, k, true, &s))) return rc;
-	const size_t N = (size_t)g->N, nb = N * sizeof(double);
-	HIPCHK(hipMemcpy2DAsync(s->B, nb, B, ldb * sizeof(double), nb, (size_t)k, hipMemcpyHostToDevice, g->stream));
-	if ((rc = grm_matvec_multi_dev(g, s, s->B, N, grm_cols_iota(k), s->O, N))) return rc;
-	HIPCHK(hipMemcpy2DAsync(Out, ldb * sizeof(double), s->O, nb, nb, (size_t)k, hipMemcpyDeviceToHost, g->stream));
-	HIPCHK(hipStreamSynchronize(g->stream));
-	return SGX_OK;
+	return grm_crossprod_run(g, B, ldb, k, Out);
 }
 
-// PCG_diag_sigma (saige_fitnull.cpp:581-614) on k right-hand sides in lockstep: column j follows exactly
-// the steps of sgx_grm_pcg on B[:, j]; a column stops (and leaves the products) once rr <= tol or
-// maxiter is reached.  Each reduction step is one host sync for all columns.
-extern "C" int sgx_grm_pcg_multi(sgx_grm *g, const double *w, const double *tau, const double *B, size_t ldb, int k,
-	int maxiter, double tol, double *X_out, int *iters)
+// out = GRM b with b, out device vectors of N doubles (asynchronous until sgx_grm_sync)
+extern "C" int sgx_grm_crossprod_dev(sgx_grm *g, const double *b_dev, double *out_dev)
 {
-	if (!w || !tau || !iters) return fail(SGX_EINVAL, "sgx_grm_pcg_multi: NULL argument");
-	int rc = grm_multi_args("sgx_grm_pcg_multi", g, B, ldb, k, X_out);
+	if (!g || !b_dev || !out_dev) return fail(SGX_EINVAL, "sgx_grm_crossprod_dev: NULL argument");
+	HIPCHK(hipSetDevice(g->device));
+	return grm_matvec_dev(g, b_dev, (size_t)g->N, grm_cols_iota(1), out_dev, (size_t)g->N);
+}
+
+extern "C" int sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size_t ldb, int k, double *Out_dev)
+{
+	int rc = grm_multi_args("sgx_grm_crossprod_multi_dev", g, B_dev, ldb, k, Out_dev);
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(g->device));
-	GrmMulti *s = nullptr;
-	if ((rc = grm_multi_scratch(g, k, true, &s))) return rc;
+	return grm_matvec_dev(g, B_dev, ldb, grm_cols_iota(k), Out_dev, ldb);
+}
+
+// PCG_diag_sigma (saige_fitnull.cpp:581-614): solves (tau0 diag(1/w) + tau1 GRM) x = b for k right-hand
+// sides in lockstep (host vectors, column j at B + j * ldb): every column takes the reference's steps on
+// its own scalars; a column stops (and leaves the products) once rr <= tol or maxiter is reached.  Each
+// reduction step is one host sync for all columns.
+static int grm_pcg_run(sgx_grm *g, const double *w, const double *tau, const double *B, size_t ldb, int k,
+	int maxiter, double tol, double *X_out, int *iters)
+{
+	HIPCHK(hipSetDevice(g->device));
+	HIPCHK(grm_reserve(g, k));
 	hipStream_t st = g->stream;
 	const int n = g->N;
 	const size_t N = (size_t)n, nb = N * sizeof(double);
@@ -497,12 +352,13 @@ extern "C" int sgx_grm_pcg_multi(sgx_grm *g, const double *w, const double *tau,
 	const unsigned gx = (unsigned)((n + 255) / 256);
 	const double tau0 = tau[0], tau1 = tau[1];
 	HIPCHK(hipMemcpyAsync(g->w, w, nb, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpy2DAsync(s->B, nb, B, ldb * sizeof(double), nb, (size_t)k, hipMemcpyHostToDevice, st));
+	HIPCHK(grm_copy_cols(g, g->B, B, ldb, k, hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(pcg_minv_kernel, dim3(gx), bl, 0, st, n, g->w, g->diag, tau0, tau1, g->minv);
 	const GrmCols all = grm_cols_iota(k);
-	hipLaunchKernelGGL(pcg_init_multi_kernel, dim3(gx, k), bl, 0, st, n, s->B, N, g->minv, s->R, s->Z, s->P, s->X, all);
+	hipLaunchKernelGGL(pcg_init_kernel, dim3(gx, k), bl, 0, st, n, g->B, N, g->minv, g->R, g->Z, g->P, g->X, all);
 	double rr[GRM_MAX_RHS], rz[GRM_MAX_RHS];
-	if ((rc = grm_sum_multi(g, s, s->R, s->R, N, all, rr, s->R, s->Z, N, &all, rz))) return rc;
+	int rc;
+	if ((rc = grm_sum(g, g->R, g->R, N, all, rr, g->R, g->Z, N, &all, rz))) return rc;
 	for (int j = 0; j < k; j++) iters[j] = 0;
 	for (;;) {
 		GrmCols act{};
@@ -512,23 +368,43 @@ extern "C" int sgx_grm_pcg_multi(sgx_grm *g, const double *w, const double *tau,
 		for (int y = 0; y < act.n; y++) iters[act.c[y]]++;
 		const double *gp = nullptr;
 		if (tau1 != 0) {                       // get_crossprod :569-575
-			if ((rc = grm_matvec_multi_dev(g, s, s->P, N, act, s->GP, N))) return rc;
-			gp = s->GP;
+			if ((rc = grm_matvec_dev(g, g->P, N, act, g->GP, N))) return rc;
+			gp = g->GP;
 		}
-		hipLaunchKernelGGL(pcg_ap_multi_kernel, dim3(gx, act.n), bl, 0, st, n, s->P, g->w, gp, tau0, tau1, s->AP, act);
+		hipLaunchKernelGGL(pcg_ap_kernel, dim3(gx, act.n), bl, 0, st, n, g->P, g->w, gp, tau0, tau1, g->AP, act);
 		double pAp[GRM_MAX_RHS], rz1[GRM_MAX_RHS], rrn[GRM_MAX_RHS];
-		if ((rc = grm_sum_multi(g, s, s->P, s->AP, N, act, pAp))) return rc;
+		if ((rc = grm_sum(g, g->P, g->AP, N, act, pAp))) return rc;
 		GrmScal a{};
 		for (int y = 0; y < act.n; y++) a.v[y] = rz[act.c[y]] / pAp[y];
-		hipLaunchKernelGGL(pcg_update_multi_kernel, dim3(gx, act.n), bl, 0, st, n, a, s->P, s->AP, g->minv, s->X, s->R, s->Z, act);
-		if ((rc = grm_sum_multi(g, s, s->Z, s->R, N, act, rz1, s->R, s->R, N, &act, rrn))) return rc;
+		hipLaunchKernelGGL(pcg_update_kernel, dim3(gx, act.n), bl, 0, st, n, a, g->P, g->AP, g->minv, g->X, g->R, g->Z, act);
+		if ((rc = grm_sum(g, g->Z, g->R, N, act, rz1, g->R, g->R, N, &act, rrn))) return rc;
 		GrmScal bet{};
 		for (int y = 0; y < act.n; y++) bet.v[y] = rz1[y] / rz[act.c[y]];
-		hipLaunchKernelGGL(pcg_dir_multi_kernel, dim3(gx, act.n), bl, 0, st, n, bet, s->Z, s->P, act);
+		hipLaunchKernelGGL(pcg_dir_kernel, dim3(gx, act.n), bl, 0, st, n, bet, g->Z, g->P, act);
 		for (int y = 0; y < act.n; y++) { rz[act.c[y]] = rz1[y]; rr[act.c[y]] = rrn[y]; }
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy2DAsync(X_out, ldb * sizeof(double), s->X, nb, nb, (size_t)k, hipMemcpyDeviceToHost, st));
+	HIPCHK(grm_copy_cols(g, X_out, g->X, ldb, k, hipMemcpyDeviceToHost));
 	HIPCHK(hipStreamSynchronize(st));
 	return SGX_OK;
+}
+
+extern "C" int sgx_grm_pcg(sgx_grm *g, const double *w, const double *tau, const double *b,
+	int maxiter, double tol, double *x_out, int *iters_out)
+{
+	if (!g || !w || !tau || !b || !x_out) return fail(SGX_EINVAL, "sgx_grm_pcg: NULL argument");
+	int iters = 0;
+	int rc = grm_pcg_run(g, w, tau, b, (size_t)g->N, 1, maxiter, tol, x_out, &iters);
+	if (rc) return rc;
+	if (iters_out) *iters_out = iters;
+	return SGX_OK;
+}
+
+extern "C" int sgx_grm_pcg_multi(sgx_grm *g, const double *w, const double *tau, const double *B, size_t ldb, int k,
+	int maxiter, double tol, double *X_out, int *iters)
+{
+	if (!w || !tau || !iters) return fail(SGX_EINVAL, "sgx_grm_pcg_multi: NULL argument");
+	int rc = grm_multi_args("sgx_grm_pcg_multi", g, B, ldb, k, X_out);
+	if (rc) return rc;
+	return grm_pcg_run(g, w, tau, B, ldb, k, maxiter, tol, X_out, iters);
 }

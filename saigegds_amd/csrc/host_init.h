@@ -12,7 +12,7 @@ extern "C" int sgx_device_count(void)
 
 extern "C" size_t sgx_row_stride(int32_t n_samp)
 {
-	return (size_t)((n_samp + 511) / 512) * 128;  // whole pairs of 256-sample tiles = whole 128-B lines (kern_score_mfma.h)
+	return (size_t)((n_samp + 511) / 512) * 128;  // whole pairs of 256-sample tiles = whole 128-B lines (grm_contract_kernel, kern_grm.h)
 }
 
 static double thr_or(double v, double dflt) { return std::isfinite(v) ? v : dflt; }
@@ -222,7 +222,7 @@ extern "C" int sgx_init(const sgx_model *m, int device, sgx_handle **out)
 		f[2 * K] = m->y_mu[i];
 		f[2 * K + 1] = w;
 	}
-	// Fixed-point limb tiles of the MFMA score path (kern_score3.h; kern_score_mfma.h "Limb counts"): ONE
+	// Fixed-point limb tiles of the MFMA score path (kern_score3.h; mf_fixed.h "Limb counts"): ONE
 	// group of up to 15 value fragments + the bit-1 fragment, and the table Q of the same values as int64
 	// for the sparse pass over the missing genotypes.  Sample x at an odd position of its dword is used by
 	// the kernel where it stands, two bits up (s3_scale): its value is a multiple of 4 and its digits carry
@@ -247,7 +247,7 @@ extern "C" int sgx_init(const sgx_model *m, int device, sgx_handle **out)
 		for (int k = 0; k < K; k++) { ep.cgrp[k] = 0; ep.ccol[k] = 0; ep.climb[k] = 0; }
 		// Limb counts follow the measured dynamic range of each column.  A column is quantised against
 		// its largest entry, so an entry of typical size keeps 8 nl - 2 - log2(max / typical) bits (two
-		// fewer at the odd positions): the reduced widths of kern_score_mfma.h "Limb counts" hold for
+		// fewer at the odd positions): the reduced widths of mf_fixed.h "Limb counts" hold for
 		// covariates whose largest value is a few times the typical one (max / mean|.| = 5.6 for a standard
 		// normal column at N = 430 000) and are widened for heavy-tailed ones; beyond 2^22 no width is
 		// enough and the model takes the FP64 gather kernels instead of the MFMA path.

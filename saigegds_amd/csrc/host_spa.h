@@ -24,7 +24,7 @@ static void with_pp(int P, F &&f)
 
 // Sample splits of the MFMA kernels: a few rounds of the workgroups a CU holds (wg_per_cu), and a
 // multiple of 8 splits when there are that many, so that each XCD works on whole splits
-// (kern_score_mfma.h).  vpb: variants per workgroup.
+// (grm_contract_kernel, kern_grm.h).  vpb: rows per workgroup.
 static dim3 mf_grid(int n_cu, size_t rows, int ntile, int *tps, int vpb = MF_VPB, int wg_per_cu = 2)
 {
 	const int vt = (int)((rows + vpb - 1) / vpb);

@@ -67,7 +67,7 @@ struct sgx_handle {
 	uint8_t *scr5 = nullptr; int *cur5 = nullptr; int nwg5 = 0;   // spa5_kernel: per-workgroup lists, queue cursor
 	int spa_abl = 0;                  // timing experiments (wrong results)
 	bool force_exact = false;         // test hook: every SPA variant takes the exact exp/log kernels
-	// exact-integer MFMA score path (kern_score_mfma.h)
+	// exact-integer MFMA score path (mf_fixed.h, kern_score3.h)
 	bool mf_ok = false;
 	MfTab mf[MF_MAXG]{};              // one limb table per column group
 	int mf_nbfv[MF_MAXG]{};

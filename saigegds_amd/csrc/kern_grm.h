@@ -1,6 +1,7 @@
 // kern_grm.h -- implicit-GRM operator of the null-model fit on 2-bit genotypes.
 // Part of libsaigehip.so (single translation unit: saigehip.hip).
 #pragma once
+#include <type_traits>
 
 // Reference: src/saige_fitnull.cpp
 //   saige_store_2b_geno   :159-230  standardised-genotype table, diag(GRM)
@@ -16,13 +17,30 @@
 //   pass 2 (per sample, over markers):   M out_i = C0 + X_i - Gam_i
 //        x_v = dot_v inv_v,  C0 = sum_v dot_v l0_v,
 //        X_i = sum_v code_vi x_v,  Gam_i = sum_{missing} (3 - 2 af_v) x_v
-// Both are evaluated by score_mfma_kernel<1,false> (code plane + missing plane)
-// on the marker-major matrix and on its 2-bit transpose, with b / (x, gam)
-// converted to 56-bit fixed-point limbs first, so each pass is one streaming
-// sweep of the packed matrix with exact integer accumulation.
+// Both are evaluated by grm_contract_kernel (code plane + missing plane) on the
+// marker-major matrix and on its 2-bit transpose, with b / (x, gam) converted to
+// 56-bit fixed-point limbs first (mf_fixed.h), so each pass is one streaming sweep
+// of the packed matrix with exact integer accumulation.
+//
+// Every entry point works on a set of right-hand sides (columns); a single product or solve is a
+// set of one.  Column c of a set lives at base + c * ld; blockIdx.y picks the column of a launch.
 
-#define GRM_NCOL 16          /* B tile columns: one value fragment               */
-#define GRM_NACC 32          /* ints per row: value fragment + missing fragment  */
+#define GRM_MAX_RHS 64        /* SGX_GRM_MAX_RHS                                     */
+#define GRM_MAXF 3            /* value fragments of a contraction launch (4 spill: DESIGN.md)   */
+#define GRM_GROUP (2 * GRM_MAXF)   /* columns per pass-1 launch: two per 16-column fragment         */
+#define GRM_GROUP2 GRM_MAXF        /* columns per pass-2 launch: one per fragment (x and gam limbs) */
+#define GRM_NAF 4             /* A fragments (16 rows each) per wave: 2 waves per SIMD at <= 256 registers */
+#define GRM_WAVES 4           /* waves per workgroup -> MF_VPB rows                  */
+static_assert(16 * GRM_NAF * GRM_WAVES == MF_VPB, "mf_grid plans workgroups of MF_VPB rows");
+
+struct GrmCols {              // the columns of a set a launch works on (kernel argument, by value)
+	int n;
+	int c[GRM_MAX_RHS];
+};
+
+struct GrmScal {              // one double per column of a launch (by value)
+	double v[GRM_MAX_RHS];
+};
 
 // ---- per-marker statistics: af, inv, l0  (:181-203); one workgroup per marker
 __global__ void __launch_bounds__(256)
@@ -114,10 +132,176 @@ grm_diag_kernel(const uint8_t *__restrict__ gt, size_t bpvM, int N, size_t M,
 	if (lane == 0) diag[i] = s / (double)M;
 }
 
-// ---- fixed-point conversion of a real vector into one block of 7 limb columns
-__global__ void __launch_bounds__(256)
-absmax_kernel(const double *__restrict__ x, size_t n, unsigned long long *__restrict__ out)
+// ---- the contraction: acc[row][..] += sum over samples of (code, [code == 3]) x limb columns
+// grid = (row tiles of MF_VPB, sample splits: mf_grid); block = 64 * GRM_WAVES; LDS = 2 B tiles.
+// packed: 2-bit rows of bpv bytes, bpv % 128 == 0 covering whole pairs of 256-sample tiles; tile
+// ranges (t0, t1 - t0, tb.ntile) are even.  tb.Fl: B tiles of 16 NBFV limb columns.
+// Accumulator row (acc_stride = 32 NBFV ints): [0, 16 NBFV) the code plane against every limb
+// column, [16 NBFV, 32 NBFV) the same columns summed over MISSING samples only (plane [code == 3]);
+// that plane is multiplied only in fragments that contain a missing code, which a wave decides with
+// one ballot.  A lane fetches 2 x 16 B of each of its rows per PAIR of tiles (the two halves of one
+// 128-B line, by back-to-back instructions): half as many lines in flight per byte.
+template <int NBFV>
+__global__ void __launch_bounds__(WAVE * GRM_WAVES, 2)   /* waves per SIMD */
+grm_contract_kernel(const uint8_t *__restrict__ packed, size_t bpv, int M, MfTab tb,
+	int tiles_per_split, int *__restrict__ accbuf, int acc_stride)
 {
+	constexpr int NAF = GRM_NAF;
+	constexpr int NCOL = 16 * NBFV;
+	constexpr int TILE_BYTES = 16 * NCOL * 16;
+	constexpr int NDMA = (TILE_BYTES / 1024 + GRM_WAVES - 1) / GRM_WAVES;   // DMA instructions per wave and tile
+	constexpr int AW = 2;                                                   // 16-B pieces of a row held per lane
+	static_assert(AW * NAF + NDMA <= 4 * NAF, "more loads per tile than MFMA groups");
+	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];   // 2 x TILE_BYTES, nothing else
+	uint8_t *ldsB = smem;
+
+	const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
+	const int r = lane & 15, kg = lane >> 4;
+	// Workgroups are handed to the 8 XCDs round-robin in dispatch order, so those with the same
+	// (linear id % 8) share an L2.  Give each such group whole sample splits: its resident
+	// workgroups then stream the same B tiles, which stay in that L2, while every packed row
+	// is still read once.  (A placement guess only: correctness does not depend on it.)
+	unsigned vt_idx = blockIdx.x, split = blockIdx.y;
+	{
+		const unsigned VT = gridDim.x, L = blockIdx.y * VT + blockIdx.x, full = gridDim.y & ~7u;
+		if (L < full * VT) { const unsigned q = L >> 3; split = 8 * (q / VT) + (L & 7); vt_idx = q % VT; }
+	}
+	const int vbase = vt_idx * (16 * NAF * GRM_WAVES) + wid * 16 * NAF;
+	const int t0 = split * tiles_per_split;
+	const int t1 = min(tb.ntile, t0 + tiles_per_split);
+
+	v4i acc[NAF][NBFV], accm[NAF][NBFV];
+#pragma unroll
+	for (int f = 0; f < NAF; f++) {
+#pragma unroll
+		for (int b = 0; b < NBFV; b++) acc[f][b] = (v4i){0, 0, 0, 0};
+#pragma unroll
+		for (int b = 0; b < NBFV; b++) accm[f][b] = (v4i){0, 0, 0, 0};
+	}
+	bool saw_missing = false;   // wave-uniform
+
+	// this lane's 16 B of each of its rows in tile t: dwords 16t+4kg .. +3.  Row pointers advance by
+	// 64 B per tile; bpv is a multiple of 64 that covers every tile (sgx_row_stride), rows past M
+	// are clamped (their sums are never stored)
+	const uint8_t *rowp[NAF];
+	const uint8_t *const row0 = packed + (size_t)t0 * 64 + 16 * kg;
+#pragma unroll
+	for (int f = 0; f < NAF; f++)
+		rowp[f] = row0 + (size_t)min(vbase + 16 * f + r, M - 1) * bpv;
+	auto load_A1 = [&](uint4 &dst, int f, int piece) {
+		// (measured with the streaming hint: 4.46 -> 5.04 ms per product -- a lane's 16 bytes are a quarter of a
+		// 64-byte piece that four instructions share; the hint drops the line between them)
+		dst = *reinterpret_cast<const uint4 *>(rowp[f] + 64 * piece);
+		if (piece == AW - 1) rowp[f] += 64 * AW;
+	};
+	// one KiB of B tile t -> LDS buffer (t & 1) by LDS-DMA, lane-linear
+	auto dma_B1 = [&](int t, int i) {
+		const int k = wid + i * GRM_WAVES;
+		if (k >= TILE_BYTES / 1024) return;
+		const uint8_t *src = tb.Fl + (size_t)t * TILE_BYTES;
+		uint8_t *dst = ldsB + (size_t)(t & 1) * TILE_BYTES;
+		__builtin_amdgcn_global_load_lds(
+			(const __attribute__((address_space(1))) void *)(src + (size_t)k * 1024 + lane * 16),
+			(__attribute__((address_space(3))) void *)(dst + k * 1024), 16, 0, 0);
+	};
+
+	uint4 acur[NAF][AW], anxt[NAF][AW];
+	if (t0 < t1) {
+#pragma unroll
+		for (int f = 0; f < NAF; f++)
+#pragma unroll
+			for (int p = 0; p < AW; p++) load_A1(acur[f][p], f, p);
+#pragma unroll
+		for (int i = 0; i < NDMA; i++) dma_B1(t0, i);
+	}
+
+	// one 256-sample tile; HH = which of the AW row pieces it reads
+	auto tile = [&](int t, auto HH) {
+		constexpr int hh = decltype(HH)::value;
+		__syncthreads();   // tile t landed (each wave drained its own DMA), tile t-1 fully consumed
+		const bool more_B = t + 1 < t1;                  // there is a next tile
+		const bool more_A = t + (AW - hh) < t1;          // there is a next row piece set (fetched in the hh = 0 tile)
+		// loads of this tile, one per MFMA group: the A pieces of the next tile pair, then the next B tile
+		auto vmem_slot = [&](int idx) {
+			if (hh == 0 && idx < AW * NAF) {
+				if (more_A) load_A1(anxt[idx / AW][idx % AW], idx / AW, idx % AW);
+			} else {
+				const int i = idx - (hh == 0 ? AW * NAF : 0);
+				if (i < NDMA && more_B) dma_B1(t + 1, i);
+			}
+			__builtin_amdgcn_sched_barrier(0);
+		};
+		const uint8_t *bt = ldsB + (size_t)(t & 1) * TILE_BYTES;
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const int g = 4 * kg + u;
+			v4i bfrag[NBFV];
+#pragma unroll
+			for (int b = 0; b < NBFV; b++)
+				bfrag[b] = *reinterpret_cast<const v4i *>(bt + ((size_t)(g * NCOL + b * 16 + r)) * 16);
+#pragma unroll
+			for (int f = 0; f < NAF; f++) {
+				const uint4 aw = acur[f][hh];
+				const uint32_t w = (u == 0) ? aw.x : (u == 1) ? aw.y : (u == 2) ? aw.z : aw.w;
+				vmem_slot(u * NAF + f);
+				v4i val;   // byte j of val[k] = code of sample 4j + k (mf_pos)
+#pragma unroll
+				for (int k = 0; k < 4; k++) val[k] = (int)((w >> (2 * k)) & 0x03030303u);
+#pragma unroll
+				for (int b = 0; b < NBFV; b++)
+					acc[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(val, bfrag[b], acc[f][b], 0, 0, 0);
+				// samples beyond N have all-zero limbs, so stray codes there add nothing
+				const uint32_t m3 = w & (w >> 1) & LO_MASK;
+				if (__ballot(m3 != 0)) {
+					saw_missing = true;
+					v4i ms;
+#pragma unroll
+					for (int k = 0; k < 4; k++) ms[k] = (int)((m3 >> (2 * k)) & 0x01010101u);
+#pragma unroll
+					for (int b = 0; b < NBFV; b++)
+						accm[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ms, bfrag[b], accm[f][b], 0, 0, 0);
+				}
+			}
+		}
+		if (hh == AW - 1) {
+#pragma unroll
+			for (int f = 0; f < NAF; f++)
+#pragma unroll
+				for (int p = 0; p < AW; p++) acur[f][p] = anxt[f][p];
+		}
+	};
+	for (int t = t0; t < t1; t += 2) {
+		tile(t, std::integral_constant<int, 0>());
+		tile(t + 1, std::integral_constant<int, AW - 1>());
+	}
+
+	// ---- results: integer atomics (exact, order-independent)
+#pragma unroll
+	for (int f = 0; f < NAF; f++) {
+#pragma unroll
+		for (int reg = 0; reg < 4; reg++) {
+			const int v = vbase + 16 * f + kg * 4 + reg;
+			if (v < M) {
+				int *dst = accbuf + (size_t)v * acc_stride;
+#pragma unroll
+				for (int b = 0; b < NBFV; b++) atomicAdd(&dst[b * 16 + r], acc[f][b][reg]);
+				if (saw_missing) {
+#pragma unroll
+					for (int b = 0; b < NBFV; b++)
+						if (accm[f][b][reg] != 0) atomicAdd(&dst[NCOL + b * 16 + r], accm[f][b][reg]);
+				}
+			}
+		}
+	}
+}
+
+// ---- fixed-point conversion of real vectors into limb columns
+// max|x| of column y -> out[3 * y + slot] (zeroed beforehand)
+__global__ void __launch_bounds__(256)
+absmax_kernel(const double *__restrict__ X, size_t ld, GrmCols cols, size_t n, int slot,
+	unsigned long long *__restrict__ out)
+{
+	const double *__restrict__ x = X + (size_t)cols.c[blockIdx.y] * ld;
 	double m = 0;
 	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
 		const double a = fabs(x[i]);
@@ -126,7 +310,7 @@ absmax_kernel(const double *__restrict__ x, size_t n, unsigned long long *__rest
 #pragma unroll
 	for (int o = 32; o > 0; o >>= 1) { const double t = __shfl_xor(m, o, WAVE); m = (t > m) ? t : m; }
 	// non-negative doubles order like their bit patterns
-	if ((threadIdx.x & (WAVE - 1)) == 0) atomicMax(out, (unsigned long long)__double_as_longlong(m));
+	if ((threadIdx.x & (WAVE - 1)) == 0) atomicMax(out + 3 * blockIdx.y + slot, (unsigned long long)__double_as_longlong(m));
 }
 
 // exponent e with max|x| * 2^e < 2^54
@@ -137,198 +321,11 @@ __device__ __forceinline__ int limb_scale(unsigned long long maxbits)
 	return 54 - __builtin_amdgcn_frexp_exp(mx);
 }
 
-// x[n] -> limb digits in columns [col0, col0+7) of the tile image Fl[ngrp_pad][GRM_NCOL][16];
-// the whole column range is written (zeros beyond n), other columns are left alone
+// x[n] of column y -> limb digits in 7 columns of the tile image Fl[ngrp_pad][ncol][16], the first one
+// 16 * (y / per_frag) + 7 * (y % per_frag) + off; zeros beyond n.  The columns nobody writes must be
+// zero beforehand
 __global__ void __launch_bounds__(256)
-limbs_kernel(const double *__restrict__ x, size_t n, size_t n_pad, int col0,
-	const unsigned long long *__restrict__ maxbits, uint8_t *__restrict__ Fl)
-{
-	const int e = limb_scale(*maxbits);
-	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_pad; i += (size_t)gridDim.x * blockDim.x) {
-		long long q = 0;
-		if (i < n) {
-			const double v = x[i];
-			q = isfinite(v) ? __double2ll_rn(ldexp(v, e)) : 0;
-		}
-		uint8_t *base = Fl + ((i >> 4) * GRM_NCOL + col0) * 16 + mf_pos((int)(i & 15));
-		long long rem = q;
-#pragma unroll
-		for (int l = 0; l < MF_NLIMB; l++) {
-			const long long d = (l < MF_NLIMB - 1) ? (((rem + 128) & 255) - 128) : rem;
-			rem = (rem - d) >> 8;
-			base[l * 16] = (uint8_t)(int8_t)d;
-		}
-	}
-}
-
-// deterministic block partial sums: out[blockIdx] = sum of a[i] (* b[i])
-template <bool WITH_B>
-__global__ void __launch_bounds__(256)
-dot_partial_kernel(const double *__restrict__ a, const double *__restrict__ b, size_t n,
-	double *__restrict__ out)
-{
-	__shared__ double sh[4];
-	double s[1] = {0};
-	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-		s[0] = WITH_B ? fma(a[i], b[i], s[0]) : s[0] + a[i];
-	block_sum<1, 256>(s, sh);
-	if (threadIdx.x == 0) out[blockIdx.x] = s[0];
-}
-
-// ---- pass-1 epilogue: dot_v -> x_v, gam_v, and the C0 partial sums
-__global__ void __launch_bounds__(256)
-grm_dot_epilogue(size_t M, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
-	double sum_b, const double *__restrict__ af, const double *__restrict__ inv,
-	const double *__restrict__ l0, double *__restrict__ xv, double *__restrict__ gv,
-	double *__restrict__ c0_partial)
-{
-	__shared__ double sh[4];
-	const int e = limb_scale(*maxb);
-	double c0[1] = {0};
-	for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < M; v += (size_t)gridDim.x * blockDim.x) {
-		const int *a = acc + v * GRM_NACC;
-		const HiLo V = mf_limbs(a), T3 = mf_limbs(a + GRM_NCOL);
-		const double t3 = ldexp(hl_to_double(T3), -e);
-		const double vw = ldexp(hl_to_double(hl_axpy(-3, T3, V)), -e);     // sum over codes 1,2 of code*b
-		const double dot = l0[v] * (sum_b - t3) + inv[v] * vw;
-		const double x = dot * inv[v];
-		xv[v] = x;
-		gv[v] = (3 - 2 * af[v]) * x;
-		c0[0] = fma(dot, l0[v], c0[0]);
-	}
-	block_sum<1, 256>(c0, sh);
-	if (threadIdx.x == 0) c0_partial[blockIdx.x] = c0[0];
-}
-
-// ---- pass-2 epilogue: out_i = (C0 + X_i - Gam_i) / M
-// A sample without a single non-zero standardised genotype (every code missing or on a monomorphic
-// marker: diag_i == 0, a sum of squares) has out_i = 0 as a sum of zero terms, and the reference's
-// loop gives exactly that; C0 + X_i - Gam_i only cancels to rounding level there.  0 * v keeps a
-// NaN or infinity of b visible, as 0 * dot does in the reference (:507-519).
-__device__ __forceinline__ double grm_out_value(double C0, double X, double G, size_t M, double diag_i)
-{
-	const double v = (C0 + X - G) / (double)M;
-	return (diag_i == 0) ? 0 * v : v;
-}
-
-__global__ void __launch_bounds__(256)
-grm_out_epilogue(int N, size_t M, const int *__restrict__ acc, const unsigned long long *__restrict__ maxx,
-	const unsigned long long *__restrict__ maxg, double C0, const double *__restrict__ diag, double *__restrict__ out)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= N) return;
-	const int ex = limb_scale(*maxx), eg = limb_scale(*maxg);
-	const int *a = acc + (size_t)i * GRM_NACC;
-	const double X = ldexp(hl_to_double(mf_limbs(a)), -ex);                       // code plane x x limbs
-	const double G = ldexp(hl_to_double(mf_limbs(a + GRM_NCOL + MF_NLIMB)), -eg);  // missing plane x gam limbs
-	out[i] = grm_out_value(C0, X, G, M, diag[i]);
-}
-
-// ---- vector kernels of PCG_diag_sigma (:581-614)
-// minv = 1 / max(tau0/w + tau1*diag, 1e-4)   (get_diag_sigma :542-559)
-__global__ void pcg_minv_kernel(int n, const double *w, const double *diag, double tau0, double tau1, double *minv)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	double v = tau0 / w[i] + tau1 * diag[i];
-	if (v < 1e-4) v = 1e-4;
-	minv[i] = 1 / v;
-}
-
-// r = b, z = minv*r, p = z, x = 0
-__global__ void pcg_init_kernel(int n, const double *b, const double *minv, double *r, double *z, double *p, double *x)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const double ri = b[i];
-	r[i] = ri; z[i] = minv[i] * ri; p[i] = z[i]; x[i] = 0;
-}
-
-// Ap = tau0 * p / w + tau1 * gp   (get_crossprod :564-576); gp may be NULL when tau1 == 0
-__global__ void pcg_ap_kernel(int n, const double *p, const double *w, const double *gp, double tau0, double tau1, double *Ap)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const double base = tau0 * (p[i] * (1 / w[i]));
-	Ap[i] = gp ? base + tau1 * gp[i] : base;
-}
-
-// x += a p; r -= a Ap; z = minv r
-__global__ void pcg_update_kernel(int n, double a, const double *p, const double *Ap, const double *minv,
-	double *x, double *r, double *z)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	x[i] += a * p[i];
-	const double ri = r[i] - a * Ap[i];
-	r[i] = ri; z[i] = minv[i] * ri;
-}
-
-// p = z + bet p
-__global__ void pcg_dir_kernel(int n, double bet, const double *z, double *p)
-{
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	p[i] = z[i] + bet * p[i];
-}
-
-// ===========================================================================
-// Several right-hand sides at once (sgx_grm_*_multi, host_grm.h).  Each kernel below restates one
-// kernel above for a set of columns: blockIdx.y picks the column, the grid-stride partition over
-// blockIdx.x and every expression are those of the single-vector kernel, so a column's result is
-// bit-identical to the single call on it.  Column c of a set lives at base + c * ld.
-
-#define GRM_MAX_RHS 64        /* SGX_GRM_MAX_RHS                                     */
-#define GRM_MAXF 3            /* value fragments of a batched contraction launch (4 spill: DESIGN.md) */
-#define GRM_GROUP (2 * GRM_MAXF)   /* columns per pass-1 launch: two per 16-column fragment         */
-#define GRM_GROUP2 GRM_MAXF        /* columns per pass-2 launch: one per fragment (x and gam limbs) */
-
-struct GrmCols {              // the columns of a set a launch works on (kernel argument, by value)
-	int n;
-	int c[GRM_MAX_RHS];
-};
-
-struct GrmScal {              // one double per column of a launch (by value)
-	double v[GRM_MAX_RHS];
-};
-
-// dot_partial_kernel per column: out[y * GRM_RED_BLOCKS-sized row + blockIdx.x]
-template <bool WITH_B>
-__global__ void __launch_bounds__(256)
-dot_partial_multi_kernel(const double *__restrict__ A, const double *__restrict__ B, size_t ld, GrmCols cols,
-	size_t n, double *__restrict__ out)
-{
-	__shared__ double sh[4];
-	const size_t c = (size_t)cols.c[blockIdx.y];
-	const double *__restrict__ a = A + c * ld;
-	const double *__restrict__ b = WITH_B ? B + c * ld : nullptr;
-	double s[1] = {0};
-	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-		s[0] = WITH_B ? fma(a[i], b[i], s[0]) : s[0] + a[i];
-	block_sum<1, 256>(s, sh);
-	if (threadIdx.x == 0) out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
-}
-
-// absmax_kernel per column: out[3 * y + slot]
-__global__ void __launch_bounds__(256)
-absmax_multi_kernel(const double *__restrict__ X, size_t ld, GrmCols cols, size_t n, int slot,
-	unsigned long long *__restrict__ out)
-{
-	const double *__restrict__ x = X + (size_t)cols.c[blockIdx.y] * ld;
-	double m = 0;
-	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-		const double a = fabs(x[i]);
-		m = (a > m) ? a : m;
-	}
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) { const double t = __shfl_xor(m, o, WAVE); m = (t > m) ? t : m; }
-	if ((threadIdx.x & (WAVE - 1)) == 0) atomicMax(out + 3 * blockIdx.y + slot, (unsigned long long)__double_as_longlong(m));
-}
-
-// limbs_kernel per column y into a tile image of ncol columns: first limb column
-// 16 * (y / per_frag) + 7 * (y % per_frag) + off; the columns nobody writes must be zero beforehand
-__global__ void __launch_bounds__(256)
-limbs_multi_kernel(const double *__restrict__ X, size_t ld, GrmCols cols, size_t n, size_t n_pad, int ncol,
+limbs_kernel(const double *__restrict__ X, size_t ld, GrmCols cols, size_t n, size_t n_pad, int ncol,
 	int per_frag, int off, const unsigned long long *__restrict__ maxbits, int slot, uint8_t *__restrict__ Fl)
 {
 	const int y = blockIdx.y;
@@ -352,10 +349,28 @@ limbs_multi_kernel(const double *__restrict__ X, size_t ld, GrmCols cols, size_t
 	}
 }
 
-// grm_dot_epilogue per column y of a pass-1 launch with nbfv fragments (two columns per fragment);
-// x_v, gam_v -> XV / GV row y (stride M), C0 partials -> c0_partial[y * gridDim.x + blockIdx.x]
+// deterministic block partial sums per column: out[y * gridDim.x + blockIdx.x] = sum of a[i] (* b[i])
+template <bool WITH_B>
 __global__ void __launch_bounds__(256)
-grm_dot_epilogue_multi(size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
+dot_partial_kernel(const double *__restrict__ A, const double *__restrict__ B, size_t ld, GrmCols cols,
+	size_t n, double *__restrict__ out)
+{
+	__shared__ double sh[4];
+	const size_t c = (size_t)cols.c[blockIdx.y];
+	const double *__restrict__ a = A + c * ld;
+	const double *__restrict__ b = WITH_B ? B + c * ld : nullptr;
+	double s[1] = {0};
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+		s[0] = WITH_B ? fma(a[i], b[i], s[0]) : s[0] + a[i];
+	block_sum<1, 256>(s, sh);
+	if (threadIdx.x == 0) out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
+}
+
+// ---- pass-1 epilogue: dot_v -> x_v, gam_v, and the C0 partial sums, per column y of a pass-1 launch
+// with nbfv fragments (two columns per fragment); x_v, gam_v -> XV / GV row y (stride M),
+// C0 partials -> c0_partial[y * gridDim.x + blockIdx.x]
+__global__ void __launch_bounds__(256)
+grm_dot_epilogue(size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
 	GrmScal sum_b, const double *__restrict__ af, const double *__restrict__ inv,
 	const double *__restrict__ l0, double *__restrict__ XV, double *__restrict__ GV,
 	double *__restrict__ c0_partial)
@@ -372,7 +387,7 @@ grm_dot_epilogue_multi(size_t M, int nbfv, const int *__restrict__ acc, const un
 		const int *a = acc + v * stride + col;
 		const HiLo V = mf_limbs(a), T3 = mf_limbs(a + 16 * nbfv);
 		const double t3 = ldexp(hl_to_double(T3), -e);
-		const double vw = ldexp(hl_to_double(hl_axpy(-3, T3, V)), -e);
+		const double vw = ldexp(hl_to_double(hl_axpy(-3, T3, V)), -e);     // sum over codes 1,2 of code*b
 		const double dot = l0[v] * (sb - t3) + inv[v] * vw;
 		const double x = dot * inv[v];
 		xv[v] = x;
@@ -383,9 +398,20 @@ grm_dot_epilogue_multi(size_t M, int nbfv, const int *__restrict__ acc, const un
 	if (threadIdx.x == 0) c0_partial[(size_t)y * gridDim.x + blockIdx.x] = c0[0];
 }
 
-// grm_out_epilogue per column y of a pass-2 launch with nbfv fragments (one column per fragment)
+// ---- pass-2 epilogue: out_i = (C0 + X_i - Gam_i) / M
+// A sample without a single non-zero standardised genotype (every code missing or on a monomorphic
+// marker: diag_i == 0, a sum of squares) has out_i = 0 as a sum of zero terms, and the reference's
+// loop gives exactly that; C0 + X_i - Gam_i only cancels to rounding level there.  0 * v keeps a
+// NaN or infinity of b visible, as 0 * dot does in the reference (:507-519).
+__device__ __forceinline__ double grm_out_value(double C0, double X, double G, size_t M, double diag_i)
+{
+	const double v = (C0 + X - G) / (double)M;
+	return (diag_i == 0) ? 0 * v : v;
+}
+
+// per column y of a pass-2 launch with nbfv fragments (one column per fragment: x limbs 0.., gam limbs 7..)
 __global__ void __launch_bounds__(256)
-grm_out_epilogue_multi(int N, size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
+grm_out_epilogue(int N, size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
 	GrmScal C0, const double *__restrict__ diag, double *__restrict__ Out, size_t ldo, GrmCols cols)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -393,14 +419,24 @@ grm_out_epilogue_multi(int N, size_t M, int nbfv, const int *__restrict__ acc, c
 	if (i >= N) return;
 	const int ex = limb_scale(maxb[3 * y + 1]), eg = limb_scale(maxb[3 * y + 2]);
 	const int *a = acc + (size_t)i * (32 * nbfv) + 16 * y;
-	const double X = ldexp(hl_to_double(mf_limbs(a)), -ex);
-	const double G = ldexp(hl_to_double(mf_limbs(a + 16 * nbfv + MF_NLIMB)), -eg);
+	const double X = ldexp(hl_to_double(mf_limbs(a)), -ex);                            // code plane x x limbs
+	const double G = ldexp(hl_to_double(mf_limbs(a + 16 * nbfv + MF_NLIMB)), -eg);     // missing plane x gam limbs
 	Out[(size_t)cols.c[y] * ldo + i] = grm_out_value(C0.v[y], X, G, M, diag[i]);
 }
 
-// ---- PCG_diag_sigma vector kernels per column (blockIdx.y); w and minv are shared
+// ---- vector kernels of PCG_diag_sigma (:581-614); w and minv are shared by the columns
+// minv = 1 / max(tau0/w + tau1*diag, 1e-4)   (get_diag_sigma :542-559)
+__global__ void pcg_minv_kernel(int n, const double *w, const double *diag, double tau0, double tau1, double *minv)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	double v = tau0 / w[i] + tau1 * diag[i];
+	if (v < 1e-4) v = 1e-4;
+	minv[i] = 1 / v;
+}
+
 // r = b, z = minv*r, p = z, x = 0
-__global__ void pcg_init_multi_kernel(int n, const double *B, size_t ldb, const double *minv,
+__global__ void pcg_init_kernel(int n, const double *B, size_t ldb, const double *minv,
 	double *R, double *Z, double *P, double *X, GrmCols cols)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -410,8 +446,8 @@ __global__ void pcg_init_multi_kernel(int n, const double *B, size_t ldb, const 
 	R[o] = ri; Z[o] = minv[i] * ri; P[o] = Z[o]; X[o] = 0;
 }
 
-// Ap = tau0 * p / w + tau1 * gp; GP may be NULL when tau1 == 0
-__global__ void pcg_ap_multi_kernel(int n, const double *P, const double *w, const double *GP, double tau0, double tau1,
+// Ap = tau0 * p / w + tau1 * gp   (get_crossprod :564-576); GP may be NULL when tau1 == 0
+__global__ void pcg_ap_kernel(int n, const double *P, const double *w, const double *GP, double tau0, double tau1,
 	double *AP, GrmCols cols)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -422,7 +458,7 @@ __global__ void pcg_ap_multi_kernel(int n, const double *P, const double *w, con
 }
 
 // x += a p; r -= a Ap; z = minv r   (a per column)
-__global__ void pcg_update_multi_kernel(int n, GrmScal a, const double *P, const double *AP, const double *minv,
+__global__ void pcg_update_kernel(int n, GrmScal a, const double *P, const double *AP, const double *minv,
 	double *X, double *R, double *Z, GrmCols cols)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -435,7 +471,7 @@ __global__ void pcg_update_multi_kernel(int n, GrmScal a, const double *P, const
 }
 
 // p = z + bet p   (bet per column)
-__global__ void pcg_dir_multi_kernel(int n, GrmScal bet, const double *Z, double *P, GrmCols cols)
+__global__ void pcg_dir_kernel(int n, GrmScal bet, const double *Z, double *P, GrmCols cols)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;

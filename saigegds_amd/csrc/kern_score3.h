@@ -1,8 +1,9 @@
-// kern_score3.h -- score stage v3: the exact-integer contraction of kern_score_mfma.h as a PERSISTENT
+// kern_score3.h -- score stage v3: the exact-integer contraction of mf_fixed.h as a PERSISTENT
 // streaming kernel over genotype blocks in the library's tiled device layout.
 // Part of libsaigehip.so; also included alone by tools/score3_bench.hip (S3_KERNEL_ONLY).
 //
-// What changed against score_mfma_kernel (round 2: 1.6 ms per 50 000 variants at N = 430 000, issue-bound):
+// What changed against round 2's scan kernel (a row-major kernel with a missing plane, of which the GRM
+// operator's grm_contract_kernel is what remains: 1.6 ms per 50 000 variants at N = 430 000, issue-bound):
 //   * Device layout ("block"): 16 variants x 256 samples = one contiguous KiB, [fragment][tile][lane][16 B];
 //     a wave's row load is 8 whole 128-B lines instead of 16 half lines of 16 different rows.
 //   * No missing plane.  The rows keep their code 3, the value plane still sums V = T1 + 2 T2 + 3 T3, but

@@ -79,7 +79,7 @@ __host__ __device__ __forceinline__ size_t s3_piece_off(size_t j, size_t p, int 
 // 16-byte slot of the KiB that the consumer lane (r = lane & 15: variant, kg = lane >> 4: 64-sample piece) wants
 __host__ __device__ __forceinline__ int s3_dma_lane(int lane) { return ((lane & 15) << 2) | (lane >> 4); }
 
-// Sample order inside a group of 16 (as kern_score_mfma.h mf_pos): byte j of (w >> 2t) & 0x03030303 is
+// Sample order inside a group of 16 (as mf_fixed.h mf_pos): byte j of (w >> 2t) & 0x03030303 is
 // the code of sample 4 j + t, and the B tiles store the 16 samples of a group in that order.
 __host__ __device__ __forceinline__ int s3_pos(int s) { return ((s & 3) << 2) | (s >> 2); }
 

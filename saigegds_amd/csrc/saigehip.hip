@@ -61,7 +61,7 @@ static int fail(int code, const char *fmt, ...)
 
 #include "dev_common.h"
 #include "kern_score.h"
-#include "kern_score_mfma.h"
+#include "mf_fixed.h"
 #include "kern_score3.h"
 #include "kern_spa.h"
 #include "kern_spa2.h"

@@ -15,7 +15,7 @@ from collections import namedtuple
 
 import numpy as np
 
-# ---- the limb rule (kern_score_mfma.h MF_*, host_init.h limbs_for) -------------------------------------------
+# ---- the limb rule (mf_fixed.h MF_*, host_init.h limbs_for) -------------------------------------------
 MF_NLIMB, MF_LIMB_A, MF_LIMB_E = 7, 5, 6
 LD = np.longdouble
 

@@ -1,4 +1,4 @@
-"""GPU: the implicit-GRM operator (kern_grm.h, host_grm.h, score_mfma_kernel<NBFV,false,true>) against the
+"""GPU: the implicit-GRM operator (kern_grm.h, host_grm.h, grm_contract_kernel<NBFV>) against the
 long-double reference of grm_ref.py at the tile edges of its kernels (256-row workgroups, pairs of
 256-sample tiles, the 64 x 256 transpose tile, 16-marker dwords), with N and M in both roles, at 0.5 %
 and 30 % missing, for constant, wide-range and extreme-scale vectors; stray codes in the padding; the
@@ -8,7 +8,7 @@ preconditioner clamp.
 Accuracy bound.  scaled_error (grm_ref.py) of every product is at most 4 E_ORC, E_ORC being the worst
 scaled error of the double-precision oracle over the same table (test_grm_ref.py).  The kernel's
 fma(code, inv, l0) adds one rounding per entry, of the kind of the oracle's rounded table; the limb
-quantisation is below the rounding of a double dot product (kern_score_mfma.h); 4 covers the different
+quantisation is below the rounding of a double dot product (mf_fixed.h); 4 covers the different
 summation order and the ~10 double operations of the two epilogues."""
 import numpy as np
 import pytest

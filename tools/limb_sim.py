@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """How many fixed-point bits do the covariate-projection columns of the MFMA score path need?
 
-CPU experiment behind the limb counts in kern_score_mfma.h ("Limb counts"): quantise the
+CPU experiment behind the limb counts in mf_fixed.h ("Limb counts"): quantise the
 t_XVX_inv_XV columns (c') and the w*X columns (e) to a given number of bits, form
     var2 = c'.XVX.c' + w - 2 e.c'      S = s - S_a.c'
 in long double for real variants, and report the largest relative change of var2 and the largest
