@@ -28,7 +28,7 @@ static int launch_score3(sgx_handle *h, const sgx_block *b, RowsRef rr, size_t M
 	int rc = ensure_buf(h, &h->s3_slabs, &h->s3_slabs_cap, (size_t)pl.ng * pl.ipg * s.nc * s.naf * slots * 256);
 	if (rc) return rc;
 	const size_t lds = s3_lds_bytes(s.nbf, s.naf, s.nc, s.da, s.db);
-	auto kern = score3_kernel<s.nbf, s.naf, s.nc, s.nla, s.nlb, s.da, s.db, 0, 1, 2, 1, MISS>;
+	auto kern = score3_kernel<s.nbf, s.naf, s.nc, s.nla, s.nlb, s.da, s.db, MISS>;
 	bool &attr = (MISS ? h->s3_attr_miss : h->s3_attr)[s.nbf];
 	if (!attr) {
 		HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -36,7 +36,7 @@ static int launch_score3(sgx_handle *h, const sgx_block *b, RowsRef rr, size_t M
 	}
 	HIPCHK(hipEventRecord(h->evk[0], st));
 	hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * (s.nc + s.nla + s.nlb)), lds, st,
-		rr.base, (const uint8_t *)h->dFl, pl, h->s3_slabs, (unsigned long long *)nullptr);
+		rr.base, (const uint8_t *)h->dFl, pl, h->s3_slabs);
 	HIPCHK(hipEventRecord(h->evk[1], st));
 	h->evk_set = true;
 	return SGX_OK;
@@ -110,13 +110,13 @@ static int launch_block_scan(sgx_handle *h, const sgx_block *b, size_t M, double
 	const int acc_stride = 16 * slots;
 	const int per = sh.nc * sh.naf * slots * 256;
 	hipLaunchKernelGGL(s3_reduce_kernel, dim3((unsigned)((per / 4 + 255) / 256), (unsigned)pl.vt), dim3(256), 0, st,
-		pl, (int)M, sh.nc, sh.naf, slots, 1, h->s3_slabs, h->mf_acc, acc_stride, h->counters, h->cur5);
+		pl, (int)M, sh.nc, sh.naf, slots, h->s3_slabs, h->mf_acc, acc_stride, h->counters, h->cur5);
 	const int btop = md.quant ? 0 : (int)(2 * M);
 	if (!with_k(md.K, [&](auto kk) {
 		constexpr int KK = decltype(kk)::value;
 		hipLaunchKernelGGL((score3_epilogue<KK>), dim3((unsigned)((M + s3e_vb(KK) - 1) / s3e_vb(KK))), dim3(s3e_vb(KK)), 0, st,
 			(int)M, md, h->mfe, h->mf_acc, acc_stride, miss ? 16 * NBF : 0, h->s3_t3, b->nr, L.lcnt, L.ld, h->s3_ovf, h->recs,
-			h->counters, btop, h->fb_spa2, h->fb_x2, out8, valid, h->guard_tol, (h->owner ? h->owner : h)->spa_abl >> 16);
+			h->counters, btop, h->fb_spa2, h->fb_x2, out8, valid, h->guard_tol);
 		hipLaunchKernelGGL((score2b_kernel<2 * KK + 2, 256>), dim3((unsigned)std::min<size_t>(M, 4 * (size_t)h->n_cu)), dim3(256), 0, st,
 			rr, (int)M, md, h->recs, h->counters, out8, valid, (const int *)h->s3_ovf, 23, btop, h->fb_spa2, h->fb_x2);
 	}))

@@ -1,23 +1,25 @@
-// kern_score3.h -- score stage v3: the exact-integer contraction of mf_fixed.h as a PERSISTENT
-// streaming kernel over genotype blocks in the library's tiled device layout.
-// Part of libsaigehip.so; also included alone by tools/score3_bench.hip (S3_KERNEL_ONLY).
+// kern_score3.h -- score stage v3: the exact-integer contraction of mf_fixed.h as a PERSISTENT streaming kernel
+// over the 2-bit genotype rows of a block, and what runs around it (lists' offsets, T3 pass, reduction, epilogue).
+// Part of libsaigehip.so; tools/score3_bench.hip includes the contraction kernel alone (S3_KERNEL_ONLY).
 //
-// What changed against round 2's scan kernel (a row-major kernel with a missing plane, of which the GRM
-// operator's grm_contract_kernel is what remains: 1.6 ms per 50 000 variants at N = 430 000, issue-bound):
-//   * Device layout ("block"): 16 variants x 256 samples = one contiguous KiB, [fragment][tile][lane][16 B];
-//     a wave's row load is 8 whole 128-B lines instead of 16 half lines of 16 different rows.
-//   * No missing plane.  The rows keep their code 3, the value plane still sums V = T1 + 2 T2 + 3 T3, but
-//     T3 (the sums over the MISSING samples) comes from a sparse pass over the block's list of missing
-//     genotypes (s3_t3_kernel): exact int64 sums of the same fixed-point values.  The contraction kernel
-//     loses 1.9 of its 5.9 MFMAs per fragment-step, the ballot, the second unpack and 36 accumulators.
-//   * Any K <= 16 in ONE pass: up to 13 B fragments per tile (accumulators 4 NAF NBF registers); the rows
-//     are streamed once, not once per column group.
-//   * Persistent workgroups with a static item list instead of a (variant tile, split) grid: no tail of
-//     half-empty rounds, the first tiles of the next item are in flight while the current one ends, and
-//     partial sums leave by plain stores into per-item slabs (no atomics, no memset of the accumulators).
-//   * Counted waits: the B tile (LDS-DMA) of step n + 1 is issued FIRST in step n, then the row loads of
-//     step n + D; the top of a step waits for vmcnt(NAF (D - 1)), so row loads stay in flight across the
-//     tile barrier (__syncthreads() drained every load at every tile).
+// score3_kernel multiplies every variant's row of codes into the limb tiles of the score vectors (int8 MFMAs,
+// int32 sums: exact).  One workgroup per CU works through a static list of items (s3_layout.h: a variant tile
+// against a range of sample tiles) and leaves an item's partial sums by plain stores into the item's own slab:
+// no atomics, no memset, no tail of half-empty rounds; s3_reduce_kernel adds the slabs up.
+//   * Roles.  Every byte reaches the matrix cores through LDS.  ROW LOADER waves bring the rows from HBM, B LOADER
+//     waves the limb tiles from L2, both by LDS-DMA and nothing else; CONSUMER waves read LDS, unpack and issue
+//     MFMAs, and no vector-memory instruction: a full memory queue never stalls a wave that has MFMAs to issue.
+//   * The pair ring.  A 256-sample tile of a row is 64 B, half a cache line, so the row ring holds PAIRS of tiles:
+//     a DMA instruction fetches whole 128-byte lines of eight rows, in a piece order that lets the consumers'
+//     ds_read_b128 touch every LDS bank once.
+//   * Counted waits.  One s_barrier per tile joins loaders and consumers; a loader waits with a counted vmcnt for
+//     the tile the barrier opens only, so the loads of its younger tiles stay in flight across the barrier.  The
+//     consumers' LDS reads are inline assembly with counted lgkmcnt waits (the compiler would put vmcnt(0) in
+//     front of every LDS read it sees behind an LDS-DMA).
+//   * Two forms.  Two planes (value, bit 1): the rows keep their code 3, and the sums over the MISSING samples
+//     (T3) come from a sparse pass over lists of the missing genotypes (s3_t3_kernel, kern_lists.h).  Three planes
+//     (MISS): the plane [code == 3] is multiplied into every value column as well, so T3 comes out of the
+//     contraction itself and no lists are needed.
 #pragma once
 #include <type_traits>
 
@@ -37,9 +39,13 @@ template <int OFF> __device__ __forceinline__ void s3_ds_read(s3_v4i &dst, uint3
 }
 template <int N> __device__ __forceinline__ void s3_lgkm_wait(s3_v4i &reg) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(reg) : "n"(N)); }
 __device__ __forceinline__ void s3_tie(s3_v4i &reg) { asm volatile("" : "+v"(reg)); }
-#define S3_DS_READ(dst, addr, off) s3_ds_read<(off)>(dst, addr)
-#define S3_LGKM_WAIT(n, reg) s3_lgkm_wait<(n)>(reg)
-#define S3_TIE(reg) s3_tie(reg)
+// all but the N youngest LDS reads are back: regs[0 .. CNT) may be used behind this
+template <int N, int CNT> __device__ __forceinline__ void s3_wait_regs(s3_v4i *regs)
+{
+	s3_lgkm_wait<N>(regs[0]);
+#pragma unroll
+	for (int i = 1; i < CNT; i++) s3_tie(regs[i]);
+}
 
 template <int I, int N, typename F>
 __device__ __forceinline__ void s3_static_for(F &&f)
@@ -156,52 +162,64 @@ struct s3_one {
 	}
 };
 
-// NBF: B fragments per tile (value fragments + the bit-1 fragment, the LAST one).  NAF: A fragments (16
-// variants) per consumer wave.  NC consumer waves + NLA row-loader waves + NLB B-loader waves per workgroup
-// (one workgroup per CU).
+// The B fragments of a tile reach a consumer's registers in chunks of <= BCH fragments, NCH chunks per dword step
+// and 4 NCH per tile, into S3_NBUF register buffers of one chunk each: the reads run S3_NBUF - 1 chunks ahead of
+// the MFMAs.  (With one consumer wave per SIMD and all of them reading in step behind the tile barrier an LDS read
+// takes ~270 cycles to come back.  Deeper buffers were measured and bought nothing.)
+#define S3_NBUF 2
+template <int NBF, int BCH>
+struct s3_chunks {
+	static constexpr int NCH = (NBF + BCH - 1) / BCH;
+	static constexpr int last = NBF - (NCH - 1) * BCH;                   // fragments of a dword step's last chunk
+	static constexpr int size(int ci) { return ci % NCH == NCH - 1 ? last : BCH; }
+	// fragment reads of chunks [c0, c1) of the tile
+	static constexpr int nreads(int c0, int c1) { int n = 0; for (int c = c0; c < c1 && c < 4 * NCH; c++) n += size(c); return n; }
+};
+// entering chunk ci of a tile: start the chunk S3_NBUF - 1 ahead, then wait for this one (younger reads stay in flight)
+template <typename CH, int ci, int BCH, typename RC>
+__device__ __forceinline__ void s3_enter_chunk(s3_v4i (&bf)[S3_NBUF][BCH], RC &read_chunk)
+{
+	if constexpr (ci + S3_NBUF - 1 < 4 * CH::NCH) read_chunk(std::integral_constant<int, ci + S3_NBUF - 1>());
+	s3_wait_regs<CH::nreads(ci + 1, ci + S3_NBUF), CH::size(ci)>(bf[ci % S3_NBUF]);
+}
+
+// NBF: B fragments per tile (value fragments + the bit-1 fragment, the LAST one).  NAF: A fragments (16 variants)
+// per consumer wave.  NC consumer waves + NLA row-loader waves + NLB B-loader waves per workgroup (one workgroup
+// per CU).  DA: pairs of row tiles ahead, DB: B tiles ahead.  The shapes in use: S3_FOR_EACH_NBF[_MISS] below.
+// A: the block's row-major 2-bit rows (pl.nrow rows of pl.bpv bytes), Fl: the limb tiles, out: the item slabs.
 //
-// Roles.  Every byte reaches the matrix cores through LDS: the row pieces of a tile (NC NAF KiB, from HBM) are
-// LDS-DMA'd DA tiles ahead into a ring of DA + 1 slots by the ROW LOADERS, its B tile (4 NBF KiB, from L2) DB
-// tiles ahead into DB + 1 slots by the B LOADERS; they do nothing else (buffer_load .. lds with a scalar
-// offset per piece: no vector instruction at all).  The CONSUMER waves issue no vector-memory instruction in
-// the loop (LDS reads, unpack, MFMA only), so a full memory queue never stalls a wave that has MFMAs to
-// issue.  (One symmetric wave type doing both: 1.22 ms against 0.90 for its arithmetic alone and 0.95 for its
-// memory traffic alone.)  One s_barrier per tile joins them: a loader arrives once its pieces of the tile
-// have landed (counted vmcnt: the pieces of its younger tiles stay in flight across the barrier), after it
-// the loaders refill the slot the consumers have just left.  Row and B loaders are different waves because
-// vmcnt counts in order: behind the same counter the rows could not run further ahead than the B tiles.
-// LDS per workgroup: (DB + 1) x 4 NBF + (DA + 1) x NC NAF KiB.
-// ABL (timing tool only, wrong results): 1 no unpack/MFMA, 2 no row DMA, 4 no B DMA, 8 no LDS reads of B,
-//   16 clock stamps (s_memtime / s_memrealtime per workgroup behind the slabs)
-// RM = 1: the rows are the caller's ROW-MAJOR 2-bit rows (pl.bpv bytes each, pl.nrow of them), not tiles.  A tile of
-//   a row is 64 B -- half a cache line -- and 16 half lines of 16 rows per wave instruction read 15-20 % slower than
-//   a tile's contiguous KiB, whole lines of 8 rows at the tiles' rate (measured: tools/README.md, round 4).  So the
-//   row ring holds PAIRS of tiles (DA pairs ahead, DA + 1 slots of 2 NPA KiB): a row loader's DMA instruction
-//   fetches the 128-byte line (tiles t, t + 1) of rows 8 h .. 8 h + 7 of a fragment into KiB 2 p + h of the slot,
-//   lanes 8 i .. 8 i + 7 = the eight 16-byte pieces of row 8 h + i, in the order c = j ^ sigma(i, h),
-//   sigma = (i >> 1) | (h << 2), c = 4 (tile parity) + kg: with that order the consumers' ds_read_b128 lane groups
-//   (16 lanes = the 64-sample pieces of 16 rows at one kg) touch every bank once.  The consumers' only change is
-//   the address of a row piece (per tile parity).  B tiles and the barrier stay per tile.  (Staging the lines
-//   through the loaders' registers and ds_write_b128 into a single-tile ring was built first: same memory rate,
-//   but the LDS store path -- ~80 B per clock and CU -- cost 0.18 ms of a 1.07-ms kernel.)
-//   (RM = 2: timing experiment of the tool, wrong results.)
+// Roles.  The row pieces of a pair of tiles (2 NC NAF KiB, from HBM) are LDS-DMA'd DA pairs ahead into a ring of
+// DA + 1 slots by the ROW LOADERS, a B tile (4 NBF KiB, from L2) DB tiles ahead into DB + 1 slots by the B LOADERS
+// (buffer_load .. lds with a scalar offset per piece: no vector instruction at all).  The CONSUMER waves issue
+// LDS reads, unpack operations and MFMAs only.  One s_barrier per tile joins them: a loader arrives once its
+// pieces of the tile have landed (counted vmcnt: the pieces of its younger tiles stay in flight across the
+// barrier); behind it the loaders refill the slot the consumers have just left.  Row and B loaders are different
+// waves because vmcnt counts in order: behind the same counter the rows could not run further ahead than the B
+// tiles.  LDS per workgroup: (DB + 1) x 4 NBF + (DA + 1) x 2 NC NAF KiB (s3_lds_bytes).
+//
+// The pair ring.  A tile of a row is 64 B -- half a cache line -- and 16 half lines of 16 rows per wave instruction
+// read 15-20 % slower than whole lines.  So a row loader's DMA instruction fetches the 128-byte line (tiles t, t + 1)
+// of rows 8 h .. 8 h + 7 of a fragment into KiB 2 p + h of the slot, lanes 8 i .. 8 i + 7 = the eight 16-byte pieces
+// of row 8 h + i, in the order c = j ^ sigma(i, h), sigma = (i >> 1) | (h << 2), c = 4 (tile parity) + kg: with
+// that order the consumers' ds_read_b128 lane groups (16 lanes = the 64-sample pieces of 16 rows at one kg) touch
+// every bank once.  To the consumers a pair is two tiles that differ in the address of a row piece; B tiles and
+// the barrier stay per tile.
+//
 // MISS: the three-plane form (s3_unpack3_op): a consumer wave keeps a second set of accumulators, the missing plane
 //   against the NBF - 1 value fragments; its slab is NAF x (2 NBF - 1) fragment slots, the missing plane's behind
-//   the NBF of the two-plane form.  NCB = 1 only.
-template <int NBF, int NAF, int NC, int NLA, int NLB, int DA, int DB, int ABL = 0, int NCB = 1, int NBUF_ = 2, int RM = 0, bool MISS = false>
+//   the NBF of the two-plane form.
+template <int NBF, int NAF, int NC, int NLA, int NLB, int DA, int DB, bool MISS>
 __global__ void __launch_bounds__(64 * (NC + NLA + NLB), (NC + NLA + NLB + 3) / 4)
-score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3Plan pl, int *__restrict__ out, unsigned long long *__restrict__ stamps)
+score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3Plan pl, int *__restrict__ out)
 {
 #if __HIP_DEVICE_COMPILE__      /* (the host pass only needs the stub; it does not know the buffer-resource builtins) */
-	static_assert(NC % NCB == 0 && NCB >= 1 && NCB <= 4, "consumer waves = variant groups x column groups");
-	constexpr int NCV = NC / NCB;                             // variant groups: consumer wave wid = (vg, cg) = (wid / NCB, wid % NCB)
-	constexpr int NBWMAX = (NBF + NCB - 1) / NCB;             // B fragments of a column group (the last group may hold fewer)
+	constexpr int NBUF = S3_NBUF;
 	constexpr int NCOL = 16 * NBF;
 	constexpr int TILE_BYTES = 16 * NCOL * 16;
 	constexpr int NPB = TILE_BYTES / 1024;                    // KiB pieces of a B tile = 4 NBF
-	constexpr int NPA = NCV * NAF;                            // KiB pieces of a tile's rows
-	constexpr int RA = DA + 1, RB = DB + 1;                   // ring slots (RM = 1: the row ring's slots are PAIRS of tiles)
-	constexpr int SLOT_A = (RM == 1 ? 2 : 1) * NPA * 1024;
+	constexpr int NPA = NC * NAF;                             // row fragments of a variant tile (2 KiB each per pair of tiles)
+	constexpr int RA = DA + 1, RB = DB + 1;                   // ring slots (the row ring's slots are PAIRS of tiles)
+	constexpr int SLOT_A = 2 * NPA * 1024;
 	static_assert(DA >= 1 && DB >= 1, "at least one tile ahead");
 	extern __shared__ __attribute__((aligned(16))) uint8_t s3_smem[];   // RB x TILE_BYTES (B), then RA x SLOT_A (rows)
 
@@ -209,10 +227,8 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 	const int x = blockIdx.x & 7, y = blockIdx.x >> 3;
 	const int g = x % pl.ng, i = y * (8 / pl.ng) + x / pl.ng;
 	const int nk = pl.rf + (i < pl.rem * pl.f ? 1 : 0);     // items of this workgroup
-	// tile ranges in whole PAIRS of tiles (ntile is even): a pair of tiles is one 128-byte line of a row-major row
+	// tile ranges in whole PAIRS of tiles (ntile is even): a pair of tiles is one 128-byte line of a row
 	const int T0 = 2 * (int)((long long)g * (pl.ntile / 2) / pl.ng), T1 = 2 * (int)((long long)(g + 1) * (pl.ntile / 2) / pl.ng);
-	unsigned long long st0 = 0, sr0 = 0;
-	if (ABL & 16) { st0 = __builtin_amdgcn_s_memtime(); sr0 = __builtin_amdgcn_s_memrealtime(); }
 
 	struct Pos { int k, t, t1, vtile, id; };                // wave-uniform stream positions
 	auto pos_set = [&](Pos &p, int k) {
@@ -234,15 +250,14 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 		// ---------------------------------------------------------------- loaders
 		const bool rows = wid < NC + NLA;
 		const int l = __builtin_amdgcn_readfirstlane(rows ? wid - NC : wid - NC - NLA);
-		const int voff = (rows ? s3_dma_lane(lane) : lane) * 16;   // rows: LDS slot `lane` receives the KiB's slot of (variant r, piece kg)
-		// row-major rows: LDS slot `lane` receives 16 B of row (lane & 15), piece (lane >> 4); in the block's last
-		// fragment the rows past the end are the last row again (their sums are never read)
+		const int voff = lane * 16;
 		const unsigned rm_bpv = (unsigned)pl.bpv;
 		Pos pa = pc;
 		int sl = 0;                                           // slot of the next tile to issue
 		int ahead = 0;                                        // tiles issued beyond the one the next barrier releases
-		if (rows && RM == 1) {
-			// ---- row-major rows: pairs of tiles, two DMA instructions (rows 0-7, rows 8-15) per fragment and pair
+		if (rows) {
+			// ---- pairs of tiles, two DMA instructions (rows 0-7, rows 8-15) per fragment and pair.  In the block's
+			// last fragment the rows past the end are the last row again (their sums are never read).
 			constexpr int PLO = NPA / NLA, NHI = NPA % NLA;       // loaders l < NHI take PLO + 1 fragments
 			static_assert(2 * (PLO + 1) * (DA > 1 ? DA - 1 : 1) < 64, "vmcnt range");
 			// lane = 8 i + j: row 8 h + i of the fragment, piece c = j ^ sigma(i, h) of its line
@@ -262,7 +277,7 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 #pragma unroll
 				for (int j = 0; j <= PLO; j++) {
 					const int p = l + j * NLA;
-					if (p >= NPA || (ABL & 2)) break;
+					if (p >= NPA) break;
 					const int pp = min(p, lastf);
 					// (fpw fragments x 16 rows x bpv bytes: far below 4 GiB)
 					const int so = (int)((unsigned)pp * 16u * rm_bpv + (unsigned)(pa.t >> 1) * 128u);
@@ -291,46 +306,6 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 				__builtin_amdgcn_s_barrier();                     // the pair's second tile: nothing to wait for, nothing to issue
 				pos_next(pc);
 			}
-		} else if (rows) {
-			constexpr int PLO = NPA / NLA, NHI = NPA % NLA;       // loaders l < NHI take PLO + 1 pieces
-			static_assert((PLO + 1) * (DA - 1) < 64, "vmcnt range");
-			auto issue = [&]() {
-				// rows of the item's variant tile: a descriptor at its first fragment, the fragment and the tile
-				// in the scalar offset (fpw fragments x ntile KiB: far below 4 GiB)
-				const size_t f0 = (size_t)pa.vtile * pl.fpw;
-				const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-					(void *)(A + (RM ? f0 * 16 * (size_t)pl.bpv : f0 * pl.ntile * 1024)), 0, 0xFFFFFFFFu, 0x00020000);
-				const int lastf = pl.nfrag - 1 - (int)f0;      // past the end: the last fragment again (never stored)
-#pragma unroll
-				for (int j = 0; j <= PLO; j++) {
-					const int p = l + j * NLA;
-					if (p >= NPA || (ABL & 2)) break;
-					if constexpr (RM == 1) {
-						// (not reached: RM = 1 has its own loop below)
-					} else if constexpr (RM == 2) {
-						// (timing experiment, wrong results: the same bytes as whole 128-B lines of 8 rows per instruction)
-						const int pp = min(p, lastf);
-						__builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void *)(s3_smem + RB * TILE_BYTES + sl * SLOT_A + p * 1024),
-							16, (int)((unsigned)(lane >> 3) * rm_bpv + (unsigned)(lane & 7) * 16u),
-							(int)(((unsigned)pp * 16u + (unsigned)(pa.t & 1) * 8u) * rm_bpv + (unsigned)(pa.t >> 1) * 128u), 0, 0);
-					} else
-					__builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void *)(s3_smem + RB * TILE_BYTES + sl * SLOT_A + p * 1024),
-						16, voff, (min(p, lastf) * pl.ntile + pa.t) * 1024, 0, 0);
-				}
-				sl = sl + 1 == RA ? 0 : sl + 1;
-				pos_next(pa);
-			};
-#pragma unroll
-			for (int d = 0; d < DA; d++) if (pa.k < nk) { issue(); ahead++; }
-			while (pc.k < nk) {
-				// the pieces of the tile this barrier releases have landed; `ahead - 1` younger tiles may fly
-				if (ahead == DA && DA > 1) { if (l < NHI) S3_WAITCNT_VM((PLO + 1) * (DA - 1)); else S3_WAITCNT_VM(PLO * (DA - 1)); }
-				else S3_WAITCNT_VM(0);
-				__builtin_amdgcn_s_barrier();
-				ahead--;
-				if (pa.k < nk) { issue(); ahead++; }
-				pos_next(pc);
-			}
 		} else {
 			constexpr int PLO = NPB / NLB, NHI = NPB % NLB;
 			static_assert((PLO + 1) * (DB - 1) < 64, "vmcnt range");
@@ -339,7 +314,7 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 #pragma unroll
 				for (int j = 0; j <= PLO; j++) {
 					const int b = l + j * NLB;
-					if (b >= NPB || (ABL & 4)) break;
+					if (b >= NPB) break;
 					__builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void *)(s3_smem + sl * TILE_BYTES + b * 1024),
 						16, voff, pa.t * TILE_BYTES + b * 1024, 0, 0);
 				}
@@ -362,105 +337,85 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 
 	// -------------------------------------------------------------------- consumer
 	const int r = lane & 15, kg = lane >> 4;
-	const int vg = __builtin_amdgcn_readfirstlane(wid / NCB), cgr = __builtin_amdgcn_readfirstlane(wid % NCB);
-	// LDS byte addresses of this lane's 16 B of a row piece and of its B fragment (sample group 4 kg, column r)
+	const int vg = __builtin_amdgcn_readfirstlane(wid);       // the wave's NAF row fragments of the variant tile
+	// LDS byte addresses of this lane's 16 B of a row piece and of its B fragment (sample group 4 kg, column r).
+	// Piece (r, kg) of the pair's tile of parity par sits in KiB 2 p + (r >> 3) of the pair's slot at 16-byte
+	// position 8 i + ((4 par + kg) ^ sigma(i, h)), i = r & 7, h = r >> 3 (see the loaders)
 	const uint32_t smem_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)s3_smem;
-	const uint32_t ring_lds = smem_lds + RB * TILE_BYTES + vg * (NAF * 1024) + lane * 16;
-	// row-major rows (RM = 1): piece (r, kg) of the pair's tile of parity par sits in KiB 2 p + (r >> 3) of the pair's
-	// slot at 16-byte position 8 i + ((4 par + kg) ^ sigma(i, h)), i = r & 7, h = r >> 3 (see the loaders)
 	const int rm_sig = ((r & 7) >> 1) | ((r >> 3) << 2);
 	const uint32_t ring_rm = smem_lds + RB * TILE_BYTES + vg * (NAF * 2048) + (uint32_t)(r >> 3) * 1024u + (uint32_t)(r & 7) * 128u;
 	const uint32_t ring_rm0 = ring_rm + (uint32_t)(kg ^ rm_sig) * 16u, ring_rm1 = ring_rm + (uint32_t)((4 + kg) ^ rm_sig) * 16u;
 
-	// The body of a consumer wave of column group CG: B fragments [B0, B0 + NBW) of the tile against the NAF row
-	// pieces of its variant group.  With NCB > 1 the waves of a variant group read the SAME row pieces and unpack
-	// them redundantly, each multiplying them into its own share of the columns: a wave's LDS reads per MFMA fall
-	// from (NAF + 4 NBF) / (4 NAF NBF) KiB to (NAF' + 4 NBF / NCB) / (4 NAF' NBF / NCB) with NAF' = NCB NAF pieces
-	// at the same number of accumulators -- at K >= 9 the LDS port (B reads + the DMA's writes), not the matrix
-	// pipe, was what the one-column-group form waited for.
-	auto consume = [&](auto CG) {
-		constexpr int cg = decltype(CG)::value;
-		constexpr int B0 = cg * NBWMAX;
-		constexpr int NBW = (NBF - B0 < NBWMAX) ? NBF - B0 : NBWMAX;
-		constexpr bool HASB1 = B0 + NBW == NBF;                 // the bit-1 fragment is the LAST of the tile
-		static_assert(NBW >= 1, "empty column group");
-		const uint32_t bt_lds = smem_lds + (4 * kg * NCOL + r) * 16 + B0 * 256;
+	// Both consumers enter a tile alike: the tile barrier, then the reads of the wave's row pieces of the tile in
+	// ring slot sa (parity par of its pair); b_addr: the lane's place in the B tile of slot sb.  (The ring state,
+	// bt_lds and the ring advance at the bottom of a tile stay written out in each consumer: hoisted or shared
+	// they compute the same but the compiler orders and names registers differently.)
+	auto enter_tile = [&](int sa, int sb, int par, uint32_t bt_lds, s3_v4i (&aw)[NAF], uint32_t &b_addr) {
+		__builtin_amdgcn_sched_barrier(0);
+		__builtin_amdgcn_s_barrier();
+		__builtin_amdgcn_sched_barrier(0);
+		const uint32_t a_addr = (par ? ring_rm1 : ring_rm0) + (uint32_t)(sa * SLOT_A);
+		b_addr = bt_lds + (uint32_t)(sb * TILE_BYTES);
+		s3_static_for<0, NAF>([&](auto F) { constexpr int f = decltype(F)::value; s3_ds_read<f * 2048>(aw[f], a_addr); });
+	};
 
-		s3_v4i acc[NAF][NBW];
+	// ---- the two-plane consumer: the NBF fragments of the tile against the wave's NAF row pieces
+	auto consume = [&]() {
+		const uint32_t bt_lds = smem_lds + (4 * kg * NCOL + r) * 16;
+		s3_v4i acc[NAF][NBF];
 #pragma unroll
 		for (int f = 0; f < NAF; f++)
 #pragma unroll
-			for (int b = 0; b < NBW; b++) acc[f][b] = (s3_v4i){0, 0, 0, 0};
+			for (int b = 0; b < NBF; b++) acc[f][b] = (s3_v4i){0, 0, 0, 0};
 
 		// B fragments are read one chunk (<= BCH fragments) ahead of the MFMAs that use them; per dword step u the
-		// NAF NBW MFMAs run fragment-major (a B fragment feeds NAF consecutive MFMAs) and the unpack operations --
+		// NAF NBF MFMAs run fragment-major (a B fragment feeds NAF consecutive MFMAs) and the unpack operations --
 		// the b1 planes of this step, then the value planes of the next -- are dealt out behind them, each group
 		// fenced so that the compiler keeps the order.
-		constexpr int BCH = NBUF_ > 2 ? 1 : NCB > 1 ? (NBW <= 2 ? NBW : 2) : (NBF <= 4 ? NBF : (NBF >= 9 ? 2 : (NBF % 3 == 0 ? 3 : 4)));
-		// NBUF register buffers of one chunk each: the reads run NBUF - 1 chunks ahead of the MFMAs.  (With one
-		// consumer wave per SIMD and all of them reading in step behind the tile barrier an LDS read takes ~270
-		// cycles to come back: one chunk of two fragments ahead = 2 NAF MFMAs is not enough at NAF <= 6.)
-		constexpr int NBUF = NBUF_;
+		constexpr int BCH = NBF <= 4 ? NBF : (NBF >= 9 ? 2 : (NBF % 3 == 0 ? 3 : 4));
+		using CH = s3_chunks<NBF, BCH>;
+		constexpr int NCH = CH::NCH;                            // chunks per dword step
 		// PIPE: two sets of value planes, the next dword's made evenly between ALL MFMAs of the current one (few
 		// fragments: the unpack is a large share of a step).  Otherwise ONE set leaves the registers to the
 		// accumulators, and the next dword's planes of row piece f are made right behind the last MFMA that reads
 		// the current ones (those of the wave's last value fragment), under the MFMAs that follow.
-		constexpr bool PIPE = NCB == 1 && NBF <= 8;
-		constexpr int NCH = (NBW + BCH - 1) / BCH;              // chunks per dword step
-		constexpr int NM = NAF * NBW;                           // MFMAs per dword step
-		constexpr int NV = HASB1 ? 4 * NAF : 0, NW = 5 * NAF;   // b1 operations of a step, value operations of the next
-		constexpr int BLV = HASB1 ? NBW - 2 : NBW - 1;          // the wave's last value fragment (-1: none)
+		constexpr bool PIPE = NBF <= 8;
+		constexpr int NM = NAF * NBF;                           // MFMAs per dword step
+		constexpr int NV = 4 * NAF, NW = 5 * NAF;               // b1 operations of a step, value operations of the next
+		constexpr int BLV = NBF - 2;                            // the last value fragment
 		// b1 planes of this dword: dealt over the MFMAs before the b1 fragment -- without PIPE before the last value
 		// fragment, whose slots carry the next dword's value planes (they overwrite w4)
-		constexpr int MB = HASB1 ? ((!PIPE && NBW >= 3) ? (NBW - 2) * NAF : (NBW - 1) * NAF) : 0;
-		static_assert(!HASB1 || NBW >= 2 || NCB == 1, "a column group of the b1 fragment alone has no slot for its unpack");
+		constexpr int MB = (!PIPE && NBF >= 3) ? (NBF - 2) * NAF : (NBF - 1) * NAF;
 
 		int sa = 0, sb = 0;        // ring slots of the current tile (rows, B)
 		int par = 0;               // parity of the tile in the workgroup's stream (every item is whole pairs)
 		while (pc.k < nk) {
-			__builtin_amdgcn_sched_barrier(0);
-			__builtin_amdgcn_s_barrier();
-			__builtin_amdgcn_sched_barrier(0);
-			// (LDS reads by inline asm with counted lgkmcnt waits: behind an LDS-DMA the compiler puts vmcnt(0) in
-			// front of every LDS read it can see)
-			const uint32_t a_addr = (RM == 1 ? (par ? ring_rm1 : ring_rm0) : ring_lds) + (uint32_t)(sa * SLOT_A);
-			constexpr int AFS = RM == 1 ? 2048 : 1024;            // bytes between a wave's row pieces
-			const uint32_t b_addr = bt_lds + (uint32_t)(sb * TILE_BYTES);
 			s3_v4i aw[NAF];
-			s3_static_for<0, NAF>([&](auto F) { constexpr int f = decltype(F)::value; S3_DS_READ(aw[f], a_addr, f * AFS); });
+			uint32_t b_addr;
+			enter_tile(sa, sb, par, bt_lds, aw, b_addr);
 			s3_v4i bf[NBUF][BCH];
 			auto read_chunk = [&](auto CI) {
 				constexpr int ci = decltype(CI)::value, u = ci / NCH, b0 = (ci % NCH) * BCH;
 				s3_static_for<0, BCH>([&](auto J) {
 					constexpr int j = decltype(J)::value;
-					if constexpr (b0 + j < NBW) {
-						if (ABL & 8) bf[ci % NBUF][j] = (s3_v4i){u, j, r, sa};
-						else S3_DS_READ(bf[ci % NBUF][j], b_addr, u * NCOL * 16 + (b0 + j) * 256);
-					}
+					if constexpr (b0 + j < NBF) s3_ds_read<u * NCOL * 16 + (b0 + j) * 256>(bf[ci % NBUF][j], b_addr);
 				});
 			};
-			constexpr int nread_last = NBW - (NCH - 1) * BCH;       // fragments of a dword step's last chunk
-			// fragment reads of chunks [c0, c1) of the tile
-			auto nreads = [](int c0, int c1) constexpr { int n = 0; for (int c = c0; c < c1 && c < 4 * NCH; c++) n += (c % NCH == NCH - 1) ? nread_last : BCH; return n; };
 			s3_static_for<0, NBUF - 1>([&](auto C) { if constexpr (decltype(C)::value < 4 * NCH) read_chunk(C); });
 			// the row pieces are back (the first B chunks may still be in flight): value planes of dword 0
-			if (!(ABL & 8)) { S3_LGKM_WAIT(nreads(0, NBUF - 1), aw[0]); } else { S3_LGKM_WAIT(0, aw[0]); }
-#pragma unroll
-			for (int f = 1; f < NAF; f++) S3_TIE(aw[f]);
+			s3_wait_regs<CH::nreads(0, NBUF - 1), NAF>(aw);
 			s3_v4i val[PIPE ? 2 : 1][NAF], b1[NAF];
 			uint32_t w4[PIPE ? 2 : 1][NAF];       // the dword shifted by 4: of the current dword (its b1 planes) and of the next (its value planes)
 			// (without PIPE only those of row piece 0: piece f + 1 follows behind the first MFMA of piece f)
-			if (!(ABL & 1)) {
-				s3_static_for<0, (PIPE ? NW : 5)>([&](auto O) {
-					constexpr int o = decltype(O)::value, f = o / 5, op = o % 5;
-					s3_unpack_op<op>((uint32_t)aw[f][0], w4[0][f], val[0][f], b1[f]);
-				});
-			}
+			s3_static_for<0, (PIPE ? NW : 5)>([&](auto O) {
+				constexpr int o = decltype(O)::value, f = o / 5, op = o % 5;
+				s3_unpack_op<op>((uint32_t)aw[f][0], w4[0][f], val[0][f], b1[f]);
+			});
 			__builtin_amdgcn_sched_barrier(0);
 			// Without PIPE the dword step's LAST chunk runs piece-major when it holds two fragments (both are in
 			// registers): the planes of piece f are free two MFMAs earlier, and their replacement is spread
 			// over two slots instead of five operations behind one MFMA.
-			constexpr bool FM = !PIPE && BCH == 2 && nread_last == 2;
+			constexpr bool FM = !PIPE && BCH == 2 && CH::last == 2;
 			constexpr int M0 = (NCH - 1) * BCH * NAF;              // first slot of the last chunk
 			s3_static_for<0, 4>([&](auto U) {
 				constexpr int u = decltype(U)::value;
@@ -470,68 +425,57 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 					constexpr bool fm = FM && m >= M0;
 					constexpr int b = fm ? (NCH - 1) * BCH + (m - M0) % 2 : m / NAF, f = fm ? (m - M0) / 2 : m % NAF;
 					constexpr int ch = b / BCH, ci = u * NCH + ch, j = b % BCH;
-					if constexpr (m == ch * BCH * NAF) {
-						// entering a chunk: start the one NBUF - 1 ahead, then wait for this one
-						if constexpr (ci + NBUF - 1 < 4 * NCH) read_chunk(std::integral_constant<int, ci + NBUF - 1>());
-						constexpr int inflight = (ABL & 8) ? 0 : nreads(ci + 1, ci + NBUF);
-						constexpr int nb = (ch == NCH - 1) ? nread_last : BCH;
-						S3_LGKM_WAIT(inflight, bf[ci % NBUF][0]);
-#pragma unroll
-						for (int jj = 1; jj < nb; jj++) S3_TIE(bf[ci % NBUF][jj]);
-					}
-					if (ABL & 1) { if (f == 0) acc[0][b][1] ^= bf[ci % NBUF][j][0] ^ aw[b % NAF][u]; }
-					else if (HASB1 && b == NBW - 1) acc[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(b1[f], bf[ci % NBUF][j], acc[f][b], 0, 0, 0);
+					if constexpr (m == ch * BCH * NAF) s3_enter_chunk<CH, ci>(bf, read_chunk);
+					if constexpr (b == NBF - 1) acc[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(b1[f], bf[ci % NBUF][j], acc[f][b], 0, 0, 0);
 					else acc[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(val[vb][f], bf[ci % NBUF][j], acc[f][b], 0, 0, 0);
-					if (!(ABL & 1)) {
-						// value planes of the tile's first dword, row piece f + 1
-						if constexpr (!PIPE && u == 0 && b == 0 && f + 1 < NAF) {
-							s3_static_for<0, 5>([&](auto O) {
-								constexpr int op = decltype(O)::value;
-								s3_unpack_op<op>((uint32_t)aw[f + 1][0], w4[0][f + 1], val[0][f + 1], b1[f + 1]);
-							});
-						}
-						if constexpr (m < MB) {
-							s3_static_for<m * NV / MB, (m + 1) * NV / MB>([&](auto O) {
-								constexpr int o = decltype(O)::value, ff = o / 4, op = 5 + o % 4;
-								s3_unpack_op<op>((uint32_t)aw[ff][u], w4[vb][ff], val[vb][ff], b1[ff]);
-							});
-						}
-						// value planes of the next dword
-						if constexpr (PIPE && u < 3) {
-							s3_static_for<m * NW / NM, (m + 1) * NW / NM>([&](auto O) {
-								constexpr int o = decltype(O)::value, ff = o / 5, op = o % 5;
-								s3_unpack_op<op>((uint32_t)aw[ff][u + 1], w4[vn][ff], val[vn][ff], b1[ff]);
-							});
-						}
-						if constexpr (!PIPE && u < 3) {
-							// behind the last MFMA that reads val[f] (that of fragment BLV); with the b1 fragment behind it
-							// in a piece-major chunk: two operations there, three behind the b1 MFMA
-							constexpr int lo = !fm ? ((b == BLV || (BLV < 0 && b == 0)) ? 0 : 5) : (HASB1 ? (j == 0 ? 0 : 2) : (j == 1 ? 0 : 5));
-							constexpr int hi = !fm ? 5 : (HASB1 && j == 0 ? 2 : 5);
-							s3_static_for<lo, hi>([&](auto O) {
-								constexpr int op = decltype(O)::value;
-								s3_unpack_op<op>((uint32_t)aw[f][u + 1], w4[0][f], val[0][f], b1[f]);
-							});
-						}
+					// value planes of the tile's first dword, row piece f + 1
+					if constexpr (!PIPE && u == 0 && b == 0 && f + 1 < NAF) {
+						s3_static_for<0, 5>([&](auto O) {
+							constexpr int op = decltype(O)::value;
+							s3_unpack_op<op>((uint32_t)aw[f + 1][0], w4[0][f + 1], val[0][f + 1], b1[f + 1]);
+						});
+					}
+					if constexpr (m < MB) {
+						s3_static_for<m * NV / MB, (m + 1) * NV / MB>([&](auto O) {
+							constexpr int o = decltype(O)::value, ff = o / 4, op = 5 + o % 4;
+							s3_unpack_op<op>((uint32_t)aw[ff][u], w4[vb][ff], val[vb][ff], b1[ff]);
+						});
+					}
+					// value planes of the next dword
+					if constexpr (PIPE && u < 3) {
+						s3_static_for<m * NW / NM, (m + 1) * NW / NM>([&](auto O) {
+							constexpr int o = decltype(O)::value, ff = o / 5, op = o % 5;
+							s3_unpack_op<op>((uint32_t)aw[ff][u + 1], w4[vn][ff], val[vn][ff], b1[ff]);
+						});
+					}
+					if constexpr (!PIPE && u < 3) {
+						// behind the last MFMA that reads val[f] (that of fragment BLV); with the b1 fragment behind it
+						// in a piece-major chunk: two operations there, three behind the b1 MFMA
+						constexpr int lo = !fm ? (b == BLV ? 0 : 5) : (j == 0 ? 0 : 2);
+						constexpr int hi = !fm ? 5 : (j == 0 ? 2 : 5);
+						s3_static_for<lo, hi>([&](auto O) {
+							constexpr int op = decltype(O)::value;
+							s3_unpack_op<op>((uint32_t)aw[f][u + 1], w4[0][f], val[0][f], b1[f]);
+						});
 					}
 					__builtin_amdgcn_sched_barrier(0);
 				});
 			});
 			if (pc.t + 1 == pc.t1) {
 				// the item is complete: its slab [wave][f][b][reg][lane] leaves by plain stores (256 B per instruction)
-				int *dst = out + ((size_t)pc.id * NC + wid) * (NAF * NBWMAX * 256) + lane;
+				int *dst = out + ((size_t)pc.id * NC + wid) * (NAF * NBF * 256) + lane;
 #pragma unroll
 				for (int f = 0; f < NAF; f++)
 #pragma unroll
-					for (int b = 0; b < NBW; b++)
+					for (int b = 0; b < NBF; b++)
 #pragma unroll
 						for (int reg = 0; reg < 4; reg++) {
-							dst[((f * NBWMAX + b) * 4 + reg) * 64] = acc[f][b][reg];
+							dst[((f * NBF + b) * 4 + reg) * 64] = acc[f][b][reg];
 							acc[f][b][reg] = 0;
 						}
 			}
 			pos_next(pc);
-			if (RM != 1 || par) sa = sa + 1 == RA ? 0 : sa + 1;         // (a pair's slot serves two tiles)
+			if (par) sa = sa + 1 == RA ? 0 : sa + 1;                   // (a pair's slot serves two tiles)
 			sb = sb + 1 == RB ? 0 : sb + 1;
 			par ^= 1;
 		}
@@ -544,8 +488,6 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 	// a dword step in the order of s3_one (bit-1 planes first, the last chunk piece-major), so that every plane of a
 	// row piece is free early and its next dword's operations are dealt out evenly behind the MFMAs (s3_one::slot).
 	auto consume3 = [&]() {
-		static_assert(!MISS || NCB == 1, "the three-plane form has one column group");
-		constexpr int NBUF = NBUF_;                           // chunk buffers: the B reads run NBUF - 1 chunks ahead of their MFMAs
 		constexpr int NBV = NBF - 1;                          // value fragments
 		constexpr int NVF = 2 * NBV + 1;                      // (fragment, plane) pairs of a dword step
 		constexpr int NM = NAF * NVF;                         // MFMAs per dword step
@@ -553,7 +495,9 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 		constexpr bool ONE = NBF == 4 && NAF >= 3;
 		using S1 = s3_one<NAF>;
 		static_assert(!ONE || S1::ok(), "an unpack operation of the one-set schedule lands behind the MFMA that needs it");
-		constexpr int BCH = ONE ? 2 : NBF <= 4 ? NBF : 2, NCH = (NBF + BCH - 1) / BCH;
+		constexpr int BCH = ONE ? 2 : NBF <= 4 ? NBF : 2;
+		using CH = s3_chunks<NBF, BCH>;
+		constexpr int NCH = CH::NCH;
 		constexpr int NPS = ONE ? 1 : 2;                      // sets of plane registers
 		const uint32_t bt_lds = smem_lds + (4 * kg * NCOL + r) * 16;
 		s3_v4i acc[NAF][NBF], accm[NAF][NBV > 0 ? NBV : 1];
@@ -564,31 +508,23 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 #pragma unroll
 			for (int b = 0; b < NBV; b++) accm[f][b] = (s3_v4i){0, 0, 0, 0};
 		}
-		int sa = 0, sb = 0, par = 0;
+		int sa = 0, sb = 0;        // ring slots of the current tile (rows, B)
+		int par = 0;               // parity of the tile in the workgroup's stream (every item is whole pairs)
 		while (pc.k < nk) {
-			__builtin_amdgcn_sched_barrier(0);
-			__builtin_amdgcn_s_barrier();
-			__builtin_amdgcn_sched_barrier(0);
-			const uint32_t a_addr = (RM == 1 ? (par ? ring_rm1 : ring_rm0) : ring_lds) + (uint32_t)(sa * SLOT_A);
-			constexpr int AFS = RM == 1 ? 2048 : 1024;
-			const uint32_t b_addr = bt_lds + (uint32_t)(sb * TILE_BYTES);
 			s3_v4i aw[NAF];
-			s3_static_for<0, NAF>([&](auto F) { constexpr int f = decltype(F)::value; S3_DS_READ(aw[f], a_addr, f * AFS); });
+			uint32_t b_addr;
+			enter_tile(sa, sb, par, bt_lds, aw, b_addr);
 			s3_v4i bf[NBUF][BCH];
 			auto read_chunk = [&](auto CI) {
 				constexpr int ci = decltype(CI)::value, u = ci / NCH, b0 = (ci % NCH) * BCH;
 				s3_static_for<0, BCH>([&](auto J) {
 					constexpr int j = decltype(J)::value;
 					constexpr int b = ONE ? S1::frag(ci % NCH, j) : b0 + j;
-					if constexpr (b0 + j < NBF) S3_DS_READ(bf[ci % NBUF][j], b_addr, u * NCOL * 16 + b * 256);
+					if constexpr (b0 + j < NBF) s3_ds_read<u * NCOL * 16 + b * 256>(bf[ci % NBUF][j], b_addr);
 				});
 			};
-			constexpr int nread_last = NBF - (NCH - 1) * BCH;
-			auto nreads = [](int c0, int c1) constexpr { int n = 0; for (int c = c0; c < c1 && c < 4 * NCH; c++) n += (c % NCH == NCH - 1) ? nread_last : BCH; return n; };
 			s3_static_for<0, NBUF - 1>([&](auto C) { if constexpr (decltype(C)::value < 4 * NCH) read_chunk(C); });
-			S3_LGKM_WAIT(nreads(0, NBUF - 1), aw[0]);
-#pragma unroll
-			for (int f = 1; f < NAF; f++) S3_TIE(aw[f]);
+			s3_wait_regs<CH::nreads(0, NBUF - 1), NAF>(aw);
 			s3_v4i val[NPS][NAF], b1[NPS][NAF], mis[NPS][NAF];
 			uint32_t w4[NAF], tt[NAF], m4[NAF];
 			s3_static_for<0, NOPT>([&](auto O) {
@@ -604,15 +540,7 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 					constexpr int b = ONE ? S1::frag_of(m) : vf < 2 * NBV ? vf / 2 : NBV;             // B fragment
 					constexpr int plane = ONE ? S1::plane_of(m) : vf < 2 * NBV ? (vf & 1) : 2;        // 0 value, 1 missing, 2 bit-1
 					constexpr int ch = ONE ? S1::chunk_of(m) : b / BCH, ci = u * NCH + ch, j = ONE ? S1::slot_of(m) : b % BCH;
-					if constexpr (ONE ? S1::enters(m) : f == 0 && plane != 1 && b % BCH == 0) {
-						// entering a chunk: start the next one, then wait for this one
-						if constexpr (ci + NBUF - 1 < 4 * NCH) read_chunk(std::integral_constant<int, ci + NBUF - 1>());
-						constexpr int inflight = nreads(ci + 1, ci + NBUF);
-						constexpr int nb = (ch == NCH - 1) ? nread_last : BCH;
-						S3_LGKM_WAIT(inflight, bf[ci % NBUF][0]);
-#pragma unroll
-						for (int jj = 1; jj < nb; jj++) S3_TIE(bf[ci % NBUF][jj]);
-					}
+					if constexpr (ONE ? S1::enters(m) : f == 0 && plane != 1 && b % BCH == 0) s3_enter_chunk<CH, ci>(bf, read_chunk);
 					if constexpr (plane == 0) acc[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(val[vb][f], bf[ci % NBUF][j], acc[f][b], 0, 0, 0);
 					else if constexpr (plane == 1) accm[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(mis[vb][f], bf[ci % NBUF][j], accm[f][b], 0, 0, 0);
 					else acc[f][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(b1[vb][f], bf[ci % NBUF][j], acc[f][b], 0, 0, 0);
@@ -648,22 +576,16 @@ score3_kernel(const uint8_t *__restrict__ A, const uint8_t *__restrict__ Fl, S3P
 				}
 			}
 			pos_next(pc);
-			if (RM != 1 || par) sa = sa + 1 == RA ? 0 : sa + 1;
+			if (par) sa = sa + 1 == RA ? 0 : sa + 1;                   // (a pair's slot serves two tiles)
 			sb = sb + 1 == RB ? 0 : sb + 1;
 			par ^= 1;
 		}
 	};
-	if constexpr (MISS) consume3();
-	else if constexpr (NCB == 1) consume(std::integral_constant<int, 0>());
-	else s3_static_for<0, NCB>([&](auto CG) { if (cgr == decltype(CG)::value) consume(CG); });
-	if ((ABL & 16) && tid == 0) {
-		stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st0;
-		stamps[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - sr0;
-	}
+	if constexpr (MISS) consume3(); else consume();
 #endif
 }
 
-// Per NBF the product's instantiation of score3_kernel on row-major rows (RM = 1): fragments per consumer wave,
+// Per NBF the product's instantiation of score3_kernel: fragments per consumer wave,
 // consumer / row-loader / B-loader waves, pairs of row tiles ahead, B tiles ahead -- what fits 160 KiB of LDS
 // ((DB + 1) x 4 NBF + (DA + 1) x 2 NC NAF KiB) and the registers of that many waves, the fastest of the forms
 // measured with tools/score3_bench (tools/README.md).
@@ -794,10 +716,10 @@ s3_t3_kernel(int M, int P, const long long *__restrict__ Q, S3Lists L, long long
 
 // ---- the item slabs of score3_kernel -> one row of limb sums per variant (the layout the epilogue reads:
 // accbuf[v * stride + 16 b + r]).  grid = (elements of a variant tile's slab / 256, variant tiles).
-// A slab is [consumer wave = (variant group, column group)][f][b < NBW][reg][lane]: NCW waves, NCB column groups
-// of NBW = ceil(NBF / NCB) fragment slots each (the last group's spare slots are never written).
+// A slab is [consumer wave][f][b][reg][lane]: NC waves of NAF fragments, NBF fragment slots each (2 NBF - 1 of the
+// kernel's in the three-plane form).
 __global__ void __launch_bounds__(256)
-s3_reduce_kernel(S3Plan pl, int M, int NCW, int NAF, int NBF, int NCB, const int *__restrict__ slabs, int *__restrict__ accbuf, int stride,
+s3_reduce_kernel(S3Plan pl, int M, int NC, int NAF, int NBF, const int *__restrict__ slabs, int *__restrict__ accbuf, int stride,
 	int *__restrict__ counters, int *__restrict__ cursors)
 {
 	// the step's counters and queue cursors start at zero: nothing before the epilogue touches them, and two
@@ -806,17 +728,13 @@ s3_reduce_kernel(S3Plan pl, int M, int NCW, int NAF, int NBF, int NCB, const int
 		if (threadIdx.x < 24) counters[threadIdx.x] = 0;
 		if (threadIdx.x < 8 && cursors) cursors[threadIdx.x] = 0;
 	}
-	const int NBW = (NBF + NCB - 1) / NCB;
 	// a thread takes four consecutive slab elements: the same (fragment, register, variant), four columns -- one
 	// 16-byte load per item and one 16-byte store (a quarter of the load instructions of the one-element form)
-	const int e = (blockIdx.x * 256 + threadIdx.x) * 4, per = NCW * NAF * NBW * 256, vtile = blockIdx.y;
+	const int e = (blockIdx.x * 256 + threadIdx.x) * 4, per = NC * NAF * NBF * 256, vtile = blockIdx.y;
 	if (e >= per) return;
-	const int lane = e & 63, reg = (e >> 6) & 3, fb = e >> 8;           // fb = (wave NAF + f) NBW + b
-	const int bw = fb % NBW, wf = fb / NBW;                             // wf = wave NAF + f
-	const int wave = wf / NAF, f = wf - wave * NAF;
-	const int b = (wave % NCB) * NBW + bw;                              // fragment of the tile
-	if (b >= NBF) return;
-	const int v = (vtile * pl.fpw + (wave / NCB) * NAF + f) * 16 + (lane >> 4) * 4 + reg;
+	const int lane = e & 63, reg = (e >> 6) & 3, fb = e >> 8;           // fb = (wave NAF + f) NBF + b
+	const int b = fb % NBF, wf = fb / NBF;                              // wf = wave NAF + f: the fragment of the variant tile
+	const int v = (vtile * pl.fpw + wf) * 16 + (lane >> 4) * 4 + reg;
 	if (v >= M) return;
 	s3_v4i sum = (s3_v4i){0, 0, 0, 0};
 	for (int g = 0; g < pl.ng; g++) {
@@ -847,7 +765,7 @@ score3_epilogue(int M, DevModel md, MfEpi ep, const int *__restrict__ accbuf, in
 	const long long *__restrict__ t3part /* [nr][M][P][2] per-range sums over the missing samples */, int nr,
 	const int *__restrict__ lcnt /* [nr][ld] listed missing genotypes per range, -1: not listed */, size_t ld, int *__restrict__ ovf_list,
 	SpaRec *__restrict__ recs, int *__restrict__ counters, int btop, int *__restrict__ fb_series, int *__restrict__ fb_exact,
-	double *__restrict__ out8, uint8_t *__restrict__ valid, double guard_tol, int dbg = 0)
+	double *__restrict__ out8, uint8_t *__restrict__ valid, double guard_tol)
 {
 	constexpr int P = 2 * K + 2, CW = P - 1;     // score columns c' (K), e (K), s, w; column CW carries G^2
 	constexpr int S3E_VB = s3e_vb(K);
@@ -858,14 +776,6 @@ score3_epilogue(int M, DevModel md, MfEpi ep, const int *__restrict__ accbuf, in
 	__shared__ int s_col[P][3];                   // first limb column, limbs, scale exponent
 	const int tid = threadIdx.x, j0 = blockIdx.x * S3E_VB;
 	const int N = md.N;
-	if (dbg & 1) {
-		if (tid == 0)
-#pragma unroll
-			for (int c = 0; c < P; c++) {
-				s_col[c][0] = ep.ccol[c]; s_col[c][1] = ep.climb[c]; s_col[c][2] = ep.escale[c];
-				s_ftot[c][0] = ep.ftot_hi[c]; s_ftot[c][1] = ep.ftot_lo[c];
-			}
-	} else
 	for (int c = tid; c < P; c += S3E_VB) {
 		s_col[c][0] = ep.ccol[c]; s_col[c][1] = ep.climb[c]; s_col[c][2] = ep.escale[c];
 		s_ftot[c][0] = ep.ftot_hi[c]; s_ftot[c][1] = ep.ftot_lo[c];
@@ -894,7 +804,6 @@ score3_epilogue(int M, DevModel md, MfEpi ep, const int *__restrict__ accbuf, in
 		}
 		int state = 0, n1 = 0, n2 = 0;
 		double imp = 0;
-		if (dbg & 8) over = false;
 		if (j < M) {
 			if (over) ovf_list[atomicAdd(&counters[23], 1)] = j;
 			else {
@@ -928,7 +837,7 @@ score3_epilogue(int M, DevModel md, MfEpi ep, const int *__restrict__ accbuf, in
 		if (miss_off) {
 #pragma unroll
 			for (int l = 0; l < MF_NLIMB; l++) lm[l] = a0[miss_off + cc + min(l, nl - 1)];
-		} else if (!(dbg & 2)) {
+		} else {
 			const long long *p = t3part + ((size_t)j * P + c) * 2;
 			const size_t gs = (size_t)M * P * 2;
 			for (int g0 = 0; g0 < nr; g0 += 8) {
@@ -978,7 +887,6 @@ score3_epilogue(int M, DevModel md, MfEpi ep, const int *__restrict__ accbuf, in
 	}
 	__syncthreads();
 	// ---- 2. per variant
-	if (dbg & 4) return;
 	const int j = j0 + tid;
 	if (j >= M || !s_n[tid][3]) return;
 	const int n1 = s_n[tid][0], n2 = s_n[tid][1], n3 = s_n[tid][2];

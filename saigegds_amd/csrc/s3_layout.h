@@ -1,4 +1,4 @@
-// s3_layout.h -- the tiled device layout of genotype blocks and the work decomposition of score3_kernel
+// s3_layout.h -- the work decomposition of score3_kernel and the orders of samples and pieces it shares with its callers
 // (host and device; no HIP specifics).  Part of libsaigehip.so.
 #pragma once
 #include <stddef.h>
@@ -30,7 +30,7 @@ struct S3Plan {
 	int rem;        // leftover variant tiles = vt % wpg
 	int f;          // pieces per leftover variant tile (0 if rem == 0)
 	int ipg;        // items per group = rf * wpg + rem * f
-	// row-major input (score3_kernel<.., RM = true>): the rows as the caller holds them, no tiles
+	// the rows: row-major 2-bit rows as the caller holds them
 	int nrow;       // rows (variants) that exist: the loaders never touch a row >= nrow
 	unsigned long long bpv;   // bytes per row (a multiple of 16, >= 64 ntile)
 };
@@ -66,18 +66,13 @@ __host__ __device__ __forceinline__ void s3_items_of(const S3Plan &p, int vtile,
 	else { first = g * p.ipg + p.rf * p.wpg + (vtile - p.rf * p.wpg) * p.f; count = p.f; }
 }
 
-// bytes of one tiled block of M variants: nfrag fragments x ntile KiB
-static inline size_t s3_block_bytes(size_t M, int ntile) { return ((M + 15) / 16) * (size_t)ntile * 1024; }
-
 // byte offset of the 16-B piece p (64 samples) of variant j in the tiled layout: inside the KiB of (fragment,
 // tile) the 64 bytes of a variant are contiguous, so whoever reads ONE row (the SPA kernels) touches whole
-// 64-byte sectors; the contraction kernel's loader permutes the lanes of its DMA instead (s3_dma_lane)
+// 64-byte sectors
 __host__ __device__ __forceinline__ size_t s3_piece_off(size_t j, size_t p, int ntile)
 {
 	return ((j >> 4) * (size_t)ntile + (p >> 2)) * 1024 + (((j & 15) << 2) + (p & 3)) * 16;
 }
-// 16-byte slot of the KiB that the consumer lane (r = lane & 15: variant, kg = lane >> 4: 64-sample piece) wants
-__host__ __device__ __forceinline__ int s3_dma_lane(int lane) { return ((lane & 15) << 2) | (lane >> 4); }
 
 // Sample order inside a group of 16 (as mf_fixed.h mf_pos): byte j of (w >> 2t) & 0x03030303 is
 // the code of sample 4 j + t, and the B tiles store the 16 samples of a group in that order.

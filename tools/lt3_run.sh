@@ -1,11 +1,12 @@
 #!/bin/bash
 # list + T3 pass of the tool: checks, timing, vector-instruction counts of the large launches
 mkdir -p gpurun_out/lt3
-RM=1 LT3=1 timeout -k 10 300 ./tools/score3_bench_small 430000 50000 5 > gpurun_out/lt3/b.txt 2>&1
+O=$PWD/$_        # the output directory just made, as an absolute path
+LT3=1 timeout -k 10 300 ./tools/score3_bench 430000 50000 5 > $O/b.txt 2>&1
 echo "ok lines: $(grep -c ': ok' gpurun_out/lt3/b.txt)"; grep -i "fail\|differ" gpurun_out/lt3/b.txt | head
 tail -4 gpurun_out/lt3/b.txt
 R=$(pwd); cd /tmp; export TMPDIR=/tmp
-RM=1 LT3=1 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES --output-format csv -d $R/gpurun_out/lt3/pmc -- $R/tools/score3_bench_small 430000 50000 1 > $R/gpurun_out/lt3/pmc.txt 2>&1
+LT3=1 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES --output-format csv -d $O/pmc -- $R/tools/score3_bench 430000 50000 1 > $O/pmc.txt 2>&1
 cd $R
 python3 - <<PY
 import csv,glob,collections

@@ -1,9 +1,14 @@
-// tools/score3_bench.hip -- validation and timing of score3_kernel (saigegds_amd/csrc/kern_score3.h) alone.
+// tools/score3_bench.hip -- validation and timing of score3_kernel (saigegds_amd/csrc/kern_score3.h) alone, and of the
+// list builder and the fused list + T3 pass (kern_lists.h).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -o tools/score3_bench tools/score3_bench.hip
-//   ./tools/score3_bench check            small shapes against a CPU sum (every instantiation below)
+//   ./tools/score3_bench check            small shapes against a CPU sum, element by element
 //   ./tools/score3_bench [N=430000] [M=50000] [reps=5]
-// Inputs are random tiled blocks (codes 0/1/2, 1e-3 missing) and random limb tiles: the kernel's time does
-// not depend on the values.
+//                                         the list builder (checked, then timed), then every entry of the two shape tables
+//     LT3=1       the fused list + T3 pass instead of the contraction kernel (checked, then timed); BESIDE=1|2|3: beside
+//                 a stand-in for the other lane's cumulant pass
+//     MISS16=n    n / 65 536 of the codes missing (default 66);  ZERO_A / ZERO_B: zero rows / limb tiles
+// Inputs are random row-major 2-bit rows and random limb tiles: the kernel's time does not depend on the values (but the
+// chip clocks higher on zero operands).  A shape outside the tables: add a run<...> line in main().
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -35,30 +40,27 @@ __global__ void fill_codes(uint32_t *dst, size_t ndw, uint64_t seed, uint32_t mi
 	}
 }
 
-struct Shape { int N; size_t M; };
-
-template <int NBF, int NAF, int WAVES, int NLA, int NLB, int DA, int DB, int ABL, int NCB = 1, int NBUF = 2, int RM = 0, bool MISS = false>
-static float run(const char *name, const uint8_t *A, const uint8_t *Fl, int ntile, size_t M, int wg_per_cu, int n_cu, int *out, size_t out_ints,
-	int reps, S3Plan *plan_out = nullptr, size_t bpv = 0)
+// rows: M row-major rows of bpv bytes.  Returns the best of `reps` launches (reps = 0: one launch, no line printed).
+template <int NBF, int NAF, int WAVES, int NLA, int NLB, int DA, int DB, bool MISS = false>
+static float run(const char *name, const uint8_t *rows, const uint8_t *Fl, int ntile, size_t M, int wg_per_cu, int n_cu, int *out, size_t out_ints,
+	int reps, size_t bpv, S3Plan *plan_out = nullptr)
 {
 	const int grid = n_cu * wg_per_cu;
-	constexpr int NCV = WAVES / NCB, NBW = MISS ? 2 * NBF - 1 : (NBF + NCB - 1) / NCB;
-	const S3Plan pl = s3_plan(M, ntile, grid, NAF * NCV, bpv);
+	constexpr int NBW = MISS ? 2 * NBF - 1 : NBF;            // fragment slots of a slab
+	const S3Plan pl = s3_plan(M, ntile, grid, NAF * WAVES, bpv);
 	const size_t need = (size_t)pl.ng * pl.ipg * WAVES * NAF * NBW * 256;
 	if (need > out_ints) { fprintf(stderr, "%s: out buffer too small (%zu > %zu)\n", name, need, out_ints); exit(1); }
 	if (plan_out) *plan_out = pl;
-	const size_t lds = ((size_t)(DB + 1) * 4 * NBF + (size_t)(DA + 1) * NCV * NAF * (RM == 1 ? 2 : 1)) * 1024;
+	const size_t lds = s3_lds_bytes(NBF, NAF, WAVES, DA, DB);
 	if (lds > 163840) { printf("%-40s skipped: %zu B of LDS\n", name, lds); return 0; }
-	auto kern = score3_kernel<NBF, NAF, WAVES, NLA, NLB, DA, DB, ABL, NCB, NBUF, RM, MISS>;
-	static unsigned long long *stamps = nullptr;
-	if (!stamps) CK(hipMalloc((void **)&stamps, 16 * 4096));
+	auto kern = score3_kernel<NBF, NAF, WAVES, NLA, NLB, DA, DB, MISS>;
 	CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 	hipEvent_t a, b;
 	CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
 	float best = 1e30f;
 	for (int rr = 0; rr < reps + 1; rr++) {
 		CK(hipEventRecord(a, 0));
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * (WAVES + NLA + NLB)), lds, 0, A, Fl, pl, out, stamps);
+		hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * (WAVES + NLA + NLB)), lds, 0, rows, Fl, pl, out);
 		CK(hipEventRecord(b, 0));
 		CK(hipEventSynchronize(b));
 		CK(hipGetLastError());
@@ -69,33 +71,23 @@ static float run(const char *name, const uint8_t *A, const uint8_t *Fl, int ntil
 	CK(hipEventDestroy(a)); CK(hipEventDestroy(b));
 	if (reps > 0) {
 		const double bytes = (double)M * (ntile * 64.0);
-		double ghz = 0;
-		if (ABL & 16) {
-			std::vector<unsigned long long> hs(2 * grid);
-			CK(hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost));
-			std::vector<double> c;
-			for (int b2 = 0; b2 < grid; b2++) if (hs[2 * b2 + 1]) c.push_back((double)hs[2 * b2] / (double)hs[2 * b2 + 1] * 0.1);
-			std::sort(c.begin(), c.end());
-			if (!c.empty()) ghz = c[c.size() / 2];
-		}
-		printf("%-40s %s NBF=%2d NAF=%d NC=%d/%d NL=%d+%d D=%d/%d buf %d ABL=%2d  items/grp=%4d f=%2d  %7.3f ms  %6.0f GB/s  %.3f of 8 TB/s",
-			name, MISS ? "rows3" : RM == 2 ? "lines" : RM ? "rows " : "tiles", NBF, NAF, WAVES, NCB, NLA, NLB, DA, DB, NBUF, ABL, pl.ipg, pl.f, best, bytes / best / 1e6, bytes / best / 1e6 / 8000.0);
-		if (ABL & 16) printf("  clock %.3f GHz", ghz);
-		printf("\n");
+		printf("%-40s %s NBF=%2d NAF=%d NC=%d NL=%d+%d D=%d/%d  items/grp=%4d f=%2d  %7.3f ms  %6.0f GB/s  %.3f of 8 TB/s\n",
+			name, MISS ? "rows3" : "rows ", NBF, NAF, WAVES, NLA, NLB, DA, DB, pl.ipg, pl.f, best, bytes / best / 1e6, bytes / best / 1e6 / 8000.0);
 		fflush(stdout);
 	}
 	return best;
 }
 
-// CPU check: sums of the item slabs per (variant, column) against the direct sum
-template <int NBF, int NAF, int WAVES, int NLA, int NLB, int DA, int DB, int NCB = 1, int NBUF = 2, int RM = 0, bool MISS = false>
+// CPU check: sums of the item slabs per (variant, column) against the direct sum.  Exactly M rows of
+// ntile x 64 + row_pad bytes (no padding rows: a read past the last row would fault or show).
+template <int NBF, int NAF, int WAVES, int NLA, int NLB, int DA, int DB, bool MISS = false>
 static int check(const char *name, int N, size_t M, int wg_per_cu, int n_cu, size_t row_pad = 0, uint32_t miss16 = 300)
 {
 	const int ntile = 2 * ((N + 511) / 512);
-	const size_t nfrag = (M + 15) / 16, abytes = nfrag * (size_t)ntile * 1024;
+	const size_t nfrag = (M + 15) / 16;
 	const int NCOL = 16 * NBF;
 	const size_t flbytes = (size_t)ntile * 16 * NCOL * 16;
-	std::vector<uint8_t> hA(abytes), hF(flbytes);
+	std::vector<uint8_t> hF(flbytes);
 	uint64_t x = 77 + N + M;
 	for (auto &v : hF) v = (uint8_t)sm64(x);
 	// codes: variant v, sample s
@@ -113,80 +105,55 @@ static int check(const char *name, int N, size_t M, int wg_per_cu, int n_cu, siz
 				if (s >= (size_t)N)
 					for (int c = 0; c < NCOL; c++) hF[((size_t)(t * 16 + g16) * NCOL + c) * 16 + s3_pos(e)] = 0;
 			}
-	for (size_t v = 0; v < nfrag * 16; v++)
+	const size_t bpv = (size_t)ntile * 64 + row_pad;
+	std::vector<uint8_t> hA(M * bpv, 0xFF);           // (the bytes between the rows hold missing codes: never read)
+	for (size_t v = 0; v < M; v++)
 		for (size_t p = 0; p < (size_t)ntile * 4; p++) {
 			uint32_t w[4] = {0, 0, 0, 0};
 			for (int u = 0; u < 4; u++)
 				for (int e = 0; e < 16; e++) w[u] |= (uint32_t)code[v * ntile * 256 + p * 64 + u * 16 + e] << (2 * e);
-			memcpy(&hA[s3_piece_off(v, p, ntile)], w, 16);
+			memcpy(&hA[v * bpv + p * 16], w, 16);
 		}
 	uint8_t *dA, *dF; int *dO;
-	// row-major form: exactly M rows (no padding rows: a read past the last row would fault or show)
-	const size_t bpv = (size_t)ntile * 64 + row_pad;
-	if (RM) {
-		hA.assign(M * bpv, 0xFF);                      // (the bytes between the rows hold missing codes: never read)
-		for (size_t v = 0; v < M; v++)
-			for (size_t p = 0; p < (size_t)ntile * 4; p++) {
-				uint32_t w[4] = {0, 0, 0, 0};
-				for (int u = 0; u < 4; u++)
-					for (int e = 0; e < 16; e++) w[u] |= (uint32_t)code[v * ntile * 256 + p * 64 + u * 16 + e] << (2 * e);
-				memcpy(&hA[v * bpv + p * 16], w, 16);
-			}
-	}
-	const size_t abytes_dev = RM ? M * bpv : abytes;
-	CK(hipMalloc((void **)&dA, abytes_dev)); CK(hipMalloc((void **)&dF, flbytes));
-	CK(hipMemcpy(dA, hA.data(), abytes_dev, hipMemcpyHostToDevice));
+	CK(hipMalloc((void **)&dA, M * bpv)); CK(hipMalloc((void **)&dF, flbytes));
+	CK(hipMemcpy(dA, hA.data(), M * bpv, hipMemcpyHostToDevice));
 	CK(hipMemcpy(dF, hF.data(), flbytes, hipMemcpyHostToDevice));
 	const int grid = n_cu * wg_per_cu;
-	constexpr int NCV = WAVES / NCB, NBW = MISS ? 2 * NBF - 1 : (NBF + NCB - 1) / NCB;
-	const S3Plan pl0 = s3_plan(M, ntile, grid, NAF * NCV);
+	constexpr int NBW = MISS ? 2 * NBF - 1 : NBF;
+	const S3Plan pl0 = s3_plan(M, ntile, grid, NAF * WAVES);
 	const size_t oints = (size_t)pl0.ng * pl0.ipg * WAVES * NAF * NBW * 256;
 	CK(hipMalloc((void **)&dO, oints * 4));
 	CK(hipMemset(dO, 0xCD, oints * 4));
 	S3Plan pl;
-	run<NBF, NAF, WAVES, NLA, NLB, DA, DB, 0, NCB, NBUF, RM, MISS>(name, dA, dF, ntile, M, wg_per_cu, n_cu, dO, oints, 0, &pl, bpv);
+	run<NBF, NAF, WAVES, NLA, NLB, DA, DB, MISS>(name, dA, dF, ntile, M, wg_per_cu, n_cu, dO, oints, 0, bpv, &pl);
 	std::vector<int> hO(oints);
 	CK(hipMemcpy(hO.data(), dO, oints * 4, hipMemcpyDeviceToHost));
 	long long bad = 0;
 	for (size_t v = 0; v < M; v++) {
 		const int vtile = (int)(v / (16 * (size_t)pl.fpw)), within = (int)(v % (16 * (size_t)pl.fpw));
 		const int vg = within / (16 * NAF), f = (within / 16) % NAF, row = within % 16, kg = row / 4, reg = row % 4;
-		for (int c = 0; c < NCOL; c++) {
+		// slot < NBF: value and bit-1 columns; the missing plane against the value columns in slots NBF .. 2 NBF - 2
+		for (int c = 0; c < (MISS ? 2 * NCOL - 16 : NCOL); c++) {
+			const bool mp = c >= NCOL;
+			const int cf = mp ? c - NCOL : c;                         // column of the limb tiles
 			long long ref = 0;
 			for (size_t s = 0; s < (size_t)ntile * 256; s++) {
 				const int cd = code[v * ntile * 256 + s];
 				const int t = (int)(s / 256), g16 = (int)(s % 256) / 16, e = (int)(s % 16);
-				const int a = ((c >= NCOL - 16) ? (cd & 2) : cd) * s3_scale(e);
-				ref += (long long)a * (int8_t)hF[((size_t)(t * 16 + g16) * NCOL + c) * 16 + s3_pos(e)];
+				const int a = (mp ? (cd == 3) : (cf >= NCOL - 16) ? (cd & 2) : cd) * s3_scale(e);
+				ref += (long long)a * (int8_t)hF[((size_t)(t * 16 + g16) * NCOL + cf) * 16 + s3_pos(e)];
 			}
 			long long got = 0;
 			for (int g = 0; g < pl.ng; g++) {
 				int first, count;
 				s3_items_of(pl, vtile, g, first, count);
 				for (int id = first; id < first + count; id++)
-					got += hO[(((size_t)id * WAVES + (vg * NCB + (c / 16) / NBW)) * NAF + f) * NBW * 256 + (size_t)((c / 16) % NBW) * 256 + reg * 64 + kg * 16 + (c % 16)];
+					got += hO[((((size_t)id * WAVES + vg) * NAF + f) * NBW + (size_t)(c / 16)) * 256 + reg * 64 + kg * 16 + (c % 16)];
 			}
-			if (got != ref) { if (bad < 5) fprintf(stderr, "%s: variant %zu col %d: got %lld want %lld\n", name, v, c, got, ref); bad++; }
-		}
-		// the missing plane against the value columns (slots NBF .. 2 NBF - 2 of the slab)
-		for (int c = 0; MISS && c < NCOL - 16; c++) {
-			long long ref = 0;
-			for (size_t s = 0; s < (size_t)ntile * 256; s++) {
-				const int cd = code[v * ntile * 256 + s];
-				const int t = (int)(s / 256), g16 = (int)(s % 256) / 16, e = (int)(s % 16);
-				ref += (long long)((cd == 3) * s3_scale(e)) * (int8_t)hF[((size_t)(t * 16 + g16) * NCOL + c) * 16 + s3_pos(e)];
-			}
-			long long got = 0;
-			for (int g = 0; g < pl.ng; g++) {
-				int first, count;
-				s3_items_of(pl, vtile, g, first, count);
-				for (int id = first; id < first + count; id++)
-					got += hO[(((size_t)id * WAVES + vg) * NAF + f) * NBW * 256 + (size_t)(NBF + c / 16) * 256 + reg * 64 + kg * 16 + (c % 16)];
-			}
-			if (got != ref) { if (bad < 5) fprintf(stderr, "%s: variant %zu missing-plane col %d: got %lld want %lld\n", name, v, c, got, ref); bad++; }
+			if (got != ref) { if (bad < 5) fprintf(stderr, "%s: variant %zu %scol %d: got %lld want %lld\n", name, v, mp ? "missing-plane " : "", cf, got, ref); bad++; }
 		}
 	}
-	printf("check %s %-30s N=%d M=%zu ntile=%d ng=%d wpg=%d rf=%d rem=%d f=%d: %s\n", MISS ? "rows3" : RM ? "rows " : "tiles", name, N, M, ntile, pl.ng, pl.wpg, pl.rf, pl.rem, pl.f, bad ? "FAILED" : "ok");
+	printf("check %s %-30s N=%d M=%zu ntile=%d ng=%d wpg=%d rf=%d rem=%d f=%d: %s\n", MISS ? "rows3" : "rows ", name, N, M, ntile, pl.ng, pl.wpg, pl.rf, pl.rem, pl.f, bad ? "FAILED" : "ok");
 	CK(hipFree(dA)); CK(hipFree(dF)); CK(hipFree(dO));
 	return bad ? 1 : 0;
 }
@@ -358,368 +325,125 @@ int main(int argc, char **argv)
 	const int n_cu = pr.multiProcessorCount;
 	if (argc > 1 && !strcmp(argv[1], "check")) {
 		int bad = 0;
-#ifndef S3_BENCH_SMALL
-		// grids far smaller than the chip so that rounds, leftovers and pieces all occur
-		bad += check<4, 4, 8, 3, 1, 2, 2>("k3 naf4 d2", 5000, 700, 1, 8);
-		bad += check<4, 4, 8, 3, 1, 3, 1>("k3 naf4 big grid", 3000, 300, 1, n_cu);
-		bad += check<4, 3, 8, 3, 1, 4, 1>("k3 naf3 d4/1", 4100, 1000, 1, 16);
-		bad += check<4, 6, 4, 3, 1, 4, 1>("k3 naf6 4+3+1", 4100, 1000, 1, 16);
-		bad += check<4, 4, 4, 1, 1, 1, 1>("k3 naf4 d1", 1000, 130, 1, 8);
-		bad += check<4, 4, 8, 2, 2, 2, 2>("k3 naf4 tiny N", 100, 50, 1, 8);
-		bad += check<4, 2, 12, 3, 1, 3, 2>("k3 naf2 12 waves", 9000, 2100, 1, 8);
-		bad += check<11, 4, 4, 3, 1, 3, 1>("k13 naf4 4+3+1", 2500, 800, 1, 8);
-		bad += check<6, 3, 8, 3, 1, 3, 1>("k5 naf3", 2100, 900, 1, 8);
-		bad += check<2, 4, 8, 3, 1, 3, 2>("quant naf4", 2100, 900, 1, 8);
-		bad += check<13, 3, 4, 2, 2, 3, 1>("k16 naf3 4+2+2", 1500, 500, 1, 8);
-		bad += check<8, 4, 4, 3, 1, 3, 1>("k8 naf4 4+3+1", 1500, 500, 1, 8);
-		bad += check<12, 3, 4, 2, 2, 3, 1>("k13 nbf12 naf3 4+2+2", 1500, 500, 1, 8);
-		bad += check<12, 6, 4, 2, 2, 3, 1, 2>("k13 nbf12 naf6 2x2", 1500, 700, 1, 8);
-		bad += check<11, 6, 4, 2, 2, 3, 1, 2>("k13 nbf11 naf6 2x2 (6 + 5)", 2100, 700, 1, 8);
-		bad += check<12, 5, 4, 2, 2, 3, 1, 2>("k13 nbf12 naf5 2x2", 1500, 700, 1, 8);
-		bad += check<8, 6, 4, 2, 2, 3, 1, 2>("k8 naf6 2x2", 1500, 700, 1, 8);
-		bad += check<6, 6, 8, 3, 1, 3, 1, 2>("k5 naf6 4x2", 2100, 900, 1, 8);
-		bad += check<16, 4, 4, 2, 2, 3, 1, 2>("k16 nbf16 naf4 2x2", 1100, 300, 1, 8);
-		bad += check<12, 6, 4, 2, 2, 3, 1, 2, 4>("k13 nbf12 naf6 2x2 4 buffers", 1500, 700, 1, 8);
-		bad += check<12, 3, 8, 2, 2, 3, 1, 2>("k13 nbf12 naf3 8 consumers 4x2", 1500, 900, 1, 8);
-		bad += check<13, 3, 8, 2, 2, 3, 1, 2>("k16 nbf13 naf3 8 consumers 4x2", 1100, 900, 1, 8);
-		bad += check<8, 4, 8, 2, 2, 2, 1, 2>("k8 nbf8 naf4 8 consumers 4x2", 1500, 900, 1, 8);
-		bad += check<12, 3, 4, 2, 2, 3, 1, 1, 4>("k13 nbf12 naf3 4 buffers", 1500, 500, 1, 8);
-		bad += check<11, 4, 4, 2, 2, 3, 1, 1, 3>("k13 nbf11 naf4 3 buffers", 1500, 500, 1, 8);
-		bad += check<13, 3, 4, 2, 2, 3, 1, 1, 5>("k16 nbf13 naf3 5 buffers", 1500, 500, 1, 8);
-		bad += check<6, 3, 8, 3, 1, 3, 1, 1, 3>("k5 nbf6 naf3 3 buffers", 2100, 900, 1, 8);
-#endif
-		// row-major rows (the caller's layout, no tiles): M not a multiple of 16, strides beyond the row
-		bad += check<4, 4, 8, 3, 1, 1, 1, 1, 2, 1>("k3 naf4 d1/1", 5000, 700, 1, 8);
-		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1>("k3 naf3 d1/2, M = 693, stride + 64", 5000, 693, 1, 8, 64);
-		bad += check<4, 4, 8, 3, 1, 1, 1, 1, 2, 1>("k3 naf4 big grid", 3000, 301, 1, n_cu, 16);
-		bad += check<4, 2, 8, 2, 2, 2, 2, 1, 2, 1>("k3 naf2 d2/2 tiny N", 100, 50, 1, 8);
-		bad += check<4, 4, 8, 2, 2, 1, 1, 1, 2, 1>("k3 naf4 one variant", 700, 1, 1, 8, 128);
-		bad += check<11, 4, 4, 3, 1, 1, 1, 1, 2, 1>("k13 naf4 4+3+1", 2500, 803, 1, 8);
-		bad += check<2, 4, 8, 3, 1, 1, 2, 1, 2, 1>("quant naf4", 2100, 900, 1, 8);
-		bad += check<13, 3, 4, 2, 2, 1, 1, 1, 2, 1>("k16 naf3 4+2+2", 1500, 499, 1, 8, 192);
-		bad += check<4, 4, 8, 3, 1, 1, 1, 1, 2, 1>("k3 naf4 d1/1, long rows", 70000, 100, 1, 8, 128);
-		bad += check<4, 2, 8, 3, 1, 2, 2, 1, 2, 1>("k3 naf2 d2/2, long rows", 70000, 500, 1, 8);
-		bad += check<6, 3, 8, 3, 1, 1, 1, 1, 2, 1>("k5 naf3 d1/1", 9000, 1000, 1, 16);
-		// every form of the product's table (kern_score3.h S3_FOR_EACH_NBF)
-#define CHKP(NBF, NAF, NC, NLA, NLB, DA, DB) bad += check<NBF, NAF, NC, NLA, NLB, DA, DB, 1, 2, 1>("product form", 2100 + 37 * NBF, 600 + NBF, 1, 8, (NBF & 1) * 64);
+		// grids far smaller than the chip so that rounds, leftovers and pieces all occur; M not a multiple of 16,
+		// strides beyond the row
+		bad += check<4, 4, 8, 3, 1, 1, 1>("k3 naf4 d1/1", 5000, 700, 1, 8);
+		bad += check<4, 3, 8, 3, 1, 1, 2>("k3 naf3 d1/2, M = 693, stride + 64", 5000, 693, 1, 8, 64);
+		bad += check<4, 4, 8, 3, 1, 1, 1>("k3 naf4 big grid", 3000, 301, 1, n_cu, 16);
+		bad += check<4, 2, 8, 2, 2, 2, 2>("k3 naf2 d2/2 tiny N", 100, 50, 1, 8);
+		bad += check<4, 4, 8, 2, 2, 1, 1>("k3 naf4 one variant", 700, 1, 1, 8, 128);
+		bad += check<11, 4, 4, 3, 1, 1, 1>("k13 naf4 4+3+1", 2500, 803, 1, 8);
+		bad += check<2, 4, 8, 3, 1, 1, 2>("quant naf4", 2100, 900, 1, 8);
+		bad += check<13, 3, 4, 2, 2, 1, 1>("k16 naf3 4+2+2", 1500, 499, 1, 8, 192);
+		bad += check<4, 4, 8, 3, 1, 1, 1>("k3 naf4 d1/1, long rows", 70000, 100, 1, 8, 128);
+		bad += check<4, 2, 8, 3, 1, 2, 2>("k3 naf2 d2/2, long rows", 70000, 500, 1, 8);
+		bad += check<6, 3, 8, 3, 1, 1, 1>("k5 naf3 d1/1", 9000, 1000, 1, 16);
+		// every form of the product's tables (kern_score3.h S3_FOR_EACH_NBF, S3_FOR_EACH_NBF_MISS)
+#define CHKP(NBF, NAF, NC, NLA, NLB, DA, DB) bad += check<NBF, NAF, NC, NLA, NLB, DA, DB>("product form", 2100 + 37 * NBF, 600 + NBF, 1, 8, (NBF & 1) * 64);
 		S3_FOR_EACH_NBF(CHKP)
 #undef CHKP
-#define CHKM(NBF, NAF, NC, NLA, NLB, DA, DB) bad += check<NBF, NAF, NC, NLA, NLB, DA, DB, 1, 2, 1, true>("three-plane form", 1900 + 41 * NBF, 500 + NBF, 1, 8, (NBF & 1) * 64);
+#define CHKM(NBF, NAF, NC, NLA, NLB, DA, DB) bad += check<NBF, NAF, NC, NLA, NLB, DA, DB, true>("three-plane form", 1900 + 41 * NBF, 500 + NBF, 1, 8, (NBF & 1) * 64);
 		S3_FOR_EACH_NBF_MISS(CHKM)
 #undef CHKM
-		bad += check<4, 2, 8, 3, 1, 2, 2, 1, 2, 1, true>("three planes, 1 missing code in 65536", 5000, 700, 1, 8, 0, 1);
-		bad += check<4, 2, 8, 3, 1, 2, 2, 1, 2, 1, true>("three planes, no missing code", 3000, 300, 1, 8, 64, 0);
-		bad += check<4, 2, 8, 3, 1, 2, 2, 1, 2, 1, true>("three planes, 5 % missing", 3000, 300, 1, 8, 0, 3277);
+		bad += check<4, 2, 8, 3, 1, 2, 2, true>("three planes, 1 missing code in 65536", 5000, 700, 1, 8, 0, 1);
+		bad += check<4, 2, 8, 3, 1, 2, 2, true>("three planes, no missing code", 3000, 300, 1, 8, 64, 0);
+		bad += check<4, 2, 8, 3, 1, 2, 2, true>("three planes, 5 % missing", 3000, 300, 1, 8, 0, 3277);
 		// the one-set form (NAF = 3, 384-variant tiles): around one tile, leftover tiles cut into pieces, both B rings
-		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, 1 missing code in 65536", 5000, 700, 1, 8, 0, 1);
-		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, no missing code", 3000, 300, 1, 8, 64, 0);
-		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, 5 % missing", 3000, 300, 1, 8, 0, 3277);
-		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, M = 383", 4099, 383, 1, 8);
-		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, M = 384", 4099, 384, 1, 8, 64);
-		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, M = 385", 4099, 385, 1, 8);
-		bad += check<4, 3, 8, 3, 1, 1, 2, 1, 2, 1, true>("naf3, M = 3 tiles + 7, big grid", 9000, 3 * 384 + 7, 1, n_cu);
-		bad += check<4, 3, 8, 3, 1, 1, 1, 1, 2, 1, true>("naf3 d1/1, M = 2 tiles + 1", 7001, 769, 1, 16, 0, 2600);
+		bad += check<4, 3, 8, 3, 1, 1, 2, true>("naf3, 1 missing code in 65536", 5000, 700, 1, 8, 0, 1);
+		bad += check<4, 3, 8, 3, 1, 1, 2, true>("naf3, no missing code", 3000, 300, 1, 8, 64, 0);
+		bad += check<4, 3, 8, 3, 1, 1, 2, true>("naf3, 5 % missing", 3000, 300, 1, 8, 0, 3277);
+		bad += check<4, 3, 8, 3, 1, 1, 2, true>("naf3, M = 383", 4099, 383, 1, 8);
+		bad += check<4, 3, 8, 3, 1, 1, 2, true>("naf3, M = 384", 4099, 384, 1, 8, 64);
+		bad += check<4, 3, 8, 3, 1, 1, 2, true>("naf3, M = 385", 4099, 385, 1, 8);
+		bad += check<4, 3, 8, 3, 1, 1, 2, true>("naf3, M = 3 tiles + 7, big grid", 9000, 3 * 384 + 7, 1, n_cu);
+		bad += check<4, 3, 8, 3, 1, 1, 1, true>("naf3 d1/1, M = 2 tiles + 1", 7001, 769, 1, 16, 0, 2600);
 		return bad ? 1 : 0;
 	}
 	const int N = argc > 1 ? atoi(argv[1]) : 430000;
 	const size_t M = argc > 2 ? (size_t)atoll(argv[2]) : 50000;
 	const int reps = argc > 3 ? atoi(argv[3]) : 5;
 	const int ntile = 2 * ((N + 511) / 512);
-	const size_t abytes = s3_block_bytes(M, ntile);
-	uint8_t *A, *Fl; int *out;
-	CK(hipMalloc((void **)&A, abytes));
-	fill_codes<<<4096, 256>>>((uint32_t *)A, abytes / 4, 12345);
-	if (getenv("ZERO_A")) CK(hipMemset(A, 0, abytes));
+	const size_t bpv = (size_t)ntile * 64;
+	uint8_t *Ar, *Fl; int *out;
+	CK(hipMalloc((void **)&Ar, M * bpv));
+	fill_codes<<<4096, 256>>>((uint32_t *)Ar, M * bpv / 4, 12345, getenv("MISS16") ? (uint32_t)atoi(getenv("MISS16")) : 66u);
+	if (getenv("ZERO_A")) CK(hipMemset(Ar, 0, M * bpv));
 	const int NBFMAX = 16;
 	const size_t flb = (size_t)ntile * 16 * 16 * NBFMAX * 16;
 	CK(hipMalloc((void **)&Fl, flb));
 	{ std::vector<uint8_t> hf(flb); uint64_t x = 5; for (auto &v : hf) v = getenv("ZERO_B") ? 0 : (uint8_t)sm64(x); CK(hipMemcpy(Fl, hf.data(), flb, hipMemcpyHostToDevice)); }
-	const size_t oints = (size_t)1 << 30;       // 4 GiB of slabs: enough for every variant below
+	const size_t oints = (size_t)1 << 30;       // 4 GiB of slabs: enough for every shape below
 	CK(hipMalloc((void **)&out, oints * 4));
 	CK(hipDeviceSynchronize());
 	printf("N=%d M=%zu ntile=%d rows %.3f GB, %d CUs\n", N, M, ntile, (double)M * ntile * 64 / 1e9, n_cu);
-#define R3(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, NCB, NBUF, name) do { \
-\
-	run<NBF, NAF, NC, NLA, NLB, DA, DB, ABL, NCB, NBUF>(name, A, Fl, ntile, M, 1, n_cu, out, oints, reps); } while (0)
-#define R2(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, NCB, name) R3(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, NCB, 2, name)
-#define R(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, name) R2(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, 1, name)
-	if (getenv("RM")) {
-		// row-major rows against tiles, the product forms of K = 3, quantitative, K = 13; N = 50 000 by the command line
-		const size_t bpv = (size_t)ntile * 64;
-		uint8_t *Ar;
-		CK(hipMalloc((void **)&Ar, M * bpv));
-		fill_codes<<<4096, 256>>>((uint32_t *)Ar, M * bpv / 4, 12345, getenv("MISS16") ? (uint32_t)atoi(getenv("MISS16")) : 66u);
+	{
+		// the list builder: small shapes against a CPU walk (N not a multiple of 64, a long-range shape), then the timing
+		uint8_t *Sm; const int n2 = 5003, nt2 = 2 * ((n2 + 511) / 512); const size_t m2 = 333, bp2 = (size_t)nt2 * 64 + 64;
+		CK(hipMalloc((void **)&Sm, m2 * bp2));
+		fill_codes<<<256, 256>>>((uint32_t *)Sm, m2 * bp2 / 4, 777);
 		CK(hipDeviceSynchronize());
-		{
-			// small shapes against a CPU walk (N not a multiple of 64, a long-range shape), then the timing
-			uint8_t *Sm; const int n2 = 5003, nt2 = 2 * ((n2 + 511) / 512); const size_t m2 = 333, bp2 = (size_t)nt2 * 64 + 64;
-			CK(hipMalloc((void **)&Sm, m2 * bp2));
-			fill_codes<<<256, 256>>>((uint32_t *)Sm, m2 * bp2 / 4, 777);
-			CK(hipDeviceSynchronize());
-			int badl = lists_bench(Sm, bp2, n2, m2, nt2, 0, true);
-			CK(hipFree(Sm));
-			const int n3 = 600000, nt3 = 2 * ((n3 + 511) / 512); const size_t m3 = 40, bp3 = (size_t)nt3 * 64;
-			CK(hipMalloc((void **)&Sm, m3 * bp3));
-			fill_codes<<<256, 256>>>((uint32_t *)Sm, m3 * bp3 / 4, 778);
-			CK(hipDeviceSynchronize());
-			badl += lists_bench(Sm, bp3, n3, m3, nt3, 0, true);
-			CK(hipFree(Sm));
+		int badl = lists_bench(Sm, bp2, n2, m2, nt2, 0, true);
+		CK(hipFree(Sm));
+		const int n3 = 600000, nt3 = 2 * ((n3 + 511) / 512); const size_t m3 = 40, bp3 = (size_t)nt3 * 64;
+		CK(hipMalloc((void **)&Sm, m3 * bp3));
+		fill_codes<<<256, 256>>>((uint32_t *)Sm, m3 * bp3 / 4, 778);
+		CK(hipDeviceSynchronize());
+		badl += lists_bench(Sm, bp3, n3, m3, nt3, 0, true);
+		CK(hipFree(Sm));
+		if (badl) return 1;
+		lists_bench(Ar, bpv, N, M, ntile, reps, false);
+		if (getenv("LT3")) {
+			// small shapes against the CPU (ragged N, a long-range shape, dense missing codes), then the timing
+			const int mrates[3] = {66, 655, 6000};
+			for (int q = 0; q < 3; q++) {
+				const int n4 = 70001 + 4099 * q, nt4 = 2 * ((n4 + 511) / 512); const size_t m4 = 131, bp4 = (size_t)nt4 * 64 + 128;
+				CK(hipMalloc((void **)&Sm, m4 * bp4));
+				fill_codes<<<256, 256>>>((uint32_t *)Sm, m4 * bp4 / 4, 900 + q, mrates[q]);
+				CK(hipDeviceSynchronize());
+				badl += lists_t3_bench<8>(Sm, bp4, n4, m4, nt4, 0, true, 8);
+				badl += lists_t3_bench<16>(Sm, bp4, n4, m4, nt4, 0, true, 12);
+				badl += lists_t3_bench<32>(Sm, bp4, n4, m4, nt4, 0, true, 28);
+				badl += lists_t3_bench<64>(Sm, bp4, n4, m4, nt4, 0, true, 34);
+				CK(hipFree(Sm));
+			}
+			{
+				const int n5 = 600000, nt5 = 2 * ((n5 + 511) / 512); const size_t m5 = 24, bp5 = (size_t)nt5 * 64;
+				CK(hipMalloc((void **)&Sm, m5 * bp5));
+				fill_codes<<<256, 256>>>((uint32_t *)Sm, m5 * bp5 / 4, 779, 20);
+				CK(hipDeviceSynchronize());
+				badl += lists_t3_bench<8>(Sm, bp5, n5, m5, nt5, 0, true, 8);
+				CK(hipFree(Sm));
+			}
 			if (badl) return 1;
-			lists_bench(Ar, bpv, N, M, ntile, reps, false);
-			if (getenv("LT3")) {
-				// small shapes against the CPU (ragged N, a long-range shape, dense missing codes), then the timing
-				const int mrates[3] = {66, 655, 6000};
-				for (int q = 0; q < 3; q++) {
-					const int n4 = 70001 + 4099 * q, nt4 = 2 * ((n4 + 511) / 512); const size_t m4 = 131, bp4 = (size_t)nt4 * 64 + 128;
-					CK(hipMalloc((void **)&Sm, m4 * bp4));
-					fill_codes<<<256, 256>>>((uint32_t *)Sm, m4 * bp4 / 4, 900 + q, mrates[q]);
-					CK(hipDeviceSynchronize());
-					badl += lists_t3_bench<8>(Sm, bp4, n4, m4, nt4, 0, true, 8);
-					badl += lists_t3_bench<16>(Sm, bp4, n4, m4, nt4, 0, true, 12);
-					badl += lists_t3_bench<32>(Sm, bp4, n4, m4, nt4, 0, true, 28);
-					badl += lists_t3_bench<64>(Sm, bp4, n4, m4, nt4, 0, true, 34);
-					CK(hipFree(Sm));
-				}
-				{
-					const int n5 = 600000, nt5 = 2 * ((n5 + 511) / 512); const size_t m5 = 24, bp5 = (size_t)nt5 * 64;
-					CK(hipMalloc((void **)&Sm, m5 * bp5));
-					fill_codes<<<256, 256>>>((uint32_t *)Sm, m5 * bp5 / 4, 779, 20);
-					CK(hipDeviceSynchronize());
-					badl += lists_t3_bench<8>(Sm, bp5, n5, m5, nt5, 0, true, 8);
-					CK(hipFree(Sm));
-				}
-				if (badl) return 1;
-				lists_t3_bench<8>(Ar, bpv, N, M, ntile, reps, false, 8);
-				lists_t3_bench<32>(Ar, bpv, N, M, ntile, reps, false, 28);
-				if (getenv("BESIDE")) {
-					S3Lists L{};
-					L.ld = M; L.nr = s3_nranges(ntile);
-					s3_lists_setup(L, ntile, (M * (size_t)L.nr + 3) / 4);
-					CK(hipMalloc((void **)&L.lcnt, S3_NR * M * 4));
-					long long *Q, *part; double *dummy;
-					CK(hipMalloc((void **)&Q, (size_t)ntile * 256 * 8 * 8)); CK(hipMemset(Q, 1, (size_t)ntile * 256 * 8 * 8));
-					CK(hipMalloc((void **)&part, (size_t)L.nr * M * 8 * 2 * 8)); CK(hipMalloc((void **)&dummy, 4096 * 8));
-					hipStream_t so, sl; int lo, hi; CK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-					const int mode = atoi(getenv("BESIDE"));      // 1: stand-in low / list high priority, 2: both normal, 3: stand-in high / list low
-					CK(hipStreamCreateWithPriority(&so, hipStreamNonBlocking, mode == 1 ? lo : mode == 3 ? hi : 0)); CK(hipStreamCreateWithPriority(&sl, hipStreamNonBlocking, mode == 1 ? hi : mode == 3 ? lo : 0));
-					printf("priorities: range %d (low) .. %d (high), mode %d\n", lo, hi, mode);
-					beside<46>("186 regs, 154 KiB LDS", 154 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
-					beside<46>("186 regs, 128 KiB LDS", 128 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
-					beside<46>("186 regs, 8 KiB LDS", 8 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
-					beside<28>("64 regs, 154 KiB LDS", 154 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
-					beside<28>("64 regs, 8 KiB LDS", 8 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
-				}
-				return 0;
-			}
-		}
-#define R0(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, name) run<NBF, NAF, NC, NLA, NLB, DA, DB, ABL, 1, 2, 0>(name, A, Fl, ntile, M, 1, n_cu, out, oints, reps)
-#define R1(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, name) run<NBF, NAF, NC, NLA, NLB, DA, DB, ABL, 1, 2, 1>(name, Ar, Fl, ntile, M, 1, n_cu, out, oints, reps, nullptr, bpv)
-		R0(4, 4, 8, 3, 1, 2, 2, 0, "k3 naf4 8+3+1 d2/2");
-		R0(4, 4, 8, 3, 1, 2, 1, 0, "k3 naf4 8+3+1 d2/1");
-		R0(4, 3, 8, 3, 1, 3, 2, 0, "k3 naf3 8+3+1 d3/2");
-		R0(4, 4, 8, 3, 1, 2, 2, 1, "k3 naf4 memory only");
-		R1(4, 4, 8, 3, 1, 1, 1, 0, "k3 naf4 8+3+1 pairs d1/1 (160 KiB)");
-		R1(4, 4, 8, 2, 2, 1, 1, 0, "k3 naf4 8+2+2 pairs d1/1 (160 KiB)");
-		R1(4, 3, 8, 3, 1, 1, 2, 0, "k3 naf3 8+3+1 pairs d1/2");
-		R1(4, 3, 8, 2, 2, 1, 2, 0, "k3 naf3 8+2+2 pairs d1/2");
-		R1(4, 2, 8, 3, 1, 2, 2, 0, "k3 naf2 8+3+1 pairs d2/2");
-		R1(4, 2, 12, 3, 1, 1, 2, 0, "k3 naf2 12+3+1 pairs d1/2");
-		R1(4, 4, 8, 3, 1, 1, 1, 1, "k3 naf4 pairs d1/1 memory only");
-		R1(4, 3, 8, 3, 1, 1, 2, 1, "k3 naf3 pairs d1/2 memory only");
-#define R3M(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, name) run<NBF, NAF, NC, NLA, NLB, DA, DB, ABL, 1, 2, 1, true>(name, Ar, Fl, ntile, M, 1, n_cu, out, oints, reps, nullptr, bpv)
-		R3M(4, 2, 8, 3, 1, 2, 2, 0, "k3 three planes naf2 8+3+1 d2/2");
-		R3M(4, 2, 8, 3, 1, 2, 1, 0, "k3 three planes naf2 8+3+1 d2/1");
-		R3M(4, 2, 8, 2, 2, 2, 2, 0, "k3 three planes naf2 8+2+2 d2/2");
-		R3M(4, 4, 4, 3, 1, 2, 2, 0, "k3 three planes naf4 4+3+1 d2/2");
-		R3M(4, 2, 8, 3, 1, 2, 2, 1, "k3 three planes naf2 memory only");
-#define R3M3(NBF, NAF, NC, NLA, NLB, DA, DB, ABL, name) run<NBF, NAF, NC, NLA, NLB, DA, DB, ABL, 1, 3, 1, true>(name, Ar, Fl, ntile, M, 1, n_cu, out, oints, reps, nullptr, bpv)
-		if (getenv("NBUF3")) {
-			if (check<4, 2, 8, 3, 1, 2, 2, 1, 3, 1, true>("three planes, B reads two chunks ahead", 2300, 777, 1, 8, 64)) return 1;
-			for (int rep = 0; rep < 3; rep++) {
-				R3M(4, 2, 8, 3, 1, 2, 2, 0, "k3 three planes naf2 8+3+1 d2/2");
-				R3M3(4, 2, 8, 3, 1, 2, 2, 0, "k3 three planes naf2 8+3+1 d2/2 NBUF 3");
+			lists_t3_bench<8>(Ar, bpv, N, M, ntile, reps, false, 8);
+			lists_t3_bench<32>(Ar, bpv, N, M, ntile, reps, false, 28);
+			if (getenv("BESIDE")) {
+				S3Lists L{};
+				L.ld = M; L.nr = s3_nranges(ntile);
+				s3_lists_setup(L, ntile, (M * (size_t)L.nr + 3) / 4);
+				CK(hipMalloc((void **)&L.lcnt, S3_NR * M * 4));
+				long long *Q, *part; double *dummy;
+				CK(hipMalloc((void **)&Q, (size_t)ntile * 256 * 8 * 8)); CK(hipMemset(Q, 1, (size_t)ntile * 256 * 8 * 8));
+				CK(hipMalloc((void **)&part, (size_t)L.nr * M * 8 * 2 * 8)); CK(hipMalloc((void **)&dummy, 4096 * 8));
+				hipStream_t so, sl; int lo, hi; CK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+				const int mode = atoi(getenv("BESIDE"));      // 1: stand-in low / list high priority, 2: both normal, 3: stand-in high / list low
+				CK(hipStreamCreateWithPriority(&so, hipStreamNonBlocking, mode == 1 ? lo : mode == 3 ? hi : 0)); CK(hipStreamCreateWithPriority(&sl, hipStreamNonBlocking, mode == 1 ? hi : mode == 3 ? lo : 0));
+				printf("priorities: range %d (low) .. %d (high), mode %d\n", lo, hi, mode);
+				beside<46>("186 regs, 154 KiB LDS", 154 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
+				beside<46>("186 regs, 128 KiB LDS", 128 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
+				beside<46>("186 regs, 8 KiB LDS", 8 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
+				beside<28>("64 regs, 154 KiB LDS", 154 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
+				beside<28>("64 regs, 8 KiB LDS", 8 * 1024, n_cu, so, sl, Ar, bpv, N, M, ntile, L, 8, Q, part, dummy);
 			}
 			return 0;
 		}
-#ifdef S3_BENCH_SWEEPS   /* the shapes of the three-plane K = 3 kernel that were measured and not adopted (tools/README.md): -DS3_BENCH_SWEEPS, SWEEP3 / SWEEP4 / SWEEP5=1 */
-		if (getenv("SWEEP3")) {
-			R3M(4, 3, 8, 3, 1, 1, 1, 0, "k3 three planes naf3 8+3+1 d1/1");
-			R3M(4, 3, 8, 3, 1, 1, 2, 0, "k3 three planes naf3 8+3+1 d1/2");
-			R3M(4, 3, 8, 2, 2, 1, 1, 0, "k3 three planes naf3 8+2+2 d1/1");
-			R3M(4, 4, 4, 2, 2, 2, 2, 0, "k3 three planes naf4 4+2+2 d2/2");
-			R3M(4, 4, 4, 3, 1, 3, 2, 0, "k3 three planes naf4 4+3+1 d3/2");
-			R3M(4, 2, 8, 3, 1, 3, 1, 0, "k3 three planes naf2 8+3+1 d3/1");
-			R3M(4, 2, 12, 3, 1, 1, 1, 0, "k3 three planes naf2 12+3+1 d1/1");
-			R3M(4, 3, 4, 3, 1, 2, 2, 0, "k3 three planes naf3 4+3+1 d2/2");
-			R3M(4, 4, 8, 3, 1, 1, 1, 0, "k3 three planes naf4 8+3+1 d1/1");
-		}
-		if (getenv("SWEEP5")) {
-			// NAF = 3 at two waves per SIMD (256 registers): 8 waves per workgroup
-			int badc = 0;
-			badc += check<4, 3, 6, 1, 1, 2, 2, 1, 2, 1, true>("three planes naf3 6+1+1", 2300, 777, 1, 8, 64);
-			badc += check<4, 3, 5, 2, 1, 2, 2, 1, 2, 1, true>("three planes naf3 5+2+1", 2300, 777, 1, 8, 64);
-			if (badc) return 1;
-			for (int rep = 0; rep < 2; rep++) {
-				R3M(4, 2, 8, 3, 1, 2, 2, 0, "k3 three planes naf2 8+3+1 d2/2");
-				R3M(4, 3, 6, 1, 1, 2, 2, 0, "k3 three planes naf3 6+1+1 d2/2");
-				R3M(4, 3, 6, 1, 1, 1, 2, 0, "k3 three planes naf3 6+1+1 d1/2");
-				R3M(4, 3, 5, 2, 1, 2, 2, 0, "k3 three planes naf3 5+2+1 d2/2");
-				R3M(4, 3, 5, 2, 1, 3, 2, 0, "k3 three planes naf3 5+2+1 d3/2");
-				R3M(4, 3, 6, 1, 1, 2, 2, 1, "k3 three planes naf3 6+1+1 memory only");
-			}
-			return 0;
-		}
-		if (getenv("SWEEP4")) {
-			int badc = 0;
-			badc += check<4, 4, 5, 2, 1, 2, 1, 1, 2, 1, true>("three planes naf4 5+2+1", 2300, 777, 1, 8, 64);
-			badc += check<4, 4, 6, 1, 1, 1, 2, 1, 2, 1, true>("three planes naf4 6+1+1", 2300, 777, 1, 8, 64);
-			badc += check<4, 2, 8, 2, 2, 2, 2, 1, 2, 1, true>("three planes naf2 8+2+2", 2300, 777, 1, 8, 64);
-			if (badc) return 1;
-			R3M(4, 2, 8, 2, 2, 2, 2, 0, "k3 three planes naf2 8+2+2 d2/2");
-			R3M(4, 4, 5, 2, 1, 2, 1, 0, "k3 three planes naf4 5+2+1 d2/1");
-			R3M(4, 4, 5, 2, 1, 1, 2, 0, "k3 three planes naf4 5+2+1 d1/2");
-			R3M(4, 4, 6, 1, 1, 1, 2, 0, "k3 three planes naf4 6+1+1 d1/2");
-			R3M(4, 4, 6, 1, 1, 1, 1, 0, "k3 three planes naf4 6+1+1 d1/1");
-			R3M(4, 4, 4, 2, 2, 2, 1, 0, "k3 three planes naf4 4+2+2 d2/1");
-			R3M(4, 4, 4, 3, 1, 2, 1, 0, "k3 three planes naf4 4+3+1 d2/1");
-			R3M(4, 2, 8, 2, 2, 2, 1, 0, "k3 three planes naf2 8+2+2 d2/1");
-			R3M(4, 2, 8, 2, 2, 3, 1, 0, "k3 three planes naf2 8+2+2 d3/1");
-			return 0;
-		}
-		if (getenv("SWEEP6")) {
-			// NAF = 3 with one set of planes (s3_one) against the NAF = 2 form it replaced, alternating; the other narrow forms
-			for (int rep = 0; rep < 3; rep++) {
-				R3M(4, 2, 8, 3, 1, 2, 2, 0, "k3 three planes naf2 8+3+1 d2/2");
-				R3M(4, 3, 8, 3, 1, 1, 2, 0, "k3 three planes naf3 one set d1/2");
-				R3M(4, 3, 8, 3, 1, 1, 1, 0, "k3 three planes naf3 one set d1/1");
-			}
-			R3M(4, 3, 8, 2, 2, 1, 2, 0, "k3 three planes naf3 one set 8+2+2");
-			R3M(2, 4, 8, 3, 1, 1, 2, 0, "nbf2 three planes naf4 (table)");
-			R3M(5, 2, 8, 3, 1, 2, 2, 0, "nbf5 three planes naf2 (table)");
-			return 0;
-		}
-#endif
-		R3M(2, 4, 8, 3, 1, 1, 2, 0, "quant three planes naf4");
-		R3M(6, 3, 4, 2, 2, 2, 1, 0, "k5 three planes naf3 4+2+2");
-		R3M(12, 1, 4, 2, 2, 2, 1, 0, "k13 three planes naf1 4+2+2");
-		R0(2, 4, 8, 3, 1, 3, 2, 0, "quant naf4 8+3+1 d3/2");
-		R1(2, 4, 8, 3, 1, 1, 2, 0, "quant naf4 8+3+1 pairs d1/2");
-		R1(2, 4, 8, 3, 1, 1, 3, 0, "quant naf4 8+3+1 pairs d1/3");
-		R0(12, 3, 4, 2, 2, 3, 1, 0, "k13 nbf12 naf3 4+2+2 d3/1");
-		R1(12, 3, 4, 2, 2, 1, 1, 0, "k13 nbf12 naf3 4+2+2 pairs d1/1");
-		R0(6, 3, 8, 3, 1, 3, 1, 0, "k5 naf3 8+3+1 d3/1");
-		R1(6, 3, 8, 3, 1, 1, 1, 0, "k5 naf3 8+3+1 pairs d1/1");
-		return 0;
 	}
-#ifndef S3_BENCH_SMALL
-	if (getenv("ONLY13")) {
-		R2(12, 6, 4, 2, 2, 3, 1, 0, 2, "k13 nbf12 naf6 2x2");
-		return 0;
-	}
-	if (getenv("W8")) {
-		// eight consumer waves (two per SIMD) as variant groups x column groups
-		R2(12, 6, 4, 2, 2, 3, 1, 16, 2, "k13 nbf12 naf6 4 consumers 2x2");
-		R2(12, 3, 8, 3, 1, 3, 1, 16, 2, "k13 nbf12 naf3 8 consumers 4x2 +3+1");
-		R2(12, 3, 8, 2, 2, 3, 1, 16, 2, "k13 nbf12 naf3 8 consumers 4x2 +2+2");
-		R2(12, 3, 8, 1, 3, 3, 1, 16, 2, "k13 nbf12 naf3 8 consumers 4x2 +1+3");
-		R3(12, 3, 8, 2, 2, 3, 1, 16, 2, 3, "k13 nbf12 naf3 8 consumers 4x2 +2+2, 3 buffers");
-		R2(12, 4, 8, 2, 2, 2, 1, 16, 2, "k13 nbf12 naf4 8 consumers 4x2 +2+2 d2/1");
-		R2(12, 6, 8, 2, 2, 3, 1, 16, 4, "k13 nbf12 naf6 8 consumers 2x4 +2+2");
-		R2(12, 2, 8, 2, 2, 3, 1, 16, 1, "k13 nbf12 naf2 8 consumers 8x1 +2+2");
-		R2(11, 3, 8, 2, 2, 3, 1, 16, 2, "k13 nbf11 naf3 8 consumers 4x2");
-		R2(8, 4, 8, 2, 2, 2, 1, 16, 2, "k8 nbf8 naf4 8 consumers 4x2 d2/1");
-		R2(8, 3, 8, 2, 2, 3, 1, 16, 2, "k8 nbf8 naf3 8 consumers 4x2");
-		R(8, 4, 4, 2, 2, 3, 1, 16, "k8 nbf8 naf4 4+2+2 (one group)");
-		R2(16, 3, 8, 2, 2, 2, 1, 16, 2, "nbf16 naf3 8 consumers 4x2 d2/1");
-		R2(16, 2, 8, 2, 2, 3, 1, 16, 2, "nbf16 naf2 8 consumers 4x2");
-		R2(13, 3, 8, 2, 2, 3, 1, 16, 2, "k16 nbf13 naf3 8 consumers 4x2");
-		return 0;
-	}
-	if (getenv("ABL13")) {
-		R2(12, 6, 4, 2, 2, 3, 1, 16, 2, "full");
-		R2(12, 6, 4, 2, 2, 3, 1, 2 | 16, 2, "no row DMA");
-		R2(12, 6, 4, 2, 2, 3, 1, 4 | 16, 2, "no B DMA");
-		R2(12, 6, 4, 2, 2, 3, 1, 1 | 2 | 4 | 16, 2, "LDS reads + barrier only");
-		R2(12, 6, 4, 2, 2, 3, 1, 1 | 4 | 16, 2, "row DMA + LDS reads, no arithmetic");
-		R2(12, 6, 4, 2, 2, 3, 1, 1 | 2 | 16, 2, "B DMA + LDS reads, no arithmetic");
-		R2(12, 6, 4, 2, 2, 3, 1, 1 | 2 | 8 | 16, 2, "B DMA only (no LDS reads of B, no arithmetic)");
-		R2(12, 6, 4, 2, 2, 3, 1, 1 | 2 | 4 | 8 | 16, 2, "barrier + A reads only");
-		R2(12, 6, 4, 2, 2, 3, 1, 2 | 4 | 8 | 16, 2, "arithmetic only (no DMA, no B reads)");
-		R2(12, 6, 4, 1, 3, 3, 1, 1 | 2 | 8 | 16, 2, "B DMA only, 3 B loaders");
-		R2(12, 6, 4, 1, 1, 3, 1, 1 | 2 | 8 | 16, 2, "B DMA only, 1 B loader");
-		return 0;
-	}
-	if (getenv("ONLY3")) {
-		R(4, 4, 8, 3, 1, 2, 2, 0, "k3 naf4 8+3+1 d2/2");
-		return 0;
-	}
-	if (getenv("WIDE")) {
-		// many covariates: column groups (NCB > 1) and deeper B prefetch (NBUF) against the round-3 forms
-		R(12, 3, 4, 2, 2, 3, 1, 16, "k13 nbf12 naf3 4+2+2 (one group)");
-		R3(12, 3, 4, 2, 2, 3, 1, 16, 1, 3, "k13 nbf12 naf3, 3 buffers");
-		R3(12, 3, 4, 2, 2, 3, 1, 16, 1, 4, "k13 nbf12 naf3, 4 buffers");
-		R3(12, 3, 4, 2, 2, 3, 1, 16, 1, 6, "k13 nbf12 naf3, 6 buffers");
-		R2(12, 6, 4, 2, 2, 3, 1, 16, 2, "k13 nbf12 naf6 2x2");
-		R3(12, 6, 4, 2, 2, 3, 1, 16, 2, 3, "k13 nbf12 naf6 2x2, 3 buffers");
-		R3(12, 6, 4, 2, 2, 3, 1, 16, 2, 4, "k13 nbf12 naf6 2x2, 4 buffers");
-		R3(12, 6, 4, 2, 2, 3, 1, 1 | 16, 2, 4, "k13 nbf12 naf6 2x2, 4 buffers, memory system only");
-		R3(12, 5, 4, 2, 2, 3, 1, 16, 2, 4, "k13 nbf12 naf5 2x2, 4 buffers");
-		R(11, 4, 4, 2, 2, 3, 1, 16, "k13 nbf11 naf4 4+2+2 (one group)");
-		R3(11, 4, 4, 2, 2, 3, 1, 16, 1, 3, "k13 nbf11 naf4, 3 buffers");
-		R(8, 4, 4, 2, 2, 3, 1, 16, "k8 nbf8 naf4 4+2+2 (one group)");
-		R3(8, 4, 4, 2, 2, 3, 1, 16, 1, 3, "k8 nbf8 naf4, 3 buffers");
-		R3(8, 4, 4, 2, 2, 3, 1, 16, 1, 4, "k8 nbf8 naf4, 4 buffers");
-		R(6, 3, 8, 3, 1, 3, 1, 16, "k5 nbf6 naf3 8+3+1 (one group)");
-		R3(6, 3, 8, 3, 1, 3, 1, 16, 1, 3, "k5 nbf6 naf3, 3 buffers");
-		R(13, 3, 4, 2, 2, 3, 1, 16, "k16 nbf13 naf3 (one group)");
-		R3(13, 3, 4, 2, 2, 3, 1, 16, 1, 4, "k16 nbf13 naf3, 4 buffers");
-		R(16, 2, 4, 2, 2, 3, 1, 16, "nbf16 naf2 (one group)");
-		R3(16, 2, 4, 2, 2, 3, 1, 16, 1, 4, "nbf16 naf2, 4 buffers");
-		R3(16, 4, 4, 2, 2, 3, 1, 16, 2, 4, "nbf16 naf4 2x2, 4 buffers");
-		return 0;
-	}
-	// K = 3 (3 value fragments + bit-1)
-	if (getenv("SHORT")) {
-		R(4, 4, 8, 3, 1, 2, 2, 16, "k3 naf4 8+3+1 d2/2");
-		R(4, 3, 8, 2, 2, 4, 1, 16, "k3 naf3 8+2+2 d4/1");
-		R(4, 6, 4, 3, 1, 4, 1, 16, "k3 naf6 4+3+1 d4/1");
-		R(4, 6, 4, 2, 2, 4, 1, 16, "k3 naf6 4+2+2 d4/1");
-		R(4, 4, 8, 3, 1, 3, 1, 6 | 16, "k3 naf4 no DMA");
-		R(4, 6, 4, 3, 1, 4, 1, 6 | 16, "k3 naf6 no DMA");
-		R(4, 4, 8, 3, 1, 3, 1, 1 | 16, "k3 naf4 memory system only");
-		R(2, 4, 8, 3, 1, 3, 2, 16, "quant naf4 8+3+1 d3/2");
-		R(11, 4, 4, 2, 2, 3, 1, 16, "k13 naf4 4+2+2 d3/1");
-		return 0;
-	}
-	R(4, 4, 8, 3, 1, 2, 2, 16, "k3 naf4 8+3+1 d2/2");
-	R(4, 4, 8, 3, 1, 3, 1, 16, "k3 naf4 8+3+1 d3/1");
-	R(4, 4, 8, 4, 0 + 1, 3, 1, 0, "k3 naf4 8+4+1 d3/1");
-	R(4, 3, 8, 3, 1, 4, 1, 16, "k3 naf3 8+3+1 d4/1");
-	R(4, 3, 8, 3, 1, 3, 2, 0, "k3 naf3 8+3+1 d3/2");
-	R(4, 3, 8, 3, 1, 4, 2, 0, "k3 naf3 8+3+1 d4/2");
-	R(4, 3, 8, 6, 2, 4, 1, 0, "k3 naf3 8+6+2 d4/1");
-	R(4, 3, 8, 2, 2, 4, 1, 0, "k3 naf3 8+2+2 d4/1");
-	R(4, 2, 12, 3, 1, 4, 1, 16, "k3 naf2 12+3+1 d4/1");
-	R(4, 2, 12, 3, 1, 4, 2, 0, "k3 naf2 12+3+1 d4/2");
-	R(4, 2, 8, 3, 1, 6, 2, 0, "k3 naf2 8+3+1 d6/2");
-	R(4, 4, 8, 3, 1, 3, 1, 1 | 16, "k3 naf4 memory system only");
-	R(4, 4, 8, 3, 1, 3, 1, 6 | 16, "k3 naf4 no DMA");
-	R(4, 3, 8, 3, 1, 4, 1, 1 | 16, "k3 naf3 memory system only");
-	R(4, 3, 8, 3, 1, 4, 1, 6 | 16, "k3 naf3 no DMA");
-	R(4, 3, 8, 3, 1, 4, 1, 2 | 16, "k3 naf3 no row DMA");
-	// quantitative (value fragment + bit-1: 2 fragments)
-	R(2, 4, 8, 3, 1, 3, 2, 0, "quant naf4 8+3+1 d3/2");
-	R(2, 4, 8, 3, 1, 4, 1, 0, "quant naf4 8+3+1 d4/1");
-	// K = 5, 8, 13, 16
-	R(6, 3, 8, 3, 1, 3, 1, 0, "k5 naf3 8+3+1 d3/1");
-	R(6, 3, 8, 2, 2, 3, 1, 0, "k5 naf3 8+2+2 d3/1");
-	R(8, 4, 4, 3, 1, 3, 1, 0, "k8 naf4 4+3+1 d3/1");
-	R(8, 4, 4, 2, 2, 3, 1, 0, "k8 naf4 4+2+2 d3/1");
-	R(11, 4, 4, 2, 2, 3, 1, 16, "k13 naf4 4+2+2 d3/1");
-	R(11, 4, 4, 3, 1, 3, 1, 0, "k13 naf4 4+3+1 d3/1");
-	R(11, 4, 4, 2, 2, 3, 1, 6 | 16, "k13 naf4 no DMA");
-	R(13, 3, 4, 2, 2, 3, 1, 0, "k16 naf3 4+2+2 d3/1");
-	// N = 50 000 shape is run by passing N on the command line
-#endif
+	// every entry of the product's tables
+#define RUNP(NBF, NAF, NC, NLA, NLB, DA, DB) run<NBF, NAF, NC, NLA, NLB, DA, DB>("two planes", Ar, Fl, ntile, M, 1, n_cu, out, oints, reps, bpv);
+	S3_FOR_EACH_NBF(RUNP)
+#undef RUNP
+#define RUNM(NBF, NAF, NC, NLA, NLB, DA, DB) run<NBF, NAF, NC, NLA, NLB, DA, DB, true>("three planes", Ar, Fl, ntile, M, 1, n_cu, out, oints, reps, bpv);
+	S3_FOR_EACH_NBF_MISS(RUNM)
+#undef RUNM
 	return 0;
 }
