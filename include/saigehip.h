@@ -293,6 +293,37 @@ int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant
 	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut,
 	double *score, double *cov);
 
+/* Conditional scan: the score statistic of every scanned variant, its variance and its covariances with a set C of
+ * conditioning (lead) variants -- what the test of variant j given C needs (saigegds_amd/cond.py; nothing of this is in
+ * the reference, DESIGN.md 8b "Conditional analysis").  Tables as for sgx_skat_2bit: lut[4j + code] holds mean imputation
+ * and the flip to the minor allele.  With S and Phi as sgx_skat_2bit defines them:
+ *   sgx_cond_set       installs the set: n_cond (1 .. SGX_COND_MAX) 2-bit rows in HOST memory with their tables.
+ *                      score_c[n_cond] = S_C and cov_cc[n_cond][n_cond] = Phi_CC, exactly symmetric, are made by the
+ *                      functions sgx_skat_2bit is made of and equal sgx_skat_2bit on the set as one unit bit for bit.
+ *                      The handle keeps the set's sums and the dense matrix the kernel multiplies by
+ *                      (n_samp x 16 ceil((2K + 1 + n_cond) / 16) doubles on the device).  A later call replaces the set
+ *                      once everything queued on the handle has finished; n_cond = 0 clears it.  Synchronous.
+ *   sgx_cond_2bit      rows in HOST memory, uploaded in the chunks of the host-buffer scans:
+ *                        score[j] = S_j,  var[j] = Phi_jj,  cov[j * n_cond + c] = Phi_jc,
+ *                      so that S_j^2 / Phi_jj is the chi-square behind the p.norm column of the scan of that row.
+ *                      Synchronous; a thin wrapper around the next entry: same kernel, same bits.
+ *   sgx_cond_2bit_dev  the same from rows in DEVICE memory (stride and alignment as for sgx_scan_2bit_dev); tables and
+ *                      results are device pointers.  Asynchronous on the stream of the handle's most recently issued
+ *                      call, so it is ordered behind a scan of the same rows; results are readable after sgx_sync().
+ * The sums are made in FP64 on the matrix cores (Phi_jj's quadratic term on the vector ALU) in a fixed order: no atomics,
+ * sample slabs cut by n_samp alone, so a row's results do not depend on the number of rows, on the row's position, on the
+ * other rows of the call or on how the call is cut into chunks.  A row whose table holds a non-finite value gets
+ * non-finite results and leaves the other rows alone.  n_variants = 0 succeeds and does nothing.  A NULL buffer,
+ * n_cond > SGX_COND_MAX, bytes_per_variant < ceil(n_samp / 4), a bad device stride or alignment, or sgx_cond_2bit* with no
+ * set installed returns SGX_EINVAL and launches nothing; the handle stays usable. */
+#define SGX_COND_MAX 16
+int sgx_cond_set(sgx_handle *h, const uint8_t *packed_c, size_t bytes_per_variant, size_t n_cond,
+	const double *lut_c, double *score_c, double *cov_cc);
+int sgx_cond_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant, size_t n_variants,
+	const double *lut, double *score, double *var, double *cov);
+int sgx_cond_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_per_variant, size_t n_variants,
+	const double *lut_dev, double *score_dev, double *var_dev, double *cov_dev);
+
 /* Aggregate tests on dosage input: the INTSXP / REALSXP branches of ds_mat_mafmac and ds_mat_burden
  * (src/saige_main.cpp:485-610), which the R drivers reach with .dsnode(gdsfile, dsnode) for imputed
  * data (R/assoc_aggregate.r:89,351,606).  A batch of dosage rows (u8: 0xFF = missing; i32: INT_MIN =

@@ -6,6 +6,7 @@ Public surface (mirrors the reference's R API for this path):
     init_nullmod       .init_nullmod                  (R/assoc_single.r:17-67)
     seqGLMM_GxG_spa    SNP x SNP interaction test     (R/saige_interaction.r:44-641)
     seqAssocGLMM_spaSKAT  variance-component set test (not in the reference)
+    seqAssocGLMM_SPA_cond scan given a set of conditioning variants (not in the reference)
 The compute lives in libsaigehip.so (include/saigehip.h); there is no CPU path.
 """
 from .nullmod import NullModel, ScanModel, init_nullmod, load_modobj  # noqa: F401
@@ -15,5 +16,6 @@ from .gxg import DosageMatrix, GxGTable, saddle_prob, seqGLMM_GxG_spa  # noqa: F
 from .aggregate import (AggrParamBeta, pACAT, pACAT2, seqAssocGLMM_spaACAT_O, seqAssocGLMM_spaACAT_V,  # noqa: F401
                         seqAssocGLMM_spaBurden)
 from .skat import pchisq_mix, seqAssocGLMM_spaSKAT  # noqa: F401
+from .cond import cond_tests, seqAssocGLMM_SPA_cond  # noqa: F401
 
 __version__ = "0.1.0"

@@ -25,10 +25,12 @@ EXPORTS = (
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
     "sgx_quantize_packed",
     "sgx_skat_2bit", "sgx_ds_block_skat",
+    "sgx_cond_set", "sgx_cond_2bit", "sgx_cond_2bit_dev",
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
 SKAT_MAX_VARIANTS = 4096   # SGX_SKAT_MAX_VARIANTS: entries of one unit of sgx_skat_2bit
+COND_MAX = 16         # SGX_COND_MAX: conditioning variants of one sgx_cond_set
 DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
 DS_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float64): 2}   # SGX_DS_U8 / _I32 / _F64
 # SGX_PR_*: the GDS classes whose rows cross PCIe as stored (sgx_scan_packed) and the numpy type of their values
@@ -189,6 +191,12 @@ def load():
     L.sgx_burden_2bit.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
     L.sgx_skat_2bit.restype = C.c_int
     L.sgx_skat_2bit.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
+    L.sgx_cond_set.restype = C.c_int
+    L.sgx_cond_set.argtypes = [vp, vp, sz, sz, vp, vp, vp]
+    L.sgx_cond_2bit.restype = C.c_int
+    L.sgx_cond_2bit.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
+    L.sgx_cond_2bit_dev.restype = C.c_int
+    L.sgx_cond_2bit_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
     L.sgx_dsblock_create.restype = C.c_int
     L.sgx_dsblock_create.argtypes = [C.c_int32, C.c_int, sz, C.c_int, C.POINTER(vp)]
     L.sgx_dsblock_free.restype = None
@@ -403,6 +411,39 @@ class Scanner:
                                         unit_ptr.ctypes.data, var_idx.ctypes.data, lut.ctypes.data,
                                         score.ctypes.data, cov.ctypes.data))
         return score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)]
+
+    def cond_set(self, packed_c: np.ndarray, lut_c):
+        """Installs the conditioning set of the conditional scan (``sgx_cond_set``): its 2-bit rows and 4-entry dosage
+        tables -> (score_c [C], cov_cc [C, C]), which equal ``skat_2bit`` on the rows as one unit bit for bit.  No rows
+        clears the set."""
+        packed_c = np.ascontiguousarray(packed_c, dtype=np.uint8)
+        lut_c = np.ascontiguousarray(lut_c, dtype=np.float64).reshape(-1, 4)
+        if packed_c.ndim != 2 or lut_c.shape[0] != packed_c.shape[0]:
+            raise ValueError("cond_set: one table per conditioning row")
+        c = packed_c.shape[0]
+        score, cov = np.zeros(max(1, c)), np.zeros(max(1, c * c))
+        check(self._L.sgx_cond_set(self._h, packed_c.ctypes.data, packed_c.shape[1], c, lut_c.ctypes.data,
+                                   score.ctypes.data, cov.ctypes.data))
+        self._n_cond = c
+        return score[:c], cov[:c * c].reshape(c, c)
+
+    def cond_2bit(self, packed: np.ndarray, lut):
+        """Score, variance and covariances with the installed conditioning set of every 2-bit row (one 4-entry dosage
+        table each; ``sgx_cond_2bit``) -> (score [m], var [m], cov [m, C])."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
+        if packed.ndim != 2 or lut.shape[0] != packed.shape[0]:
+            raise ValueError("cond_2bit: one table per row")
+        m, c = packed.shape[0], getattr(self, "_n_cond", 0)
+        score, var, cov = np.zeros(m), np.zeros(m), np.zeros((m, max(1, c)))
+        check(self._L.sgx_cond_2bit(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data,
+                                    score.ctypes.data, var.ctypes.data, cov.ctypes.data))
+        return score, var, cov[:, :c]
+
+    def cond_2bit_dev(self, packed_ptr: int, bpv: int, m: int, lut_ptr: int, score_ptr: int, var_ptr: int, cov_ptr: int):
+        """``cond_2bit`` on rows, tables and results in device memory (``sgx_cond_2bit_dev``; asynchronous, sync()
+        before reading)."""
+        check(self._L.sgx_cond_2bit_dev(self._h, packed_ptr, bpv, m, lut_ptr, score_ptr, var_ptr, cov_ptr))
 
     def dosage_block(self, dtype, max_variants: int) -> "DosageBlock":
         """Device storage for a batch of dosage rows of the aggregate tests (``DosageBlock`` below)."""

@@ -1,0 +1,250 @@
+"""Conditional association scan on MI355X: ``seqAssocGLMM_SPA_cond`` tests every variant given a set of conditioning
+(lead) variants, ``cond_tests`` is its host algebra.
+
+The reference has no conditional analysis (SAIGE proper has ``--condition``), so nothing here mirrors reference code
+and no reference vector pins it: the definition is tied to the project's pinned scan and SKAT paths by identities
+(DESIGN.md 8b "Conditional analysis", tests/test_gpu_cond.py).  With the score statistics ``S`` and their covariance
+``Phi`` as ``sgx_skat_2bit`` defines them, the test of variant j given the set C is the score test of the part of
+``G_j`` that the conditioning variants do not explain:
+
+    T = S_j - Phi_jC Phi_CC^-1 S_C,    V = Phi_jj - Phi_jC Phi_CC^-1 Phi_Cj,    chi-square = T^2 / V.
+
+The flow of a call: the conditioning rows are scanned at thresholds 0 / 0 / 1 and installed with ``sgx_cond_set``
+(``S_C``, ``Phi_CC``); then per block of variants the rows go to the device once, ``sgx_scan_2bit_dev`` makes the
+single-variant table, the dosage tables are built on the device from its ``AF`` column, ``sgx_cond_2bit_dev`` makes
+``S_j``, ``Phi_jj`` and ``Phi_jC`` of every row, and one download brings everything back.
+"""
+from __future__ import annotations
+
+import math
+import re
+from typing import Any, Dict, Optional
+
+import numpy as np
+
+from .assoc import BLOCK_SIZE, GenotypeSource, _is_num, _open_source, _pretty, assemble_result
+from .gds import pack_dosage_2bit, unpack_dosage_2bit
+from .nullmod import ModelError, NullModel, init_nullmod, load_modobj
+from .skat import spa_scale
+
+COND_MAX = 16             # SGX_COND_MAX: conditioning variants of one call
+COND_COLLINEAR = 1e-6     # V <= this fraction of Phi_jj: the variant is taken to be explained by the set (a definition:
+#                           Phi is good to ~1e-10 of itself, so anything near 1e-8 is noise)
+
+
+def _cholesky(a: np.ndarray) -> np.ndarray:
+    """Lower Cholesky factor; ValueError where a pivot is not above COND_COLLINEAR times its diagonal entry."""
+    c = a.shape[0]
+    L = np.zeros((c, c))
+    for k in range(c):
+        piv = a[k, k] - float(L[k, :k] @ L[k, :k])
+        if not (a[k, k] > 0 and piv > COND_COLLINEAR * a[k, k]):
+            raise ValueError("The conditioning variants are collinear.")
+        L[k, k] = math.sqrt(piv)
+        L[k + 1:, k] = (a[k + 1:, k] - L[k + 1:, :k] @ L[k, :k]) / L[k, k]
+    return L
+
+
+def cond_tests(S, var, cov, S_C, Phi_CC, d=None, d_C=None):
+    """Conditional score tests, vectorised over rows: ``S`` [m], ``var`` = Phi_jj [m], ``cov`` = Phi_jC [m, C] of the
+    scanned rows, ``S_C`` [C] and ``Phi_CC`` [C, C] of the conditioning set; ``d`` [m] / ``d_C`` [C]: the SPA scale
+    factors (``skat.spa_scale``), Phi~ = D^1/2 Phi D^1/2.  -> (beta, SE, pval):
+
+        T = S_j - Phi~_jC Phi~_CC^-1 S_C,  V = Phi~_jj - Phi~_jC Phi~_CC^-1 Phi~_Cj,
+        beta = T / V,  SE = 1 / sqrt(V),  pval = chdtrc(1, T^2 / V).
+
+    A row with ``V <= COND_COLLINEAR * Phi~_jj`` (a variant of the set itself, say) gets NaN in all three.  ``Phi~_CC``
+    is factorised once by Cholesky; if a pivot is at or below COND_COLLINEAR times its diagonal entry, ``ValueError``."""
+    from scipy.linalg import solve_triangular
+    from scipy.special import chdtrc
+    S, var = np.asarray(S, dtype=np.float64), np.asarray(var, dtype=np.float64)
+    S_C, Phi_CC = np.asarray(S_C, dtype=np.float64), np.asarray(Phi_CC, dtype=np.float64)
+    c = S_C.size
+    cov = np.asarray(cov, dtype=np.float64).reshape(S.size, c)
+    if Phi_CC.shape != (c, c) or var.shape != S.shape:
+        raise ValueError("cond_tests: inconsistent shapes")
+    if d is not None:
+        d = np.asarray(d, dtype=np.float64)
+        var, cov = var * d, cov * np.sqrt(d)[:, None]
+    if d_C is not None:
+        sc_ = np.sqrt(np.asarray(d_C, dtype=np.float64))
+        cov, Phi_CC = cov * sc_[None, :], Phi_CC * sc_[:, None] * sc_[None, :]
+    if not np.all(np.isfinite(Phi_CC)) or not np.all(np.isfinite(S_C)):
+        raise ValueError("The conditioning variants are collinear.")
+    L = _cholesky(Phi_CC)
+    z = solve_triangular(L, S_C, lower=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        Y = solve_triangular(L, np.where(np.isfinite(cov), cov, 0.0).T, lower=True)      # [C, m]
+        T = S - Y.T @ z
+        V = var - np.sum(Y * Y, axis=0)
+        ok = np.isfinite(cov).all(axis=1) & np.isfinite(S) & (V > COND_COLLINEAR * var)
+        beta, se, p = (np.full(S.size, np.nan) for _ in range(3))
+        beta[ok], se[ok] = T[ok] / V[ok], 1.0 / np.sqrt(V[ok])
+        p[ok] = chdtrc(1.0, T[ok] * T[ok] / V[ok])
+    return beta, se, p
+
+
+def _tables(af, valid):
+    """Dosage tables of the rows on the rows' device (torch): m = 2 AF, flipped where AF > 0.5 -- {0, 1, 2, m} or
+    {2, 1, 0, 2 - m}, the imputation and flip of the scan itself; NaN where the row is not valid."""
+    import torch
+    m = 2 * af
+    z = torch.zeros_like(m)
+    lut = torch.where((af > 0.5)[:, None], torch.stack([z + 2, z + 1, z, 2 - m], dim=1), torch.stack([z, z + 1, z + 2, m], dim=1))
+    return torch.where(valid[:, None], lut, torch.full_like(lut, float("nan"))).contiguous()
+
+
+def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("nan"), mac: float = 10,
+                          missing: float = 0.1, spa_pval: float = 0.05, var_ratio: float = float("nan"),
+                          res_savefn: str = "", res_compress: str = "LZMA", verbose: bool = True, dsnode: str = "",
+                          scanner_factory=None) -> Optional[Dict[str, Any]]:
+    """Single-variant scan of every variant given the variants ``condition`` (not in the reference).
+
+    ``condition``: 1 to 16 distinct values of the file's ``variant.id`` (of ``GenotypeSource.variant_id``); the other
+    arguments as ``seqAssocGLMM_SPA``.  Hard calls only (``genotype/data`` or an in-memory source of packed rows); one GPU.
+
+    The conditioning variants are scanned at thresholds 0 / 0 / 1; each must be valid with mac > 0.  Binary traits:
+    ``Phi`` is scaled by the SPA factors ``d_j`` of ``seqAssocGLMM_spaSKAT`` (scanned rows and conditioning variants
+    alike), so that without a correlated conditioning variant the conditional p-value of a row is its SPA p-value.
+    Result: the columns of ``seqAssocGLMM_SPA``, then ``beta.cond``, ``SE.cond``, ``pval.cond`` (``cond_tests``;
+    ``beta.cond`` refers to the alt allele like ``beta``).  A variant of the set itself, or one the set explains,
+    gets NaN there.  ``res_savefn``: ``.rds`` / ``.RData``; the ``.gds`` writer has fixed columns and is refused."""
+    for nm, v in (("maf", maf), ("mac", mac), ("missing", missing), ("spa.pval", spa_pval), ("var.ratio", var_ratio)):
+        if not _is_num(v):
+            raise TypeError(f"is.numeric({nm}) is not TRUE")
+    if not isinstance(dsnode, str):
+        raise TypeError("is.character(dsnode) is not TRUE")
+    if not isinstance(res_savefn, str):
+        raise TypeError("is.character(res.savefn) is not TRUE")
+    if res_compress not in ("LZMA", "LZMA_RA", "ZIP", "ZIP_RA", "none"):
+        raise ValueError("`res.compress` should be one of LZMA, LZMA_RA, ZIP, ZIP_RA and none.")
+    if re.search(r"\.gds$", res_savefn, re.I):
+        raise ValueError("The gds output has no columns for the conditional test; save to RData or RDS.")
+    try:
+        cond_ids = list(np.asarray(condition).ravel().tolist())
+    except Exception:
+        raise ValueError("`condition` should be a list of variant ids.") from None
+    if not 1 <= len(cond_ids) <= COND_MAX:
+        raise ValueError(f"`condition` should hold 1 to {COND_MAX} variant ids.")
+    if len(set(cond_ids)) != len(cond_ids):
+        raise ValueError("`condition` holds a variant id more than once.")
+    if verbose:
+        print("SAIGE conditional association analysis:")
+    mod: NullModel = load_modobj(modobj, verbose)
+    src = _open_source(gdsfile, verbose)
+    in_mem = isinstance(src, GenotypeSource)
+    if dsnode != "" or (in_mem and src.packed is None) or (not in_mem and src.node("genotype/data", silent=True) is None):
+        raise NotImplementedError("Conditional analysis on dosage input is not implemented.")
+    vid = np.asarray(src.variant_id if in_mem else src.read("variant.id"))
+    where = {v: i for i, v in enumerate(vid.tolist())}
+    unknown = [v for v in cond_ids if v not in where]
+    if unknown:
+        raise ValueError(f"`condition`: no variant with id {unknown[0]!r}.")
+    cidx = [where[v] for v in cond_ids]
+
+    # sample matching, as seqAssocGLMM_SPA
+    gsid = [str(s) for s in src.sample_id()]
+    pos = {str(s): i for i, s in enumerate(mod.sample_id)}
+    sel = [i for i, s in enumerate(gsid) if s in pos]
+    if len(sel) != len(mod.sample_id):
+        raise ModelError("Some of sample IDs are not available in the GDS file.")
+    ii = np.array([pos[gsid[i]] for i in sel], dtype=np.int64)
+    sel = np.asarray(sel, dtype=np.int64)
+    n_samp, n_all = sel.size, len(gsid)
+    n_var = src.packed.shape[0] if in_mem else src.genotype_dims()[0]
+    if n_samp <= 0:
+        raise ValueError("No sample in the genotypic data set!")
+    if n_var <= 0:
+        raise ValueError("No variant in the genotypic data set!")
+    all_samples = n_samp == n_all and np.array_equal(sel, np.arange(n_all))
+    if not math.isfinite(var_ratio):
+        var_ratio = float(np.nanmean(mod.var_ratio))
+    if verbose:
+        print(f"    # of samples: {_pretty(n_samp)}")
+        print(f"    # of variants: {_pretty(n_var)}")
+        print(f"    # of conditioning variants: {len(cidx)}")
+
+    def read_rows(off: int, end: int) -> np.ndarray:
+        """2-bit rows of variants [off, end) for the model's samples (host decoder)."""
+        if in_mem:
+            blk = src.packed[off:end]
+            return blk if all_samples else pack_dosage_2bit(unpack_dosage_2bit(blk, n_all)[:, sel])
+        return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
+
+    import torch
+    mobj = init_nullmod(mod, ii, maf, mac, missing, spa_pval, var_ratio)
+    if mod.trait_type not in ("binary", "quantitative"):
+        raise ModelError("Invalid 'modobj$trait.type'.")
+    binary = mod.trait_type == "binary"
+    if scanner_factory is None:
+        from ._lib import Scanner, load
+        if load().sgx_device_count() <= 0:
+            raise RuntimeError("seqAssocGLMM_SPA_cond: no MI355X device is visible (there is no CPU fallback)")
+        scanner_factory = Scanner
+    sc = scanner_factory(mobj)
+    try:
+        dev = torch.device(getattr(sc, "torch_device", "cuda"))
+        nb = (n_samp + 3) // 4
+
+        # the conditioning set
+        sc.set_thresholds(0.0, 0.0, 1.0, float(spa_pval))
+        rows_c = np.ascontiguousarray(np.concatenate([read_rows(i, i + 1)[:, :nb] for i in cidx]))
+        out_c, valid_c = sc.scan_2bit(rows_c)
+        for k, v in enumerate(cond_ids):
+            if not valid_c[k] or not out_c[k, 1] > 0:
+                raise ValueError(f"`condition`: variant {v!r} has no valid genotype or is monomorphic.")
+        lut_c = _tables(torch.from_numpy(out_c[:, 0].copy()), torch.ones(len(cidx), dtype=torch.bool)).numpy()
+        S_C, Phi_CC = sc.cond_set(rows_c, lut_c)
+        sc.set_thresholds(float(maf), float(mac), float(missing), float(spa_pval))
+
+        # the scan, by blocks
+        C = len(cidx)
+        stride = sc.row_stride()
+        res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
+        for off in range(0, n_var, BLOCK_SIZE):
+            end = min(n_var, off + BLOCK_SIZE)
+            m = end - off
+            host = np.zeros((m, stride), dtype=np.uint8)
+            host[:, :nb] = read_rows(off, end)[:, :nb]
+            rows = torch.from_numpy(host).to(dev)                       # the one upload
+            out8 = torch.empty((m, 8), dtype=torch.float64, device=dev)
+            valid = torch.zeros(m, dtype=torch.uint8, device=dev)
+            score, var = (torch.empty(m, dtype=torch.float64, device=dev) for _ in range(2))
+            cov = torch.empty((m, C), dtype=torch.float64, device=dev)
+            if dev.type == "cuda":
+                torch.cuda.synchronize()
+            sc.scan_2bit_dev(rows.data_ptr(), stride, m, out8.data_ptr(), valid.data_ptr())
+            sc.sync()
+            lut = _tables(out8[:, 0], valid != 0)
+            if dev.type == "cuda":
+                torch.cuda.synchronize()
+            sc.cond_2bit_dev(rows.data_ptr(), stride, m, lut.data_ptr(), score.data_ptr(), var.data_ptr(), cov.data_ptr())
+            sc.sync()
+            res[off:end] = torch.cat([out8, valid.to(torch.float64)[:, None], score[:, None], var[:, None], cov],
+                                     dim=1).cpu().numpy()              # the one download
+    finally:
+        sc.close()
+
+    x = res[:, 8] != 0
+    if verbose:
+        print(f"# of variants after filtering by MAF, MAC and missing thresholds: {_pretty(int(x.sum()))}")
+    ans = assemble_result(src, x, res[:, :8], mod.trait_type)
+    o, S, var, cov = res[x, :8], res[x, 9], res[x, 10], res[x, 11:]
+    d = d_C = None
+    if binary:
+        d = spa_scale(o, S, var, float(spa_pval))
+        d_C = spa_scale(out_c, S_C, np.diag(Phi_CC), float(spa_pval))
+    beta, se, p = cond_tests(S, var, cov, S_C, Phi_CC, d, d_C)
+    ans["beta.cond"] = np.where(o[:, 0] > 0.5, -beta, beta)        # S is the flipped row's: back to the alt allele
+    ans["SE.cond"], ans["pval.cond"] = se, p
+    if res_savefn:
+        from .results import save_result
+        if verbose:
+            print(f"Save to '{res_savefn}' ...")
+        save_result(ans, res_savefn, res_compress, sample_id=[gsid[i] for i in sel])
+        if verbose:
+            print("Done.")
+        return None
+    if verbose:
+        print("Done.")
+    return ans

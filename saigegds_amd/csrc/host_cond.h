@@ -1,0 +1,158 @@
+// host_cond.h -- the conditional scan ("Conditional analysis"): sgx_cond_set installs a set of
+// conditioning variants (their S and Phi by sgx_skat_2bit's own functions, the dense matrix B of kern_cond.h on the
+// device), sgx_cond_2bit_dev makes score, variance and the covariances with the set for rows in device memory,
+// sgx_cond_2bit is its wrapper for rows in host memory.
+// Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
+
+static const size_t COND_PART_BYTES = (size_t)256 << 20;    // per-slab partial sums of one launch
+
+static int cond_ncol(const sgx_handle *p) { return 2 * p->md.K + 1 + p->n_cond; }
+
+extern "C" int sgx_cond_set(sgx_handle *h, const uint8_t *packed_c, size_t bpv, size_t n_cond,
+	const double *lut_c, double *score_c, double *cov_cc)
+{
+	if (!h) return fail(SGX_EINVAL, "sgx_cond_set: NULL handle");
+	if (h->owner) return fail(SGX_EINVAL, "sgx_cond_set: not on a twin");
+	if (n_cond > SGX_COND_MAX)
+		return fail(SGX_EINVAL, "sgx_cond_set: %zu conditioning variants, at most %d are supported", n_cond, SGX_COND_MAX);
+	if (n_cond && (!packed_c || !lut_c || !score_c || !cov_cc)) return fail(SGX_EINVAL, "sgx_cond_set: NULL buffer");
+	const int N = h->md.N, K = h->md.K, P = h->md.P;
+	if (n_cond && bpv < (size_t)(N + 3) / 4)
+		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
+	int rc = sgx_sync(h);                       // nothing queued reads the set that is replaced
+	if (rc) return rc;
+	h->n_cond = 0;
+	if (n_cond == 0) return SGX_OK;
+
+	// S_C and Phi_CC: sgx_skat_2bit on the set as one unit
+	const int64_t unit_ptr[2] = {0, (int64_t)n_cond};
+	int32_t var_idx[SGX_COND_MAX];
+	for (size_t c = 0; c < n_cond; c++) var_idx[c] = (int32_t)c;
+	std::vector<double> dense;
+	rc = skat_2bit_host(h, packed_c, bpv, n_cond, 1, unit_ptr, var_idx, lut_c, score_c, cov_cc, dense);
+	if (rc) return rc;
+
+	// their c' and e sums, then B = (F[:, 0:2K+1] | mu2 o G_c | zeros)
+	const int C = (int)n_cond, PB = 16 * ((2 * K + 1 + C + 15) / 16);
+	std::vector<double> ce((size_t)C * 2 * K);
+	for (int c = 0; c < C; c++)
+		for (int a = 0; a < 2 * K; a++) ce[(size_t)c * 2 * K + a] = dense[(size_t)c * (2 * K + 1) + a];
+	rc = grow(h->cond_ce, h->cond_ce_cap, (size_t)SGX_COND_MAX * 2 * KMAX);
+	if (rc) return rc;
+	rc = grow(h->cond_B, h->cond_B_cap, (size_t)N * PB);
+	if (rc) return rc;
+	const size_t dbpv = (size_t)((N + 15) >> 4) * 4, o_lut = ((size_t)C * dbpv + 15) & ~(size_t)15;
+	rc = grow(h->stage_pk, h->stage_pk_cap, o_lut + (size_t)C * 4 * sizeof(double));
+	if (rc) return rc;
+	rc = copy_rows_h2d(h->stage_pk, dbpv, packed_c, bpv, (size_t)C, h->stream);
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut_c, (size_t)C * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->cond_ce, ce.data(), ce.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+	const size_t nel = (size_t)N * PB;
+	hipLaunchKernelGGL(cond_build_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, h->stream,
+		h->stage_pk, dbpv, reinterpret_cast<const double *>(h->stage_pk + o_lut), C, h->dF, P, N, PB, h->cond_B);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(h->stream));
+	h->n_cond = C;
+	return SGX_OK;
+}
+
+// Rows in device memory -> score / var / cov in device memory, queued on lane->stream: the rows in launches whose
+// per-slab sums fit COND_PART_BYTES (what a row gets does not depend on the cut), each followed by the slab sum and
+// the finish.  p: the primary handle, which holds the set.
+static int cond_rows_dev(sgx_handle *p, sgx_handle *lane, const uint8_t *rows, size_t bpv, size_t M,
+	const double *lut, double *score, double *var, double *cov)
+{
+	const int N = p->md.N, C = p->n_cond, NCT = (cond_ncol(p) + 15) / 16, WD = 16 * NCT + 1;
+	const int nslab = ((N + 255) / 256 + COND_SLAB_CH - 1) / COND_SLAB_CH;
+	size_t mchunk = COND_PART_BYTES / ((size_t)nslab * WD * sizeof(double));
+	mchunk = std::min(M, std::max<size_t>(COND_WG_ROWS, mchunk / COND_WG_ROWS * COND_WG_ROWS));
+	int rc = ensure_buf(lane, &lane->cond_part, &lane->cond_part_cap, mchunk * nslab * WD);
+	if (rc) return rc;
+	rc = ensure_buf(lane, &lane->cond_fin, &lane->cond_fin_cap, mchunk * WD);
+	if (rc) return rc;
+	hipStream_t st = lane->stream;
+	for (size_t off = 0; off < M; off += mchunk) {
+		const size_t m = std::min(mchunk, M - off);
+		const dim3 grid((unsigned)((m + COND_WG_ROWS - 1) / COND_WG_ROWS), (unsigned)nslab);
+#define SGX_COND_RECT(n) hipLaunchKernelGGL(cond_rect_kernel<n>, grid, dim3(256), 0, st, rows + off * bpv, bpv, N, m, \
+			lut + 4 * off, p->dF, p->md.P, p->cond_B, COND_SLAB_CH, lane->cond_part)
+		switch (NCT) {
+		case 1: SGX_COND_RECT(1); break;
+		case 2: SGX_COND_RECT(2); break;
+		case 3: SGX_COND_RECT(3); break;
+		default: SGX_COND_RECT(4); break;
+		}
+#undef SGX_COND_RECT
+		HIPCHK(hipGetLastError());
+		const size_t nel = m * WD;
+		hipLaunchKernelGGL(skat_reduce_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st,
+			lane->cond_part, nel, nslab, lane->cond_fin);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(cond_finish_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+			lane->cond_fin, m, WD, p->md, C, p->cond_ce, score + off, var + off, cov + off * C);
+		HIPCHK(hipGetLastError());
+	}
+	return SGX_OK;
+}
+
+extern "C" int sgx_cond_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bpv, size_t M,
+	const double *lut_dev, double *score_dev, double *var_dev, double *cov_dev)
+{
+	if (!h) return fail(SGX_EINVAL, "sgx_cond_2bit_dev: NULL handle");
+	if (h->owner) return fail(SGX_EINVAL, "sgx_cond_2bit_dev: not on a twin");
+	if (M == 0) return SGX_OK;
+	if (!packed_dev || !lut_dev || !score_dev || !var_dev || !cov_dev)
+		return fail(SGX_EINVAL, "sgx_cond_2bit_dev: NULL buffer");
+	if (h->n_cond == 0) return fail(SGX_EINVAL, "sgx_cond_2bit_dev: no conditioning set (sgx_cond_set)");
+	if (bpv % 64 != 0 || bpv < sgx_row_stride(h->md.N))
+		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu, need a multiple of 64 >= %zu",
+			bpv, sgx_row_stride(h->md.N));
+	if (((uintptr_t)packed_dev & 15u) != 0)
+		return fail(SGX_EINVAL, "sgx_cond_2bit_dev: packed_dev must be 16-byte aligned");
+	int rc = set_dev(h);
+	if (rc) return rc;
+	sgx_handle *lane = h->last_issued ? h->last_issued : h;      // behind the most recent call: a scan of the same rows
+	return cond_rows_dev(h, lane, packed_dev, bpv, M, lut_dev, score_dev, var_dev, cov_dev);
+}
+
+extern "C" int sgx_cond_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t M,
+	const double *lut, double *score, double *var, double *cov)
+{
+	if (!h) return fail(SGX_EINVAL, "sgx_cond_2bit: NULL handle");
+	if (h->owner) return fail(SGX_EINVAL, "sgx_cond_2bit: not on a twin");
+	if (M == 0) return SGX_OK;
+	if (!packed || !lut || !score || !var || !cov) return fail(SGX_EINVAL, "sgx_cond_2bit: NULL buffer");
+	if (h->n_cond == 0) return fail(SGX_EINVAL, "sgx_cond_2bit: no conditioning set (sgx_cond_set)");
+	const int N = h->md.N, C = h->n_cond;
+	if (bpv < (size_t)(N + 3) / 4)
+		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
+	int rc = set_dev(h);
+	if (rc) return rc;
+	rc = sync_lane(h);
+	if (rc) return rc;
+	h->last_issued = h;
+
+	// chunks of sgx_skat_2bit's uploads: rows at the device stride, then tables and results
+	const size_t dbpv = sgx_row_stride(N);
+	const size_t rchunk = scan_chunk(h, dbpv, M);
+	const size_t o_lut = rchunk * dbpv, o_s = o_lut + rchunk * 4 * sizeof(double), o_v = o_s + rchunk * sizeof(double),
+		o_c = o_v + rchunk * sizeof(double);
+	rc = grow(h->stage_pk, h->stage_pk_cap, o_c + rchunk * (size_t)C * sizeof(double));
+	if (rc) return rc;
+	double *d_lut = reinterpret_cast<double *>(h->stage_pk + o_lut), *d_s = reinterpret_cast<double *>(h->stage_pk + o_s),
+		*d_v = reinterpret_cast<double *>(h->stage_pk + o_v), *d_c = reinterpret_cast<double *>(h->stage_pk + o_c);
+	for (size_t off = 0; off < M; off += rchunk) {
+		const size_t m = std::min(rchunk, M - off);
+		rc = copy_rows_h2d(h->stage_pk, dbpv, packed + off * bpv, bpv, m, h->stream);
+		if (rc) return rc;
+		HIPCHK(hipMemcpyAsync(d_lut, lut + 4 * off, m * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+		rc = cond_rows_dev(h, h, h->stage_pk, dbpv, m, d_lut, d_s, d_v, d_c);
+		if (rc) return rc;
+		HIPCHK(hipMemcpyAsync(score + off, d_s, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipMemcpyAsync(var + off, d_v, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipMemcpyAsync(cov + off * C, d_c, m * (size_t)C * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
+	}
+	return SGX_OK;
+}

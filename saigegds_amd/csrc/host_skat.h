@@ -150,9 +150,10 @@ static void skat_finish(const DevModel &md, size_t n_units, const int64_t *unit_
 	}
 }
 
-extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t n_variants,
+// sgx_skat_2bit; `dense` keeps the entries' dense sums [entry][2K+1] for a caller that wants them (sgx_cond_set).
+static int skat_2bit_host(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t n_variants,
 	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut,
-	double *score, double *cov)
+	double *score, double *cov, std::vector<double> &dense)
 {
 	if (!h) return fail(SGX_EINVAL, "sgx_skat_2bit: NULL handle");
 	if (n_units == 0) return SGX_OK;
@@ -194,7 +195,6 @@ extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut, (size_t)nnz * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipMemcpyAsync(h->stage_pk + o_til, pl.tiles.data(), T * sizeof(SkatTile), hipMemcpyHostToDevice, h->stream));
 
-	std::vector<double> dense;
 	rc = skat_run(h, pl, n_units, unit_ptr, C, [&](size_t t0, size_t nt) {
 		hipLaunchKernelGGL(skat_gram_kernel, dim3((unsigned)nt, (unsigned)pl.nslab), dim3(64), 0, h->stream,
 			h->stage_pk, dbpv, N, reinterpret_cast<const int *>(h->stage_pk + o_idx),
@@ -204,4 +204,12 @@ extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 	if (rc) return rc;
 	skat_finish(h->md, n_units, unit_ptr, dense, score, cov);
 	return SGX_OK;
+}
+
+extern "C" int sgx_skat_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t n_variants,
+	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut,
+	double *score, double *cov)
+{
+	std::vector<double> dense;
+	return skat_2bit_host(h, packed, bpv, n_variants, n_units, unit_ptr, var_idx, lut, score, cov, dense);
 }

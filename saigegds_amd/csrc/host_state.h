@@ -116,6 +116,13 @@ struct sgx_handle {
 	double *skat_part = nullptr; size_t skat_part_cap = 0;   // sgx_skat_2bit: per-slab partial tiles of a launch
 	double *skat_fin = nullptr; size_t skat_fin_cap = 0;     // ... and its tiles summed over the slabs
 	double *stage_out = nullptr; uint8_t *stage_valid = nullptr; size_t stage_out_cap = 0;
+	// conditional scan (host_cond.h).  Primary: the installed set -- B of kern_cond.h, the set's c' and e sums
+	double *cond_B = nullptr; size_t cond_B_cap = 0;
+	double *cond_ce = nullptr; size_t cond_ce_cap = 0;       // [n_cond][2K]
+	int n_cond = 0;                                          // 0: no set installed
+	// ... every lane: per-slab partial sums of a launch and the rows' sums over the slabs
+	double *cond_part = nullptr; size_t cond_part_cap = 0;
+	double *cond_fin = nullptr; size_t cond_fin_cap = 0;
 	hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
 	hipEvent_t evk[2] = {nullptr, nullptr};    // around the contraction kernel alone (stats.ms_kernel)
 	bool evk_set = false;

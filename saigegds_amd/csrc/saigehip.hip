@@ -76,6 +76,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_quant.h"
 #include "kern_skat.h"
 #include "kern_skat_ds.h"
+#include "kern_cond.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -89,5 +90,6 @@ static int fail(int code, const char *fmt, ...)
 #include "host_burden_ds.h"
 #include "host_skat.h"
 #include "host_skat_ds.h"
+#include "host_cond.h"
 #include "host_util.h"
 #include "host_grm.h"

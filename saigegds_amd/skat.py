@@ -126,10 +126,23 @@ def pchisq_mix(q: float, lam) -> float:
     return float(ndtr(-z))
 
 
+def spa_scale(o, S, var, spa_pval: float) -> np.ndarray:
+    """The SPA scale factors of the covariance of score statistics (binary traits): ``o`` the rows of the scan's table,
+    ``S`` and ``var`` = Phi_jj of the same variants.  Where a variant went through the SPA stage (p.norm <= spa.pval)
+    and it converged with 0 < pval != p.norm and S_j != 0, d_j = S_j^2 / (Phi_jj qchisq(pval_j, 1, upper)), else 1."""
+    from scipy.special import chdtri
+    S, var = np.asarray(S, dtype=np.float64), np.asarray(var, dtype=np.float64)
+    pv, pn, cvg = o[:, 5], o[:, 6], o[:, 7]
+    with np.errstate(invalid="ignore"):
+        adj = (pn <= spa_pval) & (cvg != 0) & (pv > 0) & (pv != pn) & (S != 0)
+    d = np.ones(S.size)
+    d[adj] = S[adj] ** 2 / (var[adj] * chdtri(1.0, pv[adj]))
+    return d
+
+
 def _unit_tests(pr, kept, S_of, phi_of):
     """Step 3 of the flow for every unit: ``kept[u]`` the unit's variants (rows of pr.out / pr.maf), ``S_of(u)`` and
     ``phi_of(u)`` their score statistics and covariance -> (Q, pval), [n_units, n_weights] each."""
-    from scipy.special import chdtri
     nu, nw = len(kept), pr.wbeta.shape[1]
     Q, P = np.full((nu, nw), np.nan), np.full((nu, nw), np.nan)
     for u, r in enumerate(kept):
@@ -138,12 +151,7 @@ def _unit_tests(pr, kept, S_of, phi_of):
         S = np.asarray(S_of(u), dtype=np.float64)
         phi = np.array(phi_of(u), dtype=np.float64)
         if pr.binary:
-            o = pr.out[r]
-            pv, pn, cvg = o[:, 5], o[:, 6], o[:, 7]
-            adj = (pn <= pr.sm.spa_pval) & (cvg != 0) & (pv > 0) & (pv != pn) & (S != 0)
-            d = np.ones(r.size)
-            d[adj] = S[adj] ** 2 / (np.diag(phi)[adj] * chdtri(1.0, pv[adj]))
-            sd = np.sqrt(d)
+            sd = np.sqrt(spa_scale(pr.out[r], S, np.diag(phi), pr.sm.spa_pval))
             phi = phi * sd[:, None] * sd[None, :]
         for i, (a, b) in enumerate(pr.wbeta.T):
             w = _dbeta(pr.maf[r], a, b)
