@@ -374,6 +374,22 @@ int sgx_cond_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_per
  *                       is legal; a unit of more than SGX_SKAT_MAX_VARIANTS entries, an index outside the loaded rows,
  *                       a NULL buffer or a block / handle mismatch returns SGX_EINVAL and launches nothing; the handle
  *                       stays usable.
+ *   sgx_ds_block_cond_set  the conditional scan's sgx_cond_set for conditioning variants that are rows of a loaded
+ *                       block: n_cond (0 .. SGX_COND_MAX) rows var_idx[c] with flip[c] / mean[c] as for
+ *                       sgx_ds_block_skat.  score_c, cov_cc: what sgx_ds_block_skat gives for those entries as one unit,
+ *                       bit for bit (the same functions).  The set lands in the handle state sgx_cond_set fills -- the
+ *                       dense matrix is built on the device from the rows where they lie -- so it outlives the block's
+ *                       next load and serves sgx_cond_2bit* as well; n_cond = 0 clears it.
+ *   sgx_ds_block_cond   sgx_cond_2bit for all resident rows: score[j] = S_j, var[j] = Phi_jj, cov[j * n_cond + c] =
+ *                       Phi_jc of the dosage vector G_j above (flip[j] / mean[j] per resident row), HOST buffers of
+ *                       n_variants loaded rows.  FP64 matrix-core sums in a fixed order (Phi_jj's quadratic term on the
+ *                       vector ALU): no atomics, sample slabs cut by n_samp alone, so what a row gets depends on its own
+ *                       values, its flip / mean and n_samp only -- not on the number of rows, its position in the block or
+ *                       the cut into launches.  A row whose mean is not finite and is used gets non-finite results and
+ *                       leaves the other rows alone.  Nothing crosses PCIe but the tables and the results.
+ *                       Both: a NULL buffer, nothing loaded, an index outside the loaded rows, a twin handle, a block /
+ *                       handle mismatch, or sgx_ds_block_cond with no set installed returns SGX_EINVAL and launches
+ *                       nothing; the handle stays usable.
  * All of them are synchronous; block and handle must be on the same device and have the same n_samp. */
 #define SGX_DS_U8  0
 #define SGX_DS_I32 1
@@ -389,6 +405,10 @@ int  sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const void *raw, in
 	int32_t *n_valid, double *sum, int64_t *sum_trunc);
 int  sgx_ds_block_skat(sgx_handle *h, const sgx_dsblock *b, size_t n_units, const int64_t *unit_ptr,
 	const int32_t *var_idx, const uint8_t *flip, const double *mean, double *score, double *cov);
+int  sgx_ds_block_cond_set(sgx_handle *h, const sgx_dsblock *b, size_t n_cond, const int32_t *var_idx,
+	const uint8_t *flip, const double *mean, double *score_c, double *cov_cc);
+int  sgx_ds_block_cond(sgx_handle *h, const sgx_dsblock *b, const uint8_t *flip, const double *mean,
+	double *score, double *var, double *cov);
 int  sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out8, uint8_t *valid);
 int  sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_groups, const int64_t *grp_ptr,
 	const int32_t *var_idx, const uint8_t *flip, int n_cols, const double *w, const double *mw,

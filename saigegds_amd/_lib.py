@@ -25,7 +25,7 @@ EXPORTS = (
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
     "sgx_quantize_packed",
     "sgx_skat_2bit", "sgx_ds_block_skat",
-    "sgx_cond_set", "sgx_cond_2bit", "sgx_cond_2bit_dev",
+    "sgx_cond_set", "sgx_cond_2bit", "sgx_cond_2bit_dev", "sgx_ds_block_cond_set", "sgx_ds_block_cond",
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
@@ -217,6 +217,10 @@ def load():
     L.sgx_dsblock_burden.argtypes = [vp, vp, sz, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.sgx_ds_block_skat.restype = C.c_int
     L.sgx_ds_block_skat.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.sgx_ds_block_cond_set.restype = C.c_int
+    L.sgx_ds_block_cond_set.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    L.sgx_ds_block_cond.restype = C.c_int
+    L.sgx_ds_block_cond.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.sgx_decode_dbit2.restype = C.c_int
     L.sgx_decode_dbit2.argtypes = [vp, sz, C.c_int32, sz, vp, C.c_int32, vp, sz, C.c_int]
     L.sgx_geno_stats_2bit.restype = C.c_int
@@ -644,6 +648,37 @@ class DosageBlock:
             check(self._L.sgx_ds_block_skat(self._sc._h, self._b, n_units, unit_ptr.ctypes.data, var_idx.ctypes.data,
                                             flip.ctypes.data, mean.ctypes.data, score.ctypes.data, cov.ctypes.data))
         return score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)]
+
+    def cond_set(self, var_idx, flip, mean):
+        """Installs the conditioning set of the conditional scan from resident rows (``sgx_ds_block_cond_set``): 0 to
+        ``COND_MAX`` rows ``var_idx`` with ``flip`` / ``mean`` as for ``skat`` -> (S_C [C], Phi_CC [C, C]), equal to
+        ``skat`` on them as one unit bit for bit.  The scanner keeps the set (as ``Scanner.cond_set`` does) beyond the
+        block's next load; no row clears it."""
+        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        if var_idx.ndim != 1 or flip.shape != var_idx.shape or mean.shape != var_idx.shape:
+            raise ValueError("DosageBlock.cond_set: inconsistent table shapes")
+        c = var_idx.size
+        score, cov = np.zeros(max(1, c)), np.zeros(max(1, c * c))
+        check(self._L.sgx_ds_block_cond_set(self._sc._h, self._b, c, var_idx.ctypes.data, flip.ctypes.data,
+                                            mean.ctypes.data, score.ctypes.data, cov.ctypes.data))
+        self._sc._n_cond = c
+        return score[:c], cov[:c * c].reshape(c, c)
+
+    def cond(self, flip, mean):
+        """Score, variance and covariances with the installed set of every resident row (``flip`` / ``mean`` per
+        resident row; ``sgx_ds_block_cond``) -> (score [m], var [m], cov [m, C])."""
+        m = self.n_variants
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        if flip.shape != (m,) or mean.shape != (m,):
+            raise ValueError("DosageBlock.cond: one flip and one mean per resident row")
+        c = int(getattr(self._sc, "_n_cond", 0))
+        score, var, cov = np.zeros(max(1, m)), np.zeros(max(1, m)), np.zeros(max(1, m * c))
+        check(self._L.sgx_ds_block_cond(self._sc._h, self._b, flip.ctypes.data, mean.ctypes.data, score.ctypes.data,
+                                        var.ctypes.data, cov.ctypes.data))
+        return score[:m], var[:m], cov[:m * c].reshape(m, c)
 
     def close(self):
         if getattr(self, "_b", None):

@@ -29,7 +29,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from ._lib import Scanner
-from .assoc import GenotypeSource, PackedRows, _dsnode, _is_num, _open_source, packed_block_size
+from .assoc import GenotypeSource, PackedRows, _dsnode, _is_num, _open_source, dosage_matrix, dosage_row_reader, match_samples
 from .gds import GdsFile, pack_dosage_2bit, unpack_dosage_2bit
 from .nullmod import ModelError, NullModel, init_nullmod, load_modobj
 
@@ -305,12 +305,7 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
             raise TypeError(f"is.numeric({nm}) is not TRUE")
     mod: NullModel = load_modobj(modobj, verbose)
     src = _open_source(gdsfile, verbose)
-    gsid = [str(s) for s in src.sample_id()]
-    pos = {str(s): i for i, s in enumerate(mod.sample_id)}
-    sel = [i for i, s in enumerate(gsid) if s in pos]
-    if len(sel) != len(mod.sample_id):
-        raise ModelError("Some of sample IDs are not available in the GDS file.")
-    ii = np.array([pos[gsid[i]] for i in sel], dtype=np.int64)
+    gsid, sel, ii = match_samples(src, mod)
     if not isinstance(dsnode, str):
         raise TypeError("is.character(dsnode) is not TRUE")
     node = _dsnode(src, dsnode)
@@ -318,9 +313,7 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
     if isinstance(src, GenotypeSource):
         packed_all, n_all = src.packed, len(gsid)
         if packed_all is None:
-            ds_all = np.asarray(src.dosage)
-            if ds_all.ndim != 2 or ds_all.shape[1] != n_all or ds_all.dtype not in (np.uint8, np.int32, np.float64):
-                raise TypeError("the dosages should be a [variant, sample] matrix of uint8, int32 or float64")
+            ds_all = dosage_matrix(src, n_all)
             ds_dtype = ds_all.dtype
             if ds_dtype != np.float64 and _hard_calls(ds_all):
                 # hard calls: the reference's RAW branch has the same meaning -> the 2-bit path
@@ -337,32 +330,10 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
         if used.size == 0 or used.min() < 1 or used.max() > n_var_all:
             raise ValueError("No variant in the genotypic data set!")
         pr.local = {int(v): k for k, v in enumerate(used)}
-        sel_a = np.asarray(sel, dtype=np.int64)
-        whole = len(sel) == n_all and np.array_equal(sel_a, np.arange(n_all))
-
-        # a packed-real or float32 node goes to the device as stored: the variants are picked here, the samples
+        # a packed-real or float32 node goes to the device as stored: the variants are picked on the host, the samples
         # there.  (An injected scanner -- the tests' CPU stand-in for the device -- has no such load: decoded rows.)
         stored = ds_all is None and scanner_factory is None and src.dosage_raw_class(node) is not None
-
-        def read_stored(v0):         # ... -> PackedRows [len, n_all], the file's samples
-            step = packed_block_size(src.dosage_raw_row_bytes(node))
-            parts, meta = [], None
-            for a in range(int(v0[0]), int(v0[-1]) + 1, step):          # the range in pieces of a bounded size
-                pick = v0[(v0 >= a) & (v0 < a + step)]
-                if pick.size:
-                    raw, *meta = src.dosage_raw_range(node, int(pick[0]), int(pick[-1]) + 1)
-                    parts.append(raw[pick - pick[0]])
-            return PackedRows(np.concatenate(parts), *meta, None if whole else sel_a)
-
-        def read_rows(v0):           # 0-based variant indices, ascending -> [len, n_samp], the model's samples only
-            if stored:
-                return read_stored(v0)
-            if ds_all is not None:
-                rows = ds_all[v0]
-            else:
-                lo = int(v0[0])
-                rows = src.dosage_real_range(node, lo, int(v0[-1]) + 1)[v0 - lo]
-            return np.ascontiguousarray(rows if whole else rows[:, sel_a], dtype=ds_dtype)
+        read_rows = dosage_row_reader(src, node, ds_all, ds_dtype, sel, n_all, stored)
         _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner_factory)
         try:
             _run_dosage(pr, read_rows, ds_dtype, used, kinds, burden_mac, DS_BUDGET if ds_budget is None else ds_budget)

@@ -120,6 +120,56 @@ def _dsnode(src, nm: str) -> str:
     return nm
 
 
+def match_samples(src, mod):
+    """The model's samples in the genotype source -> (the source's sample ids, the indices ``sel`` of the model's
+    samples among them in the source's order, ``ii``: their rows in the model)."""
+    gsid = [str(s) for s in src.sample_id()]
+    pos = {str(s): i for i, s in enumerate(mod.sample_id)}
+    sel = [i for i, s in enumerate(gsid) if s in pos]
+    if len(sel) != len(mod.sample_id):
+        raise ModelError("Some of sample IDs are not available in the GDS file.")
+    ii = np.array([pos[gsid[i]] for i in sel], dtype=np.int64)
+    return gsid, sel, ii
+
+
+def dosage_matrix(src: "GenotypeSource", n_all: int) -> np.ndarray:
+    """The dosages of an in-memory source: a [variant, sample] matrix of uint8, int32 or float64."""
+    ds_all = np.asarray(src.dosage)
+    if ds_all.ndim != 2 or ds_all.shape[1] != n_all or ds_all.dtype not in (np.uint8, np.int32, np.float64):
+        raise TypeError("the dosages should be a [variant, sample] matrix of uint8, int32 or float64")
+    return ds_all
+
+
+def dosage_row_reader(src, node, ds_all, ds_dtype, sel, n_all, stored):
+    """``read_rows(v0)`` of the dosage drivers: 0-based variant indices, ascending -> their rows for the model's
+    samples ``sel``.  ``ds_all``: the matrix of an in-memory source, else the rows are read from ``node`` of the file.
+    ``stored``: a packed-real or float32 node goes to the device as stored -- the variants are picked here, the samples
+    there (``PackedRows`` [len, n_all], the file's samples); else decoded rows [len, n_samp] of ``ds_dtype``."""
+    sel_a = np.asarray(sel, dtype=np.int64)
+    whole = len(sel) == n_all and np.array_equal(sel_a, np.arange(n_all))
+
+    def read_stored(v0):
+        step = packed_block_size(src.dosage_raw_row_bytes(node))
+        parts, meta = [], None
+        for a in range(int(v0[0]), int(v0[-1]) + 1, step):          # the range in pieces of a bounded size
+            pick = v0[(v0 >= a) & (v0 < a + step)]
+            if pick.size:
+                raw, *meta = src.dosage_raw_range(node, int(pick[0]), int(pick[-1]) + 1)
+                parts.append(raw[pick - pick[0]])
+        return PackedRows(np.concatenate(parts), *meta, None if whole else sel_a)
+
+    def read_rows(v0):
+        if stored:
+            return read_stored(v0)
+        if ds_all is not None:
+            rows = ds_all[v0]
+        else:
+            lo = int(v0[0])
+            rows = src.dosage_real_range(node, lo, int(v0[-1]) + 1)[v0 - lo]
+        return np.ascontiguousarray(rows if whole else rows[:, sel_a], dtype=ds_dtype)
+    return read_rows
+
+
 def _pretty(n: int) -> str:
     return f"{n:,}"
 

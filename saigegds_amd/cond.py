@@ -13,6 +13,12 @@ The flow of a call: the conditioning rows are scanned at thresholds 0 / 0 / 1 an
 (``S_C``, ``Phi_CC``); then per block of variants the rows go to the device once, ``sgx_scan_2bit_dev`` makes the
 single-variant table, the dosage tables are built on the device from its ``AF`` column, ``sgx_cond_2bit_dev`` makes
 ``S_j``, ``Phi_jj`` and ``Phi_jC`` of every row, and one download brings everything back.
+
+Dosage input -- a format node such as ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` -- takes the
+resident dosage block of the aggregate drivers (``DosageBlock``): the conditioning rows are loaded into a block of
+their own, scanned and installed from there (``sgx_ds_block_cond_set``); then per batch of rows that fits
+``aggregate.DS_BUDGET`` bytes one load, ``scan()``, and ``cond(flip, mean)`` (``sgx_ds_block_cond``) with the scan's own
+imputation and flip, formed from the load's counts as the SKAT driver forms them.
 """
 from __future__ import annotations
 
@@ -22,7 +28,8 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .assoc import BLOCK_SIZE, GenotypeSource, _is_num, _open_source, _pretty, assemble_result
+from .assoc import (BLOCK_SIZE, GenotypeSource, PackedRows, _dsnode, _is_num, _open_source, _pretty, assemble_result,
+                    dosage_matrix, dosage_row_reader, match_samples)
 from .gds import pack_dosage_2bit, unpack_dosage_2bit
 from .nullmod import ModelError, NullModel, init_nullmod, load_modobj
 from .skat import spa_scale
@@ -94,6 +101,118 @@ def _tables(af, valid):
     return torch.where(valid[:, None], lut, torch.full_like(lut, float("nan"))).contiguous()
 
 
+_NO_DOSAGE = "Conditional analysis on dosage input is not implemented."
+
+
+def _check_set(cond_ids, out_c, valid_c):
+    for k, v in enumerate(cond_ids):
+        if not valid_c[k] or not out_c[k, 1] > 0:
+            raise ValueError(f"`condition`: variant {v!r} has no valid genotype or is monomorphic.")
+
+
+def _scan_hard(sc, src, sel, n_all, n_var, cidx, cond_ids, thresholds):
+    """The hard-call route: 2-bit rows -> (res [n_var, 8 + 3 + C]: the scan table, valid, S_j, Phi_jj, Phi_jC; the
+    set's scan table, S_C, Phi_CC)."""
+    import torch
+    in_mem = isinstance(src, GenotypeSource)
+    n_samp = sel.size
+    all_samples = n_samp == n_all and np.array_equal(sel, np.arange(n_all))
+
+    def read_rows(off: int, end: int) -> np.ndarray:
+        """2-bit rows of variants [off, end) for the model's samples (host decoder)."""
+        if in_mem:
+            blk = src.packed[off:end]
+            return blk if all_samples else pack_dosage_2bit(unpack_dosage_2bit(blk, n_all)[:, sel])
+        return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
+
+    dev = torch.device(getattr(sc, "torch_device", "cuda"))
+    nb = (n_samp + 3) // 4
+
+    # the conditioning set
+    sc.set_thresholds(0.0, 0.0, 1.0, thresholds[3])
+    rows_c = np.ascontiguousarray(np.concatenate([read_rows(i, i + 1)[:, :nb] for i in cidx]))
+    out_c, valid_c = sc.scan_2bit(rows_c)
+    _check_set(cond_ids, out_c, valid_c)
+    lut_c = _tables(torch.from_numpy(out_c[:, 0].copy()), torch.ones(len(cidx), dtype=torch.bool)).numpy()
+    S_C, Phi_CC = sc.cond_set(rows_c, lut_c)
+    sc.set_thresholds(*thresholds)
+
+    # the scan, by blocks
+    C = len(cidx)
+    stride = sc.row_stride()
+    res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
+    for off in range(0, n_var, BLOCK_SIZE):
+        end = min(n_var, off + BLOCK_SIZE)
+        m = end - off
+        host = np.zeros((m, stride), dtype=np.uint8)
+        host[:, :nb] = read_rows(off, end)[:, :nb]
+        rows = torch.from_numpy(host).to(dev)                       # the one upload
+        out8 = torch.empty((m, 8), dtype=torch.float64, device=dev)
+        valid = torch.zeros(m, dtype=torch.uint8, device=dev)
+        score, var = (torch.empty(m, dtype=torch.float64, device=dev) for _ in range(2))
+        cov = torch.empty((m, C), dtype=torch.float64, device=dev)
+        if dev.type == "cuda":
+            torch.cuda.synchronize()
+        sc.scan_2bit_dev(rows.data_ptr(), stride, m, out8.data_ptr(), valid.data_ptr())
+        sc.sync()
+        lut = _tables(out8[:, 0], valid != 0)
+        if dev.type == "cuda":
+            torch.cuda.synchronize()
+        sc.cond_2bit_dev(rows.data_ptr(), stride, m, lut.data_ptr(), score.data_ptr(), var.data_ptr(), cov.data_ptr())
+        sc.sync()
+        res[off:end] = torch.cat([out8, valid.to(torch.float64)[:, None], score[:, None], var[:, None], cov],
+                                 dim=1).cpu().numpy()              # the one download
+    return res, out_c, S_C, Phi_CC
+
+
+def _flip_mean(n, s):
+    """The scan's own imputation and flip from a load's counts (n non-missing, s their double sum), as the SKAT
+    driver forms them: flip = s > n, mean = s / n or 2 - s / n."""
+    n = n.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = s / n
+    fl = s > n
+    return fl.astype(np.uint8), np.where(fl, 2 - m, m)
+
+
+def _scan_dosage(sc, read_rows, ds_dtype, n_samp, n_var, cidx, cond_ids, thresholds):
+    """The dosage route: what ``_scan_hard`` returns, from resident dosage blocks."""
+    from . import aggregate
+
+    def load(blk, v0):
+        rows = read_rows(v0)
+        return blk.load_packed(*rows.args()) if isinstance(rows, PackedRows) else blk.load(rows)
+
+    make = getattr(sc, "dosage_block", None)
+    if make is None:
+        raise NotImplementedError(_NO_DOSAGE)
+    C = len(cidx)
+    order = np.argsort(cidx)                           # the readers take ascending indices
+    rank = np.argsort(order).astype(np.int32)          # conditioning variant k is row rank[k] of its block
+    with make(ds_dtype, C) as blk:
+        if not hasattr(blk, "cond"):
+            raise NotImplementedError(_NO_DOSAGE)
+        sc.set_thresholds(0.0, 0.0, 1.0, thresholds[3])
+        n, s, _ = load(blk, np.asarray(cidx, dtype=np.int64)[order])
+        out_c, valid_c = blk.scan()
+        out_c, valid_c = out_c[rank], valid_c[rank]
+        _check_set(cond_ids, out_c, valid_c)
+        fl, mean = _flip_mean(n, s)
+        S_C, Phi_CC = blk.cond_set(rank, fl[rank], mean[rank])
+        sc.set_thresholds(*thresholds)
+    row_bytes = n_samp * (1 if np.dtype(ds_dtype) == np.uint8 else 8)
+    per = int(max(1, min(n_var, aggregate.DS_BUDGET // row_bytes)))
+    res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
+    with make(ds_dtype, per) as blk:
+        for off in range(0, n_var, per):
+            end = min(n_var, off + per)
+            n, s, _ = load(blk, np.arange(off, end, dtype=np.int64))      # the one upload
+            out8, valid = blk.scan()
+            score, var, cov = blk.cond(*_flip_mean(n, s))
+            res[off:end, :8], res[off:end, 8], res[off:end, 9], res[off:end, 10], res[off:end, 11:] = out8, valid, score, var, cov
+    return res, out_c, S_C, Phi_CC
+
+
 def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("nan"), mac: float = 10,
                           missing: float = 0.1, spa_pval: float = 0.05, var_ratio: float = float("nan"),
                           res_savefn: str = "", res_compress: str = "LZMA", verbose: bool = True, dsnode: str = "",
@@ -101,7 +220,9 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     """Single-variant scan of every variant given the variants ``condition`` (not in the reference).
 
     ``condition``: 1 to 16 distinct values of the file's ``variant.id`` (of ``GenotypeSource.variant_id``); the other
-    arguments as ``seqAssocGLMM_SPA``.  Hard calls only (``genotype/data`` or an in-memory source of packed rows); one GPU.
+    arguments as ``seqAssocGLMM_SPA``.  Hard calls (``genotype/data`` or an in-memory source of packed rows) or dosages
+    (a non-empty ``dsnode``, a file without ``genotype/data`` -- then ``annotation/format/DS`` --, or an in-memory source
+    of uint8 / int32 / float64 dosages); one GPU.
 
     The conditioning variants are scanned at thresholds 0 / 0 / 1; each must be valid with mac > 0.  Binary traits:
     ``Phi`` is scaled by the SPA factors ``d_j`` of ``seqAssocGLMM_spaSKAT`` (scanned rows and conditioning variants
@@ -133,8 +254,9 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     mod: NullModel = load_modobj(modobj, verbose)
     src = _open_source(gdsfile, verbose)
     in_mem = isinstance(src, GenotypeSource)
-    if dsnode != "" or (in_mem and src.packed is None) or (not in_mem and src.node("genotype/data", silent=True) is None):
-        raise NotImplementedError("Conditional analysis on dosage input is not implemented.")
+    if dsnode != "" and in_mem and src.packed is not None:
+        raise NotImplementedError(_NO_DOSAGE)
+    dosage = dsnode != "" or (in_mem and src.packed is None) or (not in_mem and src.node("genotype/data", silent=True) is None)
     vid = np.asarray(src.variant_id if in_mem else src.read("variant.id"))
     where = {v: i for i, v in enumerate(vid.tolist())}
     unknown = [v for v in cond_ids if v not in where]
@@ -142,21 +264,22 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
         raise ValueError(f"`condition`: no variant with id {unknown[0]!r}.")
     cidx = [where[v] for v in cond_ids]
 
-    # sample matching, as seqAssocGLMM_SPA
-    gsid = [str(s) for s in src.sample_id()]
-    pos = {str(s): i for i, s in enumerate(mod.sample_id)}
-    sel = [i for i, s in enumerate(gsid) if s in pos]
-    if len(sel) != len(mod.sample_id):
-        raise ModelError("Some of sample IDs are not available in the GDS file.")
-    ii = np.array([pos[gsid[i]] for i in sel], dtype=np.int64)
+    gsid, sel, ii = match_samples(src, mod)                    # as seqAssocGLMM_SPA
     sel = np.asarray(sel, dtype=np.int64)
     n_samp, n_all = sel.size, len(gsid)
-    n_var = src.packed.shape[0] if in_mem else src.genotype_dims()[0]
+    ds_all = node = None
+    if not dosage:
+        n_var = src.packed.shape[0] if in_mem else src.genotype_dims()[0]
+    elif in_mem:
+        ds_all = dosage_matrix(src, n_all)
+        n_var = ds_all.shape[0]
+    else:
+        node = _dsnode(src, dsnode)
+        n_var = src.node(node + "/data").dims[0]
     if n_samp <= 0:
         raise ValueError("No sample in the genotypic data set!")
     if n_var <= 0:
         raise ValueError("No variant in the genotypic data set!")
-    all_samples = n_samp == n_all and np.array_equal(sel, np.arange(n_all))
     if not math.isfinite(var_ratio):
         var_ratio = float(np.nanmean(mod.var_ratio))
     if verbose:
@@ -164,18 +287,11 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
         print(f"    # of variants: {_pretty(n_var)}")
         print(f"    # of conditioning variants: {len(cidx)}")
 
-    def read_rows(off: int, end: int) -> np.ndarray:
-        """2-bit rows of variants [off, end) for the model's samples (host decoder)."""
-        if in_mem:
-            blk = src.packed[off:end]
-            return blk if all_samples else pack_dosage_2bit(unpack_dosage_2bit(blk, n_all)[:, sel])
-        return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
-
-    import torch
     mobj = init_nullmod(mod, ii, maf, mac, missing, spa_pval, var_ratio)
     if mod.trait_type not in ("binary", "quantitative"):
         raise ModelError("Invalid 'modobj$trait.type'.")
     binary = mod.trait_type == "binary"
+    stored = dosage and ds_all is None and scanner_factory is None and src.dosage_raw_class(node) is not None
     if scanner_factory is None:
         from ._lib import Scanner, load
         if load().sgx_device_count() <= 0:
@@ -183,45 +299,13 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
         scanner_factory = Scanner
     sc = scanner_factory(mobj)
     try:
-        dev = torch.device(getattr(sc, "torch_device", "cuda"))
-        nb = (n_samp + 3) // 4
-
-        # the conditioning set
-        sc.set_thresholds(0.0, 0.0, 1.0, float(spa_pval))
-        rows_c = np.ascontiguousarray(np.concatenate([read_rows(i, i + 1)[:, :nb] for i in cidx]))
-        out_c, valid_c = sc.scan_2bit(rows_c)
-        for k, v in enumerate(cond_ids):
-            if not valid_c[k] or not out_c[k, 1] > 0:
-                raise ValueError(f"`condition`: variant {v!r} has no valid genotype or is monomorphic.")
-        lut_c = _tables(torch.from_numpy(out_c[:, 0].copy()), torch.ones(len(cidx), dtype=torch.bool)).numpy()
-        S_C, Phi_CC = sc.cond_set(rows_c, lut_c)
-        sc.set_thresholds(float(maf), float(mac), float(missing), float(spa_pval))
-
-        # the scan, by blocks
-        C = len(cidx)
-        stride = sc.row_stride()
-        res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
-        for off in range(0, n_var, BLOCK_SIZE):
-            end = min(n_var, off + BLOCK_SIZE)
-            m = end - off
-            host = np.zeros((m, stride), dtype=np.uint8)
-            host[:, :nb] = read_rows(off, end)[:, :nb]
-            rows = torch.from_numpy(host).to(dev)                       # the one upload
-            out8 = torch.empty((m, 8), dtype=torch.float64, device=dev)
-            valid = torch.zeros(m, dtype=torch.uint8, device=dev)
-            score, var = (torch.empty(m, dtype=torch.float64, device=dev) for _ in range(2))
-            cov = torch.empty((m, C), dtype=torch.float64, device=dev)
-            if dev.type == "cuda":
-                torch.cuda.synchronize()
-            sc.scan_2bit_dev(rows.data_ptr(), stride, m, out8.data_ptr(), valid.data_ptr())
-            sc.sync()
-            lut = _tables(out8[:, 0], valid != 0)
-            if dev.type == "cuda":
-                torch.cuda.synchronize()
-            sc.cond_2bit_dev(rows.data_ptr(), stride, m, lut.data_ptr(), score.data_ptr(), var.data_ptr(), cov.data_ptr())
-            sc.sync()
-            res[off:end] = torch.cat([out8, valid.to(torch.float64)[:, None], score[:, None], var[:, None], cov],
-                                     dim=1).cpu().numpy()              # the one download
+        thresholds = (float(maf), float(mac), float(missing), float(spa_pval))
+        if dosage:
+            ds_dtype = np.dtype(np.float64) if ds_all is None else ds_all.dtype
+            read_rows = dosage_row_reader(src, node, ds_all, ds_dtype, sel, n_all, stored)
+            res, out_c, S_C, Phi_CC = _scan_dosage(sc, read_rows, ds_dtype, n_samp, n_var, cidx, cond_ids, thresholds)
+        else:
+            res, out_c, S_C, Phi_CC = _scan_hard(sc, src, sel, n_all, n_var, cidx, cond_ids, thresholds)
     finally:
         sc.close()
 

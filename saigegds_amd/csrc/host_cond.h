@@ -57,14 +57,16 @@ extern "C" int sgx_cond_set(sgx_handle *h, const uint8_t *packed_c, size_t bpv, 
 	return SGX_OK;
 }
 
-// Rows in device memory -> score / var / cov in device memory, queued on lane->stream: the rows in launches whose
-// per-slab sums fit COND_PART_BYTES (what a row gets does not depend on the cut), each followed by the slab sum and
-// the finish.  p: the primary handle, which holds the set.
-static int cond_rows_dev(sgx_handle *p, sgx_handle *lane, const uint8_t *rows, size_t bpv, size_t M,
-	const double *lut, double *score, double *var, double *cov)
+// M rows -> score / var / cov in device memory, queued on lane->stream: the rows in launches whose per-slab sums fit
+// COND_PART_BYTES (what a row gets does not depend on the cut), each followed by the slab sum and the finish.
+// rect(nct, grid, off, m) queues the rectangular kernel of rows [off, off + m) with nct column tiles
+// (std::integral_constant) into lane->cond_part; slab_ch: the chunks of 256 samples of its sample slabs.  p: the primary
+// handle, which holds the set.
+template <class Rect>
+static int cond_run(sgx_handle *p, sgx_handle *lane, size_t M, int slab_ch, Rect rect, double *score, double *var, double *cov)
 {
 	const int N = p->md.N, C = p->n_cond, NCT = (cond_ncol(p) + 15) / 16, WD = 16 * NCT + 1;
-	const int nslab = ((N + 255) / 256 + COND_SLAB_CH - 1) / COND_SLAB_CH;
+	const int nslab = ((N + 255) / 256 + slab_ch - 1) / slab_ch;
 	size_t mchunk = COND_PART_BYTES / ((size_t)nslab * WD * sizeof(double));
 	mchunk = std::min(M, std::max<size_t>(COND_WG_ROWS, mchunk / COND_WG_ROWS * COND_WG_ROWS));
 	int rc = ensure_buf(lane, &lane->cond_part, &lane->cond_part_cap, mchunk * nslab * WD);
@@ -72,18 +74,16 @@ static int cond_rows_dev(sgx_handle *p, sgx_handle *lane, const uint8_t *rows, s
 	rc = ensure_buf(lane, &lane->cond_fin, &lane->cond_fin_cap, mchunk * WD);
 	if (rc) return rc;
 	hipStream_t st = lane->stream;
+	using std::integral_constant;
 	for (size_t off = 0; off < M; off += mchunk) {
 		const size_t m = std::min(mchunk, M - off);
 		const dim3 grid((unsigned)((m + COND_WG_ROWS - 1) / COND_WG_ROWS), (unsigned)nslab);
-#define SGX_COND_RECT(n) hipLaunchKernelGGL(cond_rect_kernel<n>, grid, dim3(256), 0, st, rows + off * bpv, bpv, N, m, \
-			lut + 4 * off, p->dF, p->md.P, p->cond_B, COND_SLAB_CH, lane->cond_part)
 		switch (NCT) {
-		case 1: SGX_COND_RECT(1); break;
-		case 2: SGX_COND_RECT(2); break;
-		case 3: SGX_COND_RECT(3); break;
-		default: SGX_COND_RECT(4); break;
+		case 1: rect(integral_constant<int, 1>{}, grid, off, m); break;
+		case 2: rect(integral_constant<int, 2>{}, grid, off, m); break;
+		case 3: rect(integral_constant<int, 3>{}, grid, off, m); break;
+		default: rect(integral_constant<int, 4>{}, grid, off, m); break;
 		}
-#undef SGX_COND_RECT
 		HIPCHK(hipGetLastError());
 		const size_t nel = m * WD;
 		hipLaunchKernelGGL(skat_reduce_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st,
@@ -94,6 +94,16 @@ static int cond_rows_dev(sgx_handle *p, sgx_handle *lane, const uint8_t *rows, s
 		HIPCHK(hipGetLastError());
 	}
 	return SGX_OK;
+}
+
+// 2-bit rows in device memory through cond_run.
+static int cond_rows_dev(sgx_handle *p, sgx_handle *lane, const uint8_t *rows, size_t bpv, size_t M,
+	const double *lut, double *score, double *var, double *cov)
+{
+	return cond_run(p, lane, M, COND_SLAB_CH, [&](auto nct, dim3 grid, size_t off, size_t m) {
+		hipLaunchKernelGGL(cond_rect_kernel<decltype(nct)::value>, grid, dim3(256), 0, lane->stream, rows + off * bpv, bpv,
+			p->md.N, m, lut + 4 * off, p->dF, p->md.P, p->cond_B, COND_SLAB_CH, lane->cond_part);
+	}, score, var, cov);
 }
 
 extern "C" int sgx_cond_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bpv, size_t M,

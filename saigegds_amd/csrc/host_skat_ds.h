@@ -5,8 +5,10 @@
 
 static const int SKAT_DS_SLAB = 4096;       // samples per sample slab (a multiple of 64): cut by N alone
 
-extern "C" int sgx_ds_block_skat(sgx_handle *h, const sgx_dsblock *b, size_t n_units, const int64_t *unit_ptr,
-	const int32_t *var_idx, const uint8_t *flip, const double *mean, double *score, double *cov)
+// sgx_ds_block_skat; `dense` keeps the entries' dense sums [entry][2K+1] for a caller that wants them
+// (sgx_ds_block_cond_set).
+static int skat_ds_block_host(sgx_handle *h, const sgx_dsblock *b, size_t n_units, const int64_t *unit_ptr,
+	const int32_t *var_idx, const uint8_t *flip, const double *mean, double *score, double *cov, std::vector<double> &dense)
 {
 	int rc = dsblock_check(h, b, "sgx_ds_block_skat");
 	if (rc) return rc;
@@ -44,7 +46,6 @@ extern "C" int sgx_ds_block_skat(sgx_handle *h, const sgx_dsblock *b, size_t n_u
 	const double *d_mean = reinterpret_cast<const double *>(b->tabs + o_mean);
 	const SkatTile *d_til = reinterpret_cast<const SkatTile *>(b->tabs + o_til);
 	const uint8_t *d_flip = b->tabs + o_flip;
-	std::vector<double> dense;
 	rc = skat_run(h, pl, n_units, unit_ptr, C, [&](size_t t0, size_t nt) {
 		const dim3 grid((unsigned)nt, (unsigned)pl.nslab);
 		if (b->dtype == SGX_DS_U8)
@@ -57,4 +58,11 @@ extern "C" int sgx_ds_block_skat(sgx_handle *h, const sgx_dsblock *b, size_t n_u
 	if (rc) return rc;
 	skat_finish(h->md, n_units, unit_ptr, dense, score, cov);
 	return SGX_OK;
+}
+
+extern "C" int sgx_ds_block_skat(sgx_handle *h, const sgx_dsblock *b, size_t n_units, const int64_t *unit_ptr,
+	const int32_t *var_idx, const uint8_t *flip, const double *mean, double *score, double *cov)
+{
+	std::vector<double> dense;
+	return skat_ds_block_host(h, b, n_units, unit_ptr, var_idx, flip, mean, score, cov, dense);
 }

@@ -77,6 +77,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_skat.h"
 #include "kern_skat_ds.h"
 #include "kern_cond.h"
+#include "kern_cond_ds.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -91,5 +92,6 @@ static int fail(int code, const char *fmt, ...)
 #include "host_skat.h"
 #include "host_skat_ds.h"
 #include "host_cond.h"
+#include "host_cond_ds.h"
 #include "host_util.h"
 #include "host_grm.h"
