@@ -529,6 +529,33 @@ int  sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size_t ldb, in
 int  sgx_grm_pcg_multi(sgx_grm *g, const double *w, const double *tau, const double *B, size_t ldb, int k,
 	int maxiter, double tol, double *X, int *iters);
 
+/* Leave-one-group-out columns (LOCO: a variant of chromosome c is tested against a null model whose GRM
+ * leaves out the markers of c).  A handle takes one group id per marker; column j of a *_loco call then works
+ * on the GRM of the markers outside group excl[j] (-1: of all markers): G_c'(G_c b)/(M - M_c), with the
+ * matching diagonal.  The packed genotypes are swept once for all columns of a call, whatever they leave out.
+ *   sgx_grm_set_groups     group[n_markers]: 0 <= id < n_groups <= SGX_GRM_MAX_GROUPS, in any order (groups
+ *                          need not be contiguous, and may be empty); a second call replaces the first
+ *   sgx_grm_group_sizes    sizes_out[n_groups]: markers per group
+ *   sgx_grm_diag_loco      diag of the GRM without group excl: (sum over the other groups, in ascending
+ *                          order, of their sums of squares) / (M - M_excl); excl = -1: sgx_grm_diag
+ *   sgx_grm_crossprod_loco column j = GRM_{-excl[j]} B[:, j]; with excl[j] = -1 the bits of
+ *                          sgx_grm_crossprod_multi
+ *   sgx_grm_pcg_loco       column j solves (tau0 diag(1/w_j) + tau1 GRM_{-excl[j]}) x = B[:, j] with
+ *                          w_j = row w_idx[j] of W ([n_w][ldw], 1 <= n_w <= SGX_GRM_MAX_RHS, ldw >= N) and the
+ *                          preconditioner of its own w_j and diagonal; columns run in lockstep and stop
+ *                          as in sgx_grm_pcg_multi, whose bits a call with one w and excl = -1 gives
+ * A column's result depends only on its own b, w and excl: not on the other columns of the call, its
+ * position among them, or k.  k and ldb as above.  SGX_EINVAL: excl[j] >= 0 before sgx_grm_set_groups,
+ * excl[j] >= n_groups, or a group that holds every marker (nothing is left).  Excluding an empty group is
+ * excluding nothing. */
+#define SGX_GRM_MAX_GROUPS 64
+int  sgx_grm_set_groups(sgx_grm *g, const int32_t *group, int n_groups);
+int  sgx_grm_group_sizes(sgx_grm *g, int64_t *sizes_out);
+int  sgx_grm_diag_loco(sgx_grm *g, int excl, double *diag_out);
+int  sgx_grm_crossprod_loco(sgx_grm *g, const double *B, size_t ldb, int k, const int *excl, double *Out);
+int  sgx_grm_pcg_loco(sgx_grm *g, const double *W, size_t ldw, int n_w, const int *w_idx, const double *tau,
+	const double *B, size_t ldb, int k, const int *excl, int maxiter, double tol, double *X, int *iters);
+
 #ifdef __cplusplus
 }
 #endif

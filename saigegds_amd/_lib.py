@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Optional
 
 import numpy as np
 
@@ -20,6 +21,7 @@ EXPORTS = (
     "sgx_sync", "sgx_get_stats", "sgx_get_stats_total", "sgx_row_stride", "sgx_synth_2bit_dev", "sgx_selftest", "sgx_set_option",
     "sgx_grm_init", "sgx_grm_init_dev", "sgx_grm_crossprod_dev", "sgx_grm_sync", "sgx_grm_free", "sgx_grm_diag", "sgx_grm_crossprod", "sgx_grm_pcg",
     "sgx_grm_crossprod_multi", "sgx_grm_crossprod_multi_dev", "sgx_grm_pcg_multi",
+    "sgx_grm_set_groups", "sgx_grm_group_sizes", "sgx_grm_diag_loco", "sgx_grm_crossprod_loco", "sgx_grm_pcg_loco",
     "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
     "sgx_scan_packed", "sgx_ds_block_load_packed",
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
@@ -29,6 +31,7 @@ EXPORTS = (
 )
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
+GRM_MAX_GROUPS = 64   # SGX_GRM_MAX_GROUPS: marker groups of one GRM handle
 SKAT_MAX_VARIANTS = 4096   # SGX_SKAT_MAX_VARIANTS: entries of one unit of sgx_skat_2bit
 COND_MAX = 16         # SGX_COND_MAX: conditioning variants of one sgx_cond_set
 DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
@@ -261,6 +264,16 @@ def load():
     L.sgx_grm_crossprod_multi_dev.argtypes = [vp, vp, sz, C.c_int, vp]
     L.sgx_grm_pcg_multi.restype = C.c_int
     L.sgx_grm_pcg_multi.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int, dp, vp, vp]
+    L.sgx_grm_set_groups.restype = C.c_int
+    L.sgx_grm_set_groups.argtypes = [vp, vp, C.c_int]
+    L.sgx_grm_group_sizes.restype = C.c_int
+    L.sgx_grm_group_sizes.argtypes = [vp, vp]
+    L.sgx_grm_diag_loco.restype = C.c_int
+    L.sgx_grm_diag_loco.argtypes = [vp, C.c_int, vp]
+    L.sgx_grm_crossprod_loco.restype = C.c_int
+    L.sgx_grm_crossprod_loco.argtypes = [vp, vp, sz, C.c_int, vp, vp]
+    L.sgx_grm_pcg_loco.restype = C.c_int
+    L.sgx_grm_pcg_loco.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, sz, C.c_int, vp, C.c_int, dp, vp, vp]
     _lib = L
     return L
 
@@ -878,4 +891,70 @@ class GrmOperator:
             k = min(GRM_MAX_RHS, B.shape[0] - j0)
             check(self._L.sgx_grm_pcg_multi(self._h, w.ctypes.data, tau.ctypes.data, B[j0].ctypes.data, self.n, k,
                                             int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
+        return X, iters
+
+    # -- marker groups; a column of a *_loco call leaves one group out (excl[j], -1: none)
+    def set_groups(self, group, n_groups: Optional[int] = None):
+        """One group id per marker (0 <= id < n_groups <= GRM_MAX_GROUPS, any order, groups may be empty);
+        n_groups defaults to max(group) + 1."""
+        g = np.ascontiguousarray(np.clip(np.asarray(group, dtype=np.int64), -1, np.iinfo(np.int32).max), dtype=np.int32)
+        if g.shape != (self.m,):
+            raise ValueError("group must have one entry per marker")
+        if n_groups is None:
+            n_groups = int(g.max()) + 1
+        check(self._L.sgx_grm_set_groups(self._h, g.ctypes.data, int(n_groups)))
+        self.n_groups = int(n_groups)
+
+    def group_sizes(self) -> np.ndarray:
+        out = np.zeros(GRM_MAX_GROUPS, dtype=np.int64)
+        check(self._L.sgx_grm_group_sizes(self._h, out.ctypes.data))
+        return out[:getattr(self, "n_groups", 0)].copy()
+
+    def diag_loco(self, excl: int) -> np.ndarray:
+        """diag of the GRM of the markers outside group excl (-1: diag())."""
+        out = np.empty(self.n, dtype=np.float64)
+        check(self._L.sgx_grm_diag_loco(self._h, int(excl), out.ctypes.data))
+        return out
+
+    def _excl(self, excl, k: int) -> np.ndarray:
+        e = np.ascontiguousarray(np.clip(np.asarray(excl, dtype=np.int64), -2, np.iinfo(np.int32).max), dtype=np.int32)
+        if e.shape != (k,):
+            raise ValueError("excl must name one group (or -1) per row of B")
+        return e
+
+    def crossprod_loco(self, B: np.ndarray, excl) -> np.ndarray:
+        """Row j: the GRM of the markers outside group excl[j] times B[j] ([k, N] -> [k, N]).  A row's result
+        depends only on its own b and excl; with excl[j] = -1 it is crossprod(B[j]) bit for bit."""
+        B = self._rhs(B)
+        e = self._excl(excl, B.shape[0])
+        out = np.empty_like(B)
+        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
+            k = min(GRM_MAX_RHS, B.shape[0] - j0)
+            check(self._L.sgx_grm_crossprod_loco(self._h, B[j0].ctypes.data, self.n, k, e[j0:].ctypes.data,
+                                                 out[j0].ctypes.data))
+        return out
+
+    def pcg_loco(self, W: np.ndarray, w_idx, tau, B: np.ndarray, excl, maxiter: int = 500, tol: float = 1e-5):
+        """pcg on every row of B in lockstep, row j with the weights W[w_idx[j]] ([n_w, N]) on the GRM of the
+        markers outside group excl[j] -> (X [k, N], iters [k]).  A row's result depends only on its own b, w
+        and excl; one w and excl = -1 give pcg_many's bits."""
+        B = self._rhs(B)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.n or W.shape[0] < 1:
+            raise ValueError("W must be [n_w, N]: one weight vector of N samples per row")
+        wi = np.asarray(w_idx, dtype=np.int64)
+        if wi.shape != (B.shape[0],) or (wi.size and (wi.min() < 0 or wi.max() >= W.shape[0])):
+            raise ValueError("w_idx must name one row of W per row of B")
+        e = self._excl(excl, B.shape[0])
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        X = np.empty_like(B)
+        iters = np.zeros(B.shape[0], dtype=np.int32)
+        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
+            k = min(GRM_MAX_RHS, B.shape[0] - j0)
+            rows, loc = np.unique(wi[j0:j0 + k], return_inverse=True)     # the weight rows this batch uses
+            Wb = np.ascontiguousarray(W[rows])
+            loc = np.ascontiguousarray(loc, dtype=np.int32)
+            check(self._L.sgx_grm_pcg_loco(self._h, Wb.ctypes.data, self.n, int(rows.size), loc.ctypes.data,
+                                           tau.ctypes.data, B[j0].ctypes.data, self.n, k, e[j0:].ctypes.data,
+                                           int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
         return X, iters

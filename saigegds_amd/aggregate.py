@@ -31,7 +31,7 @@ import numpy as np
 from ._lib import Scanner
 from .assoc import GenotypeSource, PackedRows, _dsnode, _is_num, _open_source, dosage_matrix, dosage_row_reader, match_samples
 from .gds import GdsFile, pack_dosage_2bit, unpack_dosage_2bit
-from .nullmod import ModelError, NullModel, init_nullmod, load_modobj
+from .nullmod import ModelError, NullModel, init_nullmod, load_modobj, no_loco
 
 # AggrParamBeta, R/assoc_aggregate.r:18-19: columns (shape1, shape2) = (1,1) and (1,25)
 AggrParamBeta = np.array([[1.0, 1.0], [1.0, 25.0]]).T     # [2, n_weights]
@@ -304,6 +304,7 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
         if not _is_num(v):
             raise TypeError(f"is.numeric({nm}) is not TRUE")
     mod: NullModel = load_modobj(modobj, verbose)
+    no_loco(mod, what.rstrip(":"))
     src = _open_source(gdsfile, verbose)
     gsid, sel, ii = match_samples(src, mod)
     if not isinstance(dsnode, str):

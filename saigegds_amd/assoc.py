@@ -297,9 +297,27 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         bl_size = packed_block_size(src.dosage_raw_row_bytes(node))
     elif kind == "packed" and not isinstance(src, GenotypeSource) and GENOTYPE_DECODE == "device":
         bl_size = packed_block_size(src.genotype_raw_row_bytes())      # a stored row is twice a 2-bit row
-    blocks = [(off, min(n_var, off + bl_size)) for off in range(0, n_var, bl_size)]
     t_loop = time.perf_counter()
-    scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, read_block, kind == "packed", out, valid, timing)
+    if not mod.loco:
+        blocks = [(off, min(n_var, off + bl_size)) for off in range(0, n_var, bl_size)]
+        scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, read_block, kind == "packed", out, valid, timing)
+    else:
+        # leave-one-chromosome-out: the block list is cut at chromosome boundaries, and every run of one
+        # chromosome is scanned against that chromosome's model (its fitted values; y, V, XV, XXVX_inv and
+        # the variance ratio are the full model's) by scanners of its own, freed before the next run
+        chrom = [str(c) for c in (src.chromosome if isinstance(src, GenotypeSource) else src.read("chromosome"))]
+        reported = set()
+        for r0, r1, ch in chromosome_runs(chrom):
+            if ch in mod.loco:
+                run_obj = init_nullmod(mod.for_chromosome(ch), ii, maf, mac, missing, spa_pval, var_ratio)
+            else:
+                run_obj = mobj
+                if verbose and ch not in reported:
+                    print(f"    chromosome '{ch}' has no leave-one-chromosome-out model: the full model is used")
+                reported.add(ch)
+            blocks = [(off, min(r1, off + bl_size)) for off in range(r0, r1, bl_size)]
+            scan_blocks(lambda d, o=run_obj: Scanner(o, device=d), ngpu, blocks, read_block, kind == "packed", out, valid,
+                        timing)
     if timing is not None:
         timing["blocks_s"] = time.perf_counter() - t_loop      # handles + every block (decode and scan overlapped)
 
@@ -320,6 +338,17 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     if verbose:
         print("Done.")
     return ans
+
+
+def chromosome_runs(chrom):
+    """Maximal runs of equal consecutive values -> [(start, end, value)]."""
+    runs = []
+    for i, c in enumerate(chrom):
+        if runs and runs[-1][2] == c:
+            runs[-1][1] = i + 1
+        else:
+            runs.append([i, i + 1, c])
+    return [tuple(r) for r in runs]
 
 
 def scan_blocks(make_scanner, ngpu: int, blocks, read_block, packed_rows: bool, out: np.ndarray, valid: np.ndarray,

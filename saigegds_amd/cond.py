@@ -31,7 +31,7 @@ import numpy as np
 from .assoc import (BLOCK_SIZE, GenotypeSource, PackedRows, _dsnode, _is_num, _open_source, _pretty, assemble_result,
                     dosage_matrix, dosage_row_reader, match_samples)
 from .gds import pack_dosage_2bit, unpack_dosage_2bit
-from .nullmod import ModelError, NullModel, init_nullmod, load_modobj
+from .nullmod import ModelError, NullModel, init_nullmod, load_modobj, no_loco
 from .skat import spa_scale
 
 COND_MAX = 16             # SGX_COND_MAX: conditioning variants of one call
@@ -252,6 +252,7 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     if verbose:
         print("SAIGE conditional association analysis:")
     mod: NullModel = load_modobj(modobj, verbose)
+    no_loco(mod, "seqAssocGLMM_SPA_cond")
     src = _open_source(gdsfile, verbose)
     in_mem = isinstance(src, GenotypeSource)
     if dsnode != "" and in_mem and src.packed is not None:

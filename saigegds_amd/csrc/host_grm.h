@@ -30,8 +30,16 @@ struct sgx_grm {
 	int kcap = 0;                          // columns the [k][N] vectors below have room for (the largest k seen)
 	double *B = nullptr, *O = nullptr;               // [k][N] staging of host-pointer calls
 	double *R = nullptr, *Z = nullptr, *P = nullptr, *X = nullptr, *AP = nullptr, *GP = nullptr;   // [k][N]
+	// marker groups (sgx_grm_set_groups): a column of a *_loco call leaves one group out
+	int n_groups = 0;
+	int *grp = nullptr;                    // [M] group id per marker
+	size_t gsize[GRM_MAX_GROUPS] = {};     // markers per group
+	double *diagx = nullptr;               // [1 + n_groups][N]: row 0 = diag, row 1 + c = diag(GRM without group c)
+	int kcap_w = 0;                        // columns Wc / Mc have room for
+	double *Wc = nullptr, *Mc = nullptr;   // [k][N]: weight rows and per-column minv of sgx_grm_pcg_loco
 };
 static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
+static_assert(GRM_MAX_GROUPS == SGX_GRM_MAX_GROUPS, "kern_grm.h and saigehip.h disagree on the group limit");
 
 // room for k columns (k <= GRM_MAX_RHS) in the [k][N] vectors
 static hipError_t grm_reserve(sgx_grm *g, int k)
@@ -48,13 +56,28 @@ static hipError_t grm_reserve(sgx_grm *g, int k)
 	return hipSuccess;
 }
 
+// room for k columns in the per-column weights and preconditioners
+static hipError_t grm_reserve_w(sgx_grm *g, int k)
+{
+	if (k <= g->kcap_w) return hipSuccess;
+	g->kcap_w = 0;
+	for (double **p : {&g->Wc, &g->Mc}) {
+		hipError_t e = *p ? hipFree(*p) : hipSuccess;
+		*p = nullptr;
+		if (e == hipSuccess) e = hipMalloc((void **)p, (size_t)k * g->N * sizeof(double));
+		if (e != hipSuccess) return e;
+	}
+	g->kcap_w = k;
+	return hipSuccess;
+}
+
 extern "C" void sgx_grm_free(sgx_grm *g)
 {
 	if (!g) return;
 	(void)hipSetDevice(g->device);
 	if (g->stream) (void)hipStreamSynchronize(g->stream);
 	void *ptrs[] = {g->G, g->Gt, g->af, g->inv, g->l0, g->diag, g->FlN, g->FlM, g->accV, g->accS, g->xv, g->gv,
-		g->maxb, g->part, g->minv, g->w, g->B, g->O, g->R, g->Z, g->P, g->X, g->AP, g->GP};
+		g->maxb, g->part, g->minv, g->w, g->B, g->O, g->R, g->Z, g->P, g->X, g->AP, g->GP, g->grp, g->diagx, g->Wc, g->Mc};
 	for (void *p : ptrs) (void)hipFree(p);
 	if (g->h_part) (void)hipHostFree(g->h_part);
 	if (g->stream) (void)hipStreamDestroy(g->stream);
@@ -205,7 +228,10 @@ static void grm_contract(sgx_grm *g, int nbfv, const uint8_t *packed, size_t bpv
 // Out[:, c] = G'(G B[:, c])/M for c in cols (columns at base + c * ld), device vectors
 // (get_crossprod_b_grm, saige_fitnull.cpp:435-536).  A column's result does not depend on the other
 // columns of the call: its limbs, its exact integer sums and its reductions are its own.
-static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols &cols, double *Out, size_t ldo)
+// excl (NULL: the whole GRM, the plain kernels): excl[c] is the marker group column c leaves out, -1 for none
+// (checked by grm_excl_args).  Only the two epilogues differ: the contraction and the limb steps are the same.
+static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols &cols, double *Out, size_t ldo,
+	const int *excl = nullptr)
 {
 	hipStream_t st = g->stream;
 	const size_t N = (size_t)g->N, M = g->M;
@@ -217,7 +243,8 @@ static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols
 		GrmCols gc{};
 		gc.n = std::min(GRM_GROUP, cols.n - g0);
 		GrmScal sb{};
-		for (int y = 0; y < gc.n; y++) { gc.c[y] = cols.c[g0 + y]; sb.v[y] = sum_b[g0 + y]; }
+		GrmIdx ex{};
+		for (int y = 0; y < gc.n; y++) { gc.c[y] = cols.c[g0 + y]; sb.v[y] = sum_b[g0 + y]; ex.v[y] = excl ? excl[gc.c[y]] : -1; }
 		// ---- pass 1: per marker, over samples; column y in fragment y / 2, limbs 7 (y % 2) ..
 		const int nb1 = (gc.n + 1) / 2;
 		HIPCHK(hipMemsetAsync(g->maxb, 0, (size_t)gc.n * 3 * sizeof(unsigned long long), st));
@@ -227,8 +254,12 @@ static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols
 			16 * nb1, 2, 0, g->maxb, 0, g->FlN);
 		HIPCHK(hipMemsetAsync(g->accV, 0, M * 32 * nb1 * sizeof(int), st));
 		grm_contract(g, nb1, g->G, g->bpvN, (int)M, g->FlN, g->ntileN, g->accV);
-		hipLaunchKernelGGL(grm_dot_epilogue, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, g->accV, g->maxb, sb,
-			g->af, g->inv, g->l0, g->xv, g->gv, g->part);
+		if (excl)
+			hipLaunchKernelGGL(grm_dot_epilogue<true>, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, g->accV, g->maxb, sb,
+				g->af, g->inv, g->l0, g->xv, g->gv, g->part, g->grp, ex);
+		else
+			hipLaunchKernelGGL(grm_dot_epilogue<false>, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, g->accV, g->maxb, sb,
+				g->af, g->inv, g->l0, g->xv, g->gv, g->part, g->grp, ex);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipMemcpyAsync(g->h_part, g->part, (size_t)gc.n * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
@@ -247,8 +278,13 @@ static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols
 		for (int s0 = 0; s0 < gc.n; s0 += GRM_GROUP2) {
 			GrmCols sc{}, oc{};
 			sc.n = oc.n = std::min(GRM_GROUP2, gc.n - s0);
-			GrmScal c0s{};
-			for (int y = 0; y < sc.n; y++) { sc.c[y] = s0 + y; oc.c[y] = gc.c[s0 + y]; c0s.v[y] = C0.v[s0 + y]; }
+			GrmScal c0s{}, msub{};
+			GrmIdx ex2{};
+			for (int y = 0; y < sc.n; y++) {
+				sc.c[y] = s0 + y; oc.c[y] = gc.c[s0 + y]; c0s.v[y] = C0.v[s0 + y];
+				ex2.v[y] = ex.v[s0 + y];
+				msub.v[y] = (double)(M - (ex2.v[y] >= 0 ? g->gsize[ex2.v[y]] : 0));
+			}
 			const int nb2 = sc.n;
 			const unsigned long long *mb = g->maxb + 3 * s0;
 			HIPCHK(hipMemsetAsync(g->FlM, 0, (size_t)g->ntileM * 16 * (16 * nb2) * 16, st));
@@ -258,8 +294,12 @@ static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols
 				16 * nb2, 1, MF_NLIMB, mb, 2, g->FlM);
 			HIPCHK(hipMemsetAsync(g->accS, 0, N * 32 * nb2 * sizeof(int), st));
 			grm_contract(g, nb2, g->Gt, g->bpvM, g->N, g->FlM, g->ntileM, g->accS);
-			hipLaunchKernelGGL(grm_out_epilogue, dim3((unsigned)((N + 255) / 256), sc.n), bl, 0, st, g->N, M, nb2,
-				g->accS, mb, c0s, g->diag, Out, ldo, oc);
+			if (excl)      // (no groups on the handle: every excl is -1 and only row 0 of the table is read)
+				hipLaunchKernelGGL(grm_out_epilogue<true>, dim3((unsigned)((N + 255) / 256), sc.n), bl, 0, st, g->N, M, nb2,
+					g->accS, mb, c0s, g->diagx ? g->diagx : g->diag, Out, ldo, oc, msub, ex2);
+			else
+				hipLaunchKernelGGL(grm_out_epilogue<false>, dim3((unsigned)((N + 255) / 256), sc.n), bl, 0, st, g->N, M, nb2,
+					g->accS, mb, c0s, g->diag, Out, ldo, oc, msub, ex2);
 			HIPCHK(hipGetLastError());
 		}
 	}
@@ -293,13 +333,13 @@ static hipError_t grm_copy_cols(sgx_grm *g, double *dst, const double *src, size
 }
 
 // Out = GRM B for k host vectors, column j at B + j * ldb (and Out + j * ldb)
-static int grm_crossprod_run(sgx_grm *g, const double *B, size_t ldb, int k, double *Out)
+static int grm_crossprod_run(sgx_grm *g, const double *B, size_t ldb, int k, double *Out, const int *excl = nullptr)
 {
 	HIPCHK(hipSetDevice(g->device));
 	HIPCHK(grm_reserve(g, k));
 	const size_t N = (size_t)g->N;
 	HIPCHK(grm_copy_cols(g, g->B, B, ldb, k, hipMemcpyHostToDevice));
-	int rc = grm_matvec_dev(g, g->B, N, grm_cols_iota(k), g->O, N);
+	int rc = grm_matvec_dev(g, g->B, N, grm_cols_iota(k), g->O, N, excl);
 	if (rc) return rc;
 	HIPCHK(grm_copy_cols(g, Out, g->O, ldb, k, hipMemcpyDeviceToHost));
 	HIPCHK(hipStreamSynchronize(g->stream));
@@ -340,8 +380,15 @@ extern "C" int sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size
 // sides in lockstep (host vectors, column j at B + j * ldb): every column takes the reference's steps on
 // its own scalars; a column stops (and leaves the products) once rr <= tol or maxiter is reached.  Each
 // reduction step is one host sync for all columns.
+// lo (NULL: one w and the whole GRM for all columns, the plain kernels): column j has the weights lo->W row
+// lo->w_idx[j] (w is not read), leaves out group lo->excl[j], and is preconditioned with its own diagonal.
+struct GrmLoco {
+	const double *W; size_t ldw; int n_w;
+	const int *w_idx, *excl;               // [k], checked (grm_excl_args)
+};
+
 static int grm_pcg_run(sgx_grm *g, const double *w, const double *tau, const double *B, size_t ldb, int k,
-	int maxiter, double tol, double *X_out, int *iters)
+	int maxiter, double tol, double *X_out, int *iters, const GrmLoco *lo = nullptr)
 {
 	HIPCHK(hipSetDevice(g->device));
 	HIPCHK(grm_reserve(g, k));
@@ -351,11 +398,21 @@ static int grm_pcg_run(sgx_grm *g, const double *w, const double *tau, const dou
 	const dim3 bl(256);
 	const unsigned gx = (unsigned)((n + 255) / 256);
 	const double tau0 = tau[0], tau1 = tau[1];
-	HIPCHK(hipMemcpyAsync(g->w, w, nb, hipMemcpyHostToDevice, st));
-	HIPCHK(grm_copy_cols(g, g->B, B, ldb, k, hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(pcg_minv_kernel, dim3(gx), bl, 0, st, n, g->w, g->diag, tau0, tau1, g->minv);
 	const GrmCols all = grm_cols_iota(k);
-	hipLaunchKernelGGL(pcg_init_kernel, dim3(gx, k), bl, 0, st, n, g->B, N, g->minv, g->R, g->Z, g->P, g->X, all);
+	GrmIdx widx{}, ex{};
+	HIPCHK(grm_copy_cols(g, g->B, B, ldb, k, hipMemcpyHostToDevice));
+	if (lo) {
+		HIPCHK(grm_reserve_w(g, std::max(k, lo->n_w)));
+		HIPCHK(grm_copy_cols(g, g->Wc, lo->W, lo->ldw, lo->n_w, hipMemcpyHostToDevice));
+		for (int j = 0; j < k; j++) { widx.v[j] = lo->w_idx[j]; ex.v[j] = lo->excl[j]; }
+		hipLaunchKernelGGL(pcg_minv_cols_kernel, dim3(gx, k), bl, 0, st, n, g->Wc, widx, g->diagx ? g->diagx : g->diag, ex,
+			tau0, tau1, g->Mc, all);
+		hipLaunchKernelGGL(pcg_init_kernel<true>, dim3(gx, k), bl, 0, st, n, g->B, N, g->Mc, g->R, g->Z, g->P, g->X, all);
+	} else {
+		HIPCHK(hipMemcpyAsync(g->w, w, nb, hipMemcpyHostToDevice, st));
+		hipLaunchKernelGGL(pcg_minv_kernel, dim3(gx), bl, 0, st, n, g->w, g->diag, tau0, tau1, g->minv);
+		hipLaunchKernelGGL(pcg_init_kernel<false>, dim3(gx, k), bl, 0, st, n, g->B, N, g->minv, g->R, g->Z, g->P, g->X, all);
+	}
 	double rr[GRM_MAX_RHS], rz[GRM_MAX_RHS];
 	int rc;
 	if ((rc = grm_sum(g, g->R, g->R, N, all, rr, g->R, g->Z, N, &all, rz))) return rc;
@@ -368,15 +425,17 @@ static int grm_pcg_run(sgx_grm *g, const double *w, const double *tau, const dou
 		for (int y = 0; y < act.n; y++) iters[act.c[y]]++;
 		const double *gp = nullptr;
 		if (tau1 != 0) {                       // get_crossprod :569-575
-			if ((rc = grm_matvec_dev(g, g->P, N, act, g->GP, N))) return rc;
+			if ((rc = grm_matvec_dev(g, g->P, N, act, g->GP, N, lo ? lo->excl : nullptr))) return rc;
 			gp = g->GP;
 		}
-		hipLaunchKernelGGL(pcg_ap_kernel, dim3(gx, act.n), bl, 0, st, n, g->P, g->w, gp, tau0, tau1, g->AP, act);
+		if (lo) hipLaunchKernelGGL(pcg_ap_kernel<true>, dim3(gx, act.n), bl, 0, st, n, g->P, g->Wc, gp, tau0, tau1, g->AP, act, widx);
+		else hipLaunchKernelGGL(pcg_ap_kernel<false>, dim3(gx, act.n), bl, 0, st, n, g->P, g->w, gp, tau0, tau1, g->AP, act, widx);
 		double pAp[GRM_MAX_RHS], rz1[GRM_MAX_RHS], rrn[GRM_MAX_RHS];
 		if ((rc = grm_sum(g, g->P, g->AP, N, act, pAp))) return rc;
 		GrmScal a{};
 		for (int y = 0; y < act.n; y++) a.v[y] = rz[act.c[y]] / pAp[y];
-		hipLaunchKernelGGL(pcg_update_kernel, dim3(gx, act.n), bl, 0, st, n, a, g->P, g->AP, g->minv, g->X, g->R, g->Z, act);
+		if (lo) hipLaunchKernelGGL(pcg_update_kernel<true>, dim3(gx, act.n), bl, 0, st, n, a, g->P, g->AP, g->Mc, g->X, g->R, g->Z, act);
+		else hipLaunchKernelGGL(pcg_update_kernel<false>, dim3(gx, act.n), bl, 0, st, n, a, g->P, g->AP, g->minv, g->X, g->R, g->Z, act);
 		if ((rc = grm_sum(g, g->Z, g->R, N, act, rz1, g->R, g->R, N, &act, rrn))) return rc;
 		GrmScal bet{};
 		for (int y = 0; y < act.n; y++) bet.v[y] = rz1[y] / rz[act.c[y]];
@@ -407,4 +466,114 @@ extern "C" int sgx_grm_pcg_multi(sgx_grm *g, const double *w, const double *tau,
 	int rc = grm_multi_args("sgx_grm_pcg_multi", g, B, ldb, k, X_out);
 	if (rc) return rc;
 	return grm_pcg_run(g, w, tau, B, ldb, k, maxiter, tol, X_out, iters);
+}
+
+// ===========================================================================
+// Marker groups and leave-one-group-out columns (LOCO: a variant of chromosome c is tested against a null
+// model whose GRM leaves out the markers of c).  Column j of a *_loco call works on the GRM of the markers
+// outside group excl[j]: pass 1 zeroes the excluded markers' dot products, pass 2 divides by M - M_excl, and
+// the diagonal is the matching one.  The genotype sweeps are shared by all columns of a call.
+
+extern "C" int sgx_grm_set_groups(sgx_grm *g, const int32_t *group, int n_groups)
+{
+	if (!g || !group) return fail(SGX_EINVAL, "sgx_grm_set_groups: NULL argument");
+	if (n_groups < 1 || n_groups > SGX_GRM_MAX_GROUPS)
+		return fail(SGX_EINVAL, "sgx_grm_set_groups: n_groups=%d outside 1..%d", n_groups, SGX_GRM_MAX_GROUPS);
+	const size_t N = (size_t)g->N, M = g->M;
+	size_t sizes[GRM_MAX_GROUPS] = {};
+	for (size_t v = 0; v < M; v++) {
+		if (group[v] < 0 || group[v] >= n_groups)
+			return fail(SGX_EINVAL, "sgx_grm_set_groups: group[%zu]=%d outside 0..%d", v, (int)group[v], n_groups - 1);
+		sizes[group[v]]++;
+	}
+	HIPCHK(hipSetDevice(g->device));
+	hipStream_t st = g->stream;
+	HIPCHK(hipStreamSynchronize(st));
+	g->n_groups = 0;                       // (no groups until the new tables are complete)
+	if (!g->grp) HIPCHK(hipMalloc((void **)&g->grp, M * sizeof(int)));
+	if (g->diagx) { HIPCHK(hipFree(g->diagx)); g->diagx = nullptr; }
+	HIPCHK(hipMalloc((void **)&g->diagx, (size_t)(1 + n_groups) * N * sizeof(double)));
+	double *S = nullptr, *msub = nullptr;
+	double h_msub[GRM_MAX_GROUPS];
+	for (int c = 0; c < n_groups; c++) h_msub[c] = (double)(M - sizes[c]);
+	hipError_t e = hipMalloc((void **)&S, (size_t)n_groups * N * sizeof(double));
+	if (e == hipSuccess) e = hipMalloc((void **)&msub, GRM_MAX_GROUPS * sizeof(double));
+	if (e == hipSuccess) e = hipMemcpyAsync(g->grp, group, M * sizeof(int), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(msub, h_msub, (size_t)n_groups * sizeof(double), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(grm_diag_groups_kernel, dim3((unsigned)N), dim3(WAVE), (size_t)n_groups * WAVE * sizeof(double), st,
+			g->Gt, g->bpvM, g->N, M, g->inv, g->l0, g->grp, n_groups, S);
+		hipLaunchKernelGGL(grm_diag_excl_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g->N, n_groups, S, msub,
+			g->diag, g->diagx);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	(void)hipFree(S);
+	(void)hipFree(msub);
+	HIPCHK(e);
+	for (int c = 0; c < GRM_MAX_GROUPS; c++) g->gsize[c] = sizes[c];
+	g->n_groups = n_groups;
+	return SGX_OK;
+}
+
+extern "C" int sgx_grm_group_sizes(sgx_grm *g, int64_t *sizes_out)
+{
+	if (!g || !sizes_out) return fail(SGX_EINVAL, "sgx_grm_group_sizes: NULL argument");
+	if (g->n_groups == 0) return fail(SGX_EINVAL, "sgx_grm_group_sizes: no marker groups (sgx_grm_set_groups)");
+	for (int c = 0; c < g->n_groups; c++) sizes_out[c] = (int64_t)g->gsize[c];
+	return SGX_OK;
+}
+
+// excl[k] of a *_loco call -> out[k]: checked, and an empty group (excluding it is excluding nothing) as -1
+static int grm_excl_args(const char *fn, sgx_grm *g, const int *excl, int k, int *out)
+{
+	if (!excl) return fail(SGX_EINVAL, "%s: NULL argument", fn);
+	for (int j = 0; j < k; j++) {
+		const int c = excl[j];
+		if (c < -1) return fail(SGX_EINVAL, "%s: excl[%d]=%d (a group, or -1 for none)", fn, j, c);
+		if (c >= 0 && g->n_groups == 0) return fail(SGX_EINVAL, "%s: excl[%d]=%d before sgx_grm_set_groups", fn, j, c);
+		if (c >= g->n_groups && c >= 0) return fail(SGX_EINVAL, "%s: excl[%d]=%d outside -1..%d", fn, j, c, g->n_groups - 1);
+		if (c >= 0 && g->gsize[c] == g->M)
+			return fail(SGX_EINVAL, "%s: excl[%d]=%d leaves no marker (the group holds all %zu)", fn, j, c, g->M);
+		out[j] = (c >= 0 && g->gsize[c] == 0) ? -1 : c;
+	}
+	return SGX_OK;
+}
+
+extern "C" int sgx_grm_diag_loco(sgx_grm *g, int excl, double *diag_out)
+{
+	if (!g || !diag_out) return fail(SGX_EINVAL, "sgx_grm_diag_loco: NULL argument");
+	int ex = -1;
+	int rc = grm_excl_args("sgx_grm_diag_loco", g, &excl, 1, &ex);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(g->device));
+	const double *src = ex < 0 ? g->diag : g->diagx + (size_t)(1 + ex) * g->N;
+	HIPCHK(hipMemcpy(diag_out, src, (size_t)g->N * sizeof(double), hipMemcpyDeviceToHost));
+	return SGX_OK;
+}
+
+extern "C" int sgx_grm_crossprod_loco(sgx_grm *g, const double *B, size_t ldb, int k, const int *excl, double *Out)
+{
+	int rc = grm_multi_args("sgx_grm_crossprod_loco", g, B, ldb, k, Out);
+	if (rc) return rc;
+	int ex[GRM_MAX_RHS];
+	if ((rc = grm_excl_args("sgx_grm_crossprod_loco", g, excl, k, ex))) return rc;
+	return grm_crossprod_run(g, B, ldb, k, Out, ex);
+}
+
+extern "C" int sgx_grm_pcg_loco(sgx_grm *g, const double *W, size_t ldw, int n_w, const int *w_idx, const double *tau,
+	const double *B, size_t ldb, int k, const int *excl, int maxiter, double tol, double *X_out, int *iters)
+{
+	if (!W || !w_idx || !tau || !iters) return fail(SGX_EINVAL, "sgx_grm_pcg_loco: NULL argument");
+	int rc = grm_multi_args("sgx_grm_pcg_loco", g, B, ldb, k, X_out);
+	if (rc) return rc;
+	if (n_w < 1 || n_w > SGX_GRM_MAX_RHS) return fail(SGX_EINVAL, "sgx_grm_pcg_loco: n_w=%d outside 1..%d", n_w, SGX_GRM_MAX_RHS);
+	if (ldw < (size_t)g->N) return fail(SGX_EINVAL, "sgx_grm_pcg_loco: ldw=%zu < N=%d", ldw, g->N);
+	for (int j = 0; j < k; j++)
+		if (w_idx[j] < 0 || w_idx[j] >= n_w)
+			return fail(SGX_EINVAL, "sgx_grm_pcg_loco: w_idx[%d]=%d outside 0..%d", j, w_idx[j], n_w - 1);
+	int ex[GRM_MAX_RHS];
+	if ((rc = grm_excl_args("sgx_grm_pcg_loco", g, excl, k, ex))) return rc;
+	const GrmLoco lo{W, ldw, n_w, w_idx, ex};
+	return grm_pcg_run(g, nullptr, tau, B, ldb, k, maxiter, tol, X_out, iters, &lo);
 }

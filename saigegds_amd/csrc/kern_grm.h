@@ -42,6 +42,12 @@ struct GrmScal {              // one double per column of a launch (by value)
 	double v[GRM_MAX_RHS];
 };
 
+#define GRM_MAX_GROUPS 64     /* SGX_GRM_MAX_GROUPS: marker groups of a handle (leave-one-group-out columns) */
+
+struct GrmIdx {               // one index per column of a launch (by value): excluded group (-1: none), weight row
+	int v[GRM_MAX_RHS];
+};
+
 // ---- per-marker statistics: af, inv, l0  (:181-203); one workgroup per marker
 __global__ void __launch_bounds__(256)
 grm_marker_stats(const uint8_t *__restrict__ packed, size_t bpv, int N, size_t M,
@@ -130,6 +136,66 @@ grm_diag_kernel(const uint8_t *__restrict__ gt, size_t bpvM, int N, size_t M,
 	}
 	s = wave_sum(s);
 	if (lane == 0) diag[i] = s / (double)M;
+}
+
+// ---- diag(GRM) by marker group: S[c][i] = sum over the markers v of group c of lut_v[code_vi]^2; one wave
+// (= one workgroup) per sample on the sample-major matrix, addressed as grm_diag_kernel.  A lane keeps the sum of
+// its current run of one group in a register and adds it to its own LDS slot acc[c][lane] when the group
+// changes; the lanes' slots are then summed by wave_sum.  The order of every sum is fixed by the group layout
+// alone.  LDS: ngroups * WAVE doubles.
+__global__ void __launch_bounds__(WAVE)
+grm_diag_groups_kernel(const uint8_t *__restrict__ gt, size_t bpvM, int N, size_t M,
+	const double *__restrict__ inv, const double *__restrict__ l0, const int *__restrict__ grp, int ngroups,
+	double *__restrict__ S)
+{
+	extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+	double *acc = reinterpret_cast<double *>(smem);      // [ngroups][WAVE]
+	const int lane = threadIdx.x;
+	const int i = blockIdx.x;
+	if (i >= N) return;
+	for (int c = 0; c < ngroups; c++) acc[c * WAVE + lane] = 0;
+	const uint32_t *row = reinterpret_cast<const uint32_t *>(gt + (size_t)i * bpvM);
+	const size_t ndw = (M + 15) >> 4;
+	double s = 0;
+	int cur = -1;
+	for (size_t d = lane; d < ndw; d += WAVE) {
+		const uint32_t w = row[d];
+		for (int k = 0; k < 16; k++) {
+			const size_t v = d * 16 + k;
+			if (v >= M) break;
+			const int c = grp[v];
+			if (c != cur) {
+				if (cur >= 0) acc[cur * WAVE + lane] += s;
+				s = 0; cur = c;
+			}
+			const uint32_t code = (w >> (2 * k)) & 3u;
+			const double g = (code == 3u) ? 0.0 : fma((double)code, inv[v], l0[v]);
+			s = fma(g, g, s);
+		}
+	}
+	if (cur >= 0) acc[cur * WAVE + lane] += s;
+	for (int c = 0; c < ngroups; c++) {
+		const double t = wave_sum(acc[c * WAVE + lane]);
+		if (lane == 0) S[(size_t)c * N + i] = t;
+	}
+}
+
+// diag_excl[c][i] = (sum over c' != c of S[c'][i], ascending c') / (M - M_c) -> D row 1 + c; row 0 is the
+// diagonal of the whole GRM (excl = -1).  Every term is non-negative: nothing cancels when one group holds
+// most markers.  A group that holds every marker has no complement: its row is 0 and is never used.
+__global__ void __launch_bounds__(256)
+grm_diag_excl_kernel(int N, int ngroups, const double *__restrict__ S, const double *__restrict__ msub,
+	const double *__restrict__ diag, double *__restrict__ D)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= N) return;
+	D[i] = diag[i];
+	for (int c = 0; c < ngroups; c++) {
+		double t = 0;
+		for (int c2 = 0; c2 < ngroups; c2++)
+			if (c2 != c) t += S[(size_t)c2 * N + i];
+		D[(size_t)(1 + c) * N + i] = (msub[c] > 0) ? t / msub[c] : 0.0;
+	}
 }
 
 // ---- the contraction: acc[row][..] += sum over samples of (code, [code == 3]) x limb columns
@@ -369,14 +435,18 @@ dot_partial_kernel(const double *__restrict__ A, const double *__restrict__ B, s
 // ---- pass-1 epilogue: dot_v -> x_v, gam_v, and the C0 partial sums, per column y of a pass-1 launch
 // with nbfv fragments (two columns per fragment); x_v, gam_v -> XV / GV row y (stride M),
 // C0 partials -> c0_partial[y * gridDim.x + blockIdx.x]
+// LOCO: column y leaves out the markers of group excl.v[y] (-1: none): they get x_v = gam_v = 0 and no C0
+// term, so pass 2 never sees them; every other marker's values are those of the plain form, bit for bit.
+template <bool LOCO>
 __global__ void __launch_bounds__(256)
 grm_dot_epilogue(size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
 	GrmScal sum_b, const double *__restrict__ af, const double *__restrict__ inv,
 	const double *__restrict__ l0, double *__restrict__ XV, double *__restrict__ GV,
-	double *__restrict__ c0_partial)
+	double *__restrict__ c0_partial, const int *__restrict__ grp, GrmIdx excl)
 {
 	__shared__ double sh[4];
 	const int y = blockIdx.y;
+	const int ex = LOCO ? excl.v[y] : -1;
 	const int stride = 32 * nbfv, col = 16 * (y >> 1) + MF_NLIMB * (y & 1);
 	const int e = limb_scale(maxb[3 * y]);
 	const double sb = sum_b.v[y];
@@ -390,6 +460,9 @@ grm_dot_epilogue(size_t M, int nbfv, const int *__restrict__ acc, const unsigned
 		const double vw = ldexp(hl_to_double(hl_axpy(-3, T3, V)), -e);     // sum over codes 1,2 of code*b
 		const double dot = l0[v] * (sb - t3) + inv[v] * vw;
 		const double x = dot * inv[v];
+		if constexpr (LOCO) {
+			if (ex >= 0 && grp[v] == ex) { xv[v] = 0; gv[v] = 0; continue; }
+		}
 		xv[v] = x;
 		gv[v] = (3 - 2 * af[v]) * x;
 		c0[0] = fma(dot, l0[v], c0[0]);
@@ -403,16 +476,20 @@ grm_dot_epilogue(size_t M, int nbfv, const int *__restrict__ acc, const unsigned
 // marker: diag_i == 0, a sum of squares) has out_i = 0 as a sum of zero terms, and the reference's
 // loop gives exactly that; C0 + X_i - Gam_i only cancels to rounding level there.  0 * v keeps a
 // NaN or infinity of b visible, as 0 * dot does in the reference (:507-519).
-__device__ __forceinline__ double grm_out_value(double C0, double X, double G, size_t M, double diag_i)
+__device__ __forceinline__ double grm_out_value(double C0, double X, double G, double M, double diag_i)
 {
-	const double v = (C0 + X - G) / (double)M;
+	const double v = (C0 + X - G) / M;
 	return (diag_i == 0) ? 0 * v : v;
 }
 
 // per column y of a pass-2 launch with nbfv fragments (one column per fragment: x limbs 0.., gam limbs 7..)
+// LOCO: the divisor is the column's own marker count msub.v[y] = M - M_excl, and the diag_i == 0 rule reads the
+// column's own diagonal, row 1 + excl.v[y] of diag ([1 + groups][N]; row 0: the whole GRM)
+template <bool LOCO>
 __global__ void __launch_bounds__(256)
 grm_out_epilogue(int N, size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
-	GrmScal C0, const double *__restrict__ diag, double *__restrict__ Out, size_t ldo, GrmCols cols)
+	GrmScal C0, const double *__restrict__ diag, double *__restrict__ Out, size_t ldo, GrmCols cols,
+	GrmScal msub, GrmIdx excl)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	const int y = blockIdx.y;
@@ -421,10 +498,13 @@ grm_out_epilogue(int N, size_t M, int nbfv, const int *__restrict__ acc, const u
 	const int *a = acc + (size_t)i * (32 * nbfv) + 16 * y;
 	const double X = ldexp(hl_to_double(mf_limbs(a)), -ex);                            // code plane x x limbs
 	const double G = ldexp(hl_to_double(mf_limbs(a + 16 * nbfv + MF_NLIMB)), -eg);     // missing plane x gam limbs
-	Out[(size_t)cols.c[y] * ldo + i] = grm_out_value(C0.v[y], X, G, M, diag[i]);
+	const double m = LOCO ? msub.v[y] : (double)M;
+	const double di = LOCO ? diag[(size_t)(1 + excl.v[y]) * N + i] : diag[i];
+	Out[(size_t)cols.c[y] * ldo + i] = grm_out_value(C0.v[y], X, G, m, di);
 }
 
-// ---- vector kernels of PCG_diag_sigma (:581-614); w and minv are shared by the columns
+// ---- vector kernels of PCG_diag_sigma (:581-614); w and minv are shared by the columns, or (PERCOL) column c
+// has its own: weights W row widx.v[c], minv row c
 // minv = 1 / max(tau0/w + tau1*diag, 1e-4)   (get_diag_sigma :542-559)
 __global__ void pcg_minv_kernel(int n, const double *w, const double *diag, double tau0, double tau1, double *minv)
 {
@@ -435,7 +515,20 @@ __global__ void pcg_minv_kernel(int n, const double *w, const double *diag, doub
 	minv[i] = 1 / v;
 }
 
+// the same per column c of cols: w = W row widx.v[c], diag = row 1 + excl.v[c] of D ([1 + groups][n]) -> Minv row c
+__global__ void pcg_minv_cols_kernel(int n, const double *W, GrmIdx widx, const double *D, GrmIdx excl,
+	double tau0, double tau1, double *Minv, GrmCols cols)
+{
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const size_t c = (size_t)cols.c[blockIdx.y];
+	double v = tau0 / W[(size_t)widx.v[c] * n + i] + tau1 * D[(size_t)(1 + excl.v[c]) * n + i];
+	if (v < 1e-4) v = 1e-4;
+	Minv[c * n + i] = 1 / v;
+}
+
 // r = b, z = minv*r, p = z, x = 0
+template <bool PERCOL>
 __global__ void pcg_init_kernel(int n, const double *B, size_t ldb, const double *minv,
 	double *R, double *Z, double *P, double *X, GrmCols cols)
 {
@@ -443,21 +536,24 @@ __global__ void pcg_init_kernel(int n, const double *B, size_t ldb, const double
 	if (i >= n) return;
 	const size_t c = (size_t)cols.c[blockIdx.y], o = c * n + i;
 	const double ri = B[c * ldb + i];
-	R[o] = ri; Z[o] = minv[i] * ri; P[o] = Z[o]; X[o] = 0;
+	R[o] = ri; Z[o] = minv[PERCOL ? o : (size_t)i] * ri; P[o] = Z[o]; X[o] = 0;
 }
 
 // Ap = tau0 * p / w + tau1 * gp   (get_crossprod :564-576); GP may be NULL when tau1 == 0
+template <bool PERCOL>
 __global__ void pcg_ap_kernel(int n, const double *P, const double *w, const double *GP, double tau0, double tau1,
-	double *AP, GrmCols cols)
+	double *AP, GrmCols cols, GrmIdx widx)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	const size_t o = (size_t)cols.c[blockIdx.y] * n + i;
-	const double base = tau0 * (P[o] * (1 / w[i]));
+	const size_t wi = PERCOL ? (size_t)widx.v[cols.c[blockIdx.y]] * n + i : (size_t)i;
+	const double base = tau0 * (P[o] * (1 / w[wi]));
 	AP[o] = GP ? base + tau1 * GP[o] : base;
 }
 
 // x += a p; r -= a Ap; z = minv r   (a per column)
+template <bool PERCOL>
 __global__ void pcg_update_kernel(int n, GrmScal a, const double *P, const double *AP, const double *minv,
 	double *X, double *R, double *Z, GrmCols cols)
 {
@@ -467,7 +563,7 @@ __global__ void pcg_update_kernel(int n, GrmScal a, const double *P, const doubl
 	const double ai = a.v[blockIdx.y];
 	X[o] += ai * P[o];
 	const double ri = R[o] - ai * AP[o];
-	R[o] = ri; Z[o] = minv[i] * ri;
+	R[o] = ri; Z[o] = minv[PERCOL ? o : (size_t)i] * ri;
 }
 
 // p = z + bet p   (bet per column)

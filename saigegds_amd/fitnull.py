@@ -217,31 +217,76 @@ class _Fitter:
         else:
             Sigma_iY = self.pcg(w, tau, Y)
             Sigma_iX = np.column_stack([self.pcg(w, tau, np.ascontiguousarray(X[:, i])) for i in range(X.shape[1])])
+        cov, alpha, eta = self.coeff_of_solves(Y, w, tau, Sigma_iY, Sigma_iX)
+        return Sigma_iY, Sigma_iX, cov, alpha, eta
+
+    def coeff_of_solves(self, Y, w, tau, Sigma_iY, Sigma_iX):
+        """The dense part of get_coeff_w, given its solves."""
+        X = self.X
         cov = _mat_inv(X.T @ Sigma_iX)
         alpha = cov @ (Sigma_iX.T @ Y)
         eta = Y - tau[0] * (Sigma_iY - Sigma_iX @ alpha) / w
-        return Sigma_iY, Sigma_iX, cov, alpha, eta
+        return cov, alpha, eta
+
+    def working(self, eta):
+        """mu, the working response Y and the IRLS weights W at eta (offset included)."""
+        fam, y, offset = self.fam, self.y, self.offset
+        mu = fam.linkinv(eta)
+        mu_eta = fam.mu_eta(eta)
+        Y = eta - offset + (y - mu) / mu_eta
+        W = mu_eta * mu_eta / fam.variance(mu)
+        return mu, Y, W
 
     # get_coeff (:778-813)
     def get_coeff(self, tau, alpha0, eta0):
-        fam, y, offset = self.fam, self.y, self.offset
+        offset = self.offset
         tol_coef = 0.1
-        mu = fam.linkinv(eta0)
-        mu_eta = fam.mu_eta(eta0)
-        Y = eta0 - offset + (y - mu) / mu_eta
-        W = mu_eta * mu_eta / fam.variance(mu)
+        mu, Y, W = self.working(eta0)
         a0 = alpha0
         for _ in range(self.p.maxiter):
             Sigma_iY, Sigma_iX, cov, alpha, eta = self.get_coeff_w(Y, W, tau)
             eta = eta + offset
-            mu = fam.linkinv(eta)
-            mu_eta = fam.mu_eta(eta)
-            Y = eta - offset + (y - mu) / mu_eta
-            W = mu_eta * mu_eta / fam.variance(mu)
+            mu, Y, W = self.working(eta)
             if np.max(np.abs(alpha - a0) / (np.abs(alpha) + np.abs(a0) + tol_coef)) < tol_coef:
                 break
             a0 = alpha
         return dict(Y=Y, mu=mu, alpha=alpha, eta=eta, W=W, cov=cov, Sigma_iY=Sigma_iY, Sigma_iX=Sigma_iX)
+
+    def get_coeff_lockstep(self, tau, alpha0, eta0, keys, solve):
+        """``get_coeff`` for several operators at once (the leave-one-chromosome-out models, SAIGE's
+        Get_Coef_LOCO): every key starts from (alpha0, eta0) and takes get_coeff's IRLS steps with its own
+        W, and leaves the step list when its own alpha criterion is met.  ``solve(act, B, W)`` solves, for
+        every key in ``act``, the 1 + K right-hand sides ``B[key]`` ([1 + K, N]: Y, then the columns of X)
+        with the weights ``W[key]`` on that key's operator -> {key: (S [1 + K, N], iters [1 + K])}.
+        -> {key: get_coeff's dict plus steps (IRLS steps taken) and pcg_iters ([steps, 1 + K])}."""
+        offset, X = self.offset, self.X
+        tol_coef = 0.1
+        st = {}
+        for k in keys:
+            mu, Y, W = self.working(eta0)
+            st[k] = dict(Y=Y, mu=mu, W=W, a0=alpha0, steps=0, pcg_iters=[])
+        act = list(keys)
+        for _ in range(self.p.maxiter):
+            if not act:
+                break
+            S = solve(act, {k: np.vstack([st[k]["Y"][None, :], X.T]) for k in act}, {k: st[k]["W"] for k in act})
+            still = []
+            for k in act:
+                c = st[k]
+                Sk, its = S[k]
+                Sigma_iY, Sigma_iX = Sk[0], np.ascontiguousarray(Sk[1:].T)
+                cov, alpha, eta = self.coeff_of_solves(c["Y"], c["W"], tau, Sigma_iY, Sigma_iX)
+                eta = eta + offset
+                mu, Y, W = self.working(eta)
+                c.update(Y=Y, mu=mu, W=W, alpha=alpha, eta=eta, cov=cov, Sigma_iY=Sigma_iY, Sigma_iX=Sigma_iX,
+                         steps=c["steps"] + 1)
+                c["pcg_iters"].append([int(v) for v in its])
+                if np.max(np.abs(alpha - c["a0"]) / (np.abs(alpha) + np.abs(c["a0"]) + tol_coef)) < tol_coef:
+                    continue
+                c["a0"] = alpha
+                still.append(k)
+            act = still
+        return st
 
     # get_trace (:627-668) / get_trace_q (:672-718)
     def get_trace(self, Sigma_iX, w, tau, cov, quant: bool):
@@ -479,6 +524,7 @@ class FittedNullModel(NullModel):
     var_ratio_table: Dict[str, np.ndarray] = field(default_factory=dict)
     mu_noK: Optional[np.ndarray] = None
     res_noK: Optional[np.ndarray] = None
+    loco_steps: Dict[str, Dict[str, Any]] = field(default_factory=dict)    # per chromosome: IRLS steps, PCG iterations
 
 
 _DS_NODE = "annotation/format/DS"
@@ -634,6 +680,65 @@ def _load_grm_markers(phenovar: str, covars: List[str], cols: Dict[str, np.ndarr
                 var_ids=var_ids, n_before=n_before, rng=rng, src=src)
 
 
+LOCO_MAX_CHROM = 64                            # SGX_GRM_MAX_GROUPS: marker groups of one GRM handle
+
+
+def _marker_chromosomes(src, idx: np.ndarray):
+    """The chromosomes of the GRM markers -> (names in order of first appearance, group id per marker)."""
+    from .assoc import GenotypeSource
+    chrom = src.chromosome if isinstance(src, GenotypeSource) else src.read("chromosome")
+    chrom = np.asarray([str(c) for c in chrom], dtype=object)[idx]
+    names: List[str] = []
+    seen: Dict[str, int] = {}
+    group = np.empty(chrom.size, dtype=np.int32)
+    for i, c in enumerate(chrom):
+        if c not in seen:
+            seen[c] = len(names)
+            names.append(c)
+        group[i] = seen[c]
+    if len(names) < 2:
+        raise ValueError(f"loco=True needs GRM markers on more than one chromosome: all {chrom.size} markers are on "
+                         f"chromosome '{names[0] if names else ''}'.")
+    if len(names) > LOCO_MAX_CHROM:
+        raise ValueError(f"loco=True takes at most {LOCO_MAX_CHROM} chromosomes among the GRM markers, found {len(names)}.")
+    return names, group
+
+
+def _fit_loco(fitter: _Fitter, op, operator_factory, packed: np.ndarray, n_samp: int, names: List[str],
+              group: np.ndarray, tau: np.ndarray, alpha: np.ndarray, eta: np.ndarray) -> Dict[str, Dict[str, Any]]:
+    """Get_Coef_LOCO: for every chromosome, get_coeff at the fitted tau on the GRM without its markers, started
+    from the full model's alpha and eta.  On an operator with ``pcg_loco`` all chromosomes run in lockstep and
+    share the sweeps of the genotype matrix: an IRLS step is one call of (1 + K) right-hand sides per
+    chromosome still iterating, each with its chromosome's weights.  Any other operator (an injected one):
+    one operator per chromosome, built from the markers outside it, one after the other."""
+    p = fitter.p
+    if hasattr(op, "pcg_loco"):
+        op.set_groups(group, len(names))
+
+        def solve(act, B, W):
+            nb = 1 + fitter.X.shape[1]
+            X, its = op.pcg_loco(np.stack([W[c] for c in act]), np.repeat(np.arange(len(act)), nb), tau,
+                                 np.vstack([B[c] for c in act]), np.repeat(np.asarray(act), nb), p.maxiterPCG, p.tolPCG)
+            return {c: (X[j * nb:(j + 1) * nb], its[j * nb:(j + 1) * nb]) for j, c in enumerate(act)}
+
+        st = fitter.get_coeff_lockstep(tau, alpha, eta, list(range(len(names))), solve)
+    else:
+        st = {}
+        for c in range(len(names)):
+            sub = operator_factory(np.ascontiguousarray(packed[group != c]), n_samp)
+
+            def solve(act, B, W, sub=sub):
+                S = [sub.pcg(W[act[0]], tau, np.ascontiguousarray(b), p.maxiterPCG, p.tolPCG) for b in B[act[0]]]
+                return {act[0]: (np.stack([x for x, _ in S]), [it for _, it in S])}
+
+            try:
+                st.update(fitter.get_coeff_lockstep(tau, alpha, eta, [c], solve))
+            finally:
+                if hasattr(sub, "close"):
+                    sub.close()
+    return {names[c]: st[c] for c in range(len(names))}
+
+
 def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: str = "binary",
                        sample_col: str = "sample.id", maf: float = 0.005, missing_rate: float = 0.01,
                        max_num_snp: int = 1000000, variant_id: Optional[Sequence[int]] = None,
@@ -641,7 +746,8 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
                        nrun: int = 30, tolPCG: float = 1e-5, maxiterPCG: int = 500, num_marker: int = 30,
                        tau_init=(0, 0), traceCVcutoff: float = 0.0025, ratioCVcutoff: float = 0.001,
                        geno_sparse: bool = True, num_thread: int = 1, model_savefn: str = "", seed: int = 200,
-                       fork_loading: bool = False, verbose: bool = True, operator_factory=None) -> FittedNullModel:
+                       fork_loading: bool = False, verbose: bool = True, operator_factory=None,
+                       loco: bool = False) -> FittedNullModel:
     """Fit the SAIGE null model ``formula + var(GRM)`` on MI355X.
 
     ``data``: mapping column -> sequence (a pandas DataFrame works);
@@ -654,6 +760,14 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
     one implemented -- ``geno_sparse=FALSE`` is not, and the argument is
     accepted for signature compatibility, as are ``num_thread`` and
     ``fork_loading`` (threads only).
+
+    ``loco=True`` adds the leave-one-chromosome-out models (SAIGE's ``LOCO``): after tau is fitted on the whole
+    GRM, every chromosome among the GRM markers gets the coefficients and fitted values of the model whose GRM
+    leaves that chromosome's markers out (``Get_Coef_LOCO``: ``get_coeff`` at the fitted tau, started from the
+    full model), in ``model.loco[chromosome]``; ``seqAssocGLMM_SPA`` then tests the variants of a chromosome
+    against its own entry.  tau is not refitted, and the variance ratio stays the single one of the full
+    model, as in SAIGE.  The markers must lie on 2 .. 64 chromosomes.  An injected operator without
+    ``pcg_loco`` is replaced, per chromosome, by ``operator_factory`` on the markers outside it.
     """
     if trait_type not in ("binary", "quantitative"):
         raise ValueError("'arg' should be one of \"binary\", \"quantitative\"")
@@ -676,6 +790,8 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
     yv, Xc, sample_ids, n_samp = g["y"], g["Xc"], g["sample_id"], g["n_samp"]
     packed, idx, var_ids, n_before, rng = g["packed"], g["idx"], g["var_ids"], g["n_before"], g["rng"]
     n_var = idx.size
+    if loco:
+        chrom_names, chrom_group = _marker_chromosomes(g["src"], idx)
     if verbose:
         print(f"Fit the null model: {formula} + var(GRM)")
         print(f"    # of samples: {n_samp:,}")
@@ -756,6 +872,12 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
         rng.set_seed(seed)
         rand_index = rng.sample_int(n_var)
         rows_vr = fitter.var_ratio(glmm["tau"], obj_noK, marker, rand_index, quant=(trait_type != "binary"))
+        loco_fit = None
+        if loco:
+            if verbose:
+                print(f"Leave-one-chromosome-out models: {len(chrom_names)} chromosomes")
+            loco_fit = _fit_loco(fitter, op, operator_factory, packed, n_samp, chrom_names, chrom_group, glmm["tau"],
+                                 glmm["coefficients"], glmm["linear_predictors"])
     finally:
         if hasattr(op, "close"):
             op.close()
@@ -777,6 +899,14 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
         linear_predictors=glmm["linear_predictors"], residuals=glmm["residuals"], cov=glmm["cov"],
         converged=glmm["converged"], var_ratio_table=vr, mu_noK=obj_noK["mu"], res_noK=obj_noK["res"])
     model.coef_names = X_name
+    if loco_fit is not None:
+        for name, c in loco_fit.items():
+            a = np.linalg.solve(X_qrr, c["alpha"] * math.sqrt(n_samp)) if do_tx else c["alpha"]
+            model.loco[name] = dict(coefficients=a, linear_predictors=c["eta"], fitted_values=c["mu"],
+                                    residuals=fitter.y - c["mu"], cov=c["cov"])
+            model.loco_steps[name] = dict(steps=c["steps"], pcg_iters=c["pcg_iters"])
+            if verbose:
+                print(f"    chr {name}: {c['steps']} step(s), fixed coeff: (" + ", ".join(f"{v:.7g}" for v in a) + ")")
     if model_savefn:
         from .results import save_model
         if verbose:

@@ -13,8 +13,8 @@ the column-major K x N matrices the reference passes.
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
-from typing import Any, Optional, Sequence
+from dataclasses import dataclass, field, replace
+from typing import Any, Dict, Optional, Sequence
 
 import numpy as np
 
@@ -41,6 +41,24 @@ class NullModel:
     XXVX_inv: np.ndarray       # obj.noK$XXVX_inv [N, K]
     coefficients: Optional[np.ndarray] = None
     variant_id: Optional[np.ndarray] = None
+    # leave-one-chromosome-out models (seqFitNullGLMM_SPA(loco=True)): chromosome -> {coefficients,
+    # linear_predictors, fitted_values, residuals, cov} of the model whose GRM leaves that chromosome out
+    loco: Dict[str, Dict[str, np.ndarray]] = field(default_factory=dict)
+
+    def for_chromosome(self, chrom: str) -> "NullModel":
+        """A copy that carries the fitted values of ``loco[chrom]``; y, V, XV, XXVX_inv and var_ratio unchanged."""
+        return replace(self, fitted_values=_as_f64(self.loco[chrom]["fitted_values"]), loco={})
+
+
+LOCO_FIELDS = (("coefficients", "coefficients"), ("linear.predictors", "linear_predictors"),
+               ("fitted.values", "fitted_values"), ("residuals", "residuals"), ("cov", "cov"))
+
+
+def no_loco(mod: "NullModel", what: str):
+    """The drivers that test every variant against the one full model refuse a model with LOCO entries."""
+    if getattr(mod, "loco", None):
+        raise NotImplementedError(f"{what}: leave-one-chromosome-out models (modobj$LOCOResult) are used by "
+                                  "seqAssocGLMM_SPA only; pass a model fitted with loco=False.")
 
 
 def _as_f64(x) -> np.ndarray:
@@ -57,12 +75,18 @@ def modobj_from_rlist(m: RList) -> NullModel:
     ratio = vr["ratio"] if isinstance(vr, RList) else vr
     sid = m["sample.id"]
     sid = list(sid) if isinstance(sid, list) else np.asarray(sid).tolist()
+    loco = {}
+    if "LOCOResult" in m:
+        for e in m["LOCOResult"]:
+            chrom = e["chromosome"]
+            chrom = chrom[0] if isinstance(chrom, (list, tuple)) else str(chrom)
+            loco[str(chrom)] = {py: _as_f64(e[r]) for r, py in LOCO_FIELDS}
     return NullModel(
         trait_type=tt, tau=_as_f64(m["tau"]), fitted_values=_as_f64(m["fitted.values"]),
         sample_id=sid, var_ratio=_as_f64(ratio), y=_as_f64(nk["y"]), V=_as_f64(nk["V"]),
         X1=_as_f64(nk["X1"]), XV=_as_f64(nk["XV"]), XXVX_inv=_as_f64(nk["XXVX_inv"]),
         coefficients=_as_f64(m["coefficients"]) if "coefficients" in m else None,
-        variant_id=np.asarray(m["variant.id"]) if "variant.id" in m else None)
+        variant_id=np.asarray(m["variant.id"]) if "variant.id" in m else None, loco=loco)
 
 
 def load_modobj(modobj: Any, verbose: bool = False) -> NullModel:

@@ -157,6 +157,12 @@ def serialize_model(m) -> bytes:
         ("sample.id", _vector(list(m.sample_id))),
         ("variant.id", _vector(np.asarray(m.variant_id))),
     ]
+    if getattr(m, "loco", None):
+        # one unnamed list per chromosome, as SAIGE's LOCOResult: the model without that chromosome's markers
+        from .nullmod import LOCO_FIELDS
+        ent = [_rlist([("chromosome", _strsxp([str(ch)]))] + [(r, _num(e[py])) for r, py in LOCO_FIELDS])
+               for ch, e in m.loco.items()]
+        items.append(("LOCOResult", _i(19) + _i(len(ent)) + b"".join(ent)))
     return _HEADER + _rlist(items, rclass="ClassSAIGE_NullModel")
 
 
