@@ -49,6 +49,7 @@ extern "C" {
 #define SGX_EHIP       -2   /* HIP runtime error                               */
 #define SGX_ENOMEM     -3   /* allocation failed                               */
 #define SGX_ENODEV     -4   /* no usable gfx950 device                         */
+#define SGX_ENOSPACE   -5   /* output buffer too small: the needed size is returned */
 
 #define SGX_MAX_COEFF  16   /* K = nrow(XV) supported by the compiled kernels  */
 #define SGX_TRAIT_BINARY 0
@@ -555,6 +556,37 @@ int  sgx_grm_diag_loco(sgx_grm *g, int excl, double *diag_out);
 int  sgx_grm_crossprod_loco(sgx_grm *g, const double *B, size_t ldb, int k, const int *excl, double *Out);
 int  sgx_grm_pcg_loco(sgx_grm *g, const double *W, size_t ldw, int n_w, const int *w_idx, const double *tau,
 	const double *B, size_t ldb, int k, const int *excl, int maxiter, double tol, double *X, int *iters);
+
+/* The explicit GRM: K = G'G/M as numbers (not in the reference, which has the operator only).
+ * K_ij = (1/M) sum_v g_vi g_vj, g = fma(code, inv_v, l0_v), 0 for a missing code, summed in FP64 in marker
+ * order (slabs of 65536 markers, added in slab order).  The bits of K_ij depend on the two samples' genotypes,
+ * the marker table and M only: not on the rectangle, the cutoff, the other samples or the call.  K_ij and K_ji
+ * are the same bits.  Marker groups (sgx_grm_set_groups) are ignored: K is always the GRM of all markers.
+ *   sgx_grm_dense   out[(i - i0) * ld + (j - j0)] = K_ij, i0 <= i < i0 + ni, j0 <= j < j0 + nj: a host buffer,
+ *                   any rectangle inside [0, N) x [0, N), ld >= nj; synchronous
+ *   sgx_grm_sparse  every pair i <= j with K_ij >= cutoff and every diagonal entry, K_ij being the number
+ *                   sgx_grm_dense gives, sorted by (i, j).  An exact int8 screen with a rigorous bound selects
+ *                   the 16 x 16 sub-tiles that go to FP64; it only saves work.  *n_out is the number of entries
+ *                   that exist; if it exceeds cap, SGX_ENOSPACE is returned and the buffers are not written
+ *                   (call again with cap >= *n_out).  cutoff must be finite; cutoff <= -1e300 returns every
+ *                   pair.  stats may be NULL.
+ * SGX_EINVAL (nothing launched, nothing written): a NULL buffer, a rectangle outside [0, N), ld < nj, a
+ * non-finite cutoff.  The scratch of both is allocated on first use and freed by sgx_grm_free. */
+typedef struct {
+	int64_t tiles_screened;      /* 64 x 64 workgroup tiles of the screen (bj >= bi)            */
+	int64_t subtiles_total;      /* 16 x 16 sub-tiles with tj >= ti                             */
+	int64_t subtiles_flagged;    /* those that went to FP64                                     */
+	int64_t entries;             /* = *n_out                                                    */
+	int32_t s;                   /* the screen quantises g to round(g 2^s)                      */
+	int32_t reserved;
+	double ms_prepare;           /* per-handle tables of the screen (first call only)           */
+	double ms_screen, ms_fp64, ms_sort;   /* ms_fp64: tiles and compaction; ms_sort: copy and sort */
+} sgx_grm_sparse_stats;
+int  sgx_grm_dense(sgx_grm *g, int32_t i0, int32_t ni, int32_t j0, int32_t nj, double *out, size_t ld);
+/* milliseconds the kernels of the last sgx_grm_dense call took on the device (tiles and gather; not the copy out) */
+int  sgx_grm_dense_kernel_ms(sgx_grm *g, double *ms_out);
+int  sgx_grm_sparse(sgx_grm *g, double cutoff, size_t cap, int32_t *i_out, int32_t *j_out, double *v_out,
+	size_t *n_out, sgx_grm_sparse_stats *stats);
 
 #ifdef __cplusplus
 }

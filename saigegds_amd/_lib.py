@@ -22,6 +22,7 @@ EXPORTS = (
     "sgx_grm_init", "sgx_grm_init_dev", "sgx_grm_crossprod_dev", "sgx_grm_sync", "sgx_grm_free", "sgx_grm_diag", "sgx_grm_crossprod", "sgx_grm_pcg",
     "sgx_grm_crossprod_multi", "sgx_grm_crossprod_multi_dev", "sgx_grm_pcg_multi",
     "sgx_grm_set_groups", "sgx_grm_group_sizes", "sgx_grm_diag_loco", "sgx_grm_crossprod_loco", "sgx_grm_pcg_loco",
+    "sgx_grm_dense", "sgx_grm_dense_kernel_ms", "sgx_grm_sparse",
     "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
     "sgx_scan_packed", "sgx_ds_block_load_packed",
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
@@ -32,6 +33,7 @@ EXPORTS = (
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
 GRM_MAX_GROUPS = 64   # SGX_GRM_MAX_GROUPS: marker groups of one GRM handle
+ENOSPACE = -5         # SGX_ENOSPACE: sgx_grm_sparse found more entries than the buffers hold
 SKAT_MAX_VARIANTS = 4096   # SGX_SKAT_MAX_VARIANTS: entries of one unit of sgx_skat_2bit
 COND_MAX = 16         # SGX_COND_MAX: conditioning variants of one sgx_cond_set
 DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
@@ -111,6 +113,17 @@ class SgxStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SgxGrmSparseStats(C.Structure):
+    _fields_ = [
+        ("tiles_screened", C.c_int64), ("subtiles_total", C.c_int64), ("subtiles_flagged", C.c_int64),
+        ("entries", C.c_int64), ("s", C.c_int32), ("reserved", C.c_int32),
+        ("ms_prepare", C.c_double), ("ms_screen", C.c_double), ("ms_fp64", C.c_double), ("ms_sort", C.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
 _lib = None
@@ -272,6 +285,12 @@ def load():
     L.sgx_grm_diag_loco.argtypes = [vp, C.c_int, vp]
     L.sgx_grm_crossprod_loco.restype = C.c_int
     L.sgx_grm_crossprod_loco.argtypes = [vp, vp, sz, C.c_int, vp, vp]
+    L.sgx_grm_dense.restype = C.c_int
+    L.sgx_grm_dense.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, sz]
+    L.sgx_grm_dense_kernel_ms.restype = C.c_int
+    L.sgx_grm_dense_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.sgx_grm_sparse.restype = C.c_int
+    L.sgx_grm_sparse.argtypes = [vp, C.c_double, sz, vp, vp, vp, C.POINTER(sz), C.POINTER(SgxGrmSparseStats)]
     L.sgx_grm_pcg_loco.restype = C.c_int
     L.sgx_grm_pcg_loco.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, sz, C.c_int, vp, C.c_int, dp, vp, vp]
     _lib = L
@@ -840,6 +859,56 @@ class GrmOperator:
         out = np.empty(self.n, dtype=np.float64)
         check(self._L.sgx_grm_diag(self._h, out.ctypes.data))
         return out
+
+    # -- the explicit GRM (sgx_grm_dense / sgx_grm_sparse); marker groups are ignored
+    DENSE_BLOCK = 4096     # rows / columns per sgx_grm_dense call of dense()
+
+    def dense_block(self, i0: int, ni: int, j0: int, nj: int) -> np.ndarray:
+        """K[i0:i0+ni, j0:j0+nj] of the GRM K = G'G/M, [ni, nj] float64."""
+        out = np.empty((max(int(ni), 0), max(int(nj), 0)), dtype=np.float64)
+        check(self._L.sgx_grm_dense(self._h, int(i0), int(ni), int(j0), int(nj), out.ctypes.data, out.shape[1]))
+        return out
+
+    def dense_kernel_ms(self) -> float:
+        """Device milliseconds of the kernels of the last dense_block call (without the copy to the host)."""
+        ms = C.c_double(0)
+        check(self._L.sgx_grm_dense_kernel_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def dense(self) -> np.ndarray:
+        """The whole GRM [N, N]: the blocks on and above the diagonal, the others mirrored."""
+        n, bs = self.n, self.DENSE_BLOCK
+        K = np.empty((n, n), dtype=np.float64)
+        for i0 in range(0, n, bs):
+            ni = min(bs, n - i0)
+            for j0 in range(i0, n, bs):
+                nj = min(bs, n - j0)
+                blk = self.dense_block(i0, ni, j0, nj)
+                K[i0:i0 + ni, j0:j0 + nj] = blk
+                if j0 != i0:
+                    K[j0:j0 + nj, i0:i0 + ni] = blk.T
+        return K
+
+    def sparse(self, cutoff: float, cap: Optional[int] = None, return_stats: bool = False):
+        """The pairs i <= j with K_ij >= cutoff and every diagonal entry -> (i, j, x), sorted by (i, j); x holds
+        the numbers dense() gives.  Retries once with the size the library reports when ``cap`` entries (default
+        8 N) do not hold them.  With ``return_stats`` the dict of sgx_grm_sparse_stats comes fourth."""
+        cap = int(8 * self.n if cap is None else cap)
+        for attempt in (0, 1):
+            i = np.empty(cap, dtype=np.int32)
+            j = np.empty(cap, dtype=np.int32)
+            x = np.empty(cap, dtype=np.float64)
+            n_out = C.c_size_t(0)
+            st = SgxGrmSparseStats()
+            rc = self._L.sgx_grm_sparse(self._h, float(cutoff), cap, i.ctypes.data, j.ctypes.data, x.ctypes.data,
+                                        C.byref(n_out), C.byref(st))
+            if rc == ENOSPACE and attempt == 0:
+                cap = int(n_out.value)
+                continue
+            check(rc)
+            k = int(n_out.value)
+            res = (i[:k].copy(), j[:k].copy(), x[:k].copy())
+            return res + (st.as_dict(),) if return_stats else res
 
     def crossprod(self, b: np.ndarray) -> np.ndarray:
         b = np.ascontiguousarray(b, dtype=np.float64)

@@ -37,6 +37,18 @@ struct sgx_grm {
 	double *diagx = nullptr;               // [1 + n_groups][N]: row 0 = diag, row 1 + c = diag(GRM without group c)
 	int kcap_w = 0;                        // columns Wc / Mc have room for
 	double *Wc = nullptr, *Mc = nullptr;   // [k][N]: weight rows and per-column minv of sgx_grm_pcg_loco
+	// explicit GRM (host_grm_dense.h): scratch of sgx_grm_dense / sgx_grm_sparse, allocated on first use
+	double *gd_part = nullptr, *gd_out = nullptr;    // slab tiles [nslab][tiles][256]; a rectangle of K
+	size_t gd_part_cap = 0, gd_out_cap = 0;          // (doubles)
+	bool gd_ready = false;                           // the screen's tables below are built
+	int gd_s = 0;                                    // Q = round(g 2^s)
+	uint2 *gd_lut = nullptr;                         // [markers padded to 512] limb bytes per code
+	double *gd_A = nullptr, *gd_R = nullptr;         // [N] bound terms per sample
+	unsigned long long *gd_cnt = nullptr;            // [2]: flagged sub-tiles, entries (also the table maximum)
+	GdTile *gd_list = nullptr; size_t gd_list_cap = 0;
+	int *gd_i = nullptr, *gd_j = nullptr; double *gd_v = nullptr; size_t gd_ent_cap = 0;
+	hipEvent_t gd_ev0 = nullptr, gd_ev1 = nullptr;   // around the kernels of a piece of sgx_grm_dense
+	double gd_ms_kernel = 0;                         // their time over the last sgx_grm_dense call
 };
 static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
 static_assert(GRM_MAX_GROUPS == SGX_GRM_MAX_GROUPS, "kern_grm.h and saigehip.h disagree on the group limit");
@@ -77,9 +89,12 @@ extern "C" void sgx_grm_free(sgx_grm *g)
 	(void)hipSetDevice(g->device);
 	if (g->stream) (void)hipStreamSynchronize(g->stream);
 	void *ptrs[] = {g->G, g->Gt, g->af, g->inv, g->l0, g->diag, g->FlN, g->FlM, g->accV, g->accS, g->xv, g->gv,
-		g->maxb, g->part, g->minv, g->w, g->B, g->O, g->R, g->Z, g->P, g->X, g->AP, g->GP, g->grp, g->diagx, g->Wc, g->Mc};
+		g->maxb, g->part, g->minv, g->w, g->B, g->O, g->R, g->Z, g->P, g->X, g->AP, g->GP, g->grp, g->diagx, g->Wc, g->Mc,
+		g->gd_part, g->gd_out, g->gd_lut, g->gd_A, g->gd_R, g->gd_cnt, g->gd_list, g->gd_i, g->gd_j, g->gd_v};
 	for (void *p : ptrs) (void)hipFree(p);
 	if (g->h_part) (void)hipHostFree(g->h_part);
+	if (g->gd_ev0) (void)hipEventDestroy(g->gd_ev0);
+	if (g->gd_ev1) (void)hipEventDestroy(g->gd_ev1);
 	if (g->stream) (void)hipStreamDestroy(g->stream);
 	delete g;
 }

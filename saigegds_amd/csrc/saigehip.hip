@@ -78,6 +78,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_skat_ds.h"
 #include "kern_cond.h"
 #include "kern_cond_ds.h"
+#include "kern_grm_dense.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -95,3 +96,4 @@ static int fail(int code, const char *fmt, ...)
 #include "host_cond_ds.h"
 #include "host_util.h"
 #include "host_grm.h"
+#include "host_grm_dense.h"

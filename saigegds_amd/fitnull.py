@@ -589,7 +589,7 @@ def _load_grm_markers(phenovar: str, covars: List[str], cols: Dict[str, np.ndarr
     # complete cases, then the GDS sample order (R/saige_main.r:299-311)
     num = np.column_stack([np.asarray(cols[c], dtype=np.float64) for c in [phenovar] + covars])
     keep = ~np.isnan(num).any(axis=1)
-    from .assoc import GenotypeSource, _open_source
+    from .assoc import _open_source
     src = _open_source(gdsfile, verbose)
     gsid = [str(s) for s in src.sample_id()]
     pos = {s: i for i, s in enumerate(sids) if keep[i]}
@@ -602,6 +602,17 @@ def _load_grm_markers(phenovar: str, covars: List[str], cols: Dict[str, np.ndarr
     sample_ids = [gsid[i] for i in sel]
     n_samp = len(sel)
 
+    m = _select_grm_markers(src, sel, gsid, maf, missing_rate, max_num_snp, variant_id, seed, verbose, use_gpu_counts)
+    return dict(y=yv, Xc=Xc, rows=rows, sample_id=sample_ids, n_samp=n_samp, src=src, **m)
+
+
+def _select_grm_markers(src, sel: List[int], gsid: List[str], maf: float, missing_rate: float, max_num_snp: int,
+                        variant_id, seed: int, verbose: bool, use_gpu_counts: bool) -> Dict[str, Any]:
+    """The GRM markers of the samples ``sel`` (increasing indices into the file's samples ``gsid``): the maf /
+    missing-rate filter (or ``variant_id``), then ``max_num_snp`` markers drawn by R's ``sample()`` after
+    ``set.seed(seed)``.  Shared by the null-model fit and the explicit GRM (grm.py)."""
+    from .assoc import GenotypeSource
+    n_samp = len(sel)
     # genotypes of the selected samples; variant filter (seqSetFilterCond, :314-321)
     want = None if variant_id is None else set(int(v) for v in variant_id)
     ds_route = False
@@ -676,8 +687,7 @@ def _load_grm_markers(phenovar: str, covars: List[str], cols: Dict[str, np.ndarr
         rng.set_seed(seed)
         pick = np.sort(rng.sample_int(idx.size)[:max_num_snp] - 1)     # sample(which(v), max.num.snp)
         idx, packed = idx[pick], np.ascontiguousarray(packed[pick])
-    return dict(y=yv, Xc=Xc, rows=rows, sample_id=sample_ids, n_samp=n_samp, packed=packed, idx=idx,
-                var_ids=var_ids, n_before=n_before, rng=rng, src=src)
+    return dict(packed=packed, idx=idx, var_ids=var_ids, n_before=n_before, rng=rng)
 
 
 LOCO_MAX_CHROM = 64                            # SGX_GRM_MAX_GROUPS: marker groups of one GRM handle

@@ -49,6 +49,8 @@ _P_DIM = b"\x02\xc3Ca"
 _P_DATA = b"\t\xc4\xc3|\x0c"
 _P_OFFSET = b"\x13\x86\x16E\x1e\xf4\x01"
 _P_SCALE = b"\x13\x85\xe70\x17\x04"
+_P_ATTRCNT = bytes.fromhex("0807f37d9d937d")
+_P_ATTRDATA = bytes.fromhex("0108f37ddd45791f")
 
 
 def _u48(b: bytes, o: int) -> int:
@@ -290,6 +292,38 @@ class GdsFile:
         i = s.find(_P_SCALE)
         if i >= 0:
             node.scale = struct.unpack_from("<d", s, i + len(_P_SCALE))[0]
+
+    def attrs(self, path: str = "") -> Dict[str, Optional[str]]:
+        """The attributes of a node (the root for ""): {name: short string, or None for one without a value}.
+        The records are parsed by their lengths; an attribute of another type ends the list."""
+        s = self.stream(self.node(path).block_id)
+        i = s.find(_P_ATTRCNT)
+        if i < 0:
+            return {}
+        cnt = struct.unpack_from("<I", s, i + len(_P_ATTRCNT))[0]
+        o = i + len(_P_ATTRCNT) + 4
+        out: Dict[str, Optional[str]] = {}
+        if cnt == 0 or s[o:o + len(_P_ATTRDATA)] != _P_ATTRDATA:
+            return out
+        o += len(_P_ATTRDATA)
+        end = o + _u48(s, o)
+        o += 6
+        for _ in range(cnt):
+            if o >= end:
+                break
+            ln = s[o]
+            name = s[o + 1:o + 1 + ln].decode("utf-8")
+            o += 1 + ln
+            if s[o] == 0x00:
+                out[name] = None
+                o += 1
+            elif s[o] == 0x0E:
+                vl = s[o + 1]
+                out[name] = s[o + 2:o + 2 + vl].decode("utf-8")
+                o += 2 + vl
+            else:
+                break
+        return out
 
     # ------------------------------------------------------------------
     def node(self, path: str, silent: bool = False) -> Optional[GdsNode]:

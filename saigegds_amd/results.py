@@ -9,7 +9,7 @@ import gzip
 import lzma
 import re
 import struct
-from typing import Any, Dict, List
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -99,6 +99,83 @@ def save_result(ans: Dict[str, Any], fn: str, res_compress: str = "LZMA", sample
         raise ValueError("Unknown format of the output file, and it should be RData, RDS or gds.")
     with open(fn, "wb") as f:
         f.write(_compress(raw, res_compress))
+
+
+# ---------------------------------------------------------------------------
+# seqSAIGE_LoadPval (R/saige_main.r:164-215): the three files above, read back
+
+
+def _take(col, index):
+    if index is None:
+        return col
+    if isinstance(col, list):
+        ix = np.arange(len(col))[index]
+        return [col[int(k)] for k in np.atleast_1d(ix)]
+    return np.asarray(col)[index]
+
+
+def _column(v):
+    """A loaded column as a numeric / logical array, or a list of strings."""
+    if isinstance(v, np.ndarray) and v.dtype.kind in "fiub":
+        return v
+    return [str(s) for s in v]
+
+
+def _load_gds_columns(fn: str, varnm) -> Dict[str, Any]:
+    from .gds import GdsFile
+    g = GdsFile(fn)
+    if g.attrs().get("FileFormat") not in ("SAIGE_OUTPUT", "SAIGE_OUTPUT_SET"):
+        raise ValueError("FileFormat should be 'SAIGE_OUTPUT' or 'SAIGE_OUTPUT_SET'.")
+    have = g.ls()
+    names = [k for k in (have if varnm is None else varnm) if k != "sample.id"]
+    cols = {}
+    for k in names:
+        if k not in have:
+            raise KeyError(f"no column {k!r} in '{fn}'")
+        v = g.read(k)
+        if "R.logical" in g.attrs(k):
+            v = np.asarray(v) == 1
+        cols[k] = v
+    return cols
+
+
+def seqSAIGE_LoadPval(fn, varnm: Optional[Sequence[str]] = None, index=None, verbose: bool = False) -> Dict[str, Any]:
+    """Load the association results of ``res.savefn``: ``.gds`` (SAIGE_OUTPUT), ``.rda/.RData`` or ``.rds`` ->
+    {column: array or list of strings}.  ``varnm``: the columns to load (default: all); ``index``: the rows
+    (0-based indices, a slice or a boolean mask).  A list of files is loaded one by one and the rows appended;
+    ``index`` must then be None."""
+    if not isinstance(fn, str):
+        files = list(fn)
+        if not files:
+            raise ValueError("'fn' should name at least one file.")
+        if index is not None:
+            raise ValueError("'index' should be NULL for multiple input files.")
+        parts = [seqSAIGE_LoadPval(f, varnm, None, verbose) for f in files]
+        out: Dict[str, Any] = {}
+        for k in parts[0]:
+            vals = [p[k] for p in parts]
+            out[k] = sum(vals, []) if isinstance(vals[0], list) else np.concatenate([np.asarray(v) for v in vals])
+        return out
+    if verbose:
+        print(f"Loading '{fn}' ...")
+    varnm = None if varnm is None else list(varnm)
+    if re.search(r"\.gds$", fn, re.I):
+        cols = _load_gds_columns(fn, varnm)
+    elif re.search(r"\.(rda|RData)$", fn, re.I):
+        from .rds import data_frame_columns, read_rdata
+        cols = data_frame_columns(next(iter(read_rdata(fn).values())))
+    elif re.search(r"\.rds$", fn, re.I):
+        from .rds import data_frame_columns, read_rds
+        cols = data_frame_columns(read_rds(fn))
+    else:
+        raise ValueError("Unknown format, should be RData, RDS or gds.")
+    if varnm is not None:
+        names = [k for k in varnm if k != "sample.id"]
+        lack = [k for k in names if k not in cols]
+        if lack:
+            raise KeyError(f"no column {lack[0]!r} in '{fn}'")
+        cols = {k: cols[k] for k in names}
+    return {k: _take(_column(v), index) for k, v in cols.items()}
 
 
 # ---------------------------------------------------------------------------
