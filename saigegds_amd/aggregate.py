@@ -23,15 +23,16 @@ driver (``skat.py``) takes its score statistics and covariance matrices from the
 """
 from __future__ import annotations
 
+import dataclasses
 import math
-from typing import Any, Dict, List, Optional, Sequence, Union
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
 from ._lib import Scanner
-from .assoc import GenotypeSource, PackedRows, _dsnode, _is_num, _open_source, dosage_matrix, dosage_row_reader, match_samples
-from .gds import GdsFile, pack_dosage_2bit, unpack_dosage_2bit
-from .nullmod import ModelError, NullModel, init_nullmod, load_modobj, no_loco
+from .assoc import PackedRows, ScanInput, _is_num, open_scan_input
+from .gds import pack_dosage_2bit, unpack_dosage_2bit
+from .nullmod import NullModel, ScanModel, init_nullmod, load_modobj, no_loco
 
 # AggrParamBeta, R/assoc_aggregate.r:18-19: columns (shape1, shape2) = (1,1) and (1,25)
 AggrParamBeta = np.array([[1.0, 1.0], [1.0, 25.0]]).T     # [2, n_weights]
@@ -140,17 +141,40 @@ def _check_beta(wbeta) -> np.ndarray:
     return wb
 
 
+@dataclasses.dataclass(slots=True)
 class _Prepared:
-    pass
+    """What ``_prepare`` hands a set-test driver.  The per-variant arrays are indexed by ``local``."""
+    units: _Units
+    wbeta: np.ndarray                       # [2, n_weights]
+    inp: ScanInput = None                   # the opened input
+    local: Dict[int, int] = None            # 1-based variant index -> row of the per-variant arrays
+    sm: ScanModel = None                    # the model at thresholds 0 / 0 / 1
+    binary: bool = False
+    wb_colnm: List[str] = None              # "b<a>_<b>" per weight set
+    sc: Any = None                          # the scanner; the driver closes it
+    n: np.ndarray = None                    # per variant: non-missing samples,
+    s: np.ndarray = None                    # their sum (a double sum for real dosages),
+    maf: np.ndarray = None
+    mac: np.ndarray = None
+    pval: np.ndarray = None                 # the single-variant p-value (NaN: rejected by the scan's filter)
+    out: np.ndarray = None                  # the scan table [n, 8] and
+    valid: np.ndarray = None                # its valid flags (dosage route: the SKAT driver only)
+    rows: List[List[int]] = None            # per unit: rows of the per-variant arrays (_summary_cols)
+    packed: np.ndarray = None               # 2-bit route: the variants' rows for the model's samples
+    st: np.ndarray = None                   # dosage route: the truncated `int sum` of ds_mat_burden
+    ds_out: Optional[Dict[str, Any]] = None  # dosage route: column kind -> (burden rows [n_units, n_weights, 8], valid)
+    skat_rows: List[np.ndarray] = None      # dosage route, SKAT: per unit the variants in the test,
+    skat_S: List[np.ndarray] = None         # their score statistics
+    skat_Phi: List[np.ndarray] = None       # and covariance
 
 
-def _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner_factory):
+def _prepare_model(pr, mod, used, spa_pval, var_ratio, verbose, scanner_factory):
     """The model and the scanner of a driver call (and what the reference prints about the units)."""
     if not math.isfinite(var_ratio):
         var_ratio = float(np.nanmean(mod.var_ratio))
     sizes = np.array([len(ix) for ix in pr.units.index])
     if verbose:
-        print(f"    # of samples: {len(sel):,}")
+        print(f"    # of samples: {pr.inp.n_samp:,}")
         print(f"    # of variants in total: {used.size:,}")
         print(f"    # of units: {len(pr.units.index):,}")
         print(f"    avg. # of variants per unit: {sizes.mean()}")
@@ -159,9 +183,8 @@ def _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner
         print(f"    p-value threshold for SPA adjustment: {spa_pval}")
         print(f"    variance ratio for approximation: {var_ratio}")
         print("    variant weights: " + ", ".join(f"beta({a:g},{b:g})" for a, b in pr.wbeta.T))
-    pr.mod = mod
     # .init_nullmod(modobj, ii, 0, 0, 1, spa.pval, var.ratio, ...): maf 0, mac 0, missing 1
-    pr.sm = init_nullmod(mod, ii, 0.0, 0.0, 1.0, spa_pval, var_ratio)
+    pr.sm = init_nullmod(mod, pr.inp.ii, 0.0, 0.0, 1.0, spa_pval, var_ratio)
     pr.binary = mod.trait_type == "binary"
     pr.wb_colnm = [f"b{a:g}_{b:g}" for a, b in pr.wbeta.T]
     pr.sc = Scanner(pr.sm) if scanner_factory is None else scanner_factory(pr.sm)   # tests inject the CPU oracle
@@ -170,6 +193,16 @@ def _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner
 
 
 DS_BUDGET = 1 << 30      # bytes of dosage rows resident on the device per batch of units
+
+
+def flip_mean(n, s):
+    """The scan's own imputation and flip of rows from their counts (n non-missing, s their double sum) ->
+    (flip = s > n as uint8, mean = s / n, or 2 - s / n where flipped)."""
+    n = np.asarray(n, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = s / n
+    fl = s > n
+    return fl.astype(np.uint8), np.where(fl, 2 - m, m)
 
 
 def _sets_all(pr, r):
@@ -189,7 +222,7 @@ def _hard_calls(ds: np.ndarray) -> bool:
     return bool(np.all((ds == miss) | ((ds >= 0) & (ds <= 2))))
 
 
-def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
+def _run_dosage(pr, stored, used, kinds, burden_mac, budget):
     """Dosage flow: the units in batches of consecutive units whose distinct variants fit ``budget`` bytes of
     resident rows (a unit larger than that is a batch of its own).  Per batch: rows -> block (one upload), counts and
     single-variant tests into the per-variant arrays, weights, one burden call with every column of the driver.
@@ -203,6 +236,7 @@ def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
     from the truncated ``st``, which is a quirk of the reference's burden code only."""
     if "rare" in kinds and not pr.binary:
         return                                    # ACAT-V / ACAT-O of a quantitative trait: the driver raises, as the reference does
+    read_rows, dtype = pr.inp.dosage_reader(stored), pr.inp.ds_dtype
     n_samp = pr.sm.n
     row_bytes = n_samp * (1 if np.dtype(dtype) == np.uint8 else 8)
     index = [np.array([pr.local[int(v)] for v in ix], dtype=np.int64) for ix in pr.units.index]
@@ -215,7 +249,6 @@ def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
         cur.append(u)
         seen |= new
     batches.append(cur)
-    pr.n_batches = len(batches)
     skat = "skat" in kinds
     kinds = tuple(k for k in kinds if k != "skat")
     nv_used, nu, nw, nk = used.size, len(index), pr.wbeta.shape[1], len(kinds)
@@ -249,12 +282,9 @@ def _run_dosage(pr, read_rows, dtype, used, kinds, burden_mac, budget):
                 ok = (pr.valid != 0) & (pr.mac > 0)
                 kept = [index[u][ok[index[u]]] for u in bt]
                 rows_k = np.concatenate(kept)
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    m = pr.s[rows_k] / pr.n[rows_k]
-                fl = pr.s[rows_k] > pr.n[rows_k]
                 unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])])
                 score, cov = blk.skat(unit_ptr, np.array([loc[int(v)] for v in rows_k], dtype=np.int32),
-                                      fl.astype(np.uint8), np.where(fl, 2 - m, m))
+                                      *flip_mean(pr.n[rows_k], pr.s[rows_k]))
                 for k, u in enumerate(bt):
                     pr.skat_rows[u], pr.skat_Phi[u] = kept[k], np.array(cov[k], dtype=np.float64)
                     pr.skat_S[u] = np.array(score[unit_ptr[k]:unit_ptr[k + 1]], dtype=np.float64)
@@ -297,70 +327,39 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
     device side, the burden rows of the driver's column ``kinds`` included (``_run_dosage``)."""
     if verbose:
         print(what)
-    pr = _Prepared()
-    pr.units = _Units(units)
-    pr.wbeta = _check_beta(wbeta)
+    pr = _Prepared(_Units(units), _check_beta(wbeta))
     for nm, v in (("spa.pval", spa_pval), ("var.ratio", var_ratio)):
         if not _is_num(v):
             raise TypeError(f"is.numeric({nm}) is not TRUE")
     mod: NullModel = load_modobj(modobj, verbose)
     no_loco(mod, what.rstrip(":"))
-    src = _open_source(gdsfile, verbose)
-    gsid, sel, ii = match_samples(src, mod)
-    if not isinstance(dsnode, str):
-        raise TypeError("is.character(dsnode) is not TRUE")
-    node = _dsnode(src, dsnode)
-    ds_all, ds_dtype = None, None                 # dosage input: the matrix in memory (else read from `node`), its type
-    if isinstance(src, GenotypeSource):
-        packed_all, n_all = src.packed, len(gsid)
-        if packed_all is None:
-            ds_all = dosage_matrix(src, n_all)
-            ds_dtype = ds_all.dtype
-            if ds_dtype != np.float64 and _hard_calls(ds_all):
-                # hard calls: the reference's RAW branch has the same meaning -> the 2-bit path
-                packed_all, ds_all = pack_dosage_2bit(np.where((ds_all < 0) | (ds_all > 2), 3, ds_all).astype(np.uint8)), None
-    elif node == "$dosage_alt":
-        packed_all, n_all, _ = src.dosage_alt_packed()
-    else:
-        packed_all, ds_dtype = None, np.dtype(np.float64)
-        n_var_ds, n_all = src.node(node + "/data").dims[:2]
-    pr.ds_out = None
-    if packed_all is None:
-        n_var_all = ds_all.shape[0] if ds_all is not None else n_var_ds
-        used = np.unique(np.concatenate(pr.units.index))
-        if used.size == 0 or used.min() < 1 or used.max() > n_var_all:
-            raise ValueError("No variant in the genotypic data set!")
-        pr.local = {int(v): k for k, v in enumerate(used)}
-        # a packed-real or float32 node goes to the device as stored: the variants are picked on the host, the samples
-        # there.  (An injected scanner -- the tests' CPU stand-in for the device -- has no such load: decoded rows.)
-        stored = ds_all is None and scanner_factory is None and src.dosage_raw_class(node) is not None
-        read_rows = dosage_row_reader(src, node, ds_all, ds_dtype, sel, n_all, stored)
-        _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner_factory)
+    inp = open_scan_input(gdsfile, mod, dsnode, verbose)
+    if inp.kind == "dosage" and inp.in_mem and inp.ds_dtype != np.float64 and _hard_calls(inp.ds_all):
+        # hard calls: the reference's RAW branch has the same meaning -> the 2-bit path
+        codes = np.where((inp.ds_all < 0) | (inp.ds_all > 2), 3, inp.ds_all).astype(np.uint8)
+        inp = dataclasses.replace(inp, kind="packed", packed=pack_dosage_2bit(codes), ds_all=None, ds_dtype=None)
+    pr.inp = inp
+    used = np.unique(np.concatenate(pr.units.index))
+    if used.size == 0 or used.min() < 1 or used.max() > inp.n_var:
+        raise ValueError("No variant in the genotypic data set!")
+    pr.local = {int(v): k for k, v in enumerate(used)}
+    if inp.kind != "packed":
+        _prepare_model(pr, mod, used, spa_pval, var_ratio, verbose, scanner_factory)
         try:
-            _run_dosage(pr, read_rows, ds_dtype, used, kinds, burden_mac, DS_BUDGET if ds_budget is None else ds_budget)
+            _run_dosage(pr, inp.stored_ok(scanner_factory), used, kinds, burden_mac, DS_BUDGET if ds_budget is None else ds_budget)
         except BaseException:
             pr.sc.close()
             raise
         return pr
-    n_var_all = packed_all.shape[0]
-    used = np.unique(np.concatenate(pr.units.index))
-    if used.size == 0 or used.min() < 1 or used.max() > n_var_all:
-        raise ValueError("No variant in the genotypic data set!")
-    if len(sel) == n_all and np.array_equal(sel, np.arange(n_all)):
-        packed = np.ascontiguousarray(packed_all[used - 1])
-    else:
-        packed = pack_dosage_2bit(unpack_dosage_2bit(packed_all[used - 1], n_all)[:, sel])
-    pr.local = {int(v): k for k, v in enumerate(used)}        # 1-based variant index -> row of `packed`
-    pr.packed = packed
-    _prepare_model(pr, mod, ii, sel, used, spa_pval, var_ratio, verbose, scanner_factory)
+    pr.packed = packed = inp.packed_rows_at(used - 1)
+    _prepare_model(pr, mod, used, spa_pval, var_ratio, verbose, scanner_factory)
     out, valid = pr.sc.scan_2bit(packed)
     # ds_mat_mafmac (src/saige_main.cpp:466-524), RAW branch: n non-missing, s = sum of codes
     num = out[:, 2]
-    n_all_missing = ~np.isfinite(out[:, 0]) & (valid == 0)
     # a variant rejected by the scan's filter (monomorphic: maf = 0) still has counts: redo them on the host
     codes = None
     if (valid == 0).any():
-        codes = unpack_dosage_2bit(packed[valid == 0], len(sel)).astype(np.int64)
+        codes = unpack_dosage_2bit(packed[valid == 0], inp.n_samp).astype(np.int64)
     n = np.where(valid != 0, num, 0).astype(np.float64)
     s = np.where(valid != 0, np.rint(out[:, 0] * 2 * np.where(valid != 0, num, 0)), 0.0)
     if codes is not None:
@@ -368,7 +367,6 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
         sm_ = np.where(codes != 3, codes, 0).sum(axis=1)
         n[valid == 0] = nm
         s[valid == 0] = sm_
-    del n_all_missing
     with np.errstate(invalid="ignore", divide="ignore"):
         af = s / (2 * n)
     pr.n, pr.s = n, s

@@ -8,9 +8,9 @@ forks SeqArray worker processes instead, R/assoc_single.r:167-204).
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, List, Optional, Union
-
 import time
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Union
 
 import numpy as np
 
@@ -109,6 +109,8 @@ def _open_source(gdsfile, verbose):
 
 def _dsnode(src, nm: str) -> str:
     """``.dsnode`` (R/assoc_single.r:69-85)."""
+    if not isinstance(nm, str):
+        raise TypeError("is.character(dsnode) is not TRUE")
     if isinstance(src, GenotypeSource):
         return "$dosage_alt" if src.packed is not None else "annotation/format/DS"
     if nm == "":
@@ -121,53 +123,129 @@ def _dsnode(src, nm: str) -> str:
 
 
 def match_samples(src, mod):
-    """The model's samples in the genotype source -> (the source's sample ids, the indices ``sel`` of the model's
-    samples among them in the source's order, ``ii``: their rows in the model)."""
+    """The model's samples in the genotype source (R/assoc_single.r:135-142) -> (the source's sample ids, the indices
+    ``sel`` (int64) of the model's samples among them in the source's order, ``ii``: their rows in the model)."""
     gsid = [str(s) for s in src.sample_id()]
     pos = {str(s): i for i, s in enumerate(mod.sample_id)}
     sel = [i for i, s in enumerate(gsid) if s in pos]
     if len(sel) != len(mod.sample_id):
         raise ModelError("Some of sample IDs are not available in the GDS file.")
     ii = np.array([pos[gsid[i]] for i in sel], dtype=np.int64)
-    return gsid, sel, ii
+    return gsid, np.asarray(sel, dtype=np.int64), ii
 
 
-def dosage_matrix(src: "GenotypeSource", n_all: int) -> np.ndarray:
-    """The dosages of an in-memory source: a [variant, sample] matrix of uint8, int32 or float64."""
-    ds_all = np.asarray(src.dosage)
-    if ds_all.ndim != 2 or ds_all.shape[1] != n_all or ds_all.dtype not in (np.uint8, np.int32, np.float64):
-        raise TypeError("the dosages should be a [variant, sample] matrix of uint8, int32 or float64")
-    return ds_all
+@dataclass(frozen=True)
+class ScanInput:
+    """The opened input of one driver call (``open_scan_input``): where the genotypes come from, which of the source's
+    samples are the model's, and how rows are read for them.  Nothing is decoded when it is made (the reference never
+    holds more than one block of .bl_size variants either, R/assoc_single.r:202-209)."""
+    src: Any                    # GenotypeSource or GdsFile
+    in_mem: bool                # src is a GenotypeSource
+    node: str                   # "$dosage_alt", or the dosage node
+    kind: str                   # "packed": 2-bit hard calls; "dosage": rows decoded on the host; "stored": a packed-real
+    #                             or float32 node, whose rows can cross PCIe as the file stores them
+    n_var: int
+    n_all: int                  # samples of the source
+    gsid: List[str]             # their ids
+    sel: np.ndarray             # int64: the model's samples among them, in the source's order
+    ii: np.ndarray              # int64: their rows in the model
+    all_samples: bool           # the source's samples are the model's, in order
+    packed: Optional[np.ndarray] = None     # in-memory 2-bit rows
+    ds_all: Optional[np.ndarray] = None     # in-memory dosage matrix
+    ds_dtype: Optional[np.dtype] = None     # dosage input: the type of the decoded rows
+
+    @property
+    def n_samp(self) -> int:
+        return self.sel.size
+
+    def sample_id(self) -> List[str]:
+        return [self.gsid[i] for i in self.sel]
+
+    def _select(self, rows: np.ndarray) -> np.ndarray:
+        """2-bit rows of the source's samples -> of the model's."""
+        return rows if self.all_samples else pack_dosage_2bit(unpack_dosage_2bit(rows, self.n_all)[:, self.sel])
+
+    def packed_rows(self, off: int, end: int) -> np.ndarray:
+        """2-bit rows of variants [off, end) for the model's samples (host decoder)."""
+        if self.in_mem:
+            return self._select(self.packed[off:end])
+        return self.src.dosage_alt_packed_range(off, end, None if self.all_samples else self.sel)
+
+    def packed_rows_at(self, idx: np.ndarray) -> np.ndarray:
+        """... of the variants ``idx`` (0-based, ascending); a file is decoded whole, once."""
+        return np.ascontiguousarray(self._select((self.packed if self.in_mem else self.src.dosage_alt_packed()[0])[idx]))
+
+    def read_block(self, off: int, end: int):
+        """Genotypes of variants [off, end) for the model's samples, as ``scan_blocks`` takes them."""
+        sel = None if self.all_samples else self.sel
+        if self.kind == "packed":
+            if not self.in_mem and GENOTYPE_DECODE == "device":
+                raw, bit0, reps = self.src.genotype_raw_range(off, end)
+                if reps is None or int(reps.max()) <= MAX_STORED_ROWS:      # (the host decoder has no such limit)
+                    return StoredGenotypes(raw, bit0, self.n_all, reps, sel, end - off)
+            return self.packed_rows(off, end)
+        if self.kind == "stored":
+            return PackedRows(*self.src.dosage_raw_range(self.node, off, end), sel)
+        blk = self.ds_all[off:end] if self.in_mem else self.src.dosage_real_range(self.node, off, end)
+        return blk if self.all_samples else np.ascontiguousarray(blk[:, self.sel])
+
+    def stored_ok(self, scanner_factory) -> bool:
+        """A packed-real or float32 node goes to the device as stored: the variants are picked on the host, the
+        samples there.  (An injected scanner -- the tests' CPU stand-in for the device -- has no such load: decoded
+        rows.)"""
+        return self.kind == "stored" and scanner_factory is None
+
+    def dosage_reader(self, stored: bool):
+        """``read_rows(v0)`` of the dosage drivers: 0-based variant indices, ascending -> their rows for the model's
+        samples.  ``stored`` (``stored_ok``): ``PackedRows`` [len, n_all] of the file's samples, the model's picked
+        on the device; else decoded rows [len, n_samp] of ``ds_dtype``."""
+        src, node = self.src, self.node
+
+        def read_stored(v0):
+            step = packed_block_size(src.dosage_raw_row_bytes(node))
+            parts, meta = [], None
+            for a in range(int(v0[0]), int(v0[-1]) + 1, step):          # the range in pieces of a bounded size
+                pick = v0[(v0 >= a) & (v0 < a + step)]
+                if pick.size:
+                    raw, *meta = src.dosage_raw_range(node, int(pick[0]), int(pick[-1]) + 1)
+                    parts.append(raw[pick - pick[0]])
+            return PackedRows(np.concatenate(parts), *meta, None if self.all_samples else self.sel)
+
+        def read_rows(v0):
+            if self.in_mem:
+                rows = self.ds_all[v0]
+            else:
+                lo = int(v0[0])
+                rows = src.dosage_real_range(node, lo, int(v0[-1]) + 1)[v0 - lo]
+            return np.ascontiguousarray(rows if self.all_samples else rows[:, self.sel], dtype=self.ds_dtype)
+        return read_stored if stored else read_rows
 
 
-def dosage_row_reader(src, node, ds_all, ds_dtype, sel, n_all, stored):
-    """``read_rows(v0)`` of the dosage drivers: 0-based variant indices, ascending -> their rows for the model's
-    samples ``sel``.  ``ds_all``: the matrix of an in-memory source, else the rows are read from ``node`` of the file.
-    ``stored``: a packed-real or float32 node goes to the device as stored -- the variants are picked here, the samples
-    there (``PackedRows`` [len, n_all], the file's samples); else decoded rows [len, n_samp] of ``ds_dtype``."""
-    sel_a = np.asarray(sel, dtype=np.int64)
-    whole = len(sel) == n_all and np.array_equal(sel_a, np.arange(n_all))
-
-    def read_stored(v0):
-        step = packed_block_size(src.dosage_raw_row_bytes(node))
-        parts, meta = [], None
-        for a in range(int(v0[0]), int(v0[-1]) + 1, step):          # the range in pieces of a bounded size
-            pick = v0[(v0 >= a) & (v0 < a + step)]
-            if pick.size:
-                raw, *meta = src.dosage_raw_range(node, int(pick[0]), int(pick[-1]) + 1)
-                parts.append(raw[pick - pick[0]])
-        return PackedRows(np.concatenate(parts), *meta, None if whole else sel_a)
-
-    def read_rows(v0):
-        if stored:
-            return read_stored(v0)
-        if ds_all is not None:
-            rows = ds_all[v0]
-        else:
-            lo = int(v0[0])
-            rows = src.dosage_real_range(node, lo, int(v0[-1]) + 1)[v0 - lo]
-        return np.ascontiguousarray(rows if whole else rows[:, sel_a], dtype=ds_dtype)
-    return read_rows
+def open_scan_input(gdsfile, mod, dsnode: str, verbose: bool, any_matrix: bool = False) -> ScanInput:
+    """Open the genotype source of a driver call, match the model's samples in it and classify it.  An in-memory
+    dosage matrix is [variant, sample] of uint8, int32 or float64, unless ``any_matrix`` (the single-variant driver:
+    its scanner converts what it is given)."""
+    src = _open_source(gdsfile, verbose)
+    gsid, sel, ii = match_samples(src, mod)
+    node = _dsnode(src, dsnode)
+    in_mem, n_all = isinstance(src, GenotypeSource), len(gsid)
+    packed = ds_all = ds_dtype = None
+    if in_mem and src.packed is not None:
+        kind, packed, n_var = "packed", src.packed, src.packed.shape[0]
+    elif in_mem:
+        ds_all = src.dosage if any_matrix else np.asarray(src.dosage)
+        if not any_matrix and (ds_all.ndim != 2 or ds_all.shape[1] != n_all or ds_all.dtype not in (np.uint8, np.int32, np.float64)):
+            raise TypeError("the dosages should be a [variant, sample] matrix of uint8, int32 or float64")
+        kind, n_var, ds_dtype = "dosage", ds_all.shape[0], ds_all.dtype
+    elif node == "$dosage_alt":
+        kind = "packed"
+        n_var, n_all = src.genotype_dims()
+    else:
+        kind = "dosage" if src.dosage_raw_class(node) is None else "stored"
+        n_var, n_all = src.node(node + "/data").dims[:2]
+        ds_dtype = np.dtype(np.float64)
+    all_samples = sel.size == n_all and np.array_equal(sel, np.arange(n_all))
+    return ScanInput(src, in_mem, node, kind, n_var, n_all, gsid, sel, ii, all_samples, packed, ds_all, ds_dtype)
 
 
 def _pretty(n: int) -> str:
@@ -176,6 +254,43 @@ def _pretty(n: int) -> str:
 
 def _is_num(x) -> bool:
     return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+
+def check_scan_args(maf, mac, missing, spa_pval, var_ratio, dsnode, res_savefn, res_compress, verbose=True):
+    """The argument checks of R/assoc_single.r:96-107, in its order."""
+    for nm, v in (("maf", maf), ("mac", mac), ("missing", missing), ("spa.pval", spa_pval), ("var.ratio", var_ratio)):
+        if not _is_num(v):
+            raise TypeError(f"is.numeric({nm}) is not TRUE")
+    if not isinstance(dsnode, str):
+        raise TypeError("is.character(dsnode) is not TRUE")
+    if not isinstance(res_savefn, str):
+        raise TypeError("is.character(res.savefn) is not TRUE")
+    if res_compress not in ("LZMA", "LZMA_RA", "ZIP", "ZIP_RA", "none"):
+        raise ValueError("`res.compress` should be one of LZMA, LZMA_RA, ZIP, ZIP_RA and none.")
+    if not isinstance(verbose, bool):
+        raise TypeError("is.logical(verbose) is not TRUE")
+
+
+def require_device(what: str) -> int:
+    """The number of visible devices; none is an error (there is no CPU path)."""
+    from ._lib import load
+    ndev = load().sgx_device_count()
+    if ndev <= 0:
+        raise RuntimeError(f"{what}: no MI355X device is visible (there is no CPU fallback)")
+    return ndev
+
+
+def finish_result(ans, res_savefn: str, res_compress: str, verbose: bool, sample_id):
+    """The tail of a scan driver (R/assoc_single.r:236-334): the table, or None once it is saved to ``res_savefn``."""
+    if res_savefn:
+        from .results import save_result
+        if verbose:
+            print(f"Save to '{res_savefn}' ...")
+        save_result(ans, res_savefn, res_compress, sample_id=sample_id)
+        ans = None
+    if verbose:
+        print("Done.")
+    return ans
 
 
 def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, maf: float = float("nan"),
@@ -189,19 +304,7 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     mac, num, beta, SE, pval and, for binary traits, p.norm, converged
     (man/seqAssocGLMM_SPA.Rd:60-74).
     """
-    # argument checks, R/assoc_single.r:96-107
-    for nm, v in (("maf", maf), ("mac", mac), ("missing", missing), ("spa.pval", spa_pval),
-                  ("var.ratio", var_ratio)):
-        if not _is_num(v):
-            raise TypeError(f"is.numeric({nm}) is not TRUE")
-    if not isinstance(dsnode, str):
-        raise TypeError("is.character(dsnode) is not TRUE")
-    if not isinstance(res_savefn, str):
-        raise TypeError("is.character(res.savefn) is not TRUE")
-    if res_compress not in ("LZMA", "LZMA_RA", "ZIP", "ZIP_RA", "none"):
-        raise ValueError("`res.compress` should be one of LZMA, LZMA_RA, ZIP, ZIP_RA and none.")
-    if not isinstance(verbose, bool):
-        raise TypeError("is.logical(verbose) is not TRUE")
+    check_scan_args(maf, mac, missing, spa_pval, var_ratio, dsnode, res_savefn, res_compress, verbose)
     if verbose:
         print("SAIGE association analysis:")
 
@@ -209,31 +312,9 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         raise ValueError("saigegds_amd.assoc.GENOTYPE_DECODE should be 'device' or 'host'.")
     mod: NullModel = load_modobj(modobj, verbose)
     src = _open_source(gdsfile, verbose)
-    node = _dsnode(src, dsnode)
-
-    # sample matching, R/assoc_single.r:135-142
-    gsid = [str(s) for s in src.sample_id()]
-    pos = {str(s): i for i, s in enumerate(mod.sample_id)}
-    sel = [i for i, s in enumerate(gsid) if s in pos]
-    if len(sel) != len(mod.sample_id):
-        raise ModelError("Some of sample IDs are not available in the GDS file.")
-    ii = np.array([pos[gsid[i]] for i in sel], dtype=np.int64)
-    sel = np.asarray(sel, dtype=np.int64)
-    n_samp = sel.size
-
-    # where the genotypes come from; nothing is decoded yet (the reference never holds more than one
-    # block of .bl_size variants either, R/assoc_single.r:202-209)
-    if isinstance(src, GenotypeSource):
-        kind = "packed" if src.packed is not None else "dosage"
-        n_all = len(gsid)
-        n_var = (src.packed if src.packed is not None else src.dosage).shape[0]
-    elif node == "$dosage_alt":
-        kind = "packed"
-        n_var, n_all = src.genotype_dims()
-    else:
-        # packed-real and float32 nodes go to the device as stored; dFloat64 / integer nodes are decoded here
-        kind = "dosage" if src.dosage_raw_class(node) is None else "stored"
-        n_var, n_all = src.node(node + "/data").dims[:2]
+    _dsnode(src, dsnode)      # (a file without dosages is refused before its samples are looked at, R/assoc_single.r:133)
+    inp = open_scan_input(src, mod, dsnode, verbose, any_matrix=True)
+    kind, n_samp, n_var, ii = inp.kind, inp.n_samp, inp.n_var, inp.ii
     if verbose:
         print(f"    # of samples: {_pretty(n_samp)}")
         print(f"    # of variants: {_pretty(n_var)}")
@@ -249,40 +330,15 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         raise ValueError("No sample in the genotypic data set!")
     if n_var <= 0:
         raise ValueError("No variant in the genotypic data set!")
-    all_samples = n_samp == n_all and np.array_equal(sel, np.arange(n_all))
-
-    def read_block(off: int, end: int):
-        """Genotypes of variants [off, end) for the selected samples."""
-        if isinstance(src, GenotypeSource):
-            if kind == "packed":
-                blk = src.packed[off:end]
-                if not all_samples:
-                    blk = pack_dosage_2bit(unpack_dosage_2bit(blk, n_all)[:, sel])
-                return blk
-            blk = src.dosage[off:end]
-            return blk if all_samples else np.ascontiguousarray(blk[:, sel])
-        if kind == "packed" and GENOTYPE_DECODE == "device":
-            raw, bit0, reps = src.genotype_raw_range(off, end)
-            if reps is not None and int(reps.max()) > MAX_STORED_ROWS:      # (the host decoder has no such limit)
-                return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
-            return StoredGenotypes(raw, bit0, n_all, reps, None if all_samples else sel, end - off)
-        if kind == "packed":
-            return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
-        if kind == "stored":
-            return PackedRows(*src.dosage_raw_range(node, off, end), None if all_samples else sel)
-        blk = src.dosage_real_range(node, off, end)
-        return blk if all_samples else np.ascontiguousarray(blk[:, sel])
 
     mobj: ScanModel = init_nullmod(mod, ii, maf, mac, missing, spa_pval, var_ratio)
     if mod.trait_type not in ("binary", "quantitative"):
         raise ModelError("Invalid 'modobj$trait.type'.")
 
     # devices, R/assoc_single.r:167-171 ('parallel' = number of GPUs here)
-    from ._lib import Scanner, load
+    from ._lib import Scanner
     ngpu = 1 if parallel in (False, None, 0, 1) else int(parallel)
-    ndev = load().sgx_device_count()
-    if ndev <= 0:
-        raise RuntimeError("seqAssocGLMM_SPA: no MI355X device is visible (there is no CPU fallback)")
+    ndev = require_device("seqAssocGLMM_SPA")
     if ngpu > ndev:
         raise ValueError(f"parallel={ngpu} but only {ndev} GPU(s) are visible")
     if verbose:
@@ -294,18 +350,18 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     valid = np.zeros(n_var, dtype=np.uint8)
     bl_size = BLOCK_SIZE
     if kind == "stored":
-        bl_size = packed_block_size(src.dosage_raw_row_bytes(node))
-    elif kind == "packed" and not isinstance(src, GenotypeSource) and GENOTYPE_DECODE == "device":
+        bl_size = packed_block_size(src.dosage_raw_row_bytes(inp.node))
+    elif kind == "packed" and not inp.in_mem and GENOTYPE_DECODE == "device":
         bl_size = packed_block_size(src.genotype_raw_row_bytes())      # a stored row is twice a 2-bit row
     t_loop = time.perf_counter()
     if not mod.loco:
         blocks = [(off, min(n_var, off + bl_size)) for off in range(0, n_var, bl_size)]
-        scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, read_block, kind == "packed", out, valid, timing)
+        scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, inp.read_block, kind == "packed", out, valid, timing)
     else:
         # leave-one-chromosome-out: the block list is cut at chromosome boundaries, and every run of one
         # chromosome is scanned against that chromosome's model (its fitted values; y, V, XV, XXVX_inv and
         # the variance ratio are the full model's) by scanners of its own, freed before the next run
-        chrom = [str(c) for c in (src.chromosome if isinstance(src, GenotypeSource) else src.read("chromosome"))]
+        chrom = [str(c) for c in (src.chromosome if inp.in_mem else src.read("chromosome"))]
         reported = set()
         for r0, r1, ch in chromosome_runs(chrom):
             if ch in mod.loco:
@@ -316,7 +372,7 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
                     print(f"    chromosome '{ch}' has no leave-one-chromosome-out model: the full model is used")
                 reported.add(ch)
             blocks = [(off, min(r1, off + bl_size)) for off in range(r0, r1, bl_size)]
-            scan_blocks(lambda d, o=run_obj: Scanner(o, device=d), ngpu, blocks, read_block, kind == "packed", out, valid,
+            scan_blocks(lambda d, o=run_obj: Scanner(o, device=d), ngpu, blocks, inp.read_block, kind == "packed", out, valid,
                         timing)
     if timing is not None:
         timing["blocks_s"] = time.perf_counter() - t_loop      # handles + every block (decode and scan overlapped)
@@ -325,19 +381,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     if verbose:
         print("# of variants after filtering by MAF, MAC and missing thresholds: "
               f"{_pretty(int(x.sum()))}")
-    ans = assemble_result(src, x, out, mod.trait_type)
-
-    if res_savefn:
-        from .results import save_result
-        if verbose:
-            print(f"Save to '{res_savefn}' ...")
-        save_result(ans, res_savefn, res_compress, sample_id=[gsid[i] for i in sel])
-        if verbose:
-            print("Done.")
-        return None
-    if verbose:
-        print("Done.")
-    return ans
+    return finish_result(assemble_result(src, x, out, mod.trait_type), res_savefn, res_compress, verbose,
+                         inp.sample_id() if res_savefn else None)
 
 
 def chromosome_runs(chrom):

@@ -28,9 +28,9 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .assoc import (BLOCK_SIZE, GenotypeSource, PackedRows, _dsnode, _is_num, _open_source, _pretty, assemble_result,
-                    dosage_matrix, dosage_row_reader, match_samples)
-from .gds import pack_dosage_2bit, unpack_dosage_2bit
+from . import aggregate
+from .assoc import (BLOCK_SIZE, GenotypeSource, PackedRows, ScanInput, _open_source, _pretty, assemble_result,
+                    check_scan_args, finish_result, open_scan_input, require_device)
 from .nullmod import ModelError, NullModel, init_nullmod, load_modobj, no_loco
 from .skat import spa_scale
 
@@ -110,21 +110,11 @@ def _check_set(cond_ids, out_c, valid_c):
             raise ValueError(f"`condition`: variant {v!r} has no valid genotype or is monomorphic.")
 
 
-def _scan_hard(sc, src, sel, n_all, n_var, cidx, cond_ids, thresholds):
+def _scan_hard(sc, inp: ScanInput, cidx, cond_ids, thresholds):
     """The hard-call route: 2-bit rows -> (res [n_var, 8 + 3 + C]: the scan table, valid, S_j, Phi_jj, Phi_jC; the
     set's scan table, S_C, Phi_CC)."""
     import torch
-    in_mem = isinstance(src, GenotypeSource)
-    n_samp = sel.size
-    all_samples = n_samp == n_all and np.array_equal(sel, np.arange(n_all))
-
-    def read_rows(off: int, end: int) -> np.ndarray:
-        """2-bit rows of variants [off, end) for the model's samples (host decoder)."""
-        if in_mem:
-            blk = src.packed[off:end]
-            return blk if all_samples else pack_dosage_2bit(unpack_dosage_2bit(blk, n_all)[:, sel])
-        return src.dosage_alt_packed_range(off, end, None if all_samples else sel)
-
+    n_samp, n_var, read_rows = inp.n_samp, inp.n_var, inp.packed_rows
     dev = torch.device(getattr(sc, "torch_device", "cuda"))
     nb = (n_samp + 3) // 4
 
@@ -165,19 +155,9 @@ def _scan_hard(sc, src, sel, n_all, n_var, cidx, cond_ids, thresholds):
     return res, out_c, S_C, Phi_CC
 
 
-def _flip_mean(n, s):
-    """The scan's own imputation and flip from a load's counts (n non-missing, s their double sum), as the SKAT
-    driver forms them: flip = s > n, mean = s / n or 2 - s / n."""
-    n = n.astype(np.float64)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        m = s / n
-    fl = s > n
-    return fl.astype(np.uint8), np.where(fl, 2 - m, m)
-
-
-def _scan_dosage(sc, read_rows, ds_dtype, n_samp, n_var, cidx, cond_ids, thresholds):
+def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds):
     """The dosage route: what ``_scan_hard`` returns, from resident dosage blocks."""
-    from . import aggregate
+    read_rows, ds_dtype, n_samp, n_var = inp.dosage_reader(stored), inp.ds_dtype, inp.n_samp, inp.n_var
 
     def load(blk, v0):
         rows = read_rows(v0)
@@ -197,7 +177,7 @@ def _scan_dosage(sc, read_rows, ds_dtype, n_samp, n_var, cidx, cond_ids, thresho
         out_c, valid_c = blk.scan()
         out_c, valid_c = out_c[rank], valid_c[rank]
         _check_set(cond_ids, out_c, valid_c)
-        fl, mean = _flip_mean(n, s)
+        fl, mean = aggregate.flip_mean(n, s)
         S_C, Phi_CC = blk.cond_set(rank, fl[rank], mean[rank])
         sc.set_thresholds(*thresholds)
     row_bytes = n_samp * (1 if np.dtype(ds_dtype) == np.uint8 else 8)
@@ -208,7 +188,7 @@ def _scan_dosage(sc, read_rows, ds_dtype, n_samp, n_var, cidx, cond_ids, thresho
             end = min(n_var, off + per)
             n, s, _ = load(blk, np.arange(off, end, dtype=np.int64))      # the one upload
             out8, valid = blk.scan()
-            score, var, cov = blk.cond(*_flip_mean(n, s))
+            score, var, cov = blk.cond(*aggregate.flip_mean(n, s))
             res[off:end, :8], res[off:end, 8], res[off:end, 9], res[off:end, 10], res[off:end, 11:] = out8, valid, score, var, cov
     return res, out_c, S_C, Phi_CC
 
@@ -230,15 +210,7 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     Result: the columns of ``seqAssocGLMM_SPA``, then ``beta.cond``, ``SE.cond``, ``pval.cond`` (``cond_tests``;
     ``beta.cond`` refers to the alt allele like ``beta``).  A variant of the set itself, or one the set explains,
     gets NaN there.  ``res_savefn``: ``.rds`` / ``.RData``; the ``.gds`` writer has fixed columns and is refused."""
-    for nm, v in (("maf", maf), ("mac", mac), ("missing", missing), ("spa.pval", spa_pval), ("var.ratio", var_ratio)):
-        if not _is_num(v):
-            raise TypeError(f"is.numeric({nm}) is not TRUE")
-    if not isinstance(dsnode, str):
-        raise TypeError("is.character(dsnode) is not TRUE")
-    if not isinstance(res_savefn, str):
-        raise TypeError("is.character(res.savefn) is not TRUE")
-    if res_compress not in ("LZMA", "LZMA_RA", "ZIP", "ZIP_RA", "none"):
-        raise ValueError("`res.compress` should be one of LZMA, LZMA_RA, ZIP, ZIP_RA and none.")
+    check_scan_args(maf, mac, missing, spa_pval, var_ratio, dsnode, res_savefn, res_compress)
     if re.search(r"\.gds$", res_savefn, re.I):
         raise ValueError("The gds output has no columns for the conditional test; save to RData or RDS.")
     try:
@@ -257,7 +229,6 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     in_mem = isinstance(src, GenotypeSource)
     if dsnode != "" and in_mem and src.packed is not None:
         raise NotImplementedError(_NO_DOSAGE)
-    dosage = dsnode != "" or (in_mem and src.packed is None) or (not in_mem and src.node("genotype/data", silent=True) is None)
     vid = np.asarray(src.variant_id if in_mem else src.read("variant.id"))
     where = {v: i for i, v in enumerate(vid.tolist())}
     unknown = [v for v in cond_ids if v not in where]
@@ -265,18 +236,10 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
         raise ValueError(f"`condition`: no variant with id {unknown[0]!r}.")
     cidx = [where[v] for v in cond_ids]
 
-    gsid, sel, ii = match_samples(src, mod)                    # as seqAssocGLMM_SPA
-    sel = np.asarray(sel, dtype=np.int64)
-    n_samp, n_all = sel.size, len(gsid)
-    ds_all = node = None
-    if not dosage:
-        n_var = src.packed.shape[0] if in_mem else src.genotype_dims()[0]
-    elif in_mem:
-        ds_all = dosage_matrix(src, n_all)
-        n_var = ds_all.shape[0]
-    else:
-        node = _dsnode(src, dsnode)
-        n_var = src.node(node + "/data").dims[0]
+    inp = open_scan_input(src, mod, dsnode, verbose)
+    if dsnode != "" and inp.kind == "packed":
+        src.node(dsnode + "/data")      # a named node is a dosage node here: "$dosage_alt" is refused as the missing node it is
+    n_samp, n_var = inp.n_samp, inp.n_var
     if n_samp <= 0:
         raise ValueError("No sample in the genotypic data set!")
     if n_var <= 0:
@@ -288,25 +251,22 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
         print(f"    # of variants: {_pretty(n_var)}")
         print(f"    # of conditioning variants: {len(cidx)}")
 
-    mobj = init_nullmod(mod, ii, maf, mac, missing, spa_pval, var_ratio)
+    mobj = init_nullmod(mod, inp.ii, maf, mac, missing, spa_pval, var_ratio)
     if mod.trait_type not in ("binary", "quantitative"):
         raise ModelError("Invalid 'modobj$trait.type'.")
     binary = mod.trait_type == "binary"
-    stored = dosage and ds_all is None and scanner_factory is None and src.dosage_raw_class(node) is not None
+    stored = inp.stored_ok(scanner_factory)
     if scanner_factory is None:
-        from ._lib import Scanner, load
-        if load().sgx_device_count() <= 0:
-            raise RuntimeError("seqAssocGLMM_SPA_cond: no MI355X device is visible (there is no CPU fallback)")
+        from ._lib import Scanner
+        require_device("seqAssocGLMM_SPA_cond")
         scanner_factory = Scanner
     sc = scanner_factory(mobj)
     try:
         thresholds = (float(maf), float(mac), float(missing), float(spa_pval))
-        if dosage:
-            ds_dtype = np.dtype(np.float64) if ds_all is None else ds_all.dtype
-            read_rows = dosage_row_reader(src, node, ds_all, ds_dtype, sel, n_all, stored)
-            res, out_c, S_C, Phi_CC = _scan_dosage(sc, read_rows, ds_dtype, n_samp, n_var, cidx, cond_ids, thresholds)
+        if inp.kind == "packed":
+            res, out_c, S_C, Phi_CC = _scan_hard(sc, inp, cidx, cond_ids, thresholds)
         else:
-            res, out_c, S_C, Phi_CC = _scan_hard(sc, src, sel, n_all, n_var, cidx, cond_ids, thresholds)
+            res, out_c, S_C, Phi_CC = _scan_dosage(sc, inp, stored, cidx, cond_ids, thresholds)
     finally:
         sc.close()
 
@@ -322,14 +282,4 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     beta, se, p = cond_tests(S, var, cov, S_C, Phi_CC, d, d_C)
     ans["beta.cond"] = np.where(o[:, 0] > 0.5, -beta, beta)        # S is the flipped row's: back to the alt allele
     ans["SE.cond"], ans["pval.cond"] = se, p
-    if res_savefn:
-        from .results import save_result
-        if verbose:
-            print(f"Save to '{res_savefn}' ...")
-        save_result(ans, res_savefn, res_compress, sample_id=[gsid[i] for i in sel])
-        if verbose:
-            print("Done.")
-        return None
-    if verbose:
-        print("Done.")
-    return ans
+    return finish_result(ans, res_savefn, res_compress, verbose, inp.sample_id() if res_savefn else None)

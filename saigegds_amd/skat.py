@@ -24,7 +24,7 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .aggregate import AggrParamBeta, _dbeta, _prepare, _save, _summary_cols
+from .aggregate import AggrParamBeta, _dbeta, _prepare, _save, _summary_cols, flip_mean
 from .assoc import GenotypeSource
 
 LAMBDA_DROP = 1e-10      # eigenvalues at or below this fraction of the largest one are dropped
@@ -200,12 +200,9 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
             kept = [np.asarray(r, dtype=np.int64)[ok[np.asarray(r, dtype=np.int64)]] for r in pr.rows]
             var_idx = np.concatenate(kept).astype(np.int32) if kept else np.zeros(0, dtype=np.int32)
             unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])]).astype(np.int64)
-            n, s = pr.n[var_idx], pr.s[var_idx]
-            with np.errstate(invalid="ignore", divide="ignore"):
-                m = s / n                                               # (double)sum / n, as _burden_rows
-            flip = s > n
-            lut = np.where(flip[:, None], np.stack([2 + 0 * m, 1 + 0 * m, 0 * m, 2 - m], axis=1),
-                           np.stack([0 * m, 1 + 0 * m, 2 + 0 * m, m], axis=1))
+            flip, m = flip_mean(pr.n[var_idx], pr.s[var_idx])         # (double)sum / n, as _burden_rows
+            z = 0 * m
+            lut = np.where(flip[:, None] != 0, np.stack([z + 2, z + 1, z, m], axis=1), np.stack([z, z + 1, z + 2, m], axis=1))
             score, cov = pr.sc.skat_2bit(pr.packed, unit_ptr, var_idx, lut)
             S_of, phi_of = (lambda u: score[unit_ptr[u]:unit_ptr[u + 1]]), cov.__getitem__
     finally:
