@@ -588,6 +588,36 @@ int  sgx_grm_dense_kernel_ms(sgx_grm *g, double *ms_out);
 int  sgx_grm_sparse(sgx_grm *g, double cutoff, size_t cap, int32_t *i_out, int32_t *j_out, double *v_out,
 	size_t *n_out, sgx_grm_sparse_stats *stats);
 
+/* Operator of an explicit symmetric matrix K [n][n] resident on one device: the null-model fit on the matrix
+ * sgx_grm_sparse / sgx_grm_dense made (SAIGE's useSparseGRMtoFitNULL, upstream SAIGEgds 2.x grm.mat=; not in the
+ * reference, which has the implicit operator only: DESIGN.md 8f).
+ *   sgx_kmat_init_csr    the full symmetric pattern (both triangles): row_ptr[n + 1] from 0, columns strictly
+ *                        ascending within a row.  A row may be empty; a row without a diagonal entry has diag 0.
+ *                        SGX_EINVAL: unsorted or duplicate columns, a column outside 0..n-1, a row_ptr that
+ *                        decreases or does not start at 0, a non-finite value, n < 1.
+ *   sgx_kmat_init_dense  row-major K with ld >= n, copied to the device; SGX_EINVAL above 8 GiB (8 n^2 bytes).
+ * The other entry points follow their sgx_grm_* namesakes: host vectors, column j at B + j * ldb, Out / X with the
+ * same ldb, 1 <= k <= SGX_GRM_MAX_RHS, ldb >= n, SGX_EINVAL otherwise; the _dev form takes device pointers and is
+ * asynchronous until sgx_kmat_sync.  sgx_kmat_pcg_multi solves (tau[0] diag(1/w) + tau[1] K) x = b by the loop of
+ * sgx_grm_pcg_multi (the same preconditioner floor, per-column scalars and exits; no product when tau[1] == 0).
+ * The bits of (K b)_i depend on row i's stored entries and on b only: not on k, on the other columns of the call,
+ * on the other rows or on earlier calls.  CSR rows with fewer than SGX_KMAT_WAVE_ROW entries are summed by one
+ * thread in ascending column order; longer rows by a wave, lane-strided, with a fixed reduction tree.
+ *   sgx_kmat_matvec_ms   milliseconds the kernels of the last product took on the device (waits for them) */
+#define SGX_KMAT_WAVE_ROW 33
+typedef struct sgx_kmat sgx_kmat;
+int  sgx_kmat_init_csr(int32_t n, const int64_t *row_ptr, const int32_t *col, const double *val, int device,
+	sgx_kmat **out);
+int  sgx_kmat_init_dense(const double *K, size_t ld, int32_t n, int device, sgx_kmat **out);
+void sgx_kmat_free(sgx_kmat *m);
+int  sgx_kmat_sync(sgx_kmat *m);
+int  sgx_kmat_diag(sgx_kmat *m, double *diag_out);
+int  sgx_kmat_crossprod_multi(sgx_kmat *m, const double *B, size_t ldb, int k, double *Out);
+int  sgx_kmat_crossprod_multi_dev(sgx_kmat *m, const double *B_dev, size_t ldb, int k, double *Out_dev);
+int  sgx_kmat_pcg_multi(sgx_kmat *m, const double *w, const double *tau, const double *B, size_t ldb, int k,
+	int maxiter, double tol, double *X_out, int *iters);
+int  sgx_kmat_matvec_ms(sgx_kmat *m, double *ms_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ Public surface (mirrors the reference's R API for this path):
     seqAssocGLMM_spaSKAT  variance-component set test (not in the reference)
     seqAssocGLMM_SPA_cond scan given a set of conditioning variants (not in the reference)
     seqFitDenseGRM, seqFitSparseGRM  the explicit GRM, dense and thresholded (not in the reference)
+    load_grm, ExplicitGrmOperator    read it back; the operator seqFitNullGLMM_SPA(grm_mat=) fits on
     seqSAIGE_LoadPval  load saved association results     (R/saige_main.r:164-215)
 The compute lives in libsaigehip.so (include/saigehip.h); there is no CPU path.
 """
@@ -19,7 +20,8 @@ from .aggregate import (AggrParamBeta, pACAT, pACAT2, seqAssocGLMM_spaACAT_O, se
                         seqAssocGLMM_spaBurden)
 from .skat import pchisq_mix, seqAssocGLMM_spaSKAT  # noqa: F401
 from .cond import cond_tests, seqAssocGLMM_SPA_cond  # noqa: F401
-from .grm import SparseGRM, seqFitDenseGRM, seqFitSparseGRM  # noqa: F401
+from .grm import SparseGRM, load_grm, seqFitDenseGRM, seqFitSparseGRM  # noqa: F401
+from ._lib import ExplicitGrmOperator  # noqa: F401
 from .results import seqSAIGE_LoadPval  # noqa: F401
 
 __version__ = "0.1.0"

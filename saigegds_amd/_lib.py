@@ -23,6 +23,8 @@ EXPORTS = (
     "sgx_grm_crossprod_multi", "sgx_grm_crossprod_multi_dev", "sgx_grm_pcg_multi",
     "sgx_grm_set_groups", "sgx_grm_group_sizes", "sgx_grm_diag_loco", "sgx_grm_crossprod_loco", "sgx_grm_pcg_loco",
     "sgx_grm_dense", "sgx_grm_dense_kernel_ms", "sgx_grm_sparse",
+    "sgx_kmat_init_csr", "sgx_kmat_init_dense", "sgx_kmat_free", "sgx_kmat_sync", "sgx_kmat_diag",
+    "sgx_kmat_crossprod_multi", "sgx_kmat_crossprod_multi_dev", "sgx_kmat_pcg_multi", "sgx_kmat_matvec_ms",
     "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
     "sgx_scan_packed", "sgx_ds_block_load_packed",
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
@@ -33,6 +35,7 @@ EXPORTS = (
 
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
 GRM_MAX_GROUPS = 64   # SGX_GRM_MAX_GROUPS: marker groups of one GRM handle
+KMAT_WAVE_ROW = 33    # SGX_KMAT_WAVE_ROW: CSR rows of sgx_kmat with at least this many entries take the wave form
 ENOSPACE = -5         # SGX_ENOSPACE: sgx_grm_sparse found more entries than the buffers hold
 SKAT_MAX_VARIANTS = 4096   # SGX_SKAT_MAX_VARIANTS: entries of one unit of sgx_skat_2bit
 COND_MAX = 16         # SGX_COND_MAX: conditioning variants of one sgx_cond_set
@@ -291,6 +294,24 @@ def load():
     L.sgx_grm_dense_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.sgx_grm_sparse.restype = C.c_int
     L.sgx_grm_sparse.argtypes = [vp, C.c_double, sz, vp, vp, vp, C.POINTER(sz), C.POINTER(SgxGrmSparseStats)]
+    L.sgx_kmat_init_csr.restype = C.c_int
+    L.sgx_kmat_init_csr.argtypes = [C.c_int32, vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.sgx_kmat_init_dense.restype = C.c_int
+    L.sgx_kmat_init_dense.argtypes = [vp, sz, C.c_int32, C.c_int, C.POINTER(vp)]
+    L.sgx_kmat_free.restype = None
+    L.sgx_kmat_free.argtypes = [vp]
+    L.sgx_kmat_sync.restype = C.c_int
+    L.sgx_kmat_sync.argtypes = [vp]
+    L.sgx_kmat_diag.restype = C.c_int
+    L.sgx_kmat_diag.argtypes = [vp, vp]
+    L.sgx_kmat_crossprod_multi.restype = C.c_int
+    L.sgx_kmat_crossprod_multi.argtypes = [vp, vp, sz, C.c_int, vp]
+    L.sgx_kmat_crossprod_multi_dev.restype = C.c_int
+    L.sgx_kmat_crossprod_multi_dev.argtypes = [vp, vp, sz, C.c_int, vp]
+    L.sgx_kmat_pcg_multi.restype = C.c_int
+    L.sgx_kmat_pcg_multi.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int, dp, vp, vp]
+    L.sgx_kmat_matvec_ms.restype = C.c_int
+    L.sgx_kmat_matvec_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.sgx_grm_pcg_loco.restype = C.c_int
     L.sgx_grm_pcg_loco.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, sz, C.c_int, vp, C.c_int, dp, vp, vp]
     _lib = L
@@ -1027,3 +1048,130 @@ class GrmOperator:
                                            tau.ctypes.data, B[j0].ctypes.data, self.n, k, e[j0:].ctypes.data,
                                            int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
         return X, iters
+
+
+def csr_of_upper(n: int, i, j, x):
+    """The full symmetric CSR (row_ptr int64 [n + 1], col int32, val float64; columns ascending within a row) of
+    a matrix given by its upper triangle (i <= j, each pair once)."""
+    i, j = np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64)
+    x = np.asarray(x, dtype=np.float64)
+    off = i != j
+    rows, cols = np.concatenate([i, j[off]]), np.concatenate([j, i[off]])
+    vals = np.concatenate([x, x[off]])
+    o = np.lexsort((cols, rows))
+    row_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=row_ptr[1:])
+    return row_ptr, np.ascontiguousarray(cols[o], dtype=np.int32), np.ascontiguousarray(vals[o])
+
+
+class ExplicitGrmOperator:
+    """Operator of an explicit GRM resident on one GPU (``sgx_kmat``): what ``seqFitNullGLMM_SPA(grm_mat=)`` fits
+    the null model on.  ``grm``: a ``SparseGRM`` (its upper triangle is expanded to the full CSR here) or a square
+    float64 array (dense storage).  Products and solves as ``GrmOperator``.  ``csr=(row_ptr, col, val)`` instead of
+    ``grm`` hands a CSR to the library as it is; ``n`` / ``ld`` override the size and the row stride the library
+    is told (its argument checks are tested this way)."""
+
+    def __init__(self, grm=None, device: int = 0, csr=None, n: Optional[int] = None, ld: Optional[int] = None):
+        L = load()
+        self._L = L
+        h = C.c_void_p()
+        if csr is not None:
+            rp = np.ascontiguousarray(csr[0], dtype=np.int64)
+            col = np.ascontiguousarray(csr[1], dtype=np.int32)
+            val = np.ascontiguousarray(csr[2], dtype=np.float64)
+            self.n = int(rp.size - 1 if n is None else n)
+            self.storage = "csr"
+            check(L.sgx_kmat_init_csr(self.n, rp.ctypes.data, col.ctypes.data, val.ctypes.data, int(device), C.byref(h)))
+        elif hasattr(grm, "i") and hasattr(grm, "x"):
+            self.n = int(grm.n)
+            self.storage = "csr"
+            rp, col, val = csr_of_upper(self.n, grm.i, grm.j, grm.x)
+            check(L.sgx_kmat_init_csr(self.n, rp.ctypes.data, col.ctypes.data, val.ctypes.data, int(device), C.byref(h)))
+        else:
+            K = np.ascontiguousarray(grm, dtype=np.float64)       # (with ld: [n, ld], the matrix in its first n columns)
+            if K.ndim != 2 or (ld is None and K.shape[0] != K.shape[1]):
+                raise ValueError("the GRM must be a square matrix")
+            self.n = int(K.shape[0] if n is None else n)
+            self.storage = "dense"
+            check(L.sgx_kmat_init_dense(K.ctypes.data, int(K.shape[1] if ld is None else ld), self.n, int(device),
+                                        C.byref(h)))
+        self._h = h
+
+    def sync(self):
+        check(self._L.sgx_kmat_sync(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.sgx_kmat_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def diag(self) -> np.ndarray:
+        out = np.empty(self.n, dtype=np.float64)
+        check(self._L.sgx_kmat_diag(self._h, out.ctypes.data))
+        return out
+
+    def matvec_ms(self) -> float:
+        """Device milliseconds of the kernels of the last product."""
+        ms = C.c_double(0)
+        check(self._L.sgx_kmat_matvec_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def _rhs(self, B) -> np.ndarray:
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[1] != self.n:
+            raise ValueError("B must be [k, N]: one right-hand side of N samples per row")
+        return B
+
+    def crossprod_many(self, B: np.ndarray) -> np.ndarray:
+        """K b_j for every row b_j of B ([k, N] -> [k, N]); row j equals crossprod(B[j]) bit for bit."""
+        B = self._rhs(B)
+        out = np.empty_like(B)
+        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
+            k = min(GRM_MAX_RHS, B.shape[0] - j0)
+            check(self._L.sgx_kmat_crossprod_multi(self._h, B[j0].ctypes.data, self.n, k, out[j0].ctypes.data))
+        return out
+
+    def crossprod(self, b: np.ndarray) -> np.ndarray:
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (self.n,):
+            raise ValueError("b must have one entry per sample")
+        return self.crossprod_many(b[None, :])[0]
+
+    def crossprod_many_dev(self, b_ptr: int, ldb: int, k: int, out_ptr: int):
+        """Device form: k vectors at b_ptr + j * ldb doubles (asynchronous until sync())."""
+        check(self._L.sgx_kmat_crossprod_multi_dev(self._h, b_ptr, int(ldb), int(k), out_ptr))
+
+    def pcg_many(self, w: np.ndarray, tau, B: np.ndarray, maxiter: int = 500, tol: float = 1e-5):
+        """pcg on every row of B in lockstep -> (X [k, N], iters [k]); row j equals pcg(w, tau, B[j])
+        bit for bit, with the same iteration count."""
+        B = self._rhs(B)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (self.n,):
+            raise ValueError("w must have one entry per sample")
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        X = np.empty_like(B)
+        iters = np.zeros(B.shape[0], dtype=np.int32)
+        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
+            k = min(GRM_MAX_RHS, B.shape[0] - j0)
+            check(self._L.sgx_kmat_pcg_multi(self._h, w.ctypes.data, tau.ctypes.data, B[j0].ctypes.data, self.n, k,
+                                             int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
+        return X, iters
+
+    def pcg(self, w: np.ndarray, tau, b: np.ndarray, maxiter: int = 500, tol: float = 1e-5):
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (self.n,):
+            raise ValueError("b must have one entry per sample")
+        X, it = self.pcg_many(w, tau, b[None, :], maxiter, tol)
+        return X[0], int(it[0])

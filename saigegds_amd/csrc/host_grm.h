@@ -10,8 +10,6 @@
 // columns thus streams the genotypes three times (G once, Gt twice) where 6 single products stream
 // them 12 times.
 
-#define GRM_RED_BLOCKS 256
-
 struct sgx_grm {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -24,19 +22,13 @@ struct sgx_grm {
 	int *accV = nullptr, *accS = nullptr;            // [M][32 GRM_MAXF], [N][32 GRM_MAXF]
 	double *xv = nullptr, *gv = nullptr;             // [GRM_GROUP][M]
 	unsigned long long *maxb = nullptr;              // [GRM_MAX_RHS][3]: b, x, gam
-	double *part = nullptr, *h_part = nullptr;       // [2 * GRM_MAX_RHS][GRM_RED_BLOCKS] block partials (device / pinned)
-	double *minv = nullptr, *w = nullptr;            // [N]
+	PcgWork pw;                            // block partials, staging and solver vectors (host_pcg.h)
 	int n_cu = 256;
-	int kcap = 0;                          // columns the [k][N] vectors below have room for (the largest k seen)
-	double *B = nullptr, *O = nullptr;               // [k][N] staging of host-pointer calls
-	double *R = nullptr, *Z = nullptr, *P = nullptr, *X = nullptr, *AP = nullptr, *GP = nullptr;   // [k][N]
 	// marker groups (sgx_grm_set_groups): a column of a *_loco call leaves one group out
 	int n_groups = 0;
 	int *grp = nullptr;                    // [M] group id per marker
 	size_t gsize[GRM_MAX_GROUPS] = {};     // markers per group
 	double *diagx = nullptr;               // [1 + n_groups][N]: row 0 = diag, row 1 + c = diag(GRM without group c)
-	int kcap_w = 0;                        // columns Wc / Mc have room for
-	double *Wc = nullptr, *Mc = nullptr;   // [k][N]: weight rows and per-column minv of sgx_grm_pcg_loco
 	// explicit GRM (host_grm_dense.h): scratch of sgx_grm_dense / sgx_grm_sparse, allocated on first use
 	double *gd_part = nullptr, *gd_out = nullptr;    // slab tiles [nslab][tiles][256]; a rectangle of K
 	size_t gd_part_cap = 0, gd_out_cap = 0;          // (doubles)
@@ -53,46 +45,16 @@ struct sgx_grm {
 static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
 static_assert(GRM_MAX_GROUPS == SGX_GRM_MAX_GROUPS, "kern_grm.h and saigehip.h disagree on the group limit");
 
-// room for k columns (k <= GRM_MAX_RHS) in the [k][N] vectors
-static hipError_t grm_reserve(sgx_grm *g, int k)
-{
-	if (k <= g->kcap) return hipSuccess;
-	g->kcap = 0;
-	for (double **p : {&g->B, &g->O, &g->R, &g->Z, &g->P, &g->X, &g->AP, &g->GP}) {
-		hipError_t e = *p ? hipFree(*p) : hipSuccess;
-		*p = nullptr;
-		if (e == hipSuccess) e = hipMalloc((void **)p, (size_t)k * g->N * sizeof(double));
-		if (e != hipSuccess) return e;
-	}
-	g->kcap = k;
-	return hipSuccess;
-}
-
-// room for k columns in the per-column weights and preconditioners
-static hipError_t grm_reserve_w(sgx_grm *g, int k)
-{
-	if (k <= g->kcap_w) return hipSuccess;
-	g->kcap_w = 0;
-	for (double **p : {&g->Wc, &g->Mc}) {
-		hipError_t e = *p ? hipFree(*p) : hipSuccess;
-		*p = nullptr;
-		if (e == hipSuccess) e = hipMalloc((void **)p, (size_t)k * g->N * sizeof(double));
-		if (e != hipSuccess) return e;
-	}
-	g->kcap_w = k;
-	return hipSuccess;
-}
-
 extern "C" void sgx_grm_free(sgx_grm *g)
 {
 	if (!g) return;
 	(void)hipSetDevice(g->device);
 	if (g->stream) (void)hipStreamSynchronize(g->stream);
 	void *ptrs[] = {g->G, g->Gt, g->af, g->inv, g->l0, g->diag, g->FlN, g->FlM, g->accV, g->accS, g->xv, g->gv,
-		g->maxb, g->part, g->minv, g->w, g->B, g->O, g->R, g->Z, g->P, g->X, g->AP, g->GP, g->grp, g->diagx, g->Wc, g->Mc,
+		g->maxb, g->grp, g->diagx,
 		g->gd_part, g->gd_out, g->gd_lut, g->gd_A, g->gd_R, g->gd_cnt, g->gd_list, g->gd_i, g->gd_j, g->gd_v};
 	for (void *p : ptrs) (void)hipFree(p);
-	if (g->h_part) (void)hipHostFree(g->h_part);
+	pcg_work_free(&g->pw);
 	if (g->gd_ev0) (void)hipEventDestroy(g->gd_ev0);
 	if (g->gd_ev1) (void)hipEventDestroy(g->gd_ev1);
 	if (g->stream) (void)hipStreamDestroy(g->stream);
@@ -152,7 +114,7 @@ static int grm_init_impl(const uint8_t *packed, size_t bytes_per_marker, int32_t
 	GTRY(hipMemcpy2DAsync(g->G, g->bpvN, packed, bytes_per_marker, std::min(bytes_per_marker, g->bpvN), M,
 		kind, g->stream));
 	for (double **p : {&g->af, &g->inv, &g->l0}) GTRY(hipMalloc((void **)p, M * sizeof(double)));
-	for (double **p : {&g->diag, &g->minv, &g->w}) GTRY(hipMalloc((void **)p, N * sizeof(double)));
+	GTRY(hipMalloc((void **)&g->diag, N * sizeof(double)));
 	// scratch of a product: every launch zeroes what it reads of it
 	GTRY(hipMalloc((void **)&g->FlN, (size_t)g->ntileN * 16 * (16 * GRM_MAXF) * 16));
 	GTRY(hipMalloc((void **)&g->FlM, (size_t)g->ntileM * 16 * (16 * GRM_MAXF) * 16));
@@ -161,9 +123,7 @@ static int grm_init_impl(const uint8_t *packed, size_t bytes_per_marker, int32_t
 	GTRY(hipMalloc((void **)&g->xv, GRM_GROUP * M * sizeof(double)));
 	GTRY(hipMalloc((void **)&g->gv, GRM_GROUP * M * sizeof(double)));
 	GTRY(hipMalloc((void **)&g->maxb, GRM_MAX_RHS * 3 * sizeof(unsigned long long)));
-	GTRY(hipMalloc((void **)&g->part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double)));
-	GTRY(hipHostMalloc((void **)&g->h_part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double), hipHostMallocDefault));
-	GTRY(grm_reserve(g, 1));
+	GTRY(pcg_work_init(&g->pw, device, g->stream, n_samp));
 	// marker statistics, transpose, diag(GRM)
 	hipLaunchKernelGGL(grm_marker_stats, dim3((unsigned)M), dim3(256), 0, g->stream, g->G, g->bpvN, g->N, M, g->af, g->inv, g->l0);
 	hipLaunchKernelGGL(transpose_2bit, dim3((unsigned)((N + 255) / 256), (unsigned)((M + 63) / 64)), dim3(256), 0, g->stream,
@@ -190,33 +150,6 @@ extern "C" int sgx_grm_sync(sgx_grm *g)
 	if (!g) return fail(SGX_EINVAL, "sgx_grm_sync: NULL handle");
 	HIPCHK(hipSetDevice(g->device));
 	HIPCHK(hipStreamSynchronize(g->stream));
-	return SGX_OK;
-}
-
-// per column y of cols: out[y] = sum a (* b) as GRM_RED_BLOCKS block partials summed on the host in
-// fixed order; one host sync for up to two sets (a1/b1 over cols1, then a2/b2 over cols2; a2 == NULL: none)
-static int grm_sum(sgx_grm *g, const double *a1, const double *b1, size_t ld1, const GrmCols &c1,
-	double *out1, const double *a2 = nullptr, const double *b2 = nullptr, size_t ld2 = 0, const GrmCols *c2 = nullptr,
-	double *out2 = nullptr)
-{
-	hipStream_t st = g->stream;
-	const size_t n = (size_t)g->N;
-	auto launch = [&](const double *a, const double *b, size_t ld, const GrmCols &c, double *part) {
-		if (b) hipLaunchKernelGGL((dot_partial_kernel<true>), dim3(GRM_RED_BLOCKS, c.n), dim3(256), 0, st, a, b, ld, c, n, part);
-		else hipLaunchKernelGGL((dot_partial_kernel<false>), dim3(GRM_RED_BLOCKS, c.n), dim3(256), 0, st, a, b, ld, c, n, part);
-	};
-	const int n1 = c1.n, n2 = a2 ? c2->n : 0;
-	if (n1 + n2 == 0) return SGX_OK;
-	if (n1) launch(a1, b1, ld1, c1, g->part);
-	if (n2) launch(a2, b2, ld2, *c2, g->part + (size_t)n1 * GRM_RED_BLOCKS);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(g->h_part, g->part, (size_t)(n1 + n2) * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	for (int y = 0; y < n1 + n2; y++) {
-		double v = 0;
-		for (int i = 0; i < GRM_RED_BLOCKS; i++) v += g->h_part[(size_t)y * GRM_RED_BLOCKS + i];   // fixed order
-		if (y < n1) out1[y] = v; else out2[y - n1] = v;
-	}
 	return SGX_OK;
 }
 
@@ -252,7 +185,7 @@ static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols
 	const size_t N = (size_t)g->N, M = g->M;
 	const dim3 bl(256);
 	double sum_b[GRM_MAX_RHS];
-	int rc = grm_sum(g, B, nullptr, ldb, cols, sum_b);
+	int rc = pcg_sum(&g->pw, B, nullptr, ldb, cols, sum_b);
 	if (rc) return rc;
 	for (int g0 = 0; g0 < cols.n; g0 += GRM_GROUP) {
 		GrmCols gc{};
@@ -271,17 +204,17 @@ static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols
 		grm_contract(g, nb1, g->G, g->bpvN, (int)M, g->FlN, g->ntileN, g->accV);
 		if (excl)
 			hipLaunchKernelGGL(grm_dot_epilogue<true>, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, g->accV, g->maxb, sb,
-				g->af, g->inv, g->l0, g->xv, g->gv, g->part, g->grp, ex);
+				g->af, g->inv, g->l0, g->xv, g->gv, g->pw.part, g->grp, ex);
 		else
 			hipLaunchKernelGGL(grm_dot_epilogue<false>, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, g->accV, g->maxb, sb,
-				g->af, g->inv, g->l0, g->xv, g->gv, g->part, g->grp, ex);
+				g->af, g->inv, g->l0, g->xv, g->gv, g->pw.part, g->grp, ex);
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(g->h_part, g->part, (size_t)gc.n * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(g->pw.h_part, g->pw.part, (size_t)gc.n * GRM_RED_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
 		GrmScal C0{};
 		for (int y = 0; y < gc.n; y++) {
 			double c0 = 0;
-			for (int i = 0; i < GRM_RED_BLOCKS; i++) c0 += g->h_part[(size_t)y * GRM_RED_BLOCKS + i];   // fixed order
+			for (int i = 0; i < GRM_RED_BLOCKS; i++) c0 += g->pw.h_part[(size_t)y * GRM_RED_BLOCKS + i];   // fixed order
 			C0.v[y] = c0;
 		}
 		// ---- pass 2: per sample, over markers; column y of a sub-group in fragment y (x limbs 0.., gam limbs 7..)
@@ -321,44 +254,18 @@ static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols
 	return SGX_OK;
 }
 
-static int grm_multi_args(const char *fn, sgx_grm *g, const void *B, size_t ldb, int k, const void *Out)
-{
-	if (!g || !B || !Out) return fail(SGX_EINVAL, "%s: NULL argument", fn);
-	if (k < 1 || k > SGX_GRM_MAX_RHS) return fail(SGX_EINVAL, "%s: k=%d outside 1..%d", fn, k, SGX_GRM_MAX_RHS);
-	if (ldb < (size_t)g->N) return fail(SGX_EINVAL, "%s: ldb=%zu < N=%d", fn, ldb, g->N);
-	return SGX_OK;
-}
-
-static GrmCols grm_cols_iota(int k)
-{
-	GrmCols c{};
-	c.n = k;
-	for (int j = 0; j < k; j++) c.c[j] = j;
-	return c;
-}
-
-// k columns of N doubles between a host array with columns ldh doubles apart and a packed [k][N] device array
-// (one linear copy when the host columns are packed too)
-static hipError_t grm_copy_cols(sgx_grm *g, double *dst, const double *src, size_t ldh, int k, hipMemcpyKind kind)
-{
-	const size_t nb = (size_t)g->N * sizeof(double);
-	if (ldh == (size_t)g->N || k == 1) return hipMemcpyAsync(dst, src, (size_t)k * nb, kind, g->stream);
-	const bool up = kind == hipMemcpyHostToDevice;
-	return hipMemcpy2DAsync(dst, up ? nb : ldh * sizeof(double), src, up ? ldh * sizeof(double) : nb, nb, (size_t)k, kind, g->stream);
-}
-
 // Out = GRM B for k host vectors, column j at B + j * ldb (and Out + j * ldb)
 static int grm_crossprod_run(sgx_grm *g, const double *B, size_t ldb, int k, double *Out, const int *excl = nullptr)
 {
-	HIPCHK(hipSetDevice(g->device));
-	HIPCHK(grm_reserve(g, k));
-	const size_t N = (size_t)g->N;
-	HIPCHK(grm_copy_cols(g, g->B, B, ldb, k, hipMemcpyHostToDevice));
-	int rc = grm_matvec_dev(g, g->B, N, grm_cols_iota(k), g->O, N, excl);
-	if (rc) return rc;
-	HIPCHK(grm_copy_cols(g, Out, g->O, ldb, k, hipMemcpyDeviceToHost));
-	HIPCHK(hipStreamSynchronize(g->stream));
-	return SGX_OK;
+	return pcg_crossprod_run(&g->pw, B, ldb, k, Out,
+		[&](const double *Bd, size_t ld, const GrmCols &cols, double *Od, size_t ldo) {
+			return grm_matvec_dev(g, Bd, ld, cols, Od, ldo, excl);
+		});
+}
+
+static int grm_multi_args(const char *fn, sgx_grm *g, const void *B, size_t ldb, int k, const void *Out)
+{
+	return pcg_multi_args(fn, g, g ? g->N : 0, B, ldb, k, Out);
 }
 
 // get_crossprod_b_grm: out = GRM b, host vectors of length N
@@ -380,7 +287,7 @@ extern "C" int sgx_grm_crossprod_dev(sgx_grm *g, const double *b_dev, double *ou
 {
 	if (!g || !b_dev || !out_dev) return fail(SGX_EINVAL, "sgx_grm_crossprod_dev: NULL argument");
 	HIPCHK(hipSetDevice(g->device));
-	return grm_matvec_dev(g, b_dev, (size_t)g->N, grm_cols_iota(1), out_dev, (size_t)g->N);
+	return grm_matvec_dev(g, b_dev, (size_t)g->N, pcg_cols_iota(1), out_dev, (size_t)g->N);
 }
 
 extern "C" int sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size_t ldb, int k, double *Out_dev)
@@ -388,79 +295,19 @@ extern "C" int sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size
 	int rc = grm_multi_args("sgx_grm_crossprod_multi_dev", g, B_dev, ldb, k, Out_dev);
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(g->device));
-	return grm_matvec_dev(g, B_dev, ldb, grm_cols_iota(k), Out_dev, ldb);
+	return grm_matvec_dev(g, B_dev, ldb, pcg_cols_iota(k), Out_dev, ldb);
 }
 
-// PCG_diag_sigma (saige_fitnull.cpp:581-614): solves (tau0 diag(1/w) + tau1 GRM) x = b for k right-hand
-// sides in lockstep (host vectors, column j at B + j * ldb): every column takes the reference's steps on
-// its own scalars; a column stops (and leaves the products) once rr <= tol or maxiter is reached.  Each
-// reduction step is one host sync for all columns.
-// lo (NULL: one w and the whole GRM for all columns, the plain kernels): column j has the weights lo->W row
-// lo->w_idx[j] (w is not read), leaves out group lo->excl[j], and is preconditioned with its own diagonal.
-struct GrmLoco {
-	const double *W; size_t ldw; int n_w;
-	const int *w_idx, *excl;               // [k], checked (grm_excl_args)
-};
-
+// PCG_diag_sigma (saige_fitnull.cpp:581-614) on the implicit GRM: the loop is pcg_run (host_pcg.h).
+// excl (NULL: the whole GRM for all columns): column j leaves out group excl[j] and, with pc, has its own weights
+// and diagonal (sgx_grm_pcg_loco).
 static int grm_pcg_run(sgx_grm *g, const double *w, const double *tau, const double *B, size_t ldb, int k,
-	int maxiter, double tol, double *X_out, int *iters, const GrmLoco *lo = nullptr)
+	int maxiter, double tol, double *X_out, int *iters, const int *excl = nullptr, const PcgPerCol *pc = nullptr)
 {
-	HIPCHK(hipSetDevice(g->device));
-	HIPCHK(grm_reserve(g, k));
-	hipStream_t st = g->stream;
-	const int n = g->N;
-	const size_t N = (size_t)n, nb = N * sizeof(double);
-	const dim3 bl(256);
-	const unsigned gx = (unsigned)((n + 255) / 256);
-	const double tau0 = tau[0], tau1 = tau[1];
-	const GrmCols all = grm_cols_iota(k);
-	GrmIdx widx{}, ex{};
-	HIPCHK(grm_copy_cols(g, g->B, B, ldb, k, hipMemcpyHostToDevice));
-	if (lo) {
-		HIPCHK(grm_reserve_w(g, std::max(k, lo->n_w)));
-		HIPCHK(grm_copy_cols(g, g->Wc, lo->W, lo->ldw, lo->n_w, hipMemcpyHostToDevice));
-		for (int j = 0; j < k; j++) { widx.v[j] = lo->w_idx[j]; ex.v[j] = lo->excl[j]; }
-		hipLaunchKernelGGL(pcg_minv_cols_kernel, dim3(gx, k), bl, 0, st, n, g->Wc, widx, g->diagx ? g->diagx : g->diag, ex,
-			tau0, tau1, g->Mc, all);
-		hipLaunchKernelGGL(pcg_init_kernel<true>, dim3(gx, k), bl, 0, st, n, g->B, N, g->Mc, g->R, g->Z, g->P, g->X, all);
-	} else {
-		HIPCHK(hipMemcpyAsync(g->w, w, nb, hipMemcpyHostToDevice, st));
-		hipLaunchKernelGGL(pcg_minv_kernel, dim3(gx), bl, 0, st, n, g->w, g->diag, tau0, tau1, g->minv);
-		hipLaunchKernelGGL(pcg_init_kernel<false>, dim3(gx, k), bl, 0, st, n, g->B, N, g->minv, g->R, g->Z, g->P, g->X, all);
-	}
-	double rr[GRM_MAX_RHS], rz[GRM_MAX_RHS];
-	int rc;
-	if ((rc = grm_sum(g, g->R, g->R, N, all, rr, g->R, g->Z, N, &all, rz))) return rc;
-	for (int j = 0; j < k; j++) iters[j] = 0;
-	for (;;) {
-		GrmCols act{};
-		for (int j = 0; j < k; j++)
-			if (iters[j] < maxiter && rr[j] > tol) act.c[act.n++] = j;
-		if (act.n == 0) break;
-		for (int y = 0; y < act.n; y++) iters[act.c[y]]++;
-		const double *gp = nullptr;
-		if (tau1 != 0) {                       // get_crossprod :569-575
-			if ((rc = grm_matvec_dev(g, g->P, N, act, g->GP, N, lo ? lo->excl : nullptr))) return rc;
-			gp = g->GP;
-		}
-		if (lo) hipLaunchKernelGGL(pcg_ap_kernel<true>, dim3(gx, act.n), bl, 0, st, n, g->P, g->Wc, gp, tau0, tau1, g->AP, act, widx);
-		else hipLaunchKernelGGL(pcg_ap_kernel<false>, dim3(gx, act.n), bl, 0, st, n, g->P, g->w, gp, tau0, tau1, g->AP, act, widx);
-		double pAp[GRM_MAX_RHS], rz1[GRM_MAX_RHS], rrn[GRM_MAX_RHS];
-		if ((rc = grm_sum(g, g->P, g->AP, N, act, pAp))) return rc;
-		GrmScal a{};
-		for (int y = 0; y < act.n; y++) a.v[y] = rz[act.c[y]] / pAp[y];
-		if (lo) hipLaunchKernelGGL(pcg_update_kernel<true>, dim3(gx, act.n), bl, 0, st, n, a, g->P, g->AP, g->Mc, g->X, g->R, g->Z, act);
-		else hipLaunchKernelGGL(pcg_update_kernel<false>, dim3(gx, act.n), bl, 0, st, n, a, g->P, g->AP, g->minv, g->X, g->R, g->Z, act);
-		if ((rc = grm_sum(g, g->Z, g->R, N, act, rz1, g->R, g->R, N, &act, rrn))) return rc;
-		GrmScal bet{};
-		for (int y = 0; y < act.n; y++) bet.v[y] = rz1[y] / rz[act.c[y]];
-		hipLaunchKernelGGL(pcg_dir_kernel, dim3(gx, act.n), bl, 0, st, n, bet, g->Z, g->P, act);
-		for (int y = 0; y < act.n; y++) { rz[act.c[y]] = rz1[y]; rr[act.c[y]] = rrn[y]; }
-	}
-	HIPCHK(hipGetLastError());
-	HIPCHK(grm_copy_cols(g, X_out, g->X, ldb, k, hipMemcpyDeviceToHost));
-	HIPCHK(hipStreamSynchronize(st));
-	return SGX_OK;
+	return pcg_run(&g->pw, g->diag, w, tau, B, ldb, k, maxiter, tol, X_out, iters,
+		[&](const double *Bd, size_t ld, const GrmCols &cols, double *Od, size_t ldo) {
+			return grm_matvec_dev(g, Bd, ld, cols, Od, ldo, excl);
+		}, pc);
 }
 
 extern "C" int sgx_grm_pcg(sgx_grm *g, const double *w, const double *tau, const double *b,
@@ -589,6 +436,6 @@ extern "C" int sgx_grm_pcg_loco(sgx_grm *g, const double *W, size_t ldw, int n_w
 			return fail(SGX_EINVAL, "sgx_grm_pcg_loco: w_idx[%d]=%d outside 0..%d", j, w_idx[j], n_w - 1);
 	int ex[GRM_MAX_RHS];
 	if ((rc = grm_excl_args("sgx_grm_pcg_loco", g, excl, k, ex))) return rc;
-	const GrmLoco lo{W, ldw, n_w, w_idx, ex};
-	return grm_pcg_run(g, nullptr, tau, B, ldb, k, maxiter, tol, X_out, iters, &lo);
+	const PcgPerCol pc{W, ldw, n_w, w_idx, ex, g->diagx ? g->diagx : g->diag};
+	return grm_pcg_run(g, nullptr, tau, B, ldb, k, maxiter, tol, X_out, iters, ex, &pc);
 }

@@ -79,6 +79,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_cond.h"
 #include "kern_cond_ds.h"
 #include "kern_grm_dense.h"
+#include "kern_kmat.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -95,5 +96,7 @@ static int fail(int code, const char *fmt, ...)
 #include "host_cond.h"
 #include "host_cond_ds.h"
 #include "host_util.h"
+#include "host_pcg.h"
 #include "host_grm.h"
 #include "host_grm_dense.h"
+#include "host_kmat.h"

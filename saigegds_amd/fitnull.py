@@ -757,7 +757,7 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
                        tau_init=(0, 0), traceCVcutoff: float = 0.0025, ratioCVcutoff: float = 0.001,
                        geno_sparse: bool = True, num_thread: int = 1, model_savefn: str = "", seed: int = 200,
                        fork_loading: bool = False, verbose: bool = True, operator_factory=None,
-                       loco: bool = False) -> FittedNullModel:
+                       loco: bool = False, grm_mat=None) -> FittedNullModel:
     """Fit the SAIGE null model ``formula + var(GRM)`` on MI355X.
 
     ``data``: mapping column -> sequence (a pandas DataFrame works);
@@ -778,6 +778,14 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
     against its own entry.  tau is not refitted, and the variance ratio stays the single one of the full
     model, as in SAIGE.  The markers must lie on 2 .. 64 chromosomes.  An injected operator without
     ``pcg_loco`` is replaced, per chromosome, by ``operator_factory`` on the markers outside it.
+
+    ``grm_mat`` fits the model on an explicit GRM instead of the implicit one over the markers (SAIGE's
+    ``useSparseGRMtoFitNULL``, upstream SAIGEgds 2.x ``grm.mat=``): the ``SparseGRM`` of ``seqFitSparseGRM``, the
+    ``(sample_id, K)`` pair of ``seqFitDenseGRM``, or a file either of them wrote (``load_grm``).  Every sample
+    of the model must be in the matrix, which is subset and permuted to them; the operator is
+    ``ExplicitGrmOperator``, or ``operator_factory(aligned_grm, n_samp)``, and the solves that share (w, tau)
+    run as one batched call.  ``gdsfile`` is still needed: the variance-ratio markers and ``variant_id`` come
+    from it as without ``grm_mat``.  ``loco=True`` needs the markers and is refused with ``grm_mat``.
     """
     if trait_type not in ("binary", "quantitative"):
         raise ValueError("'arg' should be one of \"binary\", \"quantitative\"")
@@ -792,6 +800,8 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
     sids = [str(s) for s in cols[sample_col]]
     if len(set(sids)) != len(sids):
         raise ValueError(f"'{sample_col}' in data should be unique.")
+    if grm_mat is not None and loco:
+        raise ValueError("loco=True needs the GRM markers: it cannot be combined with 'grm_mat'.")
     if verbose:
         print("SAIGE association analysis:")
 
@@ -822,8 +832,16 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
     else:
         X_fit = X
 
-    # GRM operator (saige_store_2b_geno / saige_store_sp_geno)
-    if operator_factory is None:
+    # GRM operator (saige_store_2b_geno / saige_store_sp_geno), or the one of an explicit matrix
+    if grm_mat is not None:
+        from .grm import _align_grm_mat
+        aligned = _align_grm_mat(grm_mat, sample_ids)
+        if operator_factory is None:
+            from ._lib import ExplicitGrmOperator
+            op = ExplicitGrmOperator(aligned)
+        else:
+            op = operator_factory(aligned, n_samp)
+    elif operator_factory is None:
         from ._lib import GrmOperator
         op = GrmOperator(packed, n_samp)
     else:
@@ -854,7 +872,7 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
             XXVX_inv = X_fit @ np.linalg.inv(X_fit.T @ (X_fit * V[:, None]))
             obj_noK = dict(y=yv, mu=mu0, res=yv - mu0, V=V, X1=X_fit, XV=XV, XXVX_inv=XXVX_inv)
             tau = np.array([1.0, 0.5 if tau_init[1] == 0 else tau_init[1]])     # :490-497
-            fitter = _Fitter(op, X_fit, yv, fit0, param, rng)
+            fitter = _Fitter(op, X_fit, yv, fit0, param, rng, batched=grm_mat is not None)
             glmm = fitter.fit(tau, quant=False)
         else:
             y_fit = yv
@@ -874,7 +892,7 @@ def seqFitNullGLMM_SPA(formula: str, data: Dict[str, Any], gdsfile, trait_type: 
                 tau = np.array([0.5, 0.5])
             Yw = fit0.linear_predictors + (fit0.y - mu0)
             tau = float(np.var(Yw, ddof=1)) * tau / tau.sum()              # :582-589
-            fitter = _Fitter(op, X_fit, fit0.y, fit0, param, rng)
+            fitter = _Fitter(op, X_fit, fit0.y, fit0, param, rng, batched=grm_mat is not None)
             glmm = fitter.fit(tau, quant=True)
 
         if verbose:

@@ -47,6 +47,26 @@ class SparseGRM:
         np.add.at(out, self.j[off], self.x[off] * b[self.i[off]])
         return out
 
+    def subset(self, sample_id: Sequence[str]) -> "SparseGRM":
+        """The matrix of those samples in that order: re-indexed, the entries of other samples dropped, i <= j,
+        sorted by (i, j)."""
+        ids = [str(s) for s in sample_id]
+        if len(set(ids)) != len(ids):
+            raise ValueError("'sample_id' should be unique.")
+        pos = {s: k for k, s in enumerate(self.sample_id)}
+        miss = [s for s in ids if s not in pos]
+        if miss:
+            raise ValueError(f"{len(miss)} sample(s) not in the GRM: {miss[:5]}")
+        new = np.full(self.n, -1, dtype=np.int64)          # old index -> new index, -1: dropped
+        new[[pos[s] for s in ids]] = np.arange(len(ids))
+        a, b = new[self.i], new[self.j]
+        keep = (a >= 0) & (b >= 0)
+        a, b, x = a[keep], b[keep], self.x[keep]
+        i, j = np.minimum(a, b), np.maximum(a, b)
+        o = np.lexsort((j, i))
+        return SparseGRM(sample_id=ids, n=len(ids), n_markers=self.n_markers, rel_cutoff=self.rel_cutoff,
+                         i=i[o].astype(np.int32), j=j[o].astype(np.int32), x=np.ascontiguousarray(x[o]))
+
     def related_pairs(self) -> List[Tuple[str, str, float]]:
         """The off-diagonal entries as (sample id, sample id, kinship coefficient K_ij)."""
         off = np.flatnonzero(self.i != self.j)
@@ -181,6 +201,73 @@ def seqFitSparseGRM(gdsfile, sample_id: Optional[Sequence[str]] = None, variant_
                             ("n", _vector(np.array([res.n], dtype=np.int32))),
                             ("rel.cutoff", _vector(np.array([res.rel_cutoff])))], out_fn)
     return res
+
+
+def load_grm(fn: str):
+    """Read what ``seqFitSparseGRM`` / ``seqFitDenseGRM`` wrote with ``out_fn`` (``.rds`` or ``.npz``): a
+    ``SparseGRM`` (the files' 1-based i / j back to 0-based; they do not hold the marker count, so ``n_markers``
+    is 0), or ``(sample_id, K)`` for a dense matrix."""
+    _check_out_fn(fn)
+    if re.search(r"\.npz$", fn, re.I):
+        with np.load(fn) as z:
+            d = {k: z[k] for k in z.files}
+        d = {{"sample_id": "sample.id", "K": "grm", "rel_cutoff": "rel.cutoff"}.get(k, k): v for k, v in d.items()}
+    else:
+        from .rds import read_rds
+        r = read_rds(fn)
+        if not hasattr(r, "names") or "sample.id" not in r.names:
+            raise ValueError(f"'{fn}' is not a GRM file of seqFitSparseGRM / seqFitDenseGRM.")
+        d = {k: r[k] for k in r.names}
+    ids = [str(s) for s in d["sample.id"]]
+    if "grm" in d:
+        K = np.ascontiguousarray(np.asarray(d["grm"], dtype=np.float64))
+        if K.shape != (len(ids), len(ids)):
+            raise ValueError(f"'{fn}': the matrix is {K.shape}, with {len(ids)} sample ids.")
+        return ids, K
+    if not all(k in d for k in ("i", "j", "x", "n", "rel.cutoff")):
+        raise ValueError(f"'{fn}' is not a GRM file of seqFitSparseGRM / seqFitDenseGRM.")
+    n = int(np.asarray(d["n"]).reshape(-1)[0])
+    i, j = np.asarray(d["i"], dtype=np.int64) - 1, np.asarray(d["j"], dtype=np.int64) - 1
+    x = np.ascontiguousarray(np.asarray(d["x"], dtype=np.float64))
+    if n != len(ids) or i.shape != x.shape or j.shape != x.shape or (x.size and (i.min() < 0 or j.max() >= n or (i > j).any())):
+        raise ValueError(f"'{fn}': inconsistent sparse GRM.")
+    return SparseGRM(sample_id=ids, n=n, n_markers=0, rel_cutoff=float(np.asarray(d["rel.cutoff"]).reshape(-1)[0]),
+                     i=i.astype(np.int32), j=j.astype(np.int32), x=x)
+
+
+def _align_grm_mat(grm_mat, sample_id: Sequence[str]):
+    """``grm_mat`` of ``seqFitNullGLMM_SPA`` (a ``SparseGRM``, ``(sample_id, K)`` or a file of ``load_grm``) as the
+    matrix of the model's samples in their order: a ``SparseGRM`` or a square float64 array."""
+    if isinstance(grm_mat, str):
+        grm_mat = load_grm(grm_mat)
+    ids = [str(s) for s in sample_id]
+
+    def missing(have):
+        have = set(have)
+        miss = [s for s in ids if s not in have]
+        if miss:
+            raise ValueError(f"{len(miss)} sample(s) of the model are not in 'grm_mat': {miss[:5]}")
+
+    if isinstance(grm_mat, SparseGRM):
+        missing(grm_mat.sample_id)
+        return grm_mat.subset(ids)
+    try:
+        gids, K = grm_mat
+    except (TypeError, ValueError):
+        raise ValueError("'grm_mat' should be a SparseGRM, (sample_id, K) or a file name.") from None
+    gids = [str(s) for s in gids]
+    K = np.asarray(K, dtype=np.float64)
+    if K.ndim != 2 or K.shape[0] != K.shape[1] or K.shape[0] != len(gids):
+        raise ValueError(f"'grm_mat' should be a square matrix with one row per sample id: it is "
+                         f"{'x'.join(str(v) for v in K.shape)} with {len(gids)} sample ids.")
+    if len(set(gids)) != len(gids):
+        raise ValueError("The sample ids of 'grm_mat' should be unique.")
+    missing(gids)
+    if gids == ids:
+        return np.ascontiguousarray(K)
+    pos = {s: k for k, s in enumerate(gids)}
+    ix = np.array([pos[s] for s in ids], dtype=np.int64)
+    return np.ascontiguousarray(K[np.ix_(ix, ix)])
 
 
 def _check_out_fn(out_fn: str):
