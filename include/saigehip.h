@@ -617,6 +617,42 @@ int  sgx_kmat_crossprod_multi_dev(sgx_kmat *m, const double *B_dev, size_t ldb, 
 int  sgx_kmat_pcg_multi(sgx_kmat *m, const double *w, const double *tau, const double *B, size_t ldb, int k,
 	int maxiter, double tol, double *X_out, int *iters);
 int  sgx_kmat_matvec_ms(sgx_kmat *m, double *ms_out);
+/* sgx_kmat_pcg_multi on vectors that are resident on the matrix's device: w_dev [n], B_dev and X_dev at [k][ldb]
+ * (they may not overlap).  The same loop on the same scalars: iterates and iters equal sgx_kmat_pcg_multi's bit for
+ * bit, and column j's do not depend on k or on the other columns of the call.  Only the per-iteration scalars cross
+ * to the host.  The weights cannot be checked here (the caller's: positive and finite).  Synchronous. */
+int  sgx_kmat_pcg_multi_dev(sgx_kmat *m, const double *w_dev, const double *tau, const double *B_dev, size_t ldb,
+	int k, int maxiter, double tol, double *X_dev, int *iters);
+
+/* SKAT on an explicit GRM: the score statistics of sgx_skat_2bit and their covariance under the fitted model itself
+ * (SAIGE-GENE's exact form; not in the reference).  Units, tables, adj_e and score[e] = S_e as for
+ * sgx_skat_2bit; w [N] and tau[2] as for sgx_kmat_pcg_multi: Sigma = tau[0] diag(1/w) + tau[1] K, K the matrix of km.
+ * With A the columns adj_e of a unit, X the model's covariates, Y = Sigma^-1 A (one solve per entry, in chunks of at
+ * most SGX_GRM_MAX_RHS columns), Z = Sigma^-1 X (K solves per call, shared by its units), C = A'Y, D = A'Z, E = X'Z:
+ *   cov, unit u (laid out as sgx_skat_2bit's):   Phi^K = 1/2 (C + C') - D E^-1 D'  =  A' P A,
+ *   P = Sigma^-1 - Sigma^-1 X (X' Sigma^-1 X)^-1 X' Sigma^-1, exactly symmetric; E^-1 is made on the host in FP64.
+ * No var_ratio factor: the model's own covariance needs none.  For tau[1] == 0 no product with K is made and
+ * Phi^K_ef = (1 / tau[0]) sum_i w_i adj_ei adj_fi.  The solves are sgx_kmat_pcg_multi_dev's (same preconditioner floor,
+ * per-column scalars and exits: a column that has not converged after maxiter steps keeps its last iterate);
+ * iters[e] (may be NULL) is the step count of entry e's column.
+ * Fixed order everywhere: the column sums c' and s are slab sums (slabs cut by N alone) added in slab order, so
+ * score equals sgx_skat_2bit's to rounding (1e-10 relative, the scan's own bound), not bit for bit; the products run
+ * in FP64 on the matrix cores over slabs of 2048 samples added in slab order, no atomics.  The bits of C_ef depend on
+ * columns e and f and on N only: not on m, on the entry's position or 64-column chunk, on the other units of the
+ * call or on earlier calls.  An entry whose table holds a non-finite value stays out of the solve, gets a non-finite
+ * score and a non-finite row and column of its unit's cov, and leaves the other entries alone.
+ * Device memory: with lda = N rounded up to 16, the call keeps 2 m lda doubles for its largest unit (A and Y), 2 K lda
+ * for X and Z, and the solver's 8 min(m, 64) N; what does not fit returns SGX_ENOMEM.  The rows cross PCIe once per
+ * call in the chunks of the host-buffer scans.
+ * SGX_EINVAL (nothing launched, both handles stay usable): a NULL buffer, km on another device than h or of another
+ * sample count, a unit above SGX_SKAT_MAX_VARIANTS, an index outside [0, n_variants), a non-finite or non-positive
+ * w, tau[0] <= 0 or tau[1] < 0.  A unit of 0 entries writes nothing.  Synchronous.
+ *   sgx_skat_kmat_ms   host milliseconds of the last call: ms[0] rows and columns, ms[1] solves, ms[2] products */
+int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *packed, size_t bytes_per_variant,
+	size_t n_variants, size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx,
+	const double *lut, const double *w, const double *tau, int maxiter, double tol,
+	double *score, double *cov, int32_t *iters /* per entry, may be NULL */);
+int sgx_skat_kmat_ms(sgx_handle *h, double *ms);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@ EXPORTS = (
     "sgx_grm_dense", "sgx_grm_dense_kernel_ms", "sgx_grm_sparse",
     "sgx_kmat_init_csr", "sgx_kmat_init_dense", "sgx_kmat_free", "sgx_kmat_sync", "sgx_kmat_diag",
     "sgx_kmat_crossprod_multi", "sgx_kmat_crossprod_multi_dev", "sgx_kmat_pcg_multi", "sgx_kmat_matvec_ms",
+    "sgx_kmat_pcg_multi_dev", "sgx_skat_kmat_2bit", "sgx_skat_kmat_ms",
     "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
     "sgx_scan_packed", "sgx_ds_block_load_packed",
     "sgx_scan_dbit2", "sgx_block_load_dbit2",
@@ -310,6 +311,12 @@ def load():
     L.sgx_kmat_crossprod_multi_dev.argtypes = [vp, vp, sz, C.c_int, vp]
     L.sgx_kmat_pcg_multi.restype = C.c_int
     L.sgx_kmat_pcg_multi.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int, dp, vp, vp]
+    L.sgx_kmat_pcg_multi_dev.restype = C.c_int
+    L.sgx_kmat_pcg_multi_dev.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int, dp, vp, vp]
+    L.sgx_skat_kmat_2bit.restype = C.c_int
+    L.sgx_skat_kmat_2bit.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.c_int, dp, vp, vp, vp]
+    L.sgx_skat_kmat_ms.restype = C.c_int
+    L.sgx_skat_kmat_ms.argtypes = [vp, vp]
     L.sgx_kmat_matvec_ms.restype = C.c_int
     L.sgx_kmat_matvec_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.sgx_grm_pcg_loco.restype = C.c_int
@@ -468,6 +475,42 @@ class Scanner:
                                         unit_ptr.ctypes.data, var_idx.ctypes.data, lut.ctypes.data,
                                         score.ctypes.data, cov.ctypes.data))
         return score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)]
+
+    def skat_kmat(self, op, packed: np.ndarray, unit_ptr, var_idx, lut, w, tau, maxiter: int = 500, tol: float = 1e-5):
+        """``skat_2bit`` with the covariance under the fitted model on the explicit GRM of ``op`` (an
+        ``ExplicitGrmOperator`` on this scanner's device): ``Phi^K = A' P A`` with ``Sigma = tau[0] diag(1/w) +
+        tau[1] K`` (``sgx_skat_kmat_2bit``) -> (score [entries], cov: per unit an [m, m] symmetric matrix,
+        iters [entries]: PCG steps of every entry's solve)."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        unit_ptr = np.ascontiguousarray(unit_ptr, dtype=np.int64)
+        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+        lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        n_units = unit_ptr.size - 1
+        if packed.ndim != 2 or lut.shape[0] != var_idx.size or n_units < 0 or unit_ptr[-1] != var_idx.size:
+            raise ValueError("skat_kmat: inconsistent CSR / table shapes")
+        if w.shape != (op.n,) or tau.shape != (2,):
+            raise ValueError("skat_kmat: w must have one entry per sample of the matrix and tau two entries")
+        sizes = np.diff(unit_ptr)
+        if (sizes < 0).any():
+            raise ValueError("skat_kmat: unit_ptr not ascending")
+        offs = np.concatenate([[0], np.cumsum(sizes * sizes)])
+        score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
+        iters = np.zeros(max(1, var_idx.size), dtype=np.int32)
+        if var_idx.size:
+            check(self._L.sgx_skat_kmat_2bit(self._h, op._h, packed.ctypes.data, packed.shape[1], packed.shape[0], n_units,
+                                             unit_ptr.ctypes.data, var_idx.ctypes.data, lut.ctypes.data, w.ctypes.data,
+                                             tau.ctypes.data, int(maxiter), float(tol), score.ctypes.data, cov.ctypes.data,
+                                             iters.ctypes.data))
+        return (score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)],
+                iters[:var_idx.size])
+
+    def skat_kmat_ms(self) -> np.ndarray:
+        """Host milliseconds of the last ``skat_kmat`` call: columns, solves, products."""
+        ms = np.zeros(3)
+        check(self._L.sgx_skat_kmat_ms(self._h, ms.ctypes.data))
+        return ms
 
     def cond_set(self, packed_c: np.ndarray, lut_c):
         """Installs the conditioning set of the conditional scan (``sgx_cond_set``): its 2-bit rows and 4-entry dosage
@@ -1168,6 +1211,16 @@ class ExplicitGrmOperator:
             check(self._L.sgx_kmat_pcg_multi(self._h, w.ctypes.data, tau.ctypes.data, B[j0].ctypes.data, self.n, k,
                                              int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
         return X, iters
+
+    def pcg_many_dev(self, w_ptr: int, tau, b_ptr: int, ldb: int, k: int, x_ptr: int, maxiter: int = 500,
+                     tol: float = 1e-5) -> np.ndarray:
+        """Device form of ``pcg_many`` for k <= GRM_MAX_RHS columns: weights at w_ptr, right-hand sides at
+        b_ptr + j * ldb doubles, solutions to x_ptr + j * ldb (synchronous) -> iters [k]; bit for bit ``pcg_many``."""
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        iters = np.zeros(max(1, int(k)), dtype=np.int32)
+        check(self._L.sgx_kmat_pcg_multi_dev(self._h, w_ptr, tau.ctypes.data, b_ptr, int(ldb), int(k), int(maxiter),
+                                             float(tol), x_ptr, iters.ctypes.data))
+        return iters[:int(k)]
 
     def pcg(self, w: np.ndarray, tau, b: np.ndarray, maxiter: int = 500, tol: float = 1e-5):
         b = np.ascontiguousarray(b, dtype=np.float64)

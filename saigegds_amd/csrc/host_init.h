@@ -403,6 +403,8 @@ extern "C" void sgx_free(sgx_handle *h)
 	if (h->cstream) (void)hipStreamDestroy(h->cstream);
 	(void)hipFree(h->stage_in); (void)hipFree(h->stage_out); (void)hipFree(h->stage_valid); (void)hipFree(h->stage_pk); (void)hipFree(h->ds_part);
 	(void)hipFree(h->skat_part); (void)hipFree(h->skat_fin);
+	(void)hipFree(h->skk_A); (void)hipFree(h->skk_Y); (void)hipFree(h->skk_XZ); (void)hipFree(h->skk_cpart);
+	(void)hipFree(h->skk_cs); (void)hipFree(h->skk_tiles);
 	(void)hipFree(h->cond_B); (void)hipFree(h->cond_ce); (void)hipFree(h->cond_part); (void)hipFree(h->cond_fin);
 	if (h->h_counters) (void)hipHostFree(h->h_counters);
 	for (int i = 0; i < 3; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);

@@ -152,32 +152,31 @@ struct PcgPerCol {
 	const double *D;                       // device [rows][N]
 };
 
+// The loop on vectors that are resident: the right-hand sides at Bd + j * ldB and (pc == NULL) the weights wd are device
+// arrays, the workspace has room for k columns (pcg_reserve), the device is current.  The iterates end in pw->X
+// ([k][N], packed) behind the stream's last reduction; only the per-iteration scalars cross to the host.
 template <class Product>
-static int pcg_run(PcgWork *pw, const double *diag, const double *w, const double *tau, const double *B, size_t ldb, int k,
-	int maxiter, double tol, double *X_out, int *iters, Product product, const PcgPerCol *pc = nullptr)
+static int pcg_core(PcgWork *pw, const double *diag, const double *wd, const double *tau, const double *Bd, size_t ldB, int k,
+	int maxiter, double tol, int *iters, Product product, const PcgPerCol *pc)
 {
-	HIPCHK(hipSetDevice(pw->device));
-	HIPCHK(pcg_reserve(pw, k));
 	hipStream_t st = pw->stream;
 	const int n = pw->N;
-	const size_t N = (size_t)n, nb = N * sizeof(double);
+	const size_t N = (size_t)n;
 	const dim3 bl(256);
 	const unsigned gx = (unsigned)((n + 255) / 256);
 	const double tau0 = tau[0], tau1 = tau[1];
 	const GrmCols all = pcg_cols_iota(k);
 	GrmIdx widx{}, ex{};
-	HIPCHK(pcg_copy_cols(pw, pw->B, B, ldb, k, hipMemcpyHostToDevice));
 	if (pc) {
 		HIPCHK(pcg_reserve_w(pw, std::max(k, pc->n_w)));
 		HIPCHK(pcg_copy_cols(pw, pw->Wc, pc->W, pc->ldw, pc->n_w, hipMemcpyHostToDevice));
 		for (int j = 0; j < k; j++) { widx.v[j] = pc->w_idx[j]; ex.v[j] = pc->drow[j]; }
 		hipLaunchKernelGGL(pcg_minv_cols_kernel, dim3(gx, k), bl, 0, st, n, pw->Wc, widx, pc->D, ex,
 			tau0, tau1, pw->Mc, all);
-		hipLaunchKernelGGL(pcg_init_kernel<true>, dim3(gx, k), bl, 0, st, n, pw->B, N, pw->Mc, pw->R, pw->Z, pw->P, pw->X, all);
+		hipLaunchKernelGGL(pcg_init_kernel<true>, dim3(gx, k), bl, 0, st, n, Bd, ldB, pw->Mc, pw->R, pw->Z, pw->P, pw->X, all);
 	} else {
-		HIPCHK(hipMemcpyAsync(pw->w, w, nb, hipMemcpyHostToDevice, st));
-		hipLaunchKernelGGL(pcg_minv_kernel, dim3(gx), bl, 0, st, n, pw->w, diag, tau0, tau1, pw->minv);
-		hipLaunchKernelGGL(pcg_init_kernel<false>, dim3(gx, k), bl, 0, st, n, pw->B, N, pw->minv, pw->R, pw->Z, pw->P, pw->X, all);
+		hipLaunchKernelGGL(pcg_minv_kernel, dim3(gx), bl, 0, st, n, wd, diag, tau0, tau1, pw->minv);
+		hipLaunchKernelGGL(pcg_init_kernel<false>, dim3(gx, k), bl, 0, st, n, Bd, ldB, pw->minv, pw->R, pw->Z, pw->P, pw->X, all);
 	}
 	double rr[GRM_MAX_RHS], rz[GRM_MAX_RHS];
 	int rc;
@@ -195,7 +194,7 @@ static int pcg_run(PcgWork *pw, const double *diag, const double *w, const doubl
 			gp = pw->GP;
 		}
 		if (pc) hipLaunchKernelGGL(pcg_ap_kernel<true>, dim3(gx, act.n), bl, 0, st, n, pw->P, pw->Wc, gp, tau0, tau1, pw->AP, act, widx);
-		else hipLaunchKernelGGL(pcg_ap_kernel<false>, dim3(gx, act.n), bl, 0, st, n, pw->P, pw->w, gp, tau0, tau1, pw->AP, act, widx);
+		else hipLaunchKernelGGL(pcg_ap_kernel<false>, dim3(gx, act.n), bl, 0, st, n, pw->P, wd, gp, tau0, tau1, pw->AP, act, widx);
 		double pAp[GRM_MAX_RHS], rz1[GRM_MAX_RHS], rrn[GRM_MAX_RHS];
 		if ((rc = pcg_sum(pw, pw->P, pw->AP, N, act, pAp))) return rc;
 		GrmScal a{};
@@ -209,6 +208,21 @@ static int pcg_run(PcgWork *pw, const double *diag, const double *w, const doubl
 		for (int y = 0; y < act.n; y++) { rz[act.c[y]] = rz1[y]; rr[act.c[y]] = rrn[y]; }
 	}
 	HIPCHK(hipGetLastError());
+	return SGX_OK;
+}
+
+// pcg_core on host vectors (column j at B + j * ldb; w on the host, not read with pc): up, solve, down.
+template <class Product>
+static int pcg_run(PcgWork *pw, const double *diag, const double *w, const double *tau, const double *B, size_t ldb, int k,
+	int maxiter, double tol, double *X_out, int *iters, Product product, const PcgPerCol *pc = nullptr)
+{
+	HIPCHK(hipSetDevice(pw->device));
+	HIPCHK(pcg_reserve(pw, k));
+	hipStream_t st = pw->stream;
+	HIPCHK(pcg_copy_cols(pw, pw->B, B, ldb, k, hipMemcpyHostToDevice));
+	if (!pc) HIPCHK(hipMemcpyAsync(pw->w, w, (size_t)pw->N * sizeof(double), hipMemcpyHostToDevice, st));
+	int rc = pcg_core(pw, diag, pw->w, tau, pw->B, (size_t)pw->N, k, maxiter, tol, iters, product, pc);
+	if (rc) return rc;
 	HIPCHK(pcg_copy_cols(pw, X_out, pw->X, ldb, k, hipMemcpyDeviceToHost));
 	HIPCHK(hipStreamSynchronize(st));
 	return SGX_OK;

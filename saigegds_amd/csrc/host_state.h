@@ -116,6 +116,14 @@ struct sgx_handle {
 	double *skat_part = nullptr; size_t skat_part_cap = 0;   // sgx_skat_2bit: per-slab partial tiles of a launch
 	double *skat_fin = nullptr; size_t skat_fin_cap = 0;     // ... and its tiles summed over the slabs
 	double *stage_out = nullptr; uint8_t *stage_valid = nullptr; size_t stage_out_cap = 0;
+	// sgx_skat_kmat_2bit (host_skat_kmat.h): a unit's adj columns and their solves [m][lda], the covariate columns and
+	// theirs [2K][lda], the column sums per slab and summed, the tiles of a launch; milliseconds of the last call
+	double *skk_A = nullptr, *skk_Y = nullptr; size_t skk_A_cap = 0, skk_Y_cap = 0;
+	double *skk_XZ = nullptr; size_t skk_XZ_cap = 0;
+	double *skk_cpart = nullptr; size_t skk_cpart_cap = 0;
+	double *skk_cs = nullptr; size_t skk_cs_cap = 0;
+	SkkTile *skk_tiles = nullptr; size_t skk_tiles_cap = 0;
+	double skk_ms[3] = {0, 0, 0};      // columns, solve, contraction
 	// conditional scan (host_cond.h).  Primary: the installed set -- B of kern_cond.h, the set's c' and e sums
 	double *cond_B = nullptr; size_t cond_B_cap = 0;
 	double *cond_ce = nullptr; size_t cond_ce_cap = 0;       // [n_cond][2K]

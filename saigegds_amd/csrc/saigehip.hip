@@ -20,6 +20,7 @@
 #include <math.h>
 #include <cmath>
 #include <algorithm>
+#include <chrono>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -80,6 +81,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_cond_ds.h"
 #include "kern_grm_dense.h"
 #include "kern_kmat.h"
+#include "kern_skat_kmat.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -100,3 +102,4 @@ static int fail(int code, const char *fmt, ...)
 #include "host_grm.h"
 #include "host_grm_dense.h"
 #include "host_kmat.h"
+#include "host_skat_kmat.h"

@@ -9,6 +9,8 @@ burden paths by identities (tests/test_gpu_skat.py).  The flow of 
    0 / 0 / 1) for maf, mac and the single-variant p-values;
 2. one ``sgx_skat_2bit`` for all units: score statistics ``S`` and their covariance ``Phi`` per unit, the weighted Gram
    matrix of the unit's 2-bit rows on the device's matrix cores;
+   With ``grm_mat=`` it is one ``sgx_skat_kmat_2bit`` instead: ``Phi`` becomes the covariance under the fitted model
+   on the explicit GRM, ``Phi^K = A' P A`` (DESIGN.md 8g), with no variance ratio;
 3. on the host, per unit and weight column: the SPA adjustment of ``Phi`` (binary traits), ``Q = sum w_j^2 S_j^2`` and
    its p-value under the mixture of chi-squares with the eigenvalues of ``diag(w) Phi diag(w)``.
 
@@ -162,10 +164,31 @@ def _unit_tests(pr, kept, S_of, phi_of):
     return Q, P
 
 
+def _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat):
+    """The refusals of ``seqAssocGLMM_spaSKAT(grm_mat=)``, before any row is read -> (the opened source, the matrix of the
+    scan's samples in the scan's order, the model's weights V in that order)."""
+    from .aggregate import _hard_calls
+    from .assoc import _open_source, open_scan_input
+    from .grm import _align_grm_mat
+    from .nullmod import load_modobj, no_loco
+    if not (parallel is False or parallel is None or (isinstance(parallel, (int, np.integer)) and int(parallel) in (0, 1))):
+        raise ValueError("SKAT with 'grm_mat' runs on one GPU: 'parallel' should be FALSE or 1.")
+    mod = load_modobj(modobj, False)
+    no_loco(mod, "SAIGE SKAT analysis")
+    if dsnode != "":
+        raise NotImplementedError("SKAT with 'grm_mat' on dosage input is not implemented.")
+    src = _open_source(gdsfile, False)          # opened once: the driver goes on with this object
+    inp = open_scan_input(src, mod, dsnode, False)
+    if inp.kind != "packed" and not (inp.kind == "dosage" and inp.in_mem and inp.ds_dtype != np.float64 and _hard_calls(inp.ds_all)):
+        raise NotImplementedError("SKAT with 'grm_mat' on dosage input is not implemented.")
+    return src, _align_grm_mat(grm_mat, inp.sample_id()), np.ascontiguousarray(np.asarray(mod.V, dtype=np.float64)[inp.ii])
+
+
 def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: str = "", spa_pval: float = 0.05,
                          var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
                          parallel=False, verbose: bool = True, verbose_maf: bool = True,
-                         scanner_factory=None, ds_budget: Optional[int] = None) -> Dict[str, Any]:
+                         scanner_factory=None, ds_budget: Optional[int] = None, grm_mat=None, tol_pcg: float = 1e-5,
+                         maxiter_pcg: int = 500) -> Dict[str, Any]:
     """SKAT per unit and weight set (not in the reference; arguments as ``seqAssocGLMM_spaBurden``), on hard calls or
     on dosages (``dsnode``, or a file without ``genotype/data``, or an in-memory dosage matrix that is float64 or holds
     more than hard calls; ``ds_budget``: bytes of resident dosage rows per batch of units).
@@ -183,11 +206,22 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
     Two kinds of dosage input are refused with ``NotImplementedError`` (both pinned by
     tests/test_skat.py::test_driver_refuses_dosage_input): a non-empty ``dsnode`` together with an in-memory source of
     packed rows, which has no nodes; and a scanner whose ``dosage_block(...)`` object has no ``skat`` method (checked
-    right after the block is made, before any row is read; the scanner is closed)."""
+    right after the block is made, before any row is read; the scanner is closed).
+
+    ``grm_mat`` (what ``seqFitNullGLMM_SPA(grm_mat=)`` accepts: a ``SparseGRM``, ``(sample_id, K)`` or a file of
+    ``load_grm``; every sample of the model must be in it) replaces ``Phi`` by the covariance under the fitted model
+    itself, ``Phi^K = A' P A`` with ``Sigma = tau[0] diag(1/V) + tau[1] K`` (``sgx_skat_kmat_2bit``; solves
+    to ``tol_pcg`` in at most ``maxiter_pcg`` steps): no variance ratio enters it.  The SPA scale factors are then formed
+    against ``Phi^K_jj``; weights, ``Q`` and ``pchisq_mix`` are the same code, and a column ``n.iter`` holds the largest
+    PCG step count of the unit.  Refused before any row is read: dosage input (``NotImplementedError``), a LOCO model,
+    ``parallel`` other than one GPU (``ValueError``)."""
     if not isinstance(dsnode, str):
         raise TypeError("is.character(dsnode) is not TRUE")
     if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
         raise NotImplementedError("SKAT on dosage input is not implemented.")
+    aligned = None
+    if grm_mat is not None:
+        gdsfile, aligned, aligned_w = _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat)
     pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT analysis:", scanner_factory,
                   dsnode, ("skat",), ds_budget=ds_budget)
     try:
@@ -203,12 +237,23 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
             flip, m = flip_mean(pr.n[var_idx], pr.s[var_idx])         # (double)sum / n, as _burden_rows
             z = 0 * m
             lut = np.where(flip[:, None] != 0, np.stack([z + 2, z + 1, z, m], axis=1), np.stack([z, z + 1, z + 2, m], axis=1))
-            score, cov = pr.sc.skat_2bit(pr.packed, unit_ptr, var_idx, lut)
+            n_iter = None
+            if aligned is None:
+                score, cov = pr.sc.skat_2bit(pr.packed, unit_ptr, var_idx, lut)
+            else:
+                from ._lib import ExplicitGrmOperator
+                with ExplicitGrmOperator(aligned) as op:
+                    score, cov, it = pr.sc.skat_kmat(op, pr.packed, unit_ptr, var_idx, lut, aligned_w, pr.sm.tau,
+                                                     maxiter=maxiter_pcg, tol=tol_pcg)
+                n_iter = np.array([int(it[unit_ptr[u]:unit_ptr[u + 1]].max()) if k.size else 0 for u, k in enumerate(kept)],
+                                  dtype=np.int64)
             S_of, phi_of = (lambda u: score[unit_ptr[u]:unit_ptr[u + 1]]), cov.__getitem__
     finally:
         pr.sc.close()
     Q, P = _unit_tests(pr, kept, S_of, phi_of)
     ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
+    if aligned is not None:
+        ans["n.iter"] = n_iter
     for i, nm in enumerate(pr.wb_colnm):
         sfx = f".{nm}" if len(pr.wb_colnm) > 1 else ""
         ans["Q" + sfx], ans["pval" + sfx] = Q[:, i], P[:, i]
