@@ -14,26 +14,6 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SAIGEHIP_LIB") or os.path.join(_HERE, "libsaigehip.so")   # (the override: A/B runs of two builds)
 
-EXPORTS = (
-    "sgx_version", "sgx_last_error", "sgx_device_count", "sgx_init", "sgx_free",
-    "sgx_set_thresholds", "sgx_score_layout", "sgx_scan_2bit", "sgx_scan_2bit_dev", "sgx_scan_u8", "sgx_scan_i32", "sgx_scan_f64", "sgx_host_alloc", "sgx_host_free", "sgx_burden_2bit", "sgx_geno_stats_2bit", "sgx_decode_dbit2",
-    "sgx_block_bytes", "sgx_block_create", "sgx_block_create_ex", "sgx_block_free", "sgx_block_load_dev", "sgx_block_load", "sgx_block_variants", "sgx_scan_block",
-    "sgx_sync", "sgx_get_stats", "sgx_get_stats_total", "sgx_row_stride", "sgx_synth_2bit_dev", "sgx_selftest", "sgx_set_option",
-    "sgx_grm_init", "sgx_grm_init_dev", "sgx_grm_crossprod_dev", "sgx_grm_sync", "sgx_grm_free", "sgx_grm_diag", "sgx_grm_crossprod", "sgx_grm_pcg",
-    "sgx_grm_crossprod_multi", "sgx_grm_crossprod_multi_dev", "sgx_grm_pcg_multi",
-    "sgx_grm_set_groups", "sgx_grm_group_sizes", "sgx_grm_diag_loco", "sgx_grm_crossprod_loco", "sgx_grm_pcg_loco",
-    "sgx_grm_dense", "sgx_grm_dense_kernel_ms", "sgx_grm_sparse",
-    "sgx_kmat_init_csr", "sgx_kmat_init_dense", "sgx_kmat_free", "sgx_kmat_sync", "sgx_kmat_diag",
-    "sgx_kmat_crossprod_multi", "sgx_kmat_crossprod_multi_dev", "sgx_kmat_pcg_multi", "sgx_kmat_matvec_ms",
-    "sgx_kmat_pcg_multi_dev", "sgx_skat_kmat_2bit", "sgx_skat_kmat_ms",
-    "sgx_dsblock_create", "sgx_dsblock_free", "sgx_dsblock_load", "sgx_dsblock_scan", "sgx_dsblock_burden",
-    "sgx_scan_packed", "sgx_ds_block_load_packed",
-    "sgx_scan_dbit2", "sgx_block_load_dbit2",
-    "sgx_quantize_packed",
-    "sgx_skat_2bit", "sgx_ds_block_skat",
-    "sgx_cond_set", "sgx_cond_2bit", "sgx_cond_2bit_dev", "sgx_ds_block_cond_set", "sgx_ds_block_cond",
-)
-
 GRM_MAX_RHS = 64      # SGX_GRM_MAX_RHS: columns of one batched GRM call
 GRM_MAX_GROUPS = 64   # SGX_GRM_MAX_GROUPS: marker groups of one GRM handle
 KMAT_WAVE_ROW = 33    # SGX_KMAT_WAVE_ROW: CSR rows of sgx_kmat with at least this many entries take the wave form
@@ -130,6 +110,98 @@ class SgxGrmSparseStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+def _abi():
+    """include/saigehip.h as ctypes: every exported function -> (restype, argtypes; None: takes no argument)."""
+    vp, sz, dp, ci, i32, ll, u64, ptr = (C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_int32, C.c_longlong, C.c_uint64,
+                                         C.POINTER)
+    pvp = ptr(vp)
+    return {
+        "sgx_version": (C.c_char_p, None),
+        "sgx_last_error": (C.c_char_p, None),
+        "sgx_device_count": (ci, None),
+        "sgx_init": (ci, [ptr(SgxModel), ci, pvp]),
+        "sgx_free": (None, [vp]),
+        "sgx_set_thresholds": (ci, [vp, dp, dp, dp, dp]),
+        "sgx_score_layout": (ci, [vp, vp, i32, ptr(i32)]),
+        "sgx_scan_2bit": (ci, [vp, vp, sz, sz, vp, vp]),
+        "sgx_scan_2bit_dev": (ci, [vp, vp, sz, sz, vp, vp]),
+        "sgx_scan_u8": (ci, [vp, vp, sz, vp, vp]),
+        "sgx_scan_i32": (ci, [vp, vp, sz, vp, vp]),
+        "sgx_scan_f64": (ci, [vp, vp, sz, vp, vp]),
+        "sgx_host_alloc": (vp, [sz]),
+        "sgx_host_free": (None, [vp]),
+        "sgx_burden_2bit": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
+        "sgx_geno_stats_2bit": (ci, [vp, sz, i32, sz, ci, vp, vp]),
+        "sgx_decode_dbit2": (ci, [vp, sz, i32, sz, vp, i32, vp, sz, ci]),
+        "sgx_block_bytes": (sz, [i32, sz]),
+        "sgx_block_create": (ci, [i32, sz, ci, pvp]),
+        "sgx_block_create_ex": (ci, [i32, sz, ci, ll, pvp]),
+        "sgx_block_free": (None, [vp]),
+        "sgx_block_load_dev": (ci, [vp, vp, vp, sz, sz]),
+        "sgx_block_load": (ci, [vp, vp, vp, sz, sz]),
+        "sgx_block_variants": (sz, [vp]),
+        "sgx_scan_block": (ci, [vp, vp, vp, vp]),
+        "sgx_sync": (ci, [vp]),
+        "sgx_get_stats": (ci, [vp, ptr(SgxStats)]),
+        "sgx_get_stats_total": (ci, [vp, ptr(SgxStats), ptr(u64), ci]),
+        "sgx_row_stride": (sz, [i32]),
+        "sgx_synth_2bit_dev": (ci, [vp, vp, sz, i32, sz, u64, u64, vp]),
+        "sgx_selftest": (ci, [ci]),
+        "sgx_set_option": (ci, [vp, C.c_char_p, ll]),
+        "sgx_grm_init": (ci, [vp, sz, i32, sz, ci, pvp]),
+        "sgx_grm_init_dev": (ci, [vp, sz, i32, sz, ci, pvp]),
+        "sgx_grm_crossprod_dev": (ci, [vp, vp, vp]),
+        "sgx_grm_sync": (ci, [vp]),
+        "sgx_grm_free": (None, [vp]),
+        "sgx_grm_diag": (ci, [vp, vp]),
+        "sgx_grm_crossprod": (ci, [vp, vp, vp]),
+        "sgx_grm_pcg": (ci, [vp, vp, vp, vp, ci, dp, vp, ptr(ci)]),
+        "sgx_grm_crossprod_multi": (ci, [vp, vp, sz, ci, vp]),
+        "sgx_grm_crossprod_multi_dev": (ci, [vp, vp, sz, ci, vp]),
+        "sgx_grm_pcg_multi": (ci, [vp, vp, vp, vp, sz, ci, ci, dp, vp, vp]),
+        "sgx_grm_set_groups": (ci, [vp, vp, ci]),
+        "sgx_grm_group_sizes": (ci, [vp, vp]),
+        "sgx_grm_diag_loco": (ci, [vp, ci, vp]),
+        "sgx_grm_crossprod_loco": (ci, [vp, vp, sz, ci, vp, vp]),
+        "sgx_grm_pcg_loco": (ci, [vp, vp, sz, ci, vp, vp, vp, sz, ci, vp, ci, dp, vp, vp]),
+        "sgx_grm_dense": (ci, [vp, i32, i32, i32, i32, vp, sz]),
+        "sgx_grm_dense_kernel_ms": (ci, [vp, ptr(dp)]),
+        "sgx_grm_sparse": (ci, [vp, dp, sz, vp, vp, vp, ptr(sz), ptr(SgxGrmSparseStats)]),
+        "sgx_kmat_init_csr": (ci, [i32, vp, vp, vp, ci, pvp]),
+        "sgx_kmat_init_dense": (ci, [vp, sz, i32, ci, pvp]),
+        "sgx_kmat_free": (None, [vp]),
+        "sgx_kmat_sync": (ci, [vp]),
+        "sgx_kmat_diag": (ci, [vp, vp]),
+        "sgx_kmat_crossprod_multi": (ci, [vp, vp, sz, ci, vp]),
+        "sgx_kmat_crossprod_multi_dev": (ci, [vp, vp, sz, ci, vp]),
+        "sgx_kmat_pcg_multi": (ci, [vp, vp, vp, vp, sz, ci, ci, dp, vp, vp]),
+        "sgx_kmat_matvec_ms": (ci, [vp, ptr(dp)]),
+        "sgx_kmat_pcg_multi_dev": (ci, [vp, vp, vp, vp, sz, ci, ci, dp, vp, vp]),
+        "sgx_skat_kmat_2bit": (ci, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
+        "sgx_skat_kmat_ms": (ci, [vp, vp]),
+        "sgx_dsblock_create": (ci, [i32, ci, sz, ci, pvp]),
+        "sgx_dsblock_free": (None, [vp]),
+        "sgx_dsblock_load": (ci, [vp, vp, vp, sz, vp, vp, vp]),
+        "sgx_dsblock_scan": (ci, [vp, vp, vp, vp]),
+        "sgx_dsblock_burden": (ci, [vp, vp, sz, vp, vp, vp, ci, vp, vp, vp, vp]),
+        "sgx_scan_packed": (ci, [vp, vp, ci, sz, dp, dp, vp, sz, vp, vp]),
+        "sgx_ds_block_load_packed": (ci, [vp, vp, vp, ci, sz, dp, dp, vp, sz, vp, vp, vp]),
+        "sgx_scan_dbit2": (ci, [vp, vp, sz, sz, vp, vp, sz, vp, vp]),
+        "sgx_block_load_dbit2": (ci, [vp, vp, vp, sz, sz, vp, vp, sz]),
+        "sgx_quantize_packed": (ci, [vp, ci, sz, dp, dp, vp, i32, sz, ci, sz, vp, sz, vp, vp, vp, vp]),
+        "sgx_skat_2bit": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
+        "sgx_ds_block_skat": (ci, [vp, vp, sz, vp, vp, vp, vp, vp, vp]),
+        "sgx_cond_set": (ci, [vp, vp, sz, sz, vp, vp, vp]),
+        "sgx_cond_2bit": (ci, [vp, vp, sz, sz, vp, vp, vp, vp]),
+        "sgx_cond_2bit_dev": (ci, [vp, vp, sz, sz, vp, vp, vp, vp]),
+        "sgx_ds_block_cond_set": (ci, [vp, vp, sz, vp, vp, vp, vp, vp]),
+        "sgx_ds_block_cond": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+    }
+
+
+ABI = _abi()
+EXPORTS = tuple(ABI)
+
 _lib = None
 
 
@@ -163,164 +235,11 @@ def load():
             "(or __graft_entry__.build()).  There is no CPU fallback.")
     _share_hip_runtime_with_torch()
     L = C.CDLL(LIB_PATH)
-    vp, sz, dp = C.c_void_p, C.c_size_t, C.c_double
-    L.sgx_version.restype = C.c_char_p
-    L.sgx_last_error.restype = C.c_char_p
-    L.sgx_device_count.restype = C.c_int
-    L.sgx_selftest.restype = C.c_int
-    L.sgx_selftest.argtypes = [C.c_int]
-    L.sgx_init.restype = C.c_int
-    L.sgx_init.argtypes = [C.POINTER(SgxModel), C.c_int, C.POINTER(vp)]
-    L.sgx_free.restype = None
-    L.sgx_free.argtypes = [vp]
-    L.sgx_set_thresholds.restype = C.c_int
-    L.sgx_set_thresholds.argtypes = [vp, dp, dp, dp, dp]
-    L.sgx_score_layout.restype = C.c_int
-    L.sgx_score_layout.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
-    L.sgx_scan_2bit.restype = C.c_int
-    L.sgx_scan_2bit.argtypes = [vp, vp, sz, sz, vp, vp]
-    L.sgx_scan_2bit_dev.restype = C.c_int
-    L.sgx_scan_2bit_dev.argtypes = [vp, vp, sz, sz, vp, vp]
-    L.sgx_block_bytes.restype = sz
-    L.sgx_block_bytes.argtypes = [C.c_int32, sz]
-    L.sgx_block_create.restype = C.c_int
-    L.sgx_block_create.argtypes = [C.c_int32, sz, C.c_int, C.POINTER(vp)]
-    L.sgx_block_create_ex.restype = C.c_int
-    L.sgx_block_create_ex.argtypes = [C.c_int32, sz, C.c_int, C.c_longlong, C.POINTER(vp)]
-    L.sgx_block_free.restype = None
-    L.sgx_block_free.argtypes = [vp]
-    L.sgx_block_load_dev.restype = C.c_int
-    L.sgx_block_load_dev.argtypes = [vp, vp, vp, sz, sz]
-    L.sgx_block_load.restype = C.c_int
-    L.sgx_block_load.argtypes = [vp, vp, vp, sz, sz]
-    L.sgx_block_variants.restype = sz
-    L.sgx_block_variants.argtypes = [vp]
-    L.sgx_scan_block.restype = C.c_int
-    L.sgx_scan_block.argtypes = [vp, vp, vp, vp]
-    L.sgx_scan_u8.restype = C.c_int
-    L.sgx_scan_u8.argtypes = [vp, vp, sz, vp, vp]
-    L.sgx_scan_f64.restype = C.c_int
-    L.sgx_scan_f64.argtypes = [vp, vp, sz, vp, vp]
-    L.sgx_host_alloc.restype = vp
-    L.sgx_host_alloc.argtypes = [sz]
-    L.sgx_host_free.restype = None
-    L.sgx_host_free.argtypes = [vp]
-    L.sgx_scan_i32.restype = C.c_int
-    L.sgx_scan_i32.argtypes = [vp, vp, sz, vp, vp]
-    L.sgx_burden_2bit.restype = C.c_int
-    L.sgx_burden_2bit.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
-    L.sgx_skat_2bit.restype = C.c_int
-    L.sgx_skat_2bit.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
-    L.sgx_cond_set.restype = C.c_int
-    L.sgx_cond_set.argtypes = [vp, vp, sz, sz, vp, vp, vp]
-    L.sgx_cond_2bit.restype = C.c_int
-    L.sgx_cond_2bit.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
-    L.sgx_cond_2bit_dev.restype = C.c_int
-    L.sgx_cond_2bit_dev.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
-    L.sgx_dsblock_create.restype = C.c_int
-    L.sgx_dsblock_create.argtypes = [C.c_int32, C.c_int, sz, C.c_int, C.POINTER(vp)]
-    L.sgx_dsblock_free.restype = None
-    L.sgx_dsblock_free.argtypes = [vp]
-    L.sgx_dsblock_load.restype = C.c_int
-    L.sgx_dsblock_load.argtypes = [vp, vp, vp, sz, vp, vp, vp]
-    L.sgx_scan_packed.restype = C.c_int
-    L.sgx_scan_packed.argtypes = [vp, vp, C.c_int, sz, dp, dp, vp, sz, vp, vp]
-    L.sgx_scan_dbit2.restype = C.c_int
-    L.sgx_scan_dbit2.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, vp]
-    L.sgx_block_load_dbit2.restype = C.c_int
-    L.sgx_block_load_dbit2.argtypes = [vp, vp, vp, sz, sz, vp, vp, sz]
-    L.sgx_ds_block_load_packed.restype = C.c_int
-    L.sgx_ds_block_load_packed.argtypes = [vp, vp, vp, C.c_int, sz, dp, dp, vp, sz, vp, vp, vp]
-    L.sgx_dsblock_scan.restype = C.c_int
-    L.sgx_dsblock_scan.argtypes = [vp, vp, vp, vp]
-    L.sgx_dsblock_burden.restype = C.c_int
-    L.sgx_dsblock_burden.argtypes = [vp, vp, sz, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    L.sgx_ds_block_skat.restype = C.c_int
-    L.sgx_ds_block_skat.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp]
-    L.sgx_ds_block_cond_set.restype = C.c_int
-    L.sgx_ds_block_cond_set.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
-    L.sgx_ds_block_cond.restype = C.c_int
-    L.sgx_ds_block_cond.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.sgx_decode_dbit2.restype = C.c_int
-    L.sgx_decode_dbit2.argtypes = [vp, sz, C.c_int32, sz, vp, C.c_int32, vp, sz, C.c_int]
-    L.sgx_geno_stats_2bit.restype = C.c_int
-    L.sgx_geno_stats_2bit.argtypes = [vp, sz, C.c_int32, sz, C.c_int, vp, vp]
-    L.sgx_quantize_packed.restype = C.c_int
-    L.sgx_quantize_packed.argtypes = [vp, C.c_int, sz, dp, dp, vp, C.c_int32, sz, C.c_int, sz, vp, sz, vp, vp, vp, vp]
-    L.sgx_set_option.restype = C.c_int
-    L.sgx_set_option.argtypes = [vp, C.c_char_p, C.c_longlong]
-    L.sgx_sync.restype = C.c_int
-    L.sgx_sync.argtypes = [vp]
-    L.sgx_get_stats.restype = C.c_int
-    L.sgx_get_stats.argtypes = [vp, C.POINTER(SgxStats)]
-    L.sgx_get_stats_total.restype = C.c_int
-    L.sgx_get_stats_total.argtypes = [vp, C.POINTER(SgxStats), C.POINTER(C.c_uint64), C.c_int]
-    L.sgx_row_stride.restype = sz
-    L.sgx_row_stride.argtypes = [C.c_int32]
-    L.sgx_synth_2bit_dev.restype = C.c_int
-    L.sgx_synth_2bit_dev.argtypes = [vp, vp, sz, C.c_int32, sz, C.c_uint64, C.c_uint64, vp]
-    L.sgx_grm_init.restype = C.c_int
-    L.sgx_grm_init.argtypes = [vp, sz, C.c_int32, sz, C.c_int, C.POINTER(vp)]
-    L.sgx_grm_init_dev.restype = C.c_int
-    L.sgx_grm_init_dev.argtypes = [vp, sz, C.c_int32, sz, C.c_int, C.POINTER(vp)]
-    L.sgx_grm_crossprod_dev.restype = C.c_int
-    L.sgx_grm_crossprod_dev.argtypes = [vp, vp, vp]
-    L.sgx_grm_sync.restype = C.c_int
-    L.sgx_grm_sync.argtypes = [vp]
-    L.sgx_grm_free.restype = None
-    L.sgx_grm_free.argtypes = [vp]
-    L.sgx_grm_diag.restype = C.c_int
-    L.sgx_grm_diag.argtypes = [vp, vp]
-    L.sgx_grm_crossprod.restype = C.c_int
-    L.sgx_grm_crossprod.argtypes = [vp, vp, vp]
-    L.sgx_grm_pcg.restype = C.c_int
-    L.sgx_grm_pcg.argtypes = [vp, vp, vp, vp, C.c_int, dp, vp, C.POINTER(C.c_int)]
-    L.sgx_grm_crossprod_multi.restype = C.c_int
-    L.sgx_grm_crossprod_multi.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.sgx_grm_crossprod_multi_dev.restype = C.c_int
-    L.sgx_grm_crossprod_multi_dev.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.sgx_grm_pcg_multi.restype = C.c_int
-    L.sgx_grm_pcg_multi.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int, dp, vp, vp]
-    L.sgx_grm_set_groups.restype = C.c_int
-    L.sgx_grm_set_groups.argtypes = [vp, vp, C.c_int]
-    L.sgx_grm_group_sizes.restype = C.c_int
-    L.sgx_grm_group_sizes.argtypes = [vp, vp]
-    L.sgx_grm_diag_loco.restype = C.c_int
-    L.sgx_grm_diag_loco.argtypes = [vp, C.c_int, vp]
-    L.sgx_grm_crossprod_loco.restype = C.c_int
-    L.sgx_grm_crossprod_loco.argtypes = [vp, vp, sz, C.c_int, vp, vp]
-    L.sgx_grm_dense.restype = C.c_int
-    L.sgx_grm_dense.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, sz]
-    L.sgx_grm_dense_kernel_ms.restype = C.c_int
-    L.sgx_grm_dense_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_grm_sparse.restype = C.c_int
-    L.sgx_grm_sparse.argtypes = [vp, C.c_double, sz, vp, vp, vp, C.POINTER(sz), C.POINTER(SgxGrmSparseStats)]
-    L.sgx_kmat_init_csr.restype = C.c_int
-    L.sgx_kmat_init_csr.argtypes = [C.c_int32, vp, vp, vp, C.c_int, C.POINTER(vp)]
-    L.sgx_kmat_init_dense.restype = C.c_int
-    L.sgx_kmat_init_dense.argtypes = [vp, sz, C.c_int32, C.c_int, C.POINTER(vp)]
-    L.sgx_kmat_free.restype = None
-    L.sgx_kmat_free.argtypes = [vp]
-    L.sgx_kmat_sync.restype = C.c_int
-    L.sgx_kmat_sync.argtypes = [vp]
-    L.sgx_kmat_diag.restype = C.c_int
-    L.sgx_kmat_diag.argtypes = [vp, vp]
-    L.sgx_kmat_crossprod_multi.restype = C.c_int
-    L.sgx_kmat_crossprod_multi.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.sgx_kmat_crossprod_multi_dev.restype = C.c_int
-    L.sgx_kmat_crossprod_multi_dev.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.sgx_kmat_pcg_multi.restype = C.c_int
-    L.sgx_kmat_pcg_multi.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int, dp, vp, vp]
-    L.sgx_kmat_pcg_multi_dev.restype = C.c_int
-    L.sgx_kmat_pcg_multi_dev.argtypes = [vp, vp, vp, vp, sz, C.c_int, C.c_int, dp, vp, vp]
-    L.sgx_skat_kmat_2bit.restype = C.c_int
-    L.sgx_skat_kmat_2bit.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, C.c_int, dp, vp, vp, vp]
-    L.sgx_skat_kmat_ms.restype = C.c_int
-    L.sgx_skat_kmat_ms.argtypes = [vp, vp]
-    L.sgx_kmat_matvec_ms.restype = C.c_int
-    L.sgx_kmat_matvec_ms.argtypes = [vp, C.POINTER(C.c_double)]
-    L.sgx_grm_pcg_loco.restype = C.c_int
-    L.sgx_grm_pcg_loco.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, sz, C.c_int, vp, C.c_int, dp, vp, vp]
+    for name, (restype, argtypes) in ABI.items():
+        f = getattr(L, name)
+        f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
     _lib = L
     return L
 
@@ -330,12 +249,59 @@ def check(rc: int):
         raise SgxError(rc, load().sgx_last_error().decode("utf-8", "replace"))
 
 
-class Scanner:
+class _Handle:
+    """An object the library made: the attribute ``_attr`` holds it, the function ``_free`` releases it.  ``close()``
+    may come any number of times; ``with`` and the collector close too."""
+
+    _attr, _free = "_h", None
+    _L = property(lambda self: load())
+
+    def close(self):
+        if getattr(self, self._attr, None):
+            getattr(self._L, self._free)(getattr(self, self._attr))
+            setattr(self, self._attr, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _unit_args(what: str, unit_ptr, var_idx, entries, ok: bool = True):
+    """Checks of the set tests' units (CSR ``unit_ptr`` / ``var_idx`` over rows; ``entries``: the per-entry arrays,
+    each with the shape of one entry; ``ok``: the caller's own condition) -> (unit_ptr int64, var_idx int32, n_units,
+    the units' sizes m, the offsets of their m x m matrices in one buffer)."""
+    unit_ptr = np.ascontiguousarray(unit_ptr, dtype=np.int64)
+    var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+    n_units = unit_ptr.size - 1
+    if not ok or var_idx.ndim != 1 or any(a.shape != var_idx.shape + one for a, one in entries) or n_units < 0 \
+            or unit_ptr[-1] != var_idx.size:
+        raise ValueError(f"{what}: inconsistent CSR / table shapes")
+    sizes = np.diff(unit_ptr)
+    if (sizes < 0).any():
+        raise ValueError(f"{what}: unit_ptr not ascending")
+    return unit_ptr, var_idx, n_units, sizes, np.concatenate([[0], np.cumsum(sizes * sizes)])
+
+
+def _unit_matrices(cov: np.ndarray, sizes, offs):
+    """The buffer of all units' matrices -> per unit an [m, m] view."""
+    return [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(sizes.size)]
+
+
+class Scanner(_Handle):
     """One model resident on one GPU (an ``sgx_handle``)."""
+
+    _free = "sgx_free"
 
     def __init__(self, sm, device: int = 0):
         L = load()
-        self._L = L
         self.n, self.k, self.quant = sm.n, sm.k, sm.quant
         f = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
         self._keep = dict(y=f(sm.y), mu=f(sm.mu), y_mu=f(sm.y_mu), mu2=f(sm.mu2),
@@ -353,24 +319,6 @@ class Scanner:
         check(L.sgx_init(C.byref(m), int(device), C.byref(h)))
         self._h = h
         self.device = device
-
-    # -- lifetime --------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sgx_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     # -- host-buffer scans -------------------------------------------------
     def _out(self, m):
@@ -459,22 +407,14 @@ class Scanner:
         """Score statistics and their covariance per unit (CSR over the rows of ``packed``, one 4-entry dosage table
         per entry; ``sgx_skat_2bit``) -> (score [entries], cov: per unit an [m, m] symmetric matrix)."""
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        unit_ptr = np.ascontiguousarray(unit_ptr, dtype=np.int64)
-        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
         lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
-        n_units = unit_ptr.size - 1
-        if packed.ndim != 2 or lut.shape[0] != var_idx.size or n_units < 0 or unit_ptr[-1] != var_idx.size:
-            raise ValueError("skat_2bit: inconsistent CSR / table shapes")
-        sizes = np.diff(unit_ptr)
-        if (sizes < 0).any():
-            raise ValueError("skat_2bit: unit_ptr not ascending")
-        offs = np.concatenate([[0], np.cumsum(sizes * sizes)])
+        unit_ptr, var_idx, n_units, sizes, offs = _unit_args("skat_2bit", unit_ptr, var_idx, [(lut, (4,))], packed.ndim == 2)
         score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
         if var_idx.size:
             check(self._L.sgx_skat_2bit(self._h, packed.ctypes.data, packed.shape[1], packed.shape[0], n_units,
                                         unit_ptr.ctypes.data, var_idx.ctypes.data, lut.ctypes.data,
                                         score.ctypes.data, cov.ctypes.data))
-        return score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)]
+        return score[:var_idx.size], _unit_matrices(cov, sizes, offs)
 
     def skat_kmat(self, op, packed: np.ndarray, unit_ptr, var_idx, lut, w, tau, maxiter: int = 500, tol: float = 1e-5):
         """``skat_2bit`` with the covariance under the fitted model on the explicit GRM of ``op`` (an
@@ -482,20 +422,12 @@ class Scanner:
         tau[1] K`` (``sgx_skat_kmat_2bit``) -> (score [entries], cov: per unit an [m, m] symmetric matrix,
         iters [entries]: PCG steps of every entry's solve)."""
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        unit_ptr = np.ascontiguousarray(unit_ptr, dtype=np.int64)
-        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
         lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
         w = np.ascontiguousarray(w, dtype=np.float64)
         tau = np.ascontiguousarray(tau, dtype=np.float64)
-        n_units = unit_ptr.size - 1
-        if packed.ndim != 2 or lut.shape[0] != var_idx.size or n_units < 0 or unit_ptr[-1] != var_idx.size:
-            raise ValueError("skat_kmat: inconsistent CSR / table shapes")
+        unit_ptr, var_idx, n_units, sizes, offs = _unit_args("skat_kmat", unit_ptr, var_idx, [(lut, (4,))], packed.ndim == 2)
         if w.shape != (op.n,) or tau.shape != (2,):
             raise ValueError("skat_kmat: w must have one entry per sample of the matrix and tau two entries")
-        sizes = np.diff(unit_ptr)
-        if (sizes < 0).any():
-            raise ValueError("skat_kmat: unit_ptr not ascending")
-        offs = np.concatenate([[0], np.cumsum(sizes * sizes)])
         score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
         iters = np.zeros(max(1, var_idx.size), dtype=np.int32)
         if var_idx.size:
@@ -503,8 +435,7 @@ class Scanner:
                                              unit_ptr.ctypes.data, var_idx.ctypes.data, lut.ctypes.data, w.ctypes.data,
                                              tau.ctypes.data, int(maxiter), float(tol), score.ctypes.data, cov.ctypes.data,
                                              iters.ctypes.data))
-        return (score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)],
-                iters[:var_idx.size])
+        return score[:var_idx.size], _unit_matrices(cov, sizes, offs), iters[:var_idx.size]
 
     def skat_kmat_ms(self) -> np.ndarray:
         """Host milliseconds of the last ``skat_kmat`` call: columns, solves, products."""
@@ -606,14 +537,15 @@ class Scanner:
         check(self._L.sgx_set_thresholds(self._h, maf, mac, missing, spa_pval))
 
 
-class Block:
+class Block(_Handle):
     """A block of variants resident on the device (``sgx_block``: the 2-bit rows, the positions of their missing
     genotypes, the carrier lists of the rare variants): depends on the number of samples only, so one loaded
     block can be scanned with any number of models.  ``clist_avg`` (test hook): room of the carrier lists in
     entries per variant."""
 
+    _attr, _free = "_b", "sgx_block_free"
+
     def __init__(self, n_samp: int, max_variants: int, device: int = 0, clist_avg: int = None):
-        self._L = load()
         b = C.c_void_p()
         if clist_avg is None:
             check(self._L.sgx_block_create(int(n_samp), int(max_variants), int(device), C.byref(b)))
@@ -638,32 +570,16 @@ class Block:
     def n_variants(self) -> int:
         return int(self._L.sgx_block_variants(self._b))
 
-    def close(self):
-        if getattr(self, "_b", None):
-            self._L.sgx_block_free(self._b)
-            self._b = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class DosageBlock:
+class DosageBlock(_Handle):
     """A batch of dosage rows resident on the device (``sgx_dsblock``) for the aggregate tests: loaded once, it
     serves the per-variant counts, the single-variant test of every row, the burden rows of all units and the SKAT
     sums of all units.
     ``dtype``: uint8 (0xFF = missing), int32 (INT_MIN = missing) or float64 (NaN / Inf = missing)."""
 
+    _attr, _free = "_b", "sgx_dsblock_free"
+
     def __init__(self, sc: Scanner, dtype, max_variants: int):
-        self._L = load()
         dt = np.dtype(dtype)
         if dt not in DS_DTYPES:
             raise TypeError("the dosages should be uint8, int32 or float64")
@@ -727,23 +643,14 @@ class DosageBlock:
         """Score statistics and their covariance per unit (CSR over the block's rows; per entry ``flip`` and the mean
         that stands in for a missing dosage, already flipped; ``sgx_ds_block_skat``) -> (score [entries], cov: per unit
         an [m, m] symmetric matrix), as ``Scanner.skat_2bit``."""
-        unit_ptr = np.ascontiguousarray(unit_ptr, dtype=np.int64)
-        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
         flip = np.ascontiguousarray(flip, dtype=np.uint8)
         mean = np.ascontiguousarray(mean, dtype=np.float64)
-        n_units = unit_ptr.size - 1
-        if var_idx.ndim != 1 or flip.shape != var_idx.shape or mean.shape != var_idx.shape or n_units < 0 \
-                or unit_ptr[-1] != var_idx.size:
-            raise ValueError("DosageBlock.skat: inconsistent CSR / table shapes")
-        sizes = np.diff(unit_ptr)
-        if (sizes < 0).any():
-            raise ValueError("DosageBlock.skat: unit_ptr not ascending")
-        offs = np.concatenate([[0], np.cumsum(sizes * sizes)])
+        unit_ptr, var_idx, n_units, sizes, offs = _unit_args("DosageBlock.skat", unit_ptr, var_idx, [(flip, ()), (mean, ())])
         score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
         if var_idx.size:
             check(self._L.sgx_ds_block_skat(self._sc._h, self._b, n_units, unit_ptr.ctypes.data, var_idx.ctypes.data,
                                             flip.ctypes.data, mean.ctypes.data, score.ctypes.data, cov.ctypes.data))
-        return score[:var_idx.size], [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(n_units)]
+        return score[:var_idx.size], _unit_matrices(cov, sizes, offs)
 
     def cond_set(self, var_idx, flip, mean):
         """Installs the conditioning set of the conditional scan from resident rows (``sgx_ds_block_cond_set``): 0 to
@@ -775,23 +682,6 @@ class DosageBlock:
         check(self._L.sgx_ds_block_cond(self._sc._h, self._b, flip.ctypes.data, mean.ctypes.data, score.ctypes.data,
                                         var.ctypes.data, cov.ctypes.data))
         return score[:m], var[:m], cov[:m * c].reshape(m, c)
-
-    def close(self):
-        if getattr(self, "_b", None):
-            self._L.sgx_dsblock_free(self._b)
-            self._b = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 class PinnedBuffer:
@@ -872,17 +762,77 @@ def quantize_packed(raw, cls, scale, offset, n_samp: int, sel=None, device: int 
     return packed, nv, sm, dv, dsum
 
 
-class GrmOperator:
+class _Operator(_Handle):
+    """What the operators on a GRM of ``n`` samples share: the entry points that the library has once per kind of
+    GRM under the same name and prototype, ``_prefix`` + name.  Several right-hand sides are the rows of B ([k, N]),
+    k of any size: they go to the library in batches of GRM_MAX_RHS."""
+
+    _prefix = None
+
+    def _fn(self, name: str):
+        return getattr(self._L, self._prefix + name)
+
+    def _rhs(self, B) -> np.ndarray:
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[1] != self.n:
+            raise ValueError("B must be [k, N]: one right-hand side of N samples per row")
+        return B
+
+    def _weights(self, w) -> np.ndarray:
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (self.n,):
+            raise ValueError("w must have one entry per sample")
+        return w
+
+    @staticmethod
+    def _batches(k: int):
+        return [(j0, min(GRM_MAX_RHS, k - j0)) for j0 in range(0, k, GRM_MAX_RHS)]
+
+    def sync(self):
+        check(self._fn("sync")(self._h))
+
+    def diag(self) -> np.ndarray:
+        out = np.empty(self.n, dtype=np.float64)
+        check(self._fn("diag")(self._h, out.ctypes.data))
+        return out
+
+    def crossprod_many(self, B: np.ndarray) -> np.ndarray:
+        """GRM b_j for every row b_j of B ([k, N] -> [k, N]); row j equals crossprod(B[j]) bit for bit."""
+        B = self._rhs(B)
+        out = np.empty_like(B)
+        for j0, k in self._batches(B.shape[0]):
+            check(self._fn("crossprod_multi")(self._h, B[j0].ctypes.data, self.n, k, out[j0].ctypes.data))
+        return out
+
+    def crossprod_many_dev(self, b_ptr: int, ldb: int, k: int, out_ptr: int):
+        """Device form: k vectors at b_ptr + j * ldb doubles (asynchronous until sync())."""
+        check(self._fn("crossprod_multi_dev")(self._h, b_ptr, int(ldb), int(k), out_ptr))
+
+    def pcg_many(self, w: np.ndarray, tau, B: np.ndarray, maxiter: int = 500, tol: float = 1e-5):
+        """pcg on every row of B in lockstep -> (X [k, N], iters [k]); row j equals pcg(w, tau, B[j])
+        bit for bit, with the same iteration count."""
+        B, w = self._rhs(B), self._weights(w)
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        X = np.empty_like(B)
+        iters = np.zeros(B.shape[0], dtype=np.int32)
+        for j0, k in self._batches(B.shape[0]):
+            check(self._fn("pcg_multi")(self._h, w.ctypes.data, tau.ctypes.data, B[j0].ctypes.data, self.n, k,
+                                        int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
+        return X, iters
+
+
+class GrmOperator(_Operator):
     """Implicit GRM of the null-model fit on one GPU (``sgx_grm``): the operator
     behind ``saige_store_2b_geno`` / ``get_crossprod_b_grm`` / ``PCG_diag_sigma``
     (reference src/saige_fitnull.cpp:159-230, 435-536, 581-614)."""
+
+    _prefix, _free = "sgx_grm_", "sgx_grm_free"
 
     def __init__(self, packed, n_samp: int, device: int = 0, dev_ptr: int = 0, n_markers: int = 0,
                  bytes_per_marker: int = 0):
         """packed: numpy [n_markers, bytes_per_marker]; or dev_ptr/n_markers/bytes_per_marker
         for a matrix already in this GPU's memory."""
         L = load()
-        self._L = L
         h = C.c_void_p()
         self.n = int(n_samp)
         if dev_ptr:
@@ -898,31 +848,6 @@ class GrmOperator:
 
     def crossprod_dev(self, b_ptr: int, out_ptr: int):
         check(self._L.sgx_grm_crossprod_dev(self._h, b_ptr, out_ptr))
-
-    def sync(self):
-        check(self._L.sgx_grm_sync(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sgx_grm_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def diag(self) -> np.ndarray:
-        out = np.empty(self.n, dtype=np.float64)
-        check(self._L.sgx_grm_diag(self._h, out.ctypes.data))
-        return out
 
     # -- the explicit GRM (sgx_grm_dense / sgx_grm_sparse); marker groups are ignored
     DENSE_BLOCK = 4096     # rows / columns per sgx_grm_dense call of dense()
@@ -983,7 +908,7 @@ class GrmOperator:
         return out
 
     def pcg(self, w: np.ndarray, tau, b: np.ndarray, maxiter: int = 500, tol: float = 1e-5):
-        w = np.ascontiguousarray(w, dtype=np.float64)
+        w = self._weights(w)
         b = np.ascontiguousarray(b, dtype=np.float64)
         tau = np.ascontiguousarray(tau, dtype=np.float64)
         x = np.empty(self.n, dtype=np.float64)
@@ -991,40 +916,6 @@ class GrmOperator:
         check(self._L.sgx_grm_pcg(self._h, w.ctypes.data, tau.ctypes.data, b.ctypes.data, int(maxiter),
                                   float(tol), x.ctypes.data, C.byref(it)))
         return x, int(it.value)
-
-    # -- several right-hand sides: B is [k, N] (row j = vector j), k of any size (batches of GRM_MAX_RHS)
-    def _rhs(self, B) -> np.ndarray:
-        B = np.ascontiguousarray(B, dtype=np.float64)
-        if B.ndim != 2 or B.shape[1] != self.n:
-            raise ValueError("B must be [k, N]: one right-hand side of N samples per row")
-        return B
-
-    def crossprod_many(self, B: np.ndarray) -> np.ndarray:
-        """GRM b_j for every row b_j of B ([k, N] -> [k, N]); row j equals crossprod(B[j]) bit for bit."""
-        B = self._rhs(B)
-        out = np.empty_like(B)
-        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
-            k = min(GRM_MAX_RHS, B.shape[0] - j0)
-            check(self._L.sgx_grm_crossprod_multi(self._h, B[j0].ctypes.data, self.n, k, out[j0].ctypes.data))
-        return out
-
-    def crossprod_many_dev(self, b_ptr: int, ldb: int, k: int, out_ptr: int):
-        """Device form: k vectors at b_ptr + j * ldb doubles (asynchronous until sync())."""
-        check(self._L.sgx_grm_crossprod_multi_dev(self._h, b_ptr, int(ldb), int(k), out_ptr))
-
-    def pcg_many(self, w: np.ndarray, tau, B: np.ndarray, maxiter: int = 500, tol: float = 1e-5):
-        """pcg on every row of B in lockstep -> (X [k, N], iters [k]); row j equals pcg(w, tau, B[j])
-        bit for bit, with the same iteration count."""
-        B = self._rhs(B)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        tau = np.ascontiguousarray(tau, dtype=np.float64)
-        X = np.empty_like(B)
-        iters = np.zeros(B.shape[0], dtype=np.int32)
-        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
-            k = min(GRM_MAX_RHS, B.shape[0] - j0)
-            check(self._L.sgx_grm_pcg_multi(self._h, w.ctypes.data, tau.ctypes.data, B[j0].ctypes.data, self.n, k,
-                                            int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
-        return X, iters
 
     # -- marker groups; a column of a *_loco call leaves one group out (excl[j], -1: none)
     def set_groups(self, group, n_groups: Optional[int] = None):
@@ -1061,8 +952,7 @@ class GrmOperator:
         B = self._rhs(B)
         e = self._excl(excl, B.shape[0])
         out = np.empty_like(B)
-        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
-            k = min(GRM_MAX_RHS, B.shape[0] - j0)
+        for j0, k in self._batches(B.shape[0]):
             check(self._L.sgx_grm_crossprod_loco(self._h, B[j0].ctypes.data, self.n, k, e[j0:].ctypes.data,
                                                  out[j0].ctypes.data))
         return out
@@ -1082,8 +972,7 @@ class GrmOperator:
         tau = np.ascontiguousarray(tau, dtype=np.float64)
         X = np.empty_like(B)
         iters = np.zeros(B.shape[0], dtype=np.int32)
-        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
-            k = min(GRM_MAX_RHS, B.shape[0] - j0)
+        for j0, k in self._batches(B.shape[0]):
             rows, loc = np.unique(wi[j0:j0 + k], return_inverse=True)     # the weight rows this batch uses
             Wb = np.ascontiguousarray(W[rows])
             loc = np.ascontiguousarray(loc, dtype=np.int32)
@@ -1107,16 +996,17 @@ def csr_of_upper(n: int, i, j, x):
     return row_ptr, np.ascontiguousarray(cols[o], dtype=np.int32), np.ascontiguousarray(vals[o])
 
 
-class ExplicitGrmOperator:
+class ExplicitGrmOperator(_Operator):
     """Operator of an explicit GRM resident on one GPU (``sgx_kmat``): what ``seqFitNullGLMM_SPA(grm_mat=)`` fits
     the null model on.  ``grm``: a ``SparseGRM`` (its upper triangle is expanded to the full CSR here) or a square
-    float64 array (dense storage).  Products and solves as ``GrmOperator``.  ``csr=(row_ptr, col, val)`` instead of
-    ``grm`` hands a CSR to the library as it is; ``n`` / ``ld`` override the size and the row stride the library
-    is told (its argument checks are tested this way)."""
+    float64 array (dense storage).  Products and solves as ``GrmOperator``; the single ones are the k = 1 case of
+    the many.  ``csr=(row_ptr, col, val)`` instead of ``grm`` hands a CSR to the library as it is; ``n`` / ``ld``
+    override the size and the row stride the library is told (its argument checks are tested this way)."""
+
+    _prefix, _free = "sgx_kmat_", "sgx_kmat_free"
 
     def __init__(self, grm=None, device: int = 0, csr=None, n: Optional[int] = None, ld: Optional[int] = None):
         L = load()
-        self._L = L
         h = C.c_void_p()
         if csr is not None:
             rp = np.ascontiguousarray(csr[0], dtype=np.int64)
@@ -1140,77 +1030,17 @@ class ExplicitGrmOperator:
                                         C.byref(h)))
         self._h = h
 
-    def sync(self):
-        check(self._L.sgx_kmat_sync(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sgx_kmat_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def diag(self) -> np.ndarray:
-        out = np.empty(self.n, dtype=np.float64)
-        check(self._L.sgx_kmat_diag(self._h, out.ctypes.data))
-        return out
-
     def matvec_ms(self) -> float:
         """Device milliseconds of the kernels of the last product."""
         ms = C.c_double(0)
         check(self._L.sgx_kmat_matvec_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
-    def _rhs(self, B) -> np.ndarray:
-        B = np.ascontiguousarray(B, dtype=np.float64)
-        if B.ndim != 2 or B.shape[1] != self.n:
-            raise ValueError("B must be [k, N]: one right-hand side of N samples per row")
-        return B
-
-    def crossprod_many(self, B: np.ndarray) -> np.ndarray:
-        """K b_j for every row b_j of B ([k, N] -> [k, N]); row j equals crossprod(B[j]) bit for bit."""
-        B = self._rhs(B)
-        out = np.empty_like(B)
-        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
-            k = min(GRM_MAX_RHS, B.shape[0] - j0)
-            check(self._L.sgx_kmat_crossprod_multi(self._h, B[j0].ctypes.data, self.n, k, out[j0].ctypes.data))
-        return out
-
     def crossprod(self, b: np.ndarray) -> np.ndarray:
         b = np.ascontiguousarray(b, dtype=np.float64)
         if b.shape != (self.n,):
             raise ValueError("b must have one entry per sample")
         return self.crossprod_many(b[None, :])[0]
-
-    def crossprod_many_dev(self, b_ptr: int, ldb: int, k: int, out_ptr: int):
-        """Device form: k vectors at b_ptr + j * ldb doubles (asynchronous until sync())."""
-        check(self._L.sgx_kmat_crossprod_multi_dev(self._h, b_ptr, int(ldb), int(k), out_ptr))
-
-    def pcg_many(self, w: np.ndarray, tau, B: np.ndarray, maxiter: int = 500, tol: float = 1e-5):
-        """pcg on every row of B in lockstep -> (X [k, N], iters [k]); row j equals pcg(w, tau, B[j])
-        bit for bit, with the same iteration count."""
-        B = self._rhs(B)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        if w.shape != (self.n,):
-            raise ValueError("w must have one entry per sample")
-        tau = np.ascontiguousarray(tau, dtype=np.float64)
-        X = np.empty_like(B)
-        iters = np.zeros(B.shape[0], dtype=np.int32)
-        for j0 in range(0, B.shape[0], GRM_MAX_RHS):
-            k = min(GRM_MAX_RHS, B.shape[0] - j0)
-            check(self._L.sgx_kmat_pcg_multi(self._h, w.ctypes.data, tau.ctypes.data, B[j0].ctypes.data, self.n, k,
-                                             int(maxiter), float(tol), X[j0].ctypes.data, iters[j0:].ctypes.data))
-        return X, iters
 
     def pcg_many_dev(self, w_ptr: int, tau, b_ptr: int, ldb: int, k: int, x_ptr: int, maxiter: int = 500,
                      tol: float = 1e-5) -> np.ndarray:

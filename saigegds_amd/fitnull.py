@@ -182,9 +182,12 @@ class _Param:
 
 
 class _Fitter:
-    """``batched``: the solves that share (w, tau) -- Y and the columns of X, the trace vectors -- go to
-    the operator's ``pcg_many`` / ``crossprod_many`` in one call (each column bit-identical to the
-    single solve); an operator without them is called column by column."""
+    """The algorithm is written once, on ``solve`` and ``products``: rows of right-hand sides that share
+    (w, tau) -- Y and the columns of X, the trace vectors, the columns of X1 -- in, rows out.  Only those
+    two methods know how the rows reach the operator: ``batched`` and an operator with ``pcg_many`` /
+    ``crossprod_many`` take them in one call, anything else one ``pcg`` / ``crossprod`` per row, in row
+    order.  The operators give every row of a batched call the bits of its single call, so ``batched`` is a
+    cost choice and changes no result."""
 
     def __init__(self, op, X: np.ndarray, y: np.ndarray, fit0: GlmFit, param: _Param, rng: RRandom,
                  batched: bool = False):
@@ -197,36 +200,29 @@ class _Fitter:
         x, _ = self.op.pcg(w, tau, b, self.p.maxiterPCG, self.p.tolPCG)
         return x
 
-    def pcg_many(self, w, tau, B):
+    def solve(self, w, tau, B):
         """Solves of the rows of B ([k, N]) -> [k, N]."""
-        if hasattr(self.op, "pcg_many"):
+        if self.batched and hasattr(self.op, "pcg_many"):
             return self.op.pcg_many(w, tau, B, self.p.maxiterPCG, self.p.tolPCG)[0]
         return np.stack([self.pcg(w, tau, np.ascontiguousarray(b)) for b in B])
 
-    def crossprod_many(self, B):
-        if hasattr(self.op, "crossprod_many"):
+    def products(self, B):
+        """GRM products of the rows of B ([k, N]) -> [k, N]."""
+        if self.batched and hasattr(self.op, "crossprod_many"):
             return self.op.crossprod_many(B)
         return np.stack([self.op.crossprod(np.ascontiguousarray(b)) for b in B])
 
     # get_coeff_w (:739-758)
-    def get_coeff_w(self, Y, w, tau):
+    def get_coeff_w(self, Y, w, tau, S=None):
+        """``S``: the solves of Y and of the columns of X ([1 + K, N]) where the caller has them already."""
         X = self.X
-        if self.batched:
-            S = self.pcg_many(w, tau, np.vstack([Y[None, :], X.T]))
-            Sigma_iY, Sigma_iX = S[0], np.ascontiguousarray(S[1:].T)
-        else:
-            Sigma_iY = self.pcg(w, tau, Y)
-            Sigma_iX = np.column_stack([self.pcg(w, tau, np.ascontiguousarray(X[:, i])) for i in range(X.shape[1])])
-        cov, alpha, eta = self.coeff_of_solves(Y, w, tau, Sigma_iY, Sigma_iX)
-        return Sigma_iY, Sigma_iX, cov, alpha, eta
-
-    def coeff_of_solves(self, Y, w, tau, Sigma_iY, Sigma_iX):
-        """The dense part of get_coeff_w, given its solves."""
-        X = self.X
+        if S is None:
+            S = self.solve(w, tau, np.vstack([Y[None, :], X.T]))
+        Sigma_iY, Sigma_iX = S[0], np.ascontiguousarray(S[1:].T)
         cov = _mat_inv(X.T @ Sigma_iX)
         alpha = cov @ (Sigma_iX.T @ Y)
         eta = Y - tau[0] * (Sigma_iY - Sigma_iX @ alpha) / w
-        return cov, alpha, eta
+        return Sigma_iY, Sigma_iX, cov, alpha, eta
 
     def working(self, eta):
         """mu, the working response Y and the IRLS weights W at eta (offset included)."""
@@ -237,20 +233,26 @@ class _Fitter:
         W = mu_eta * mu_eta / fam.variance(mu)
         return mu, Y, W
 
+    def irls_step(self, Y, W, tau, a0, S=None):
+        """One step of get_coeff from the state (Y, W), ``S`` as for get_coeff_w -> (the next state: get_coeff's
+        dict, whether alpha is within the criterion of a0)."""
+        tol_coef = 0.1
+        Sigma_iY, Sigma_iX, cov, alpha, eta = self.get_coeff_w(Y, W, tau, S)
+        eta = eta + self.offset
+        mu, Y, W = self.working(eta)
+        done = np.max(np.abs(alpha - a0) / (np.abs(alpha) + np.abs(a0) + tol_coef)) < tol_coef
+        return dict(Y=Y, mu=mu, alpha=alpha, eta=eta, W=W, cov=cov, Sigma_iY=Sigma_iY, Sigma_iX=Sigma_iX), done
+
     # get_coeff (:778-813)
     def get_coeff(self, tau, alpha0, eta0):
-        offset = self.offset
-        tol_coef = 0.1
         mu, Y, W = self.working(eta0)
         a0 = alpha0
         for _ in range(self.p.maxiter):
-            Sigma_iY, Sigma_iX, cov, alpha, eta = self.get_coeff_w(Y, W, tau)
-            eta = eta + offset
-            mu, Y, W = self.working(eta)
-            if np.max(np.abs(alpha - a0) / (np.abs(alpha) + np.abs(a0) + tol_coef)) < tol_coef:
+            c, done = self.irls_step(Y, W, tau, a0)
+            if done:
                 break
-            a0 = alpha
-        return dict(Y=Y, mu=mu, alpha=alpha, eta=eta, W=W, cov=cov, Sigma_iY=Sigma_iY, Sigma_iX=Sigma_iX)
+            Y, W, a0 = c["Y"], c["W"], c["alpha"]
+        return c
 
     def get_coeff_lockstep(self, tau, alpha0, eta0, keys, solve):
         """``get_coeff`` for several operators at once (the leave-one-chromosome-out models, SAIGE's
@@ -259,8 +261,7 @@ class _Fitter:
         every key in ``act``, the 1 + K right-hand sides ``B[key]`` ([1 + K, N]: Y, then the columns of X)
         with the weights ``W[key]`` on that key's operator -> {key: (S [1 + K, N], iters [1 + K])}.
         -> {key: get_coeff's dict plus steps (IRLS steps taken) and pcg_iters ([steps, 1 + K])}."""
-        offset, X = self.offset, self.X
-        tol_coef = 0.1
+        X = self.X
         st = {}
         for k in keys:
             mu, Y, W = self.working(eta0)
@@ -274,17 +275,12 @@ class _Fitter:
             for k in act:
                 c = st[k]
                 Sk, its = S[k]
-                Sigma_iY, Sigma_iX = Sk[0], np.ascontiguousarray(Sk[1:].T)
-                cov, alpha, eta = self.coeff_of_solves(c["Y"], c["W"], tau, Sigma_iY, Sigma_iX)
-                eta = eta + offset
-                mu, Y, W = self.working(eta)
-                c.update(Y=Y, mu=mu, W=W, alpha=alpha, eta=eta, cov=cov, Sigma_iY=Sigma_iY, Sigma_iX=Sigma_iX,
-                         steps=c["steps"] + 1)
+                nxt, done = self.irls_step(c["Y"], c["W"], tau, c["a0"], Sk)
+                c.update(nxt, steps=c["steps"] + 1)
                 c["pcg_iters"].append([int(v) for v in its])
-                if np.max(np.abs(alpha - c["a0"]) / (np.abs(alpha) + np.abs(c["a0"]) + tol_coef)) < tol_coef:
-                    continue
-                c["a0"] = alpha
-                still.append(k)
+                if not done:
+                    c["a0"] = nxt["alpha"]
+                    still.append(k)
             act = still
         return st
 
@@ -295,23 +291,15 @@ class _Fitter:
         nrun_start, nrun_end = 0, p.nrun
         buf, buf0 = np.zeros(p.nrun), np.zeros(p.nrun)
         while True:
-            if self.batched:
-                # the vectors in the reference's draw order, then all solves and products at once
-                U = np.stack([2 * self.rng.rbinom1_half(n) - 1 for _ in range(nrun_start, nrun_end)])
-                SU, AU = self.pcg_many(w, tau, U), self.crossprod_many(U)
-                for i in range(nrun_start, nrun_end):
-                    u, Sigma_iu, Au = U[i - nrun_start], SU[i - nrun_start], AU[i - nrun_start]
-                    Pu = Sigma_iu - Sigma_iX @ (cov @ (Sigma_iX.T @ u))
-                    buf[i] = float(Au @ Pu)
-                    buf0[i] = float(u @ Pu)
-            else:
-                for i in range(nrun_start, nrun_end):
-                    u = 2 * self.rng.rbinom1_half(n) - 1
-                    Sigma_iu = self.pcg(w, tau, u)
-                    Pu = Sigma_iu - Sigma_iX @ (cov @ (Sigma_iX.T @ u))
-                    Au = self.op.crossprod(u)
-                    buf[i] = float(Au @ Pu)
-                    buf0[i] = float(u @ Pu)
+            # the round's vectors in the reference's draw order (only the draws consume the generator), then their
+            # solves, then their products
+            U = np.stack([2 * self.rng.rbinom1_half(n) - 1 for _ in range(nrun_start, nrun_end)])
+            SU, AU = self.solve(w, tau, U), self.products(U)
+            for i in range(nrun_start, nrun_end):
+                u, Sigma_iu, Au = U[i - nrun_start], SU[i - nrun_start], AU[i - nrun_start]
+                Pu = Sigma_iu - Sigma_iX @ (cov @ (Sigma_iX.T @ u))
+                buf[i] = float(Au @ Pu)
+                buf0[i] = float(u @ Pu)
             cv = _calc_cv(buf)
             cv0 = _calc_cv(buf0) if quant else 0.0
             if cv > p.traceCVcutoff or cv0 > p.traceCVcutoff:
@@ -457,7 +445,7 @@ class _Fitter:
         mu_eta = fam.mu_eta(eta)
         W = mu_eta * mu_eta / fam.variance(mu)
         X1 = obj_noK["X1"]
-        Sigma_iX = np.column_stack([self.pcg(W, tau, np.ascontiguousarray(X1[:, i])) for i in range(X1.shape[1])])
+        Sigma_iX = np.ascontiguousarray(self.solve(W, tau, X1.T).T)
         XSX_inv = _mat_inv(X1.T @ Sigma_iX)
         XXVX_inv, XV = obj_noK["XXVX_inv"], obj_noK["XV"]
         rows: List[tuple] = []
@@ -531,14 +519,23 @@ _DS_NODE = "annotation/format/DS"
 _MARKER_PASS = 4096                            # markers per pass: bounded host memory at any M x N
 
 
+def _marker_filter(nv: np.ndarray, ac: np.ndarray, n_samp: int, maf: float, missing_rate: float) -> np.ndarray:
+    """The variant filter of the GRM markers (seqSetFilterCond): per variant ``nv`` samples with a value (int64) and
+    ``ac``, the sum of their allele counts or dosages -> af = ac / (2 nv), min(af, 1 - af) >= maf and
+    (n_samp - nv) / n_samp <= missing_rate."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        af = ac / (2.0 * nv)
+    return (np.minimum(af, 1 - af) >= maf) & ((n_samp - nv) / n_samp <= missing_rate)
+
+
 def _ds_grm_markers(src: GdsFile, sel: np.ndarray, n_all: int, want, var_ids: np.ndarray, maf: float,
                     missing_rate: float, on_gpu: bool):
     """GRM markers of a file without genotypes: the rows of ``annotation/format/DS`` rounded to hard calls
     (``gds.round_dosage_codes``), in passes of ``_MARKER_PASS`` variants.  The stored rows go to the device as they
     are (``sgx_quantize_packed``) when ``on_gpu``, else -- an injected operator, or a node of a class the device
     does not take -- through the numpy statement of the same rule.  ``sel``: the model's samples as indices into
-    the file's ``n_all``.  The variant filter takes the REAL dosages (SeqArray's allele frequency on a file without
-    genotypes): af = ds_sum / (2 ds_valid), min(af, 1 - af) >= maf, (n_samp - ds_valid) / n_samp <= missing_rate;
+    the file's ``n_all``.  The variant filter (``_marker_filter``) takes the REAL dosages, their count and sum
+    (SeqArray's allele frequency on a file without genotypes);
     with ``want`` (a set of variant ids) there is no filter and only those rows are quantised.
     -> (keep_idx, keep_packed): per pass the kept row numbers and their 2-bit rows."""
     from .gds import quantize_dosage_2bit
@@ -570,10 +567,7 @@ def _ds_grm_markers(src: GdsFile, sel: np.ndarray, n_all: int, want, var_ids: np
         else:
             pk, _, _, dv, dsum = quantize_dosage_2bit(raw, cls, scale, offset, sel=sel_q)
         if loc is None:
-            with np.errstate(invalid="ignore", divide="ignore"):
-                af = dsum / (2.0 * dv)
-            v = (np.minimum(af, 1 - af) >= maf) & ((n_samp - dv.astype(np.int64)) / n_samp <= missing_rate)
-            loc = np.flatnonzero(v)
+            loc = np.flatnonzero(_marker_filter(dv.astype(np.int64), dsum, n_samp, maf, missing_rate))
             pk = np.ascontiguousarray(pk[loc])
         keep_idx.append(loc + s0)
         keep_packed.append(pk)
@@ -653,11 +647,7 @@ def _select_grm_markers(src, sel: List[int], gsid: List[str], maf: float, missin
         if gpu_counts is not None:
             nv = gpu_counts[0][s0:s0 + CH].astype(np.int64)
             ac = gpu_counts[1][s0:s0 + CH].astype(np.int64)
-            with np.errstate(invalid="ignore", divide="ignore"):
-                af = ac / (2.0 * nv)
-            mafv = np.minimum(af, 1 - af)
-            v = (mafv >= maf) & ((n_samp - nv) / n_samp <= missing_rate)
-            loc = np.flatnonzero(v)
+            loc = np.flatnonzero(_marker_filter(nv, ac, n_samp, maf, missing_rate))
             keep_idx.append(loc + s0)
             keep_packed.append(np.ascontiguousarray(blk[loc]))
             continue
@@ -669,10 +659,7 @@ def _select_grm_markers(src, sel: List[int], gsid: List[str], maf: float, missin
             valid = codes != 3
             nv = valid.sum(axis=1)
             ac = np.where(valid, codes, 0).sum(axis=1, dtype=np.int64)
-            with np.errstate(invalid="ignore", divide="ignore"):
-                af = ac / (2.0 * nv)
-            mafv = np.minimum(af, 1 - af)
-            v = (mafv >= maf) & ((n_samp - nv) / n_samp <= missing_rate)
+            v = _marker_filter(nv, ac, n_samp, maf, missing_rate)
         else:
             v = np.fromiter((int(x) in want for x in var_ids[s0:s0 + CH]), dtype=bool, count=blk.shape[0])
         loc = np.flatnonzero(v)

@@ -287,7 +287,7 @@ def _null_model_noK(X1: np.ndarray, y: np.ndarray, fit0) -> Dict[str, np.ndarray
 
 def saige_gxg_snp_bin(fitter: _Fitter, fit0, tau, G0: np.ndarray, obj_noK: Dict[str, np.ndarray]) -> Dict[str, Any]:
     """``saige_GxG_snp_bin`` (src/saige_fitnull.cpp:1477-1558): eta and mu of the glm fit, tau of the
-    GLMM; Sigma_iX and Sigma_iG are solved together when the fitter is batched."""
+    GLMM; Sigma_iX and Sigma_iG are one ``fitter.solve``."""
     from scipy.special import ndtri
     fam = fit0.family
     eta, mu = fit0.linear_predictors, fit0.fitted_values
@@ -299,12 +299,8 @@ def saige_gxg_snp_bin(fitter: _Fitter, fit0, tau, G0: np.ndarray, obj_noK: Dict[
     G0 = np.asarray(G0, dtype=np.float64)
     n_nonzero = int(np.count_nonzero(G0))
     G = G0 - obj_noK["XXVX_inv"] @ (obj_noK["XV"] @ G0)
-    if fitter.batched:
-        S = fitter.pcg_many(W, tau, np.vstack([X1.T, G[None, :]]))
-        Sigma_iX, Sigma_iG = np.ascontiguousarray(S[:-1].T), S[-1]
-    else:
-        Sigma_iX = np.column_stack([fitter.pcg(W, tau, np.ascontiguousarray(X1[:, i])) for i in range(X1.shape[1])])
-        Sigma_iG = fitter.pcg(W, tau, G)
+    S = fitter.solve(W, tau, np.vstack([X1.T, G[None, :]]))
+    Sigma_iX, Sigma_iG = np.ascontiguousarray(S[:-1].T), S[-1]
     adj = Sigma_iX @ (_mat_inv(X1.T @ Sigma_iX) @ (X1.T @ Sigma_iG))
     S_ = float(np.sum((y - mu) * G))
     var1 = float(np.sum(G * Sigma_iG)) - float(np.sum(G * adj))

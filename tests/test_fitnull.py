@@ -109,6 +109,79 @@ def test_fit_host_logic_with_oracle_operator(trait, tmp_path):
     assert np.array_equal(np.asarray(back.variant_id), np.asarray(m.variant_id))
 
 
+class _Recording:
+    """The oracle's operator with a log of (method, rows) per call."""
+
+    def __init__(self, packed, n, log):
+        from oracle.oracle import GrmOracle
+        self.op, self.n, self.log = GrmOracle(packed, n), n, log
+
+    def crossprod(self, b):
+        self.log.append(("crossprod", 1))
+        return self.op.crossprod(b)
+
+    def pcg(self, w, tau, b, maxiter=500, tol=1e-5):
+        self.log.append(("pcg", 1))
+        return self.op.pcg(w, tau, b, maxiter, tol)
+
+    def close(self):
+        self.op.close()
+
+
+class _RecordingMany(_Recording):
+    """... with the batched methods, by looping."""
+
+    def crossprod_many(self, B):
+        self.log.append(("crossprod_many", len(B)))
+        return np.stack([self.op.crossprod(np.ascontiguousarray(b)) for b in B])
+
+    def pcg_many(self, w, tau, B, maxiter=500, tol=1e-5):
+        self.log.append(("pcg_many", len(B)))
+        res = [self.op.pcg(w, tau, np.ascontiguousarray(b), maxiter, tol) for b in B]
+        return np.stack([x for x, _ in res]), np.array([it for _, it in res], dtype=np.int32)
+
+
+def test_fit_makes_the_same_operator_calls_batched_or_not():
+    """The fitter's single path: unbatched it makes the single calls the two-path fitter made (212 solves and 155
+    products on these markers, counted with this wrapper on the commit before the paths were joined); batched, an
+    operator with the ``_many`` methods gets the same rows in fewer calls and the fit keeps its bits."""
+    g = np.load(os.path.join(GOLD, "grm1k_10k_snp.npz"))
+    _, data = _inputs()
+    packed = np.ascontiguousarray(g["packed"][::8])
+    src = GenotypeSource(list(g["sample_id"]), packed=packed, variant_id=g["variant_id"][::8])
+    nrun, K = 30, 3
+
+    def rows(log, kinds):
+        return sum(k for name, k in log if name in kinds)
+
+    log1, markers = [], []
+
+    def single(p, n):
+        markers.append(p)                 # (the markers that pass the filter)
+        return _Recording(p, n, log1)
+
+    one = seqFitNullGLMM_SPA("y ~ x1 + x2", data, src, verbose=False, nrun=nrun, operator_factory=single)
+    assert set(log1) == {("pcg", 1), ("crossprod", 1)}
+    assert rows(log1, {"pcg"}) == 212 and rows(log1, {"crossprod"}) == 155
+
+    # the driver batches on an explicit GRM only: the matrix is a stand-in, the operator is the one over the markers
+    logk = []
+    many = seqFitNullGLMM_SPA("y ~ x1 + x2", data, src, verbose=False, nrun=nrun, grm_mat=(g["sample_id"], np.eye(len(g["sample_id"]))),
+                              operator_factory=lambda grm, n: _RecordingMany(markers[0], n, logk))
+    for k in ("tau", "coefficients", "fitted_values", "linear_predictors", "residuals", "cov", "var_ratio"):
+        assert np.array_equal(np.asarray(getattr(many, k)), np.asarray(getattr(one, k))), k
+    for k, v in one.var_ratio_table.items():
+        assert np.array_equal(np.asarray(many.var_ratio_table[k]), np.asarray(v)), k
+    assert rows(logk, {"pcg", "pcg_many"}) == 212 and rows(logk, {"crossprod", "crossprod_many"}) == 155
+    # Y with the columns of X per IRLS step; a trace round's vectors (nrun, then 10 more per extension), solved, then
+    # multiplied; the columns of X1 once, for the variance ratio
+    assert {k for name, k in logk if name == "pcg_many"} <= {1 + K, nrun, 10, K}
+    at = [i for i, c in enumerate(logk) if c == ("pcg_many", nrun)]
+    assert at and all(logk[i + 1] == ("crossprod_many", nrun) for i in at)
+    assert logk.count(("crossprod_many", nrun)) == len(at)
+    assert logk.count(("pcg_many", K)) == 1
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("trait", ["binary", "quantitative"])
 def test_fit_on_gpu_matches_golden_model(trait):
