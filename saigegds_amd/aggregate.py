@@ -3,28 +3,35 @@
 Python mirror of ``seqAssocGLMM_spaBurden()``, ``seqAssocGLMM_spaACAT_V()``,
 ``seqAssocGLMM_spaACAT_O()`` and ``pACAT()`` (reference R/assoc_aggregate.r:51-797,
 native side src/saige_main.cpp:466-1052).  The reference calls one native routine per
-unit; here the work of ALL units goes through the scan library in three batches:
+unit; here the units go through the scan library in batches.  One flow serves the three drivers and the SKAT driver
+(``skat.py``): ``_prepare`` opens the input, the model (thresholds 0 / 0 / 1 as ``.init_nullmod(modobj, ii, 0, 0, 1,
+...)`` sets them) and the scanner; ``_run`` then takes the batches of units of a rows backend, and per batch
 
-1. one ``sgx_scan_2bit`` over every variant that occurs in a unit (thresholds 0 / 0 / 1 as
-   ``.init_nullmod(modobj, ii, 0, 0, 1, ...)`` sets them): its AF / num columns give the
-   per-variant maf and mac of ``ds_mat_mafmac`` and its p-values are the single-variant
-   tests of ACAT-V;
-2. one ``sgx_burden_2bit`` over all (unit, weight) burden rows: the weighted, mean-imputed,
-   minor-allele-oriented collapse of ``ds_mat_burden`` is a device kernel, followed on the
-   device by the same single-variant test;
-3. the Cauchy combination (``acat_pval``) on the host.
+1. loads the batch's distinct variants: counts and the single-variant scan table;
+2. forms the per-variant maf and mac of ``ds_mat_mafmac`` and the single-variant p-values of ACAT-V
+   (``variant_stats``);
+3. for SKAT, selects each unit's variants and takes their score statistics and covariance (``skat_step``);
+4. for the driver's burden columns, makes the normalised weights, the flip and the mean of ``ds_mat_burden``
+   (``_burden_entries``) and has the device collapse the rows -- weighted, mean-imputed, minor-allele-oriented --
+   and put them through the same single-variant test;
 
-That is the flow of 2-bit genotypes (``$dosage_alt``, the RAW branch of the reference routines).  Dosage
-input -- a format node such as ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` of uint8, int32 or
-float64 (the INTSXP / REALSXP branches) -- goes through ``DosageBlock`` in batches of consecutive units whose
-distinct variants fit a byte budget on the device: the rows of a batch are uploaded once, and counts, single-variant
-tests and the burden rows of every column of the driver are made from the resident rows (``_run_dosage``); the SKAT
-driver (``skat.py``) takes its score statistics and covariance matrices from the same resident rows.
+the Cauchy combination (``acat_pval``) follows on the host.  The two backends:
+
+* 2-bit genotypes (``$dosage_alt``, the RAW branch of the reference routines; also an integer matrix that holds hard
+  calls only, ``reduce_hard_calls``): ``_packed_rows``, one batch with every unit -- one ``sgx_scan_2bit``, one
+  ``sgx_burden_2bit`` per column kind over all (unit, weight) rows, one ``sgx_skat_2bit``;
+* dosages -- a format node such as ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` of uint8, int32 or
+  float64 (the INTSXP / REALSXP branches): ``_dosage_rows``, batches of consecutive units whose distinct variants fit
+  a byte budget on the device; the rows of a batch are uploaded once to a ``DosageBlock`` and everything above is
+  made from the resident rows.
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import dataclasses
 import math
+from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -143,33 +150,258 @@ def _check_beta(wbeta) -> np.ndarray:
 
 @dataclasses.dataclass(slots=True)
 class _Prepared:
-    """What ``_prepare`` hands a set-test driver.  The per-variant arrays are indexed by ``local``."""
+    """A set-test driver's call: what ``_prepare`` opens and ``_run`` fills.  The per-variant arrays hold one row per
+    distinct variant of the units, in ascending order of the variant index."""
     units: _Units
     wbeta: np.ndarray                       # [2, n_weights]
     inp: ScanInput = None                   # the opened input
-    local: Dict[int, int] = None            # 1-based variant index -> row of the per-variant arrays
     sm: ScanModel = None                    # the model at thresholds 0 / 0 / 1
     binary: bool = False
     wb_colnm: List[str] = None              # "b<a>_<b>" per weight set
     sc: Any = None                          # the scanner; the driver closes it
+    backend: Any = None                     # the rows backend, not yet entered (_packed_rows / _dosage_rows)
+    index: List[np.ndarray] = None          # per unit: rows of the per-variant arrays
     n: np.ndarray = None                    # per variant: non-missing samples,
     s: np.ndarray = None                    # their sum (a double sum for real dosages),
     maf: np.ndarray = None
     mac: np.ndarray = None
     pval: np.ndarray = None                 # the single-variant p-value (NaN: rejected by the scan's filter)
     out: np.ndarray = None                  # the scan table [n, 8] and
-    valid: np.ndarray = None                # its valid flags (dosage route: the SKAT driver only)
-    rows: List[List[int]] = None            # per unit: rows of the per-variant arrays (_summary_cols)
-    packed: np.ndarray = None               # 2-bit route: the variants' rows for the model's samples
-    st: np.ndarray = None                   # dosage route: the truncated `int sum` of ds_mat_burden
-    ds_out: Optional[Dict[str, Any]] = None  # dosage route: column kind -> (burden rows [n_units, n_weights, 8], valid)
-    skat_rows: List[np.ndarray] = None      # dosage route, SKAT: per unit the variants in the test,
-    skat_S: List[np.ndarray] = None         # their score statistics
-    skat_Phi: List[np.ndarray] = None       # and covariance
+    valid: np.ndarray = None                # its valid flags
+    burden: Dict[str, Any] = None           # column kind -> (burden rows [n_units, n_weights, 8], valid)
+    skat: List[SkatStep] = None             # the SKAT driver: the device step of every batch of units
 
 
-def _prepare_model(pr, mod, used, spa_pval, var_ratio, verbose, scanner_factory):
-    """The model and the scanner of a driver call (and what the reference prints about the units)."""
+DS_BUDGET = 1 << 30      # bytes of dosage rows resident on the device per batch of units
+
+
+def ds_row_bytes(dtype, n_samp: int) -> int:
+    """Bytes of one resident dosage row: uint8 rows stay bytes, int32 and float64 rows are held as doubles."""
+    return n_samp * (1 if np.dtype(dtype) == np.uint8 else 8)
+
+
+def load_rows(blk, rows):
+    """What a dosage reader returned -> the block: rows as the file stores them, or decoded rows."""
+    return blk.load_packed(*rows.args()) if isinstance(rows, PackedRows) else blk.load(rows)
+
+
+def flip_mean(n, s):
+    """The scan's own imputation and flip of rows from their counts (n non-missing, s their double sum) ->
+    (flip = s > n as uint8, mean = s / n, or 2 - s / n where flipped)."""
+    n = np.asarray(n, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = s / n
+    fl = s > n
+    return fl.astype(np.uint8), np.where(fl, 2 - m, m)
+
+
+def dosage_tables(flip, mean, w=None) -> np.ndarray:
+    """The value of each 2-bit code per row, [m, 4]: {0, 1, 2, mean} w, or {2, 1, 0, mean} w where ``flip`` -- ``mean``
+    stands in for the missing code and is the flipped row's own (``flip_mean``: 2 - s / n there).  The one definition
+    of these tables on the host; ``cond._tables`` restates it in torch for rows that stay on the device."""
+    mean = np.asarray(mean, dtype=np.float64)
+    w = np.ones_like(mean) if w is None else w
+    t = np.stack([0 * w, w, 2 * w, mean * w], axis=1)
+    return np.where(np.asarray(flip)[:, None] != 0, t[:, [2, 1, 0, 3]], t)
+
+
+def reduce_hard_calls(inp: ScanInput) -> ScanInput:
+    """An in-memory integer matrix that holds 0, 1, 2 and the missing code only has the meaning of the reference's RAW
+    branch: the same input as 2-bit rows.  Any other input comes back as it is."""
+    ds = inp.ds_all
+    if inp.kind != "dosage" or not inp.in_mem or inp.ds_dtype == np.float64:
+        return inp
+    miss = 0xFF if ds.dtype == np.uint8 else np.iinfo(np.int32).min
+    if not np.all((ds == miss) | ((ds >= 0) & (ds <= 2))):
+        return inp
+    codes = np.where((ds < 0) | (ds > 2), 3, ds).astype(np.uint8)
+    return dataclasses.replace(inp, kind="packed", packed=pack_dosage_2bit(codes), ds_all=None, ds_dtype=None)
+
+
+def variant_stats(n, s, out, valid):
+    """``ds_mat_mafmac`` (src/saige_main.cpp:466-524) from a variant's counts (n non-missing, s their sum) and its row of
+    the scan table -> (maf, mac, pval); ``single_test_*`` gives NaN where the scan's filter rejects."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        af = s / (2 * n)
+    return np.where(n > 0, np.minimum(af, 1 - af), np.nan), np.minimum(s, 2 * n - s), np.where(valid != 0, out[:, 5], np.nan)
+
+
+# ---- the rows backends: batches (of units), load, burden, skat ------------------------------------------------------
+# load(bv): the distinct variants bv of a batch -> (n, s, st, out, valid): n non-missing, s their (double) sum, st the
+#   truncated `int sum` of ds_mat_burden, and the scan table of the rows;
+# burden(grp_ptr, var_idx, flip, mean, W): groups (CSR over rows of bv) x the columns of W ([entries, n_cols], NaN =
+#   entry not in that column) -> (burden rows [groups * n_cols, 8] or [groups, n_cols, 8], valid);
+# skat(unit_ptr, var_idx, flip, mean) -> (score [entries], cov per unit, PCG steps per entry or None).
+
+@contextlib.contextmanager
+def _packed_rows(pr: _Prepared, used, kmat=None):
+    """2-bit rows: one batch with every unit.  ``kmat`` = (matrix, weights, maxiter, tol): SKAT's covariance on the
+    explicit GRM (``sgx_skat_kmat_2bit``) instead of ``sgx_skat_2bit``."""
+    sc, nw = pr.sc, pr.wbeta.shape[1]
+    packed = pr.inp.packed_rows_at(used - 1)
+
+    def load(bv):
+        out, valid = sc.scan_2bit(packed)
+        ok = valid != 0
+        n = np.where(ok, out[:, 2], 0).astype(np.float64)
+        s = np.where(ok, np.rint(out[:, 0] * 2 * n), 0.0)           # RAW branch: s = sum of codes
+        if not ok.all():    # a variant rejected by the scan's filter (monomorphic: maf = 0) still has counts: from the host
+            codes = unpack_dosage_2bit(packed[~ok], pr.inp.n_samp).astype(np.int64)
+            n[~ok], s[~ok] = (codes != 3).sum(axis=1), np.where(codes != 3, codes, 0).sum(axis=1)
+        return n, s, s.astype(np.int64), out, valid                 # integer codes: nothing to truncate
+
+    def burden(grp_ptr, var_idx, flip, mean, W):
+        ng = len(grp_ptr) - 1
+        grp = np.repeat(np.arange(ng), np.diff(grp_ptr))
+        res = []
+        for c0 in range(0, W.shape[1], nw):       # one call per column kind, its rows ordered (unit, weight set)
+            e, c = np.nonzero(np.isfinite(W[:, c0:c0 + nw]))
+            row = grp[e] * nw + c
+            o = np.argsort(row, kind="stable")
+            e, c = e[o], c[o]
+            row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=ng * nw))])
+            out, valid = sc.burden_2bit(packed, row_ptr, var_idx[e], dosage_tables(flip[e], mean[e], W[e, c0 + c]))
+            res.append((out.reshape(ng, nw, 8), valid.reshape(ng, nw)))
+        return np.concatenate([o for o, _ in res], axis=1), np.concatenate([v for _, v in res], axis=1)
+
+    def skat(unit_ptr, var_idx, flip, mean):
+        lut = dosage_tables(flip, mean)
+        if kmat is None:
+            return (*sc.skat_2bit(packed, unit_ptr, var_idx, lut), None)
+        from ._lib import ExplicitGrmOperator
+        mat, w, maxiter, tol = kmat
+        with ExplicitGrmOperator(mat) as op:
+            return sc.skat_kmat(op, packed, unit_ptr, var_idx, lut, w, pr.sm.tau, maxiter=maxiter, tol=tol)
+
+    yield SimpleNamespace(batches=[list(range(len(pr.index)))], load=load, burden=burden, skat=skat)
+
+
+@contextlib.contextmanager
+def _dosage_rows(pr: _Prepared, used, stored, budget):
+    """Dosage rows: batches of consecutive units whose distinct variants fit ``budget`` bytes of resident rows (a unit
+    larger than that is a batch of its own); one ``DosageBlock`` of the largest batch's size, one upload per batch.  A
+    variant that two batches share (sliding windows) is loaded in both.  ``skat`` is None where the block has none."""
+    read_rows, dtype = pr.inp.dosage_reader(stored), pr.inp.ds_dtype
+    row_bytes = ds_row_bytes(dtype, pr.sm.n)
+    batches, cur, seen = [], [], set()
+    for u, r in enumerate(pr.index):
+        new = set(r.tolist()) - seen
+        if cur and (len(seen) + len(new)) * row_bytes > budget:
+            batches.append(cur)
+            cur, seen, new = [], set(), set(r.tolist())
+        cur.append(u)
+        seen |= new
+    batches.append(cur)
+    cap = max(np.unique(np.concatenate([pr.index[u] for u in bt])).size for bt in batches)
+    with pr.sc.dosage_block(dtype, cap) as blk:
+        def load(bv):
+            n, s, st = load_rows(blk, read_rows(used[bv] - 1))
+            return (n, s, st, *blk.scan())
+
+        def burden(grp_ptr, var_idx, flip, mean, W):
+            with np.errstate(invalid="ignore"):
+                return blk.burden(grp_ptr, var_idx, flip, W, mean[:, None] * W)
+
+        skat = (lambda *a: (*blk.skat(*a), None)) if hasattr(blk, "skat") else None
+        yield SimpleNamespace(batches=batches, load=load, burden=burden, skat=skat)
+
+
+SkatStep = collections.namedtuple("SkatStep", "kept unit_ptr var_idx flip mean score cov n_iter")
+
+
+def skat_step(pr: _Prepared, skat, rows, bv) -> SkatStep:
+    """SKAT's device step for the units whose variants are ``rows`` (per unit, rows of the per-variant arrays), all of
+    them resident as ``bv``.  ``kept``: per unit the variants in the test, those that pass the scan with mac > 0;
+    ``unit_ptr`` / ``var_idx``: the same as CSR over the resident rows; ``flip`` / ``mean``: the scan's own imputation
+    and flip, from the double sum ``s`` -- not from the truncated sum, which is a quirk of the reference's burden code
+    only; ``score`` / ``cov`` / ``n_iter``: what the backend's ``skat`` returns for them."""
+    ok = (pr.valid != 0) & (pr.mac > 0)
+    kept = [r[ok[r]] for r in rows]
+    rows_k = np.concatenate(kept)
+    unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])]).astype(np.int64)
+    var_idx = np.searchsorted(bv, rows_k).astype(np.int32)
+    flip, mean = flip_mean(pr.n[rows_k], pr.s[rows_k])
+    return SkatStep(kept, unit_ptr, var_idx, flip, mean, *skat(unit_ptr, var_idx, flip, mean))
+
+
+def _burden_entries(pr: _Prepared, rows, bv, n, st, kinds, burden_mac):
+    """``ds_mat_burden`` (src/saige_main.cpp:526-610) up to the collapse itself, for the units whose variants are
+    ``rows``: per unit a group of entries (the variants with a weight in any column) -> (grp_ptr, var_idx into the
+    resident rows bv, flip, mean, W [entries, kinds x weight sets]).  Column kind "all": weights dbeta(maf); "rare",
+    ACAT-V's burden of the rare variants: the same where mac < burden_mac (mac >= threshold -> single-variant test, not
+    in the burden).  The weights are normalised per column (``f64_normalize``); the mean and the flip come from the
+    reference's `int sum` ``st``."""
+    grp_ptr, var_idx, flip, mean, ws = [0], [], [], [], []
+    for r in rows:
+        cols = []
+        for kind in kinds:
+            keep = pr.mac[r] < burden_mac if kind == "rare" else True
+            cols += [np.where(keep, _dbeta(pr.maf[r], a, b), np.nan) for a, b in pr.wbeta.T]
+        W = np.array(cols, dtype=np.float64).reshape(len(cols), len(r)).T.copy()
+        for c in range(W.shape[1]):
+            fin = np.isfinite(W[:, c])
+            sm = W[fin, c].sum()
+            if sm > 0:
+                W[fin, c] = W[fin, c] * (1 / sm)                   # f64_normalize
+        p = np.searchsorted(bv, r)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = st[p] / n[p]                                       # (double)sum / n
+        fl = st[p] > n[p]
+        keep = np.isfinite(W).any(axis=1)
+        var_idx.append(p[keep])
+        flip.append(fl[keep])
+        mean.append(np.where(fl, 2 - m, m)[keep])
+        ws.append(W[keep])
+        grp_ptr.append(grp_ptr[-1] + int(keep.sum()))
+    return (grp_ptr, np.concatenate(var_idx).astype(np.int32), np.concatenate(flip).astype(np.uint8), np.concatenate(mean),
+            np.concatenate(ws).reshape(-1, len(kinds) * pr.wbeta.shape[1]))
+
+
+def _run(pr: _Prepared, kinds=(), burden_mac=float("nan"), skat=False):
+    """The device side of a driver call, per batch of units of the rows backend: load the batch's distinct variants,
+    fill the per-variant arrays, then SKAT's step (``skat``: pr.skat gets one ``SkatStep`` per batch) and one burden call
+    with every column of the driver (``kinds``: pr.burden[kind] = (rows [n_units, n_weights, 8], valid))."""
+    nu, nw, nv = len(pr.index), pr.wbeta.shape[1], np.unique(np.concatenate(pr.index)).size
+    pr.n, pr.s, pr.out, pr.valid = np.zeros(nv), np.zeros(nv), np.full((nv, 8), np.nan), np.zeros(nv, dtype=np.uint8)
+    pr.maf, pr.mac, pr.pval = np.full(nv, np.nan), np.full(nv, np.nan), np.full(nv, np.nan)
+    rows_out, rows_valid = np.full((nu, len(kinds) * nw, 8), np.nan), np.zeros((nu, len(kinds) * nw), dtype=np.uint8)
+    pr.skat = [] if skat else None
+    with pr.backend as be:
+        if skat and be.skat is None:
+            raise NotImplementedError("SKAT on dosage input is not implemented.")
+        for bt in be.batches:
+            rows = [pr.index[u] for u in bt]
+            bv = np.unique(np.concatenate(rows))                    # rows of the per-variant arrays
+            n, s, st, out, valid = be.load(bv)
+            n = n.astype(np.float64)
+            pr.n[bv], pr.s[bv], pr.out[bv], pr.valid[bv] = n, s, out, valid
+            pr.maf[bv], pr.mac[bv], pr.pval[bv] = variant_stats(n, s, out, valid)
+            if skat:
+                pr.skat.append(skat_step(pr, be.skat, rows, bv))
+            if kinds:
+                ob, vb = be.burden(*_burden_entries(pr, rows, bv, n, st, kinds, burden_mac))
+                rows_out[bt], rows_valid[bt] = ob.reshape(len(bt), -1, 8), vb.reshape(len(bt), -1)
+    pr.burden = {kind: (rows_out[:, k * nw:(k + 1) * nw], rows_valid[:, k * nw:(k + 1) * nw]) for k, kind in enumerate(kinds)}
+
+
+def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, scanner_factory=None, dsnode="",
+             ds_budget=None, kmat=None) -> _Prepared:
+    """Common head of the set-test drivers (R/assoc_aggregate.r:55-150): checks, sample matching, the model, the scanner
+    and the rows backend of the input (and what the reference prints about the units).  Nothing has gone to the device
+    yet: ``_run`` does that."""
+    if verbose:
+        print(what)
+    pr = _Prepared(_Units(units), _check_beta(wbeta))
+    for nm, v in (("spa.pval", spa_pval), ("var.ratio", var_ratio)):
+        if not _is_num(v):
+            raise TypeError(f"is.numeric({nm}) is not TRUE")
+    mod: NullModel = load_modobj(modobj, verbose)
+    no_loco(mod, what.rstrip(":"))
+    pr.inp = inp = reduce_hard_calls(open_scan_input(gdsfile, mod, dsnode, verbose))
+    used = np.unique(np.concatenate(pr.units.index))
+    if used.size == 0 or used.min() < 1 or used.max() > inp.n_var:
+        raise ValueError("No variant in the genotypic data set!")
+    pr.index = [np.searchsorted(used, ix) for ix in pr.units.index]
     if not math.isfinite(var_ratio):
         var_ratio = float(np.nanmean(mod.var_ratio))
     sizes = np.array([len(ix) for ix in pr.units.index])
@@ -190,235 +422,20 @@ def _prepare_model(pr, mod, used, spa_pval, var_ratio, verbose, scanner_factory)
     pr.sc = Scanner(pr.sm) if scanner_factory is None else scanner_factory(pr.sm)   # tests inject the CPU oracle
     if verbose:
         print("Calculating p-values:")
-
-
-DS_BUDGET = 1 << 30      # bytes of dosage rows resident on the device per batch of units
-
-
-def flip_mean(n, s):
-    """The scan's own imputation and flip of rows from their counts (n non-missing, s their double sum) ->
-    (flip = s > n as uint8, mean = s / n, or 2 - s / n where flipped)."""
-    n = np.asarray(n, dtype=np.float64)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        m = s / n
-    fl = s > n
-    return fl.astype(np.uint8), np.where(fl, 2 - m, m)
-
-
-def _sets_all(pr, r):
-    """Weights of a unit's burden row per weight set: dbeta(maf)."""
-    return [_dbeta(pr.maf[r], a, b) for a, b in pr.wbeta.T]
-
-
-def _sets_rare(pr, r, burden_mac):
-    """... of ACAT-V's burden of the rare variants: mac >= threshold -> single-variant test, not in the burden."""
-    rare = pr.mac[r] < burden_mac
-    return [np.where(rare, _dbeta(pr.maf[r], a, b), np.nan) for a, b in pr.wbeta.T]
-
-
-def _hard_calls(ds: np.ndarray) -> bool:
-    """An integer matrix that holds 0, 1, 2 and the missing code only: the RAW branch's meaning."""
-    miss = 0xFF if ds.dtype == np.uint8 else np.iinfo(np.int32).min
-    return bool(np.all((ds == miss) | ((ds >= 0) & (ds <= 2))))
-
-
-def _run_dosage(pr, stored, used, kinds, burden_mac, budget):
-    """Dosage flow: the units in batches of consecutive units whose distinct variants fit ``budget`` bytes of
-    resident rows (a unit larger than that is a batch of its own).  Per batch: rows -> block (one upload), counts and
-    single-variant tests into the per-variant arrays, weights, one burden call with every column of the driver.
-    A variant that two batches share (sliding windows) is loaded in both.  Fills pr.n / s / maf / mac / pval and
-    pr.ds_out[kind] = (rows [n_units, n_weights, 8], valid).
-
-    Column kind ``"skat"`` (the SKAT driver's only kind) makes no burden rows: the batch's scan table is kept per
-    variant (pr.out [n, 8], pr.valid), and one ``blk.skat`` call per batch gives every unit its variants with
-    valid != 0 and mac > 0 (pr.skat_rows[u]), their score statistics and covariance (pr.skat_S[u], pr.skat_Phi[u]).
-    Its flip and mean come from the double sum ``s`` -- what the scan's own imputation 2 AF and its flip use -- not
-    from the truncated ``st``, which is a quirk of the reference's burden code only."""
-    if "rare" in kinds and not pr.binary:
-        return                                    # ACAT-V / ACAT-O of a quantitative trait: the driver raises, as the reference does
-    read_rows, dtype = pr.inp.dosage_reader(stored), pr.inp.ds_dtype
-    n_samp = pr.sm.n
-    row_bytes = n_samp * (1 if np.dtype(dtype) == np.uint8 else 8)
-    index = [np.array([pr.local[int(v)] for v in ix], dtype=np.int64) for ix in pr.units.index]
-    batches, cur, seen = [], [], set()
-    for u, r in enumerate(index):
-        new = set(r.tolist()) - seen
-        if cur and (len(seen) + len(new)) * row_bytes > budget:
-            batches.append(cur)
-            cur, seen, new = [], set(), set(r.tolist())
-        cur.append(u)
-        seen |= new
-    batches.append(cur)
-    skat = "skat" in kinds
-    kinds = tuple(k for k in kinds if k != "skat")
-    nv_used, nu, nw, nk = used.size, len(index), pr.wbeta.shape[1], len(kinds)
-    pr.n, pr.s, pr.st = np.zeros(nv_used), np.zeros(nv_used), np.zeros(nv_used, dtype=np.int64)
-    pr.maf, pr.mac, pr.pval = np.full(nv_used, np.nan), np.full(nv_used, np.nan), np.full(nv_used, np.nan)
-    out_all, valid_all = np.full((nu, nk * nw, 8), np.nan), np.zeros((nu, nk * nw), dtype=np.uint8)
-    cap = max(np.unique(np.concatenate([index[u] for u in bt])).size for bt in batches)
-    if skat:
-        pr.out, pr.valid = np.full((nv_used, 8), np.nan), np.zeros(nv_used, dtype=np.uint8)
-        pr.skat_rows, pr.skat_S, pr.skat_Phi = [None] * nu, [None] * nu, [None] * nu
-    with pr.sc.dosage_block(dtype, cap) as blk:
-        if skat and not hasattr(blk, "skat"):
-            raise NotImplementedError("SKAT on dosage input is not implemented.")
-        for bt in batches:
-            bv = np.unique(np.concatenate([index[u] for u in bt]))          # rows of the per-variant arrays
-            rows = read_rows(used[bv] - 1)
-            n, s, st = blk.load_packed(*rows.args()) if isinstance(rows, PackedRows) else blk.load(rows)
-            out, valid = blk.scan()
-            n = n.astype(np.float64)
-            # ds_mat_mafmac (src/saige_main.cpp:485-524): n non-missing, s their sum (a double sum for REAL dosages)
-            with np.errstate(invalid="ignore", divide="ignore"):
-                af = s / (2 * n)
-            pr.n[bv], pr.s[bv], pr.st[bv] = n, s, st
-            pr.maf[bv] = np.where(n > 0, np.minimum(af, 1 - af), np.nan)
-            pr.mac[bv] = np.minimum(s, 2 * n - s)
-            pr.pval[bv] = np.where(valid != 0, out[:, 5], np.nan)          # single_test_*: NaN when the filter rejects
-            # ds_mat_burden (:526-610): the mean and the flip from its `int sum` (st), weights normalised per column
-            loc = {int(v): k for k, v in enumerate(bv)}
-            if skat:
-                pr.out[bv], pr.valid[bv] = out, valid
-                ok = (pr.valid != 0) & (pr.mac > 0)
-                kept = [index[u][ok[index[u]]] for u in bt]
-                rows_k = np.concatenate(kept)
-                unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])])
-                score, cov = blk.skat(unit_ptr, np.array([loc[int(v)] for v in rows_k], dtype=np.int32),
-                                      *flip_mean(pr.n[rows_k], pr.s[rows_k]))
-                for k, u in enumerate(bt):
-                    pr.skat_rows[u], pr.skat_Phi[u] = kept[k], np.array(cov[k], dtype=np.float64)
-                    pr.skat_S[u] = np.array(score[unit_ptr[k]:unit_ptr[k + 1]], dtype=np.float64)
-            if not kinds:
-                continue
-            grp_ptr, var_idx, flip, ws, mws = [0], [], [], [], []
-            for u in bt:
-                r = index[u]
-                cols = []
-                for kind in kinds:
-                    cols += _sets_all(pr, r) if kind == "all" else _sets_rare(pr, r, burden_mac)
-                W = np.array(cols, dtype=np.float64).reshape(nk * nw, len(r)).T.copy()
-                for c in range(W.shape[1]):
-                    fin = np.isfinite(W[:, c])
-                    sm = W[fin, c].sum()
-                    if sm > 0:
-                        W[fin, c] = W[fin, c] * (1 / sm)                   # f64_normalize
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    m = pr.st[r] / pr.n[r]                                 # (double)sum / n
-                fl = pr.st[r] > pr.n[r]
-                m = np.where(fl, 2 - m, m)
-                keep = np.isfinite(W).any(axis=1)
-                var_idx += [loc[int(v)] for v in r[keep]]
-                flip += list(fl[keep])
-                ws.append(W[keep])
-                with np.errstate(invalid="ignore"):
-                    mws.append(m[keep, None] * W[keep])
-                grp_ptr.append(len(var_idx))
-            ob, vb = blk.burden(grp_ptr, np.asarray(var_idx, dtype=np.int32), np.asarray(flip, dtype=np.uint8),
-                                np.concatenate(ws).reshape(-1, nk * nw), np.concatenate(mws).reshape(-1, nk * nw))
-            out_all[bt] = ob.reshape(len(bt), nk * nw, 8)
-            valid_all[bt] = vb.reshape(len(bt), nk * nw)
-    pr.ds_out = {kind: (out_all[:, k * nw:(k + 1) * nw], valid_all[:, k * nw:(k + 1) * nw]) for k, kind in enumerate(kinds)}
-
-
-def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, scanner_factory=None, dsnode="",
-             kinds=("all",), burden_mac=float("nan"), ds_budget=None) -> _Prepared:
-    """Common head of the three drivers (R/assoc_aggregate.r:55-150): checks, sample matching,
-    model, and the per-variant scan of every variant that occurs in a unit.  Dosage input: the whole
-    device side, the burden rows of the driver's column ``kinds`` included (``_run_dosage``)."""
-    if verbose:
-        print(what)
-    pr = _Prepared(_Units(units), _check_beta(wbeta))
-    for nm, v in (("spa.pval", spa_pval), ("var.ratio", var_ratio)):
-        if not _is_num(v):
-            raise TypeError(f"is.numeric({nm}) is not TRUE")
-    mod: NullModel = load_modobj(modobj, verbose)
-    no_loco(mod, what.rstrip(":"))
-    inp = open_scan_input(gdsfile, mod, dsnode, verbose)
-    if inp.kind == "dosage" and inp.in_mem and inp.ds_dtype != np.float64 and _hard_calls(inp.ds_all):
-        # hard calls: the reference's RAW branch has the same meaning -> the 2-bit path
-        codes = np.where((inp.ds_all < 0) | (inp.ds_all > 2), 3, inp.ds_all).astype(np.uint8)
-        inp = dataclasses.replace(inp, kind="packed", packed=pack_dosage_2bit(codes), ds_all=None, ds_dtype=None)
-    pr.inp = inp
-    used = np.unique(np.concatenate(pr.units.index))
-    if used.size == 0 or used.min() < 1 or used.max() > inp.n_var:
-        raise ValueError("No variant in the genotypic data set!")
-    pr.local = {int(v): k for k, v in enumerate(used)}
-    if inp.kind != "packed":
-        _prepare_model(pr, mod, used, spa_pval, var_ratio, verbose, scanner_factory)
-        try:
-            _run_dosage(pr, inp.stored_ok(scanner_factory), used, kinds, burden_mac, DS_BUDGET if ds_budget is None else ds_budget)
-        except BaseException:
-            pr.sc.close()
-            raise
-        return pr
-    pr.packed = packed = inp.packed_rows_at(used - 1)
-    _prepare_model(pr, mod, used, spa_pval, var_ratio, verbose, scanner_factory)
-    out, valid = pr.sc.scan_2bit(packed)
-    # ds_mat_mafmac (src/saige_main.cpp:466-524), RAW branch: n non-missing, s = sum of codes
-    num = out[:, 2]
-    # a variant rejected by the scan's filter (monomorphic: maf = 0) still has counts: redo them on the host
-    codes = None
-    if (valid == 0).any():
-        codes = unpack_dosage_2bit(packed[valid == 0], inp.n_samp).astype(np.int64)
-    n = np.where(valid != 0, num, 0).astype(np.float64)
-    s = np.where(valid != 0, np.rint(out[:, 0] * 2 * np.where(valid != 0, num, 0)), 0.0)
-    if codes is not None:
-        nm = (codes != 3).sum(axis=1)
-        sm_ = np.where(codes != 3, codes, 0).sum(axis=1)
-        n[valid == 0] = nm
-        s[valid == 0] = sm_
-    with np.errstate(invalid="ignore", divide="ignore"):
-        af = s / (2 * n)
-    pr.n, pr.s = n, s
-    pr.maf = np.where(n > 0, np.minimum(af, 1 - af), np.nan)
-    pr.mac = np.minimum(s, 2 * n - s)
-    pr.pval = np.where(valid != 0, out[:, 5], np.nan)          # single_test_*: NaN when the filter rejects
-    pr.out, pr.valid = out, valid                               # the whole table: the SKAT driver's SPA adjustment
+    if inp.kind == "packed":
+        pr.backend = _packed_rows(pr, used, kmat)
+    else:
+        pr.backend = _dosage_rows(pr, used, inp.stored_ok(scanner_factory), DS_BUDGET if ds_budget is None else ds_budget)
     return pr
 
 
 def _summary_cols(pr: _Prepared) -> Dict[str, Any]:
     ans: Dict[str, Any] = dict(pr.units.desp)
-    rows = [[pr.local[int(v)] for v in ix] for ix in pr.units.index]
-    pr.rows = rows
-    ans["numvar"] = np.array([len(r) for r in rows])
-    st = np.array([[*_mean_sd(pr.maf[r]), *_minmax(pr.maf[r]), *_mean_sd(pr.mac[r]), *_minmax(pr.mac[r])] for r in rows])
+    ans["numvar"] = np.array([len(r) for r in pr.index])
+    st = np.array([[*_mean_sd(pr.maf[r]), *_minmax(pr.maf[r]), *_mean_sd(pr.mac[r]), *_minmax(pr.mac[r])] for r in pr.index])
     for k, nm in enumerate(("maf.avg", "maf.sd", "maf.min", "maf.max", "mac.avg", "mac.sd", "mac.min", "mac.max")):
         ans[nm] = st[:, k]
     return ans
-
-
-def _burden_rows(pr: _Prepared, weight_sets: List[List[np.ndarray]], kind: str = "all"):
-    """weight_sets[u][k] = per-variant weights (NaN = not in the burden) of unit u, row kind k.
-    Returns the scan rows [n_units, n_kinds, 8] and validity; ``f64_normalize`` and the tables of
-    ``ds_mat_burden`` (RAW branch) are formed here.  Dosage input: the rows of column kind ``kind`` were
-    made while their batch was resident (``_run_dosage``, from the same weights)."""
-    if pr.ds_out is not None:
-        return pr.ds_out[kind]
-    row_ptr, var_idx, lut = [0], [], []
-    for u, sets in enumerate(weight_sets):
-        r = np.asarray(pr.rows[u])
-        for w in sets:
-            w = np.asarray(w, dtype=np.float64).copy()
-            fin = np.isfinite(w)
-            sm = w[fin].sum()
-            if sm > 0:
-                w[fin] = w[fin] * (1 / sm)                         # f64_normalize
-            for j in np.flatnonzero(fin):
-                v = r[j]
-                n, s = pr.n[v], pr.s[v]
-                m = s / n if n > 0 else float("nan")             # (double)sum / n
-                if s <= n:
-                    t = [0 * w[j], 1 * w[j], 2 * w[j], m * w[j]]
-                else:
-                    t = [2 * w[j], 1 * w[j], 0 * w[j], (2 - m) * w[j]]
-                var_idx.append(v)
-                lut.append(t)
-            row_ptr.append(len(var_idx))
-    lut_a = np.asarray(lut, dtype=np.float64).reshape(-1, 4)
-    out, valid = pr.sc.burden_2bit(pr.packed, np.asarray(row_ptr), np.asarray(var_idx, dtype=np.int32), lut_a)
-    nk = len(weight_sets[0]) if weight_sets else 0
-    return out.reshape(len(weight_sets), nk, 8), valid.reshape(len(weight_sets), nk)
 
 
 def _row_result(o, ok, n_snp, summac_thr):
@@ -438,16 +455,16 @@ def seqAssocGLMM_spaBurden(gdsfile, modobj, units, wbeta=AggrParamBeta, summac: 
     if not (_is_num(summac) and math.isfinite(summac)):
         raise TypeError("is.finite(summac) is not TRUE")
     pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE burden analysis:", scanner_factory,
-                  dsnode, ("all",), ds_budget=ds_budget)
+                  dsnode, ds_budget)
     try:
-        ans = _summary_cols(pr)
-        sets = [_sets_all(pr, r) for r in pr.rows]
-        out, valid = _burden_rows(pr, sets)
+        _run(pr, ("all",))
     finally:
         pr.sc.close()
+    ans = _summary_cols(pr)
+    out, valid = pr.burden["all"]
     for i, nm in enumerate(pr.wb_colnm):
         sfx = f".{nm}" if len(pr.wb_colnm) > 1 else ""
-        res = np.array([_row_result(out[u, i], valid[u, i], len(pr.rows[u]), summac) for u in range(len(pr.rows))])
+        res = np.array([_row_result(out[u, i], valid[u, i], len(r), summac) for u, r in enumerate(pr.index)])
         ans["summac" + sfx], ans["beta" + sfx], ans["SE" + sfx], ans["pval" + sfx] = res[:, 0], res[:, 1], res[:, 2], res[:, 3]
         if pr.binary:
             ans["p.norm" + sfx] = res[:, 4]
@@ -459,21 +476,19 @@ def seqAssocGLMM_spaBurden(gdsfile, modobj, units, wbeta=AggrParamBeta, summac: 
 def _acatv(pr: _Prepared, burden_mac: float, burden_summac: float):
     """ACAT-V per unit and weight set (saige_acatv_test_bin, src/saige_main.cpp:720-830):
     returns p [n_units, n_w], and (n.single, n.burden, median/min/max of the combined p-values)."""
-    nu, nw = len(pr.rows), pr.wbeta.shape[1]
-    sets = [_sets_rare(pr, r, burden_mac) for r in pr.rows]
-    has_b = [bool(np.isfinite(s[0]).any()) for s in sets]
-    out, valid = _burden_rows(pr, sets, "rare")
+    nu, nw = len(pr.index), pr.wbeta.shape[1]
+    out, valid = pr.burden["rare"]
     p = np.full((nu, nw), np.nan)
     extra = np.full((nu, 2 + 3 * nw), np.nan)
-    for u, r in enumerate(pr.rows):
-        r = np.asarray(r)
+    for u, r in enumerate(pr.index):
         single = pr.mac[r] >= burden_mac
         n_burden = int((~single).sum())
+        has_b = np.isfinite(_dbeta(pr.maf[r][~single], *pr.wbeta[:, 0])).any()      # a rare variant with a weight
         for i, (a, b) in enumerate(pr.wbeta.T):
             mf = pr.maf[r][single]
             pv = list(pr.pval[r][single])
             wp = list(_dbeta(mf, a, b) ** 2 * mf * (1 - mf))
-            if has_b[u]:
+            if has_b:
                 sm, _, _, pb, _, _ = _row_result(out[u, i], valid[u, i], len(r), burden_summac)
                 if np.isfinite(pb):
                     pm = pr.maf[r][~single].sum() / n_burden
@@ -497,14 +512,15 @@ def seqAssocGLMM_spaACAT_V(gdsfile, modobj, units, wbeta=AggrParamBeta, burden_m
                            ds_budget: Optional[int] = None) -> Dict[str, Any]:
     """ACAT-V tests (R/assoc_aggregate.r:309-557); binary outcomes only, as in the reference."""
     pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE ACAT-V analysis:", scanner_factory,
-                  dsnode, ("rare",), burden_mac, ds_budget)
+                  dsnode, ds_budget)
     try:
         if not pr.binary:
             raise NotImplementedError("'saige_acatv_test_quant' not implemented.")
-        ans = _summary_cols(pr)
-        p, extra = _acatv(pr, burden_mac, burden_summac)
+        _run(pr, ("rare",), burden_mac)
     finally:
         pr.sc.close()
+    ans = _summary_cols(pr)
+    p, extra = _acatv(pr, burden_mac, burden_summac)
     ans["n.single"], ans["n.burden"] = extra[:, 0].astype(np.int64), extra[:, 1].astype(np.int64)
     for i, nm in enumerate(pr.wb_colnm):
         sfx = f".v{nm[1:]}" if len(pr.wb_colnm) > 1 else ""      # wb_colnm = "v%g_%g", R/assoc_aggregate.r:389
@@ -522,18 +538,18 @@ def seqAssocGLMM_spaACAT_O(gdsfile, modobj, units, wbeta=AggrParamBeta, burden_m
     """ACAT-O: burden and ACAT-V p-values of every weight set combined by ACAT
     (R/assoc_aggregate.r:564-797, saige_acato_test_bin src/saige_main.cpp:845-976)."""
     pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE ACAT-O analysis:", scanner_factory,
-                  dsnode, ("all", "rare"), burden_mac, ds_budget)
+                  dsnode, ds_budget)
     try:
         if not pr.binary:
             raise NotImplementedError("'saige_acato_test_quant' not implemented.")
-        ans = _summary_cols(pr)
-        sets = [_sets_all(pr, r) for r in pr.rows]
-        out, valid = _burden_rows(pr, sets)
-        pb = np.array([[_row_result(out[u, i], valid[u, i], len(pr.rows[u]), burden_summac)[3]
-                        for i in range(pr.wbeta.shape[1])] for u in range(len(pr.rows))])
-        pv, _ = _acatv(pr, burden_mac, burden_summac)
+        _run(pr, ("all", "rare"), burden_mac)
     finally:
         pr.sc.close()
+    ans = _summary_cols(pr)
+    out, valid = pr.burden["all"]
+    pb = np.array([[_row_result(out[u, i], valid[u, i], len(r), burden_summac)[3] for i in range(pr.wbeta.shape[1])]
+                   for u, r in enumerate(pr.index)])
+    pv, _ = _acatv(pr, burden_mac, burden_summac)
     both = np.empty((pb.shape[0], 2 * pb.shape[1]))
     both[:, 0::2], both[:, 1::2] = pb, pv
     ans["pval"] = np.array([acat_pval(row) for row in both])

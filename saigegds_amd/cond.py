@@ -29,7 +29,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 
 from . import aggregate
-from .assoc import (BLOCK_SIZE, GenotypeSource, PackedRows, ScanInput, _open_source, _pretty, assemble_result,
+from .assoc import (BLOCK_SIZE, GenotypeSource, ScanInput, _open_source, _pretty, assemble_result,
                     check_scan_args, finish_result, open_scan_input, require_device)
 from .nullmod import ModelError, NullModel, init_nullmod, load_modobj, no_loco
 from .skat import spa_scale
@@ -93,7 +93,8 @@ def cond_tests(S, var, cov, S_C, Phi_CC, d=None, d_C=None):
 
 def _tables(af, valid):
     """Dosage tables of the rows on the rows' device (torch): m = 2 AF, flipped where AF > 0.5 -- {0, 1, 2, m} or
-    {2, 1, 0, 2 - m}, the imputation and flip of the scan itself; NaN where the row is not valid."""
+    {2, 1, 0, 2 - m}, the imputation and flip of the scan itself; NaN where the row is not valid.  The tables are those
+    of ``aggregate.dosage_tables`` (the definition on the host), restated here because AF stays on the device."""
     import torch
     m = 2 * af
     z = torch.zeros_like(m)
@@ -160,8 +161,7 @@ def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds):
     read_rows, ds_dtype, n_samp, n_var = inp.dosage_reader(stored), inp.ds_dtype, inp.n_samp, inp.n_var
 
     def load(blk, v0):
-        rows = read_rows(v0)
-        return blk.load_packed(*rows.args()) if isinstance(rows, PackedRows) else blk.load(rows)
+        return aggregate.load_rows(blk, read_rows(v0))
 
     make = getattr(sc, "dosage_block", None)
     if make is None:
@@ -180,8 +180,7 @@ def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds):
         fl, mean = aggregate.flip_mean(n, s)
         S_C, Phi_CC = blk.cond_set(rank, fl[rank], mean[rank])
         sc.set_thresholds(*thresholds)
-    row_bytes = n_samp * (1 if np.dtype(ds_dtype) == np.uint8 else 8)
-    per = int(max(1, min(n_var, aggregate.DS_BUDGET // row_bytes)))
+    per = int(max(1, min(n_var, aggregate.DS_BUDGET // aggregate.ds_row_bytes(ds_dtype, n_samp))))
     res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
     with make(ds_dtype, per) as blk:
         for off in range(0, n_var, per):

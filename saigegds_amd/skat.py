@@ -5,19 +5,19 @@ The reference has no SKAT (its set tests collapse a unit to one dosage row: burd
 mirrors reference code and no reference vector pins it: the definition is tied to the project's pinned scan and
 burden paths by identities (tests/test_gpu_skat.py).  The flow of a call:
 
-1. ``_prepare`` of the aggregate drivers: one ``sgx_scan_2bit`` over every variant that occurs in a unit (thresholds
-   0 / 0 / 1) for maf, mac and the single-variant p-values;
-2. one ``sgx_skat_2bit`` for all units: score statistics ``S`` and their covariance ``Phi`` per unit, the weighted Gram
-   matrix of the unit's 2-bit rows on the device's matrix cores;
-   With ``grm_mat=`` it is one ``sgx_skat_kmat_2bit`` instead: ``Phi`` becomes the covariance under the fitted model
-   on the explicit GRM, ``Phi^K = A' P A`` (DESIGN.md 8g), with no variance ratio;
+1. the batch loop of the aggregate drivers (``aggregate._prepare`` and ``_run``): per batch of units the scan of the
+   batch's variants at thresholds 0 / 0 / 1 for maf, mac and the single-variant p-values;
+2. in that loop, ``aggregate.skat_step``: score statistics ``S`` and their covariance ``Phi`` per unit, the weighted
+   Gram matrix of the unit's rows on the device's matrix cores;
 3. on the host, per unit and weight column: the SPA adjustment of ``Phi`` (binary traits), ``Q = sum w_j^2 S_j^2`` and
    its p-value under the mixture of chi-squares with the eigenvalues of ``diag(w) Phi diag(w)``.
 
-Dosage input (a format node such as ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` that does not reduce
-to hard calls) takes the aggregate drivers' dosage flow instead of 1 and 2: per batch of units the rows go to a
-resident ``DosageBlock`` once, ``blk.scan()`` gives the per-variant table and ``blk.skat()`` (``sgx_ds_block_skat``)
-``S`` and ``Phi`` of the batch's units; step 3 is the same code.
+Hard calls are one batch: one ``sgx_scan_2bit`` and one ``sgx_skat_2bit`` for all units.  With ``grm_mat=`` that is one
+``sgx_skat_kmat_2bit`` instead: ``Phi`` becomes the covariance under the fitted model on the explicit GRM,
+``Phi^K = A' P A``, with no variance ratio.  Dosage input (a format node such as
+``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` that does not reduce to hard calls) is cut into batches
+that fit the device: the rows of a batch go to a resident ``DosageBlock`` once, ``blk.scan()`` gives the per-variant
+table and ``blk.skat()`` (``sgx_ds_block_skat``) ``S`` and ``Phi`` of the batch's units.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .aggregate import AggrParamBeta, _dbeta, _prepare, _save, _summary_cols, flip_mean
+from .aggregate import AggrParamBeta, _dbeta, _prepare, _run, _save, _summary_cols, reduce_hard_calls
 from .assoc import GenotypeSource
 
 LAMBDA_DROP = 1e-10      # eigenvalues at or below this fraction of the largest one are dropped
@@ -167,7 +167,6 @@ def _unit_tests(pr, kept, S_of, phi_of):
 def _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat):
     """The refusals of ``seqAssocGLMM_spaSKAT(grm_mat=)``, before any row is read -> (the opened source, the matrix of the
     scan's samples in the scan's order, the model's weights V in that order)."""
-    from .aggregate import _hard_calls
     from .assoc import _open_source, open_scan_input
     from .grm import _align_grm_mat
     from .nullmod import load_modobj, no_loco
@@ -179,7 +178,7 @@ def _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat):
         raise NotImplementedError("SKAT with 'grm_mat' on dosage input is not implemented.")
     src = _open_source(gdsfile, False)          # opened once: the driver goes on with this object
     inp = open_scan_input(src, mod, dsnode, False)
-    if inp.kind != "packed" and not (inp.kind == "dosage" and inp.in_mem and inp.ds_dtype != np.float64 and _hard_calls(inp.ds_all)):
+    if reduce_hard_calls(inp).kind != "packed":
         raise NotImplementedError("SKAT with 'grm_mat' on dosage input is not implemented.")
     return src, _align_grm_mat(grm_mat, inp.sample_id()), np.ascontiguousarray(np.asarray(mod.V, dtype=np.float64)[inp.ii])
 
@@ -219,41 +218,30 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
         raise TypeError("is.character(dsnode) is not TRUE")
     if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
         raise NotImplementedError("SKAT on dosage input is not implemented.")
-    aligned = None
+    kmat = None
     if grm_mat is not None:
         gdsfile, aligned, aligned_w = _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat)
+        kmat = (aligned, aligned_w, maxiter_pcg, tol_pcg)
     pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT analysis:", scanner_factory,
-                  dsnode, ("skat",), ds_budget=ds_budget)
+                  dsnode, ds_budget, kmat)
     try:
-        ans = _summary_cols(pr)
-        if pr.ds_out is not None:
-            kept = pr.skat_rows
-            S_of, phi_of = pr.skat_S.__getitem__, pr.skat_Phi.__getitem__
-        else:
-            ok = (pr.valid != 0) & (pr.mac > 0)
-            kept = [np.asarray(r, dtype=np.int64)[ok[np.asarray(r, dtype=np.int64)]] for r in pr.rows]
-            var_idx = np.concatenate(kept).astype(np.int32) if kept else np.zeros(0, dtype=np.int32)
-            unit_ptr = np.concatenate([[0], np.cumsum([k.size for k in kept])]).astype(np.int64)
-            flip, m = flip_mean(pr.n[var_idx], pr.s[var_idx])         # (double)sum / n, as _burden_rows
-            z = 0 * m
-            lut = np.where(flip[:, None] != 0, np.stack([z + 2, z + 1, z, m], axis=1), np.stack([z, z + 1, z + 2, m], axis=1))
-            n_iter = None
-            if aligned is None:
-                score, cov = pr.sc.skat_2bit(pr.packed, unit_ptr, var_idx, lut)
-            else:
-                from ._lib import ExplicitGrmOperator
-                with ExplicitGrmOperator(aligned) as op:
-                    score, cov, it = pr.sc.skat_kmat(op, pr.packed, unit_ptr, var_idx, lut, aligned_w, pr.sm.tau,
-                                                     maxiter=maxiter_pcg, tol=tol_pcg)
-                n_iter = np.array([int(it[unit_ptr[u]:unit_ptr[u + 1]].max()) if k.size else 0 for u, k in enumerate(kept)],
-                                  dtype=np.int64)
-            S_of, phi_of = (lambda u: score[unit_ptr[u]:unit_ptr[u + 1]]), cov.__getitem__
+        _run(pr, skat=True)
     finally:
         pr.sc.close()
-    Q, P = _unit_tests(pr, kept, S_of, phi_of)
+    ans = _summary_cols(pr)
+    kept, S, Phi, n_iter = [], [], [], []
+    for st in pr.skat:                                  # a batch of units each, in the units' order
+        for k, r in enumerate(st.kept):
+            a, b = st.unit_ptr[k], st.unit_ptr[k + 1]
+            kept.append(r)
+            S.append(st.score[a:b])
+            Phi.append(st.cov[k])
+            if kmat is not None:
+                n_iter.append(int(st.n_iter[a:b].max()) if r.size else 0)
+    Q, P = _unit_tests(pr, kept, S.__getitem__, Phi.__getitem__)
     ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
-    if aligned is not None:
-        ans["n.iter"] = n_iter
+    if kmat is not None:
+        ans["n.iter"] = np.array(n_iter, dtype=np.int64)
     for i, nm in enumerate(pr.wb_colnm):
         sfx = f".{nm}" if len(pr.wb_colnm) > 1 else ""
         ans["Q" + sfx], ans["pval" + sfx] = Q[:, i], P[:, i]

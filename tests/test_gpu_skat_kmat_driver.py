@@ -1,7 +1,8 @@
 """``seqAssocGLMM_spaSKAT(grm_mat=)`` on the device, on the golden file with a model fitted by
 ``seqFitNullGLMM_SPA(grm_mat=)``.
 
-The driver's steps are assembled here from their parts (``_prepare``, the tables, ``_unit_tests``) and fed
+The driver's steps are taken from the driver itself (``_prepare``, ``_run``: its ``SkatStep``; ``dosage_tables``,
+``_unit_tests``) and fed
 
 * ``Scanner.skat_2bit``: the route of the call without ``grm_mat``, whose table must come out bit for bit;
 * the long-double Phi^K of tests/skat_kmat_ref.py on the matrix, V and tau the driver must pass: the p-values of the
@@ -61,27 +62,23 @@ def same(a, b, skip=(), q_rtol=0.0):
 def assembled(mod, sp):
     """The driver's steps from their parts -> (Q, pval) of the variance-ratio route (skat_2bit), pval of _unit_tests
     on skat_2bit's scores and the long-double Phi^K."""
-    from saigegds_amd.aggregate import _prepare, _summary_cols, flip_mean
+    from saigegds_amd.aggregate import _prepare, _run, dosage_tables
     from saigegds_amd.skat import _unit_tests
-    pr = _prepare(GDS, mod, UNITS, KW["wbeta"], 0.05, float("nan"), False, "SAIGE SKAT analysis:", None, "", ("skat",))
+    pr = _prepare(GDS, mod, UNITS, KW["wbeta"], 0.05, float("nan"), False, "SAIGE SKAT analysis:")
     try:
-        _summary_cols(pr)                          # (fills pr.rows, as in the driver)
-        ok = (pr.valid != 0) & (pr.mac > 0)
-        kept = [np.asarray(r, dtype=np.int64)[ok[np.asarray(r, dtype=np.int64)]] for r in pr.rows]
-        var_idx = np.concatenate(kept).astype(np.int32)
-        up = np.concatenate([[0], np.cumsum([k.size for k in kept])]).astype(np.int64)
-        flip, m = flip_mean(pr.n[var_idx], pr.s[var_idx])
-        z = 0 * m
-        lut = np.where(flip[:, None] != 0, np.stack([z + 2, z + 1, z, m], axis=1), np.stack([z, z + 1, z + 2, m], axis=1))
-        score, cov = pr.sc.skat_2bit(pr.packed, up, var_idx, lut)
+        _run(pr, skat=True)                        # the driver's own device step: one batch, skat_2bit
     finally:
         pr.sc.close()
+    [st] = pr.skat
+    kept, up, var_idx, score, cov = st.kept, st.unit_ptr, st.var_idx, st.score, st.cov
+    lut = dosage_tables(st.flip, st.mean)
+    packed = pr.inp.packed_rows_at(np.unique(np.concatenate(UNITS)) - 1)
     S_of = lambda u: score[up[u]:up[u + 1]]      # noqa: E731
     Q0, P0 = _unit_tests(pr, kept, S_of, cov.__getitem__)
     ids = pr.inp.sample_id()
     pos = {s: k for k, s in enumerate(sp.sample_id)}
     ix = np.array([pos[s] for s in ids])
-    c = dict(sm=pr.sm, packed=pr.packed, var_idx=var_idx, lut=lut, unit_ptr=up, K=dense_of(sp)[np.ix_(ix, ix)], blocks=None,
+    c = dict(sm=pr.sm, packed=packed, var_idx=var_idx, lut=lut, unit_ptr=up, K=dense_of(sp)[np.ix_(ix, ix)], blocks=None,
              w=np.asarray(mod.V, dtype=np.float64)[pr.inp.ii], tau=np.asarray(mod.tau, dtype=np.float64))
     _, phi_ref, _ = M.phi_units(c, "ld")
     _, P1 = _unit_tests(pr, kept, S_of, lambda u: np.asarray(phi_ref[u], dtype=np.float64))
