@@ -158,6 +158,12 @@ int sgx_scan_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant
 void *sgx_host_alloc(size_t bytes);
 void  sgx_host_free(void *p);
 
+/* Device and pinned bytes held right now by everything the library owns in this process: handles, blocks,
+ * operators and the scratch of calls in progress, over all devices.  It rises when an object is made or one of
+ * its workspaces grows and is back where it was once the object is freed; memory from sgx_host_alloc is the
+ * caller's and is not counted.  A test of ownership, not an accounting of the device. */
+size_t sgx_live_bytes(void);
+
 /* Same, all buffers already resident in this GPU's HBM (device pointers): the headline path.
  * packed must be 16-byte aligned and bytes_per_variant a multiple of 64 with
  * bytes_per_variant >= sgx_row_stride(N) = 128*ceil(N/512) (rows that start on 128-byte lines are read

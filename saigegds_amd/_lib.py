@@ -130,6 +130,7 @@ def _abi():
         "sgx_scan_f64": (ci, [vp, vp, sz, vp, vp]),
         "sgx_host_alloc": (vp, [sz]),
         "sgx_host_free": (None, [vp]),
+        "sgx_live_bytes": (sz, None),
         "sgx_burden_2bit": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
         "sgx_geno_stats_2bit": (ci, [vp, sz, i32, sz, ci, vp, vp]),
         "sgx_decode_dbit2": (ci, [vp, sz, i32, sz, vp, i32, vp, sz, ci]),
@@ -242,6 +243,11 @@ def load():
             f.argtypes = argtypes
     _lib = L
     return L
+
+
+def live_bytes() -> int:
+    """Device and pinned bytes the library holds in this process (``sgx_live_bytes``); 0 once every object is closed."""
+    return int(load().sgx_live_bytes())
 
 
 def check(rc: int):

@@ -32,17 +32,11 @@ extern "C" void sgx_block_free(sgx_block *b)
 	if (!b) return;
 	(void)hipSetDevice(b->device);
 	if (b->last_read && b->was_read) (void)hipEventSynchronize(b->last_read);    // scans that read it are done
-	(void)hipFree(b->rows); (void)hipFree(b->idx); (void)hipFree(b->cursor); (void)hipFree(b->lstart); (void)hipFree(b->lcnt);
-	(void)hipFree(b->nzp); (void)hipFree(b->n2p); (void)hipFree(b->n3); (void)hipFree(b->ovf);
-	(void)hipFree(b->nzv); (void)hipFree(b->n2v); (void)hipFree(b->cptr); (void)hipFree(b->cidx); (void)hipFree(b->corient);
-	(void)hipFree(b->info);
-	if (b->h_info) (void)hipHostFree(b->h_info);
-	if (b->ready) (void)hipEventDestroy(b->ready);
-	if (b->last_read) (void)hipEventDestroy(b->last_read);
 	delete b;
 }
 
-// cavg: carrier-list entries per variant on average (resident blocks); lists_only: the scratch of a row-major scan
+// cavg: carrier-list entries per variant on average (resident blocks); lists_only: the scratch of a row-major scan.
+// The caller sizes the block: running out of memory is SGX_ENOMEM.
 static int block_create(int32_t n_samp, size_t max_variants, int device, bool lists_only, size_t cavg, sgx_block **out)
 {
 	*out = nullptr;
@@ -51,38 +45,43 @@ static int block_create(int32_t n_samp, size_t max_variants, int device, bool li
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SGX_ENODEV, "sgx_block_create: no HIP device available");
 	if (device < 0 || device >= ndev) return fail(SGX_EINVAL, "sgx_block_create: device %d out of range", device);
-	sgx_block *b = new sgx_block();
+	std::unique_ptr<sgx_block, void (*)(sgx_block *)> hold(new sgx_block(), sgx_block_free);
+	sgx_block *b = hold.get();
 	b->device = device; b->N = n_samp; b->ntile = 2 * ((n_samp + 511) / 512); b->nr = s3_nranges(b->ntile); b->cap = max_variants;
 	b->lists_only = lists_only;
 	b->bpv = (size_t)b->ntile * 64;
 	b->idx_cap = lists_only ? 0 : block_idx_cap(n_samp, max_variants);    // (the row-major calls gather on the spot: no pool)
 	b->cidx_cap = lists_only ? 0 : block_cidx_cap(n_samp, max_variants, cavg);
 	const size_t nrc = (size_t)b->nr * max_variants;
-	hipError_t e = hipSetDevice(device);
-	if (e == hipSuccess && !lists_only) e = hipMalloc((void **)&b->rows, max_variants * b->bpv);
-	if (e == hipSuccess && !lists_only) e = hipMalloc((void **)&b->idx, b->idx_cap * sizeof(unsigned));
-	if (e == hipSuccess) e = hipMalloc((void **)&b->cursor, (size_t)S3_NSUB * S3_CURSOR_STRIDE * sizeof(unsigned));
-	if (e == hipSuccess) e = hipMemset(b->cursor, 0, (size_t)S3_NSUB * S3_CURSOR_STRIDE * sizeof(unsigned));
-	if (e == hipSuccess && !lists_only) e = hipMalloc((void **)&b->lstart, nrc * sizeof(unsigned));
-	if (e == hipSuccess) e = hipMalloc((void **)&b->lcnt, nrc * sizeof(int));
-	if (e == hipSuccess) e = hipMalloc((void **)&b->n3, max_variants * sizeof(int));
-	if (e == hipSuccess) e = hipMalloc((void **)&b->ovf, max_variants);
-	if (e == hipSuccess) e = hipMalloc((void **)&b->info, 2 * sizeof(int));
-	if (e == hipSuccess) e = hipMemset(b->info, 0, 2 * sizeof(int));
-	if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_info, 2 * sizeof(int), hipHostMallocDefault);
-	if (!lists_only) {
-		if (e == hipSuccess) e = hipMalloc((void **)&b->nzp, nrc * sizeof(int));
-		if (e == hipSuccess) e = hipMalloc((void **)&b->n2p, nrc * sizeof(int));
-		if (e == hipSuccess) e = hipMalloc((void **)&b->nzv, max_variants * sizeof(int));
-		if (e == hipSuccess) e = hipMalloc((void **)&b->n2v, max_variants * sizeof(int));
-		if (e == hipSuccess) e = hipMalloc((void **)&b->cptr, (max_variants + 1) * sizeof(unsigned));
-		if (e == hipSuccess) e = hipMalloc((void **)&b->cidx, std::max<size_t>(b->cidx_cap, 1) * sizeof(unsigned));
-		if (e == hipSuccess) e = hipMalloc((void **)&b->corient, max_variants);
-	}
-	if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ready, hipEventDisableTiming);
-	if (e == hipSuccess) e = hipEventCreateWithFlags(&b->last_read, hipEventDisableTiming);
-	if (e != hipSuccess) { sgx_block_free(b); return fail(e == hipErrorOutOfMemory ? SGX_ENOMEM : SGX_EHIP, "sgx_block_create: %s", hipGetErrorString(e)); }
-	*out = b;
+	auto create = [&]() -> hipError_t {
+		HIPPASS(hipSetDevice(device));
+		HIPPASS(b->cursor.alloc((size_t)S3_NSUB * S3_CURSOR_STRIDE));
+		HIPPASS(hipMemset(b->cursor, 0, (size_t)S3_NSUB * S3_CURSOR_STRIDE * sizeof(unsigned)));
+		HIPPASS(b->lcnt.alloc(nrc));
+		HIPPASS(b->n3.alloc(max_variants));
+		HIPPASS(b->ovf.alloc(max_variants));
+		HIPPASS(b->info.alloc(2));
+		HIPPASS(hipMemset(b->info, 0, 2 * sizeof(int)));
+		HIPPASS(b->h_info.alloc(2));
+		if (!lists_only) {
+			HIPPASS(b->rows.alloc(max_variants * b->bpv));
+			HIPPASS(b->idx.alloc(b->idx_cap));
+			HIPPASS(b->lstart.alloc(nrc));
+			HIPPASS(b->nzp.alloc(nrc));
+			HIPPASS(b->n2p.alloc(nrc));
+			HIPPASS(b->nzv.alloc(max_variants));
+			HIPPASS(b->n2v.alloc(max_variants));
+			HIPPASS(b->cptr.alloc(max_variants + 1));
+			HIPPASS(b->cidx.alloc(std::max<size_t>(b->cidx_cap, 1)));
+			HIPPASS(b->corient.alloc(max_variants));
+		}
+		HIPPASS(b->ready.create(hipEventDisableTiming));
+		HIPPASS(b->last_read.create(hipEventDisableTiming));
+		return hipSuccess;
+	};
+	const hipError_t e = create();
+	if (e != hipSuccess) return fail(mem_code(e), "sgx_block_create: %s", hipGetErrorString(e));
+	*out = hold.release();
 	return SGX_OK;
 }
 

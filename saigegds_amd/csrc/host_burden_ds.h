@@ -9,12 +9,20 @@ struct sgx_dsblock {
 	int device = 0;
 	int N = 0, dtype = 0;
 	size_t cap = 0, M = 0;
-	uint8_t *rows = nullptr;
+	DevBuf<uint8_t> rows;
 	size_t row_bytes = 0;            // of a resident row: N (u8) or 8 N
-	int *d_nv = nullptr; double *d_sum = nullptr; long long *d_trunc = nullptr;   // [cap] ds_stats_kernel
-	uint8_t *tabs = nullptr; size_t tabs_cap = 0;    // sgx_dsblock_burden: groups, entries, weights
+	DevBuf<int> d_nv; DevBuf<double> d_sum; DevBuf<long long> d_trunc;   // [cap] ds_stats_kernel
+	DevBuf<uint8_t> tabs;            // sgx_dsblock_burden: groups, entries, weights
 };
 
+extern "C" void sgx_dsblock_free(sgx_dsblock *b)
+{
+	if (!b) return;
+	(void)hipSetDevice(b->device);
+	delete b;
+}
+
+// The caller sizes the block: a failed allocation is SGX_ENOMEM.
 extern "C" int sgx_dsblock_create(int32_t n_samp, int dtype, size_t max_variants, int device, sgx_dsblock **out)
 {
 	if (!out) return fail(SGX_EINVAL, "sgx_dsblock_create: NULL argument");
@@ -26,32 +34,20 @@ extern "C" int sgx_dsblock_create(int32_t n_samp, int dtype, size_t max_variants
 	if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
 		return fail(SGX_ENODEV, "sgx_dsblock_create: no device %d", device);
 	HIPCHK(hipSetDevice(device));
-	sgx_dsblock *b = new sgx_dsblock();
+	std::unique_ptr<sgx_dsblock, void (*)(sgx_dsblock *)> b(new sgx_dsblock(), sgx_dsblock_free);
 	b->device = device; b->N = n_samp; b->dtype = dtype; b->cap = max_variants;
 	b->row_bytes = (size_t)n_samp * (dtype == SGX_DS_U8 ? 1 : sizeof(double));
-	hipError_t e = hipMalloc((void **)&b->rows, b->cap * b->row_bytes + 16);
-	if (e == hipSuccess) e = hipMalloc((void **)&b->d_nv, b->cap * sizeof(int));
-	if (e == hipSuccess) e = hipMalloc((void **)&b->d_sum, b->cap * sizeof(double));
-	if (e == hipSuccess) e = hipMalloc((void **)&b->d_trunc, b->cap * sizeof(long long));
-	if (e != hipSuccess) {
-		const size_t rb = b->row_bytes;
-		sgx_dsblock_free(b);
-		return fail(SGX_ENOMEM, "sgx_dsblock_create: %zu rows of %zu bytes: %s", max_variants, rb, hipGetErrorString(e));
-	}
-	*out = b;
+	const hipError_t e = [&]() -> hipError_t {
+		HIPPASS(b->rows.alloc(b->cap * b->row_bytes + 16));
+		HIPPASS(b->d_nv.alloc(b->cap));
+		HIPPASS(b->d_sum.alloc(b->cap));
+		HIPPASS(b->d_trunc.alloc(b->cap));
+		return hipSuccess;
+	}();
+	if (e != hipSuccess)
+		return fail(SGX_ENOMEM, "sgx_dsblock_create: %zu rows of %zu bytes: %s", max_variants, b->row_bytes, hipGetErrorString(e));
+	*out = b.release();
 	return SGX_OK;
-}
-
-extern "C" void sgx_dsblock_free(sgx_dsblock *b)
-{
-	if (!b) return;
-	(void)hipSetDevice(b->device);
-	if (b->rows) (void)hipFree(b->rows);
-	if (b->d_nv) (void)hipFree(b->d_nv);
-	if (b->d_sum) (void)hipFree(b->d_sum);
-	if (b->d_trunc) (void)hipFree(b->d_trunc);
-	if (b->tabs) (void)hipFree(b->tabs);
-	delete b;
 }
 
 static int dsblock_check(sgx_handle *h, const sgx_dsblock *b, const char *who)
@@ -70,7 +66,7 @@ static int dsblock_counts(sgx_handle *h, sgx_dsblock *b, size_t M, int32_t *n_va
 			(const uint8_t *)b->rows, b->N, b->d_nv, b->d_sum, b->d_trunc);
 	else
 		hipLaunchKernelGGL((ds_stats_kernel<double>), dim3((unsigned)M), dim3(256), 0, h->stream,
-			(const double *)b->rows, b->N, b->d_nv, b->d_sum, b->d_trunc);
+			(const double *)b->rows.p, b->N, b->d_nv, b->d_sum, b->d_trunc);
 	HIPCHK(hipGetLastError());
 	static_assert(sizeof(long long) == sizeof(int64_t), "sum_trunc");
 	HIPCHK(hipMemcpyAsync(n_valid, b->d_nv, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -108,7 +104,7 @@ extern "C" int sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosag
 			[&](int k, size_t off, size_t m) -> int { return src_upload(h, src, k, off, m, src.row_bytes); },
 			[&](int k, size_t off, size_t m) -> int {
 				hipLaunchKernelGGL(i32_rows_to_f64, dim3(1024), dim3(256), 0, h->stream,
-					(const int *)h->pipe_in[k], m * (size_t)N, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
+					(const int *)h->pipe_in[k].p, m * (size_t)N, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
 				HIPCHK(hipGetLastError());
 				return SGX_OK;
 			});
@@ -230,7 +226,7 @@ extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_
 	const size_t o_w = (o_idx + ne * sizeof(int) + 15) & ~(size_t)15;
 	const size_t o_mw = o_w + ne * (size_t)n_cols * sizeof(double);
 	const size_t o_flip = o_mw + ne * (size_t)n_cols * sizeof(double);
-	rc = grow(bm->tabs, bm->tabs_cap, o_flip + ne);
+	rc = grow(bm->tabs, o_flip + ne);
 	if (rc) return rc;
 	std::vector<long long> gp(grp_ptr, grp_ptr + n_groups + 1);
 	HIPCHK(hipMemcpyAsync(b->tabs, gp.data(), gp.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
@@ -250,7 +246,7 @@ extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_
 	rc = ensure_recs(h, gchunk * n_cols);
 	if (rc) return rc;
 	sgx_stats total{};
-	const long long *d_gp = reinterpret_cast<const long long *>(b->tabs);
+	const long long *d_gp = reinterpret_cast<const long long *>(b->tabs.p);
 	const int *d_idx = reinterpret_cast<const int *>(b->tabs + o_idx);
 	const double *d_w = reinterpret_cast<const double *>(b->tabs + o_w), *d_mw = reinterpret_cast<const double *>(b->tabs + o_mw);
 	const uint8_t *d_flip = b->tabs + o_flip;
@@ -260,10 +256,10 @@ extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_
 			const int nc = std::min(SGX_DS_COLS_PER_PASS, n_cols - c0);
 			if (b->dtype == SGX_DS_U8)
 				launch_collapse_ds<uint8_t>(h->stream, (const uint8_t *)b->rows, N, ng, d_gp + off, d_idx, d_flip, n_cols, c0, nc,
-					d_w, d_mw, reinterpret_cast<double *>(h->stage_in));
+					d_w, d_mw, reinterpret_cast<double *>(h->stage_in.p));
 			else
-				launch_collapse_ds<double>(h->stream, (const double *)b->rows, N, ng, d_gp + off, d_idx, d_flip, n_cols, c0, nc,
-					d_w, d_mw, reinterpret_cast<double *>(h->stage_in));
+				launch_collapse_ds<double>(h->stream, (const double *)b->rows.p, N, ng, d_gp + off, d_idx, d_flip, n_cols, c0, nc,
+					d_w, d_mw, reinterpret_cast<double *>(h->stage_in.p));
 			HIPCHK(hipGetLastError());
 		}
 		rc = scan_staged<IN_F64>(h, h->stage_in, row_bytes, m, out8 + off * n_cols * 8, valid + off * n_cols, total);

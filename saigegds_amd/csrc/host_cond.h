@@ -37,12 +37,12 @@ extern "C" int sgx_cond_set(sgx_handle *h, const uint8_t *packed_c, size_t bpv, 
 	std::vector<double> ce((size_t)C * 2 * K);
 	for (int c = 0; c < C; c++)
 		for (int a = 0; a < 2 * K; a++) ce[(size_t)c * 2 * K + a] = dense[(size_t)c * (2 * K + 1) + a];
-	rc = grow(h->cond_ce, h->cond_ce_cap, (size_t)SGX_COND_MAX * 2 * KMAX);
+	rc = grow(h->cond_ce, (size_t)SGX_COND_MAX * 2 * KMAX);
 	if (rc) return rc;
-	rc = grow(h->cond_B, h->cond_B_cap, (size_t)N * PB);
+	rc = grow(h->cond_B, (size_t)N * PB);
 	if (rc) return rc;
 	const size_t dbpv = (size_t)((N + 15) >> 4) * 4, o_lut = ((size_t)C * dbpv + 15) & ~(size_t)15;
-	rc = grow(h->stage_pk, h->stage_pk_cap, o_lut + (size_t)C * 4 * sizeof(double));
+	rc = grow(h->stage_pk, o_lut + (size_t)C * 4 * sizeof(double));
 	if (rc) return rc;
 	rc = copy_rows_h2d(h->stage_pk, dbpv, packed_c, bpv, (size_t)C, h->stream);
 	if (rc) return rc;
@@ -50,7 +50,7 @@ extern "C" int sgx_cond_set(sgx_handle *h, const uint8_t *packed_c, size_t bpv, 
 	HIPCHK(hipMemcpyAsync(h->cond_ce, ce.data(), ce.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
 	const size_t nel = (size_t)N * PB;
 	hipLaunchKernelGGL(cond_build_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, h->stream,
-		h->stage_pk, dbpv, reinterpret_cast<const double *>(h->stage_pk + o_lut), C, h->dF, P, N, PB, h->cond_B);
+		h->stage_pk, dbpv, reinterpret_cast<const double *>(h->stage_pk + o_lut), C, h->md.F, P, N, PB, h->cond_B);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(h->stream));
 	h->n_cond = C;
@@ -69,9 +69,9 @@ static int cond_run(sgx_handle *p, sgx_handle *lane, size_t M, int slab_ch, Rect
 	const int nslab = ((N + 255) / 256 + slab_ch - 1) / slab_ch;
 	size_t mchunk = COND_PART_BYTES / ((size_t)nslab * WD * sizeof(double));
 	mchunk = std::min(M, std::max<size_t>(COND_WG_ROWS, mchunk / COND_WG_ROWS * COND_WG_ROWS));
-	int rc = ensure_buf(lane, &lane->cond_part, &lane->cond_part_cap, mchunk * nslab * WD);
+	int rc = ensure_buf(lane, lane->cond_part, mchunk * nslab * WD);
 	if (rc) return rc;
-	rc = ensure_buf(lane, &lane->cond_fin, &lane->cond_fin_cap, mchunk * WD);
+	rc = ensure_buf(lane, lane->cond_fin, mchunk * WD);
 	if (rc) return rc;
 	hipStream_t st = lane->stream;
 	using std::integral_constant;
@@ -102,7 +102,7 @@ static int cond_rows_dev(sgx_handle *p, sgx_handle *lane, const uint8_t *rows, s
 {
 	return cond_run(p, lane, M, COND_SLAB_CH, [&](auto nct, dim3 grid, size_t off, size_t m) {
 		hipLaunchKernelGGL(cond_rect_kernel<decltype(nct)::value>, grid, dim3(256), 0, lane->stream, rows + off * bpv, bpv,
-			p->md.N, m, lut + 4 * off, p->dF, p->md.P, p->cond_B, COND_SLAB_CH, lane->cond_part);
+			p->md.N, m, lut + 4 * off, p->md.F, p->md.P, p->cond_B, COND_SLAB_CH, lane->cond_part);
 	}, score, var, cov);
 }
 
@@ -148,7 +148,7 @@ extern "C" int sgx_cond_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 	const size_t rchunk = scan_chunk(h, dbpv, M);
 	const size_t o_lut = rchunk * dbpv, o_s = o_lut + rchunk * 4 * sizeof(double), o_v = o_s + rchunk * sizeof(double),
 		o_c = o_v + rchunk * sizeof(double);
-	rc = grow(h->stage_pk, h->stage_pk_cap, o_c + rchunk * (size_t)C * sizeof(double));
+	rc = grow(h->stage_pk, o_c + rchunk * (size_t)C * sizeof(double));
 	if (rc) return rc;
 	double *d_lut = reinterpret_cast<double *>(h->stage_pk + o_lut), *d_s = reinterpret_cast<double *>(h->stage_pk + o_s),
 		*d_v = reinterpret_cast<double *>(h->stage_pk + o_v), *d_c = reinterpret_cast<double *>(h->stage_pk + o_c);

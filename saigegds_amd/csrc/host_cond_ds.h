@@ -36,28 +36,28 @@ extern "C" int sgx_ds_block_cond_set(sgx_handle *h, const sgx_dsblock *b, size_t
 	std::vector<double> ce((size_t)C * 2 * K);
 	for (int c = 0; c < C; c++)
 		for (int a = 0; a < 2 * K; a++) ce[(size_t)c * 2 * K + a] = dense[(size_t)c * (2 * K + 1) + a];
-	rc = grow(h->cond_ce, h->cond_ce_cap, (size_t)SGX_COND_MAX * 2 * KMAX);
+	rc = grow(h->cond_ce, (size_t)SGX_COND_MAX * 2 * KMAX);
 	if (rc) return rc;
-	rc = grow(h->cond_B, h->cond_B_cap, (size_t)N * PB);
+	rc = grow(h->cond_B, (size_t)N * PB);
 	if (rc) return rc;
 	const size_t o_idx = (size_t)C * sizeof(double), o_flip = o_idx + (size_t)C * sizeof(int);      // means first
-	rc = grow(h->stage_pk, h->stage_pk_cap, o_flip + (size_t)C);
+	rc = grow(h->stage_pk, o_flip + (size_t)C);
 	if (rc) return rc;
 	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
 	HIPCHK(hipMemcpyAsync(h->stage_pk, mean, (size_t)C * sizeof(double), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)C * sizeof(int), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipMemcpyAsync(h->stage_pk + o_flip, flip, (size_t)C, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipMemcpyAsync(h->cond_ce, ce.data(), ce.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	const double *d_mean = reinterpret_cast<const double *>(h->stage_pk);
+	const double *d_mean = reinterpret_cast<const double *>(h->stage_pk.p);
 	const int *d_idx = reinterpret_cast<const int *>(h->stage_pk + o_idx);
 	const size_t nel = (size_t)N * PB;
 	const dim3 grid((unsigned)((nel + 255) / 256));
 	if (b->dtype == SGX_DS_U8)
 		hipLaunchKernelGGL((cond_build_ds_kernel<uint8_t>), grid, dim3(256), 0, h->stream,
-			(const uint8_t *)b->rows, d_idx, h->stage_pk + o_flip, d_mean, C, h->dF, P, N, PB, h->cond_B);
+			(const uint8_t *)b->rows, d_idx, h->stage_pk + o_flip, d_mean, C, h->md.F, P, N, PB, h->cond_B);
 	else
 		hipLaunchKernelGGL((cond_build_ds_kernel<double>), grid, dim3(256), 0, h->stream,
-			(const double *)b->rows, d_idx, h->stage_pk + o_flip, d_mean, C, h->dF, P, N, PB, h->cond_B);
+			(const double *)b->rows.p, d_idx, h->stage_pk + o_flip, d_mean, C, h->md.F, P, N, PB, h->cond_B);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(h->stream));
 	h->n_cond = C;
@@ -81,9 +81,9 @@ extern "C" int sgx_ds_block_cond(sgx_handle *h, const sgx_dsblock *b, const uint
 	const size_t M = b->M, C = (size_t)h->n_cond;
 	const int N = b->N, P = h->md.P;
 	const size_t o_flip = M * (3 + C) * sizeof(double);
-	rc = grow(h->stage_pk, h->stage_pk_cap, o_flip + M);
+	rc = grow(h->stage_pk, o_flip + M);
 	if (rc) return rc;
-	double *d_mean = reinterpret_cast<double *>(h->stage_pk), *d_s = d_mean + M, *d_v = d_s + M, *d_c = d_v + M;
+	double *d_mean = reinterpret_cast<double *>(h->stage_pk.p), *d_s = d_mean + M, *d_v = d_s + M, *d_c = d_v + M;
 	const uint8_t *d_flip = h->stage_pk + o_flip;
 	HIPCHK(hipMemcpyAsync(d_mean, mean, M * sizeof(double), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipMemcpyAsync(h->stage_pk + o_flip, flip, M, hipMemcpyHostToDevice, h->stream));
@@ -91,11 +91,11 @@ extern "C" int sgx_ds_block_cond(sgx_handle *h, const sgx_dsblock *b, const uint
 		constexpr int NCT = decltype(nct)::value;
 		if (b->dtype == SGX_DS_U8)
 			hipLaunchKernelGGL((cond_rect_ds_kernel<uint8_t, NCT>), grid, dim3(256), 0, h->stream,
-				(const uint8_t *)b->rows + off * (size_t)N, N, m, d_flip + off, d_mean + off, h->dF, P, h->cond_B, COND_DS_SLAB_CH,
+				(const uint8_t *)b->rows + off * (size_t)N, N, m, d_flip + off, d_mean + off, h->md.F, P, h->cond_B, COND_DS_SLAB_CH,
 				h->cond_part);
 		else
 			hipLaunchKernelGGL((cond_rect_ds_kernel<double, NCT>), grid, dim3(256), 0, h->stream,
-				(const double *)b->rows + off * (size_t)N, N, m, d_flip + off, d_mean + off, h->dF, P, h->cond_B, COND_DS_SLAB_CH,
+				(const double *)b->rows.p + off * (size_t)N, N, m, d_flip + off, d_mean + off, h->md.F, P, h->cond_B, COND_DS_SLAB_CH,
 				h->cond_part);
 	}, d_s, d_v, d_c);
 	if (rc) return rc;

@@ -1,4 +1,4 @@
-// host_grm.h -- implicit-GRM operator of the null-model fit (kern_grm.h).
+// host_grm.h -- implicit-GRM operator of the null-model fit (kern_grm.h): sgx_grm on the owners of host_mem.h.
 // Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
 
 // ===========================================================================
@@ -12,35 +12,35 @@
 
 struct sgx_grm {
 	int device = 0;
-	hipStream_t stream = nullptr;
+	// (released in reverse order: buffers, events, the stream -- sgx_grm_free waits for the stream first)
+	DevStream stream;
+	DevEvent gd_ev0, gd_ev1;               // host_grm_dense.h: around the kernels of a piece of sgx_grm_dense
 	int N = 0; size_t M = 0;
 	size_t bpvN = 0, bpvM = 0;             // row strides of G (marker-major) and Gt (sample-major)
-	uint8_t *G = nullptr, *Gt = nullptr;
-	double *af = nullptr, *inv = nullptr, *l0 = nullptr, *diag = nullptr;
+	DevBuf<uint8_t> G, Gt;
+	DevBuf<double> af, inv, l0, diag;
 	int ntileN = 0, ntileM = 0;            // 256-entry limb tiles over samples / over markers
-	uint8_t *FlN = nullptr, *FlM = nullptr;          // limb tile images, 16 GRM_MAXF columns wide
-	int *accV = nullptr, *accS = nullptr;            // [M][32 GRM_MAXF], [N][32 GRM_MAXF]
-	double *xv = nullptr, *gv = nullptr;             // [GRM_GROUP][M]
-	unsigned long long *maxb = nullptr;              // [GRM_MAX_RHS][3]: b, x, gam
+	DevBuf<uint8_t> FlN, FlM;              // limb tile images, 16 GRM_MAXF columns wide
+	DevBuf<int> accV, accS;                // [M][32 GRM_MAXF], [N][32 GRM_MAXF]
+	DevBuf<double> xv, gv;                 // [GRM_GROUP][M]
+	DevBuf<unsigned long long> maxb;       // [GRM_MAX_RHS][3]: b, x, gam
 	PcgWork pw;                            // block partials, staging and solver vectors (host_pcg.h)
 	int n_cu = 256;
 	// marker groups (sgx_grm_set_groups): a column of a *_loco call leaves one group out
 	int n_groups = 0;
-	int *grp = nullptr;                    // [M] group id per marker
+	DevBuf<int> grp;                       // [M] group id per marker
 	size_t gsize[GRM_MAX_GROUPS] = {};     // markers per group
-	double *diagx = nullptr;               // [1 + n_groups][N]: row 0 = diag, row 1 + c = diag(GRM without group c)
+	DevBuf<double> diagx;                  // [1 + n_groups][N]: row 0 = diag, row 1 + c = diag(GRM without group c)
 	// explicit GRM (host_grm_dense.h): scratch of sgx_grm_dense / sgx_grm_sparse, allocated on first use
-	double *gd_part = nullptr, *gd_out = nullptr;    // slab tiles [nslab][tiles][256]; a rectangle of K
-	size_t gd_part_cap = 0, gd_out_cap = 0;          // (doubles)
-	bool gd_ready = false;                           // the screen's tables below are built
-	int gd_s = 0;                                    // Q = round(g 2^s)
-	uint2 *gd_lut = nullptr;                         // [markers padded to 512] limb bytes per code
-	double *gd_A = nullptr, *gd_R = nullptr;         // [N] bound terms per sample
-	unsigned long long *gd_cnt = nullptr;            // [2]: flagged sub-tiles, entries (also the table maximum)
-	GdTile *gd_list = nullptr; size_t gd_list_cap = 0;
-	int *gd_i = nullptr, *gd_j = nullptr; double *gd_v = nullptr; size_t gd_ent_cap = 0;
-	hipEvent_t gd_ev0 = nullptr, gd_ev1 = nullptr;   // around the kernels of a piece of sgx_grm_dense
-	double gd_ms_kernel = 0;                         // their time over the last sgx_grm_dense call
+	DevBuf<double> gd_part, gd_out;        // slab tiles [nslab][tiles][256]; a rectangle of K
+	bool gd_ready = false;                 // the screen's tables below are built
+	int gd_s = 0;                          // Q = round(g 2^s)
+	DevBuf<uint2> gd_lut;                  // [markers padded to 512] limb bytes per code
+	DevBuf<double> gd_A, gd_R;             // [N] bound terms per sample
+	DevBuf<unsigned long long> gd_cnt;     // [2]: flagged sub-tiles, entries (also the table maximum)
+	DevBuf<GdTile> gd_list;
+	DevBuf<int> gd_i, gd_j; DevBuf<double> gd_v;
+	double gd_ms_kernel = 0;               // the kernels' time over the last sgx_grm_dense call
 };
 static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
 static_assert(GRM_MAX_GROUPS == SGX_GRM_MAX_GROUPS, "kern_grm.h and saigehip.h disagree on the group limit");
@@ -50,14 +50,6 @@ extern "C" void sgx_grm_free(sgx_grm *g)
 	if (!g) return;
 	(void)hipSetDevice(g->device);
 	if (g->stream) (void)hipStreamSynchronize(g->stream);
-	void *ptrs[] = {g->G, g->Gt, g->af, g->inv, g->l0, g->diag, g->FlN, g->FlM, g->accV, g->accS, g->xv, g->gv,
-		g->maxb, g->grp, g->diagx,
-		g->gd_part, g->gd_out, g->gd_lut, g->gd_A, g->gd_R, g->gd_cnt, g->gd_list, g->gd_i, g->gd_j, g->gd_v};
-	for (void *p : ptrs) (void)hipFree(p);
-	pcg_work_free(&g->pw);
-	if (g->gd_ev0) (void)hipEventDestroy(g->gd_ev0);
-	if (g->gd_ev1) (void)hipEventDestroy(g->gd_ev1);
-	if (g->stream) (void)hipStreamDestroy(g->stream);
 	delete g;
 }
 
@@ -92,13 +84,12 @@ static int grm_init_impl(const uint8_t *packed, size_t bytes_per_marker, int32_t
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SGX_ENODEV, "sgx_grm_init: no HIP device available");
 	if (device < 0 || device >= ndev) return fail(SGX_EINVAL, "sgx_grm_init: device %d out of range", device);
-	sgx_grm *g = new sgx_grm();
+	std::unique_ptr<sgx_grm, void (*)(sgx_grm *)> hold(new sgx_grm(), sgx_grm_free);   // released on every early return
+	sgx_grm *g = hold.get();
 	g->device = device;
-	hipError_t e;
-#define GTRY(x) do { e = (x); if (e != hipSuccess) { sgx_grm_free(g); return fail(SGX_EHIP, "%s: %s", #x, hipGetErrorString(e)); } } while (0)
-	GTRY(hipSetDevice(device));
+	HIPCHK(hipSetDevice(device));
 	hipDeviceProp_t prop;
-	GTRY(hipGetDeviceProperties(&prop, device));
+	HIPCHK(hipGetDeviceProperties(&prop, device));
 	g->n_cu = prop.multiProcessorCount;
 	const size_t N = (size_t)n_samp, M = n_markers;
 	g->N = n_samp; g->M = M;
@@ -106,34 +97,33 @@ static int grm_init_impl(const uint8_t *packed, size_t bytes_per_marker, int32_t
 	g->bpvM = (size_t)((M + 511) / 512) * 128;
 	g->ntileN = 2 * (int)((N + 511) / 512);
 	g->ntileM = 2 * (int)((M + 511) / 512);
-	GTRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-	GTRY(hipMalloc((void **)&g->G, M * g->bpvN));
-	GTRY(hipMalloc((void **)&g->Gt, N * g->bpvM));
-	GTRY(hipMemsetAsync(g->G, 0, M * g->bpvN, g->stream));
-	GTRY(hipMemsetAsync(g->Gt, 0, N * g->bpvM, g->stream));
-	GTRY(hipMemcpy2DAsync(g->G, g->bpvN, packed, bytes_per_marker, std::min(bytes_per_marker, g->bpvN), M,
+	HIPCHK(g->stream.create(hipStreamNonBlocking));
+	HIPCHK(g->G.alloc(M * g->bpvN));
+	HIPCHK(g->Gt.alloc(N * g->bpvM));
+	HIPCHK(hipMemsetAsync(g->G, 0, M * g->bpvN, g->stream));
+	HIPCHK(hipMemsetAsync(g->Gt, 0, N * g->bpvM, g->stream));
+	HIPCHK(hipMemcpy2DAsync(g->G, g->bpvN, packed, bytes_per_marker, std::min(bytes_per_marker, g->bpvN), M,
 		kind, g->stream));
-	for (double **p : {&g->af, &g->inv, &g->l0}) GTRY(hipMalloc((void **)p, M * sizeof(double)));
-	GTRY(hipMalloc((void **)&g->diag, N * sizeof(double)));
+	for (DevBuf<double> *p : {&g->af, &g->inv, &g->l0}) HIPCHK(p->alloc(M));
+	HIPCHK(g->diag.alloc(N));
 	// scratch of a product: every launch zeroes what it reads of it
-	GTRY(hipMalloc((void **)&g->FlN, (size_t)g->ntileN * 16 * (16 * GRM_MAXF) * 16));
-	GTRY(hipMalloc((void **)&g->FlM, (size_t)g->ntileM * 16 * (16 * GRM_MAXF) * 16));
-	GTRY(hipMalloc((void **)&g->accV, M * 32 * GRM_MAXF * sizeof(int)));
-	GTRY(hipMalloc((void **)&g->accS, N * 32 * GRM_MAXF * sizeof(int)));
-	GTRY(hipMalloc((void **)&g->xv, GRM_GROUP * M * sizeof(double)));
-	GTRY(hipMalloc((void **)&g->gv, GRM_GROUP * M * sizeof(double)));
-	GTRY(hipMalloc((void **)&g->maxb, GRM_MAX_RHS * 3 * sizeof(unsigned long long)));
-	GTRY(pcg_work_init(&g->pw, device, g->stream, n_samp));
+	HIPCHK(g->FlN.alloc((size_t)g->ntileN * 16 * (16 * GRM_MAXF) * 16));
+	HIPCHK(g->FlM.alloc((size_t)g->ntileM * 16 * (16 * GRM_MAXF) * 16));
+	HIPCHK(g->accV.alloc(M * 32 * GRM_MAXF));
+	HIPCHK(g->accS.alloc(N * 32 * GRM_MAXF));
+	HIPCHK(g->xv.alloc(GRM_GROUP * M));
+	HIPCHK(g->gv.alloc(GRM_GROUP * M));
+	HIPCHK(g->maxb.alloc(GRM_MAX_RHS * 3));
+	HIPCHK(pcg_work_init(&g->pw, device, g->stream, n_samp));
 	// marker statistics, transpose, diag(GRM)
 	hipLaunchKernelGGL(grm_marker_stats, dim3((unsigned)M), dim3(256), 0, g->stream, g->G, g->bpvN, g->N, M, g->af, g->inv, g->l0);
 	hipLaunchKernelGGL(transpose_2bit, dim3((unsigned)((N + 255) / 256), (unsigned)((M + 63) / 64)), dim3(256), 0, g->stream,
 		g->G, g->bpvN, M, g->N, g->Gt, g->bpvM);
 	hipLaunchKernelGGL(grm_diag_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, g->stream, g->Gt, g->bpvM, g->N, M,
 		g->inv, g->l0, g->diag);
-	GTRY(hipGetLastError());
-	GTRY(hipStreamSynchronize(g->stream));
-#undef GTRY
-	*out = g;
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(g->stream));
+	*out = hold.release();
 	return SGX_OK;
 }
 
@@ -352,27 +342,21 @@ extern "C" int sgx_grm_set_groups(sgx_grm *g, const int32_t *group, int n_groups
 	hipStream_t st = g->stream;
 	HIPCHK(hipStreamSynchronize(st));
 	g->n_groups = 0;                       // (no groups until the new tables are complete)
-	if (!g->grp) HIPCHK(hipMalloc((void **)&g->grp, M * sizeof(int)));
-	if (g->diagx) { HIPCHK(hipFree(g->diagx)); g->diagx = nullptr; }
-	HIPCHK(hipMalloc((void **)&g->diagx, (size_t)(1 + n_groups) * N * sizeof(double)));
-	double *S = nullptr, *msub = nullptr;
+	HIPCHK(g->grp.reserve(M));
+	HIPCHK(g->diagx.alloc((size_t)(1 + n_groups) * N));
+	DevBuf<double> S, msub;                // the call's scratch: the synchronisation below comes before their release
 	double h_msub[GRM_MAX_GROUPS];
 	for (int c = 0; c < n_groups; c++) h_msub[c] = (double)(M - sizes[c]);
-	hipError_t e = hipMalloc((void **)&S, (size_t)n_groups * N * sizeof(double));
-	if (e == hipSuccess) e = hipMalloc((void **)&msub, GRM_MAX_GROUPS * sizeof(double));
-	if (e == hipSuccess) e = hipMemcpyAsync(g->grp, group, M * sizeof(int), hipMemcpyHostToDevice, st);
-	if (e == hipSuccess) e = hipMemcpyAsync(msub, h_msub, (size_t)n_groups * sizeof(double), hipMemcpyHostToDevice, st);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(grm_diag_groups_kernel, dim3((unsigned)N), dim3(WAVE), (size_t)n_groups * WAVE * sizeof(double), st,
-			g->Gt, g->bpvM, g->N, M, g->inv, g->l0, g->grp, n_groups, S);
-		hipLaunchKernelGGL(grm_diag_excl_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g->N, n_groups, S, msub,
-			g->diag, g->diagx);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	(void)hipFree(S);
-	(void)hipFree(msub);
-	HIPCHK(e);
+	HIPCHK(S.alloc((size_t)n_groups * N));
+	HIPCHK(msub.alloc(GRM_MAX_GROUPS));
+	HIPCHK(hipMemcpyAsync(g->grp, group, M * sizeof(int), hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(msub, h_msub, (size_t)n_groups * sizeof(double), hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(grm_diag_groups_kernel, dim3((unsigned)N), dim3(WAVE), (size_t)n_groups * WAVE * sizeof(double), st,
+		g->Gt, g->bpvM, g->N, M, g->inv, g->l0, g->grp, n_groups, S);
+	hipLaunchKernelGGL(grm_diag_excl_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g->N, n_groups, S, msub,
+		g->diag, g->diagx);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(st));
 	for (int c = 0; c < GRM_MAX_GROUPS; c++) g->gsize[c] = sizes[c];
 	g->n_groups = n_groups;
 	return SGX_OK;

@@ -12,17 +12,6 @@ static double gd_ms_since(std::chrono::steady_clock::time_point t0)
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-template <typename T>
-static hipError_t gd_reserve(T **p, size_t *cap, size_t want)
-{
-	if (want <= *cap) return hipSuccess;
-	hipError_t e = *p ? hipFree(*p) : hipSuccess;
-	*p = nullptr; *cap = 0;
-	if (e == hipSuccess) e = hipMalloc((void **)p, want * sizeof(T));
-	if (e == hipSuccess) *cap = want;
-	return e;
-}
-
 static int gd_nslab(const sgx_grm *g)
 {
 	const size_t ndw = (g->M + 15) >> 4;
@@ -37,9 +26,9 @@ static int gd_rect(sgx_grm *g, int i0, int ni, int j0, int nj, double *out, size
 	const int tj0 = j0 / 16, ntj = (j0 + nj - 1) / 16 - tj0 + 1;
 	const size_t n_tiles = (size_t)nti * ntj;
 	const int nslab = gd_nslab(g);
-	HIPCHK(gd_reserve(&g->gd_part, &g->gd_part_cap, (size_t)nslab * n_tiles * 256));
-	HIPCHK(gd_reserve(&g->gd_out, &g->gd_out_cap, (size_t)ni * nj));
-	if (!g->gd_ev0) { HIPCHK(hipEventCreate(&g->gd_ev0)); HIPCHK(hipEventCreate(&g->gd_ev1)); }
+	HIPCHK(g->gd_part.reserve((size_t)nslab * n_tiles * 256));
+	HIPCHK(g->gd_out.reserve((size_t)ni * nj));
+	if (!g->gd_ev1) { if (!g->gd_ev0) HIPCHK(g->gd_ev0.create()); HIPCHK(g->gd_ev1.create()); }
 	HIPCHK(hipEventRecord(g->gd_ev0, st));
 	hipLaunchKernelGGL(grm_dense_tile_kernel, dim3((unsigned)n_tiles, (unsigned)nslab), dim3(WAVE), 0, st, g->Gt, g->bpvM,
 		g->N, g->M, g->inv, g->l0, (const GdTile *)nullptr, ti0, nti, tj0, ntj, n_tiles, g->gd_part);
@@ -87,10 +76,10 @@ static int gd_prepare(sgx_grm *g)
 	if (g->gd_ready) return SGX_OK;
 	hipStream_t st = g->stream;
 	const size_t M = g->M, Mpad = g->bpvM * 4, N = (size_t)g->N;
-	if (!g->gd_cnt) HIPCHK(hipMalloc((void **)&g->gd_cnt, 2 * sizeof(unsigned long long)));
-	if (!g->gd_lut) HIPCHK(hipMalloc((void **)&g->gd_lut, Mpad * sizeof(uint2)));
-	if (!g->gd_A) HIPCHK(hipMalloc((void **)&g->gd_A, N * sizeof(double)));
-	if (!g->gd_R) HIPCHK(hipMalloc((void **)&g->gd_R, N * sizeof(double)));
+	HIPCHK(g->gd_cnt.reserve(2));
+	HIPCHK(g->gd_lut.reserve(Mpad));
+	HIPCHK(g->gd_A.reserve(N));
+	HIPCHK(g->gd_R.reserve(N));
 	HIPCHK(hipMemsetAsync(g->gd_cnt, 0, 2 * sizeof(unsigned long long), st));
 	hipLaunchKernelGGL(gd_lutmax_kernel, dim3(GRM_RED_BLOCKS), dim3(256), 0, st, g->inv, g->l0, M, g->gd_cnt);
 	unsigned long long bits = 0;
@@ -146,14 +135,14 @@ extern "C" int sgx_grm_sparse(sgx_grm *g, double cutoff, size_t cap, int32_t *i_
 	bd.cutoff = cutoff;
 	unsigned long long n_flag = 0;
 	for (size_t want = std::min(st_total, std::max<size_t>(4 * nst + 4096, st_total / 64));;) {
-		HIPCHK(gd_reserve(&g->gd_list, &g->gd_list_cap, want));
+		HIPCHK(g->gd_list.reserve(want));
 		HIPCHK(hipMemsetAsync(g->gd_cnt, 0, 2 * sizeof(unsigned long long), st));
 		hipLaunchKernelGGL(grm_screen_kernel, dim3((unsigned)nb, (unsigned)nb), dim3(256), 0, st, g->Gt, g->bpvM, g->N,
-			(int)(g->bpvM * 4 / GD_KB), g->gd_lut, g->gd_A, g->gd_R, bd, g->gd_list, g->gd_cnt, g->gd_list_cap);
+			(int)(g->bpvM * 4 / GD_KB), g->gd_lut, g->gd_A, g->gd_R, bd, g->gd_list, g->gd_cnt, g->gd_list.cap);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipMemcpyAsync(&n_flag, g->gd_cnt, sizeof n_flag, hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
-		if (n_flag <= g->gd_list_cap) break;
+		if (n_flag <= g->gd_list.cap) break;
 		want = (size_t)n_flag;                         // (the list was too short: once more with room for all)
 	}
 	sx.subtiles_flagged = (int64_t)n_flag;
@@ -163,21 +152,13 @@ extern "C" int sgx_grm_sparse(sgx_grm *g, double cutoff, size_t cap, int32_t *i_
 	t0 = std::chrono::steady_clock::now();
 	// (room for what the flagged sub-tiles can hold at most, not for whatever the caller's cap allows)
 	const size_t ent_cap = std::max<size_t>(1, std::min(cap, (size_t)n_flag * 256));
-	if (ent_cap > g->gd_ent_cap) {
-		for (void **p : {(void **)&g->gd_i, (void **)&g->gd_j, (void **)&g->gd_v}) {
-			if (*p) HIPCHK(hipFree(*p));
-			*p = nullptr;
-		}
-		g->gd_ent_cap = 0;
-		HIPCHK(hipMalloc((void **)&g->gd_i, ent_cap * sizeof(int)));
-		HIPCHK(hipMalloc((void **)&g->gd_j, ent_cap * sizeof(int)));
-		HIPCHK(hipMalloc((void **)&g->gd_v, ent_cap * sizeof(double)));
-		g->gd_ent_cap = ent_cap;
-	}
+	HIPCHK(g->gd_i.reserve(ent_cap));
+	HIPCHK(g->gd_j.reserve(ent_cap));
+	HIPCHK(g->gd_v.reserve(ent_cap));
 	const int nslab = gd_nslab(g);
 	for (size_t f0 = 0; f0 < (size_t)n_flag; f0 += GD_BATCH) {
 		const size_t nt = std::min<size_t>(GD_BATCH, (size_t)n_flag - f0);
-		HIPCHK(gd_reserve(&g->gd_part, &g->gd_part_cap, (size_t)nslab * nt * 256));
+		HIPCHK(g->gd_part.reserve((size_t)nslab * nt * 256));
 		hipLaunchKernelGGL(grm_dense_tile_kernel, dim3((unsigned)nt, (unsigned)nslab), dim3(WAVE), 0, st, g->Gt, g->bpvM,
 			g->N, M, g->inv, g->l0, g->gd_list + f0, 0, 0, 0, 1, nt, g->gd_part);
 		hipLaunchKernelGGL(grm_sparse_compact_kernel, dim3((unsigned)nt), dim3(256), 0, st, g->gd_part, nt, nslab,

@@ -1,4 +1,4 @@
-// host_init.h -- library / model lifetime: sgx_init (the fixed-point limb tiles), thresholds, layout, sgx_free, per-call workspace.
+// host_init.h -- library / model lifetime: sgx_init (the fixed-point limb tiles), thresholds, layout, sgx_free (wait, then delete), per-call workspace.
 // Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
 extern "C" const char *sgx_version(void) { return "saigehip 0.1 (gfx950)"; }
 extern "C" const char *sgx_last_error(void) { return g_err.c_str(); }
@@ -31,10 +31,10 @@ extern "C" int sgx_set_thresholds(sgx_handle *h, double maf, double mac, double 
 }
 
 template <typename T>
-static int dev_upload(T **dst, const std::vector<T> &src)
+static int dev_upload(DevBuf<T> &dst, const std::vector<T> &src)
 {
-	HIPCHK(hipMalloc((void **)dst, src.size() * sizeof(T)));
-	HIPCHK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+	HIPCHK(dst.alloc(src.size()));
+	HIPCHK(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
 	return SGX_OK;
 }
 
@@ -116,30 +116,30 @@ static int alloc_workspace(sgx_handle *h)
 		// traces showed the list pass stretched from 0.98 to 1.44 ms and 20-us solve kernels waiting 0.7 ms behind it)
 		int least = 0, greatest = 0;
 		HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-		HIPCHK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, least));
-		HIPCHK(hipStreamCreateWithPriority(&h->hstream, hipStreamNonBlocking, greatest));
-		HIPCHK(hipStreamCreateWithPriority(&h->s3_side, hipStreamNonBlocking, greatest));
+		HIPCHK(h->stream.create(hipStreamNonBlocking, least));
+		HIPCHK(h->hstream.create(hipStreamNonBlocking, greatest));
+		HIPCHK(h->s3_side.create(hipStreamNonBlocking, greatest));
 	}
-	HIPCHK(hipEventCreateWithFlags(&h->s3_fork, hipEventDisableTiming));
-	HIPCHK(hipEventCreateWithFlags(&h->s3_join, hipEventDisableTiming));
-	HIPCHK(hipMalloc((void **)&h->counters, 24 * sizeof(int)));
-	HIPCHK(hipHostMalloc((void **)&h->h_counters, 24 * sizeof(int), hipHostMallocDefault));
-	for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&h->ev[i]));
-	for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&h->evk[i]));
-	HIPCHK(hipEventCreate(&h->ev_lists));
+	HIPCHK(h->s3_fork.create(hipEventDisableTiming));
+	HIPCHK(h->s3_join.create(hipEventDisableTiming));
+	HIPCHK(h->counters.alloc(24));
+	HIPCHK(h->h_counters.alloc(24));
+	for (DevEvent &e : h->ev) HIPCHK(e.create());
+	for (DevEvent &e : h->evk) HIPCHK(e.create());
+	HIPCHK(h->ev_lists.create());
 	// SPA scratch: one (adj, mu) list of N entries per resident workgroup
 	hipDeviceProp_t prop;
 	HIPCHK(hipGetDeviceProperties(&prop, h->device));
 	h->spa_grid = prop.multiProcessorCount * 2;
 	h->n_cu = prop.multiProcessorCount;
 	h->scratch_stride = 2 * (((size_t)N + 63) & ~(size_t)63);
-	HIPCHK(hipMalloc((void **)&h->scratch, h->scratch_stride * sizeof(double) * h->spa_grid));
+	HIPCHK(h->scratch.alloc(h->scratch_stride * h->spa_grid));
 	if (!h->md.quant) {
 		// workgroups of the per-variant kernels, each with its scratch lists: 4 per CU where a packed row is
 		// short (128-thread workgroups, see the launch), else one
 		h->nwg5 = ((size_t)((N + 63) / 64) * 16 <= 32 * 1024) ? h->n_cu * 4 : h->n_cu;
-		HIPCHK(hipMalloc((void **)&h->scr5, (size_t)h->nwg5 * spa5_wg_bytes(N)));
-		HIPCHK(hipMalloc((void **)&h->cur5, 8 * sizeof(int)));   // [0], [1] spa5_kernel queues; [2], [3] spa4_moments' item queue; [4], [5] spa5_kernel on the blocks' lists
+		HIPCHK(h->scr5.alloc((size_t)h->nwg5 * spa5_wg_bytes(N)));
+		HIPCHK(h->cur5.alloc(8));   // [0], [1] spa5_kernel queues; [2], [3] spa4_moments' item queue; [4], [5] spa5_kernel on the blocks' lists
 	}
 	return SGX_OK;
 }
@@ -197,10 +197,11 @@ extern "C" int sgx_init(const sgx_model *m, int device, sgx_handle **out)
 	if (device < 0 || device >= ndev)
 		return fail(SGX_EINVAL, "sgx_init: device %d out of range (0..%d)", device, ndev - 1);
 
-	sgx_handle *h = new sgx_handle();
+	std::unique_ptr<sgx_handle, void (*)(sgx_handle *)> hold(new sgx_handle(), sgx_free);   // released on every early return
+	sgx_handle *h = hold.get();
 	h->device = device;
 	int rc = set_dev(h);
-	if (rc) { delete h; return rc; }
+	if (rc) return rc;
 	const int P = 2 * K + 2;
 	const bool quant = m->trait == SGX_TRAIT_QUANT;
 	const int KP = (K + 2) & ~1;
@@ -345,24 +346,22 @@ extern "C" int sgx_init(const sgx_model *m, int device, sgx_handle **out)
 	}
 	for (int a = 0; a < K * K; a++) md.XVX[a] = m->XVX[a];
 	for (int a = 0; a < K; a++) { md.S_a[a] = m->S_a[a]; md.Xmu[a] = (double)xmu[a]; md.Xsum[a] = (double)xsum[a]; }
-#define TRY(x) do { rc = (x); if (rc) { sgx_free(h); return rc; } } while (0)
-	TRY(dev_upload(&h->dF, F));
-	TRY(dev_upload(&h->dX, X));
-	TRY(dev_upload(&h->dy, y));
-	TRY(dev_upload(&h->dmu, mu));
-	TRY(dev_upload(&h->dmu2, mu2));
-	TRY(dev_upload(&h->dXM, XM));
-	if (h->mf_ok) {
-		std::vector<uint8_t> Flu(Fl.begin(), Fl.end());
-		TRY(dev_upload(&h->dFl, Flu));
-		h->mf[0].Fl = h->dFl;
-		TRY(dev_upload(&h->dQ, Qt));
+	auto &dm = h->model;
+	rc = dev_upload(dm.F, F);
+	if (!rc) rc = dev_upload(dm.X, X);
+	if (!rc) rc = dev_upload(dm.y, y);
+	if (!rc) rc = dev_upload(dm.mu, mu);
+	if (!rc) rc = dev_upload(dm.mu2, mu2);
+	if (!rc) rc = dev_upload(dm.XM, XM);
+	if (!rc && h->mf_ok) {
+		rc = dev_upload(dm.Fl, std::vector<uint8_t>(Fl.begin(), Fl.end()));
+		if (!rc) rc = dev_upload(dm.Q, Qt);
+		h->mf[0].Fl = dm.Fl; h->dQ = dm.Q;
 	}
-	md.F = h->dF; md.X = h->dX; md.y = h->dy; md.mu = h->dmu; md.mu2 = h->dmu2; md.XM = h->dXM;
-	rc = alloc_workspace(h);
-	if (rc) { sgx_free(h); return rc; }
-#undef TRY
-	*out = h;
+	md.F = dm.F; md.X = dm.X; md.y = dm.y; md.mu = dm.mu; md.mu2 = dm.mu2; md.XM = dm.XM;
+	if (!rc) rc = alloc_workspace(h);
+	if (rc) return rc;
+	*out = hold.release();
 	return SGX_OK;
 }
 
@@ -376,67 +375,37 @@ extern "C" int sgx_score_layout(sgx_handle *h, int32_t *limbs, int32_t n_limbs, 
 	return SGX_OK;
 }
 
+// What the members' destructors cannot know: the device, what is still in flight, the twins and the row-major scratch blocks
 extern "C" void sgx_free(sgx_handle *h)
 {
 	if (!h) return;
 	(void)hipSetDevice(h->device);
-	if (h->stream) (void)hipStreamSynchronize(h->stream);
-	for (sgx_handle *&t : h->twins) if (t) { sgx_free(t); t = nullptr; }
-	if (!h->shares_model) {
-		(void)hipFree(h->dF); (void)hipFree(h->dX); (void)hipFree(h->dy);
-		(void)hipFree(h->dmu); (void)hipFree(h->dmu2); (void)hipFree(h->dXM); (void)hipFree(h->dFl); (void)hipFree(h->dQ);
-	}
-	(void)hipFree(h->fallback); (void)hipFree(h->fb_spa2); (void)hipFree(h->fb_x2);
-	(void)hipFree(h->s3_slabs); (void)hipFree(h->s3_t3); (void)hipFree(h->s3_ovf);
-	for (int b = 0; b < 2; b++) if (h->tmp_blk[b]) { sgx_block_free(h->tmp_blk[b]); h->tmp_blk[b] = nullptr; }
-	(void)hipFree(h->mf_acc); (void)hipFree(h->seg4); (void)hipFree(h->scr5); (void)hipFree(h->cur5);
-	(void)hipFree(h->recs); (void)hipFree(h->counters); (void)hipFree(h->scratch);
-	for (int b = 0; b < 2; b++) {
-		(void)hipFree(h->pipe_in[b]); (void)hipFree(h->pipe_pk[b]); (void)hipFree(h->pipe_raw[b]); (void)hipFree(h->pipe_out[b]); (void)hipFree(h->pipe_valid[b]);
-		if (h->pin_out[b]) (void)hipHostFree(h->pin_out[b]);
-		if (h->pin_valid[b]) (void)hipHostFree(h->pin_valid[b]);
-	}
-	(void)hipFree(h->pipe_flag); (void)hipFree(h->pk_sel); (void)hipFree(h->db2_row0);
-	if (h->h_pipe_flag) (void)hipHostFree(h->h_pipe_flag);
-	if (h->ev_h2d) (void)hipEventDestroy(h->ev_h2d);
-	for (int k = 0; k < 2; k++) { if (h->ev_copy[k]) (void)hipEventDestroy(h->ev_copy[k]); if (h->ev_done[k]) (void)hipEventDestroy(h->ev_done[k]); }
-	if (h->cstream) (void)hipStreamDestroy(h->cstream);
-	(void)hipFree(h->stage_in); (void)hipFree(h->stage_out); (void)hipFree(h->stage_valid); (void)hipFree(h->stage_pk); (void)hipFree(h->ds_part);
-	(void)hipFree(h->skat_part); (void)hipFree(h->skat_fin);
-	(void)hipFree(h->skk_A); (void)hipFree(h->skk_Y); (void)hipFree(h->skk_XZ); (void)hipFree(h->skk_cpart);
-	(void)hipFree(h->skk_cs); (void)hipFree(h->skk_tiles);
-	(void)hipFree(h->cond_B); (void)hipFree(h->cond_ce); (void)hipFree(h->cond_part); (void)hipFree(h->cond_fin);
-	if (h->h_counters) (void)hipHostFree(h->h_counters);
-	for (int i = 0; i < 3; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-	for (int i = 0; i < 2; i++) if (h->evk[i]) (void)hipEventDestroy(h->evk[i]);
-	if (h->ev_lists) (void)hipEventDestroy(h->ev_lists);
-	if (h->s3_side) { (void)hipStreamSynchronize(h->s3_side); (void)hipStreamDestroy(h->s3_side); }
-	if (h->hstream) { (void)hipStreamSynchronize(h->hstream); (void)hipStreamDestroy(h->hstream); }
-	if (h->s3_fork) (void)hipEventDestroy(h->s3_fork);
-	if (h->s3_join) (void)hipEventDestroy(h->s3_join);
-	if (h->stream) (void)hipStreamDestroy(h->stream);
+	for (hipStream_t st : {(hipStream_t)h->stream, (hipStream_t)h->s3_side, (hipStream_t)h->hstream}) if (st) (void)hipStreamSynchronize(st);
+	for (sgx_handle *t : h->twins) sgx_free(t);
+	for (sgx_block *b : h->tmp_blk) sgx_block_free(b);
 	delete h;
 }
 
+// The buffers whose size follows the variants of a call, and vcap4 / nround4 with them.  recs is the group's gate: it is
+// released before the others are touched and grown last, so it holds n variants only where the whole group does, and a
+// regrow that failed half-way is done again by the next call, whatever its n.
 static int ensure_recs(sgx_handle *h, size_t n)
 {
-	if (n <= h->recs_cap) return SGX_OK;
+	if (3 * n <= h->recs.cap) return SGX_OK;
 	HIPCHK(hipStreamSynchronize(h->stream));
-	h->recs_cap = 0;
-	int rc = renew(h->recs, 3 * n);          // tier ranges A and B (+ handed-on copies), exact range (dev_common.h)
-	if (!rc) rc = renew(h->fallback, n);
+	HIPCHK(h->recs.release());
+	int rc = grow(h->fallback, n);
 	if (!rc && !h->md.quant) {
 		h->nseg = (h->md.N + spa_seg(h->md.K) - 1) / spa_seg(h->md.K);
-		rc = renew(h->fb_spa2, n);
-		if (!rc) rc = renew(h->fb_x2, n);
+		rc = grow(h->fb_spa2, n);
+		if (!rc) rc = grow(h->fb_x2, n);
 		// flagged variants per round of the series SPA stage: a block of the usual 50 000 variants in one
 		// round (a second, normally empty round costs four kernel launches per step)
 		h->vcap4 = (int)std::min<size_t>(n, 65536);
 		h->nround4 = (int)((n + h->vcap4 - 1) / h->vcap4);
-		if (!rc) rc = renew(h->seg4, (size_t)h->nseg * SPA4_NSMAX * h->vcap4);
+		if (!rc) rc = grow(h->seg4, (size_t)h->nseg * SPA4_NSMAX * h->vcap4);
 	}
-	if (!rc && h->mf_ok) rc = renew(h->mf_acc, n * (size_t)(2 * h->mfe.acc_stride - 16));   // (three-plane form: 2 NBF - 1 fragment slots)
-	if (rc) return rc;
-	h->recs_cap = n;
-	return SGX_OK;
+	if (!rc && h->mf_ok) rc = grow(h->mf_acc, n * (size_t)(2 * h->mfe.acc_stride - 16));   // (three-plane form: 2 NBF - 1 fragment slots)
+	if (!rc) rc = grow(h->recs, 3 * n);      // tier ranges A and B (+ handed-on copies), exact range (dev_common.h)
+	return rc;
 }

@@ -7,19 +7,20 @@
 
 struct sgx_kmat {
 	int device = 0;
-	hipStream_t stream = nullptr;
+	// (released in reverse order: buffers, events, the stream -- sgx_kmat_free waits for the stream first)
+	DevStream stream;
+	DevEvent ev0, ev1;                     // around the kernels of the last product
 	int n = 0;
 	bool dense = false;
 	// CSR: the full symmetric pattern
-	int64_t *rp = nullptr; int *col = nullptr; double *val = nullptr;
-	int *long_rows = nullptr; int n_long = 0;        // the rows of the wave form, ascending
+	DevBuf<int64_t> rp; DevBuf<int> col; DevBuf<double> val;
+	DevBuf<int> long_rows; int n_long = 0; // the rows of the wave form, ascending
 	// dense: [rpad][ldd], zero padded; packed columns and slab sums of a launch
-	double *K = nullptr; size_t ldd = 0; int rpad = 0, nslab = 0;
-	double *Bp = nullptr, *part = nullptr;           // [KM_WCOLS][ldd], [nslab][KM_WCOLS][rpad]
-	double *diag = nullptr;                          // [n]
+	DevBuf<double> K; size_t ldd = 0; int rpad = 0, nslab = 0;
+	DevBuf<double> Bp, part;               // [KM_WCOLS][ldd], [nslab][KM_WCOLS][rpad]
+	DevBuf<double> diag;                   // [n]
 	std::vector<double> h_diag;
 	PcgWork pw;
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;         // around the kernels of the last product
 	bool timed = false;
 };
 static_assert(KM_SLAB % 16 == 0 && KM_ROWS == 32 && KM_WCOLS == 16, "kmat_dense_kernel's tile");
@@ -29,31 +30,24 @@ extern "C" void sgx_kmat_free(sgx_kmat *m)
 	if (!m) return;
 	(void)hipSetDevice(m->device);
 	if (m->stream) (void)hipStreamSynchronize(m->stream);
-	void *ptrs[] = {m->rp, m->col, m->val, m->long_rows, m->K, m->Bp, m->part, m->diag};
-	for (void *p : ptrs) (void)hipFree(p);
-	pcg_work_free(&m->pw);
-	if (m->ev0) (void)hipEventDestroy(m->ev0);
-	if (m->ev1) (void)hipEventDestroy(m->ev1);
-	if (m->stream) (void)hipStreamDestroy(m->stream);
 	delete m;
 }
+typedef std::unique_ptr<sgx_kmat, void (*)(sgx_kmat *)> KmatHold;   // what an init function holds its new handle by
 
-#define KTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { sgx_kmat_free(m); return fail(SGX_EHIP, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-
-// device, stream, events, the diagonal and the solver's workspace of a new handle (freed by the caller on failure)
+// device, stream, events, the diagonal and the solver's workspace of a new handle
 static int kmat_open(const char *fn, sgx_kmat *m, int n, int device)
 {
 	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { sgx_kmat_free(m); return fail(SGX_ENODEV, "%s: no HIP device available", fn); }
-	if (device < 0 || device >= ndev) { sgx_kmat_free(m); return fail(SGX_EINVAL, "%s: device %d out of range", fn, device); }
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SGX_ENODEV, "%s: no HIP device available", fn);
+	if (device < 0 || device >= ndev) return fail(SGX_EINVAL, "%s: device %d out of range", fn, device);
 	m->device = device; m->n = n;
-	KTRY(hipSetDevice(device));
-	KTRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-	KTRY(hipEventCreate(&m->ev0));
-	KTRY(hipEventCreate(&m->ev1));
-	KTRY(hipMalloc((void **)&m->diag, (size_t)n * sizeof(double)));
-	KTRY(hipMemcpyAsync(m->diag, m->h_diag.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, m->stream));
-	KTRY(pcg_work_init(&m->pw, device, m->stream, n));
+	HIPCHK(hipSetDevice(device));
+	HIPCHK(m->stream.create(hipStreamNonBlocking));
+	HIPCHK(m->ev0.create());
+	HIPCHK(m->ev1.create());
+	HIPCHK(m->diag.alloc((size_t)n));
+	HIPCHK(hipMemcpyAsync(m->diag, m->h_diag.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, m->stream));
+	HIPCHK(pcg_work_init(&m->pw, device, m->stream, n));
 	return SGX_OK;
 }
 
@@ -68,7 +62,7 @@ extern "C" int sgx_kmat_init_csr(int32_t n, const int64_t *row_ptr, const int32_
 		if (row_ptr[i + 1] < row_ptr[i]) return fail(SGX_EINVAL, "sgx_kmat_init_csr: row_ptr decreases at row %d", i);
 	const size_t nnz = (size_t)row_ptr[n];
 	if (nnz && (!col || !val)) return fail(SGX_EINVAL, "sgx_kmat_init_csr: NULL argument");
-	sgx_kmat *m = new sgx_kmat();
+	KmatHold m(new sgx_kmat(), sgx_kmat_free);
 	m->h_diag.assign((size_t)n, 0.0);
 	std::vector<int> long_rows;
 	for (int i = 0; i < n; i++) {
@@ -80,27 +74,27 @@ extern "C" int sgx_kmat_init_csr(int32_t n, const int64_t *row_ptr, const int32_
 				rc = fail(SGX_EINVAL, "sgx_kmat_init_csr: the columns of row %d are not strictly ascending", i);
 			else if (!std::isfinite(val[e]))
 				rc = fail(SGX_EINVAL, "sgx_kmat_init_csr: the entry (%d, %d) is not finite", i, (int)col[e]);
-			if (rc) { delete m; return rc; }
+			if (rc) return rc;
 			if (col[e] == i) m->h_diag[i] = val[e];
 		}
 		if (row_ptr[i + 1] - row_ptr[i] >= KM_WAVE_ROW) long_rows.push_back(i);
 	}
-	int rc = kmat_open("sgx_kmat_init_csr", m, n, device);
+	int rc = kmat_open("sgx_kmat_init_csr", m.get(), n, device);
 	if (rc) return rc;
 	m->n_long = (int)long_rows.size();
 	hipStream_t st = m->stream;
-	KTRY(hipMalloc((void **)&m->rp, (size_t)(n + 1) * sizeof(int64_t)));
-	KTRY(hipMalloc((void **)&m->col, std::max<size_t>(nnz, 1) * sizeof(int)));
-	KTRY(hipMalloc((void **)&m->val, std::max<size_t>(nnz, 1) * sizeof(double)));
-	KTRY(hipMalloc((void **)&m->long_rows, std::max<size_t>(long_rows.size(), 1) * sizeof(int)));
-	KTRY(hipMemcpyAsync(m->rp, row_ptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+	HIPCHK(m->rp.alloc((size_t)n + 1));
+	HIPCHK(m->col.alloc(std::max<size_t>(nnz, 1)));
+	HIPCHK(m->val.alloc(std::max<size_t>(nnz, 1)));
+	HIPCHK(m->long_rows.alloc(std::max<size_t>(long_rows.size(), 1)));
+	HIPCHK(hipMemcpyAsync(m->rp, row_ptr, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
 	if (nnz) {
-		KTRY(hipMemcpyAsync(m->col, col, nnz * sizeof(int), hipMemcpyHostToDevice, st));
-		KTRY(hipMemcpyAsync(m->val, val, nnz * sizeof(double), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(m->col, col, nnz * sizeof(int), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(m->val, val, nnz * sizeof(double), hipMemcpyHostToDevice, st));
 	}
-	if (m->n_long) KTRY(hipMemcpyAsync(m->long_rows, long_rows.data(), long_rows.size() * sizeof(int), hipMemcpyHostToDevice, st));
-	KTRY(hipStreamSynchronize(st));
-	*out = m;
+	if (m->n_long) HIPCHK(hipMemcpyAsync(m->long_rows, long_rows.data(), long_rows.size() * sizeof(int), hipMemcpyHostToDevice, st));
+	HIPCHK(hipStreamSynchronize(st));
+	*out = m.release();
 	return SGX_OK;
 }
 
@@ -113,28 +107,27 @@ extern "C" int sgx_kmat_init_dense(const double *K, size_t ld, int32_t n, int de
 	if ((size_t)n * (size_t)n * sizeof(double) > KMAT_DENSE_BUDGET)
 		return fail(SGX_EINVAL, "sgx_kmat_init_dense: a dense matrix of %d samples is above the limit of %zu GiB", n,
 			KMAT_DENSE_BUDGET >> 30);
-	sgx_kmat *m = new sgx_kmat();
+	KmatHold m(new sgx_kmat(), sgx_kmat_free);
 	m->dense = true;
 	m->h_diag.resize((size_t)n);
 	for (size_t i = 0; i < (size_t)n; i++) m->h_diag[i] = K[i * ld + i];
-	int rc = kmat_open("sgx_kmat_init_dense", m, n, device);
+	int rc = kmat_open("sgx_kmat_init_dense", m.get(), n, device);
 	if (rc) return rc;
 	m->ldd = ((size_t)n + 15) / 16 * 16;
 	m->rpad = (n + KM_ROWS - 1) / KM_ROWS * KM_ROWS;
 	m->nslab = (int)((m->ldd + KM_SLAB - 1) / KM_SLAB);
 	hipStream_t st = m->stream;
 	const size_t kb = (size_t)m->rpad * m->ldd * sizeof(double);
-	KTRY(hipMalloc((void **)&m->K, kb));
-	KTRY(hipMalloc((void **)&m->Bp, KM_WCOLS * m->ldd * sizeof(double)));
-	KTRY(hipMalloc((void **)&m->part, (size_t)m->nslab * KM_WCOLS * m->rpad * sizeof(double)));
-	KTRY(hipMemsetAsync(m->K, 0, kb, st));
-	KTRY(hipMemcpy2DAsync(m->K, m->ldd * sizeof(double), K, ld * sizeof(double), (size_t)n * sizeof(double), (size_t)n,
+	HIPCHK(m->K.alloc((size_t)m->rpad * m->ldd));
+	HIPCHK(m->Bp.alloc(KM_WCOLS * m->ldd));
+	HIPCHK(m->part.alloc((size_t)m->nslab * KM_WCOLS * m->rpad));
+	HIPCHK(hipMemsetAsync(m->K, 0, kb, st));
+	HIPCHK(hipMemcpy2DAsync(m->K, m->ldd * sizeof(double), K, ld * sizeof(double), (size_t)n * sizeof(double), (size_t)n,
 		hipMemcpyHostToDevice, st));
-	KTRY(hipStreamSynchronize(st));
-	*out = m;
+	HIPCHK(hipStreamSynchronize(st));
+	*out = m.release();
 	return SGX_OK;
 }
-#undef KTRY
 
 extern "C" int sgx_kmat_diag(sgx_kmat *m, double *diag_out)
 {

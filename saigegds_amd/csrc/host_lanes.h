@@ -20,17 +20,17 @@ extern "C" int sgx_set_option(sgx_handle *h, const char *name, long long value)
 		for (int i = (int)value - 1; i < 3; i++) if (h->twins[i]) { sgx_free(h->twins[i]); h->twins[i] = nullptr; }
 		for (int i = 0; i < (int)value - 1; i++) {
 			if (h->twins[i]) continue;
-			sgx_handle *t = new sgx_handle();
-			t->device = h->device; t->md = h->md; t->mf_ok = h->mf_ok; t->mfe = h->mfe;
+			std::unique_ptr<sgx_handle, void (*)(sgx_handle *)> t(new sgx_handle(), sgx_free);
+			// the views of the primary's model arrays (t->model stays empty)
+			t->device = h->device; t->md = h->md; t->mf_ok = h->mf_ok; t->mfe = h->mfe; t->dQ = h->dQ;
 			for (int g = 0; g < MF_MAXG; g++) { t->mf[g] = h->mf[g]; t->mf_nbfv[g] = h->mf_nbfv[g]; }
-			t->dF = h->dF; t->dX = h->dX; t->dy = h->dy; t->dmu = h->dmu; t->dmu2 = h->dmu2; t->dXM = h->dXM; t->dFl = h->dFl; t->dQ = h->dQ;
-			t->shares_model = true; t->owner = h;
+			t->owner = h;
 			t->force_dense = h->force_dense; t->force_v1 = h->force_v1; t->force_exact = h->force_exact;
 			t->spa_abl = h->spa_abl; t->guard_tol = h->guard_tol;
-			rc = set_dev(t);
-			if (!rc) rc = alloc_workspace(t);
-			if (rc) { sgx_free(t); return rc; }
-			h->twins[i] = t;
+			rc = set_dev(t.get());
+			if (!rc) rc = alloc_workspace(t.get());
+			if (rc) return rc;
+			h->twins[i] = t.release();
 		}
 		h->n_lanes = (int)value; h->next_lane = 0; h->last_issued = nullptr;
 		return SGX_OK;

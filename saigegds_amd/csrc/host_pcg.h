@@ -9,42 +9,24 @@ struct PcgWork {
 	int device = 0;
 	hipStream_t stream = nullptr;              // the operator's stream (not owned)
 	int N = 0;
-	double *part = nullptr, *h_part = nullptr;       // [2 * GRM_MAX_RHS][GRM_RED_BLOCKS] block partials (device / pinned)
-	double *minv = nullptr, *w = nullptr;            // [N]
-	int kcap = 0;                          // columns the [k][N] vectors below have room for (the largest k seen)
-	double *B = nullptr, *O = nullptr;               // [k][N] staging of host-pointer calls
-	double *R = nullptr, *Z = nullptr, *P = nullptr, *X = nullptr, *AP = nullptr, *GP = nullptr;   // [k][N]
-	int kcap_w = 0;                        // columns Wc / Mc have room for
-	double *Wc = nullptr, *Mc = nullptr;   // [k][N]: weight rows and per-column minv of a per-column solve
+	DevBuf<double> part; PinBuf<double> h_part;      // [2 * GRM_MAX_RHS][GRM_RED_BLOCKS] block partials (device / pinned)
+	DevBuf<double> minv, w;                          // [N]
+	DevBuf<double> B, O;                             // [k][N] staging of host-pointer calls, k the largest seen (pcg_reserve)
+	DevBuf<double> R, Z, P, X, AP, GP;               // [k][N]
+	DevBuf<double> Wc, Mc;                           // [k][N]: weight rows and per-column minv of a per-column solve
 };
 
 // room for k columns (k <= GRM_MAX_RHS) in the [k][N] vectors
 static hipError_t pcg_reserve(PcgWork *pw, int k)
 {
-	if (k <= pw->kcap) return hipSuccess;
-	pw->kcap = 0;
-	for (double **p : {&pw->B, &pw->O, &pw->R, &pw->Z, &pw->P, &pw->X, &pw->AP, &pw->GP}) {
-		hipError_t e = *p ? hipFree(*p) : hipSuccess;
-		*p = nullptr;
-		if (e == hipSuccess) e = hipMalloc((void **)p, (size_t)k * pw->N * sizeof(double));
-		if (e != hipSuccess) return e;
-	}
-	pw->kcap = k;
+	for (DevBuf<double> *b : {&pw->B, &pw->O, &pw->R, &pw->Z, &pw->P, &pw->X, &pw->AP, &pw->GP}) HIPPASS(b->reserve((size_t)k * pw->N));
 	return hipSuccess;
 }
 
 // room for k columns in the per-column weights and preconditioners
 static hipError_t pcg_reserve_w(PcgWork *pw, int k)
 {
-	if (k <= pw->kcap_w) return hipSuccess;
-	pw->kcap_w = 0;
-	for (double **p : {&pw->Wc, &pw->Mc}) {
-		hipError_t e = *p ? hipFree(*p) : hipSuccess;
-		*p = nullptr;
-		if (e == hipSuccess) e = hipMalloc((void **)p, (size_t)k * pw->N * sizeof(double));
-		if (e != hipSuccess) return e;
-	}
-	pw->kcap_w = k;
+	for (DevBuf<double> *b : {&pw->Wc, &pw->Mc}) HIPPASS(b->reserve((size_t)k * pw->N));
 	return hipSuccess;
 }
 
@@ -52,21 +34,11 @@ static hipError_t pcg_reserve_w(PcgWork *pw, int k)
 static hipError_t pcg_work_init(PcgWork *pw, int device, hipStream_t stream, int n)
 {
 	pw->device = device; pw->stream = stream; pw->N = n;
-	hipError_t e = hipSuccess;
-	for (double **p : {&pw->minv, &pw->w})
-		if (e == hipSuccess) e = hipMalloc((void **)p, (size_t)n * sizeof(double));
-	if (e == hipSuccess) e = hipMalloc((void **)&pw->part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double));
-	if (e == hipSuccess) e = hipHostMalloc((void **)&pw->h_part, 2 * GRM_MAX_RHS * GRM_RED_BLOCKS * sizeof(double), hipHostMallocDefault);
-	if (e == hipSuccess) e = pcg_reserve(pw, 1);
-	return e;
-}
-
-static void pcg_work_free(PcgWork *pw)
-{
-	void *ptrs[] = {pw->part, pw->minv, pw->w, pw->B, pw->O, pw->R, pw->Z, pw->P, pw->X, pw->AP, pw->GP, pw->Wc, pw->Mc};
-	for (void *p : ptrs) (void)hipFree(p);
-	if (pw->h_part) (void)hipHostFree(pw->h_part);
-	*pw = PcgWork();
+	HIPPASS(pw->minv.alloc((size_t)n));
+	HIPPASS(pw->w.alloc((size_t)n));
+	HIPPASS(pw->part.alloc(2 * GRM_MAX_RHS * GRM_RED_BLOCKS));
+	HIPPASS(pw->h_part.alloc(2 * GRM_MAX_RHS * GRM_RED_BLOCKS));
+	return pcg_reserve(pw, 1);
 }
 
 // per column y of cols: out[y] = sum a (* b) as GRM_RED_BLOCKS block partials summed on the host in

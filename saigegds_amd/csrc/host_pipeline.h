@@ -5,12 +5,9 @@ static const size_t STAGE_BYTES = (size_t)1 << 30;    // burden rows are made an
 
 static int ensure_stage(sgx_handle *h, size_t in_bytes, size_t M)
 {
-	int rc = grow(h->stage_in, h->stage_in_cap, in_bytes);
-	if (rc || M <= h->stage_out_cap) return rc;
-	h->stage_out_cap = 0;
-	rc = renew(h->stage_out, M * 8);
-	if (!rc) rc = renew(h->stage_valid, M);
-	if (!rc) h->stage_out_cap = M;
+	int rc = grow(h->stage_in, in_bytes);
+	if (!rc) rc = grow(h->stage_out, M * 8);
+	if (!rc) rc = grow(h->stage_valid, M);
 	return rc;
 }
 
@@ -82,28 +79,22 @@ static size_t load_chunk(const sgx_handle *h, size_t dev_row, size_t M)
 static int ensure_pipe(sgx_handle *h, size_t in_bytes, size_t pk_bytes, size_t M)
 {
 	if (!h->cstream) {
-		HIPCHK(hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking));
-		HIPCHK(hipEventCreateWithFlags(&h->ev_h2d, hipEventDisableTiming));
-		for (int k = 0; k < 2; k++) { HIPCHK(hipEventCreateWithFlags(&h->ev_copy[k], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&h->ev_done[k], hipEventDisableTiming)); }
-		HIPCHK(hipMalloc((void **)&h->pipe_flag, sizeof(int)));
-		HIPCHK(hipHostMalloc((void **)&h->h_pipe_flag, sizeof(int), hipHostMallocDefault));
+		HIPCHK(h->cstream.create(hipStreamNonBlocking));
+		HIPCHK(h->ev_h2d.create(hipEventDisableTiming));
+		for (int k = 0; k < 2; k++) { HIPCHK(h->ev_copy[k].create(hipEventDisableTiming)); HIPCHK(h->ev_done[k].create(hipEventDisableTiming)); }
+		HIPCHK(h->pipe_flag.alloc(1));
+		HIPCHK(h->h_pipe_flag.alloc(1));
 	}
-	int rc = grow2(h->pipe_in, h->pipe_in_cap, in_bytes);
-	if (!rc) rc = grow2(h->pipe_pk, h->pipe_pk_cap, pk_bytes);
-	if (rc || M <= h->pipe_out_cap) return rc;
-	h->pipe_out_cap = 0;
-	for (int b = 0; b < 2; b++) {
-		rc = renew(h->pipe_out[b], M * 8);
-		if (!rc) rc = renew(h->pipe_valid[b], M);
-		if (rc) return rc;
-		if (h->pin_out[b]) HIPCHK(hipHostFree(h->pin_out[b]));
-		if (h->pin_valid[b]) HIPCHK(hipHostFree(h->pin_valid[b]));
-		h->pin_out[b] = nullptr; h->pin_valid[b] = nullptr;
-		HIPCHK(hipHostMalloc((void **)&h->pin_out[b], M * 8 * sizeof(double), hipHostMallocDefault));
-		HIPCHK(hipHostMalloc((void **)&h->pin_valid[b], M, hipHostMallocDefault));
+	int rc = SGX_OK;
+	for (int b = 0; b < 2 && !rc; b++) {
+		rc = grow(h->pipe_in[b], in_bytes);
+		if (!rc) rc = grow(h->pipe_pk[b], pk_bytes);
+		if (!rc) rc = grow(h->pipe_out[b], M * 8);
+		if (!rc) rc = grow(h->pipe_valid[b], M);
+		if (!rc) rc = grow(h->pin_out[b], M * 8);
+		if (!rc) rc = grow(h->pin_valid[b], M);
 	}
-	h->pipe_out_cap = M;
-	return SGX_OK;
+	return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -214,19 +205,20 @@ static int src_prepare(sgx_handle *h, RowSrc &src, size_t M, size_t chunk)
 		src.span(off, std::min(chunk, M - off), byte0, bytes, nib);
 		need = std::max(need, bytes);
 	}
-	int rc = grow2(h->pipe_raw, h->pipe_raw_cap, need);
+	int rc = grow(h->pipe_raw[0], need);
+	if (!rc) rc = grow(h->pipe_raw[1], need);
 	if (rc) return rc;
 	src.sel_dev = nullptr; src.row0_dev = nullptr;
 	if (src.sel) {
 		const size_t N = (size_t)h->md.N;
-		rc = grow(h->pk_sel, h->pk_sel_cap, N);
+		rc = grow(h->pk_sel, N);
 		if (rc) return rc;
 		static_assert(sizeof(int) == sizeof(int32_t), "sel");
 		HIPCHK(hipMemcpyAsync(h->pk_sel, src.sel, N * sizeof(int), hipMemcpyHostToDevice, h->cstream));
 		src.sel_dev = h->pk_sel;
 	}
 	if (!src.row0.empty()) {
-		rc = grow(h->db2_row0, h->db2_row0_cap, M + 1);
+		rc = grow(h->db2_row0, M + 1);
 		if (rc) return rc;
 		HIPCHK(hipMemcpyAsync(h->db2_row0, src.row0.data(), (M + 1) * sizeof(unsigned), hipMemcpyHostToDevice, h->cstream));
 		src.row0_dev = h->db2_row0;
@@ -285,7 +277,7 @@ static int src_upload(sgx_handle *h, const RowSrc &src, int b, size_t off, size_
 	if (src.kind == SRC_ROWS) return copy_rows_h2d(h->pipe_in[b], dev_row, src.rows + off * src.row_bytes, src.row_bytes, m, h->cstream);
 	int rc = copy_raw(h, src, b, off, m);
 	if (rc || src.kind == SRC_DBIT2) return rc;
-	return launch_unpack(h->cstream, src, h->pipe_raw[b], h->md.N, m, reinterpret_cast<double *>(h->pipe_in[b]));
+	return launch_unpack(h->cstream, src, h->pipe_raw[b], h->md.N, m, reinterpret_cast<double *>(h->pipe_in[b].p));
 }
 
 // On the compute stream, behind the upload: dBit2 bytes -> the 2-bit rows of pipe_in[b] (the link goes on with the next
@@ -380,7 +372,7 @@ static int scan_host(sgx_handle *h, RowSrc &src, size_t dev_row_bytes, size_t M,
 					(const uint8_t *)h->pipe_in[b], N, h->pipe_pk[b], pk_row, h->pipe_flag);
 			else
 				hipLaunchKernelGGL((pack_rows_2bit<int>), g, dim3(256), 0, h->cstream,
-					(const int *)h->pipe_in[b], N, h->pipe_pk[b], pk_row, h->pipe_flag);
+					(const int *)h->pipe_in[b].p, N, h->pipe_pk[b], pk_row, h->pipe_flag);
 			HIPCHK(hipGetLastError());
 			HIPCHK(hipMemcpyAsync(h->h_pipe_flag, h->pipe_flag, sizeof(int), hipMemcpyDeviceToHost, h->cstream));
 			HIPCHK(hipStreamSynchronize(h->cstream));
@@ -390,7 +382,7 @@ static int scan_host(sgx_handle *h, RowSrc &src, size_t dev_row_bytes, size_t M,
 		if (INPUT == IN_I32 && !packed_ok) {
 			as_f64 = reinterpret_cast<double *>(h->pipe_in[b] + f64_off);
 			hipLaunchKernelGGL(i32_rows_to_f64, dim3(1024), dim3(256), 0, h->cstream,
-				(const int *)h->pipe_in[b], m * (size_t)N, as_f64);
+				(const int *)h->pipe_in[b].p, m * (size_t)N, as_f64);
 			HIPCHK(hipGetLastError());
 		}
 		const bool as_block = blocks && (INPUT == IN_2BIT || packed_ok);
@@ -576,8 +568,8 @@ extern "C" int sgx_burden_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv,
 	const size_t o_idx = (o_ptr + (n_rows + 1) * sizeof(long long) + 15) & ~(size_t)15;
 	const size_t o_lut = (o_idx + (size_t)std::max<int64_t>(nnz, 1) * sizeof(int) + 15) & ~(size_t)15;
 	const size_t need = o_lut + (size_t)std::max<int64_t>(nnz, 1) * 4 * sizeof(double);
-	if (need > h->stage_pk_cap) HIPCHK(hipStreamSynchronize(h->stream));
-	rc = grow(h->stage_pk, h->stage_pk_cap, need);
+	if (need > h->stage_pk.cap) HIPCHK(hipStreamSynchronize(h->stream));
+	rc = grow(h->stage_pk, need);
 	if (rc) return rc;
 	rc = copy_rows_h2d(h->stage_pk, dbpv, packed, bpv, n_variants, h->stream);
 	if (rc) return rc;
@@ -602,7 +594,7 @@ extern "C" int sgx_burden_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv,
 		hipLaunchKernelGGL(burden_collapse_kernel, dim3((unsigned)((ndw + 255) / 256), (unsigned)m), dim3(256), 0, h->stream,
 			h->stage_pk, dbpv, N, reinterpret_cast<const long long *>(h->stage_pk + o_ptr) + off,
 			reinterpret_cast<const int *>(h->stage_pk + o_idx), reinterpret_cast<const double *>(h->stage_pk + o_lut),
-			reinterpret_cast<double *>(h->stage_in), (size_t)N);
+			reinterpret_cast<double *>(h->stage_in.p), (size_t)N);
 		HIPCHK(hipGetLastError());
 		rc = scan_staged<IN_F64>(h, h->stage_in, row_bytes, m, out8 + off * 8, valid + off, total);
 		if (rc) return rc;

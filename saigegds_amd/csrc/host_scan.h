@@ -1,14 +1,13 @@
 // host_scan.h -- the block scan (contraction kernel forms, sparse pass, epilogue), lanes, the row-major device call.
 // Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
 
+// a lane's buffer that a call in flight may still read: the lane's streams are brought to their end before it regrows
 template <typename T>
-static int ensure_buf(sgx_handle *h, T **p, size_t *cap, size_t need)
+static int ensure_buf(sgx_handle *lane, DevBuf<T> &buf, size_t need)
 {
-	if (need <= *cap) return SGX_OK;
-	HIPCHK(hipStreamSynchronize(h->stream));
-	if (h->hstream) HIPCHK(hipStreamSynchronize(h->hstream));
-	if (h->s3_side) HIPCHK(hipStreamSynchronize(h->s3_side));
-	return grow(*p, *cap, need);
+	if (need <= buf.cap) return SGX_OK;
+	for (hipStream_t st : {(hipStream_t)lane->stream, (hipStream_t)lane->hstream, (hipStream_t)lane->s3_side}) if (st) HIPCHK(hipStreamSynchronize(st));
+	return grow(buf, need);
 }
 
 // The shapes of the contraction kernel's forms (kern_score3.h): [0] two planes, [1] three planes; entries in table order
@@ -25,7 +24,7 @@ static int launch_score3(sgx_handle *h, const sgx_block *b, RowsRef rr, size_t M
 	constexpr S3Shape s = s3_shapes[MISS][I];
 	hipStream_t st = h->hstream;
 	pl = s3_plan(M, b->ntile, grid, s.naf * s.nc, rr.bpv);
-	int rc = ensure_buf(h, &h->s3_slabs, &h->s3_slabs_cap, (size_t)pl.ng * pl.ipg * s.nc * s.naf * slots * 256);
+	int rc = ensure_buf(h, h->s3_slabs, (size_t)pl.ng * pl.ipg * s.nc * s.naf * slots * 256);
 	if (rc) return rc;
 	const size_t lds = s3_lds_bytes(s.nbf, s.naf, s.nc, s.da, s.db);
 	auto kern = score3_kernel<s.nbf, s.naf, s.nc, s.nla, s.nlb, s.da, s.db, MISS>;
@@ -36,7 +35,7 @@ static int launch_score3(sgx_handle *h, const sgx_block *b, RowsRef rr, size_t M
 	}
 	HIPCHK(hipEventRecord(h->evk[0], st));
 	hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * (s.nc + s.nla + s.nlb)), lds, st,
-		rr.base, (const uint8_t *)h->dFl, pl, h->s3_slabs);
+		rr.base, h->mf[0].Fl, pl, h->s3_slabs);
 	HIPCHK(hipEventRecord(h->evk[1], st));
 	h->evk_set = true;
 	return SGX_OK;
@@ -53,7 +52,7 @@ static int launch_block_scan(sgx_handle *h, const sgx_block *b, size_t M, double
 	hipStream_t st = h->hstream;
 	const RowsRef rr = block_rows(b);
 	const S3Lists L = block_lists(b);
-	int rc = ensure_buf(h, &h->s3_t3, &h->s3_t3_cap, (size_t)b->nr * M * md.P * 2);   // per-range sums over the missing samples (the epilogue adds them up)
+	int rc = ensure_buf(h, h->s3_t3, (size_t)b->nr * M * md.P * 2);   // per-range sums over the missing samples (the epilogue adds them up)
 	if (rc) return rc;
 	if (form == FORM_ROWS) {
 		// one pass over the rows: the missing genotypes of every (range, variant), their sums of Q gathered on the spot
@@ -69,7 +68,7 @@ static int launch_block_scan(sgx_handle *h, const sgx_block *b, size_t M, double
 	}
 	rc = scan_begin(h, st, form, b);
 	if (rc) return rc;
-	rc = ensure_buf(h, &h->s3_ovf, &h->s3_ovf_cap, M);
+	rc = ensure_buf(h, h->s3_ovf, M);
 	if (rc) return rc;
 	if (form == FORM_LISTS) {
 		// Sums over the missing samples, on the side stream, FIRST; the contraction kernel waits for them:

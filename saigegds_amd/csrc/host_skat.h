@@ -68,9 +68,9 @@ static int skat_run(sgx_handle *h, const SkatPlan &pl, size_t n_units, const int
 {
 	const size_t T = pl.tiles.size(), tchunk = pl.tchunk;
 	const int nslab = pl.nslab;
-	int rc = grow(h->skat_part, h->skat_part_cap, tchunk * (size_t)nslab * 256);
+	int rc = grow(h->skat_part, tchunk * (size_t)nslab * 256);
 	if (rc) return rc;
-	rc = grow(h->skat_fin, h->skat_fin_cap, tchunk * 256);
+	rc = grow(h->skat_fin, tchunk * 256);
 	if (rc) return rc;
 	std::vector<size_t> cov_off(n_units + 1, 0);
 	for (size_t u = 0; u < n_units; u++) {
@@ -183,7 +183,7 @@ static int skat_2bit_host(sgx_handle *h, const uint8_t *packed, size_t bpv, size
 	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
 	const size_t o_til = o_lut + (size_t)nnz * 4 * sizeof(double);
 	const size_t need = o_til + T * sizeof(SkatTile);
-	rc = grow(h->stage_pk, h->stage_pk_cap, need);
+	rc = grow(h->stage_pk, need);
 	if (rc) return rc;
 	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
 	for (size_t off = 0; off < n_variants; off += rchunk) {
@@ -198,7 +198,7 @@ static int skat_2bit_host(sgx_handle *h, const uint8_t *packed, size_t bpv, size
 	rc = skat_run(h, pl, n_units, unit_ptr, C, [&](size_t t0, size_t nt) {
 		hipLaunchKernelGGL(skat_gram_kernel, dim3((unsigned)nt, (unsigned)pl.nslab), dim3(64), 0, h->stream,
 			h->stage_pk, dbpv, N, reinterpret_cast<const int *>(h->stage_pk + o_idx),
-			reinterpret_cast<const double *>(h->stage_pk + o_lut), h->dF, P,
+			reinterpret_cast<const double *>(h->stage_pk + o_lut), h->md.F, P,
 			reinterpret_cast<const SkatTile *>(h->stage_pk + o_til) + t0, nt, SKAT_SLAB_DW, h->skat_part);
 	}, dense, cov);
 	if (rc) return rc;

@@ -34,7 +34,7 @@ static int skat_ds_block_host(sgx_handle *h, const sgx_dsblock *b, size_t n_unit
 	const size_t o_mean = ((size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
 	const size_t o_til = o_mean + (size_t)nnz * sizeof(double);
 	const size_t o_flip = o_til + T * sizeof(SkatTile);
-	rc = grow(bm->tabs, bm->tabs_cap, o_flip + (size_t)nnz);
+	rc = grow(bm->tabs, o_flip + (size_t)nnz);
 	if (rc) return rc;
 	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
 	HIPCHK(hipMemcpyAsync(b->tabs, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -42,7 +42,7 @@ static int skat_ds_block_host(sgx_handle *h, const sgx_dsblock *b, size_t n_unit
 	HIPCHK(hipMemcpyAsync(b->tabs + o_til, pl.tiles.data(), T * sizeof(SkatTile), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipMemcpyAsync(b->tabs + o_flip, flip, (size_t)nnz, hipMemcpyHostToDevice, h->stream));
 
-	const int *d_idx = reinterpret_cast<const int *>(b->tabs);
+	const int *d_idx = reinterpret_cast<const int *>(b->tabs.p);
 	const double *d_mean = reinterpret_cast<const double *>(b->tabs + o_mean);
 	const SkatTile *d_til = reinterpret_cast<const SkatTile *>(b->tabs + o_til);
 	const uint8_t *d_flip = b->tabs + o_flip;
@@ -50,10 +50,10 @@ static int skat_ds_block_host(sgx_handle *h, const sgx_dsblock *b, size_t n_unit
 		const dim3 grid((unsigned)nt, (unsigned)pl.nslab);
 		if (b->dtype == SGX_DS_U8)
 			hipLaunchKernelGGL((skat_gram_ds_kernel<uint8_t>), grid, dim3(64), 0, h->stream,
-				(const uint8_t *)b->rows, N, d_idx, d_flip, d_mean, h->dF, P, d_til + t0, nt, SKAT_DS_SLAB, h->skat_part);
+				(const uint8_t *)b->rows, N, d_idx, d_flip, d_mean, h->md.F, P, d_til + t0, nt, SKAT_DS_SLAB, h->skat_part);
 		else
 			hipLaunchKernelGGL((skat_gram_ds_kernel<double>), grid, dim3(64), 0, h->stream,
-				(const double *)b->rows, N, d_idx, d_flip, d_mean, h->dF, P, d_til + t0, nt, SKAT_DS_SLAB, h->skat_part);
+				(const double *)b->rows.p, N, d_idx, d_flip, d_mean, h->md.F, P, d_til + t0, nt, SKAT_DS_SLAB, h->skat_part);
 	}, dense, cov);
 	if (rc) return rc;
 	skat_finish(h->md, n_units, unit_ptr, dense, score, cov);

@@ -12,7 +12,7 @@ static int kmat_pcg_dev(const char *fn, sgx_kmat *m, const double *w_dev, const 
 	const hipError_t e = pcg_reserve(&m->pw, k);
 	if (e != hipSuccess) {
 		(void)hipGetLastError();
-		return fail(e == hipErrorOutOfMemory ? SGX_ENOMEM : SGX_EHIP, "%s: the workspace of %d columns: %s", fn, k, hipGetErrorString(e));
+		return fail(mem_code(e), "%s: the workspace of %d columns: %s", fn, k, hipGetErrorString(e));
 	}
 	int rc = pcg_core(&m->pw, m->diag, w_dev, tau, B_dev, ldb, k, maxiter, tol, iters, kmat_product(m), nullptr);
 	if (rc) return rc;
@@ -31,22 +31,14 @@ extern "C" int sgx_kmat_pcg_multi_dev(sgx_kmat *m, const double *w_dev, const do
 	return kmat_pcg_dev("sgx_kmat_pcg_multi_dev", m, w_dev, tau, B_dev, ldb, k, maxiter, tol, X_dev, iters);
 }
 
-// grow() with the out-of-memory code: what the call keeps per unit is the caller's to size
+// room for n elements of what the call keeps per unit, which is the caller's to size: out of memory is SGX_ENOMEM
 template <class T>
-static int skk_grow(T *&p, size_t &cap, size_t n, const char *what)
+static int skk_room(DevBuf<T> &b, size_t n, const char *what)
 {
-	if (n <= cap) return SGX_OK;
-	cap = 0;
-	if (p) HIPCHK(hipFree(p));
-	p = nullptr;
-	const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
-	if (e != hipSuccess) {
-		p = nullptr;
-		(void)hipGetLastError();
-		return fail(e == hipErrorOutOfMemory ? SGX_ENOMEM : SGX_EHIP, "sgx_skat_kmat_2bit: %zu bytes for %s: %s", n * sizeof(T), what, hipGetErrorString(e));
-	}
-	cap = n;
-	return SGX_OK;
+	const hipError_t e = b.reserve(n);
+	if (e == hipSuccess) return SGX_OK;
+	(void)hipGetLastError();
+	return fail(mem_code(e), "sgx_skat_kmat_2bit: %zu bytes for %s: %s", n * sizeof(T), what, hipGetErrorString(e));
 }
 
 // out[r][c] = (vector row0 + r of L)' (vector col0 + c of R) for r < nr, c < nc (row-major, ldo apart): the tiles,
@@ -62,9 +54,9 @@ static int skk_product(sgx_handle *h, const double *L, int row0, int nr, const d
 	const size_t T = tiles.size();
 	if (T == 0) return SGX_OK;
 	const size_t tchunk = std::min(T, std::max<size_t>(1, SKAT_PART_BYTES / ((size_t)nslab * 256 * sizeof(double))));
-	int rc = skk_grow(h->skat_part, h->skat_part_cap, tchunk * (size_t)nslab * 256, "the slab partials");
-	if (!rc) rc = skk_grow(h->skat_fin, h->skat_fin_cap, tchunk * 256, "the tiles");
-	if (!rc) rc = skk_grow(h->skk_tiles, h->skk_tiles_cap, tchunk, "the tile list");
+	int rc = skk_room(h->skat_part, tchunk * (size_t)nslab * 256, "the slab partials");
+	if (!rc) rc = skk_room(h->skat_fin, tchunk * 256, "the tiles");
+	if (!rc) rc = skk_room(h->skk_tiles, tchunk, "the tile list");
 	if (rc) return rc;
 	std::vector<double> fin(tchunk * 256);
 	for (size_t t0 = 0; t0 < T; t0 += tchunk) {
@@ -168,12 +160,12 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
 	const size_t need = o_lut + (size_t)nnz * 4 * sizeof(double);
 	const int ncslab = (ndw + SKK_CSLAB_DW - 1) / SKK_CSLAB_DW;
-	rc = skk_grow(h->stage_pk, h->stage_pk_cap, need, "the rows");
-	if (!rc) rc = skk_grow(h->skk_XZ, h->skk_XZ_cap, (size_t)2 * K * lda, "the covariate columns");
-	if (!rc) rc = skk_grow(h->skk_A, h->skk_A_cap, (size_t)m_max * lda, "a unit's columns");
-	if (!rc) rc = skk_grow(h->skk_Y, h->skk_Y_cap, (size_t)m_max * lda, "a unit's solves");
-	if (!rc) rc = skk_grow(h->skk_cpart, h->skk_cpart_cap, (size_t)m_max * ncslab * C1, "the column sums");
-	if (!rc) rc = skk_grow(h->skk_cs, h->skk_cs_cap, (size_t)m_max * C1, "the column sums");
+	rc = skk_room(h->stage_pk, need, "the rows");
+	if (!rc) rc = skk_room(h->skk_XZ, (size_t)2 * K * lda, "the covariate columns");
+	if (!rc) rc = skk_room(h->skk_A, (size_t)m_max * lda, "a unit's columns");
+	if (!rc) rc = skk_room(h->skk_Y, (size_t)m_max * lda, "a unit's solves");
+	if (!rc) rc = skk_room(h->skk_cpart, (size_t)m_max * ncslab * C1, "the column sums");
+	if (!rc) rc = skk_room(h->skk_cs, (size_t)m_max * C1, "the column sums");
 	if (rc) return rc;
 	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
 	for (size_t off = 0; off < n_variants; off += rchunk) {
@@ -187,7 +179,7 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	const double *d_lut = reinterpret_cast<const double *>(h->stage_pk + o_lut);
 	double *Xc = h->skk_XZ, *Z = h->skk_XZ + (size_t)K * lda;
 	const unsigned gl = (unsigned)((lda + 255) / 256);
-	hipLaunchKernelGGL(skk_xcols_kernel, dim3(gl, (unsigned)K), dim3(256), 0, st, h->dX, N, K, Xc, lda);
+	hipLaunchKernelGGL(skk_xcols_kernel, dim3(gl, (unsigned)K), dim3(256), 0, st, h->md.X, N, K, Xc, lda);
 	HIPCHK(hipMemsetAsync(Z, 0, (size_t)K * lda * sizeof(double), st));
 	HIPCHK(hipMemsetAsync(h->skk_Y, 0, (size_t)m_max * lda * sizeof(double), st));
 	HIPCHK(hipGetLastError());
@@ -219,11 +211,11 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 
 		t_col = std::chrono::steady_clock::now();
 		hipLaunchKernelGGL(skk_colsum_kernel, dim3((unsigned)ncslab, (unsigned)m), dim3(256), 0, st, h->stage_pk, dbpv, N,
-			d_idx + e0, d_lut + 4 * e0, h->dF, P, K, h->skk_cpart);
+			d_idx + e0, d_lut + 4 * e0, h->md.F, P, K, h->skk_cpart);
 		hipLaunchKernelGGL(skk_colfin_kernel, dim3((unsigned)(((size_t)m * C1 + 255) / 256)), dim3(256), 0, st, h->skk_cpart,
 			(size_t)m * C1, ncslab, C1, h->skk_cs);
 		hipLaunchKernelGGL(skk_adj_kernel, dim3(gl, (unsigned)m), dim3(256), 0, st, h->stage_pk, dbpv, N, d_idx + e0,
-			d_lut + 4 * e0, h->dX, K, h->skk_cs, h->skk_A, lda);
+			d_lut + 4 * e0, h->md.X, K, h->skk_cs, h->skk_A, lda);
 		HIPCHK(hipGetLastError());
 		cs.resize((size_t)m * C1);
 		HIPCHK(hipMemcpyAsync(cs.data(), h->skk_cs, cs.size() * sizeof(double), hipMemcpyDeviceToHost, st));

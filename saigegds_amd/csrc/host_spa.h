@@ -207,13 +207,10 @@ static int launch_score_fp64(sgx_handle *h, RowsRef rr, size_t M, double *out8, 
 				int ns = std::max(1, std::min((4 * h->n_cu + vb - 1) / vb, (md.N + 4095) / 4096));
 				int per = (((md.N + ns - 1) / ns) + 63) & ~63;
 				ns = (md.N + per - 1) / per;
-				const size_t need = (size_t)ns * M * (3 * P + 2) * sizeof(double);
-				if (need > h->ds_part_cap) {
+				const size_t need = (size_t)ns * M * (3 * P + 2);
+				if (need > h->ds_part.cap) {
 					HIPCHK(hipStreamSynchronize(st));
-					if (h->ds_part) HIPCHK(hipFree(h->ds_part));
-					h->ds_part = nullptr; h->ds_part_cap = 0;
-					HIPCHK(hipMalloc((void **)&h->ds_part, need));
-					h->ds_part_cap = need;
+					HIPCHK(h->ds_part.reserve(need));
 				}
 				hipLaunchKernelGGL((score_ds_tile_kernel<P, T>), dim3((unsigned)vb, (unsigned)ns), dim3(256), 0, st,
 					rows, (int)M, md, per, h->ds_part);

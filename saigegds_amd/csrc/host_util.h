@@ -84,45 +84,34 @@ extern "C" int sgx_geno_stats_2bit(const uint8_t *packed, size_t bpv, int32_t n_
 	HIPCHK(hipSetDevice(device));
 	const size_t dbpv = ((size_t)(n_samp + 15) / 16) * 4;
 	const size_t chunk = std::max<size_t>(1, std::min<size_t>(n_variants, ((size_t)1 << 30) / dbpv));
-	uint8_t *dpk = nullptr; int *dn = nullptr, *ds = nullptr;
-	HIPCHK(hipMalloc((void **)&dpk, chunk * dbpv));
-	hipError_t e = hipMalloc((void **)&dn, chunk * sizeof(int));
-	if (e == hipSuccess) e = hipMalloc((void **)&ds, chunk * sizeof(int));
-	int rc = SGX_OK;
-	for (size_t off = 0; off < n_variants && e == hipSuccess; off += chunk) {
+	DevBuf<uint8_t> dpk; DevBuf<int> dn, ds;       // (every copy below is synchronous: nothing is in flight at a return)
+	HIPCHK(dpk.alloc(chunk * dbpv));
+	HIPCHK(dn.alloc(chunk));
+	HIPCHK(ds.alloc(chunk));
+	for (size_t off = 0; off < n_variants; off += chunk) {
 		const size_t m = std::min(chunk, n_variants - off);
-		e = hipMemset(dpk, 0, m * dbpv);
-		if (e == hipSuccess) e = hipMemcpy2D(dpk, dbpv, packed + off * bpv, bpv, std::min(bpv, dbpv), m, hipMemcpyHostToDevice);
-		if (e != hipSuccess) break;
+		HIPCHK(hipMemset(dpk, 0, m * dbpv));
+		HIPCHK(hipMemcpy2D(dpk, dbpv, packed + off * bpv, bpv, std::min(bpv, dbpv), m, hipMemcpyHostToDevice));
 		hipLaunchKernelGGL(geno_stats_kernel, dim3((unsigned)m), dim3(256), 0, 0, dpk, dbpv, (int)n_samp, dn, ds);
-		e = hipGetLastError();
-		if (e == hipSuccess) e = hipMemcpy(n_valid + off, dn, m * sizeof(int), hipMemcpyDeviceToHost);
-		if (e == hipSuccess) e = hipMemcpy(allele_sum + off, ds, m * sizeof(int), hipMemcpyDeviceToHost);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpy(n_valid + off, dn, m * sizeof(int), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(allele_sum + off, ds, m * sizeof(int), hipMemcpyDeviceToHost));
 	}
-	(void)hipFree(dpk); (void)hipFree(dn); (void)hipFree(ds);
-	if (e != hipSuccess) rc = fail(SGX_EHIP, "sgx_geno_stats_2bit: %s", hipGetErrorString(e));
-	return rc;
+	return SGX_OK;
 }
 
 // What sgx_quantize_packed holds on the device, released on every way out
 struct QuantDev {
-	hipStream_t cstream = nullptr, stream = nullptr;
-	hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
-	uint8_t *raw[2] = {nullptr, nullptr}, *out = nullptr;
-	int *sel = nullptr, *part = nullptr, *cnt = nullptr;
-	double *part_s = nullptr, *sum = nullptr;
+	DevStream cstream, stream;
+	DevEvent ev_copy[2], ev_done[2];
+	DevBuf<uint8_t> raw[2], out;
+	DevBuf<int> sel, part, cnt;
+	DevBuf<double> part_s, sum;
+	// the streams' work ends before the members go (in reverse order: buffers, events, streams)
 	~QuantDev()
 	{
 		if (cstream) (void)hipStreamSynchronize(cstream);
 		if (stream) (void)hipStreamSynchronize(stream);
-		for (int k = 0; k < 2; k++) {
-			if (ev_copy[k]) (void)hipEventDestroy(ev_copy[k]);
-			if (ev_done[k]) (void)hipEventDestroy(ev_done[k]);
-			(void)hipFree(raw[k]);
-		}
-		(void)hipFree(out); (void)hipFree(sel); (void)hipFree(part); (void)hipFree(cnt); (void)hipFree(part_s); (void)hipFree(sum);
-		if (cstream) (void)hipStreamDestroy(cstream);
-		if (stream) (void)hipStreamDestroy(stream);
 	}
 };
 
@@ -147,21 +136,21 @@ extern "C" int sgx_quantize_packed(const void *raw, int cls, size_t n_file_samp,
 	const size_t chunk = std::max<size_t>(1, std::min(n_rows, chunk_bytes / src.row_bytes));
 	const unsigned nbx = (unsigned)((dstride / 4 + 255) / 256);      // blocks of a row: quantize_rows has no stride in x
 	QuantDev d;
-	HIPCHK(hipStreamCreateWithFlags(&d.cstream, hipStreamNonBlocking));
-	HIPCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+	HIPCHK(d.cstream.create(hipStreamNonBlocking));
+	HIPCHK(d.stream.create(hipStreamNonBlocking));
 	for (int k = 0; k < 2; k++) {
-		HIPCHK(hipEventCreateWithFlags(&d.ev_copy[k], hipEventDisableTiming));
-		HIPCHK(hipEventCreateWithFlags(&d.ev_done[k], hipEventDisableTiming));
-		if (k == 0 || chunk < n_rows) HIPCHK(hipMalloc((void **)&d.raw[k], chunk * src.row_bytes));
+		HIPCHK(d.ev_copy[k].create(hipEventDisableTiming));
+		HIPCHK(d.ev_done[k].create(hipEventDisableTiming));
+		if (k == 0 || chunk < n_rows) HIPCHK(d.raw[k].alloc(chunk * src.row_bytes));
 	}
-	HIPCHK(hipMalloc((void **)&d.out, chunk * dstride));
-	HIPCHK(hipMalloc((void **)&d.part, 3 * (size_t)nbx * chunk * sizeof(int)));
-	HIPCHK(hipMalloc((void **)&d.part_s, (size_t)nbx * chunk * sizeof(double)));
-	HIPCHK(hipMalloc((void **)&d.cnt, 3 * chunk * sizeof(int)));
-	HIPCHK(hipMalloc((void **)&d.sum, chunk * sizeof(double)));
+	HIPCHK(d.out.alloc(chunk * dstride));
+	HIPCHK(d.part.alloc(3 * (size_t)nbx * chunk));
+	HIPCHK(d.part_s.alloc((size_t)nbx * chunk));
+	HIPCHK(d.cnt.alloc(3 * chunk));
+	HIPCHK(d.sum.alloc(chunk));
 	if (sel) {
 		static_assert(sizeof(int) == sizeof(int32_t), "sel");
-		HIPCHK(hipMalloc((void **)&d.sel, (size_t)n_samp * sizeof(int)));
+		HIPCHK(d.sel.alloc((size_t)n_samp));
 		HIPCHK(hipMemcpyAsync(d.sel, sel, (size_t)n_samp * sizeof(int), hipMemcpyHostToDevice, d.cstream));   // ahead of the chunks
 	}
 	int *p_nv = d.part, *p_as = d.part + (size_t)nbx * chunk, *p_dv = d.part + 2 * (size_t)nbx * chunk;
@@ -177,11 +166,11 @@ extern "C" int sgx_quantize_packed(const void *raw, int cls, size_t n_file_samp,
 		// with a selection a thread keeps its 16 indices for the rows of its stride: fewer, longer strides
 		const dim3 g(nbx, (unsigned)std::min<size_t>(m, sel ? 64 : 65535));
 #define SGX_QUANT(T, S) do { \
-		hipLaunchKernelGGL((quantize_rows<T>), g, dim3(256), 0, d.stream, (const T *)d.raw[k], n_file_samp, (const int *)d.sel, \
-			(int)n_samp, m, scale, offset, d.out, dstride, p_nv, p_as, p_dv, (S *)d.part_s); \
+		hipLaunchKernelGGL((quantize_rows<T>), g, dim3(256), 0, d.stream, (const T *)d.raw[k].p, n_file_samp, (const int *)d.sel, \
+			(int)n_samp, m, scale, offset, d.out, dstride, p_nv, p_as, p_dv, (S *)d.part_s.p); \
 		HIPCHK(hipGetLastError()); \
 		hipLaunchKernelGGL((quantize_finish<S>), dim3((unsigned)std::min<size_t>((m + 255) / 256, 1024)), dim3(256), 0, d.stream, \
-			p_nv, p_as, p_dv, (const S *)d.part_s, nbx, m, scale, offset, c_nv, c_as, c_dv, d.sum); \
+			p_nv, p_as, p_dv, (const S *)d.part_s.p, nbx, m, scale, offset, c_nv, c_as, c_dv, d.sum); \
 		HIPCHK(hipGetLastError()); } while (0)
 		static_assert(sizeof(long long) == sizeof(double), "the partial sums share a buffer");
 		switch (cls) {
@@ -236,15 +225,14 @@ extern "C" int sgx_selftest(int device)
 	for (auto &v : B) { x = splitmix64(x); v = (int8_t)(x & 0xFF); }
 	for (int i = 0; i < 16; i++) for (int j = 0; j < 16; j++) for (int k = 0; k < 64; k++)
 		R[i * 16 + j] += (int)A[i * 64 + k] * (int)B[k * 16 + j];
-	int8_t *dA, *dB; int *dD;
-	HIPCHK(hipMalloc((void **)&dA, A.size())); HIPCHK(hipMalloc((void **)&dB, B.size()));
-	HIPCHK(hipMalloc((void **)&dD, 256 * sizeof(int)));
+	DevBuf<int8_t> dA, dB; DevBuf<int> dD;     // (the copies back are synchronous: nothing is in flight at a return)
+	HIPCHK(dA.alloc(A.size())); HIPCHK(dB.alloc(B.size()));
+	HIPCHK(dD.alloc(256));
 	HIPCHK(hipMemcpy(dA, A.data(), A.size(), hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(dB, B.data(), B.size(), hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, 0, dA, dB, dD);
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(D.data(), dD, 256 * sizeof(int), hipMemcpyDeviceToHost));
-	(void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dD);
 	for (int i = 0; i < 256; i++)
 		if (D[i] != R[i]) return fail(SGX_EHIP, "sgx_selftest: MFMA i8 lane map mismatch at %d: %d != %d", i, D[i], R[i]);
 
@@ -261,14 +249,13 @@ extern "C" int sgx_selftest(int device)
 		xin[NT + i] = (i < 8) ? (double[]){1.0, 0.5, 2.0, 0.70710678118654746, 0.70710678118654757, 1.0000000000000002, 0.99999999999999989, 1e308}[i]
 			: (i & 1 ? std::pow(10.0, -300.0 + 600.0 * w) : 1.0 + (w - 0.5) * std::pow(10.0, -(double)(i % 16)));
 	}
-	double *dx, *dy;
-	HIPCHK(hipMalloc((void **)&dx, xin.size() * sizeof(double)));
-	HIPCHK(hipMalloc((void **)&dy, xin.size() * sizeof(double)));
+	DevBuf<double> dx, dy;
+	HIPCHK(dx.alloc(xin.size()));
+	HIPCHK(dy.alloc(xin.size()));
 	HIPCHK(hipMemcpy(dx, xin.data(), xin.size() * sizeof(double), hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(fastmath_selftest_kernel, dim3((2 * NT + 255) / 256), dim3(256), 0, 0, dx, dy, NT);
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(yout.data(), dy, yout.size() * sizeof(double), hipMemcpyDeviceToHost));
-	(void)hipFree(dx); (void)hipFree(dy);
 	for (int i = 0; i < 2 * NT; i++) {
 		const double ref = (i < NT) ? std::exp(xin[i]) : std::log(xin[i]);
 		const double got = yout[i];

@@ -26,6 +26,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -85,6 +87,7 @@ static int fail(int code, const char *fmt, ...)
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
+#include "host_mem.h"
 #include "host_state.h"
 #include "host_init.h"
 #include "host_spa.h"
