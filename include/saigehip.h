@@ -660,6 +660,43 @@ int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *packed, size_
 	double *score, double *cov, int32_t *iters /* per entry, may be NULL */);
 int sgx_skat_kmat_ms(sgx_handle *h, double *ms);
 
+/* Conditional scan on an explicit GRM: sgx_cond_set / sgx_cond_2bit with the covariances under the fitted model itself
+ * (not in the reference).  Tables, adj_e, w, tau and Sigma = tau[0] diag(1/w) + tau[1] K as for
+ * sgx_skat_kmat_2bit; with Phi^K as that entry defines it on the unit (c_1 .. c_C, j), the set's part is made once:
+ *   sgx_cond_kmat_set   installs n_cond (1 .. SGX_COND_MAX) conditioning rows given in HOST memory: their columns A_C,
+ *                       the solves Y_C = Sigma^-1 A_C and Z = Sigma^-1 X (sgx_kmat_pcg_multi_dev), E^-1 on the host.
+ *                       score_c[n_cond] = S_C, cov_cc[n_cond][n_cond] = Phi^K_CC and iters_c[n_cond] (may be NULL) equal
+ *                       sgx_skat_kmat_2bit on the set as one unit bit for bit.  The handle keeps A_C, Y_C, Z and X
+ *                       (lda (2 n_cond + 2 K) doubles on the device, lda = n_samp rounded up to 16), D_C = A_C'Z, E^-1,
+ *                       w, tau, maxiter and tol.  n_cond = 0 clears the set; a later call replaces it once everything
+ *                       queued on the handle has finished.  The set is independent of sgx_cond_set's: either may be
+ *                       installed, replaced or cleared without disturbing the other.
+ *   sgx_cond_kmat_2bit  rows in HOST memory, uploaded in the chunks of the host-buffer scans.  Per chunk of at most
+ *                       SGX_GRM_MAX_RHS rows: the adj columns, one solve of the chunk, and one kernel that makes
+ *                       a_j'[Y_C | Z], A_C'y_j and a_j'y_j of every row (2 n_cond + 1 + K sums a row) with the set's
+ *                       vectors shared in LDS by the chunk's row tiles; then on the host
+ *                         score[j] = S_j,  var[j] = C_jj - d_j E^-1 d_j',
+ *                         cov[j * n_cond + c] = 1/2 (C_jc + C_cj) - d_j E^-1 d_c'   (both orders of the last term),
+ *                       iters[j] (may be NULL) the PCG steps of row j's column.  km: the matrix the set was installed
+ *                       with.  score, var, cov and iters of a row equal sgx_skat_kmat_2bit's on the unit
+ *                       (c_1 .. c_C, j) at the set's w, tau, maxiter and tol bit for bit: every C_ef is summed in
+ *                       that entry's order (slabs of 2048 samples in slab order, no atomics), so a row's results do
+ *                       not depend on the other rows, on its position or on the set installed before.
+ * For tau[1] == 0 no product with K is made.  A row whose table holds a non-finite value stays out of the solve, gets
+ * non-finite score, var and cov and iters = 0, and leaves the other rows alone.  n_variants = 0 succeeds and does
+ * nothing.  What does not fit in device memory (besides the set: 2 x 64 lda doubles for a chunk, the solver's 8 x 64
+ * n_samp) returns SGX_ENOMEM.  SGX_EINVAL (nothing launched, both handles stay usable, an installed set stays): a NULL
+ * required buffer, n_cond > SGX_COND_MAX, km on another device than h or of another sample count, bytes_per_variant <
+ * ceil(n_samp / 4), a non-finite or non-positive w, tau[0] <= 0 or tau[1] < 0, sgx_cond_kmat_2bit with no set installed
+ * or with another km than the set's.  Both are synchronous; sgx_skat_kmat_ms gives the host milliseconds of the last
+ * call of either (rows and columns, solves, products). */
+int sgx_cond_kmat_set(sgx_handle *h, sgx_kmat *km, const uint8_t *packed_c, size_t bytes_per_variant, size_t n_cond,
+	const double *lut_c, const double *w, const double *tau, int maxiter, double tol,
+	double *score_c, double *cov_cc, int32_t *iters_c /* may be NULL */);
+int sgx_cond_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *packed, size_t bytes_per_variant, size_t n_variants,
+	const double *lut, double *score, double *var, double *cov /* [n_variants][n_cond] */,
+	int32_t *iters /* per row, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

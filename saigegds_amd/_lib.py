@@ -180,6 +180,8 @@ def _abi():
         "sgx_kmat_pcg_multi_dev": (ci, [vp, vp, vp, vp, sz, ci, ci, dp, vp, vp]),
         "sgx_skat_kmat_2bit": (ci, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
         "sgx_skat_kmat_ms": (ci, [vp, vp]),
+        "sgx_cond_kmat_set": (ci, [vp, vp, vp, sz, sz, vp, vp, vp, ci, dp, vp, vp, vp]),
+        "sgx_cond_kmat_2bit": (ci, [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]),
         "sgx_dsblock_create": (ci, [i32, ci, sz, ci, pvp]),
         "sgx_dsblock_free": (None, [vp]),
         "sgx_dsblock_load": (ci, [vp, vp, vp, sz, vp, vp, vp]),
@@ -476,6 +478,41 @@ class Scanner(_Handle):
         check(self._L.sgx_cond_2bit(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data,
                                     score.ctypes.data, var.ctypes.data, cov.ctypes.data))
         return score, var, cov[:, :c]
+
+    def cond_kmat_set(self, op, packed_c: np.ndarray, lut_c, w, tau, maxiter: int = 500, tol: float = 1e-5):
+        """Installs the conditioning set of the conditional scan on the explicit GRM of ``op`` (an ``ExplicitGrmOperator``
+        on this scanner's device; ``sgx_cond_kmat_set``): rows, tables, ``w`` and ``tau`` as for ``skat_kmat`` ->
+        (S_C [C], Phi^K_CC [C, C], iters [C]), which equal ``skat_kmat`` on the rows as one unit bit for bit.  No rows
+        clears the set; the set of ``cond_set`` is not touched."""
+        packed_c = np.ascontiguousarray(packed_c, dtype=np.uint8)
+        lut_c = np.ascontiguousarray(lut_c, dtype=np.float64).reshape(-1, 4)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        if packed_c.ndim != 2 or lut_c.shape[0] != packed_c.shape[0]:
+            raise ValueError("cond_kmat_set: one table per conditioning row")
+        if w.shape != (op.n,) or tau.shape != (2,):
+            raise ValueError("cond_kmat_set: w must have one entry per sample of the matrix and tau two entries")
+        c = packed_c.shape[0]
+        score, cov, iters = np.zeros(max(1, c)), np.zeros(max(1, c * c)), np.zeros(max(1, c), dtype=np.int32)
+        check(self._L.sgx_cond_kmat_set(self._h, op._h, packed_c.ctypes.data, packed_c.shape[1], c, lut_c.ctypes.data,
+                                        w.ctypes.data, tau.ctypes.data, int(maxiter), float(tol), score.ctypes.data,
+                                        cov.ctypes.data, iters.ctypes.data))
+        self._n_cond_kmat = c
+        return score[:c], cov[:c * c].reshape(c, c), iters[:c]
+
+    def cond_kmat(self, op, packed: np.ndarray, lut):
+        """Score, variance and covariances with the set of ``cond_kmat_set`` of every 2-bit row under the fitted model on
+        the explicit GRM (``sgx_cond_kmat_2bit``) -> (score [m], var [m], cov [m, C], iters [m]: PCG steps of the
+        row's column)."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
+        if packed.ndim != 2 or lut.shape[0] != packed.shape[0]:
+            raise ValueError("cond_kmat: one table per row")
+        m, c = packed.shape[0], getattr(self, "_n_cond_kmat", 0)
+        score, var, cov, iters = np.zeros(m), np.zeros(m), np.zeros((m, max(1, c))), np.zeros(m, dtype=np.int32)
+        check(self._L.sgx_cond_kmat_2bit(self._h, op._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data,
+                                         score.ctypes.data, var.ctypes.data, cov.ctypes.data, iters.ctypes.data))
+        return score, var, cov[:, :c], iters
 
     def cond_2bit_dev(self, packed_ptr: int, bpv: int, m: int, lut_ptr: int, score_ptr: int, var_ptr: int, cov_ptr: int):
         """``cond_2bit`` on rows, tables and results in device memory (``sgx_cond_2bit_dev``; asynchronous, sync()

@@ -19,6 +19,10 @@ resident dosage block of the aggregate drivers (``DosageBlock``): the conditioni
 their own, scanned and installed from there (``sgx_ds_block_cond_set``); then per batch of rows that fits
 ``aggregate.DS_BUDGET`` bytes one load, ``scan()``, and ``cond(flip, mean)`` (``sgx_ds_block_cond``) with the scan's own
 imputation and flip, formed from the load's counts as the SKAT driver forms them.
+
+``grm_mat=`` (hard calls only) replaces ``Phi`` by the covariance under the fitted model on the explicit GRM, ``Phi^K`` of
+``seqAssocGLMM_spaSKAT(grm_mat=)``: the set is installed with ``sgx_cond_kmat_set``, which solves its
+columns once, and per block the rows are scanned and go through ``sgx_cond_kmat_2bit`` from host memory.
 """
 from __future__ import annotations
 
@@ -32,7 +36,7 @@ from . import aggregate
 from .assoc import (BLOCK_SIZE, GenotypeSource, ScanInput, _open_source, _pretty, assemble_result,
                     check_scan_args, finish_result, open_scan_input, require_device)
 from .nullmod import ModelError, NullModel, init_nullmod, load_modobj, no_loco
-from .skat import spa_scale
+from .skat import aligned_grm_mat, spa_scale
 
 COND_MAX = 16             # SGX_COND_MAX: conditioning variants of one call
 COND_COLLINEAR = 1e-6     # V <= this fraction of Phi_jj: the variant is taken to be explained by the set (a definition:
@@ -103,6 +107,7 @@ def _tables(af, valid):
 
 
 _NO_DOSAGE = "Conditional analysis on dosage input is not implemented."
+_NO_DOSAGE_KMAT = "Conditional analysis with 'grm_mat' on dosage input is not implemented."
 
 
 def _check_set(cond_ids, out_c, valid_c):
@@ -156,6 +161,38 @@ def _scan_hard(sc, inp: ScanInput, cidx, cond_ids, thresholds):
     return res, out_c, S_C, Phi_CC
 
 
+def _scan_kmat(sc, inp: ScanInput, cidx, cond_ids, thresholds, kmat):
+    """The hard-call route on an explicit GRM: what ``_scan_hard`` returns with ``Phi^K`` for ``Phi``, and the PCG steps
+    of every row's column.  ``kmat`` = (matrix, weights, tau, maxiter, tol)."""
+    import torch
+    n_samp, n_var, read_rows = inp.n_samp, inp.n_var, inp.packed_rows
+    nb = (n_samp + 3) // 4
+    mat, w, tau, maxiter, tol = kmat
+    make_op = getattr(sc, "grm_operator", None)
+    if make_op is None:
+        from ._lib import ExplicitGrmOperator as make_op
+    C = len(cidx)
+    res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
+    n_iter = np.zeros(n_var, dtype=np.int64)
+    with make_op(mat) as op:
+        sc.set_thresholds(0.0, 0.0, 1.0, thresholds[3])
+        rows_c = np.ascontiguousarray(np.concatenate([read_rows(i, i + 1)[:, :nb] for i in cidx]))
+        out_c, valid_c = sc.scan_2bit(rows_c)
+        _check_set(cond_ids, out_c, valid_c)
+        lut_c = _tables(torch.from_numpy(out_c[:, 0].copy()), torch.ones(C, dtype=torch.bool)).numpy()
+        S_C, Phi_CC, _ = sc.cond_kmat_set(op, rows_c, lut_c, w, tau, maxiter, tol)
+        sc.set_thresholds(*thresholds)
+        for off in range(0, n_var, BLOCK_SIZE):
+            end = min(n_var, off + BLOCK_SIZE)
+            rows = np.ascontiguousarray(read_rows(off, end)[:, :nb])
+            out8, valid = sc.scan_2bit(rows)
+            lut = _tables(torch.from_numpy(out8[:, 0].copy()), torch.from_numpy(valid != 0)).numpy()
+            score, var, cov, it = sc.cond_kmat(op, rows, lut)      # a row that failed the thresholds: NaN table, no solve
+            res[off:end, :8], res[off:end, 8], res[off:end, 9], res[off:end, 10], res[off:end, 11:] = out8, valid, score, var, cov
+            n_iter[off:end] = it
+    return res, out_c, S_C, Phi_CC, n_iter
+
+
 def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds):
     """The dosage route: what ``_scan_hard`` returns, from resident dosage blocks."""
     read_rows, ds_dtype, n_samp, n_var = inp.dosage_reader(stored), inp.ds_dtype, inp.n_samp, inp.n_var
@@ -195,7 +232,8 @@ def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds):
 def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("nan"), mac: float = 10,
                           missing: float = 0.1, spa_pval: float = 0.05, var_ratio: float = float("nan"),
                           res_savefn: str = "", res_compress: str = "LZMA", verbose: bool = True, dsnode: str = "",
-                          scanner_factory=None) -> Optional[Dict[str, Any]]:
+                          scanner_factory=None, grm_mat=None, tol_pcg: float = 1e-5,
+                          maxiter_pcg: int = 500) -> Optional[Dict[str, Any]]:
     """Single-variant scan of every variant given the variants ``condition`` (not in the reference).
 
     ``condition``: 1 to 16 distinct values of the file's ``variant.id`` (of ``GenotypeSource.variant_id``); the other
@@ -208,7 +246,14 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     alike), so that without a correlated conditioning variant the conditional p-value of a row is its SPA p-value.
     Result: the columns of ``seqAssocGLMM_SPA``, then ``beta.cond``, ``SE.cond``, ``pval.cond`` (``cond_tests``;
     ``beta.cond`` refers to the alt allele like ``beta``).  A variant of the set itself, or one the set explains,
-    gets NaN there.  ``res_savefn``: ``.rds`` / ``.RData``; the ``.gds`` writer has fixed columns and is refused."""
+    gets NaN there.  ``res_savefn``: ``.rds`` / ``.RData``; the ``.gds`` writer has fixed columns and is refused.
+
+    ``grm_mat`` (what ``seqAssocGLMM_spaSKAT(grm_mat=)`` accepts; every sample of the model must be in it) replaces
+    ``Phi`` by the covariance under the fitted model itself, ``Phi^K = A' P A`` with ``Sigma = tau[0] diag(1/V) + tau[1] K``
+    (``sgx_cond_kmat_set`` / ``sgx_cond_kmat_2bit``; solves to ``tol_pcg`` in at most ``maxiter_pcg`` steps):
+    ``var_ratio`` does not enter it, the SPA scale factors are formed against ``Phi^K_jj``, ``cond_tests`` is the same
+    code, and a column ``n.iter`` holds the PCG steps of the row's column.  Refused before any row is read: dosage input
+    (``NotImplementedError``), a sample of the model missing from ``grm_mat`` (``ValueError``), a LOCO model."""
     check_scan_args(maf, mac, missing, spa_pval, var_ratio, dsnode, res_savefn, res_compress)
     if re.search(r"\.gds$", res_savefn, re.I):
         raise ValueError("The gds output has no columns for the conditional test; save to RData or RDS.")
@@ -228,6 +273,8 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     in_mem = isinstance(src, GenotypeSource)
     if dsnode != "" and in_mem and src.packed is not None:
         raise NotImplementedError(_NO_DOSAGE)
+    if grm_mat is not None and dsnode != "":
+        raise NotImplementedError(_NO_DOSAGE_KMAT)
     vid = np.asarray(src.variant_id if in_mem else src.read("variant.id"))
     where = {v: i for i, v in enumerate(vid.tolist())}
     unknown = [v for v in cond_ids if v not in where]
@@ -238,6 +285,11 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     inp = open_scan_input(src, mod, dsnode, verbose)
     if dsnode != "" and inp.kind == "packed":
         src.node(dsnode + "/data")      # a named node is a dosage node here: "$dosage_alt" is refused as the missing node it is
+    kmat_w = None
+    if grm_mat is not None:
+        if inp.kind != "packed":
+            raise NotImplementedError(_NO_DOSAGE_KMAT)
+        kmat_w = aligned_grm_mat(grm_mat, inp, mod)
     n_samp, n_var = inp.n_samp, inp.n_var
     if n_samp <= 0:
         raise ValueError("No sample in the genotypic data set!")
@@ -262,7 +314,11 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     sc = scanner_factory(mobj)
     try:
         thresholds = (float(maf), float(mac), float(missing), float(spa_pval))
-        if inp.kind == "packed":
+        n_iter = None
+        if kmat_w is not None:
+            kmat = (*kmat_w, np.asarray(mobj.tau, dtype=np.float64), int(maxiter_pcg), float(tol_pcg))
+            res, out_c, S_C, Phi_CC, n_iter = _scan_kmat(sc, inp, cidx, cond_ids, thresholds, kmat)
+        elif inp.kind == "packed":
             res, out_c, S_C, Phi_CC = _scan_hard(sc, inp, cidx, cond_ids, thresholds)
         else:
             res, out_c, S_C, Phi_CC = _scan_dosage(sc, inp, stored, cidx, cond_ids, thresholds)
@@ -281,4 +337,6 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     beta, se, p = cond_tests(S, var, cov, S_C, Phi_CC, d, d_C)
     ans["beta.cond"] = np.where(o[:, 0] > 0.5, -beta, beta)        # S is the flipped row's: back to the alt allele
     ans["SE.cond"], ans["pval.cond"] = se, p
+    if n_iter is not None:
+        ans["n.iter"] = n_iter[x]
     return finish_result(ans, res_savefn, res_compress, verbose, inp.sample_id() if res_savefn else None)

@@ -33,12 +33,12 @@ extern "C" int sgx_kmat_pcg_multi_dev(sgx_kmat *m, const double *w_dev, const do
 
 // room for n elements of what the call keeps per unit, which is the caller's to size: out of memory is SGX_ENOMEM
 template <class T>
-static int skk_room(DevBuf<T> &b, size_t n, const char *what)
+static int skk_room(DevBuf<T> &b, size_t n, const char *what, const char *who = "sgx_skat_kmat_2bit")
 {
 	const hipError_t e = b.reserve(n);
 	if (e == hipSuccess) return SGX_OK;
 	(void)hipGetLastError();
-	return fail(mem_code(e), "sgx_skat_kmat_2bit: %zu bytes for %s: %s", n * sizeof(T), what, hipGetErrorString(e));
+	return fail(mem_code(e), "%s: %zu bytes for %s: %s", who, n * sizeof(T), what, hipGetErrorString(e));
 }
 
 // out[r][c] = (vector row0 + r of L)' (vector col0 + c of R) for r < nr, c < nc (row-major, ldo apart): the tiles,
@@ -105,6 +105,39 @@ static bool skk_inverse(int K, const std::vector<double> &E, std::vector<double>
 	return true;
 }
 
+// The host's last step, Phi^K = 1/2 (C + C') - D E^-1 D', entry by entry (shared with host_cond_kmat.h).
+// q = E^-1 d for one row d [K] of D (NaN where E was singular)
+static void skk_q(int K, const std::vector<double> &Einv, bool e_ok, const double *d, double *q)
+{
+	for (int a = 0; a < K; a++) {
+		double x = 0;
+		for (int b = 0; b < K; b++) x += (e_ok ? Einv[(size_t)a * K + b] : NAN) * d[b];
+		q[a] = x;
+	}
+}
+
+// entry (j, l): c_jl, c_lj of C, rows d_j, d_l of D and their q
+static double skk_phi_entry(int K, double c_jl, double c_lj, const double *dj, const double *dl, const double *qj, const double *ql)
+{
+	double djl = 0, dlj = 0;      // both orders, so that the entry does not depend on which of the two comes first
+	for (int a = 0; a < K; a++) {
+		djl += dj[a] * ql[a];
+		dlj += dl[a] * qj[a];
+	}
+	return 0.5 * (c_jl + c_lj) - 0.5 * (djl + dlj);
+}
+
+// the rules for w [N], tau [2] and maxiter of the entries that solve with Sigma = tau[0] diag(1/w) + tau[1] K
+static int skk_sigma_args(const char *who, int N, const double *w, const double *tau, int maxiter)
+{
+	if (!(tau[0] > 0) || !(tau[1] >= 0) || !std::isfinite(tau[0]) || !std::isfinite(tau[1]))
+		return fail(SGX_EINVAL, "%s: tau = (%g, %g), need tau[0] > 0 and tau[1] >= 0", who, tau[0], tau[1]);
+	for (int i = 0; i < N; i++)
+		if (!(w[i] > 0) || !std::isfinite(w[i])) return fail(SGX_EINVAL, "%s: w[%d] = %g is not a positive finite weight", who, i, w[i]);
+	if (maxiter < 0) return fail(SGX_EINVAL, "%s: maxiter = %d", who, maxiter);
+	return SGX_OK;
+}
+
 static double skk_ms_since(const std::chrono::steady_clock::time_point &t0)
 {
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -122,13 +155,10 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	if (km->n != N) return fail(SGX_EINVAL, "%s: the matrix has %d samples, the model has %d", who, km->n, N);
 	if (bpv < (size_t)(N + 3) / 4)
 		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	if (!(tau[0] > 0) || !(tau[1] >= 0) || !std::isfinite(tau[0]) || !std::isfinite(tau[1]))
-		return fail(SGX_EINVAL, "%s: tau = (%g, %g), need tau[0] > 0 and tau[1] >= 0", who, tau[0], tau[1]);
-	for (int i = 0; i < N; i++)
-		if (!(w[i] > 0) || !std::isfinite(w[i])) return fail(SGX_EINVAL, "%s: w[%d] = %g is not a positive finite weight", who, i, w[i]);
-	if (maxiter < 0) return fail(SGX_EINVAL, "%s: maxiter = %d", who, maxiter);
+	int rc = skk_sigma_args(who, N, w, tau, maxiter);
+	if (rc) return rc;
 	if (n_units == 0) return SGX_OK;
-	int rc = skat_units_check(who, n_units, unit_ptr, var_idx, n_variants);
+	rc = skat_units_check(who, n_units, unit_ptr, var_idx, n_variants);
 	if (rc) return rc;
 	const int64_t nnz = unit_ptr[n_units];
 	if (nnz == 0) return SGX_OK;
@@ -248,20 +278,11 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 		if (rc) return rc;
 		// Phi^K = 1/2 (C + C') - D E^-1 D': the upper triangle, mirrored
 		q.assign((size_t)m * K, 0.0);
-		for (int j = 0; j < m; j++)
-			for (int a = 0; a < K; a++) {
-				double x = 0;
-				for (int b = 0; b < K; b++) x += (e_ok ? Einv[(size_t)a * K + b] : NAN) * Dm[(size_t)j * K + b];
-				q[(size_t)j * K + a] = x;
-			}
+		for (int j = 0; j < m; j++) skk_q(K, Einv, e_ok, &Dm[(size_t)j * K], &q[(size_t)j * K]);
 		for (int j = 0; j < m; j++)
 			for (int l = j; l < m; l++) {
-				double djl = 0, dlj = 0;      // both orders, so that the entry does not depend on which of the two comes first
-				for (int a = 0; a < K; a++) {
-					djl += Dm[(size_t)j * K + a] * q[(size_t)l * K + a];
-					dlj += Dm[(size_t)l * K + a] * q[(size_t)j * K + a];
-				}
-				double v = 0.5 * (Cm[(size_t)j * m + l] + Cm[(size_t)l * m + j]) - 0.5 * (djl + dlj);
+				double v = skk_phi_entry(K, Cm[(size_t)j * m + l], Cm[(size_t)l * m + j], &Dm[(size_t)j * K], &Dm[(size_t)l * K],
+					&q[(size_t)j * K], &q[(size_t)l * K]);
 				if (bad[e0 + j] || bad[e0 + l]) v = NAN;
 				phi[(size_t)j * m + l] = v;
 				phi[(size_t)l * m + j] = v;

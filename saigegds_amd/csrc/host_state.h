@@ -127,6 +127,17 @@ struct sgx_handle {
 	DevBuf<double> skk_A, skk_Y, skk_XZ, skk_cpart, skk_cs;
 	DevBuf<SkkTile> skk_tiles;
 	double skk_ms[3] = {0, 0, 0};      // columns, solve, contraction
+	// conditional scan on an explicit GRM (host_cond_kmat.h): the installed set -- its vectors [A_C | Y_C | Z | X][lda],
+	// what the host's last step needs of it (D_C = A_C'Z [n][K], q_C = E^-1 D_C', E^-1, rows with a non-finite table)
+	// and the solve's arguments; a chunk's columns and solves are in skk_A / skk_Y
+	DevBuf<double> ckm_set;
+	int ckm_n = 0;                    // 0: no set installed
+	sgx_kmat *ckm_km = nullptr;       // the operator the set was solved with (compared, not owned)
+	std::vector<double> ckm_D, ckm_q, ckm_Einv, ckm_w;
+	std::vector<uint8_t> ckm_bad;
+	bool ckm_eok = false;
+	double ckm_tau[2] = {0, 0}, ckm_tol = 0;
+	int ckm_maxiter = 0;
 	// conditional scan (host_cond.h).  Primary: the installed set -- B of kern_cond.h, the set's c' and e sums
 	DevBuf<double> cond_B;
 	DevBuf<double> cond_ce;           // [n_cond][2K]

@@ -84,6 +84,21 @@ struct SkkTile {
 	int nrow, ncol;     // 1..16; the others are computed as zeros and never read
 };
 
+// 16 samples of one tile's sum, the body of the slab loop of every kernel that makes a C_ef (skk_gram_kernel here,
+// ckm_panel_kernel of kern_cond_kmat.h): a4 / b4 are the lane's four samples i .. i + 3 (i = s + 4 h) of its row vector
+// and of its column vector, rok / cok whether the lane's row / column is inside the tile.  A tile's accumulator starts
+// at zero and takes these steps for s = slab start, + 16, ... in ascending order: that order is what fixes the bits.
+__device__ __forceinline__ void skk_step16(skat_d4 &acc, const skat_d4 &a4, const skat_d4 &b4, bool rok, bool cok, int i, int N)
+{
+#pragma unroll
+	for (int q = 0; q < 4; q++) {
+		const bool ok = i + q < N;
+		const double a = (rok && ok) ? a4[q] : 0.0;
+		const double b = (cok && ok) ? b4[q] : 0.0;
+		acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+	}
+}
+
 // grid = (tiles, sample slabs of SKK_SLAB), block = one wave.  L and R hold one vector per row, ldl and ldr doubles
 // apart: multiples of 4, at least N rounded up to 16, on 32-byte boundaries.  v_mfma_f64_16x16x4_f64 with the lane map
 // of skat_gram_kernel: lane (v = lane & 15, h = lane >> 4) gives A[row v][k = h] and B[k = h][col v].  Which sample a k
@@ -108,13 +123,7 @@ skk_gram_kernel(const double *__restrict__ L, size_t ldl, const double *__restri
 		const int i = s + 4 * hq;
 		const skat_d4 a4 = *reinterpret_cast<const skat_d4 *>(lp + i);
 		const skat_d4 b4 = *reinterpret_cast<const skat_d4 *>(rp + i);
-#pragma unroll
-		for (int q = 0; q < 4; q++) {
-			const bool ok = i + q < N;
-			const double a = (rok && ok) ? a4[q] : 0.0;
-			const double b = (cok && ok) ? b4[q] : 0.0;
-			acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-		}
+		skk_step16(acc, a4, b4, rok, cok, i, N);
 	}
 	double *o = part + ((size_t)blockIdx.y * n_tiles + blockIdx.x) * 256;
 #pragma unroll

@@ -164,11 +164,17 @@ def _unit_tests(pr, kept, S_of, phi_of):
     return Q, P
 
 
+def aligned_grm_mat(grm_mat, inp, mod):
+    """``grm_mat`` as the matrix of the scan's samples in the scan's order, and the model's weights V in that order (the
+    drivers that take ``grm_mat=``: SKAT here, the conditional scan in cond.py)."""
+    from .grm import _align_grm_mat
+    return _align_grm_mat(grm_mat, inp.sample_id()), np.ascontiguousarray(np.asarray(mod.V, dtype=np.float64)[inp.ii])
+
+
 def _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat):
     """The refusals of ``seqAssocGLMM_spaSKAT(grm_mat=)``, before any row is read -> (the opened source, the matrix of the
     scan's samples in the scan's order, the model's weights V in that order)."""
     from .assoc import _open_source, open_scan_input
-    from .grm import _align_grm_mat
     from .nullmod import load_modobj, no_loco
     if not (parallel is False or parallel is None or (isinstance(parallel, (int, np.integer)) and int(parallel) in (0, 1))):
         raise ValueError("SKAT with 'grm_mat' runs on one GPU: 'parallel' should be FALSE or 1.")
@@ -180,7 +186,7 @@ def _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat):
     inp = open_scan_input(src, mod, dsnode, False)
     if reduce_hard_calls(inp).kind != "packed":
         raise NotImplementedError("SKAT with 'grm_mat' on dosage input is not implemented.")
-    return src, _align_grm_mat(grm_mat, inp.sample_id()), np.ascontiguousarray(np.asarray(mod.V, dtype=np.float64)[inp.ii])
+    return (src, *aligned_grm_mat(grm_mat, inp, mod))
 
 
 def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: str = "", spa_pval: float = 0.05,
