@@ -697,6 +697,47 @@ int sgx_cond_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *packed, size_
 	const double *lut, double *score, double *var, double *cov /* [n_variants][n_cond] */,
 	int32_t *iters /* per row, may be NULL */);
 
+/* The three entries above on the dosage rows of a resident sgx_dsblock (imputed data; not in the reference, DESIGN.md
+ * 8i).  They stand here, not beside sgx_ds_block_skat / sgx_ds_block_cond*, because they take an sgx_kmat.  Units,
+ * indices and the dosage vector of an entry are sgx_ds_block_skat's,
+ *     G_e(i) = present ? (flip[e] ? 2 - x : x) : mean[e],    x = row var_idx[e] at sample i
+ * (u8 rows: 0xFF is missing; f64 and i32 blocks hold doubles: a non-finite value is missing; mean[e] arrives flipped);
+ * w, tau, Sigma, Phi^K, the layouts, tau[1] == 0, the chunks of SGX_GRM_MAX_RHS columns, the device memory and
+ * sgx_skat_kmat_ms are those of the 2-bit entries: only the kernels that make the columns adj_e and the sums c', s of
+ * an entry differ.  They read a row once for all K + 1 sums, each sum in the order of the 2-bit column kernel (slabs
+ * of 8192 samples cut by n_samp alone and added in slab order; in a slab thread t of 256 takes the 16-sample groups
+ * t, t + 256, ... and adds a group's samples in ascending order by fma; then the block's fixed tree): no atomics, and a
+ * row of hard calls gives score, cov / var and iters of its 2-bit form with the table {0, 1, 2, mean} (flipped:
+ * {2, 1, 0, mean}) bit for bit.  An entry's column depends on its row, its flip / mean and n_samp only.
+ *   sgx_ds_block_skat_kmat      sgx_skat_kmat_2bit for units over the loaded rows.
+ *   sgx_ds_block_cond_kmat_set  sgx_cond_kmat_set for n_cond (1 .. SGX_COND_MAX) loaded rows var_idx[c].  The set lands
+ *                               in the handle state sgx_cond_kmat_set fills: it outlives the block's next load and
+ *                               serves sgx_cond_kmat_2bit as well; n_cond = 0 clears it (b and the buffers are not
+ *                               looked at then).
+ *   sgx_ds_block_cond_kmat      sgx_cond_kmat_2bit for ALL loaded rows of the block, flip[j] / mean[j] per loaded row;
+ *                               HOST buffers of that many rows.  A row's results equal sgx_ds_block_skat_kmat's on the
+ *                               unit (c_1 .. c_C, j) bit for bit.
+ * An entry whose mean is not finite is treated like a 2-bit entry with a non-finite table -- WHETHER OR NOT a sample of
+ * its row is missing (sgx_ds_block_skat looks at the mean only where it is used): its column is zeros and takes no
+ * solve step, its score and its row and column of cov (var, cov of a scanned row) are non-finite at the end, its
+ * iters 0, and the other entries of its unit keep their bits.
+ * Nothing crosses PCIe but the entries' tables, the weights and the results.  SGX_EINVAL (nothing launched, the handles
+ * stay usable, an installed set stays): a NULL handle, block or required buffer, nothing loaded, an index outside the
+ * loaded rows, a unit above SGX_SKAT_MAX_VARIANTS, n_cond > SGX_COND_MAX, a twin handle, block / handle / matrix on
+ * different devices or of different sample counts, a non-finite or non-positive w, tau[0] <= 0 or tau[1] < 0,
+ * maxiter < 0, sgx_ds_block_cond_kmat with no set installed or with another km than the set's.  What does not fit in
+ * device memory returns SGX_ENOMEM.  All three are synchronous. */
+int sgx_ds_block_skat_kmat(sgx_handle *h, sgx_kmat *km, const sgx_dsblock *b, size_t n_units,
+	const int64_t *unit_ptr, const int32_t *var_idx, const uint8_t *flip, const double *mean,
+	const double *w, const double *tau, int maxiter, double tol,
+	double *score, double *cov, int32_t *iters /* per entry, may be NULL */);
+int sgx_ds_block_cond_kmat_set(sgx_handle *h, sgx_kmat *km, const sgx_dsblock *b, size_t n_cond,
+	const int32_t *var_idx, const uint8_t *flip, const double *mean, const double *w, const double *tau,
+	int maxiter, double tol, double *score_c, double *cov_cc, int32_t *iters_c /* may be NULL */);
+int sgx_ds_block_cond_kmat(sgx_handle *h, sgx_kmat *km, const sgx_dsblock *b, const uint8_t *flip,
+	const double *mean, double *score, double *var, double *cov /* [rows loaded][n_cond] */,
+	int32_t *iters /* per row, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,9 @@ def _abi():
         "sgx_cond_2bit_dev": (ci, [vp, vp, sz, sz, vp, vp, vp, vp]),
         "sgx_ds_block_cond_set": (ci, [vp, vp, sz, vp, vp, vp, vp, vp]),
         "sgx_ds_block_cond": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "sgx_ds_block_skat_kmat": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
+        "sgx_ds_block_cond_kmat_set": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
+        "sgx_ds_block_cond_kmat": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
 
 
@@ -725,6 +728,67 @@ class DosageBlock(_Handle):
         check(self._L.sgx_ds_block_cond(self._sc._h, self._b, flip.ctypes.data, mean.ctypes.data, score.ctypes.data,
                                         var.ctypes.data, cov.ctypes.data))
         return score[:m], var[:m], cov[:m * c].reshape(m, c)
+
+    def _sigma_args(self, what: str, op, w, tau):
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        if w.shape != (op.n,) or tau.shape != (2,):
+            raise ValueError(f"{what}: w must have one entry per sample of the matrix and tau two entries")
+        return w, tau
+
+    def skat_kmat(self, op, unit_ptr, var_idx, flip, mean, w, tau, maxiter: int = 500, tol: float = 1e-5):
+        """``skat`` with the covariance under the fitted model on the explicit GRM of ``op`` (an ``ExplicitGrmOperator``
+        on the scanner's device), ``Phi^K = A' P A`` as ``Scanner.skat_kmat`` defines it (``sgx_ds_block_skat_kmat``) ->
+        (score [entries], cov: per unit an [m, m] symmetric matrix, iters [entries]: PCG steps of every entry's solve).
+        An entry whose mean is not finite gets non-finite results, whether or not a sample of its row is missing."""
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        w, tau = self._sigma_args("DosageBlock.skat_kmat", op, w, tau)
+        unit_ptr, var_idx, n_units, sizes, offs = _unit_args("DosageBlock.skat_kmat", unit_ptr, var_idx,
+                                                             [(flip, ()), (mean, ())])
+        score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
+        iters = np.zeros(max(1, var_idx.size), dtype=np.int32)
+        if var_idx.size:
+            check(self._L.sgx_ds_block_skat_kmat(self._sc._h, op._h, self._b, n_units, unit_ptr.ctypes.data,
+                                                 var_idx.ctypes.data, flip.ctypes.data, mean.ctypes.data, w.ctypes.data,
+                                                 tau.ctypes.data, int(maxiter), float(tol), score.ctypes.data,
+                                                 cov.ctypes.data, iters.ctypes.data))
+        return score[:var_idx.size], _unit_matrices(cov, sizes, offs), iters[:var_idx.size]
+
+    def cond_kmat_set(self, op, var_idx, flip, mean, w, tau, maxiter: int = 500, tol: float = 1e-5):
+        """Installs the conditioning set of the conditional scan on the explicit GRM of ``op`` from resident rows
+        (``sgx_ds_block_cond_kmat_set``): rows ``var_idx`` with ``flip`` / ``mean`` as for ``skat`` -> (S_C [C],
+        Phi^K_CC [C, C], iters [C]), equal to ``skat_kmat`` on them as one unit bit for bit.  The scanner keeps the set
+        (the one ``Scanner.cond_kmat_set`` fills) beyond the block's next load; no row clears it."""
+        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        if var_idx.ndim != 1 or flip.shape != var_idx.shape or mean.shape != var_idx.shape:
+            raise ValueError("DosageBlock.cond_kmat_set: inconsistent table shapes")
+        w, tau = self._sigma_args("DosageBlock.cond_kmat_set", op, w, tau)
+        c = var_idx.size
+        score, cov, iters = np.zeros(max(1, c)), np.zeros(max(1, c * c)), np.zeros(max(1, c), dtype=np.int32)
+        check(self._L.sgx_ds_block_cond_kmat_set(self._sc._h, op._h, self._b, c, var_idx.ctypes.data, flip.ctypes.data,
+                                                 mean.ctypes.data, w.ctypes.data, tau.ctypes.data, int(maxiter),
+                                                 float(tol), score.ctypes.data, cov.ctypes.data, iters.ctypes.data))
+        self._sc._n_cond_kmat = c
+        return score[:c], cov[:c * c].reshape(c, c), iters[:c]
+
+    def cond_kmat(self, op, flip, mean):
+        """Score, variance and covariances with the set of ``cond_kmat_set`` of every resident row under the fitted model
+        on the explicit GRM (``flip`` / ``mean`` per resident row; ``sgx_ds_block_cond_kmat``) -> (score [m], var [m],
+        cov [m, C], iters [m]: PCG steps of the row's column), as ``Scanner.cond_kmat``."""
+        m = self.n_variants
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        if flip.shape != (m,) or mean.shape != (m,):
+            raise ValueError("DosageBlock.cond_kmat: one flip and one mean per resident row")
+        c = int(getattr(self._sc, "_n_cond_kmat", 0))
+        score, var, cov = np.zeros(max(1, m)), np.zeros(max(1, m)), np.zeros(max(1, m * c))
+        iters = np.zeros(max(1, m), dtype=np.int32)
+        check(self._L.sgx_ds_block_cond_kmat(self._sc._h, op._h, self._b, flip.ctypes.data, mean.ctypes.data,
+                                             score.ctypes.data, var.ctypes.data, cov.ctypes.data, iters.ctypes.data))
+        return score[:m], var[:m], cov[:m * c].reshape(m, c), iters[:m]
 
 
 class PinnedBuffer:

@@ -276,11 +276,17 @@ def _packed_rows(pr: _Prepared, used, kmat=None):
     yield SimpleNamespace(batches=[list(range(len(pr.index)))], load=load, burden=burden, skat=skat)
 
 
+_NO_DOSAGE_KMAT = "SKAT with 'grm_mat' on dosage input is not implemented."
+
+
 @contextlib.contextmanager
-def _dosage_rows(pr: _Prepared, used, stored, budget):
+def _dosage_rows(pr: _Prepared, used, stored, budget, kmat=None):
     """Dosage rows: batches of consecutive units whose distinct variants fit ``budget`` bytes of resident rows (a unit
     larger than that is a batch of its own); one ``DosageBlock`` of the largest batch's size, one upload per batch.  A
-    variant that two batches share (sliding windows) is loaded in both.  ``skat`` is None where the block has none."""
+    variant that two batches share (sliding windows) is loaded in both.  ``skat`` is None where the block has none.
+    ``kmat`` (as for ``_packed_rows``): ``skat`` is the block's ``skat_kmat`` (``sgx_ds_block_skat_kmat``) on one operator
+    for all batches -- the scanner's ``grm_operator`` where it has one (the tests' stand-ins); a scanner without
+    ``dosage_block`` or a block without ``skat_kmat`` is refused before any row is read."""
     read_rows, dtype = pr.inp.dosage_reader(stored), pr.inp.ds_dtype
     row_bytes = ds_row_bytes(dtype, pr.sm.n)
     batches, cur, seen = [], [], set()
@@ -293,7 +299,11 @@ def _dosage_rows(pr: _Prepared, used, stored, budget):
         seen |= new
     batches.append(cur)
     cap = max(np.unique(np.concatenate([pr.index[u] for u in bt])).size for bt in batches)
-    with pr.sc.dosage_block(dtype, cap) as blk:
+    if kmat is not None and not hasattr(pr.sc, "dosage_block"):
+        raise NotImplementedError(_NO_DOSAGE_KMAT)
+    with contextlib.ExitStack() as stack:
+        blk = stack.enter_context(pr.sc.dosage_block(dtype, cap))
+
         def load(bv):
             n, s, st = load_rows(blk, read_rows(used[bv] - 1))
             return (n, s, st, *blk.scan())
@@ -302,7 +312,19 @@ def _dosage_rows(pr: _Prepared, used, stored, budget):
             with np.errstate(invalid="ignore"):
                 return blk.burden(grp_ptr, var_idx, flip, W, mean[:, None] * W)
 
-        skat = (lambda *a: (*blk.skat(*a), None)) if hasattr(blk, "skat") else None
+        if kmat is None:
+            skat = (lambda *a: (*blk.skat(*a), None)) if hasattr(blk, "skat") else None
+        else:
+            if not hasattr(blk, "skat_kmat"):
+                raise NotImplementedError(_NO_DOSAGE_KMAT)
+            mat, w, maxiter, tol = kmat
+            make_op = getattr(pr.sc, "grm_operator", None)
+            if make_op is None:
+                from ._lib import ExplicitGrmOperator as make_op
+            op = stack.enter_context(make_op(mat))
+
+            def skat(*a):
+                return blk.skat_kmat(op, *a, w, pr.sm.tau, maxiter=maxiter, tol=tol)
         yield SimpleNamespace(batches=batches, load=load, burden=burden, skat=skat)
 
 
@@ -425,7 +447,8 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
     if inp.kind == "packed":
         pr.backend = _packed_rows(pr, used, kmat)
     else:
-        pr.backend = _dosage_rows(pr, used, inp.stored_ok(scanner_factory), DS_BUDGET if ds_budget is None else ds_budget)
+        pr.backend = _dosage_rows(pr, used, inp.stored_ok(scanner_factory), DS_BUDGET if ds_budget is None else ds_budget,
+                                  kmat)
     return pr
 
 

@@ -20,12 +20,15 @@ their own, scanned and installed from there (``sgx_ds_block_cond_set``); then pe
 ``aggregate.DS_BUDGET`` bytes one load, ``scan()``, and ``cond(flip, mean)`` (``sgx_ds_block_cond``) with the scan's own
 imputation and flip, formed from the load's counts as the SKAT driver forms them.
 
-``grm_mat=`` (hard calls only) replaces ``Phi`` by the covariance under the fitted model on the explicit GRM, ``Phi^K`` of
+``grm_mat=`` replaces ``Phi`` by the covariance under the fitted model on the explicit GRM, ``Phi^K`` of
 ``seqAssocGLMM_spaSKAT(grm_mat=)``: the set is installed with ``sgx_cond_kmat_set``, which solves its
-columns once, and per block the rows are scanned and go through ``sgx_cond_kmat_2bit`` from host memory.
+columns once, and per block the rows are scanned and go through ``sgx_cond_kmat_2bit`` from host memory.  On dosage
+input the same two steps are the block's ``cond_kmat_set`` and ``cond_kmat``
+(``sgx_ds_block_cond_kmat_set`` / ``sgx_ds_block_cond_kmat``) on the resident rows.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import re
 from typing import Any, Dict, Optional
@@ -193,40 +196,60 @@ def _scan_kmat(sc, inp: ScanInput, cidx, cond_ids, thresholds, kmat):
     return res, out_c, S_C, Phi_CC, n_iter
 
 
-def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds):
-    """The dosage route: what ``_scan_hard`` returns, from resident dosage blocks."""
+def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds, kmat=None):
+    """The dosage route: what ``_scan_hard`` returns, from resident dosage blocks -- with ``kmat`` (as for ``_scan_kmat``)
+    what ``_scan_kmat`` returns: the set by the block's ``cond_kmat_set``, the rows by its ``cond_kmat``, on one operator
+    (the scanner's ``grm_operator`` where it has one).  A row that failed the thresholds gets a NaN mean there: no solve."""
     read_rows, ds_dtype, n_samp, n_var = inp.dosage_reader(stored), inp.ds_dtype, inp.n_samp, inp.n_var
 
     def load(blk, v0):
         return aggregate.load_rows(blk, read_rows(v0))
 
+    refusal = _NO_DOSAGE if kmat is None else _NO_DOSAGE_KMAT
     make = getattr(sc, "dosage_block", None)
     if make is None:
-        raise NotImplementedError(_NO_DOSAGE)
+        raise NotImplementedError(refusal)
     C = len(cidx)
     order = np.argsort(cidx)                           # the readers take ascending indices
     rank = np.argsort(order).astype(np.int32)          # conditioning variant k is row rank[k] of its block
-    with make(ds_dtype, C) as blk:
-        if not hasattr(blk, "cond"):
-            raise NotImplementedError(_NO_DOSAGE)
+    n_iter = np.zeros(n_var, dtype=np.int64)
+    with contextlib.ExitStack() as stack:
+        blk = stack.enter_context(make(ds_dtype, C))
+        if not hasattr(blk, "cond" if kmat is None else "cond_kmat"):
+            raise NotImplementedError(refusal)
+        op = None
+        if kmat is not None:
+            mat, w, tau, maxiter, tol = kmat
+            make_op = getattr(sc, "grm_operator", None)
+            if make_op is None:
+                from ._lib import ExplicitGrmOperator as make_op
+            op = stack.enter_context(make_op(mat))
         sc.set_thresholds(0.0, 0.0, 1.0, thresholds[3])
         n, s, _ = load(blk, np.asarray(cidx, dtype=np.int64)[order])
         out_c, valid_c = blk.scan()
         out_c, valid_c = out_c[rank], valid_c[rank]
         _check_set(cond_ids, out_c, valid_c)
         fl, mean = aggregate.flip_mean(n, s)
-        S_C, Phi_CC = blk.cond_set(rank, fl[rank], mean[rank])
+        if kmat is None:
+            S_C, Phi_CC = blk.cond_set(rank, fl[rank], mean[rank])
+        else:
+            S_C, Phi_CC, _ = blk.cond_kmat_set(op, rank, fl[rank], mean[rank], w, tau, maxiter, tol)
         sc.set_thresholds(*thresholds)
-    per = int(max(1, min(n_var, aggregate.DS_BUDGET // aggregate.ds_row_bytes(ds_dtype, n_samp))))
-    res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
-    with make(ds_dtype, per) as blk:
+        blk.close()                                    # the set is the scanner's: the rows' block takes the memory
+        per = int(max(1, min(n_var, aggregate.DS_BUDGET // aggregate.ds_row_bytes(ds_dtype, n_samp))))
+        res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
+        blk = stack.enter_context(make(ds_dtype, per))
         for off in range(0, n_var, per):
             end = min(n_var, off + per)
             n, s, _ = load(blk, np.arange(off, end, dtype=np.int64))      # the one upload
             out8, valid = blk.scan()
-            score, var, cov = blk.cond(*aggregate.flip_mean(n, s))
+            fl, mean = aggregate.flip_mean(n, s)
+            if kmat is None:
+                score, var, cov = blk.cond(fl, mean)
+            else:
+                score, var, cov, n_iter[off:end] = blk.cond_kmat(op, fl, np.where(valid != 0, mean, np.nan))
             res[off:end, :8], res[off:end, 8], res[off:end, 9], res[off:end, 10], res[off:end, 11:] = out8, valid, score, var, cov
-    return res, out_c, S_C, Phi_CC
+    return (res, out_c, S_C, Phi_CC) if kmat is None else (res, out_c, S_C, Phi_CC, n_iter)
 
 
 def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("nan"), mac: float = 10,
@@ -252,7 +275,9 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     ``Phi`` by the covariance under the fitted model itself, ``Phi^K = A' P A`` with ``Sigma = tau[0] diag(1/V) + tau[1] K``
     (``sgx_cond_kmat_set`` / ``sgx_cond_kmat_2bit``; solves to ``tol_pcg`` in at most ``maxiter_pcg`` steps):
     ``var_ratio`` does not enter it, the SPA scale factors are formed against ``Phi^K_jj``, ``cond_tests`` is the same
-    code, and a column ``n.iter`` holds the PCG steps of the row's column.  Refused before any row is read: dosage input
+    code, and a column ``n.iter`` holds the PCG steps of the row's column.  Dosage input takes
+    ``sgx_ds_block_cond_kmat_set`` / ``sgx_ds_block_cond_kmat`` on the resident rows.  Refused before any
+    row is read: dosage input on a scanner without ``dosage_block`` or whose block has no ``cond_kmat``
     (``NotImplementedError``), a sample of the model missing from ``grm_mat`` (``ValueError``), a LOCO model."""
     check_scan_args(maf, mac, missing, spa_pval, var_ratio, dsnode, res_savefn, res_compress)
     if re.search(r"\.gds$", res_savefn, re.I):
@@ -273,8 +298,6 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     in_mem = isinstance(src, GenotypeSource)
     if dsnode != "" and in_mem and src.packed is not None:
         raise NotImplementedError(_NO_DOSAGE)
-    if grm_mat is not None and dsnode != "":
-        raise NotImplementedError(_NO_DOSAGE_KMAT)
     vid = np.asarray(src.variant_id if in_mem else src.read("variant.id"))
     where = {v: i for i, v in enumerate(vid.tolist())}
     unknown = [v for v in cond_ids if v not in where]
@@ -287,7 +310,8 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
         src.node(dsnode + "/data")      # a named node is a dosage node here: "$dosage_alt" is refused as the missing node it is
     kmat_w = None
     if grm_mat is not None:
-        if inp.kind != "packed":
+        # dosage input needs a scanner with dosage blocks: a factory that is a class without them is refused unmade
+        if inp.kind != "packed" and isinstance(scanner_factory, type) and not hasattr(scanner_factory, "dosage_block"):
             raise NotImplementedError(_NO_DOSAGE_KMAT)
         kmat_w = aligned_grm_mat(grm_mat, inp, mod)
     n_samp, n_var = inp.n_samp, inp.n_var
@@ -317,7 +341,10 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
         n_iter = None
         if kmat_w is not None:
             kmat = (*kmat_w, np.asarray(mobj.tau, dtype=np.float64), int(maxiter_pcg), float(tol_pcg))
-            res, out_c, S_C, Phi_CC, n_iter = _scan_kmat(sc, inp, cidx, cond_ids, thresholds, kmat)
+            if inp.kind == "packed":
+                res, out_c, S_C, Phi_CC, n_iter = _scan_kmat(sc, inp, cidx, cond_ids, thresholds, kmat)
+            else:
+                res, out_c, S_C, Phi_CC, n_iter = _scan_dosage(sc, inp, stored, cidx, cond_ids, thresholds, kmat)
         elif inp.kind == "packed":
             res, out_c, S_C, Phi_CC = _scan_hard(sc, inp, cidx, cond_ids, thresholds)
         else:

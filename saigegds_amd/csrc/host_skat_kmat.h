@@ -143,75 +143,118 @@ static double skk_ms_since(const std::chrono::steady_clock::time_point &t0)
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *packed, size_t bpv, size_t n_variants,
-	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut, const double *w,
-	const double *tau, int maxiter, double tol, double *score, double *cov, int32_t *iters)
+// Where the columns of a call's entries come from -- the only thing in which the 2-bit entries and the entries on a
+// resident dosage block (host_kmat_ds.h) differ.  Entry e of the source is row idx[e] of its rows, with its table
+// lut[e][4] (2-bit rows on the device, dbpv bytes apart) or its flip[e] / mean[e] (dosage rows, N elements apart:
+// kern_kmat_ds.h; flip[e] & SKK_DS_ZERO: a column of zeros).  All pointers are device pointers.
+struct SkkSrc {
+	const int *idx = nullptr;
+	const uint8_t *rows = nullptr; size_t dbpv = 0; const double *lut = nullptr;             // 2-bit rows
+	const void *ds = nullptr; int ds_dtype = 0; const uint8_t *flip = nullptr; const double *mean = nullptr;   // dosage rows
+	// the source of the entries from e on
+	SkkSrc from(size_t e) const
+	{
+		SkkSrc s = *this;
+		s.idx += e;
+		if (ds) { s.flip += e; s.mean += e; } else s.lut += 4 * e;
+		return s;
+	}
+};
+
+template <typename T, int NS>
+static void skk_launch_colsum_ds(sgx_handle *h, const SkkSrc &src, int ncslab, int m)
 {
-	const char *who = "sgx_skat_kmat_2bit";
-	if (!h || !km) return fail(SGX_EINVAL, "%s: NULL handle", who);
-	if (!packed || !unit_ptr || !var_idx || !lut || !w || !tau || !score || !cov) return fail(SGX_EINVAL, "%s: NULL buffer", who);
+	hipLaunchKernelGGL((skk_colsum_ds_kernel<T, NS>), dim3((unsigned)ncslab, (unsigned)m), dim3(256), 0, h->stream,
+		(const T *)src.ds, h->md.N, src.idx, src.flip, src.mean, h->md.F, h->md.P, h->md.K, h->skk_cpart);
+}
+
+// the accumulators a thread of skk_colsum_ds_kernel holds: the smallest of 4, 9, 17 that takes the K + 1 sums
+template <typename T>
+static void skk_colsum_ds(sgx_handle *h, const SkkSrc &src, int ncslab, int m)
+{
+	const int C1 = h->md.K + 1;
+	if (C1 <= 4) skk_launch_colsum_ds<T, 4>(h, src, ncslab, m);
+	else if (C1 <= 9) skk_launch_colsum_ds<T, 9>(h, src, ncslab, m);
+	else skk_launch_colsum_ds<T, 17>(h, src, ncslab, m);
+}
+static_assert(KMAX + 1 <= 17, "skk_colsum_ds: K + 1 sums");
+
+// the first m entries of `src` -> their adj columns A [m][lda] and score statistics: the column sums per slab
+// (skk_cpart), the slabs added (skk_cs), the columns, and S = s - S_a . c' on the host.  Synchronous.
+static int skk_columns(sgx_handle *h, const SkkSrc &src, int m, double *A, size_t lda, double *score)
+{
 	const int N = h->md.N, K = h->md.K, P = h->md.P, C1 = K + 1;
-	if (km->device != h->device) return fail(SGX_EINVAL, "%s: the matrix is on device %d, the handle on device %d", who, km->device, h->device);
-	if (km->n != N) return fail(SGX_EINVAL, "%s: the matrix has %d samples, the model has %d", who, km->n, N);
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	int rc = skk_sigma_args(who, N, w, tau, maxiter);
-	if (rc) return rc;
-	if (n_units == 0) return SGX_OK;
-	rc = skat_units_check(who, n_units, unit_ptr, var_idx, n_variants);
-	if (rc) return rc;
-	const int64_t nnz = unit_ptr[n_units];
-	if (nnz == 0) return SGX_OK;
-	rc = set_dev(h);
-	if (rc) return rc;
-	rc = sync_lane(h);
-	if (rc) return rc;
-	h->last_issued = h;
+	const int ndw = (N + 15) >> 4, ncslab = (ndw + SKK_CSLAB_DW - 1) / SKK_CSLAB_DW;
+	const unsigned gl = (unsigned)((lda + 255) / 256);
 	hipStream_t st = h->stream;
-	auto t_col = std::chrono::steady_clock::now();
-	h->skk_ms[0] = h->skk_ms[1] = h->skk_ms[2] = 0;
-
-	// an entry with a non-finite table stays out of the sums and the solve (a table of zeros: a right-hand side of
-	// zeros takes no step) and gets its non-finite results at the end
-	std::vector<double> lut_ok(lut, lut + (size_t)nnz * 4);
-	std::vector<uint8_t> bad((size_t)nnz, 0);
-	int64_t m_max = 0;
-	for (int64_t e = 0; e < nnz; e++) {
-		for (int c = 0; c < 4; c++) if (!std::isfinite(lut[4 * e + c])) bad[e] = 1;
-		if (bad[e]) for (int c = 0; c < 4; c++) lut_ok[4 * e + c] = 0;
+	if (!src.ds)
+		hipLaunchKernelGGL(skk_colsum_kernel, dim3((unsigned)ncslab, (unsigned)m), dim3(256), 0, st, src.rows, src.dbpv, N,
+			src.idx, src.lut, h->md.F, P, K, h->skk_cpart);
+	else if (src.ds_dtype == SGX_DS_U8) skk_colsum_ds<uint8_t>(h, src, ncslab, m);
+	else skk_colsum_ds<double>(h, src, ncslab, m);
+	hipLaunchKernelGGL(skk_colfin_kernel, dim3((unsigned)(((size_t)m * C1 + 255) / 256)), dim3(256), 0, st, h->skk_cpart,
+		(size_t)m * C1, ncslab, C1, h->skk_cs);
+	if (!src.ds)
+		hipLaunchKernelGGL(skk_adj_kernel, dim3(gl, (unsigned)m), dim3(256), 0, st, src.rows, src.dbpv, N, src.idx, src.lut,
+			h->md.X, K, h->skk_cs, A, lda);
+	else if (src.ds_dtype == SGX_DS_U8)
+		hipLaunchKernelGGL((skk_adj_ds_kernel<uint8_t>), dim3(gl, (unsigned)m), dim3(256), 0, st, (const uint8_t *)src.ds, N,
+			src.idx, src.flip, src.mean, h->md.X, K, h->skk_cs, A, lda);
+	else
+		hipLaunchKernelGGL((skk_adj_ds_kernel<double>), dim3(gl, (unsigned)m), dim3(256), 0, st, (const double *)src.ds, N,
+			src.idx, src.flip, src.mean, h->md.X, K, h->skk_cs, A, lda);
+	HIPCHK(hipGetLastError());
+	std::vector<double> cs((size_t)m * C1);
+	HIPCHK(hipMemcpyAsync(cs.data(), h->skk_cs, cs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	for (int j = 0; j < m; j++) {
+		const double *cj = &cs[(size_t)j * C1];
+		double sa = 0;
+		for (int a = 0; a < K; a++) sa += h->md.S_a[a] * cj[a];
+		const double S = cj[K] - sa;
+		score[j] = h->md.quant ? S / h->md.tau0 : S;
 	}
-	for (size_t u = 0; u < n_units; u++) m_max = std::max(m_max, unit_ptr[u + 1] - unit_ptr[u]);
+	return SGX_OK;
+}
 
-	// device copies: the rows (dword stride) in the host-row pipeline's chunks, then entries and tables
-	const int ndw = (N + 15) >> 4;
+// what the arguments of the entries on an explicit GRM have in common: matrix and handle on one device, of one size
+static int skk_km_check(const char *who, const sgx_handle *h, const sgx_kmat *km)
+{
+	if (km->device != h->device) return fail(SGX_EINVAL, "%s: the matrix is on device %d, the handle on device %d", who, km->device, h->device);
+	if (km->n != h->md.N) return fail(SGX_EINVAL, "%s: the matrix has %d samples, the model has %d", who, km->n, h->md.N);
+	return SGX_OK;
+}
+
+// device room of the unit loop: units of at most m_max entries
+static int skk_unit_room(const char *who, sgx_handle *h, size_t m_max)
+{
+	const int N = h->md.N, K = h->md.K, C1 = K + 1;
+	const int ndw = (N + 15) >> 4, ncslab = (ndw + SKK_CSLAB_DW - 1) / SKK_CSLAB_DW;
 	const size_t lda = (size_t)ndw * 16;
-	const size_t dbpv = (size_t)ndw * 4;
-	const size_t o_idx = (n_variants * dbpv + 15) & ~(size_t)15;
-	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
-	const size_t need = o_lut + (size_t)nnz * 4 * sizeof(double);
-	const int ncslab = (ndw + SKK_CSLAB_DW - 1) / SKK_CSLAB_DW;
-	rc = skk_room(h->stage_pk, need, "the rows");
-	if (!rc) rc = skk_room(h->skk_XZ, (size_t)2 * K * lda, "the covariate columns");
-	if (!rc) rc = skk_room(h->skk_A, (size_t)m_max * lda, "a unit's columns");
-	if (!rc) rc = skk_room(h->skk_Y, (size_t)m_max * lda, "a unit's solves");
-	if (!rc) rc = skk_room(h->skk_cpart, (size_t)m_max * ncslab * C1, "the column sums");
-	if (!rc) rc = skk_room(h->skk_cs, (size_t)m_max * C1, "the column sums");
-	if (rc) return rc;
-	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
-	for (size_t off = 0; off < n_variants; off += rchunk) {
-		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), st);
-		if (rc) return rc;
-	}
-	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut_ok.data(), (size_t)nnz * 4 * sizeof(double), hipMemcpyHostToDevice, st));
-	const int *d_idx = reinterpret_cast<const int *>(h->stage_pk + o_idx);
-	const double *d_lut = reinterpret_cast<const double *>(h->stage_pk + o_lut);
+	int rc = skk_room(h->skk_XZ, (size_t)2 * K * lda, "the covariate columns", who);
+	if (!rc) rc = skk_room(h->skk_A, m_max * lda, "a unit's columns", who);
+	if (!rc) rc = skk_room(h->skk_Y, m_max * lda, "a unit's solves", who);
+	if (!rc) rc = skk_room(h->skk_cpart, m_max * ncslab * C1, "the column sums", who);
+	if (!rc) rc = skk_room(h->skk_cs, m_max * C1, "the column sums", who);
+	return rc;
+}
+
+// The flow of a SKAT call on an explicit GRM once its source is on the device (queued on the handle's stream): the
+// covariate columns, Z = Sigma^-1 X and E = X'Z once, then per unit the columns, the solves in chunks of
+// SGX_GRM_MAX_RHS, the products and the host's last step.  bad [entries]: entries whose column is zeros and whose
+// results are non-finite at the end; t_col: when the call began (skk_ms[0]).
+static int skk_units(const char *who, sgx_handle *h, sgx_kmat *km, const SkkSrc &src, size_t n_units, const int64_t *unit_ptr,
+	const std::vector<uint8_t> &bad, size_t m_max, const double *w, const double *tau, int maxiter, double tol,
+	std::chrono::steady_clock::time_point t_col, double *score, double *cov, int32_t *iters)
+{
+	const int N = h->md.N, K = h->md.K;
+	const size_t lda = (size_t)((N + 15) >> 4) * 16;
+	hipStream_t st = h->stream;
 	double *Xc = h->skk_XZ, *Z = h->skk_XZ + (size_t)K * lda;
 	const unsigned gl = (unsigned)((lda + 255) / 256);
 	hipLaunchKernelGGL(skk_xcols_kernel, dim3(gl, (unsigned)K), dim3(256), 0, st, h->md.X, N, K, Xc, lda);
 	HIPCHK(hipMemsetAsync(Z, 0, (size_t)K * lda * sizeof(double), st));
-	HIPCHK(hipMemsetAsync(h->skk_Y, 0, (size_t)m_max * lda * sizeof(double), st));
+	HIPCHK(hipMemsetAsync(h->skk_Y, 0, m_max * lda * sizeof(double), st));
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(st));
 	h->skk_ms[0] += skk_ms_since(t_col);
@@ -220,7 +263,7 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	auto t_sol = std::chrono::steady_clock::now();
 	HIPCHK(hipMemcpyAsync(km->pw.w, w, (size_t)N * sizeof(double), hipMemcpyHostToDevice, km->stream));
 	std::vector<int> it_z((size_t)K), it_u;
-	rc = kmat_pcg_dev(who, km, km->pw.w, tau, Xc, lda, K, maxiter, tol, Z, it_z.data());
+	int rc = kmat_pcg_dev(who, km, km->pw.w, tau, Xc, lda, K, maxiter, tol, Z, it_z.data());
 	if (rc) return rc;
 	h->skk_ms[1] += skk_ms_since(t_sol);
 	auto t_con = std::chrono::steady_clock::now();
@@ -230,7 +273,7 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	const bool e_ok = skk_inverse(K, E, Einv);
 	h->skk_ms[2] += skk_ms_since(t_con);
 
-	std::vector<double> cs, Cm, Dm, q;
+	std::vector<double> Cm, Dm, q;
 	size_t off = 0;
 	for (size_t u = 0; u < n_units; u++) {
 		const int64_t e0 = unit_ptr[u];
@@ -240,23 +283,8 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 		off += (size_t)m * m;
 
 		t_col = std::chrono::steady_clock::now();
-		hipLaunchKernelGGL(skk_colsum_kernel, dim3((unsigned)ncslab, (unsigned)m), dim3(256), 0, st, h->stage_pk, dbpv, N,
-			d_idx + e0, d_lut + 4 * e0, h->md.F, P, K, h->skk_cpart);
-		hipLaunchKernelGGL(skk_colfin_kernel, dim3((unsigned)(((size_t)m * C1 + 255) / 256)), dim3(256), 0, st, h->skk_cpart,
-			(size_t)m * C1, ncslab, C1, h->skk_cs);
-		hipLaunchKernelGGL(skk_adj_kernel, dim3(gl, (unsigned)m), dim3(256), 0, st, h->stage_pk, dbpv, N, d_idx + e0,
-			d_lut + 4 * e0, h->md.X, K, h->skk_cs, h->skk_A, lda);
-		HIPCHK(hipGetLastError());
-		cs.resize((size_t)m * C1);
-		HIPCHK(hipMemcpyAsync(cs.data(), h->skk_cs, cs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));
-		for (int j = 0; j < m; j++) {
-			const double *cj = &cs[(size_t)j * C1];
-			double sa = 0;
-			for (int a = 0; a < K; a++) sa += h->md.S_a[a] * cj[a];
-			const double S = cj[K] - sa;
-			score[e0 + j] = h->md.quant ? S / h->md.tau0 : S;
-		}
+		rc = skk_columns(h, src.from((size_t)e0), m, h->skk_A, lda, score + e0);
+		if (rc) return rc;
 		h->skk_ms[0] += skk_ms_since(t_col);
 
 		t_sol = std::chrono::steady_clock::now();
@@ -293,7 +321,78 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	return SGX_OK;
 }
 
-// milliseconds of the last sgx_skat_kmat_2bit call on this handle, as the host saw them: ms[0] rows, tables and columns,
+// tables with the non-finite ones replaced by zeros (a column of zeros takes no step of the solve) and flagged
+static void skk_tables(const double *lut, size_t m, std::vector<double> &lut_ok, std::vector<uint8_t> &bad)
+{
+	lut_ok.assign(lut, lut + m * 4);
+	bad.assign(m, 0);
+	for (size_t e = 0; e < m; e++) {
+		for (int c = 0; c < 4; c++) if (!std::isfinite(lut[4 * e + c])) bad[e] = 1;
+		if (bad[e]) for (int c = 0; c < 4; c++) lut_ok[4 * e + c] = 0;
+	}
+}
+
+extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *packed, size_t bpv, size_t n_variants,
+	size_t n_units, const int64_t *unit_ptr, const int32_t *var_idx, const double *lut, const double *w,
+	const double *tau, int maxiter, double tol, double *score, double *cov, int32_t *iters)
+{
+	const char *who = "sgx_skat_kmat_2bit";
+	if (!h || !km) return fail(SGX_EINVAL, "%s: NULL handle", who);
+	if (!packed || !unit_ptr || !var_idx || !lut || !w || !tau || !score || !cov) return fail(SGX_EINVAL, "%s: NULL buffer", who);
+	const int N = h->md.N;
+	int rc = skk_km_check(who, h, km);
+	if (rc) return rc;
+	if (bpv < (size_t)(N + 3) / 4)
+		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
+	rc = skk_sigma_args(who, N, w, tau, maxiter);
+	if (rc) return rc;
+	if (n_units == 0) return SGX_OK;
+	rc = skat_units_check(who, n_units, unit_ptr, var_idx, n_variants);
+	if (rc) return rc;
+	const int64_t nnz = unit_ptr[n_units];
+	if (nnz == 0) return SGX_OK;
+	rc = set_dev(h);
+	if (rc) return rc;
+	rc = sync_lane(h);
+	if (rc) return rc;
+	h->last_issued = h;
+	hipStream_t st = h->stream;
+	auto t_col = std::chrono::steady_clock::now();
+	h->skk_ms[0] = h->skk_ms[1] = h->skk_ms[2] = 0;
+
+	// an entry with a non-finite table stays out of the sums and the solve (a table of zeros: a right-hand side of
+	// zeros takes no step) and gets its non-finite results at the end
+	std::vector<double> lut_ok;
+	std::vector<uint8_t> bad;
+	skk_tables(lut, (size_t)nnz, lut_ok, bad);
+	int64_t m_max = 0;
+	for (size_t u = 0; u < n_units; u++) m_max = std::max(m_max, unit_ptr[u + 1] - unit_ptr[u]);
+
+	// device copies: the rows (dword stride) in the host-row pipeline's chunks, then entries and tables
+	const int ndw = (N + 15) >> 4;
+	const size_t dbpv = (size_t)ndw * 4;
+	const size_t o_idx = (n_variants * dbpv + 15) & ~(size_t)15;
+	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
+	const size_t need = o_lut + (size_t)nnz * 4 * sizeof(double);
+	rc = skk_room(h->stage_pk, need, "the rows");
+	if (!rc) rc = skk_unit_room(who, h, (size_t)m_max);
+	if (rc) return rc;
+	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
+	for (size_t off = 0; off < n_variants; off += rchunk) {
+		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), st);
+		if (rc) return rc;
+	}
+	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut_ok.data(), (size_t)nnz * 4 * sizeof(double), hipMemcpyHostToDevice, st));
+	SkkSrc src;
+	src.idx = reinterpret_cast<const int *>(h->stage_pk + o_idx);
+	src.rows = h->stage_pk; src.dbpv = dbpv;
+	src.lut = reinterpret_cast<const double *>(h->stage_pk + o_lut);
+	return skk_units(who, h, km, src, n_units, unit_ptr, bad, (size_t)m_max, w, tau, maxiter, tol, t_col, score, cov, iters);
+}
+
+// milliseconds of the last sgx_skat_kmat_2bit / sgx_ds_block_skat_kmat call on this handle, as the host saw them: ms[0] rows, tables and columns,
 // ms[1] the solves, ms[2] the products and the host's last step
 extern "C" int sgx_skat_kmat_ms(sgx_handle *h, double *ms)
 {

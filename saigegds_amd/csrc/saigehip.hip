@@ -84,6 +84,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_grm_dense.h"
 #include "kern_kmat.h"
 #include "kern_skat_kmat.h"
+#include "kern_kmat_ds.h"
 #include "kern_cond_kmat.h"
 
 // ---------------------------------------------------------------------------
@@ -108,3 +109,4 @@ static int fail(int code, const char *fmt, ...)
 #include "host_kmat.h"
 #include "host_skat_kmat.h"
 #include "host_cond_kmat.h"
+#include "host_kmat_ds.h"

@@ -17,7 +17,8 @@ Hard calls are one batch: one ``sgx_scan_2bit`` and one ``sgx_skat_2bit`` for al
 ``Phi^K = A' P A``, with no variance ratio.  Dosage input (a format node such as
 ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` that does not reduce to hard calls) is cut into batches
 that fit the device: the rows of a batch go to a resident ``DosageBlock`` once, ``blk.scan()`` gives the per-variant
-table and ``blk.skat()`` (``sgx_ds_block_skat``) ``S`` and ``Phi`` of the batch's units.
+table and ``blk.skat()`` (``sgx_ds_block_skat``) ``S`` and ``Phi`` of the batch's units -- with ``grm_mat=``
+``blk.skat_kmat()`` (``sgx_ds_block_skat_kmat``) on one operator for all batches.
 """
 from __future__ import annotations
 
@@ -26,7 +27,7 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .aggregate import AggrParamBeta, _dbeta, _prepare, _run, _save, _summary_cols, reduce_hard_calls
+from .aggregate import AggrParamBeta, _dbeta, _prepare, _run, _save, _summary_cols
 from .assoc import GenotypeSource
 
 LAMBDA_DROP = 1e-10      # eigenvalues at or below this fraction of the largest one are dropped
@@ -172,20 +173,17 @@ def aligned_grm_mat(grm_mat, inp, mod):
 
 
 def _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat):
-    """The refusals of ``seqAssocGLMM_spaSKAT(grm_mat=)``, before any row is read -> (the opened source, the matrix of the
-    scan's samples in the scan's order, the model's weights V in that order)."""
+    """The refusals of ``seqAssocGLMM_spaSKAT(grm_mat=)`` that need no scanner, before any row is read -> (the opened
+    source, the matrix of the scan's samples in the scan's order, the model's weights V in that order).  Dosage input
+    is refused only where the scanner cannot serve it (``aggregate._dosage_rows``)."""
     from .assoc import _open_source, open_scan_input
     from .nullmod import load_modobj, no_loco
     if not (parallel is False or parallel is None or (isinstance(parallel, (int, np.integer)) and int(parallel) in (0, 1))):
         raise ValueError("SKAT with 'grm_mat' runs on one GPU: 'parallel' should be FALSE or 1.")
     mod = load_modobj(modobj, False)
     no_loco(mod, "SAIGE SKAT analysis")
-    if dsnode != "":
-        raise NotImplementedError("SKAT with 'grm_mat' on dosage input is not implemented.")
     src = _open_source(gdsfile, False)          # opened once: the driver goes on with this object
     inp = open_scan_input(src, mod, dsnode, False)
-    if reduce_hard_calls(inp).kind != "packed":
-        raise NotImplementedError("SKAT with 'grm_mat' on dosage input is not implemented.")
     return (src, *aligned_grm_mat(grm_mat, inp, mod))
 
 
@@ -218,8 +216,10 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
     itself, ``Phi^K = A' P A`` with ``Sigma = tau[0] diag(1/V) + tau[1] K`` (``sgx_skat_kmat_2bit``; solves
     to ``tol_pcg`` in at most ``maxiter_pcg`` steps): no variance ratio enters it.  The SPA scale factors are then formed
     against ``Phi^K_jj``; weights, ``Q`` and ``pchisq_mix`` are the same code, and a column ``n.iter`` holds the largest
-    PCG step count of the unit.  Refused before any row is read: dosage input (``NotImplementedError``), a LOCO model,
-    ``parallel`` other than one GPU (``ValueError``)."""
+    PCG step count of the unit.  Dosage input takes ``sgx_ds_block_skat_kmat`` per batch with the scan's
+    own mean and flip.  Refused before any row is read: dosage input on a scanner without ``dosage_block`` or whose block
+    has no ``skat_kmat`` (``NotImplementedError``; the scanner is closed), a LOCO model, ``parallel`` other than one GPU
+    (``ValueError``)."""
     if not isinstance(dsnode, str):
         raise TypeError("is.character(dsnode) is not TRUE")
     if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
