@@ -331,6 +331,31 @@ int sgx_cond_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant
 int sgx_cond_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_per_variant, size_t n_variants,
 	const double *lut_dev, double *score_dev, double *var_dev, double *cov_dev);
 
+/* Firth bias-reduced effect size of a binary-trait row (saigegds_amd/firth.py; nothing of this is in the reference,
+ * DESIGN.md 8j).  Tables as for sgx_skat_2bit / sgx_cond_2bit: g_i = lut[4j + code_i].  With the model's fitted mean mu as
+ * offset, logit p_i = logit mu_i + beta g_i, w_i = p_i (1 - p_i) and, over the samples with g_i != 0,
+ *   I = sum w g^2,  A = sum w (1 - 2p) g^3,  B = sum w (1 - 6w) g^4,  U* = sum g (y - p) + A / 2I
+ * (U*: the score of loglik + 1/2 log I), the result is the root of U*:
+ *   out4[4j .. 4j + 3] = {beta, SE = 1 / sqrt(I(beta)), iterations, converged (1 / 0)}
+ * for the table's orientation (a driver negates beta of a flipped row).  The root is found by Newton's iteration from 0
+ * with Fisher scoring's step where dU* / dbeta >= 0, steps capped at +-5 and bisected into the sign bracket once both its
+ * ends are known, to |step| <= 1e-12 max(1, |beta|) in at most maxit iterations.  A row with no non-zero dosage
+ * (I = 0) or a non-finite table value gets {NaN, NaN, ., 0}; a row that runs out of iterations {beta of the last
+ * iterate, NaN, maxit, 0}; neither disturbs another row.
+ *   sgx_firth_2bit      rows in HOST memory, uploaded in the chunks of the host-buffer scans.  Synchronous; a thin
+ *                       wrapper around the next entry: same kernel, same bits.
+ *   sgx_firth_2bit_dev  rows in DEVICE memory (stride and alignment as for sgx_scan_2bit_dev); table and results are
+ *                       device pointers.  Asynchronous on the handle's stream; results are readable after sgx_sync().
+ * One workgroup per row, FP64 sums in a fixed order, no atomics: a row's results depend on the row, its table and the
+ * model only -- not on its position, the other rows, the grid or the chunks.  Lists that do not fit LDS go to a scratch
+ * buffer the handle allocates on first use and frees with itself.  n_variants = 0 succeeds and does nothing.  A
+ * quantitative-trait handle, a NULL buffer, bytes_per_variant < ceil(n_samp / 4), a bad device stride or alignment, or
+ * maxit < 1 returns SGX_EINVAL and launches nothing; the handle stays usable. */
+int sgx_firth_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant, size_t n_variants,
+	const double *lut, int maxit, double *out4);
+int sgx_firth_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_per_variant, size_t n_variants,
+	const double *lut_dev, int maxit, double *out4_dev);
+
 /* Aggregate tests on dosage input: the INTSXP / REALSXP branches of ds_mat_mafmac and ds_mat_burden
  * (src/saige_main.cpp:485-610), which the R drivers reach with .dsnode(gdsfile, dsnode) for imputed
  * data (R/assoc_aggregate.r:89,351,606).  A batch of dosage rows (u8: 0xFF = missing; i32: INT_MIN =

@@ -197,6 +197,8 @@ def _abi():
         "sgx_cond_set": (ci, [vp, vp, sz, sz, vp, vp, vp]),
         "sgx_cond_2bit": (ci, [vp, vp, sz, sz, vp, vp, vp, vp]),
         "sgx_cond_2bit_dev": (ci, [vp, vp, sz, sz, vp, vp, vp, vp]),
+        "sgx_firth_2bit": (ci, [vp, vp, sz, sz, vp, ci, vp]),
+        "sgx_firth_2bit_dev": (ci, [vp, vp, sz, sz, vp, ci, vp]),
         "sgx_ds_block_cond_set": (ci, [vp, vp, sz, vp, vp, vp, vp, vp]),
         "sgx_ds_block_cond": (ci, [vp, vp, vp, vp, vp, vp, vp]),
         "sgx_ds_block_skat_kmat": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
@@ -521,6 +523,25 @@ class Scanner(_Handle):
         """``cond_2bit`` on rows, tables and results in device memory (``sgx_cond_2bit_dev``; asynchronous, sync()
         before reading)."""
         check(self._L.sgx_cond_2bit_dev(self._h, packed_ptr, bpv, m, lut_ptr, score_ptr, var_ptr, cov_ptr))
+
+    def firth_2bit(self, packed: np.ndarray, lut, maxit: int = 50):
+        """Firth bias-reduced effect size of every 2-bit row (one 4-entry dosage table each; ``sgx_firth_2bit``; binary
+        traits) -> out4 [m, 4]: beta for the table's orientation, SE, iterations, converged (1 / 0).  NaN / NaN / 0 for a
+        row without a non-zero dosage or with a non-finite table value."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
+        if packed.ndim != 2 or lut.shape[0] != packed.shape[0]:
+            raise ValueError("firth_2bit: one table per row")
+        m = packed.shape[0]
+        out4 = np.zeros((max(1, m), 4))
+        check(self._L.sgx_firth_2bit(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data, int(maxit),
+                                     out4.ctypes.data))
+        return out4[:m]
+
+    def firth_2bit_dev(self, packed_ptr: int, bpv: int, m: int, lut_ptr: int, out4_ptr: int, maxit: int = 50):
+        """``firth_2bit`` on rows, tables and results in device memory (``sgx_firth_2bit_dev``; asynchronous, sync()
+        before reading)."""
+        check(self._L.sgx_firth_2bit_dev(self._h, packed_ptr, bpv, m, lut_ptr, int(maxit), out4_ptr))
 
     def dosage_block(self, dtype, max_variants: int) -> "DosageBlock":
         """Device storage for a batch of dosage rows of the aggregate tests (``DosageBlock`` below)."""

@@ -8,6 +8,7 @@ forks SeqArray worker processes instead, R/assoc_single.r:167-204).
 from __future__ import annotations
 
 import math
+import re
 import time
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Union
@@ -296,15 +297,30 @@ def finish_result(ans, res_savefn: str, res_compress: str, verbose: bool, sample
 def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, maf: float = float("nan"),
                      mac: float = 10, missing: float = 0.1, dsnode: str = "", spa_pval: float = 0.05,
                      var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
-                     parallel: Union[bool, int] = False, verbose: bool = True, timing: Optional[Dict[str, float]] = None):
+                     parallel: Union[bool, int] = False, verbose: bool = True, timing: Optional[Dict[str, float]] = None,
+                     firth_pval: Optional[float] = None, firth_maxit: int = 50):
     """SAIGE single-variant association scan on MI355X.
 
     Returns a ``dict`` of equal-length columns (``pandas.DataFrame(result)``
     gives the reference's data.frame): id, chr, pos, [rs.id], ref, alt, AF.alt,
     mac, num, beta, SE, pval and, for binary traits, p.norm, converged
     (man/seqAssocGLMM_SPA.Rd:60-74).
+
+    ``firth_pval`` (not in the reference; binary traits, hard calls): a number in (0, 1] -- after the scan every valid
+    row with ``pval <= firth_pval`` gets a Firth bias-reduced fit (``saigegds_amd.firth``; at most
+    ``firth_maxit`` iterations) on device 0, with a LOCO model against its chromosome's model, and the result gains
+    ``beta.firth`` (for the alt allele, like ``beta``), ``SE.firth`` and ``cvg.firth`` (NaN / NaN / False on the other
+    rows).  None: no such columns and no such pass.  ``res_savefn``: ``.rds`` / ``.RData``; the ``.gds`` writer has
+    fixed columns and is refused.
     """
     check_scan_args(maf, mac, missing, spa_pval, var_ratio, dsnode, res_savefn, res_compress, verbose)
+    if firth_pval is not None:
+        if not _is_num(firth_pval) or not 0 < firth_pval <= 1:
+            raise ValueError("`firth_pval` should be None or a number in (0, 1].")
+        if not isinstance(firth_maxit, (int, np.integer)) or isinstance(firth_maxit, bool) or firth_maxit < 1:
+            raise ValueError("`firth_maxit` should be a positive integer.")
+        if re.search(r"\.gds$", res_savefn, re.I):
+            raise ValueError("The gds output has no columns for the Firth effect sizes; save to RData or RDS.")
     if verbose:
         print("SAIGE association analysis:")
 
@@ -315,6 +331,12 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     _dsnode(src, dsnode)      # (a file without dosages is refused before its samples are looked at, R/assoc_single.r:133)
     inp = open_scan_input(src, mod, dsnode, verbose, any_matrix=True)
     kind, n_samp, n_var, ii = inp.kind, inp.n_samp, inp.n_var, inp.ii
+    firth_inp = None
+    if firth_pval is not None:
+        from . import firth
+        if mod.trait_type != "binary":
+            raise ValueError("Firth effect sizes are for binary traits.")
+        firth_inp = firth.hard_call_input(inp)          # (dosage input: NotImplementedError, before any row is scanned)
     if verbose:
         print(f"    # of samples: {_pretty(n_samp)}")
         print(f"    # of variants: {_pretty(n_var)}")
@@ -322,6 +344,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         print(f"    MAC threshold: {mac}")
         print(f"    missing threshold for variants: {missing}")
         print(f"    p-value threshold for SPA adjustment: {spa_pval}")
+        if firth_pval is not None:
+            print(f"    p-value threshold for Firth effect sizes: {firth_pval}")
     if not math.isfinite(var_ratio):
         var_ratio = float(np.nanmean(mod.var_ratio))
     if verbose:
@@ -354,9 +378,23 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     elif kind == "packed" and not inp.in_mem and GENOTYPE_DECODE == "device":
         bl_size = packed_block_size(src.genotype_raw_row_bytes())      # a stored row is twice a 2-bit row
     t_loop = time.perf_counter()
+    fcols = None
+    if firth_pval is not None:
+        fcols = (np.full(n_var, np.nan), np.full(n_var, np.nan), np.zeros(n_var, dtype=bool))
+
+    def firth_rows(r0, r1, obj):
+        """The Firth pass of the scanned rows [r0, r1) against the model they were scanned with."""
+        with np.errstate(invalid="ignore"):
+            rows = r0 + np.flatnonzero((valid[r0:r1] != 0) & (out[r0:r1, 5] <= firth_pval))
+        got = firth.firth_pass(firth_inp, out, valid, rows, lambda: Scanner(obj, device=0), firth_maxit)
+        for col, g in zip(fcols, got):
+            col[rows] = g[rows]
+
     if not mod.loco:
         blocks = [(off, min(n_var, off + bl_size)) for off in range(0, n_var, bl_size)]
         scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, inp.read_block, kind == "packed", out, valid, timing)
+        if fcols is not None:
+            firth_rows(0, n_var, mobj)
     else:
         # leave-one-chromosome-out: the block list is cut at chromosome boundaries, and every run of one
         # chromosome is scanned against that chromosome's model (its fitted values; y, V, XV, XXVX_inv and
@@ -374,6 +412,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
             blocks = [(off, min(r1, off + bl_size)) for off in range(r0, r1, bl_size)]
             scan_blocks(lambda d, o=run_obj: Scanner(o, device=d), ngpu, blocks, inp.read_block, kind == "packed", out, valid,
                         timing)
+            if fcols is not None:
+                firth_rows(r0, r1, run_obj)
     if timing is not None:
         timing["blocks_s"] = time.perf_counter() - t_loop      # handles + every block (decode and scan overlapped)
 
@@ -381,8 +421,10 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     if verbose:
         print("# of variants after filtering by MAF, MAC and missing thresholds: "
               f"{_pretty(int(x.sum()))}")
-    return finish_result(assemble_result(src, x, out, mod.trait_type), res_savefn, res_compress, verbose,
-                         inp.sample_id() if res_savefn else None)
+    ans = assemble_result(src, x, out, mod.trait_type)
+    if fcols is not None:
+        ans["beta.firth"], ans["SE.firth"], ans["cvg.firth"] = (c[x] for c in fcols)
+    return finish_result(ans, res_savefn, res_compress, verbose, inp.sample_id() if res_savefn else None)
 
 
 def chromosome_runs(chrom):

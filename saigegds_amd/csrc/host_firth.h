@@ -1,0 +1,79 @@
+// host_firth.h -- Firth bias-reduced effect sizes of binary-trait rows (kern_firth.h): sgx_firth_2bit_dev
+// queues the kernel for rows in device memory, sgx_firth_2bit is its wrapper for rows in host memory.
+// Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
+
+static int firth_check(const sgx_handle *h, const char *who, int maxit)
+{
+	if (!h) return fail(SGX_EINVAL, "%s: NULL handle", who);
+	if (h->owner) return fail(SGX_EINVAL, "%s: not on a twin", who);
+	if (h->md.quant) return fail(SGX_EINVAL, "%s: the Firth fit is for binary traits", who);
+	if (maxit < 1) return fail(SGX_EINVAL, "%s: maxit=%d, need at least 1", who, maxit);
+	return SGX_OK;
+}
+
+// M rows in device memory -> out4, queued on the handle's stream.  The grid, and with it the scratch of the lists that
+// do not fit LDS (allocated on first use, kept), follows the handle, not M: what a row gets depends on neither.
+static int firth_rows_dev(sgx_handle *h, const uint8_t *rows, size_t bpv, size_t M, const double *lut, int maxit, double *out4)
+{
+	const int N = h->md.N, grid = std::max(1, h->spa_grid);
+	int rc = ensure_buf(h, h->firth_scr, firth_slice_bytes(N) * (size_t)grid);
+	if (rc) return rc;
+	hipLaunchKernelGGL(firth_kernel, dim3((unsigned)std::min<size_t>(M, (size_t)grid)), dim3(FIRTH_BLOCK), 0, h->stream,
+		rows, bpv, N, M, lut, h->md.mu, h->md.y, maxit, (uint8_t *)h->firth_scr, out4);
+	HIPCHK(hipGetLastError());
+	return SGX_OK;
+}
+
+extern "C" int sgx_firth_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bpv, size_t M,
+	const double *lut_dev, int maxit, double *out4_dev)
+{
+	int rc = firth_check(h, "sgx_firth_2bit_dev", maxit);
+	if (rc) return rc;
+	if (M == 0) return SGX_OK;
+	if (!packed_dev || !lut_dev || !out4_dev) return fail(SGX_EINVAL, "sgx_firth_2bit_dev: NULL buffer");
+	if (bpv % 64 != 0 || bpv < sgx_row_stride(h->md.N))
+		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu, need a multiple of 64 >= %zu",
+			bpv, sgx_row_stride(h->md.N));
+	if (((uintptr_t)packed_dev & 15u) != 0)
+		return fail(SGX_EINVAL, "sgx_firth_2bit_dev: packed_dev must be 16-byte aligned");
+	if (((uintptr_t)lut_dev & 7u) != 0 || ((uintptr_t)out4_dev & 7u) != 0)
+		return fail(SGX_EINVAL, "sgx_firth_2bit_dev: lut_dev and out4_dev must be 8-byte aligned");
+	rc = set_dev(h);
+	if (rc) return rc;
+	return firth_rows_dev(h, packed_dev, bpv, M, lut_dev, maxit, out4_dev);
+}
+
+extern "C" int sgx_firth_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t M,
+	const double *lut, int maxit, double *out4)
+{
+	int rc = firth_check(h, "sgx_firth_2bit", maxit);
+	if (rc) return rc;
+	if (M == 0) return SGX_OK;
+	if (!packed || !lut || !out4) return fail(SGX_EINVAL, "sgx_firth_2bit: NULL buffer");
+	const int N = h->md.N;
+	if (bpv < (size_t)(N + 3) / 4)
+		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
+	rc = set_dev(h);
+	if (rc) return rc;
+	rc = sync_lane(h);
+	if (rc) return rc;
+
+	// chunks of the host-buffer scans: rows at the device stride, then tables and results
+	const size_t dbpv = sgx_row_stride(N);
+	const size_t rchunk = scan_chunk(h, dbpv, M);
+	const size_t o_lut = rchunk * dbpv, o_out = o_lut + rchunk * 4 * sizeof(double);
+	rc = grow(h->stage_pk, o_out + rchunk * 4 * sizeof(double));
+	if (rc) return rc;
+	double *d_lut = reinterpret_cast<double *>(h->stage_pk + o_lut), *d_out = reinterpret_cast<double *>(h->stage_pk + o_out);
+	for (size_t off = 0; off < M; off += rchunk) {
+		const size_t m = std::min(rchunk, M - off);
+		rc = copy_rows_h2d(h->stage_pk, dbpv, packed + off * bpv, bpv, m, h->stream);
+		if (rc) return rc;
+		HIPCHK(hipMemcpyAsync(d_lut, lut + 4 * off, m * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+		rc = firth_rows_dev(h, h->stage_pk, dbpv, m, d_lut, maxit, d_out);
+		if (rc) return rc;
+		HIPCHK(hipMemcpyAsync(out4 + 4 * off, d_out, m * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
+	}
+	return SGX_OK;
+}

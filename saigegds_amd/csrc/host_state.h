@@ -144,6 +144,8 @@ struct sgx_handle {
 	int n_cond = 0;                   // 0: no set installed
 	// ... every lane: per-slab partial sums of a launch and the rows' sums over the slabs
 	DevBuf<double> cond_part, cond_fin;
+	// Firth effect sizes (host_firth.h): per-workgroup slices for the lists that do not fit LDS, allocated on first use
+	DevBuf<uint8_t> firth_scr;
 	bool evk_set = false;
 	bool lists_timed = false;
 	sgx_stats stats{};

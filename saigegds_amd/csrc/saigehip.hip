@@ -86,6 +86,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_skat_kmat.h"
 #include "kern_kmat_ds.h"
 #include "kern_cond_kmat.h"
+#include "kern_firth.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -110,3 +111,4 @@ static int fail(int code, const char *fmt, ...)
 #include "host_skat_kmat.h"
 #include "host_cond_kmat.h"
 #include "host_kmat_ds.h"
+#include "host_firth.h"
