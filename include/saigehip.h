@@ -422,6 +422,21 @@ int sgx_firth_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_pe
  *                       Both: a NULL buffer, nothing loaded, an index outside the loaded rows, a twin handle, a block /
  *                       handle mismatch, or sgx_ds_block_cond with no set installed returns SGX_EINVAL and launches
  *                       nothing; the handle stays usable.
+ *   sgx_ds_block_firth  sgx_firth_2bit for resident rows: row r of out4 = {beta, SE, iterations, converged} of loaded row
+ *                       var_idx[r] with the dosage vector G above (flip[r] / mean[r] per REQUEST; indices may repeat and
+ *                       come in any order), conventions as for sgx_firth_2bit: beta for the orientation flip[r] gives, a
+ *                       request whose mean is not finite {NaN, NaN, 0, 0} whether or not a sample is missing, a row
+ *                       without a non-zero dosage {NaN, NaN, ., 0}.  HOST buffers of n_rows entries.  One workgroup per
+ *                       request compacts the samples with G != 0 in sample order (kern_firth_ds.h) and runs the iteration
+ *                       of sgx_firth_2bit on that list, FP64 sums in a fixed order, no atomics: what a request gets
+ *                       depends on its row's values, its flip / mean and the model only -- not on the row's place in the
+ *                       block, the request's place in var_idx, the grid or the other requests -- and a row of hard calls
+ *                       gives the bits of sgx_firth_2bit on its 2-bit form with the table {0, 1, 2, mean} ({2, 1, 0, mean}
+ *                       where flipped), the iteration count included.  Lists that do not fit LDS go to the scratch buffer
+ *                       of sgx_firth_2bit (allocated on first use, at most 2 GiB, freed with the handle).  n_rows = 0
+ *                       succeeds and does nothing.  A NULL handle, block or buffer, a twin handle, a quantitative-trait
+ *                       handle, maxit < 1, nothing loaded, an index outside the loaded rows or a block / handle mismatch
+ *                       returns SGX_EINVAL and launches nothing; handle and block stay usable.
  * All of them are synchronous; block and handle must be on the same device and have the same n_samp. */
 #define SGX_DS_U8  0
 #define SGX_DS_I32 1
@@ -441,6 +456,8 @@ int  sgx_ds_block_cond_set(sgx_handle *h, const sgx_dsblock *b, size_t n_cond, c
 	const uint8_t *flip, const double *mean, double *score_c, double *cov_cc);
 int  sgx_ds_block_cond(sgx_handle *h, const sgx_dsblock *b, const uint8_t *flip, const double *mean,
 	double *score, double *var, double *cov);
+int  sgx_ds_block_firth(sgx_handle *h, const sgx_dsblock *b, size_t n_rows, const int32_t *var_idx,
+	const uint8_t *flip, const double *mean, int maxit, double *out4);
 int  sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out8, uint8_t *valid);
 int  sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_groups, const int64_t *grp_ptr,
 	const int32_t *var_idx, const uint8_t *flip, int n_cols, const double *w, const double *mw,

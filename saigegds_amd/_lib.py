@@ -201,6 +201,7 @@ def _abi():
         "sgx_firth_2bit_dev": (ci, [vp, vp, sz, sz, vp, ci, vp]),
         "sgx_ds_block_cond_set": (ci, [vp, vp, sz, vp, vp, vp, vp, vp]),
         "sgx_ds_block_cond": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "sgx_ds_block_firth": (ci, [vp, vp, sz, vp, vp, vp, ci, vp]),
         "sgx_ds_block_skat_kmat": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
         "sgx_ds_block_cond_kmat_set": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
         "sgx_ds_block_cond_kmat": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -749,6 +750,23 @@ class DosageBlock(_Handle):
         check(self._L.sgx_ds_block_cond(self._sc._h, self._b, flip.ctypes.data, mean.ctypes.data, score.ctypes.data,
                                         var.ctypes.data, cov.ctypes.data))
         return score[:m], var[:m], cov[:m * c].reshape(m, c)
+
+    def firth(self, var_idx, flip, mean, maxit: int = 50):
+        """Firth bias-reduced effect size of the resident rows ``var_idx`` (any order, repeats allowed) with ``flip`` /
+        ``mean`` per entry as for ``skat`` (``sgx_ds_block_firth``; binary traits) -> out4 [n_rows, 4]: beta for the
+        entry's orientation, SE, iterations, converged (1 / 0), as ``Scanner.firth_2bit`` -- bit for bit what it gives on
+        the 2-bit form of a row of hard calls.  NaN / NaN / 0 for a row without a non-zero dosage or with a non-finite
+        mean."""
+        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        if var_idx.ndim != 1 or flip.shape != var_idx.shape or mean.shape != var_idx.shape:
+            raise ValueError("DosageBlock.firth: one flip and one mean per entry of var_idx")
+        m = var_idx.size
+        out4 = np.zeros((max(1, m), 4))
+        check(self._L.sgx_ds_block_firth(self._sc._h, self._b, m, var_idx.ctypes.data, flip.ctypes.data, mean.ctypes.data,
+                                         int(maxit), out4.ctypes.data))
+        return out4[:m]
 
     def _sigma_args(self, what: str, op, w, tau):
         w = np.ascontiguousarray(w, dtype=np.float64)

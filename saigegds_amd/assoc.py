@@ -306,8 +306,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     mac, num, beta, SE, pval and, for binary traits, p.norm, converged
     (man/seqAssocGLMM_SPA.Rd:60-74).
 
-    ``firth_pval`` (not in the reference; binary traits, hard calls): a number in (0, 1] -- after the scan every valid
-    row with ``pval <= firth_pval`` gets a Firth bias-reduced fit (``saigegds_amd.firth``; at most
+    ``firth_pval`` (not in the reference; binary traits; every input the scan takes: hard calls by ``sgx_firth_2bit``,
+    dosages by ``sgx_ds_block_firth`` on a resident dosage block): a number in (0, 1] -- after the scan every valid row with ``pval <= firth_pval`` gets a Firth bias-reduced fit (``saigegds_amd.firth``; at most
     ``firth_maxit`` iterations) on device 0, with a LOCO model against its chromosome's model, and the result gains
     ``beta.firth`` (for the alt allele, like ``beta``), ``SE.firth`` and ``cvg.firth`` (NaN / NaN / False on the other
     rows).  None: no such columns and no such pass.  ``res_savefn``: ``.rds`` / ``.RData``; the ``.gds`` writer has
@@ -336,7 +336,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         from . import firth
         if mod.trait_type != "binary":
             raise ValueError("Firth effect sizes are for binary traits.")
-        firth_inp = firth.hard_call_input(inp)          # (dosage input: NotImplementedError, before any row is scanned)
+        from . import _lib
+        firth_inp = firth.firth_input(inp, _lib.Scanner)      # (no dosage route: NotImplementedError, before any row is scanned)
     if verbose:
         print(f"    # of samples: {_pretty(n_samp)}")
         print(f"    # of variants: {_pretty(n_var)}")
@@ -378,15 +379,17 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     elif kind == "packed" and not inp.in_mem and GENOTYPE_DECODE == "device":
         bl_size = packed_block_size(src.genotype_raw_row_bytes())      # a stored row is twice a 2-bit row
     t_loop = time.perf_counter()
-    fcols = None
+    fcols, firth_stored = None, False
     if firth_pval is not None:
         fcols = (np.full(n_var, np.nan), np.full(n_var, np.nan), np.zeros(n_var, dtype=bool))
+        if firth_inp.kind != "packed":
+            firth_stored = firth.dosage_route(firth_inp, lambda: Scanner(mobj, device=0))
 
     def firth_rows(r0, r1, obj):
         """The Firth pass of the scanned rows [r0, r1) against the model they were scanned with."""
         with np.errstate(invalid="ignore"):
             rows = r0 + np.flatnonzero((valid[r0:r1] != 0) & (out[r0:r1, 5] <= firth_pval))
-        got = firth.firth_pass(firth_inp, out, valid, rows, lambda: Scanner(obj, device=0), firth_maxit)
+        got = firth.firth_pass(firth_inp, out, valid, rows, lambda: Scanner(obj, device=0), firth_maxit, firth_stored)
         for col, g in zip(fcols, got):
             col[rows] = g[rows]
 

@@ -1,5 +1,6 @@
 // host_firth.h -- Firth bias-reduced effect sizes of binary-trait rows (kern_firth.h): sgx_firth_2bit_dev
-// queues the kernel for rows in device memory, sgx_firth_2bit is its wrapper for rows in host memory.
+// queues the kernel for rows in device memory, sgx_firth_2bit is its wrapper for rows in host memory, sgx_ds_block_firth
+// serves the dosage rows of a resident sgx_dsblock (kern_firth_ds.h).
 // Part of libsaigehip.so: included by saigehip.hip (one translation unit), not a header of its own.
 
 static int firth_check(const sgx_handle *h, const char *who, int maxit)
@@ -75,5 +76,61 @@ extern "C" int sgx_firth_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, 
 		HIPCHK(hipMemcpyAsync(out4 + 4 * off, d_out, m * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
 	}
+	return SGX_OK;
+}
+
+// Bound on the scratch of the dosage kernel's long lists.  A slice is (N - FIRTH_DS_LDS_N) entries of 17 bytes (double
+// rows) or 10 (u8 rows) -- 7.3 MB at N = 430 000, about twice the 2-bit kernel's -- so the grid is capped where the
+// handle's own would ask for more: 293 workgroups of double rows at that N, still more than one a CU.  Results do not
+// depend on the grid.
+static const size_t FIRTH_DS_SCR_MAX = (size_t)2 << 30;
+
+extern "C" int sgx_ds_block_firth(sgx_handle *h, const sgx_dsblock *b, size_t n_rows, const int32_t *var_idx,
+	const uint8_t *flip, const double *mean, int maxit, double *out4)
+{
+	int rc = firth_check(h, "sgx_ds_block_firth", maxit);
+	if (rc) return rc;
+	rc = dsblock_check(h, b, "sgx_ds_block_firth");
+	if (rc) return rc;
+	if (n_rows == 0) return SGX_OK;
+	if (!var_idx || !flip || !mean || !out4) return fail(SGX_EINVAL, "sgx_ds_block_firth: NULL buffer");
+	if (b->M == 0) return fail(SGX_EINVAL, "sgx_ds_block_firth: nothing loaded");
+	for (size_t r = 0; r < n_rows; r++)
+		if (var_idx[r] < 0 || (size_t)var_idx[r] >= b->M)
+			return fail(SGX_EINVAL, "sgx_ds_block_firth: variant index %d outside the block's %zu rows", var_idx[r], b->M);
+	rc = sync_lane(h);
+	if (rc) return rc;
+	h->last_issued = h;
+
+	const int N = b->N;
+	const bool u8 = b->dtype == SGX_DS_U8;
+	const size_t slice = u8 ? firth_ds_slice_bytes<uint8_t>(N) : firth_ds_slice_bytes<double>(N);
+	size_t grid = (size_t)std::max(1, h->spa_grid);
+	if (slice) grid = std::max<size_t>(1, std::min(grid, FIRTH_DS_SCR_MAX / slice));
+	rc = ensure_buf(h, h->firth_scr, slice * grid);
+	if (rc) return rc;
+
+	// tables and results on the device: means, results, then the indices and the flips
+	const size_t o_out = n_rows * sizeof(double), o_idx = o_out + n_rows * 4 * sizeof(double);
+	const size_t o_flip = o_idx + n_rows * sizeof(int);
+	rc = grow(h->stage_pk, o_flip + n_rows);
+	if (rc) return rc;
+	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
+	double *d_mean = reinterpret_cast<double *>(h->stage_pk.p), *d_out = reinterpret_cast<double *>(h->stage_pk + o_out);
+	int *d_idx = reinterpret_cast<int *>(h->stage_pk + o_idx);
+	uint8_t *d_flip = h->stage_pk + o_flip;
+	HIPCHK(hipMemcpyAsync(d_mean, mean, n_rows * sizeof(double), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(d_idx, var_idx, n_rows * sizeof(int), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(d_flip, flip, n_rows, hipMemcpyHostToDevice, h->stream));
+	const dim3 g((unsigned)std::min(n_rows, grid));
+	if (u8)
+		hipLaunchKernelGGL((firth_ds_kernel<uint8_t>), g, dim3(FIRTH_BLOCK), 0, h->stream,
+			(const uint8_t *)b->rows, N, n_rows, d_idx, d_flip, d_mean, h->md.mu, h->md.y, maxit, (uint8_t *)h->firth_scr, d_out);
+	else
+		hipLaunchKernelGGL((firth_ds_kernel<double>), g, dim3(FIRTH_BLOCK), 0, h->stream,
+			(const double *)b->rows.p, N, n_rows, d_idx, d_flip, d_mean, h->md.mu, h->md.y, maxit, (uint8_t *)h->firth_scr, d_out);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(out4, d_out, n_rows * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return SGX_OK;
 }

@@ -19,10 +19,10 @@
 //      step of zero does not (the iterate is an end of its own bracket); done when |step| <= 1e-12 max(1, |b|).  The four sums of an iteration come from one pass over
 //      the list: every thread its entries k = tid, tid + BLOCK, ... in order, then block_sum's fixed tree -- no
 //      atomics, so a row's bits depend on the row, its table and the model only.
-// Only four values of g occur, so exp(b g) is evaluated per code, not per entry; an entry costs one reciprocal.
+// Only four values of g occur, so e = exp(-|b g|) is evaluated per code, not per entry; an entry costs one reciprocal.
 // p and 1 - p are formed without cancellation and without overflow from
-//     b g <= 0:  a = mu e^{bg},  c = 1 - mu           b g > 0:  a = mu,  c = (1 - mu) e^{-bg}
-//     p = a / (a + c),   1 - p = c / (a + c).
+//     b g <= 0:  a = mu e,  c = 1 - mu           b g > 0:  a = mu,  c = (1 - mu) e
+//     p = a / (a + c),   1 - p = c / (a + c)          (firth_entry, shared with kern_firth_ds.h).
 // All threads execute the scalar control flow redundantly on identical values (as kern_spa.h).
 
 #define FIRTH_LDS_N 4096          /* list entries held in LDS: 36 KiB a workgroup, four workgroups a CU */
@@ -51,15 +51,30 @@ struct FirthList {
 	int nnz;
 };
 
+// One list entry's terms of I, A, B and sum g (y - p): m its fitted mean, gi != 0 its dosage, yi its trait, e =
+// exp(-|b gi|), pos = b gi > 0.  The one statement of the per-entry arithmetic: firth_sums below and kern_firth_ds.h
+// both inline it, so that the compiler contracts it the same way in both.
+__device__ __forceinline__ void firth_entry(double m, double gi, bool yi, double e, bool pos, double (&s)[4])
+{
+	const double a = pos ? m : m * e, c = pos ? (1 - m) * e : 1 - m;
+	const double r = fast_rcp(a + c);
+	const double p = a * r, q = c * r, w = p * q, g2 = gi * gi;
+	s[0] = fma(w, g2, s[0]);
+	s[1] = fma(w * (q - p), g2 * gi, s[1]);
+	s[2] = fma(w * fma(-6.0, w, 1.0), g2 * g2, s[2]);
+	s[3] = fma(gi, yi ? q : -p, s[3]);
+}
+
 // I, A, B and sum g (y - p) at b over the list
 __device__ __forceinline__ void firth_sums(double b, const double (&g)[4], const FirthList &L, double *sh, double (&s)[4])
 {
-	double ea[4], ec[4];
+	double e[4];
+	uint32_t pos = 0;                         // bit c: b g[c] > 0
 #pragma unroll
 	for (int c = 0; c < 4; c++) {
 		const double x = b * g[c];
-		ea[c] = x <= 0 ? exp(x) : 1.0;
-		ec[c] = x <= 0 ? 1.0 : exp(-x);
+		e[c] = exp(-fabs(x));
+		pos |= (x > 0) ? (1u << c) : 0u;
 	}
 	s[0] = s[1] = s[2] = s[3] = 0;
 	for (int k = threadIdx.x; k < L.nnz; k += FIRTH_BLOCK) {
@@ -67,15 +82,48 @@ __device__ __forceinline__ void firth_sums(double b, const double (&g)[4], const
 		const double m = in_lds ? L.mu_l[k] : L.mu_g[k - FIRTH_LDS_N];
 		const uint32_t cy = in_lds ? L.cy_l[k] : L.cy_g[k - FIRTH_LDS_N];
 		const uint32_t code = cy & 3u;
-		const double gi = sel4(g, code), a = m * sel4(ea, code), c = (1 - m) * sel4(ec, code);
-		const double r = fast_rcp(a + c);
-		const double p = a * r, q = c * r, w = p * q, g2 = gi * gi;
-		s[0] = fma(w, g2, s[0]);
-		s[1] = fma(w * (q - p), g2 * gi, s[1]);
-		s[2] = fma(w * fma(-6.0, w, 1.0), g2 * g2, s[2]);
-		s[3] = fma(gi, (cy & 4u) ? q : -p, s[3]);
+		firth_entry(m, sel4(g, code), (cy & 4u) != 0, sel4(e, code), ((pos >> code) & 1u) != 0, s);
 	}
 	block_sum<4, FIRTH_BLOCK>(s, sh);
+}
+
+// Phase B: the root of U* over a list of nnz entries whose four sums at b `sums(b, s)` makes (every thread calls it
+// with the same b and gets the same s) -> o[0..3] = {beta, SE, iterations, converged}, written by thread 0.
+template <typename F>
+__device__ __forceinline__ void firth_root(int nnz, int maxit, F &&sums, double *o)
+{
+	double beta = 0, lo = -INFINITY, hi = INFINITY, se = NAN;
+	int it = 0, state = 0;                // 0 running, 1 converged, 2 no information (I = 0 or a non-finite sum)
+	double s[4];
+	if (nnz == 0) state = 2;
+	while (state == 0 && it < maxit) {
+		it++;
+		sums(beta, s);
+		const double I = s[0], A = s[1], B = s[2];
+		const double U = s[3] + 0.5 * A / I;
+		if (!(I > 0) || !isfinite(U)) { state = 2; break; }
+		const double dU = -I + 0.5 * (B / I - (A / I) * (A / I));
+		if (U > 0) lo = beta; else if (U < 0) hi = beta;
+		double d = (dU < 0) ? -U / dU : U / I;
+		d = fmin(FIRTH_STEP_MAX, fmax(-FIRTH_STEP_MAX, d));
+		double nb = beta + d;
+		if (isfinite(lo) && isfinite(hi) && nb != beta && !(nb > lo && nb < hi)) nb = 0.5 * (lo + hi);
+		if (U == 0) nb = beta;
+		d = nb - beta;
+		beta = nb;
+		if (fabs(d) <= FIRTH_TOL * fmax(1.0, fabs(beta))) state = 1;
+	}
+	if (state == 1) {                     // SE at the root itself
+		sums(beta, s);
+		se = 1.0 / sqrt(s[0]);
+		if (!(s[0] > 0)) state = 2;
+	}
+	if (threadIdx.x == 0) {
+		o[0] = state == 2 ? NAN : beta;
+		o[1] = state == 1 ? se : NAN;
+		o[2] = (double)it;
+		o[3] = state == 1 ? 1.0 : 0.0;
+	}
 }
 
 __global__ void __launch_bounds__(FIRTH_BLOCK)
@@ -157,37 +205,6 @@ firth_kernel(const uint8_t *__restrict__ rows, size_t bpv, int N, size_t M, cons
 
 		// ---- B: the root of U*
 		const FirthList L = {mu_l, cy_l, mu_g, cy_g, nnz};
-		double beta = 0, lo = -INFINITY, hi = INFINITY, se = NAN;
-		int it = 0, state = 0;                // 0 running, 1 converged, 2 no information (I = 0 or a non-finite sum)
-		double s[4];
-		if (nnz == 0) state = 2;
-		while (state == 0 && it < maxit) {
-			it++;
-			firth_sums(beta, g, L, sh, s);
-			const double I = s[0], A = s[1], B = s[2];
-			const double U = s[3] + 0.5 * A / I;
-			if (!(I > 0) || !isfinite(U)) { state = 2; break; }
-			const double dU = -I + 0.5 * (B / I - (A / I) * (A / I));
-			if (U > 0) lo = beta; else if (U < 0) hi = beta;
-			double d = (dU < 0) ? -U / dU : U / I;
-			d = fmin(FIRTH_STEP_MAX, fmax(-FIRTH_STEP_MAX, d));
-			double nb = beta + d;
-			if (isfinite(lo) && isfinite(hi) && nb != beta && !(nb > lo && nb < hi)) nb = 0.5 * (lo + hi);
-			if (U == 0) nb = beta;
-			d = nb - beta;
-			beta = nb;
-			if (fabs(d) <= FIRTH_TOL * fmax(1.0, fabs(beta))) state = 1;
-		}
-		if (state == 1) {                     // SE at the root itself
-			firth_sums(beta, g, L, sh, s);
-			se = 1.0 / sqrt(s[0]);
-			if (!(s[0] > 0)) state = 2;
-		}
-		if (tid == 0) {
-			o[0] = state == 2 ? NAN : beta;
-			o[1] = state == 1 ? se : NAN;
-			o[2] = (double)it;
-			o[3] = state == 1 ? 1.0 : 0.0;
-		}
+		firth_root(nnz, maxit, [&](double b, double (&s)[4]) { firth_sums(b, g, L, sh, s); }, o);
 	}
 }

@@ -87,6 +87,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_kmat_ds.h"
 #include "kern_cond_kmat.h"
 #include "kern_firth.h"
+#include "kern_firth_ds.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files

@@ -13,10 +13,15 @@ parameter,
 the scan's own dosage -- mean imputation and the flip to the minor allele, ``aggregate.dosage_tables`` -- so only the
 samples with ``g != 0`` enter, and the sign is turned back to the alt allele like ``beta`` and ``beta.cond``.
 
-``firth_pass`` is the host side: it takes the flagged rows in batches of bounded bytes, reads their 2-bit rows
-(``ScanInput.packed_rows_at``: in-memory sources, host-decoded and device-decoded files alike), forms the tables from
-the ``AF.alt`` column and talks to the device through ``Scanner.firth_2bit`` alone (``sgx_firth_2bit``, kern_firth.h).
-Out of scope: dosage rows, the set-test and conditional drivers, more than one GPU.
+``firth_pass`` is the host side: it takes the flagged rows in batches of bounded bytes.  Hard calls (``genotype/data``,
+packed in-memory rows, an in-memory uint8 / int32 matrix of hard calls): their 2-bit rows (``ScanInput.packed_rows_at``:
+in-memory sources, host-decoded and device-decoded files alike), the tables from the ``AF.alt`` column, and
+``Scanner.firth_2bit`` (``sgx_firth_2bit``, kern_firth.h).  Dosages (a ``dsnode``, a file of ``annotation/format/DS``
+alone, a stored packed-real or float32 node, any other in-memory matrix): the rows by ``ScanInput.dosage_reader`` -- a
+stored node in its file form -- into one resident ``DosageBlock``, flip and mean from the load's own counts
+(``aggregate.flip_mean``, as the conditional driver), and ``DosageBlock.firth`` (``sgx_ds_block_firth``,
+kern_firth_ds.h).  Dosage input on a scanner without ``dosage_block``, or whose block has no ``firth``, is refused.
+Out of scope: the set-test and conditional drivers, more than one GPU.
 """
 from __future__ import annotations
 
@@ -40,24 +45,47 @@ def firth_tables(af: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     return aggregate.dosage_tables(flip.astype(np.uint8), mean), flip
 
 
-def hard_call_input(inp):
-    """The opened input of a driver call as 2-bit rows: hard calls as they are, an in-memory uint8 / int32 matrix that
-    holds 0, 1, 2 and the missing code only as the rows it means (``aggregate.reduce_hard_calls``); any other input --
-    a dosage node, a file of dosages only, a matrix of other values -- is refused."""
+def firth_input(inp, scanner_cls):
+    """The opened input of a driver call as the Firth pass takes it: hard calls as 2-bit rows -- as they are, or an
+    in-memory uint8 / int32 matrix that holds 0, 1, 2 and the missing code only as the rows it means
+    (``aggregate.reduce_hard_calls``); any other input -- a dosage node, a file of dosages only, a matrix of other
+    values -- as dosage rows of the type the scan gives them (uint8, int32 for other integers, else float64), refused
+    where ``scanner_cls`` has no ``dosage_block``."""
     if inp.kind == "dosage" and inp.in_mem:
         ds = np.asarray(inp.ds_all)
         if ds.ndim == 2 and ds.dtype in (np.uint8, np.int32):
             inp = aggregate.reduce_hard_calls(dataclasses.replace(inp, ds_all=ds, ds_dtype=ds.dtype))
-    if inp.kind != "packed":
+    if inp.kind == "packed":
+        return inp
+    if not hasattr(scanner_cls, "dosage_block"):
         raise NotImplementedError(NO_DOSAGE)
+    if inp.in_mem:
+        ds = np.asarray(inp.ds_all)
+        dt = ds.dtype if ds.dtype == np.uint8 else np.dtype(np.int32 if np.issubdtype(ds.dtype, np.integer) else np.float64)
+        inp = dataclasses.replace(inp, ds_all=ds, ds_dtype=dt)
     return inp
 
 
-def firth_pass(inp, out: np.ndarray, valid: np.ndarray, rows, make_scanner: Callable, maxit: int = 50):
+def dosage_route(inp, make_scanner) -> bool:
+    """Dosage input, before any row is scanned: the scanner's dosage block must have ``firth`` (else
+    ``NotImplementedError``) -> whether a stored node goes to it in its file form (the block has ``load_packed``)."""
+    sc = make_scanner()
+    try:
+        with sc.dosage_block(inp.ds_dtype, 1) as blk:
+            if not hasattr(blk, "firth"):
+                raise NotImplementedError(NO_DOSAGE)
+            return inp.kind == "stored" and hasattr(blk, "load_packed")
+    finally:
+        sc.close()
+
+
+def firth_pass(inp, out: np.ndarray, valid: np.ndarray, rows, make_scanner: Callable, maxit: int = 50, stored: bool = False):
     """Firth fits of the variants ``rows`` (0-based indices into the input's variants) of a finished scan: ``out``
-    [n_var, 8] and ``valid`` [n_var] are the scan's table and flags.  ``make_scanner()`` gives an object with
-    ``firth_2bit(packed, lut, maxit)`` and ``close()`` for the model of these rows.  -> (beta, SE, converged), each
-    [n_var]: NaN / NaN / False off ``rows``; beta refers to the alt allele."""
+    [n_var, 8] and ``valid`` [n_var] are the scan's table and flags.  ``make_scanner()`` gives an object for the model of
+    these rows with ``close()`` and, for 2-bit input, ``firth_2bit(packed, lut, maxit)``; for dosage input
+    ``dosage_block(dtype, max_variants)`` whose block has ``load`` (``stored``, from ``dosage_route``: ``load_packed``)
+    and ``firth(var_idx, flip, mean, maxit)``.  -> (beta, SE, converged), each [n_var]: NaN / NaN / False off ``rows``;
+    beta refers to the alt allele."""
     n_var = out.shape[0]
     beta, se = np.full(n_var, np.nan), np.full(n_var, np.nan)
     cvg = np.zeros(n_var, dtype=bool)
@@ -65,18 +93,35 @@ def firth_pass(inp, out: np.ndarray, valid: np.ndarray, rows, make_scanner: Call
     rows = rows[np.asarray(valid)[rows] != 0]
     if rows.size == 0:
         return beta, se, cvg
-    if inp.kind != "packed":
-        raise NotImplementedError(NO_DOSAGE)
-    per = max(1, FIRTH_BATCH_BYTES // max(1, (inp.n_samp + 3) // 4))
+
+    def put(idx, flip, o4):
+        beta[idx] = np.where(flip, -o4[:, 0], o4[:, 0])
+        se[idx] = o4[:, 1]
+        cvg[idx] = o4[:, 3] == 1
+
     sc = make_scanner()
     try:
-        for a in range(0, rows.size, per):
-            idx = rows[a:a + per]
-            lut, flip = firth_tables(out[idx, 0])
-            o4 = np.asarray(sc.firth_2bit(inp.packed_rows_at(idx), lut, int(maxit)))
-            beta[idx] = np.where(flip, -o4[:, 0], o4[:, 0])
-            se[idx] = o4[:, 1]
-            cvg[idx] = o4[:, 3] == 1
+        if inp.kind == "packed":
+            per = max(1, FIRTH_BATCH_BYTES // max(1, (inp.n_samp + 3) // 4))
+            for a in range(0, rows.size, per):
+                idx = rows[a:a + per]
+                lut, flip = firth_tables(out[idx, 0])
+                put(idx, flip, np.asarray(sc.firth_2bit(inp.packed_rows_at(idx), lut, int(maxit))))
+        else:
+            make = getattr(sc, "dosage_block", None)
+            if make is None:
+                raise NotImplementedError(NO_DOSAGE)
+            read_rows, dtype = inp.dosage_reader(stored), inp.ds_dtype
+            per = max(1, aggregate.DS_BUDGET // max(1, aggregate.ds_row_bytes(dtype, inp.n_samp)))
+            with make(dtype, min(per, rows.size)) as blk:
+                if not hasattr(blk, "firth"):
+                    raise NotImplementedError(NO_DOSAGE)
+                for a in range(0, rows.size, per):
+                    idx = rows[a:a + per]
+                    n, s, _ = aggregate.load_rows(blk, read_rows(idx))        # the one upload; the load's own counts
+                    flip, mean = aggregate.flip_mean(n, s)
+                    o4 = np.asarray(blk.firth(np.arange(idx.size, dtype=np.int32), flip, mean, int(maxit)))
+                    put(idx, flip != 0, o4)
     finally:
         sc.close()
     return beta, se, cvg
