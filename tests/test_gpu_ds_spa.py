@@ -2,7 +2,8 @@
 spa_pval = 0.05, so that the flagged variants go through spa4_moments_ds<K, NC, INPUT> (segments of spa_seg(K) samples,
 both tiers), spa4_solve and the IN_U8 / IN_F64 forms of the per-variant kernels -- or, under "score_v1", through
 spa_kernel<K, 512, INPUT> alone.  Full rows against the CPU oracle; the score stage on its own is
-test_gpu_ds_score.py's."""
+test_gpu_ds_score.py's.  Dosage rows always start in tier A; 2-bit rows are routed by their carrier count and reach
+the cumulant pass only with more than 8192 carriers: see test_gpu_spa2b.py."""
 import numpy as np
 import pytest
 
