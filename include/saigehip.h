@@ -780,6 +780,28 @@ int sgx_ds_block_cond_kmat(sgx_handle *h, sgx_kmat *km, const sgx_dsblock *b, co
 	const double *mean, double *score, double *var, double *cov /* [rows loaded][n_cond] */,
 	int32_t *iters /* per row, may be NULL */);
 
+/* SKAT-O: the null eigenvalues of a batch of units (saigegds_amd/skato.py; nothing of this is in the reference, DESIGN.md
+ * 8k).  Problem u is a symmetric m[u] x m[u] matrix A_u = diag(w) Phi diag(w) in HOST memory; the matrices are
+ * concatenated row-major as sgx_skat_2bit lays out cov (only the upper triangles are read).  One grid rho[n_rho],
+ * strictly increasing within [0, 1], is shared by all problems.  With r = A 1, c = 1'A 1 (summed in a fixed order),
+ * a = sqrt(1 - rho) and b = (sqrt(1 - rho + m rho) - a) / m, the n_rho + 1 matrices of a problem are
+ *   k < n_rho:   B_rho[k] = R^(1/2) A R^(1/2),  R = (1 - rho) I + rho 11':   B_ij = a^2 A_ij + a b (r_i + r_j) + b^2 c
+ *   k = n_rho:   W = A - r r' / c
+ * (a grid of more than one value takes a value above 0.999 as 0.999; W is not clipped).
+ *   eig      per problem (n_rho + 1) * m[u] doubles at (n_rho + 1) times the sum of m[v] over v < u: matrix k's
+ *            eigenvalues ascending at k * m[u]
+ *   sweeps   [n][n_rho + 1]: the Jacobi sweeps that rotated (0: the matrix was diagonal), at most 30
+ * One workgroup per matrix runs a cyclic two-sided Jacobi iteration in FP64 (kern_eig.h): the matrix in LDS up to
+ * m = 128, above that in a slice of device scratch; no eigenvectors, no atomics, a fixed order throughout, so a
+ * matrix's eigenvalues have the same bits from call to call and do not depend on the other problems of the call, on
+ * their order or on the other grid values; scaling A by a power of two scales them exactly.  rho = 0 iterates on A's own
+ * bits.  A matrix with a non-finite entry (in A, or as formed: c = 0 for W) gets NaN eigenvalues and sweeps = -1 and
+ * leaves the others alone.  n = 0 and m[u] = 0 are legal.  m[u] outside [0, SGX_SKATO_MAX_M], a bad grid or a NULL
+ * buffer returns SGX_EINVAL and launches nothing; the handle stays usable.  Synchronous. */
+#define SGX_SKATO_MAX_M 256
+int sgx_skato_spectra(sgx_handle *h, size_t n, const int32_t *m, const double *mats, size_t n_rho,
+	const double *rho, double *eig, int32_t *sweeps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ Public surface (mirrors the reference's R API for this path):
     init_nullmod       .init_nullmod                  (R/assoc_single.r:17-67)
     seqGLMM_GxG_spa    SNP x SNP interaction test     (R/saige_interaction.r:44-641)
     seqAssocGLMM_spaSKAT  variance-component set test (not in the reference)
+    seqAssocGLMM_spaSKATO SKAT-O: burden and SKAT combined over a grid of rho (not in the reference)
     seqAssocGLMM_SPA_cond scan given a set of conditioning variants (not in the reference)
     seqFitDenseGRM, seqFitSparseGRM  the explicit GRM, dense and thresholded (not in the reference)
     load_grm, ExplicitGrmOperator    read it back; the operator seqFitNullGLMM_SPA(grm_mat=) fits on
@@ -19,6 +20,7 @@ from .gxg import DosageMatrix, GxGTable, saddle_prob, seqGLMM_GxG_spa  # noqa: F
 from .aggregate import (AggrParamBeta, pACAT, pACAT2, seqAssocGLMM_spaACAT_O, seqAssocGLMM_spaACAT_V,  # noqa: F401
                         seqAssocGLMM_spaBurden)
 from .skat import pchisq_mix, seqAssocGLMM_spaSKAT  # noqa: F401
+from .skato import pchisq_mix_vec, seqAssocGLMM_spaSKATO, skato_pvalue  # noqa: F401
 from .cond import cond_tests, seqAssocGLMM_SPA_cond  # noqa: F401
 from .grm import SparseGRM, load_grm, seqFitDenseGRM, seqFitSparseGRM  # noqa: F401
 from ._lib import ExplicitGrmOperator  # noqa: F401

@@ -19,6 +19,7 @@ GRM_MAX_GROUPS = 64   # SGX_GRM_MAX_GROUPS: marker groups of one GRM handle
 KMAT_WAVE_ROW = 33    # SGX_KMAT_WAVE_ROW: CSR rows of sgx_kmat with at least this many entries take the wave form
 ENOSPACE = -5         # SGX_ENOSPACE: sgx_grm_sparse found more entries than the buffers hold
 SKAT_MAX_VARIANTS = 4096   # SGX_SKAT_MAX_VARIANTS: entries of one unit of sgx_skat_2bit
+SKATO_MAX_M = 256     # SGX_SKATO_MAX_M: order of one matrix of sgx_skato_spectra
 COND_MAX = 16         # SGX_COND_MAX: conditioning variants of one sgx_cond_set
 DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
 DS_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float64): 2}   # SGX_DS_U8 / _I32 / _F64
@@ -205,6 +206,7 @@ def _abi():
         "sgx_ds_block_skat_kmat": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
         "sgx_ds_block_cond_kmat_set": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
         "sgx_ds_block_cond_kmat": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sgx_skato_spectra": (ci, [vp, sz, vp, vp, sz, vp, vp, vp]),
     }
 
 
@@ -456,6 +458,27 @@ class Scanner(_Handle):
         ms = np.zeros(3)
         check(self._L.sgx_skat_kmat_ms(self._h, ms.ctypes.data))
         return ms
+
+    def skato_spectra(self, mats, rho):
+        """The SKAT-O null eigenvalues of a batch of units (``sgx_skato_spectra``): ``mats`` a list of symmetric [m, m]
+        matrices ``A = diag(w) Phi diag(w)`` (m up to ``SKATO_MAX_M``), ``rho`` the grid shared by all -> (per problem
+        an array [len(rho) + 1, m]: row k the eigenvalues of ``B_rho[k]`` ascending, the last row those of ``W = A -
+        r r' / c``, not clipped; sweeps [n, len(rho) + 1] int32: Jacobi sweeps that rotated, -1 where the matrix held a
+        non-finite entry and its eigenvalues are NaN)."""
+        mats = [np.ascontiguousarray(a, dtype=np.float64) for a in mats]
+        if any(a.ndim != 2 or a.shape[0] != a.shape[1] for a in mats):
+            raise ValueError("skato_spectra: every problem must be a square matrix")
+        rho = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
+        n, nmat = len(mats), rho.size + 1
+        m = np.array([a.shape[0] for a in mats], dtype=np.int32)
+        flat = np.concatenate([a.ravel() for a in mats]) if n else np.zeros(0)
+        flat = np.ascontiguousarray(flat) if flat.size else np.zeros(1)
+        eig = np.zeros(max(1, nmat * int(m.sum(dtype=np.int64))))
+        sweeps = np.zeros((max(1, n), nmat), dtype=np.int32)
+        check(self._L.sgx_skato_spectra(self._h, n, m.ctypes.data if n else None, flat.ctypes.data, rho.size,
+                                        rho.ctypes.data if rho.size else None, eig.ctypes.data, sweeps.ctypes.data))
+        offs = np.concatenate([[0], np.cumsum(m.astype(np.int64) * nmat)])
+        return [eig[offs[u]:offs[u + 1]].reshape(nmat, m[u]) for u in range(n)], sweeps[:n]
 
     def cond_set(self, packed_c: np.ndarray, lut_c):
         """Installs the conditioning set of the conditional scan (``sgx_cond_set``): its 2-bit rows and 4-entry dosage

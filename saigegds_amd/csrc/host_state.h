@@ -146,6 +146,12 @@ struct sgx_handle {
 	DevBuf<double> cond_part, cond_fin;
 	// Firth effect sizes (host_firth.h): per-workgroup slices for the lists that do not fit LDS, allocated on first use
 	DevBuf<uint8_t> firth_scr;
+	// sgx_skato_spectra (host_skato.h): the matrices, the eigenvalues, the sweep counts, offsets and lists, and the
+	// workgroups' slices of the class whose working matrix does not fit LDS
+	DevBuf<double> eig_A, eig_out, eig_scr;
+	DevBuf<int> eig_sw;
+	DevBuf<uint8_t> eig_meta;
+	bool eig_attr_set = false;
 	bool evk_set = false;
 	bool lists_timed = false;
 	sgx_stats stats{};

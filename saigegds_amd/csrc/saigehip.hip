@@ -88,6 +88,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_cond_kmat.h"
 #include "kern_firth.h"
 #include "kern_firth_ds.h"
+#include "kern_eig.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -113,3 +114,4 @@ static int fail(int code, const char *fmt, ...)
 #include "host_cond_kmat.h"
 #include "host_kmat_ds.h"
 #include "host_firth.h"
+#include "host_skato.h"
