@@ -311,6 +311,37 @@ def _unit_matrices(cov: np.ndarray, sizes, offs):
     return [cov[offs[u]:offs[u + 1]].reshape(sizes[u], sizes[u]) for u in range(sizes.size)]
 
 
+def _row_tables(what: str, packed, lut, per: str = "row"):
+    """2-bit rows with one 4-entry dosage table each -> (packed uint8, lut float64 [m, 4])."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint8)
+    lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
+    if packed.ndim != 2 or lut.shape[0] != packed.shape[0]:
+        raise ValueError(f"{what}: one table per {per}")
+    return packed, lut
+
+
+def _flip_mean(what: str, msg: str, flip, mean, var_idx=None, n: int = 0):
+    """``flip`` / ``mean`` of the entries on a dosage block, one per entry of ``var_idx`` or, without it, ``n`` of each
+    -> (flip uint8, mean float64, var_idx int32)."""
+    flip = np.ascontiguousarray(flip, dtype=np.uint8)
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    if var_idx is not None:
+        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
+    shape = (n,) if var_idx is None else var_idx.shape
+    if len(shape) != 1 or flip.shape != shape or mean.shape != shape:
+        raise ValueError(f"{what}: {msg}")
+    return flip, mean, var_idx
+
+
+def _sigma_args(what: str, op, w, tau):
+    """``w`` [samples of the matrix] and ``tau`` [2] of the entries on an explicit GRM, as float64."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    tau = np.ascontiguousarray(tau, dtype=np.float64)
+    if w.shape != (op.n,) or tau.shape != (2,):
+        raise ValueError(f"{what}: w must have one entry per sample of the matrix and tau two entries")
+    return w, tau
+
+
 class Scanner(_Handle):
     """One model resident on one GPU (an ``sgx_handle``)."""
 
@@ -439,11 +470,8 @@ class Scanner(_Handle):
         iters [entries]: PCG steps of every entry's solve)."""
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
         lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        tau = np.ascontiguousarray(tau, dtype=np.float64)
         unit_ptr, var_idx, n_units, sizes, offs = _unit_args("skat_kmat", unit_ptr, var_idx, [(lut, (4,))], packed.ndim == 2)
-        if w.shape != (op.n,) or tau.shape != (2,):
-            raise ValueError("skat_kmat: w must have one entry per sample of the matrix and tau two entries")
+        w, tau = _sigma_args("skat_kmat", op, w, tau)
         score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
         iters = np.zeros(max(1, var_idx.size), dtype=np.int32)
         if var_idx.size:
@@ -484,10 +512,7 @@ class Scanner(_Handle):
         """Installs the conditioning set of the conditional scan (``sgx_cond_set``): its 2-bit rows and 4-entry dosage
         tables -> (score_c [C], cov_cc [C, C]), which equal ``skat_2bit`` on the rows as one unit bit for bit.  No rows
         clears the set."""
-        packed_c = np.ascontiguousarray(packed_c, dtype=np.uint8)
-        lut_c = np.ascontiguousarray(lut_c, dtype=np.float64).reshape(-1, 4)
-        if packed_c.ndim != 2 or lut_c.shape[0] != packed_c.shape[0]:
-            raise ValueError("cond_set: one table per conditioning row")
+        packed_c, lut_c = _row_tables("cond_set", packed_c, lut_c, "conditioning row")
         c = packed_c.shape[0]
         score, cov = np.zeros(max(1, c)), np.zeros(max(1, c * c))
         check(self._L.sgx_cond_set(self._h, packed_c.ctypes.data, packed_c.shape[1], c, lut_c.ctypes.data,
@@ -498,10 +523,7 @@ class Scanner(_Handle):
     def cond_2bit(self, packed: np.ndarray, lut):
         """Score, variance and covariances with the installed conditioning set of every 2-bit row (one 4-entry dosage
         table each; ``sgx_cond_2bit``) -> (score [m], var [m], cov [m, C])."""
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
-        if packed.ndim != 2 or lut.shape[0] != packed.shape[0]:
-            raise ValueError("cond_2bit: one table per row")
+        packed, lut = _row_tables("cond_2bit", packed, lut)
         m, c = packed.shape[0], getattr(self, "_n_cond", 0)
         score, var, cov = np.zeros(m), np.zeros(m), np.zeros((m, max(1, c)))
         check(self._L.sgx_cond_2bit(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data,
@@ -513,14 +535,8 @@ class Scanner(_Handle):
         on this scanner's device; ``sgx_cond_kmat_set``): rows, tables, ``w`` and ``tau`` as for ``skat_kmat`` ->
         (S_C [C], Phi^K_CC [C, C], iters [C]), which equal ``skat_kmat`` on the rows as one unit bit for bit.  No rows
         clears the set; the set of ``cond_set`` is not touched."""
-        packed_c = np.ascontiguousarray(packed_c, dtype=np.uint8)
-        lut_c = np.ascontiguousarray(lut_c, dtype=np.float64).reshape(-1, 4)
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        tau = np.ascontiguousarray(tau, dtype=np.float64)
-        if packed_c.ndim != 2 or lut_c.shape[0] != packed_c.shape[0]:
-            raise ValueError("cond_kmat_set: one table per conditioning row")
-        if w.shape != (op.n,) or tau.shape != (2,):
-            raise ValueError("cond_kmat_set: w must have one entry per sample of the matrix and tau two entries")
+        packed_c, lut_c = _row_tables("cond_kmat_set", packed_c, lut_c, "conditioning row")
+        w, tau = _sigma_args("cond_kmat_set", op, w, tau)
         c = packed_c.shape[0]
         score, cov, iters = np.zeros(max(1, c)), np.zeros(max(1, c * c)), np.zeros(max(1, c), dtype=np.int32)
         check(self._L.sgx_cond_kmat_set(self._h, op._h, packed_c.ctypes.data, packed_c.shape[1], c, lut_c.ctypes.data,
@@ -533,10 +549,7 @@ class Scanner(_Handle):
         """Score, variance and covariances with the set of ``cond_kmat_set`` of every 2-bit row under the fitted model on
         the explicit GRM (``sgx_cond_kmat_2bit``) -> (score [m], var [m], cov [m, C], iters [m]: PCG steps of the
         row's column)."""
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
-        if packed.ndim != 2 or lut.shape[0] != packed.shape[0]:
-            raise ValueError("cond_kmat: one table per row")
+        packed, lut = _row_tables("cond_kmat", packed, lut)
         m, c = packed.shape[0], getattr(self, "_n_cond_kmat", 0)
         score, var, cov, iters = np.zeros(m), np.zeros(m), np.zeros((m, max(1, c))), np.zeros(m, dtype=np.int32)
         check(self._L.sgx_cond_kmat_2bit(self._h, op._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data,
@@ -552,10 +565,7 @@ class Scanner(_Handle):
         """Firth bias-reduced effect size of every 2-bit row (one 4-entry dosage table each; ``sgx_firth_2bit``; binary
         traits) -> out4 [m, 4]: beta for the table's orientation, SE, iterations, converged (1 / 0).  NaN / NaN / 0 for a
         row without a non-zero dosage or with a non-finite table value."""
-        packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        lut = np.ascontiguousarray(lut, dtype=np.float64).reshape(-1, 4)
-        if packed.ndim != 2 or lut.shape[0] != packed.shape[0]:
-            raise ValueError("firth_2bit: one table per row")
+        packed, lut = _row_tables("firth_2bit", packed, lut)
         m = packed.shape[0]
         out4 = np.zeros((max(1, m), 4))
         check(self._L.sgx_firth_2bit(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data, int(maxit),
@@ -748,11 +758,7 @@ class DosageBlock(_Handle):
         ``COND_MAX`` rows ``var_idx`` with ``flip`` / ``mean`` as for ``skat`` -> (S_C [C], Phi_CC [C, C]), equal to
         ``skat`` on them as one unit bit for bit.  The scanner keeps the set (as ``Scanner.cond_set`` does) beyond the
         block's next load; no row clears it."""
-        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
-        flip = np.ascontiguousarray(flip, dtype=np.uint8)
-        mean = np.ascontiguousarray(mean, dtype=np.float64)
-        if var_idx.ndim != 1 or flip.shape != var_idx.shape or mean.shape != var_idx.shape:
-            raise ValueError("DosageBlock.cond_set: inconsistent table shapes")
+        flip, mean, var_idx = _flip_mean("DosageBlock.cond_set", "inconsistent table shapes", flip, mean, var_idx)
         c = var_idx.size
         score, cov = np.zeros(max(1, c)), np.zeros(max(1, c * c))
         check(self._L.sgx_ds_block_cond_set(self._sc._h, self._b, c, var_idx.ctypes.data, flip.ctypes.data,
@@ -764,10 +770,7 @@ class DosageBlock(_Handle):
         """Score, variance and covariances with the installed set of every resident row (``flip`` / ``mean`` per
         resident row; ``sgx_ds_block_cond``) -> (score [m], var [m], cov [m, C])."""
         m = self.n_variants
-        flip = np.ascontiguousarray(flip, dtype=np.uint8)
-        mean = np.ascontiguousarray(mean, dtype=np.float64)
-        if flip.shape != (m,) or mean.shape != (m,):
-            raise ValueError("DosageBlock.cond: one flip and one mean per resident row")
+        flip, mean, _ = _flip_mean("DosageBlock.cond", "one flip and one mean per resident row", flip, mean, n=m)
         c = int(getattr(self._sc, "_n_cond", 0))
         score, var, cov = np.zeros(max(1, m)), np.zeros(max(1, m)), np.zeros(max(1, m * c))
         check(self._L.sgx_ds_block_cond(self._sc._h, self._b, flip.ctypes.data, mean.ctypes.data, score.ctypes.data,
@@ -780,23 +783,12 @@ class DosageBlock(_Handle):
         entry's orientation, SE, iterations, converged (1 / 0), as ``Scanner.firth_2bit`` -- bit for bit what it gives on
         the 2-bit form of a row of hard calls.  NaN / NaN / 0 for a row without a non-zero dosage or with a non-finite
         mean."""
-        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
-        flip = np.ascontiguousarray(flip, dtype=np.uint8)
-        mean = np.ascontiguousarray(mean, dtype=np.float64)
-        if var_idx.ndim != 1 or flip.shape != var_idx.shape or mean.shape != var_idx.shape:
-            raise ValueError("DosageBlock.firth: one flip and one mean per entry of var_idx")
+        flip, mean, var_idx = _flip_mean("DosageBlock.firth", "one flip and one mean per entry of var_idx", flip, mean, var_idx)
         m = var_idx.size
         out4 = np.zeros((max(1, m), 4))
         check(self._L.sgx_ds_block_firth(self._sc._h, self._b, m, var_idx.ctypes.data, flip.ctypes.data, mean.ctypes.data,
                                          int(maxit), out4.ctypes.data))
         return out4[:m]
-
-    def _sigma_args(self, what: str, op, w, tau):
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        tau = np.ascontiguousarray(tau, dtype=np.float64)
-        if w.shape != (op.n,) or tau.shape != (2,):
-            raise ValueError(f"{what}: w must have one entry per sample of the matrix and tau two entries")
-        return w, tau
 
     def skat_kmat(self, op, unit_ptr, var_idx, flip, mean, w, tau, maxiter: int = 500, tol: float = 1e-5):
         """``skat`` with the covariance under the fitted model on the explicit GRM of ``op`` (an ``ExplicitGrmOperator``
@@ -805,7 +797,7 @@ class DosageBlock(_Handle):
         An entry whose mean is not finite gets non-finite results, whether or not a sample of its row is missing."""
         flip = np.ascontiguousarray(flip, dtype=np.uint8)
         mean = np.ascontiguousarray(mean, dtype=np.float64)
-        w, tau = self._sigma_args("DosageBlock.skat_kmat", op, w, tau)
+        w, tau = _sigma_args("DosageBlock.skat_kmat", op, w, tau)
         unit_ptr, var_idx, n_units, sizes, offs = _unit_args("DosageBlock.skat_kmat", unit_ptr, var_idx,
                                                              [(flip, ()), (mean, ())])
         score, cov = np.zeros(max(1, var_idx.size)), np.zeros(max(1, int(offs[-1])))
@@ -822,12 +814,8 @@ class DosageBlock(_Handle):
         (``sgx_ds_block_cond_kmat_set``): rows ``var_idx`` with ``flip`` / ``mean`` as for ``skat`` -> (S_C [C],
         Phi^K_CC [C, C], iters [C]), equal to ``skat_kmat`` on them as one unit bit for bit.  The scanner keeps the set
         (the one ``Scanner.cond_kmat_set`` fills) beyond the block's next load; no row clears it."""
-        var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
-        flip = np.ascontiguousarray(flip, dtype=np.uint8)
-        mean = np.ascontiguousarray(mean, dtype=np.float64)
-        if var_idx.ndim != 1 or flip.shape != var_idx.shape or mean.shape != var_idx.shape:
-            raise ValueError("DosageBlock.cond_kmat_set: inconsistent table shapes")
-        w, tau = self._sigma_args("DosageBlock.cond_kmat_set", op, w, tau)
+        flip, mean, var_idx = _flip_mean("DosageBlock.cond_kmat_set", "inconsistent table shapes", flip, mean, var_idx)
+        w, tau = _sigma_args("DosageBlock.cond_kmat_set", op, w, tau)
         c = var_idx.size
         score, cov, iters = np.zeros(max(1, c)), np.zeros(max(1, c * c)), np.zeros(max(1, c), dtype=np.int32)
         check(self._L.sgx_ds_block_cond_kmat_set(self._sc._h, op._h, self._b, c, var_idx.ctypes.data, flip.ctypes.data,
@@ -841,10 +829,7 @@ class DosageBlock(_Handle):
         on the explicit GRM (``flip`` / ``mean`` per resident row; ``sgx_ds_block_cond_kmat``) -> (score [m], var [m],
         cov [m, C], iters [m]: PCG steps of the row's column), as ``Scanner.cond_kmat``."""
         m = self.n_variants
-        flip = np.ascontiguousarray(flip, dtype=np.uint8)
-        mean = np.ascontiguousarray(mean, dtype=np.float64)
-        if flip.shape != (m,) or mean.shape != (m,):
-            raise ValueError("DosageBlock.cond_kmat: one flip and one mean per resident row")
+        flip, mean, _ = _flip_mean("DosageBlock.cond_kmat", "one flip and one mean per resident row", flip, mean, n=m)
         c = int(getattr(self._sc, "_n_cond_kmat", 0))
         score, var, cov = np.zeros(max(1, m)), np.zeros(max(1, m)), np.zeros(max(1, m * c))
         iters = np.zeros(max(1, m), dtype=np.int32)

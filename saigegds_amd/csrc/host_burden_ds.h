@@ -61,12 +61,10 @@ static int dsblock_check(sgx_handle *h, const sgx_dsblock *b, const char *who)
 // ds_stats_kernel on the M rows just put into the block, the counts to the caller; the block is loaded when they are back
 static int dsblock_counts(sgx_handle *h, sgx_dsblock *b, size_t M, int32_t *n_valid, double *sum, int64_t *sum_trunc)
 {
-	if (b->dtype == SGX_DS_U8)
-		hipLaunchKernelGGL((ds_stats_kernel<uint8_t>), dim3((unsigned)M), dim3(256), 0, h->stream,
-			(const uint8_t *)b->rows, b->N, b->d_nv, b->d_sum, b->d_trunc);
-	else
-		hipLaunchKernelGGL((ds_stats_kernel<double>), dim3((unsigned)M), dim3(256), 0, h->stream,
-			(const double *)b->rows.p, b->N, b->d_nv, b->d_sum, b->d_trunc);
+	with_ds_rows(b->dtype, b->rows.p, [&](auto *rows, auto t) {
+		hipLaunchKernelGGL((ds_stats_kernel<decltype(t)>), dim3((unsigned)M), dim3(256), 0, h->stream,
+			rows, b->N, b->d_nv, b->d_sum, b->d_trunc);
+	});
 	HIPCHK(hipGetLastError());
 	static_assert(sizeof(long long) == sizeof(int64_t), "sum_trunc");
 	HIPCHK(hipMemcpyAsync(n_valid, b->d_nv, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -154,9 +152,8 @@ extern "C" int sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out
 	if (rc) return rc;
 	if (!out8 || !valid) return fail(SGX_EINVAL, "sgx_dsblock_scan: NULL buffer");
 	if (b->M == 0) return fail(SGX_EINVAL, "sgx_dsblock_scan: nothing loaded");
-	rc = sync_lane(h);
+	rc = begin_call(h);
 	if (rc) return rc;
-	h->last_issued = h;
 	const size_t N = (size_t)b->N, M = b->M;
 	const size_t per_row = b->dtype == SGX_DS_U8 ? N : b->dtype == SGX_DS_I32 ? N * (sizeof(int32_t) + sizeof(double)) : N * sizeof(double);
 	const size_t chunk = scan_chunk(h, per_row, M);
@@ -216,26 +213,18 @@ extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_
 	if (rc) return rc;
 	if (bad) return fail(SGX_EINVAL, "sgx_dsblock_burden: variant index %d outside the block's %zu rows", *bad, b->M);
 	const int64_t nnz = grp_ptr[n_groups];
-	rc = sync_lane(h);
+	rc = begin_call(h);
 	if (rc) return rc;
-	h->last_issued = h;
-	// device copies of the tables
-	sgx_dsblock *bm = const_cast<sgx_dsblock *>(b);
-	const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
-	const size_t o_idx = ((n_groups + 1) * sizeof(long long) + 15) & ~(size_t)15;
-	const size_t o_w = (o_idx + ne * sizeof(int) + 15) & ~(size_t)15;
-	const size_t o_mw = o_w + ne * (size_t)n_cols * sizeof(double);
-	const size_t o_flip = o_mw + ne * (size_t)n_cols * sizeof(double);
-	rc = grow(bm->tabs, o_flip + ne);
-	if (rc) return rc;
+	// device copies of the tables (those of the entries are empty slots where no group has one)
 	std::vector<long long> gp(grp_ptr, grp_ptr + n_groups + 1);
-	HIPCHK(hipMemcpyAsync(b->tabs, gp.data(), gp.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-	if (nnz > 0) {
-		HIPCHK(hipMemcpyAsync(b->tabs + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, h->stream));
-		HIPCHK(hipMemcpyAsync(b->tabs + o_w, w, (size_t)nnz * n_cols * sizeof(double), hipMemcpyHostToDevice, h->stream));
-		HIPCHK(hipMemcpyAsync(b->tabs + o_mw, mw, (size_t)nnz * n_cols * sizeof(double), hipMemcpyHostToDevice, h->stream));
-		HIPCHK(hipMemcpyAsync(b->tabs + o_flip, flip, (size_t)nnz, hipMemcpyHostToDevice, h->stream));
-	}
+	TabLayout tl;
+	const auto s_gp = tl.add(gp.size(), gp.data());
+	const auto s_idx = tl.add(nnz, var_idx);
+	const auto s_w = tl.add((size_t)nnz * n_cols, w), s_mw = tl.add((size_t)nnz * n_cols, mw);
+	const auto s_flip = tl.add(nnz, flip);
+	rc = grow(const_cast<sgx_dsblock *>(b)->tabs, tl.bytes());
+	if (!rc) rc = tabs_upload(b->tabs, h->stream, s_gp, s_idx, s_w, s_mw, s_flip);
+	if (rc) return rc;
 	HIPCHK(hipStreamSynchronize(h->stream));      // gp is a local
 	const int N = b->N;
 	const size_t row_bytes = (size_t)N * sizeof(double);
@@ -246,20 +235,14 @@ extern "C" int sgx_dsblock_burden(sgx_handle *h, const sgx_dsblock *b, size_t n_
 	rc = ensure_recs(h, gchunk * n_cols);
 	if (rc) return rc;
 	sgx_stats total{};
-	const long long *d_gp = reinterpret_cast<const long long *>(b->tabs.p);
-	const int *d_idx = reinterpret_cast<const int *>(b->tabs + o_idx);
-	const double *d_w = reinterpret_cast<const double *>(b->tabs + o_w), *d_mw = reinterpret_cast<const double *>(b->tabs + o_mw);
-	const uint8_t *d_flip = b->tabs + o_flip;
 	for (size_t off = 0; off < n_groups; off += gchunk) {
 		const size_t ng = std::min(gchunk, n_groups - off), m = ng * (size_t)n_cols;
 		for (int c0 = 0; c0 < n_cols; c0 += SGX_DS_COLS_PER_PASS) {
 			const int nc = std::min(SGX_DS_COLS_PER_PASS, n_cols - c0);
-			if (b->dtype == SGX_DS_U8)
-				launch_collapse_ds<uint8_t>(h->stream, (const uint8_t *)b->rows, N, ng, d_gp + off, d_idx, d_flip, n_cols, c0, nc,
-					d_w, d_mw, reinterpret_cast<double *>(h->stage_in.p));
-			else
-				launch_collapse_ds<double>(h->stream, (const double *)b->rows.p, N, ng, d_gp + off, d_idx, d_flip, n_cols, c0, nc,
-					d_w, d_mw, reinterpret_cast<double *>(h->stage_in.p));
+			with_ds_rows(b->dtype, b->rows.p, [&](auto *rows, auto) {
+				launch_collapse_ds(h->stream, rows, N, ng, tl.at(b->tabs, s_gp) + off, tl.at(b->tabs, s_idx), tl.at(b->tabs, s_flip),
+					n_cols, c0, nc, tl.at(b->tabs, s_w), tl.at(b->tabs, s_mw), reinterpret_cast<double *>(h->stage_in.p));
+			});
 			HIPCHK(hipGetLastError());
 		}
 		rc = scan_staged<IN_F64>(h, h->stage_in, row_bytes, m, out8 + off * n_cols * 8, valid + off * n_cols, total);

@@ -8,6 +8,29 @@ static const size_t COND_PART_BYTES = (size_t)256 << 20;    // per-slab partial 
 
 static int cond_ncol(const sgx_handle *p) { return 2 * p->md.K + 1 + p->n_cond; }
 
+// Installs a set of C conditioning variants whose S and Phi the caller has made with SKAT's functions on the set as one
+// unit: from their dense sums [c][2K+1] the c' and e sums (cond_ce), then B = (F[:, 0:2K+1] | mu2 o G_c | zeros) by
+// build(PB, grid), which queues the entry's build kernel (and the tables it reads) into h->cond_B on the handle's stream.
+template <class Build>
+static int cond_install(sgx_handle *h, int C, const std::vector<double> &dense, Build build)
+{
+	const int N = h->md.N, K = h->md.K, PB = 16 * ((2 * K + 1 + C + 15) / 16);
+	std::vector<double> ce((size_t)C * 2 * K);
+	for (int c = 0; c < C; c++)
+		for (int a = 0; a < 2 * K; a++) ce[(size_t)c * 2 * K + a] = dense[(size_t)c * (2 * K + 1) + a];
+	int rc = grow(h->cond_ce, (size_t)SGX_COND_MAX * 2 * KMAX);
+	if (!rc) rc = grow(h->cond_B, (size_t)N * PB);
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(h->cond_ce, ce.data(), ce.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+	const size_t nel = (size_t)N * PB;
+	rc = build(PB, dim3((unsigned)((nel + 255) / 256)));
+	if (rc) return rc;
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(h->stream));
+	h->n_cond = C;
+	return SGX_OK;
+}
+
 extern "C" int sgx_cond_set(sgx_handle *h, const uint8_t *packed_c, size_t bpv, size_t n_cond,
 	const double *lut_c, double *score_c, double *cov_cc)
 {
@@ -16,10 +39,9 @@ extern "C" int sgx_cond_set(sgx_handle *h, const uint8_t *packed_c, size_t bpv, 
 	if (n_cond > SGX_COND_MAX)
 		return fail(SGX_EINVAL, "sgx_cond_set: %zu conditioning variants, at most %d are supported", n_cond, SGX_COND_MAX);
 	if (n_cond && (!packed_c || !lut_c || !score_c || !cov_cc)) return fail(SGX_EINVAL, "sgx_cond_set: NULL buffer");
-	const int N = h->md.N, K = h->md.K, P = h->md.P;
-	if (n_cond && bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	int rc = sgx_sync(h);                       // nothing queued reads the set that is replaced
+	const int N = h->md.N;
+	int rc = n_cond ? bpv_check(bpv, N) : SGX_OK;
+	if (!rc) rc = sgx_sync(h);                  // nothing queued reads the set that is replaced
 	if (rc) return rc;
 	h->n_cond = 0;
 	if (n_cond == 0) return SGX_OK;
@@ -32,29 +54,20 @@ extern "C" int sgx_cond_set(sgx_handle *h, const uint8_t *packed_c, size_t bpv, 
 	rc = skat_2bit_host(h, packed_c, bpv, n_cond, 1, unit_ptr, var_idx, lut_c, score_c, cov_cc, dense);
 	if (rc) return rc;
 
-	// their c' and e sums, then B = (F[:, 0:2K+1] | mu2 o G_c | zeros)
-	const int C = (int)n_cond, PB = 16 * ((2 * K + 1 + C + 15) / 16);
-	std::vector<double> ce((size_t)C * 2 * K);
-	for (int c = 0; c < C; c++)
-		for (int a = 0; a < 2 * K; a++) ce[(size_t)c * 2 * K + a] = dense[(size_t)c * (2 * K + 1) + a];
-	rc = grow(h->cond_ce, (size_t)SGX_COND_MAX * 2 * KMAX);
-	if (rc) return rc;
-	rc = grow(h->cond_B, (size_t)N * PB);
-	if (rc) return rc;
-	const size_t dbpv = (size_t)((N + 15) >> 4) * 4, o_lut = ((size_t)C * dbpv + 15) & ~(size_t)15;
-	rc = grow(h->stage_pk, o_lut + (size_t)C * 4 * sizeof(double));
-	if (rc) return rc;
-	rc = copy_rows_h2d(h->stage_pk, dbpv, packed_c, bpv, (size_t)C, h->stream);
-	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut_c, (size_t)C * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->cond_ce, ce.data(), ce.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	const size_t nel = (size_t)N * PB;
-	hipLaunchKernelGGL(cond_build_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, h->stream,
-		h->stage_pk, dbpv, reinterpret_cast<const double *>(h->stage_pk + o_lut), C, h->md.F, P, N, PB, h->cond_B);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipStreamSynchronize(h->stream));
-	h->n_cond = C;
-	return SGX_OK;
+	const int C = (int)n_cond;
+	return cond_install(h, C, dense, [&](int PB, dim3 grid) -> int {
+		const size_t dbpv = (size_t)((N + 15) >> 4) * 4;
+		TabLayout tl;
+		tl.add<uint8_t>((size_t)C * dbpv);
+		const auto s_lut = tl.add((size_t)C * 4, lut_c);
+		int rc = grow(h->stage_pk, tl.bytes());
+		if (!rc) rc = copy_rows_h2d(h->stage_pk, dbpv, packed_c, bpv, (size_t)C, h->stream);
+		if (!rc) rc = tabs_upload(h->stage_pk, h->stream, s_lut);
+		if (rc) return rc;
+		hipLaunchKernelGGL(cond_build_kernel, grid, dim3(256), 0, h->stream,
+			h->stage_pk, dbpv, tl.at(h->stage_pk, s_lut), C, h->md.F, h->md.P, N, PB, h->cond_B);
+		return SGX_OK;
+	});
 }
 
 // M rows -> score / var / cov in device memory, queued on lane->stream: the rows in launches whose per-slab sums fit
@@ -115,12 +128,8 @@ extern "C" int sgx_cond_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_
 	if (!packed_dev || !lut_dev || !score_dev || !var_dev || !cov_dev)
 		return fail(SGX_EINVAL, "sgx_cond_2bit_dev: NULL buffer");
 	if (h->n_cond == 0) return fail(SGX_EINVAL, "sgx_cond_2bit_dev: no conditioning set (sgx_cond_set)");
-	if (bpv % 64 != 0 || bpv < sgx_row_stride(h->md.N))
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu, need a multiple of 64 >= %zu",
-			bpv, sgx_row_stride(h->md.N));
-	if (((uintptr_t)packed_dev & 15u) != 0)
-		return fail(SGX_EINVAL, "sgx_cond_2bit_dev: packed_dev must be 16-byte aligned");
-	int rc = set_dev(h);
+	int rc = dev_rows_check("sgx_cond_2bit_dev", packed_dev, bpv, h->md.N);
+	if (!rc) rc = set_dev(h);
 	if (rc) return rc;
 	sgx_handle *lane = h->last_issued ? h->last_issued : h;      // behind the most recent call: a scan of the same rows
 	return cond_rows_dev(h, lane, packed_dev, bpv, M, lut_dev, score_dev, var_dev, cov_dev);
@@ -135,29 +144,26 @@ extern "C" int sgx_cond_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 	if (!packed || !lut || !score || !var || !cov) return fail(SGX_EINVAL, "sgx_cond_2bit: NULL buffer");
 	if (h->n_cond == 0) return fail(SGX_EINVAL, "sgx_cond_2bit: no conditioning set (sgx_cond_set)");
 	const int N = h->md.N, C = h->n_cond;
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	int rc = set_dev(h);
+	int rc = bpv_check(bpv, N);
+	if (!rc) rc = begin_call(h);
 	if (rc) return rc;
-	rc = sync_lane(h);
-	if (rc) return rc;
-	h->last_issued = h;
 
 	// chunks of sgx_skat_2bit's uploads: rows at the device stride, then tables and results
 	const size_t dbpv = sgx_row_stride(N);
 	const size_t rchunk = scan_chunk(h, dbpv, M);
-	const size_t o_lut = rchunk * dbpv, o_s = o_lut + rchunk * 4 * sizeof(double), o_v = o_s + rchunk * sizeof(double),
-		o_c = o_v + rchunk * sizeof(double);
-	rc = grow(h->stage_pk, o_c + rchunk * (size_t)C * sizeof(double));
+	TabLayout tl;
+	tl.add<uint8_t>(rchunk * dbpv);
+	const auto s_lut = tl.add<double>(rchunk * 4);
+	const auto s_s = tl.add<double>(rchunk), s_v = tl.add<double>(rchunk), s_c = tl.add<double>(rchunk * (size_t)C);
+	rc = grow(h->stage_pk, tl.bytes());
 	if (rc) return rc;
-	double *d_lut = reinterpret_cast<double *>(h->stage_pk + o_lut), *d_s = reinterpret_cast<double *>(h->stage_pk + o_s),
-		*d_v = reinterpret_cast<double *>(h->stage_pk + o_v), *d_c = reinterpret_cast<double *>(h->stage_pk + o_c);
+	double *d_lut = tl.at(h->stage_pk, s_lut), *d_s = tl.at(h->stage_pk, s_s), *d_v = tl.at(h->stage_pk, s_v),
+		*d_c = tl.at(h->stage_pk, s_c);
 	for (size_t off = 0; off < M; off += rchunk) {
 		const size_t m = std::min(rchunk, M - off);
 		rc = copy_rows_h2d(h->stage_pk, dbpv, packed + off * bpv, bpv, m, h->stream);
-		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(d_lut, lut + 4 * off, m * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-		rc = cond_rows_dev(h, h, h->stage_pk, dbpv, m, d_lut, d_s, d_v, d_c);
+		if (!rc) rc = tab_copy(h->stage_pk, s_lut, lut + 4 * off, 4 * m, h->stream);
+		if (!rc) rc = cond_rows_dev(h, h, h->stage_pk, dbpv, m, d_lut, d_s, d_v, d_c);
 		if (rc) return rc;
 		HIPCHK(hipMemcpyAsync(score + off, d_s, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipMemcpyAsync(var + off, d_v, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -16,11 +16,9 @@ extern "C" int sgx_ds_block_cond_set(sgx_handle *h, const sgx_dsblock *b, size_t
 	if (n_cond) {
 		if (!var_idx || !flip || !mean || !score_c || !cov_cc) return fail(SGX_EINVAL, "sgx_ds_block_cond_set: NULL buffer");
 		if (b->M == 0) return fail(SGX_EINVAL, "sgx_ds_block_cond_set: nothing loaded");
-		for (size_t c = 0; c < n_cond; c++)
-			if (var_idx[c] < 0 || (size_t)var_idx[c] >= b->M)
-				return fail(SGX_EINVAL, "sgx_ds_block_cond_set: variant index %d outside the block's %zu rows", var_idx[c], b->M);
+		rc = block_idx_check("sgx_ds_block_cond_set", var_idx, n_cond, b->M);
 	}
-	rc = sgx_sync(h);                           // nothing queued reads the set that is replaced
+	if (!rc) rc = sgx_sync(h);                  // nothing queued reads the set that is replaced
 	if (rc) return rc;
 	h->n_cond = 0;
 	if (n_cond == 0) return SGX_OK;
@@ -31,37 +29,21 @@ extern "C" int sgx_ds_block_cond_set(sgx_handle *h, const sgx_dsblock *b, size_t
 	rc = skat_ds_block_host(h, b, 1, unit_ptr, var_idx, flip, mean, score_c, cov_cc, dense);
 	if (rc) return rc;
 
-	// their c' and e sums, then B = (F[:, 0:2K+1] | mu2 o G_c | zeros)
-	const int N = b->N, K = h->md.K, P = h->md.P, C = (int)n_cond, PB = 16 * ((2 * K + 1 + C + 15) / 16);
-	std::vector<double> ce((size_t)C * 2 * K);
-	for (int c = 0; c < C; c++)
-		for (int a = 0; a < 2 * K; a++) ce[(size_t)c * 2 * K + a] = dense[(size_t)c * (2 * K + 1) + a];
-	rc = grow(h->cond_ce, (size_t)SGX_COND_MAX * 2 * KMAX);
-	if (rc) return rc;
-	rc = grow(h->cond_B, (size_t)N * PB);
-	if (rc) return rc;
-	const size_t o_idx = (size_t)C * sizeof(double), o_flip = o_idx + (size_t)C * sizeof(int);      // means first
-	rc = grow(h->stage_pk, o_flip + (size_t)C);
-	if (rc) return rc;
-	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
-	HIPCHK(hipMemcpyAsync(h->stage_pk, mean, (size_t)C * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)C * sizeof(int), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_flip, flip, (size_t)C, hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->cond_ce, ce.data(), ce.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	const double *d_mean = reinterpret_cast<const double *>(h->stage_pk.p);
-	const int *d_idx = reinterpret_cast<const int *>(h->stage_pk + o_idx);
-	const size_t nel = (size_t)N * PB;
-	const dim3 grid((unsigned)((nel + 255) / 256));
-	if (b->dtype == SGX_DS_U8)
-		hipLaunchKernelGGL((cond_build_ds_kernel<uint8_t>), grid, dim3(256), 0, h->stream,
-			(const uint8_t *)b->rows, d_idx, h->stage_pk + o_flip, d_mean, C, h->md.F, P, N, PB, h->cond_B);
-	else
-		hipLaunchKernelGGL((cond_build_ds_kernel<double>), grid, dim3(256), 0, h->stream,
-			(const double *)b->rows.p, d_idx, h->stage_pk + o_flip, d_mean, C, h->md.F, P, N, PB, h->cond_B);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipStreamSynchronize(h->stream));
-	h->n_cond = C;
-	return SGX_OK;
+	const int C = (int)n_cond;
+	return cond_install(h, C, dense, [&](int PB, dim3 grid) -> int {
+		TabLayout tl;
+		const auto s_mean = tl.add(n_cond, mean);
+		const auto s_idx = tl.add(n_cond, var_idx);
+		const auto s_flip = tl.add(n_cond, flip);
+		int rc = grow(h->stage_pk, tl.bytes());
+		if (!rc) rc = tabs_upload(h->stage_pk, h->stream, s_mean, s_idx, s_flip);
+		if (rc) return rc;
+		with_ds_rows(b->dtype, b->rows.p, [&](auto *rows, auto t) {
+			hipLaunchKernelGGL((cond_build_ds_kernel<decltype(t)>), grid, dim3(256), 0, h->stream, rows, tl.at(h->stage_pk, s_idx),
+				tl.at(h->stage_pk, s_flip), tl.at(h->stage_pk, s_mean), C, h->md.F, h->md.P, b->N, PB, h->cond_B);
+		});
+		return SGX_OK;
+	});
 }
 
 extern "C" int sgx_ds_block_cond(sgx_handle *h, const sgx_dsblock *b, const uint8_t *flip, const double *mean,
@@ -73,30 +55,26 @@ extern "C" int sgx_ds_block_cond(sgx_handle *h, const sgx_dsblock *b, const uint
 	if (!flip || !mean || !score || !var || !cov) return fail(SGX_EINVAL, "sgx_ds_block_cond: NULL buffer");
 	if (b->M == 0) return fail(SGX_EINVAL, "sgx_ds_block_cond: nothing loaded");
 	if (h->n_cond == 0) return fail(SGX_EINVAL, "sgx_ds_block_cond: no conditioning set (sgx_ds_block_cond_set)");
-	rc = sync_lane(h);
+	rc = begin_call(h);
 	if (rc) return rc;
-	h->last_issued = h;
 
 	// tables and results on the device: means, score, var, cov, then the flips
 	const size_t M = b->M, C = (size_t)h->n_cond;
 	const int N = b->N, P = h->md.P;
-	const size_t o_flip = M * (3 + C) * sizeof(double);
-	rc = grow(h->stage_pk, o_flip + M);
+	TabLayout tl;
+	const auto s_mean = tl.add(M, mean);
+	const auto s_s = tl.add<double>(M), s_v = tl.add<double>(M), s_c = tl.add<double>(M * C);
+	const auto s_flip = tl.add(M, flip);
+	rc = grow(h->stage_pk, tl.bytes());
+	if (!rc) rc = tabs_upload(h->stage_pk, h->stream, s_mean, s_flip);
 	if (rc) return rc;
-	double *d_mean = reinterpret_cast<double *>(h->stage_pk.p), *d_s = d_mean + M, *d_v = d_s + M, *d_c = d_v + M;
-	const uint8_t *d_flip = h->stage_pk + o_flip;
-	HIPCHK(hipMemcpyAsync(d_mean, mean, M * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_flip, flip, M, hipMemcpyHostToDevice, h->stream));
+	double *d_s = tl.at(h->stage_pk, s_s), *d_v = tl.at(h->stage_pk, s_v), *d_c = tl.at(h->stage_pk, s_c);
 	rc = cond_run(h, h, M, COND_DS_SLAB_CH, [&](auto nct, dim3 grid, size_t off, size_t m) {
-		constexpr int NCT = decltype(nct)::value;
-		if (b->dtype == SGX_DS_U8)
-			hipLaunchKernelGGL((cond_rect_ds_kernel<uint8_t, NCT>), grid, dim3(256), 0, h->stream,
-				(const uint8_t *)b->rows + off * (size_t)N, N, m, d_flip + off, d_mean + off, h->md.F, P, h->cond_B, COND_DS_SLAB_CH,
-				h->cond_part);
-		else
-			hipLaunchKernelGGL((cond_rect_ds_kernel<double, NCT>), grid, dim3(256), 0, h->stream,
-				(const double *)b->rows.p + off * (size_t)N, N, m, d_flip + off, d_mean + off, h->md.F, P, h->cond_B, COND_DS_SLAB_CH,
-				h->cond_part);
+		with_ds_rows(b->dtype, b->rows.p, [&](auto *rows, auto t) {
+			hipLaunchKernelGGL((cond_rect_ds_kernel<decltype(t), decltype(nct)::value>), grid, dim3(256), 0, h->stream,
+				rows + off * (size_t)N, N, m, tl.at(h->stage_pk, s_flip) + off, tl.at(h->stage_pk, s_mean) + off, h->md.F, P, h->cond_B,
+				COND_DS_SLAB_CH, h->cond_part);
+		});
 	}, d_s, d_v, d_c);
 	if (rc) return rc;
 	HIPCHK(hipMemcpyAsync(score, d_s, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -13,18 +13,19 @@ static int ckm_sum_room(const char *who, sgx_handle *h, size_t m)
 	const int N = h->md.N, C1 = h->md.K + 1;
 	const int ndw = (N + 15) >> 4, ncslab = (ndw + SKK_CSLAB_DW - 1) / SKK_CSLAB_DW;
 	const size_t mc = std::min<size_t>(m, SGX_GRM_MAX_RHS);
-	int rc = skk_room(h->skk_cpart, mc * ncslab * C1, "the column sums", who);
-	if (!rc) rc = skk_room(h->skk_cs, mc * C1, "the column sums", who);
+	int rc = dev_room(h->skk_cpart, mc * ncslab * C1, "the column sums", who);
+	if (!rc) rc = dev_room(h->skk_cs, mc * C1, "the column sums", who);
 	return rc;
 }
 
-// ... and for m 2-bit rows themselves with index list and tables behind them
-static int ckm_room(const char *who, sgx_handle *h, size_t m, size_t dbpv, size_t *o_idx, size_t *o_lut)
+// ... and for m 2-bit rows themselves (the first slot of h->stage_pk) with a chunk's index list and the tables behind them
+static int ckm_room(const char *who, sgx_handle *h, size_t m, size_t dbpv, TabSlot<int> &s_idx, TabSlot<double> &s_lut)
 {
-	const size_t mc = std::min<size_t>(m, SGX_GRM_MAX_RHS);
-	*o_idx = (m * dbpv + 15) & ~(size_t)15;
-	*o_lut = (*o_idx + mc * sizeof(int) + 15) & ~(size_t)15;
-	int rc = skk_room(h->stage_pk, *o_lut + m * 4 * sizeof(double), "the rows", who);
+	TabLayout tl;
+	tl.add<uint8_t>(m * dbpv);
+	s_idx = tl.add<int>(std::min<size_t>(m, SGX_GRM_MAX_RHS));
+	s_lut = tl.add<double>(m * 4);
+	int rc = dev_room(h->stage_pk, tl.bytes(), "the rows", who);
 	if (!rc) rc = ckm_sum_room(who, h, m);
 	return rc;
 }
@@ -58,7 +59,7 @@ static int ckm_install(const char *who, sgx_handle *h, sgx_kmat *km, const SkkSr
 	const int N = h->md.N, K = h->md.K;
 	const size_t lda = (size_t)((N + 15) >> 4) * 16;
 	hipStream_t st = h->stream;
-	int rc = skk_room(h->ckm_set, (size_t)(2 * C + 2 * K) * lda, "the set's vectors", who);
+	int rc = dev_room(h->ckm_set, (size_t)(2 * C + 2 * K) * lda, "the set's vectors", who);
 	if (rc) return rc;
 	double *A_C = h->ckm_set, *Y_C = A_C + (size_t)C * lda, *Z = Y_C + (size_t)C * lda, *Xc = Z + (size_t)K * lda;
 	hipLaunchKernelGGL(skk_xcols_kernel, dim3((unsigned)((lda + 255) / 256), (unsigned)K), dim3(256), 0, st, h->md.X, N, K, Xc, lda);
@@ -121,13 +122,10 @@ extern "C" int sgx_cond_kmat_set(sgx_handle *h, sgx_kmat *km, const uint8_t *pac
 	const int N = h->md.N, C = (int)n_cond;
 	rc = skk_km_check(who, h, km);
 	if (rc) return rc;
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	rc = skk_sigma_args(who, N, w, tau, maxiter);
-	if (rc) return rc;
-	rc = sgx_sync(h);                            // nothing queued reads the set that is replaced
-	if (rc) return rc;
-	rc = set_dev(h);
+	rc = bpv_check(bpv, N);
+	if (!rc) rc = skk_sigma_args(who, N, w, tau, maxiter);
+	if (!rc) rc = sgx_sync(h);                   // nothing queued reads the set that is replaced
+	if (!rc) rc = set_dev(h);
 	if (rc) return rc;
 	h->last_issued = h;
 	hipStream_t st = h->stream;
@@ -135,23 +133,23 @@ extern "C" int sgx_cond_kmat_set(sgx_handle *h, sgx_kmat *km, const uint8_t *pac
 	h->skk_ms[0] = h->skk_ms[1] = h->skk_ms[2] = 0;
 
 	const size_t dbpv = (size_t)((N + 15) >> 4) * 4;
-	size_t o_idx, o_lut;
-	rc = ckm_room(who, h, (size_t)C, dbpv, &o_idx, &o_lut);
+	TabSlot<int> s_idx; TabSlot<double> s_lut;
+	rc = ckm_room(who, h, (size_t)C, dbpv, s_idx, s_lut);
 	if (rc) return rc;
-	h->ckm_n = 0;                                // from here on the old set is gone
+	h->ckm_n = 0;                               // from here on the old set is gone
 	h->ckm_km = nullptr;
 	std::vector<double> lut_ok;
 	skk_tables(lut_c, (size_t)C, lut_ok, h->ckm_bad);
 	int32_t iota[SGX_COND_MAX];
 	for (int c = 0; c < C; c++) iota[c] = c;
 	rc = copy_rows_h2d(h->stage_pk, dbpv, packed_c, bpv, (size_t)C, st);
+	if (!rc) rc = tab_copy(h->stage_pk, s_idx, iota, (size_t)C, st);
+	if (!rc) rc = tab_copy(h->stage_pk, s_lut, lut_ok.data(), (size_t)C * 4, st);
 	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, iota, (size_t)C * sizeof(int), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut_ok.data(), (size_t)C * 4 * sizeof(double), hipMemcpyHostToDevice, st));
 	SkkSrc src;
-	src.idx = reinterpret_cast<const int *>(h->stage_pk + o_idx);
+	src.idx = TabLayout::at(h->stage_pk, s_idx);
 	src.rows = h->stage_pk; src.dbpv = dbpv;
-	src.lut = reinterpret_cast<const double *>(h->stage_pk + o_lut);
+	src.lut = TabLayout::at(h->stage_pk, s_lut);
 	return ckm_install(who, h, km, src, C, w, tau, maxiter, tol, t_col, score_c, cov_cc, iters_c);
 }
 
@@ -182,10 +180,10 @@ static int ckm_scan_begin(const char *who, sgx_handle *h, sgx_kmat *km, size_t m
 	cs.nslab = ((int)cs.lda + SKK_SLAB - 1) / SKK_SLAB;
 	cs.NPT = (cs.C + cs.K + 15) / 16; cs.NT = cs.NPT + 2;
 	const size_t nrt_max = (mc_max + 15) / 16;
-	int rc = skk_room(h->skk_A, mc_max * cs.lda, "a chunk's columns", who);
-	if (!rc) rc = skk_room(h->skk_Y, mc_max * cs.lda, "a chunk's solves", who);
-	if (!rc) rc = skk_room(h->skat_part, (size_t)cs.nslab * nrt_max * cs.NT * 256, "the slab partials", who);
-	if (!rc) rc = skk_room(h->skat_fin, nrt_max * cs.NT * 256, "the tiles", who);
+	int rc = dev_room(h->skk_A, mc_max * cs.lda, "a chunk's columns", who);
+	if (!rc) rc = dev_room(h->skk_Y, mc_max * cs.lda, "a chunk's solves", who);
+	if (!rc) rc = dev_room(h->skat_part, (size_t)cs.nslab * nrt_max * cs.NT * 256, "the slab partials", who);
+	if (!rc) rc = dev_room(h->skat_fin, nrt_max * cs.NT * 256, "the tiles", who);
 	if (rc) return rc;
 	cs.fin.resize(nrt_max * cs.NT * 256);
 	cs.dj.resize((size_t)cs.K); cs.qj.resize((size_t)cs.K);
@@ -259,13 +257,9 @@ extern "C" int sgx_cond_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	const int N = h->md.N, C = h->ckm_n;
 	rc = skk_km_check(who, h, km);
 	if (rc) return rc;
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	rc = set_dev(h);
+	rc = bpv_check(bpv, N);
+	if (!rc) rc = begin_call(h);
 	if (rc) return rc;
-	rc = sync_lane(h);
-	if (rc) return rc;
-	h->last_issued = h;
 	hipStream_t st = h->stream;
 	h->skk_ms[0] = h->skk_ms[1] = h->skk_ms[2] = 0;
 	auto t_col = std::chrono::steady_clock::now();
@@ -273,9 +267,9 @@ extern "C" int sgx_cond_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	const size_t dbpv = (size_t)((N + 15) >> 4) * 4;
 	const size_t rchunk = scan_chunk(h, dbpv, M);
 	const size_t mc_max = std::min<size_t>(rchunk, SGX_GRM_MAX_RHS);
-	size_t o_idx, o_lut;
+	TabSlot<int> s_idx; TabSlot<double> s_lut;
 	CkmScan cs;
-	rc = ckm_room(who, h, rchunk, dbpv, &o_idx, &o_lut);
+	rc = ckm_room(who, h, rchunk, dbpv, s_idx, s_lut);
 	if (rc) return rc;
 	std::vector<double> lut_ok;
 	std::vector<uint8_t> bad;
@@ -283,25 +277,25 @@ extern "C" int sgx_cond_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	int32_t iota[SGX_GRM_MAX_RHS];
 	for (int j = 0; j < SGX_GRM_MAX_RHS; j++) iota[j] = j;
 	rc = ckm_scan_begin(who, h, km, mc_max, cs);
+	if (!rc) rc = tab_copy(h->stage_pk, s_idx, iota, mc_max, st);
 	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, iota, mc_max * sizeof(int), hipMemcpyHostToDevice, st));
 	h->skk_ms[0] += skk_ms_since(t_col);
 
 	SkkSrc src;
-	src.idx = reinterpret_cast<const int *>(h->stage_pk + o_idx);
+	src.idx = TabLayout::at(h->stage_pk, s_idx);
 	src.dbpv = dbpv;
 	for (size_t off = 0; off < M; off += rchunk) {
 		t_col = std::chrono::steady_clock::now();
 		const size_t mr = std::min(rchunk, M - off);
 		rc = copy_rows_h2d(h->stage_pk, dbpv, packed + off * bpv, bpv, mr, st);
+		if (!rc) rc = tab_copy(h->stage_pk, s_lut, lut_ok.data() + 4 * off, 4 * mr, st);
 		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut_ok.data() + 4 * off, mr * 4 * sizeof(double), hipMemcpyHostToDevice, st));
 		h->skk_ms[0] += skk_ms_since(t_col);
 		for (size_t j0 = 0; j0 < mr; j0 += SGX_GRM_MAX_RHS) {
 			const int m = (int)std::min<size_t>(SGX_GRM_MAX_RHS, mr - j0);
 			const size_t g0 = off + j0;
 			src.rows = h->stage_pk + j0 * dbpv;
-			src.lut = reinterpret_cast<const double *>(h->stage_pk + o_lut) + 4 * j0;
+			src.lut = TabLayout::at(h->stage_pk, s_lut) + 4 * j0;
 			rc = ckm_chunk(who, h, km, src, m, &bad[g0], cs, score + g0, var + g0, cov + g0 * (size_t)C, iters ? iters + g0 : nullptr);
 			if (rc) return rc;
 		}

@@ -32,11 +32,8 @@ extern "C" int sgx_firth_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size
 	if (rc) return rc;
 	if (M == 0) return SGX_OK;
 	if (!packed_dev || !lut_dev || !out4_dev) return fail(SGX_EINVAL, "sgx_firth_2bit_dev: NULL buffer");
-	if (bpv % 64 != 0 || bpv < sgx_row_stride(h->md.N))
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu, need a multiple of 64 >= %zu",
-			bpv, sgx_row_stride(h->md.N));
-	if (((uintptr_t)packed_dev & 15u) != 0)
-		return fail(SGX_EINVAL, "sgx_firth_2bit_dev: packed_dev must be 16-byte aligned");
+	rc = dev_rows_check("sgx_firth_2bit_dev", packed_dev, bpv, h->md.N);
+	if (rc) return rc;
 	if (((uintptr_t)lut_dev & 7u) != 0 || ((uintptr_t)out4_dev & 7u) != 0)
 		return fail(SGX_EINVAL, "sgx_firth_2bit_dev: lut_dev and out4_dev must be 8-byte aligned");
 	rc = set_dev(h);
@@ -52,26 +49,24 @@ extern "C" int sgx_firth_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, 
 	if (M == 0) return SGX_OK;
 	if (!packed || !lut || !out4) return fail(SGX_EINVAL, "sgx_firth_2bit: NULL buffer");
 	const int N = h->md.N;
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	rc = set_dev(h);
-	if (rc) return rc;
-	rc = sync_lane(h);
+	rc = bpv_check(bpv, N);
+	if (!rc) rc = sync_lane(h);             // (not begin_call: this entry leaves last_issued as it is)
 	if (rc) return rc;
 
 	// chunks of the host-buffer scans: rows at the device stride, then tables and results
 	const size_t dbpv = sgx_row_stride(N);
 	const size_t rchunk = scan_chunk(h, dbpv, M);
-	const size_t o_lut = rchunk * dbpv, o_out = o_lut + rchunk * 4 * sizeof(double);
-	rc = grow(h->stage_pk, o_out + rchunk * 4 * sizeof(double));
+	TabLayout tl;
+	tl.add<uint8_t>(rchunk * dbpv);
+	const auto s_lut = tl.add<double>(rchunk * 4), s_out = tl.add<double>(rchunk * 4);
+	rc = grow(h->stage_pk, tl.bytes());
 	if (rc) return rc;
-	double *d_lut = reinterpret_cast<double *>(h->stage_pk + o_lut), *d_out = reinterpret_cast<double *>(h->stage_pk + o_out);
+	double *d_lut = tl.at(h->stage_pk, s_lut), *d_out = tl.at(h->stage_pk, s_out);
 	for (size_t off = 0; off < M; off += rchunk) {
 		const size_t m = std::min(rchunk, M - off);
 		rc = copy_rows_h2d(h->stage_pk, dbpv, packed + off * bpv, bpv, m, h->stream);
-		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(d_lut, lut + 4 * off, m * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-		rc = firth_rows_dev(h, h->stage_pk, dbpv, m, d_lut, maxit, d_out);
+		if (!rc) rc = tab_copy(h->stage_pk, s_lut, lut + 4 * off, 4 * m, h->stream);
+		if (!rc) rc = firth_rows_dev(h, h->stage_pk, dbpv, m, d_lut, maxit, d_out);
 		if (rc) return rc;
 		HIPCHK(hipMemcpyAsync(out4 + 4 * off, d_out, m * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
@@ -95,40 +90,32 @@ extern "C" int sgx_ds_block_firth(sgx_handle *h, const sgx_dsblock *b, size_t n_
 	if (n_rows == 0) return SGX_OK;
 	if (!var_idx || !flip || !mean || !out4) return fail(SGX_EINVAL, "sgx_ds_block_firth: NULL buffer");
 	if (b->M == 0) return fail(SGX_EINVAL, "sgx_ds_block_firth: nothing loaded");
-	for (size_t r = 0; r < n_rows; r++)
-		if (var_idx[r] < 0 || (size_t)var_idx[r] >= b->M)
-			return fail(SGX_EINVAL, "sgx_ds_block_firth: variant index %d outside the block's %zu rows", var_idx[r], b->M);
-	rc = sync_lane(h);
+	rc = block_idx_check("sgx_ds_block_firth", var_idx, n_rows, b->M);
+	if (!rc) rc = begin_call(h);
 	if (rc) return rc;
-	h->last_issued = h;
 
 	const int N = b->N;
-	const bool u8 = b->dtype == SGX_DS_U8;
-	const size_t slice = u8 ? firth_ds_slice_bytes<uint8_t>(N) : firth_ds_slice_bytes<double>(N);
+	const size_t slice = b->dtype == SGX_DS_U8 ? firth_ds_slice_bytes<uint8_t>(N) : firth_ds_slice_bytes<double>(N);
 	size_t grid = (size_t)std::max(1, h->spa_grid);
 	if (slice) grid = std::max<size_t>(1, std::min(grid, FIRTH_DS_SCR_MAX / slice));
 	rc = ensure_buf(h, h->firth_scr, slice * grid);
 	if (rc) return rc;
 
 	// tables and results on the device: means, results, then the indices and the flips
-	const size_t o_out = n_rows * sizeof(double), o_idx = o_out + n_rows * 4 * sizeof(double);
-	const size_t o_flip = o_idx + n_rows * sizeof(int);
-	rc = grow(h->stage_pk, o_flip + n_rows);
+	TabLayout tl;
+	const auto s_mean = tl.add(n_rows, mean);
+	const auto s_out = tl.add<double>(n_rows * 4);
+	const auto s_idx = tl.add(n_rows, var_idx);
+	const auto s_flip = tl.add(n_rows, flip);
+	rc = grow(h->stage_pk, tl.bytes());
+	if (!rc) rc = tabs_upload(h->stage_pk, h->stream, s_mean, s_idx, s_flip);
 	if (rc) return rc;
-	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
-	double *d_mean = reinterpret_cast<double *>(h->stage_pk.p), *d_out = reinterpret_cast<double *>(h->stage_pk + o_out);
-	int *d_idx = reinterpret_cast<int *>(h->stage_pk + o_idx);
-	uint8_t *d_flip = h->stage_pk + o_flip;
-	HIPCHK(hipMemcpyAsync(d_mean, mean, n_rows * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(d_idx, var_idx, n_rows * sizeof(int), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(d_flip, flip, n_rows, hipMemcpyHostToDevice, h->stream));
-	const dim3 g((unsigned)std::min(n_rows, grid));
-	if (u8)
-		hipLaunchKernelGGL((firth_ds_kernel<uint8_t>), g, dim3(FIRTH_BLOCK), 0, h->stream,
-			(const uint8_t *)b->rows, N, n_rows, d_idx, d_flip, d_mean, h->md.mu, h->md.y, maxit, (uint8_t *)h->firth_scr, d_out);
-	else
-		hipLaunchKernelGGL((firth_ds_kernel<double>), g, dim3(FIRTH_BLOCK), 0, h->stream,
-			(const double *)b->rows.p, N, n_rows, d_idx, d_flip, d_mean, h->md.mu, h->md.y, maxit, (uint8_t *)h->firth_scr, d_out);
+	double *d_out = tl.at(h->stage_pk, s_out);
+	with_ds_rows(b->dtype, b->rows.p, [&](auto *rows, auto t) {
+		hipLaunchKernelGGL((firth_ds_kernel<decltype(t)>), dim3((unsigned)std::min(n_rows, grid)), dim3(FIRTH_BLOCK), 0, h->stream,
+			rows, N, n_rows, tl.at(h->stage_pk, s_idx), tl.at(h->stage_pk, s_flip), tl.at(h->stage_pk, s_mean), h->md.mu, h->md.y,
+			maxit, (uint8_t *)h->firth_scr, d_out);
+	});
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(out4, d_out, n_rows * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(hipStreamSynchronize(h->stream));

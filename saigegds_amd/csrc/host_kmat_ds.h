@@ -8,26 +8,16 @@
 // The tables of n dosage entries in h->stage_pk: means [n], row indices [n], flips [n].  An entry whose mean is not
 // finite is flagged in `bad` and gets a column of zeros (SKK_DS_ZERO), like a 2-bit entry with a non-finite table.
 // var_idx == nullptr: the rows 0 .. n_idx - 1 (a chunk's own numbering) instead of one index per entry.
-struct KdsTabs {
-	size_t o_idx = 0, o_flip = 0;
-	std::vector<double> mean;
-	std::vector<uint8_t> flip;
-};
-
 static int kds_tables(const char *who, sgx_handle *h, size_t n, const int32_t *var_idx, size_t n_idx, const uint8_t *flip,
-	const double *mean, KdsTabs &t, std::vector<uint8_t> &bad, const sgx_dsblock *b, SkkSrc &src)
+	const double *mean, std::vector<uint8_t> &bad, const sgx_dsblock *b, SkkSrc &src)
 {
-	t.o_idx = n * sizeof(double);
-	t.o_flip = t.o_idx + n_idx * sizeof(int);
-	int rc = skk_room(h->stage_pk, t.o_flip + n, "the entries' tables", who);
-	if (rc) return rc;
-	t.mean.assign(mean, mean + n);
-	t.flip.resize(n);
+	std::vector<double> mean_ok(mean, mean + n);
+	std::vector<uint8_t> flip_ok(n);
 	bad.assign(n, 0);
 	for (size_t e = 0; e < n; e++) {
 		bad[e] = !std::isfinite(mean[e]);
-		t.flip[e] = bad[e] ? SKK_DS_ZERO : (flip[e] != 0);
-		if (bad[e]) t.mean[e] = 0;
+		flip_ok[e] = bad[e] ? SKK_DS_ZERO : (flip[e] != 0);
+		if (bad[e]) mean_ok[e] = 0;
 	}
 	std::vector<int32_t> iota;
 	if (!var_idx) {
@@ -35,17 +25,19 @@ static int kds_tables(const char *who, sgx_handle *h, size_t n, const int32_t *v
 		for (size_t j = 0; j < n_idx; j++) iota[j] = (int32_t)j;
 		var_idx = iota.data();
 	}
-	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
-	hipStream_t st = h->stream;
-	HIPCHK(hipMemcpyAsync(h->stage_pk, t.mean.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + t.o_idx, var_idx, n_idx * sizeof(int), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + t.o_flip, t.flip.data(), n, hipMemcpyHostToDevice, st));
-	HIPCHK(hipStreamSynchronize(st));            // iota is a local
+	TabLayout tl;
+	const auto s_mean = tl.add(n, mean_ok.data());
+	const auto s_idx = tl.add(n_idx, var_idx);
+	const auto s_flip = tl.add(n, flip_ok.data());
+	int rc = dev_room(h->stage_pk, tl.bytes(), "the entries' tables", who);
+	if (!rc) rc = tabs_upload(h->stage_pk, h->stream, s_mean, s_idx, s_flip);
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(h->stream));     // mean_ok, flip_ok and iota are locals
 	src = SkkSrc();
-	src.idx = reinterpret_cast<const int *>(h->stage_pk + t.o_idx);
+	src.idx = tl.at(h->stage_pk, s_idx);
 	src.ds = b->rows.p; src.ds_dtype = b->dtype == SGX_DS_U8 ? SGX_DS_U8 : SGX_DS_F64;
-	src.flip = h->stage_pk + t.o_flip;
-	src.mean = reinterpret_cast<const double *>(h->stage_pk.p);
+	src.flip = tl.at(h->stage_pk, s_flip);
+	src.mean = tl.at(h->stage_pk, s_mean);
 	return SGX_OK;
 }
 
@@ -67,21 +59,16 @@ extern "C" int sgx_ds_block_skat_kmat(sgx_handle *h, sgx_kmat *km, const sgx_dsb
 	if (rc) return rc;
 	const int64_t nnz = unit_ptr[n_units];
 	if (nnz == 0) return SGX_OK;
-	rc = set_dev(h);
+	rc = begin_call(h);
 	if (rc) return rc;
-	rc = sync_lane(h);
-	if (rc) return rc;
-	h->last_issued = h;
 	auto t_col = std::chrono::steady_clock::now();
 	h->skk_ms[0] = h->skk_ms[1] = h->skk_ms[2] = 0;
 	int64_t m_max = 0;
 	for (size_t u = 0; u < n_units; u++) m_max = std::max(m_max, unit_ptr[u + 1] - unit_ptr[u]);
-	rc = skk_unit_room(who, h, (size_t)m_max);
-	if (rc) return rc;
-	KdsTabs t;
 	std::vector<uint8_t> bad;
 	SkkSrc src;
-	rc = kds_tables(who, h, (size_t)nnz, var_idx, (size_t)nnz, flip, mean, t, bad, b, src);
+	rc = skk_unit_room(who, h, (size_t)m_max);
+	if (!rc) rc = kds_tables(who, h, (size_t)nnz, var_idx, (size_t)nnz, flip, mean, bad, b, src);
 	if (rc) return rc;
 	return skk_units(who, h, km, src, n_units, unit_ptr, bad, (size_t)m_max, w, tau, maxiter, tol, t_col, score, cov, iters);
 }
@@ -101,12 +88,9 @@ extern "C" int sgx_ds_block_cond_kmat_set(sgx_handle *h, sgx_kmat *km, const sgx
 	if (!rc) rc = skk_sigma_args(who, h->md.N, w, tau, maxiter);
 	if (rc) return rc;
 	if (b->M == 0) return fail(SGX_EINVAL, "%s: nothing loaded", who);
-	for (size_t c = 0; c < n_cond; c++)
-		if (var_idx[c] < 0 || (size_t)var_idx[c] >= b->M)
-			return fail(SGX_EINVAL, "%s: variant index %d outside the block's %zu rows", who, var_idx[c], b->M);
-	rc = sgx_sync(h);                            // nothing queued reads the set that is replaced
-	if (rc) return rc;
-	rc = set_dev(h);
+	rc = block_idx_check(who, var_idx, n_cond, b->M);
+	if (!rc) rc = sgx_sync(h);                   // nothing queued reads the set that is replaced
+	if (!rc) rc = set_dev(h);
 	if (rc) return rc;
 	h->last_issued = h;
 	auto t_col = std::chrono::steady_clock::now();
@@ -115,9 +99,8 @@ extern "C" int sgx_ds_block_cond_kmat_set(sgx_handle *h, sgx_kmat *km, const sgx
 	if (rc) return rc;
 	h->ckm_n = 0;                                // from here on the old set is gone
 	h->ckm_km = nullptr;
-	KdsTabs t;
 	SkkSrc src;
-	rc = kds_tables(who, h, n_cond, var_idx, n_cond, flip, mean, t, h->ckm_bad, b, src);
+	rc = kds_tables(who, h, n_cond, var_idx, n_cond, flip, mean, h->ckm_bad, b, src);
 	if (rc) return rc;
 	return ckm_install(who, h, km, src, (int)n_cond, w, tau, maxiter, tol, t_col, score_c, cov_cc, iters_c);
 }
@@ -134,11 +117,8 @@ extern "C" int sgx_ds_block_cond_kmat(sgx_handle *h, sgx_kmat *km, const sgx_dsb
 	if (!rc) rc = skk_km_check(who, h, km);
 	if (rc) return rc;
 	if (b->M == 0) return fail(SGX_EINVAL, "%s: nothing loaded", who);
-	rc = set_dev(h);
+	rc = begin_call(h);
 	if (rc) return rc;
-	rc = sync_lane(h);
-	if (rc) return rc;
-	h->last_issued = h;
 	h->skk_ms[0] = h->skk_ms[1] = h->skk_ms[2] = 0;
 	auto t_col = std::chrono::steady_clock::now();
 
@@ -147,10 +127,9 @@ extern "C" int sgx_ds_block_cond_kmat(sgx_handle *h, sgx_kmat *km, const sgx_dsb
 	CkmScan cs;
 	rc = ckm_sum_room(who, h, M);
 	if (rc) return rc;
-	KdsTabs t;
 	std::vector<uint8_t> bad;
 	SkkSrc all;
-	rc = kds_tables(who, h, M, nullptr, mc_max, flip, mean, t, bad, b, all);      // a chunk's rows are 0 .. m - 1 of its own
+	rc = kds_tables(who, h, M, nullptr, mc_max, flip, mean, bad, b, all);         // a chunk's rows are 0 .. m - 1 of its own
 	if (!rc) rc = ckm_scan_begin(who, h, km, mc_max, cs);
 	if (rc) return rc;
 	h->skk_ms[0] += skk_ms_since(t_col);

@@ -107,6 +107,16 @@ static int sync_lane(sgx_handle *h)
 	return SGX_OK;
 }
 
+// how a synchronous entry begins once its arguments are checked: on the handle's device (sync_lane sets it), its lane
+// idle, and the handle the one that issued last
+static int begin_call(sgx_handle *h)
+{
+	const int rc = sync_lane(h);
+	if (rc) return rc;
+	h->last_issued = h;
+	return SGX_OK;
+}
+
 extern "C" int sgx_sync(sgx_handle *h)
 {
 	if (!h) return fail(SGX_EINVAL, "sgx_sync: NULL handle");

@@ -13,8 +13,8 @@
 //    so a struct declares its streams first, then its events, then its buffers.
 //
 // Error codes.  reserve / alloc / create report the hipError_t.  grow() and HIPCHK turn it into SGX_EHIP, as for every
-// other HIP call.  Where the CALLER sizes what is kept (sgx_block_create, sgx_dsblock_create, the buffers of
-// sgx_skat_kmat_2bit) running out of memory is SGX_ENOMEM: those collect the hipError_t (HIPPASS), give mem_code() of it
+// other HIP call.  Where the CALLER sizes what is kept (sgx_block_create, sgx_dsblock_create; dev_room for the entries
+// on an explicit GRM) running out of memory is SGX_ENOMEM: those collect the hipError_t (HIPPASS), give mem_code() of it
 // and keep their own messages.
 
 static std::atomic<size_t> g_live_bytes{0};
@@ -65,12 +65,24 @@ struct MemBuf {
 template <class T> using DevBuf = MemBuf<T, false>;
 template <class T> using PinBuf = MemBuf<T, true>;
 
-// reserve() as the library's return code
+// Room for n elements, three ways: a new entry takes dev_room for what its caller sizes (rows, units, sets: SGX_ENOMEM
+// with a text that says what for), grow for the rest (reserve() as the library's return code), and ensure_buf
+// (host_scan.h) instead of either for a lane's buffer that a call still in flight may read.
 template <class B>
 static int grow(B &b, size_t n)
 {
 	HIPCHK(b.reserve(n));
 	return SGX_OK;
+}
+
+// reserve() with out of memory as SGX_ENOMEM: `what` the room is for, `who` asks
+template <class T>
+static int dev_room(DevBuf<T> &b, size_t n, const char *what, const char *who)
+{
+	const hipError_t e = b.reserve(n);
+	if (e == hipSuccess) return SGX_OK;
+	(void)hipGetLastError();
+	return fail(mem_code(e), "%s: %zu bytes for %s: %s", who, n * sizeof(T), what, hipGetErrorString(e));
 }
 
 struct DevEvent {

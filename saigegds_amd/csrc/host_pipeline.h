@@ -472,8 +472,8 @@ extern "C" int sgx_block_load(sgx_handle *h, sgx_block *b, const uint8_t *packed
 	if (b->lists_only) return fail(SGX_EINVAL, "sgx_block_load: not a resident block");
 	if (b->device != h->device) return fail(SGX_EINVAL, "sgx_block_load: block and handle are on different devices");
 	if (M == 0 || M > b->cap) return fail(SGX_EINVAL, "sgx_block_load: %zu variants, the block holds up to %zu", M, b->cap);
-	if (bpv < (size_t)(b->N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(b->N + 3) / 4);
+	const int rc = bpv_check(bpv, b->N);
+	if (rc) return rc;
 	RowSrc src = plain_rows(packed, bpv);
 	return block_load_host(h, b, src, M);
 }
@@ -496,9 +496,8 @@ extern "C" int sgx_block_load_dbit2(sgx_handle *h, sgx_block *b, const uint8_t *
 extern "C" int sgx_scan_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, size_t M,
 	double *out8, uint8_t *valid)
 {
-	if (h && bpv < (size_t)(h->md.N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu",
-			bpv, (size_t)(h->md.N + 3) / 4);
+	const int rc = h ? bpv_check(bpv, h->md.N) : SGX_OK;
+	if (rc) return rc;
 	RowSrc src = plain_rows(packed, bpv);
 	return scan_host<IN_2BIT>(h, src, h ? sgx_row_stride(h->md.N) : 0, M, out8, valid);
 }
@@ -552,10 +551,9 @@ extern "C" int sgx_burden_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv,
 	if (!packed || !row_ptr || !var_idx || !lut || !out8 || !valid)
 		return fail(SGX_EINVAL, "sgx_burden_2bit: NULL buffer");
 	const int N = h->md.N;
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
 	const int32_t *bad;
-	int rc = csr_check("sgx_burden_2bit", "row_ptr", n_rows, row_ptr, var_idx, n_variants, &bad);
+	int rc = bpv_check(bpv, N);
+	if (!rc) rc = csr_check("sgx_burden_2bit", "row_ptr", n_rows, row_ptr, var_idx, n_variants, &bad);
 	if (rc) return rc;
 	if (bad) return fail(SGX_EINVAL, "sgx_burden_2bit: variant index %d out of range", *bad);
 	const int64_t nnz = row_ptr[n_rows];

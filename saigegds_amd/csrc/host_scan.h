@@ -228,12 +228,8 @@ extern "C" int sgx_scan_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_
 	if (!packed_dev || !out8_dev || !valid_dev)
 		return fail(SGX_EINVAL, "sgx_scan_2bit_dev: NULL buffer");
 	if (M > 0x7fffffffu / S3_NR) return fail(SGX_EINVAL, "sgx_scan_2bit_dev: too many variants in one call");
-	if (bpv % 64 != 0 || bpv < sgx_row_stride(h->md.N))
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu, need a multiple of 64 >= %zu",
-			bpv, sgx_row_stride(h->md.N));
-	if (((uintptr_t)packed_dev & 15u) != 0)
-		return fail(SGX_EINVAL, "sgx_scan_2bit_dev: packed_dev must be 16-byte aligned");
-	int rc = set_dev(h);
+	int rc = dev_rows_check("sgx_scan_2bit_dev", packed_dev, bpv, h->md.N);
+	if (!rc) rc = set_dev(h);
 	if (rc) return rc;
 	sgx_handle *lane = nullptr;
 	rc = next_lane(h, M, &lane);

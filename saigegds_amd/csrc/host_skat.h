@@ -160,46 +160,39 @@ static int skat_2bit_host(sgx_handle *h, const uint8_t *packed, size_t bpv, size
 	if (!packed || !unit_ptr || !var_idx || !lut || !score || !cov)
 		return fail(SGX_EINVAL, "sgx_skat_2bit: NULL buffer");
 	const int N = h->md.N, K = h->md.K, P = h->md.P, C = 2 * K + 1;
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	int rc = skat_units_check("sgx_skat_2bit", n_units, unit_ptr, var_idx, n_variants);
+	int rc = bpv_check(bpv, N);
+	if (!rc) rc = skat_units_check("sgx_skat_2bit", n_units, unit_ptr, var_idx, n_variants);
 	if (rc) return rc;
 	const int64_t nnz = unit_ptr[n_units];
 	if (nnz == 0) return SGX_OK;
-	rc = set_dev(h);
+	rc = begin_call(h);
 	if (rc) return rc;
-	rc = sync_lane(h);
-	if (rc) return rc;
-	h->last_issued = h;
 
 	const int ndw = (N + 15) >> 4;
 	SkatPlan pl;
 	skat_plan(pl, n_units, unit_ptr, C, (ndw + SKAT_SLAB_DW - 1) / SKAT_SLAB_DW);
-	const size_t T = pl.tiles.size();
 
 	// device copies: the rows (dword stride) in the host-row pipeline's chunks, then entries, tables, tiles
 	const size_t dbpv = (size_t)ndw * 4;
-	const size_t o_idx = (n_variants * dbpv + 15) & ~(size_t)15;
-	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
-	const size_t o_til = o_lut + (size_t)nnz * 4 * sizeof(double);
-	const size_t need = o_til + T * sizeof(SkatTile);
-	rc = grow(h->stage_pk, need);
+	TabLayout tl;
+	tl.add<uint8_t>(n_variants * dbpv);
+	const auto s_idx = tl.add(nnz, var_idx);
+	const auto s_lut = tl.add(nnz * 4, lut);
+	const auto s_til = tl.add(pl.tiles.size(), pl.tiles.data());
+	rc = grow(h->stage_pk, tl.bytes());
 	if (rc) return rc;
 	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
 	for (size_t off = 0; off < n_variants; off += rchunk) {
 		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), h->stream);
 		if (rc) return rc;
 	}
-	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut, (size_t)nnz * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_til, pl.tiles.data(), T * sizeof(SkatTile), hipMemcpyHostToDevice, h->stream));
+	rc = tabs_upload(h->stage_pk, h->stream, s_idx, s_lut, s_til);
+	if (rc) return rc;
 
 	rc = skat_run(h, pl, n_units, unit_ptr, C, [&](size_t t0, size_t nt) {
 		hipLaunchKernelGGL(skat_gram_kernel, dim3((unsigned)nt, (unsigned)pl.nslab), dim3(64), 0, h->stream,
-			h->stage_pk, dbpv, N, reinterpret_cast<const int *>(h->stage_pk + o_idx),
-			reinterpret_cast<const double *>(h->stage_pk + o_lut), h->md.F, P,
-			reinterpret_cast<const SkatTile *>(h->stage_pk + o_til) + t0, nt, SKAT_SLAB_DW, h->skat_part);
+			h->stage_pk, dbpv, N, tl.at(h->stage_pk, s_idx), tl.at(h->stage_pk, s_lut), h->md.F, P,
+			tl.at(h->stage_pk, s_til) + t0, nt, SKAT_SLAB_DW, h->skat_part);
 	}, dense, cov);
 	if (rc) return rc;
 	skat_finish(h->md, n_units, unit_ptr, dense, score, cov);

@@ -20,40 +20,29 @@ static int skat_ds_block_host(sgx_handle *h, const sgx_dsblock *b, size_t n_unit
 	if (rc) return rc;
 	const int64_t nnz = unit_ptr[n_units];
 	if (nnz == 0) return SGX_OK;
-	rc = sync_lane(h);
+	rc = begin_call(h);
 	if (rc) return rc;
-	h->last_issued = h;
 	const int N = b->N, P = h->md.P, C = 2 * h->md.K + 1;
 
 	SkatPlan pl;
 	skat_plan(pl, n_units, unit_ptr, C, (N + SKAT_DS_SLAB - 1) / SKAT_DS_SLAB);
-	const size_t T = pl.tiles.size();
 
 	// device copies of the tables: entries, means, tiles, flips
-	sgx_dsblock *bm = const_cast<sgx_dsblock *>(b);
-	const size_t o_mean = ((size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
-	const size_t o_til = o_mean + (size_t)nnz * sizeof(double);
-	const size_t o_flip = o_til + T * sizeof(SkatTile);
-	rc = grow(bm->tabs, o_flip + (size_t)nnz);
+	TabLayout tl;
+	const auto s_idx = tl.add(nnz, var_idx);
+	const auto s_mean = tl.add(nnz, mean);
+	const auto s_til = tl.add(pl.tiles.size(), pl.tiles.data());
+	const auto s_flip = tl.add(nnz, flip);
+	rc = grow(const_cast<sgx_dsblock *>(b)->tabs, tl.bytes());
+	if (!rc) rc = tabs_upload(b->tabs, h->stream, s_idx, s_mean, s_til, s_flip);
 	if (rc) return rc;
-	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
-	HIPCHK(hipMemcpyAsync(b->tabs, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(b->tabs + o_mean, mean, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(b->tabs + o_til, pl.tiles.data(), T * sizeof(SkatTile), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(hipMemcpyAsync(b->tabs + o_flip, flip, (size_t)nnz, hipMemcpyHostToDevice, h->stream));
 
-	const int *d_idx = reinterpret_cast<const int *>(b->tabs.p);
-	const double *d_mean = reinterpret_cast<const double *>(b->tabs + o_mean);
-	const SkatTile *d_til = reinterpret_cast<const SkatTile *>(b->tabs + o_til);
-	const uint8_t *d_flip = b->tabs + o_flip;
 	rc = skat_run(h, pl, n_units, unit_ptr, C, [&](size_t t0, size_t nt) {
-		const dim3 grid((unsigned)nt, (unsigned)pl.nslab);
-		if (b->dtype == SGX_DS_U8)
-			hipLaunchKernelGGL((skat_gram_ds_kernel<uint8_t>), grid, dim3(64), 0, h->stream,
-				(const uint8_t *)b->rows, N, d_idx, d_flip, d_mean, h->md.F, P, d_til + t0, nt, SKAT_DS_SLAB, h->skat_part);
-		else
-			hipLaunchKernelGGL((skat_gram_ds_kernel<double>), grid, dim3(64), 0, h->stream,
-				(const double *)b->rows.p, N, d_idx, d_flip, d_mean, h->md.F, P, d_til + t0, nt, SKAT_DS_SLAB, h->skat_part);
+		with_ds_rows(b->dtype, b->rows.p, [&](auto *rows, auto t) {
+			hipLaunchKernelGGL((skat_gram_ds_kernel<decltype(t)>), dim3((unsigned)nt, (unsigned)pl.nslab), dim3(64), 0, h->stream,
+				rows, N, tl.at(b->tabs, s_idx), tl.at(b->tabs, s_flip), tl.at(b->tabs, s_mean), h->md.F, P,
+				tl.at(b->tabs, s_til) + t0, nt, SKAT_DS_SLAB, h->skat_part);
+		});
 	}, dense, cov);
 	if (rc) return rc;
 	skat_finish(h->md, n_units, unit_ptr, dense, score, cov);

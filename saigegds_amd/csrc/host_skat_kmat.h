@@ -31,16 +31,6 @@ extern "C" int sgx_kmat_pcg_multi_dev(sgx_kmat *m, const double *w_dev, const do
 	return kmat_pcg_dev("sgx_kmat_pcg_multi_dev", m, w_dev, tau, B_dev, ldb, k, maxiter, tol, X_dev, iters);
 }
 
-// room for n elements of what the call keeps per unit, which is the caller's to size: out of memory is SGX_ENOMEM
-template <class T>
-static int skk_room(DevBuf<T> &b, size_t n, const char *what, const char *who = "sgx_skat_kmat_2bit")
-{
-	const hipError_t e = b.reserve(n);
-	if (e == hipSuccess) return SGX_OK;
-	(void)hipGetLastError();
-	return fail(mem_code(e), "%s: %zu bytes for %s: %s", who, n * sizeof(T), what, hipGetErrorString(e));
-}
-
 // out[r][c] = (vector row0 + r of L)' (vector col0 + c of R) for r < nr, c < nc (row-major, ldo apart): the tiles,
 // as many per launch as SKAT_PART_BYTES holds slab partials of, then the slabs added in slab order
 static int skk_product(sgx_handle *h, const double *L, int row0, int nr, const double *R, int col0, int nc, size_t ld,
@@ -54,9 +44,10 @@ static int skk_product(sgx_handle *h, const double *L, int row0, int nr, const d
 	const size_t T = tiles.size();
 	if (T == 0) return SGX_OK;
 	const size_t tchunk = std::min(T, std::max<size_t>(1, SKAT_PART_BYTES / ((size_t)nslab * 256 * sizeof(double))));
-	int rc = skk_room(h->skat_part, tchunk * (size_t)nslab * 256, "the slab partials");
-	if (!rc) rc = skk_room(h->skat_fin, tchunk * 256, "the tiles");
-	if (!rc) rc = skk_room(h->skk_tiles, tchunk, "the tile list");
+	const char *who = "sgx_skat_kmat_2bit";      // whichever entry the product is for: the text has named this one so far
+	int rc = dev_room(h->skat_part, tchunk * (size_t)nslab * 256, "the slab partials", who);
+	if (!rc) rc = dev_room(h->skat_fin, tchunk * 256, "the tiles", who);
+	if (!rc) rc = dev_room(h->skk_tiles, tchunk, "the tile list", who);
 	if (rc) return rc;
 	std::vector<double> fin(tchunk * 256);
 	for (size_t t0 = 0; t0 < T; t0 += tchunk) {
@@ -190,19 +181,17 @@ static int skk_columns(sgx_handle *h, const SkkSrc &src, int m, double *A, size_
 	if (!src.ds)
 		hipLaunchKernelGGL(skk_colsum_kernel, dim3((unsigned)ncslab, (unsigned)m), dim3(256), 0, st, src.rows, src.dbpv, N,
 			src.idx, src.lut, h->md.F, P, K, h->skk_cpart);
-	else if (src.ds_dtype == SGX_DS_U8) skk_colsum_ds<uint8_t>(h, src, ncslab, m);
-	else skk_colsum_ds<double>(h, src, ncslab, m);
+	else with_ds_rows(src.ds_dtype, src.ds, [&](auto *, auto t) { skk_colsum_ds<decltype(t)>(h, src, ncslab, m); });
 	hipLaunchKernelGGL(skk_colfin_kernel, dim3((unsigned)(((size_t)m * C1 + 255) / 256)), dim3(256), 0, st, h->skk_cpart,
 		(size_t)m * C1, ncslab, C1, h->skk_cs);
 	if (!src.ds)
 		hipLaunchKernelGGL(skk_adj_kernel, dim3(gl, (unsigned)m), dim3(256), 0, st, src.rows, src.dbpv, N, src.idx, src.lut,
 			h->md.X, K, h->skk_cs, A, lda);
-	else if (src.ds_dtype == SGX_DS_U8)
-		hipLaunchKernelGGL((skk_adj_ds_kernel<uint8_t>), dim3(gl, (unsigned)m), dim3(256), 0, st, (const uint8_t *)src.ds, N,
-			src.idx, src.flip, src.mean, h->md.X, K, h->skk_cs, A, lda);
 	else
-		hipLaunchKernelGGL((skk_adj_ds_kernel<double>), dim3(gl, (unsigned)m), dim3(256), 0, st, (const double *)src.ds, N,
-			src.idx, src.flip, src.mean, h->md.X, K, h->skk_cs, A, lda);
+		with_ds_rows(src.ds_dtype, src.ds, [&](auto *rows, auto t) {
+			hipLaunchKernelGGL((skk_adj_ds_kernel<decltype(t)>), dim3(gl, (unsigned)m), dim3(256), 0, st, rows, N,
+				src.idx, src.flip, src.mean, h->md.X, K, h->skk_cs, A, lda);
+		});
 	HIPCHK(hipGetLastError());
 	std::vector<double> cs((size_t)m * C1);
 	HIPCHK(hipMemcpyAsync(cs.data(), h->skk_cs, cs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -231,11 +220,11 @@ static int skk_unit_room(const char *who, sgx_handle *h, size_t m_max)
 	const int N = h->md.N, K = h->md.K, C1 = K + 1;
 	const int ndw = (N + 15) >> 4, ncslab = (ndw + SKK_CSLAB_DW - 1) / SKK_CSLAB_DW;
 	const size_t lda = (size_t)ndw * 16;
-	int rc = skk_room(h->skk_XZ, (size_t)2 * K * lda, "the covariate columns", who);
-	if (!rc) rc = skk_room(h->skk_A, m_max * lda, "a unit's columns", who);
-	if (!rc) rc = skk_room(h->skk_Y, m_max * lda, "a unit's solves", who);
-	if (!rc) rc = skk_room(h->skk_cpart, m_max * ncslab * C1, "the column sums", who);
-	if (!rc) rc = skk_room(h->skk_cs, m_max * C1, "the column sums", who);
+	int rc = dev_room(h->skk_XZ, (size_t)2 * K * lda, "the covariate columns", who);
+	if (!rc) rc = dev_room(h->skk_A, m_max * lda, "a unit's columns", who);
+	if (!rc) rc = dev_room(h->skk_Y, m_max * lda, "a unit's solves", who);
+	if (!rc) rc = dev_room(h->skk_cpart, m_max * ncslab * C1, "the column sums", who);
+	if (!rc) rc = dev_room(h->skk_cs, m_max * C1, "the column sums", who);
 	return rc;
 }
 
@@ -342,20 +331,16 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	const int N = h->md.N;
 	int rc = skk_km_check(who, h, km);
 	if (rc) return rc;
-	if (bpv < (size_t)(N + 3) / 4)
-		return fail(SGX_EINVAL, "Invalid length of dosages: bytes_per_variant=%zu < ceil(N/4)=%zu", bpv, (size_t)(N + 3) / 4);
-	rc = skk_sigma_args(who, N, w, tau, maxiter);
+	rc = bpv_check(bpv, N);
+	if (!rc) rc = skk_sigma_args(who, N, w, tau, maxiter);
 	if (rc) return rc;
 	if (n_units == 0) return SGX_OK;
 	rc = skat_units_check(who, n_units, unit_ptr, var_idx, n_variants);
 	if (rc) return rc;
 	const int64_t nnz = unit_ptr[n_units];
 	if (nnz == 0) return SGX_OK;
-	rc = set_dev(h);
+	rc = begin_call(h);
 	if (rc) return rc;
-	rc = sync_lane(h);
-	if (rc) return rc;
-	h->last_issued = h;
 	hipStream_t st = h->stream;
 	auto t_col = std::chrono::steady_clock::now();
 	h->skk_ms[0] = h->skk_ms[1] = h->skk_ms[2] = 0;
@@ -371,10 +356,11 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	// device copies: the rows (dword stride) in the host-row pipeline's chunks, then entries and tables
 	const int ndw = (N + 15) >> 4;
 	const size_t dbpv = (size_t)ndw * 4;
-	const size_t o_idx = (n_variants * dbpv + 15) & ~(size_t)15;
-	const size_t o_lut = (o_idx + (size_t)nnz * sizeof(int) + 15) & ~(size_t)15;
-	const size_t need = o_lut + (size_t)nnz * 4 * sizeof(double);
-	rc = skk_room(h->stage_pk, need, "the rows");
+	TabLayout tl;
+	tl.add<uint8_t>(n_variants * dbpv);
+	const auto s_idx = tl.add(nnz, var_idx);
+	const auto s_lut = tl.add(nnz * 4, lut_ok.data());
+	rc = dev_room(h->stage_pk, tl.bytes(), "the rows", who);
 	if (!rc) rc = skk_unit_room(who, h, (size_t)m_max);
 	if (rc) return rc;
 	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
@@ -382,13 +368,12 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), st);
 		if (rc) return rc;
 	}
-	static_assert(sizeof(int) == sizeof(int32_t), "var_idx");
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_idx, var_idx, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(h->stage_pk + o_lut, lut_ok.data(), (size_t)nnz * 4 * sizeof(double), hipMemcpyHostToDevice, st));
+	rc = tabs_upload(h->stage_pk, st, s_idx, s_lut);
+	if (rc) return rc;
 	SkkSrc src;
-	src.idx = reinterpret_cast<const int *>(h->stage_pk + o_idx);
+	src.idx = tl.at(h->stage_pk, s_idx);
 	src.rows = h->stage_pk; src.dbpv = dbpv;
-	src.lut = reinterpret_cast<const double *>(h->stage_pk + o_lut);
+	src.lut = tl.at(h->stage_pk, s_lut);
 	return skk_units(who, h, km, src, n_units, unit_ptr, bad, (size_t)m_max, w, tau, maxiter, tol, t_col, score, cov, iters);
 }
 

@@ -61,7 +61,6 @@ extern "C" int sgx_skato_spectra(sgx_handle *h, size_t n, const int32_t *m_of, c
 	if (!rc) rc = grow(h->eig_out, ne);
 	if (!rc) rc = grow(h->eig_sw, n * (size_t)nmat);
 	if (rc) return rc;
-	static_assert(sizeof(int) == sizeof(int32_t), "m_of");
 	const long long *d_aoff = reinterpret_cast<const long long *>(h->eig_meta.p);
 	const long long *d_eoff = reinterpret_cast<const long long *>(h->eig_meta + o_eoff);
 	const double *d_ab = reinterpret_cast<const double *>(h->eig_meta + o_ab);

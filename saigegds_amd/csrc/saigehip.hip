@@ -93,6 +93,7 @@ static int fail(int code, const char *fmt, ...)
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
 #include "host_mem.h"
+#include "host_tabs.h"
 #include "host_state.h"
 #include "host_init.h"
 #include "host_spa.h"

@@ -258,3 +258,27 @@ def scaled_error(cov, ref):
     with np.errstate(divide="ignore", invalid="ignore"):
         e = np.where(sc > 0, d / sc, np.where(d == 0, 0.0, np.inf))
     return float(e.max())
+
+
+def chunk_case(m, seed):
+    """The inputs of the tests that cut the host rows into chunks: N = 70 001, K = 2 covariates, m rows of hard calls,
+    and a GRM of pairs (1 on the diagonal, 0.5 between samples 2i and 2i + 1; the last sample alone) as CSR, so that
+    the solves are trivial.  Made once per (m, seed)."""
+    key = ("chunk", m, seed)
+    if key not in _cases:
+        from saigegds_amd.gds import pack_dosage_2bit
+        n = 70001
+        mod, sm = flat_model(n, 2, "binary")
+        assert sm.k == 2
+        codes = hard_calls(n, m, seed)
+        from skat_ref import tables
+        i = np.arange(n)
+        mate = i ^ 1
+        cols = np.stack([np.minimum(i, mate), np.maximum(i, mate)], axis=1)
+        keep = cols < n
+        row_ptr = np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int64)
+        val = np.where(cols == i[:, None], 1.0, 0.5)
+        _cases[key] = dict(sm=sm, packed=pack_dosage_2bit(codes), lut=tables(codes), storage="csr", K=None,
+                           csr=(row_ptr, cols[keep].astype(np.int32), val[keep]),
+                           w=np.ascontiguousarray(np.asarray(mod.V, dtype=np.float64)), tau=np.array([1.0, 0.5]))
+    return _cases[key]

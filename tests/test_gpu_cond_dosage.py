@@ -339,3 +339,19 @@ def test_9_driver_file_of_dosages():
     cond = [mem.variant_id[25], mem.variant_id[63]]
     got, ref, near = _driver_pair(path, mod, cond, mac=1)
     _driver_check(got, ref, mem.variant_id, near, cond)
+
+
+def test_3_an_odd_count_of_entries_at_odd_n():
+    """A set of 7 rows, not in block order, of a u8 block at N = 1001: the means, the index list and the flips each end
+    off a 16-byte boundary, and each table still starts on one.  Phi_CC against the reference of test 1 (the set's
+    rows there, of which these are 7), S_C and Phi_CC against skat on the set as one unit, bit for bit."""
+    import torch  # noqa: F401
+    from saigegds_amd._lib import Scanner
+    c = _case(1001, "u8")
+    idx = np.array([6, 0, 3, 7, 1, 5, 2], dtype=np.int32)
+    with Scanner(c["sm"]) as sc, _block(sc, c["rows_c"]) as blk:
+        s, covs = blk.skat([0, idx.size], idx, c["fc"][idx], c["mc"][idx])
+        s_c, phi_cc = blk.cond_set(idx, c["fc"][idx], c["mc"][idx])
+    assert s_c.tobytes() == s.tobytes() and phi_cc.tobytes() == covs[0].tobytes()
+    R_cc = np.asarray(c["ref"]["Phi_CC"], dtype=np.float64)[np.ix_(idx, idx)]
+    assert np.all(np.abs(phi_cc - R_cc) <= 1e-10 * np.sqrt(np.outer(np.diag(R_cc), np.diag(R_cc))))

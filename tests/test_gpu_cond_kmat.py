@@ -214,3 +214,31 @@ def test_7_errors_launch_nothing_and_leave_the_handles_usable():
         sc.cond_set(packed[:0], lut[:0])
         again = sc.cond_kmat(op, packed[1:], lut[1:])
         assert same_bits(again[1], good[1]) and same_bits(again[2], good[2])
+
+
+def test_8_host_rows_in_chunks_of_more_than_one_solve():
+    """sgx_cond_kmat_2bit sends its rows up in chunks of pipe_mb MiB at the device stride 4 ceil(N / 16): 17 504 bytes at
+    N = 70 001, so pipe_mb = 2 is 119 rows a chunk -- more than the SGX_GRM_MAX_RHS = 64 columns of a solve and not a
+    multiple of them, so that a chunk is two solves (64 + 55) whose second reads the rows and tables from row 64 on.
+    120 rows (a chunk and one row) and 245 (two chunks and a tail of 7, not a multiple of 16), K = 2, C = 2, on a GRM of
+    pairs: the bits of the one-chunk call."""
+    import torch  # noqa: F401
+    from saigegds_amd._lib import Scanner
+    c = M.chunk_case(2 + 245, 43)
+    packed, lut = c["packed"], c["lut"]
+    assert (2 << 20) // (4 * ((70001 + 15) // 16)) == 119
+    with Scanner(c["sm"]) as sc, operator(c) as op:
+        sc.cond_kmat_set(op, packed[2:4], lut[2:4], c["w"], c["tau"], M.MAXITER, M.TOL_SOLVE)
+        rows, tabs = np.delete(packed, [2, 3], axis=0), np.delete(lut, [2, 3], axis=0)
+        try:
+            for m in (120, 245):
+                got = {}
+                for pipe_mb in (0, 2):
+                    sc.set_option("pipe_mb", pipe_mb)
+                    got[pipe_mb] = sc.cond_kmat(op, rows[:m], tabs[:m])
+                assert np.isfinite(got[0][1]).sum() >= m - 2 and got[0][2].shape == (m, 2)
+                for k in range(3):
+                    assert got[0][k].tobytes() == got[2][k].tobytes(), (m, k)
+                assert np.array_equal(got[0][3], got[2][3]), m
+        finally:
+            sc.set_option("pipe_mb", 0)

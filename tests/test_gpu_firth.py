@@ -251,3 +251,31 @@ def test_memory_returns():
     assert live_bytes() == held
     sc.close()
     assert live_bytes() == start
+
+
+def test_host_rows_in_chunks():
+    """sgx_firth_2bit sends its rows up in chunks of pipe_mb MiB at the device stride sgx_row_stride(N) = 128 ceil(N / 512):
+    17 536 bytes at N = 70 001, so pipe_mb = 1 is 59 rows a chunk.  60 rows (a chunk and one row) and 125 (two chunks and
+    a tail of 7, not a multiple of 16) give the bits of the one-chunk call."""
+    from saigegds_amd._lib import Scanner
+    from saigegds_amd.gds import pack_dosage_2bit
+    n, m = 70001, 125
+    sm = _model(n)
+    rng = np.random.default_rng(12)
+    f = rng.choice([0.003, 0.02, 0.1], m)[:, None]
+    u = rng.random((m, n))
+    codes = ((u < f * f).astype(np.uint8) + (u < 1 - (1 - f) ** 2)).astype(np.uint8)
+    codes[rng.random((m, n)) < 0.01] = 3
+    packed, lut = pack_dosage_2bit(codes), _tables(codes)
+    with Scanner(sm) as sc:
+        assert (1 << 20) // sc.row_stride() == 59
+        try:
+            for rows in (60, m):
+                sc.set_option("pipe_mb", 0)
+                one = sc.firth_2bit(packed[:rows], lut[:rows])
+                sc.set_option("pipe_mb", 1)
+                cut = sc.firth_2bit(packed[:rows], lut[:rows])
+                assert (one[:, 3] == 1).sum() > rows // 2
+                assert one.tobytes() == cut.tobytes(), rows
+        finally:
+            sc.set_option("pipe_mb", 0)

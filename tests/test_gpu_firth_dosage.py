@@ -283,3 +283,18 @@ def test_7_memory_returns():
     blk.close()
     sc.close()
     assert live_bytes() == start
+
+
+def test_1_an_odd_count_of_entries_at_odd_n():
+    """7 entries, not in block order, of a u8 block at N = 1027: the means, the results, the index list and the flips
+    each end off a 16-byte boundary, and each table still starts on one.  Against the reference of test 1."""
+    from saigegds_amd._lib import Scanner
+    from saigegds_amd.gds import unpack_dosage_2bit
+    n = 1027
+    sm, packed, lut, ref = _case(n)
+    rows = _as_dosage(unpack_dosage_2bit(packed, n), np.uint8)
+    flip, mean = (lut[:, 0] == 2).astype(np.uint8), lut[:, 3].copy()
+    idx = np.array([7, 0, 4, 2, 6, 3, 1], dtype=np.int32)
+    with Scanner(sm) as sc:
+        got = _firth(sc, rows, idx, flip[idx], mean[idx])
+    check(got, ref[idx], f"N={n} u8, 7 entries")

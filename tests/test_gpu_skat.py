@@ -221,3 +221,31 @@ def test_7_driver_end_to_end():
     for c in ("Q.b1_1", "pval.b1_1", "Q.b1_25", "pval.b1_25", "maf.avg", "mac.avg"):
         close(got[c], ref[c], 1e-9, c)
     assert np.isfinite(got["pval.b1_25"]).all()
+
+
+def test_8_rows_uploaded_in_chunks():
+    """sgx_skat_2bit sends its rows up in chunks of pipe_mb MiB at the device stride 4 ceil(N / 16): 17 504 bytes at
+    N = 70 001, so pipe_mb = 1 is 59 rows a chunk.  60 rows (a chunk and one row) and 125 (two chunks and a tail of 7,
+    not a multiple of 16), two units whose entries point across the chunks, give the bits of the one-chunk call."""
+    import torch  # noqa: F401
+    from saigegds_amd._lib import Scanner
+    from saigegds_amd.gds import pack_dosage_2bit
+    n = 70001
+    sm = _case(n)[0]
+    codes = R.hard_calls(n, 125, 31 + n)
+    packed, lut = pack_dosage_2bit(codes), R.tables(codes)
+    assert (1 << 20) // (4 * ((n + 15) // 16)) == 59
+    with Scanner(sm) as sc:
+        try:
+            for rows, cut in ((60, 17), (125, 40)):
+                idx = np.random.default_rng(rows).permutation(rows)
+                got = {}
+                for pipe_mb in (0, 1):
+                    sc.set_option("pipe_mb", pipe_mb)
+                    got[pipe_mb] = sc.skat_2bit(packed[:rows], [0, cut, rows], idx, lut[idx])
+                assert np.isfinite(got[0][0]).all()
+                assert got[0][0].tobytes() == got[1][0].tobytes(), rows
+                for a, b in zip(got[0][1], got[1][1]):
+                    assert a.tobytes() == b.tobytes(), rows
+        finally:
+            sc.set_option("pipe_mb", 0)

@@ -308,3 +308,15 @@ def test_8_driver_on_a_packed_real_file(tmp_path):
         b = seqAssocGLMM_spaSKAT(src, mod, units, verbose=False, ds_budget=budget)
         A.same_dicts(a, b, f"budget {budget}")
         assert np.isfinite(a["pval.b1_25"]).sum() >= len(units) // 2 and (a["n.var"] > 0).sum() >= len(units) // 2
+
+
+def test_9_an_odd_count_of_entries_at_odd_n():
+    """15 entries, not in block order, of a u8 block at N = 1001: the index list, the means and the flips each end off
+    a 16-byte boundary, and each table still starts on one.  Against the reference of test 1."""
+    import torch  # noqa: F401
+    from saigegds_amd._lib import Scanner
+    sm, rows, flip, mean, S, cov = _case(1001, "u8")
+    idx = np.random.default_rng(15).permutation(40)[:15].astype(np.int32)
+    with Scanner(sm) as sc, _block(sc, rows) as blk:
+        score, covs = blk.skat([0, 15], idx, flip[idx], mean[idx])
+    check(score, covs[0], S[idx], cov[np.ix_(idx, idx)], "u8 N=1001, 15 entries")

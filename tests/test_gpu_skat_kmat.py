@@ -207,3 +207,30 @@ def test_8_the_device_form_of_the_solve_equals_the_host_form(name, k):
         it_d = op.pcg_many_dev(w_d.data_ptr(), c["tau"], B_d.data_ptr(), ldb, k, X_d.data_ptr(), maxiter=500, tol=1e-9)
         Xh = X_d.cpu().numpy()
     assert np.array_equal(it_d, it) and same_bits(np.ascontiguousarray(Xh[:, :n]), X) and np.all(Xh[:, n:] == 0)
+
+
+def test_9_rows_uploaded_in_chunks():
+    """sgx_skat_kmat_2bit sends its rows up as sgx_skat_2bit does, in chunks of pipe_mb MiB at the device stride
+    4 ceil(N / 16): 17 504 bytes at N = 70 001, so pipe_mb = 1 is 59 rows a chunk.  60 rows (a chunk and one row) and
+    125 (two chunks and a tail of 7, not a multiple of 16), two units whose entries point across the chunks, K = 2, on
+    a GRM of pairs: the bits of the one-chunk call."""
+    import torch  # noqa: F401
+    from saigegds_amd._lib import Scanner
+    c = M.chunk_case(125, 41)
+    packed, lut = c["packed"], c["lut"]
+    with Scanner(c["sm"]) as sc, operator(c) as op:
+        try:
+            for rows, cut in ((60, 17), (125, 40)):
+                idx = np.random.default_rng(rows).permutation(rows)
+                got = {}
+                for pipe_mb in (0, 1):
+                    sc.set_option("pipe_mb", pipe_mb)
+                    got[pipe_mb] = sc.skat_kmat(op, packed[:rows], [0, cut, rows], idx, lut[idx], c["w"], c["tau"],
+                                                maxiter=M.MAXITER, tol=M.TOL_SOLVE)
+                keep = np.flatnonzero(np.isfinite(got[0][0]))
+                assert keep.size >= rows - 2                 # (the monomorphic row has no finite statistics)
+                assert got[0][0].tobytes() == got[1][0].tobytes() and np.array_equal(got[0][2], got[1][2]), rows
+                for a, b in zip(got[0][1], got[1][1]):
+                    assert a.tobytes() == b.tobytes(), rows
+        finally:
+            sc.set_option("pipe_mb", 0)
