@@ -356,6 +356,33 @@ int sgx_firth_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_varian
 int sgx_firth_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_per_variant, size_t n_variants,
 	const double *lut_dev, int maxit, double *out4_dev);
 
+/* Exact p-value of a binary-trait row with few minor alleles (saigegds_amd/exact.py; SAIGE proper's "efficient
+ * resampling"; nothing of this is in the reference).  Table as above, t = lut[4j .. 4j + 3], g_i = t[code_i];
+ * it is valid when t[1] == 1, (t[0], t[2]) is (0, 2) or (2, 0) and t[3] is finite.  Carriers: the samples with code 0..2
+ * and g_i in {1, 2}, in ascending sample order; MAC = sum g_i over them.  Samples with code 3 (imputed to t[3]) are not
+ * resampled: delta = t[3] * sum_{code 3} (y_i - mu_i).  The scan's score is T = A - m' with A = sum_carriers g_i y_i, an
+ * integer in 0..MAC, and m' = sum_carriers g_i mu_i - delta.  Under the null the carriers' y_i are independent
+ * Bernoulli(mu_i): the pmf f of A starts as [1, 0, ...] and takes a carrier by f[a] <- (1 - mu_i) f[a] + mu_i f[a - g_i].
+ * With d_a = |a - m'| and d_obs = |A_obs - m'| in double, summed over ascending a,
+ *   p.full = sum_{d_a >= d_obs} f[a],     p.mid = sum_{d_a > d_obs} f[a] + 0.5 sum_{d_a == d_obs} f[a],
+ *   out4[4j .. 4j + 3] = {p.mid, p.full, MAC, done};
+ * done = 0 with NaN p-values for MAC == 0, MAC > max_mac or an invalid table (then out4[4j + 2] = 0 too); none of these
+ * disturbs another row.  The samples are taken as independent: neither the variance ratio nor the GRM enters.
+ *   sgx_exact_2bit      rows in HOST memory, uploaded in the chunks of sgx_firth_2bit.  Synchronous; a thin wrapper
+ *                       around the next entry: same kernel, same bits.
+ *   sgx_exact_2bit_dev  rows in DEVICE memory (stride and alignment as for sgx_scan_2bit_dev); table and results are
+ *                       device pointers.  Asynchronous on the handle's stream; results are readable after sgx_sync().
+ * One wave per row, one pass over the row, FP64 sums in a fixed order, no atomics, no scratch: a row's results depend on
+ * the row, its table and the model only -- not on its position, the other rows, the grid or the chunks.  n_variants = 0
+ * succeeds and does nothing.  max_mac outside 1..SGX_EXACT_MAX_MAC, a quantitative-trait handle, a NULL buffer,
+ * bytes_per_variant < ceil(n_samp / 4), or a bad device stride or alignment returns SGX_EINVAL and launches nothing; the
+ * handle stays usable. */
+#define SGX_EXACT_MAX_MAC 63
+int sgx_exact_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant, size_t n_variants,
+	const double *lut, int max_mac, double *out4);
+int sgx_exact_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_per_variant, size_t n_variants,
+	const double *lut_dev, int max_mac, double *out4_dev);
+
 /* Aggregate tests on dosage input: the INTSXP / REALSXP branches of ds_mat_mafmac and ds_mat_burden
  * (src/saige_main.cpp:485-610), which the R drivers reach with .dsnode(gdsfile, dsnode) for imputed
  * data (R/assoc_aggregate.r:89,351,606).  A batch of dosage rows (u8: 0xFF = missing; i32: INT_MIN =

@@ -10,6 +10,7 @@ Public surface (mirrors the reference's R API for this path):
     seqAssocGLMM_SPA_cond scan given a set of conditioning variants (not in the reference)
     seqFitDenseGRM, seqFitSparseGRM  the explicit GRM, dense and thresholded (not in the reference)
     load_grm, ExplicitGrmOperator    read it back; the operator seqFitNullGLMM_SPA(grm_mat=) fits on
+    exact_pass, EXACT_MAX_MAC  exact p-values of ultra-rare rows, seqAssocGLMM_SPA(exact_mac=) (not in the reference)
     seqSAIGE_LoadPval  load saved association results     (R/saige_main.r:164-215)
 The compute lives in libsaigehip.so (include/saigehip.h); there is no CPU path.
 """
@@ -25,5 +26,6 @@ from .cond import cond_tests, seqAssocGLMM_SPA_cond  # noqa: F401
 from .grm import SparseGRM, load_grm, seqFitDenseGRM, seqFitSparseGRM  # noqa: F401
 from ._lib import ExplicitGrmOperator  # noqa: F401
 from .results import seqSAIGE_LoadPval  # noqa: F401
+from .exact import EXACT_MAX_MAC, exact_pass  # noqa: F401
 
 __version__ = "0.1.0"

@@ -200,6 +200,8 @@ def _abi():
         "sgx_cond_2bit_dev": (ci, [vp, vp, sz, sz, vp, vp, vp, vp]),
         "sgx_firth_2bit": (ci, [vp, vp, sz, sz, vp, ci, vp]),
         "sgx_firth_2bit_dev": (ci, [vp, vp, sz, sz, vp, ci, vp]),
+        "sgx_exact_2bit": (ci, [vp, vp, sz, sz, vp, ci, vp]),
+        "sgx_exact_2bit_dev": (ci, [vp, vp, sz, sz, vp, ci, vp]),
         "sgx_ds_block_cond_set": (ci, [vp, vp, sz, vp, vp, vp, vp, vp]),
         "sgx_ds_block_cond": (ci, [vp, vp, vp, vp, vp, vp, vp]),
         "sgx_ds_block_firth": (ci, [vp, vp, sz, vp, vp, vp, ci, vp]),
@@ -576,6 +578,23 @@ class Scanner(_Handle):
         """``firth_2bit`` on rows, tables and results in device memory (``sgx_firth_2bit_dev``; asynchronous, sync()
         before reading)."""
         check(self._L.sgx_firth_2bit_dev(self._h, packed_ptr, bpv, m, lut_ptr, int(maxit), out4_ptr))
+
+    def exact_2bit(self, packed: np.ndarray, lut, max_mac: int):
+        """Exact p-values of the 2-bit rows with at most ``max_mac`` (1..63) minor alleles (one 4-entry dosage table
+        each; ``sgx_exact_2bit``; binary traits) -> out4 [m, 4]: p.mid, p.full, MAC, done (1 / 0).  NaN /
+        NaN / MAC / 0 for a row with no carrier or more than ``max_mac`` minor alleles, NaN / NaN / 0 / 0 for a table
+        that is not {0, 1, 2, finite} or {2, 1, 0, finite}."""
+        packed, lut = _row_tables("exact_2bit", packed, lut)
+        m = packed.shape[0]
+        out4 = np.zeros((max(1, m), 4))
+        check(self._L.sgx_exact_2bit(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data, int(max_mac),
+                                     out4.ctypes.data))
+        return out4[:m]
+
+    def exact_2bit_dev(self, packed_ptr: int, bpv: int, m: int, lut_ptr: int, out4_ptr: int, max_mac: int):
+        """``exact_2bit`` on rows, tables and results in device memory (``sgx_exact_2bit_dev``; asynchronous, sync()
+        before reading)."""
+        check(self._L.sgx_exact_2bit_dev(self._h, packed_ptr, bpv, m, lut_ptr, int(max_mac), out4_ptr))
 
     def dosage_block(self, dtype, max_variants: int) -> "DosageBlock":
         """Device storage for a batch of dosage rows of the aggregate tests (``DosageBlock`` below)."""

@@ -298,7 +298,7 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
                      mac: float = 10, missing: float = 0.1, dsnode: str = "", spa_pval: float = 0.05,
                      var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
                      parallel: Union[bool, int] = False, verbose: bool = True, timing: Optional[Dict[str, float]] = None,
-                     firth_pval: Optional[float] = None, firth_maxit: int = 50):
+                     firth_pval: Optional[float] = None, firth_maxit: int = 50, exact_mac: Optional[int] = None):
     """SAIGE single-variant association scan on MI355X.
 
     Returns a ``dict`` of equal-length columns (``pandas.DataFrame(result)``
@@ -312,6 +312,15 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     ``beta.firth`` (for the alt allele, like ``beta``), ``SE.firth`` and ``cvg.firth`` (NaN / NaN / False on the other
     rows).  None: no such columns and no such pass.  ``res_savefn``: ``.rds`` / ``.RData``; the ``.gds`` writer has
     fixed columns and is refused.
+
+    ``exact_mac`` (not in the reference; SAIGE proper's ``--max_MAC_for_ER``; binary traits; hard calls only): an
+    integer in 1..63 -- after the scan every valid row with ``mac <= exact_mac`` gets the exact null distribution of
+    its score over the carriers' phenotypes (``saigegds_amd.exact``; ``sgx_exact_2bit``) on device 0, with
+    a LOCO model against its chromosome's model, and the result gains ``pval.exact`` (mid-p) and ``pval.exact.full``
+    (NaN on the other rows).  The test takes the samples as independent: neither the variance ratio nor the GRM
+    enters.  Rows below the scan's own ``mac`` filter (default 10) are never valid: lower ``mac`` for the option to
+    bite.  None: no such columns and no such pass.  It combines freely with ``firth_pval``; the ``.gds`` writer is
+    refused as for it.
     """
     check_scan_args(maf, mac, missing, spa_pval, var_ratio, dsnode, res_savefn, res_compress, verbose)
     if firth_pval is not None:
@@ -321,6 +330,11 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
             raise ValueError("`firth_maxit` should be a positive integer.")
         if re.search(r"\.gds$", res_savefn, re.I):
             raise ValueError("The gds output has no columns for the Firth effect sizes; save to RData or RDS.")
+    if exact_mac is not None:
+        if not isinstance(exact_mac, (int, np.integer)) or isinstance(exact_mac, bool) or not 1 <= exact_mac <= 63:
+            raise ValueError("`exact_mac` should be None or an integer in 1..63.")
+        if re.search(r"\.gds$", res_savefn, re.I):
+            raise ValueError("The gds output has no columns for the exact p-values; save to RData or RDS.")
     if verbose:
         print("SAIGE association analysis:")
 
@@ -338,6 +352,12 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
             raise ValueError("Firth effect sizes are for binary traits.")
         from . import _lib
         firth_inp = firth.firth_input(inp, _lib.Scanner)      # (no dosage route: NotImplementedError, before any row is scanned)
+    exact_inp = None
+    if exact_mac is not None:
+        from . import exact
+        if mod.trait_type != "binary":
+            raise ValueError("Exact p-values are for binary traits.")
+        exact_inp = exact.exact_input(inp)                    # (true dosages: NotImplementedError, before any row is scanned)
     if verbose:
         print(f"    # of samples: {_pretty(n_samp)}")
         print(f"    # of variants: {_pretty(n_var)}")
@@ -347,6 +367,9 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         print(f"    p-value threshold for SPA adjustment: {spa_pval}")
         if firth_pval is not None:
             print(f"    p-value threshold for Firth effect sizes: {firth_pval}")
+        if exact_mac is not None:
+            print(f"    MAC threshold for exact p-values: {exact_mac} (rows below the MAC threshold above, {mac}, are "
+                  "never valid: lower `mac` to reach them)")
     if not math.isfinite(var_ratio):
         var_ratio = float(np.nanmean(mod.var_ratio))
     if verbose:
@@ -393,11 +416,25 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         for col, g in zip(fcols, got):
             col[rows] = g[rows]
 
+    ecols = None
+    if exact_mac is not None:
+        ecols = (np.full(n_var, np.nan), np.full(n_var, np.nan))
+
+    def exact_rows(r0, r1, obj):
+        """The exact pass of the scanned rows [r0, r1) against the model they were scanned with."""
+        with np.errstate(invalid="ignore"):
+            rows = r0 + np.flatnonzero((valid[r0:r1] != 0) & (out[r0:r1, 1] <= exact_mac))
+        got = exact.exact_pass(exact_inp, out, valid, rows, lambda: Scanner(obj, device=0), int(exact_mac))
+        for col, g in zip(ecols, got):
+            col[rows] = g[rows]
+
     if not mod.loco:
         blocks = [(off, min(n_var, off + bl_size)) for off in range(0, n_var, bl_size)]
         scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, inp.read_block, kind == "packed", out, valid, timing)
         if fcols is not None:
             firth_rows(0, n_var, mobj)
+        if ecols is not None:
+            exact_rows(0, n_var, mobj)
     else:
         # leave-one-chromosome-out: the block list is cut at chromosome boundaries, and every run of one
         # chromosome is scanned against that chromosome's model (its fitted values; y, V, XV, XXVX_inv and
@@ -417,6 +454,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
                         timing)
             if fcols is not None:
                 firth_rows(r0, r1, run_obj)
+            if ecols is not None:
+                exact_rows(r0, r1, run_obj)
     if timing is not None:
         timing["blocks_s"] = time.perf_counter() - t_loop      # handles + every block (decode and scan overlapped)
 
@@ -427,6 +466,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     ans = assemble_result(src, x, out, mod.trait_type)
     if fcols is not None:
         ans["beta.firth"], ans["SE.firth"], ans["cvg.firth"] = (c[x] for c in fcols)
+    if ecols is not None:
+        ans["pval.exact"], ans["pval.exact.full"] = (c[x] for c in ecols)
     return finish_result(ans, res_savefn, res_compress, verbose, inp.sample_id() if res_savefn else None)
 
 

@@ -88,6 +88,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_cond_kmat.h"
 #include "kern_firth.h"
 #include "kern_firth_ds.h"
+#include "kern_exact.h"
 #include "kern_eig.h"
 
 // ---------------------------------------------------------------------------
@@ -115,4 +116,5 @@ static int fail(int code, const char *fmt, ...)
 #include "host_cond_kmat.h"
 #include "host_kmat_ds.h"
 #include "host_firth.h"
+#include "host_exact.h"
 #include "host_skato.h"
