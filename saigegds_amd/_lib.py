@@ -563,38 +563,41 @@ class Scanner(_Handle):
         before reading)."""
         check(self._L.sgx_cond_2bit_dev(self._h, packed_ptr, bpv, m, lut_ptr, score_ptr, var_ptr, cov_ptr))
 
+    def _out4_2bit(self, what: str, packed, lut, opt: int):
+        """``sgx_<what>`` on 2-bit rows with one table each and the entry's integer option -> out4 [m, 4]."""
+        packed, lut = _row_tables(what, packed, lut)
+        m = packed.shape[0]
+        out4 = np.zeros((max(1, m), 4))
+        check(getattr(self._L, "sgx_" + what)(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data, int(opt),
+                                              out4.ctypes.data))
+        return out4[:m]
+
+    def _out4_2bit_dev(self, what: str, packed_ptr: int, bpv: int, m: int, lut_ptr: int, opt: int, out4_ptr: int):
+        """``sgx_<what>`` on rows, tables and out4 in device memory, with the entry's integer option."""
+        check(getattr(self._L, "sgx_" + what)(self._h, packed_ptr, bpv, m, lut_ptr, int(opt), out4_ptr))
+
     def firth_2bit(self, packed: np.ndarray, lut, maxit: int = 50):
         """Firth bias-reduced effect size of every 2-bit row (one 4-entry dosage table each; ``sgx_firth_2bit``; binary
         traits) -> out4 [m, 4]: beta for the table's orientation, SE, iterations, converged (1 / 0).  NaN / NaN / 0 for a
         row without a non-zero dosage or with a non-finite table value."""
-        packed, lut = _row_tables("firth_2bit", packed, lut)
-        m = packed.shape[0]
-        out4 = np.zeros((max(1, m), 4))
-        check(self._L.sgx_firth_2bit(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data, int(maxit),
-                                     out4.ctypes.data))
-        return out4[:m]
+        return self._out4_2bit("firth_2bit", packed, lut, maxit)
 
     def firth_2bit_dev(self, packed_ptr: int, bpv: int, m: int, lut_ptr: int, out4_ptr: int, maxit: int = 50):
         """``firth_2bit`` on rows, tables and results in device memory (``sgx_firth_2bit_dev``; asynchronous, sync()
         before reading)."""
-        check(self._L.sgx_firth_2bit_dev(self._h, packed_ptr, bpv, m, lut_ptr, int(maxit), out4_ptr))
+        self._out4_2bit_dev("firth_2bit_dev", packed_ptr, bpv, m, lut_ptr, maxit, out4_ptr)
 
     def exact_2bit(self, packed: np.ndarray, lut, max_mac: int):
         """Exact p-values of the 2-bit rows with at most ``max_mac`` (1..63) minor alleles (one 4-entry dosage table
         each; ``sgx_exact_2bit``; binary traits) -> out4 [m, 4]: p.mid, p.full, MAC, done (1 / 0).  NaN /
         NaN / MAC / 0 for a row with no carrier or more than ``max_mac`` minor alleles, NaN / NaN / 0 / 0 for a table
         that is not {0, 1, 2, finite} or {2, 1, 0, finite}."""
-        packed, lut = _row_tables("exact_2bit", packed, lut)
-        m = packed.shape[0]
-        out4 = np.zeros((max(1, m), 4))
-        check(self._L.sgx_exact_2bit(self._h, packed.ctypes.data, packed.shape[1], m, lut.ctypes.data, int(max_mac),
-                                     out4.ctypes.data))
-        return out4[:m]
+        return self._out4_2bit("exact_2bit", packed, lut, max_mac)
 
     def exact_2bit_dev(self, packed_ptr: int, bpv: int, m: int, lut_ptr: int, out4_ptr: int, max_mac: int):
         """``exact_2bit`` on rows, tables and results in device memory (``sgx_exact_2bit_dev``; asynchronous, sync()
         before reading)."""
-        check(self._L.sgx_exact_2bit_dev(self._h, packed_ptr, bpv, m, lut_ptr, int(max_mac), out4_ptr))
+        self._out4_2bit_dev("exact_2bit_dev", packed_ptr, bpv, m, lut_ptr, max_mac, out4_ptr)
 
     def dosage_block(self, dtype, max_variants: int) -> "DosageBlock":
         """Device storage for a batch of dosage rows of the aggregate tests (``DosageBlock`` below)."""

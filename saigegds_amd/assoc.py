@@ -345,19 +345,17 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     _dsnode(src, dsnode)      # (a file without dosages is refused before its samples are looked at, R/assoc_single.r:133)
     inp = open_scan_input(src, mod, dsnode, verbose, any_matrix=True)
     kind, n_samp, n_var, ii = inp.kind, inp.n_samp, inp.n_var, inp.ii
-    firth_inp = None
+    passes = []               # the per-row follow-ups (firth.FollowUp), in the order of their columns
     if firth_pval is not None:
-        from . import firth
+        from . import _lib, firth
         if mod.trait_type != "binary":
             raise ValueError("Firth effect sizes are for binary traits.")
-        from . import _lib
-        firth_inp = firth.firth_input(inp, _lib.Scanner)      # (no dosage route: NotImplementedError, before any row is scanned)
-    exact_inp = None
+        passes.append(firth.follow_up(inp, _lib.Scanner, firth_pval, firth_maxit))      # (no dosage route: NotImplementedError)
     if exact_mac is not None:
         from . import exact
         if mod.trait_type != "binary":
             raise ValueError("Exact p-values are for binary traits.")
-        exact_inp = exact.exact_input(inp)                    # (true dosages: NotImplementedError, before any row is scanned)
+        passes.append(exact.follow_up(inp, int(exact_mac), mac))                         # (true dosages: NotImplementedError)
     if verbose:
         print(f"    # of samples: {_pretty(n_samp)}")
         print(f"    # of variants: {_pretty(n_var)}")
@@ -365,11 +363,8 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         print(f"    MAC threshold: {mac}")
         print(f"    missing threshold for variants: {missing}")
         print(f"    p-value threshold for SPA adjustment: {spa_pval}")
-        if firth_pval is not None:
-            print(f"    p-value threshold for Firth effect sizes: {firth_pval}")
-        if exact_mac is not None:
-            print(f"    MAC threshold for exact p-values: {exact_mac} (rows below the MAC threshold above, {mac}, are "
-                  "never valid: lower `mac` to reach them)")
+        for p in passes:
+            print(p.note)
     if not math.isfinite(var_ratio):
         var_ratio = float(np.nanmean(mod.var_ratio))
     if verbose:
@@ -402,39 +397,22 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
     elif kind == "packed" and not inp.in_mem and GENOTYPE_DECODE == "device":
         bl_size = packed_block_size(src.genotype_raw_row_bytes())      # a stored row is twice a 2-bit row
     t_loop = time.perf_counter()
-    fcols, firth_stored = None, False
-    if firth_pval is not None:
-        fcols = (np.full(n_var, np.nan), np.full(n_var, np.nan), np.zeros(n_var, dtype=bool))
-        if firth_inp.kind != "packed":
-            firth_stored = firth.dosage_route(firth_inp, lambda: Scanner(mobj, device=0))
+    cols = {name: np.full(n_var, fill, dtype=dt) for p in passes for name, fill, dt in p.columns}
+    for p in passes:
+        p.ready(lambda: Scanner(mobj, device=0))
 
-    def firth_rows(r0, r1, obj):
-        """The Firth pass of the scanned rows [r0, r1) against the model they were scanned with."""
-        with np.errstate(invalid="ignore"):
-            rows = r0 + np.flatnonzero((valid[r0:r1] != 0) & (out[r0:r1, 5] <= firth_pval))
-        got = firth.firth_pass(firth_inp, out, valid, rows, lambda: Scanner(obj, device=0), firth_maxit, firth_stored)
-        for col, g in zip(fcols, got):
-            col[rows] = g[rows]
-
-    ecols = None
-    if exact_mac is not None:
-        ecols = (np.full(n_var, np.nan), np.full(n_var, np.nan))
-
-    def exact_rows(r0, r1, obj):
-        """The exact pass of the scanned rows [r0, r1) against the model they were scanned with."""
-        with np.errstate(invalid="ignore"):
-            rows = r0 + np.flatnonzero((valid[r0:r1] != 0) & (out[r0:r1, 1] <= exact_mac))
-        got = exact.exact_pass(exact_inp, out, valid, rows, lambda: Scanner(obj, device=0), int(exact_mac))
-        for col, g in zip(ecols, got):
-            col[rows] = g[rows]
+    def follow_ups(r0, r1, obj):
+        """Every follow-up pass of the scanned rows [r0, r1) against the model they were scanned with."""
+        for p in passes:
+            with np.errstate(invalid="ignore"):
+                rows = r0 + np.flatnonzero(p.flagged(out[r0:r1], valid[r0:r1]))
+            for (name, _, _), g in zip(p.columns, p.run(out, valid, rows, lambda: Scanner(obj, device=0))):
+                cols[name][rows] = g[rows]
 
     if not mod.loco:
         blocks = [(off, min(n_var, off + bl_size)) for off in range(0, n_var, bl_size)]
         scan_blocks(lambda d: Scanner(mobj, device=d), ngpu, blocks, inp.read_block, kind == "packed", out, valid, timing)
-        if fcols is not None:
-            firth_rows(0, n_var, mobj)
-        if ecols is not None:
-            exact_rows(0, n_var, mobj)
+        follow_ups(0, n_var, mobj)
     else:
         # leave-one-chromosome-out: the block list is cut at chromosome boundaries, and every run of one
         # chromosome is scanned against that chromosome's model (its fitted values; y, V, XV, XXVX_inv and
@@ -452,10 +430,7 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
             blocks = [(off, min(r1, off + bl_size)) for off in range(r0, r1, bl_size)]
             scan_blocks(lambda d, o=run_obj: Scanner(o, device=d), ngpu, blocks, inp.read_block, kind == "packed", out, valid,
                         timing)
-            if fcols is not None:
-                firth_rows(r0, r1, run_obj)
-            if ecols is not None:
-                exact_rows(r0, r1, run_obj)
+            follow_ups(r0, r1, run_obj)
     if timing is not None:
         timing["blocks_s"] = time.perf_counter() - t_loop      # handles + every block (decode and scan overlapped)
 
@@ -464,10 +439,7 @@ def seqAssocGLMM_SPA(gdsfile: Union[str, GdsFile, GenotypeSource], modobj: Any, 
         print("# of variants after filtering by MAF, MAC and missing thresholds: "
               f"{_pretty(int(x.sum()))}")
     ans = assemble_result(src, x, out, mod.trait_type)
-    if fcols is not None:
-        ans["beta.firth"], ans["SE.firth"], ans["cvg.firth"] = (c[x] for c in fcols)
-    if ecols is not None:
-        ans["pval.exact"], ans["pval.exact.full"] = (c[x] for c in ecols)
+    ans.update((name, c[x]) for name, c in cols.items())
     return finish_result(ans, res_savefn, res_compress, verbose, inp.sample_id() if res_savefn else None)
 
 

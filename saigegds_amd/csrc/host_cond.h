@@ -143,32 +143,11 @@ extern "C" int sgx_cond_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, s
 	if (M == 0) return SGX_OK;
 	if (!packed || !lut || !score || !var || !cov) return fail(SGX_EINVAL, "sgx_cond_2bit: NULL buffer");
 	if (h->n_cond == 0) return fail(SGX_EINVAL, "sgx_cond_2bit: no conditioning set (sgx_cond_set)");
-	const int N = h->md.N, C = h->n_cond;
-	int rc = bpv_check(bpv, N);
+	int rc = bpv_check(bpv, h->md.N);
 	if (!rc) rc = begin_call(h);
 	if (rc) return rc;
-
-	// chunks of sgx_skat_2bit's uploads: rows at the device stride, then tables and results
-	const size_t dbpv = sgx_row_stride(N);
-	const size_t rchunk = scan_chunk(h, dbpv, M);
-	TabLayout tl;
-	tl.add<uint8_t>(rchunk * dbpv);
-	const auto s_lut = tl.add<double>(rchunk * 4);
-	const auto s_s = tl.add<double>(rchunk), s_v = tl.add<double>(rchunk), s_c = tl.add<double>(rchunk * (size_t)C);
-	rc = grow(h->stage_pk, tl.bytes());
-	if (rc) return rc;
-	double *d_lut = tl.at(h->stage_pk, s_lut), *d_s = tl.at(h->stage_pk, s_s), *d_v = tl.at(h->stage_pk, s_v),
-		*d_c = tl.at(h->stage_pk, s_c);
-	for (size_t off = 0; off < M; off += rchunk) {
-		const size_t m = std::min(rchunk, M - off);
-		rc = copy_rows_h2d(h->stage_pk, dbpv, packed + off * bpv, bpv, m, h->stream);
-		if (!rc) rc = tab_copy(h->stage_pk, s_lut, lut + 4 * off, 4 * m, h->stream);
-		if (!rc) rc = cond_rows_dev(h, h, h->stage_pk, dbpv, m, d_lut, d_s, d_v, d_c);
-		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(score + off, d_s, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipMemcpyAsync(var + off, d_v, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipMemcpyAsync(cov + off * C, d_c, m * (size_t)C * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipStreamSynchronize(h->stream));
-	}
-	return SGX_OK;
+	return rows_2bit_host(h, packed, bpv, M, lut, {{score, 1}, {var, 1}, {cov, (size_t)h->n_cond}},
+		[&](const uint8_t *rows, size_t dbpv, size_t m, const double *d_lut, double *const *d_out) {
+			return cond_rows_dev(h, h, rows, dbpv, m, d_lut, d_out[0], d_out[1], d_out[2]);
+		});
 }

@@ -4,9 +4,8 @@
 
 static int exact_check(const sgx_handle *h, const char *who, int max_mac)
 {
-	if (!h) return fail(SGX_EINVAL, "%s: NULL handle", who);
-	if (h->owner) return fail(SGX_EINVAL, "%s: not on a twin", who);
-	if (h->md.quant) return fail(SGX_EINVAL, "%s: the exact test is for binary traits", who);
+	int rc = binary_check(h, who, "the exact test");
+	if (rc) return rc;
 	if (max_mac < 1 || max_mac > SGX_EXACT_MAX_MAC)
 		return fail(SGX_EINVAL, "%s: max_mac=%d, need 1..%d", who, max_mac, SGX_EXACT_MAX_MAC);
 	return SGX_OK;
@@ -28,15 +27,8 @@ extern "C" int sgx_exact_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size
 	const double *lut_dev, int max_mac, double *out4_dev)
 {
 	int rc = exact_check(h, "sgx_exact_2bit_dev", max_mac);
-	if (rc) return rc;
-	if (M == 0) return SGX_OK;
-	if (!packed_dev || !lut_dev || !out4_dev) return fail(SGX_EINVAL, "sgx_exact_2bit_dev: NULL buffer");
-	rc = dev_rows_check("sgx_exact_2bit_dev", packed_dev, bpv, h->md.N);
-	if (rc) return rc;
-	if (((uintptr_t)lut_dev & 7u) != 0 || ((uintptr_t)out4_dev & 7u) != 0)
-		return fail(SGX_EINVAL, "sgx_exact_2bit_dev: lut_dev and out4_dev must be 8-byte aligned");
-	rc = set_dev(h);
-	if (rc) return rc;
+	if (!rc) rc = out4_dev_check(h, "sgx_exact_2bit_dev", packed_dev, bpv, M, lut_dev, out4_dev);
+	if (rc || M == 0) return rc;
 	return exact_rows_dev(h, packed_dev, bpv, M, lut_dev, max_mac, out4_dev);
 }
 
@@ -47,28 +39,11 @@ extern "C" int sgx_exact_2bit(sgx_handle *h, const uint8_t *packed, size_t bpv, 
 	if (rc) return rc;
 	if (M == 0) return SGX_OK;
 	if (!packed || !lut || !out4) return fail(SGX_EINVAL, "sgx_exact_2bit: NULL buffer");
-	const int N = h->md.N;
-	rc = bpv_check(bpv, N);
+	rc = bpv_check(bpv, h->md.N);
 	if (!rc) rc = sync_lane(h);             // (not begin_call: this entry leaves last_issued as it is)
 	if (rc) return rc;
-
-	// the chunks of sgx_firth_2bit: rows at the device stride, then tables and results
-	const size_t dbpv = sgx_row_stride(N);
-	const size_t rchunk = scan_chunk(h, dbpv, M);
-	TabLayout tl;
-	tl.add<uint8_t>(rchunk * dbpv);
-	const auto s_lut = tl.add<double>(rchunk * 4), s_out = tl.add<double>(rchunk * 4);
-	rc = grow(h->stage_pk, tl.bytes());
-	if (rc) return rc;
-	double *d_lut = tl.at(h->stage_pk, s_lut), *d_out = tl.at(h->stage_pk, s_out);
-	for (size_t off = 0; off < M; off += rchunk) {
-		const size_t m = std::min(rchunk, M - off);
-		rc = copy_rows_h2d(h->stage_pk, dbpv, packed + off * bpv, bpv, m, h->stream);
-		if (!rc) rc = tab_copy(h->stage_pk, s_lut, lut + 4 * off, 4 * m, h->stream);
-		if (!rc) rc = exact_rows_dev(h, h->stage_pk, dbpv, m, d_lut, max_mac, d_out);
-		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(out4 + 4 * off, d_out, m * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(hipStreamSynchronize(h->stream));
-	}
-	return SGX_OK;
+	return rows_2bit_host(h, packed, bpv, M, lut, {{out4, 4}},
+		[&](const uint8_t *rows, size_t dbpv, size_t m, const double *d_lut, double *const *d_out) {
+			return exact_rows_dev(h, rows, dbpv, m, d_lut, max_mac, d_out[0]);
+		});
 }

@@ -102,6 +102,7 @@ static int fail(int code, const char *fmt, ...)
 #include "host_blocks.h"
 #include "host_scan.h"
 #include "host_pipeline.h"
+#include "host_rows.h"
 #include "host_burden_ds.h"
 #include "host_skat.h"
 #include "host_skat_ds.h"

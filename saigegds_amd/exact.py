@@ -24,12 +24,12 @@ set-test and conditional drivers, more than one GPU.
 """
 from __future__ import annotations
 
-import dataclasses
+import contextlib
 from typing import Callable, Tuple
 
 import numpy as np
 
-from . import aggregate, firth
+from . import firth
 
 EXACT_MAX_MAC = 63              # SGX_EXACT_MAX_MAC: f[a] lives in lane a of one wave
 NO_DOSAGE = "Exact p-values on dosage input are not implemented: the test needs hard calls."
@@ -39,10 +39,7 @@ def exact_input(inp):
     """The opened input of a driver call as the exact pass takes it: 2-bit rows as they are, an in-memory uint8 / int32
     matrix that holds 0, 1, 2 and the missing code only as the rows it means (``aggregate.reduce_hard_calls``).  Any
     other input -- a dosage node, a file of dosages only, a matrix of other values -- is refused."""
-    if inp.kind == "dosage" and inp.in_mem:
-        ds = np.asarray(inp.ds_all)
-        if ds.ndim == 2 and ds.dtype in (np.uint8, np.int32):
-            inp = aggregate.reduce_hard_calls(dataclasses.replace(inp, ds_all=ds, ds_dtype=ds.dtype))
+    inp = firth.hard_call_input(inp)
     if inp.kind != "packed":
         raise NotImplementedError(NO_DOSAGE)
     return inp
@@ -56,21 +53,26 @@ def exact_pass(inp, out: np.ndarray, valid: np.ndarray, rows, make_scanner: Call
     ``rows``, on rows that are not valid and on rows the kernel does not finish (more than ``max_mac`` minor alleles)."""
     n_var = out.shape[0]
     mid, full = np.full(n_var, np.nan), np.full(n_var, np.nan)
-    rows = np.unique(np.asarray(rows, dtype=np.int64))
-    rows = rows[np.asarray(valid)[rows] != 0]
+    rows = firth.valid_rows(rows, valid)
     if rows.size == 0:
         return mid, full
     if inp.kind != "packed":
         raise NotImplementedError(NO_DOSAGE)
-    sc = make_scanner()
-    try:
-        per = max(1, firth.FIRTH_BATCH_BYTES // max(1, (inp.n_samp + 3) // 4))
-        for a in range(0, rows.size, per):
-            idx = rows[a:a + per]
-            lut, _ = firth.firth_tables(out[idx, 0])
-            o4 = np.asarray(sc.exact_2bit(inp.packed_rows_at(idx), lut, int(max_mac)))
+    with contextlib.closing(make_scanner()) as sc:
+        for idx, packed, lut, _ in firth.hard_call_batches(inp, out, rows):
+            o4 = np.asarray(sc.exact_2bit(packed, lut, int(max_mac)))
             done = o4[:, 3] == 1
             mid[idx[done]], full[idx[done]] = o4[done, 0], o4[done, 1]
-    finally:
-        sc.close()
     return mid, full
+
+
+def follow_up(inp, max_mac: int, mac) -> firth.FollowUp:
+    """``seqAssocGLMM_SPA(exact_mac=)`` of a scan with the filter ``mac``: the exact pass of every valid row with
+    ``mac <= exact_mac``.  True dosages are refused here."""
+    inp = exact_input(inp)
+    return firth.FollowUp(
+        f"    MAC threshold for exact p-values: {max_mac} (rows below the MAC threshold above, {mac}, are "
+        "never valid: lower `mac` to reach them)",
+        (("pval.exact", np.nan, np.float64), ("pval.exact.full", np.nan, np.float64)),
+        lambda out, valid: (valid != 0) & (out[:, 1] <= max_mac),
+        lambda out, valid, rows, make_scanner: exact_pass(inp, out, valid, rows, make_scanner, int(max_mac)))

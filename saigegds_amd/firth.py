@@ -25,8 +25,9 @@ Out of scope: the set-test and conditional drivers, more than one GPU.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
-from typing import Callable, Tuple
+from typing import Callable, NamedTuple, Tuple
 
 import numpy as np
 
@@ -45,16 +46,46 @@ def firth_tables(af: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     return aggregate.dosage_tables(flip.astype(np.uint8), mean), flip
 
 
+class FollowUp(NamedTuple):
+    """One per-row follow-up of ``seqAssocGLMM_SPA``, as the driver runs it after each ``scan_blocks`` call."""
+    note: str                   # the verbose line of the option
+    columns: tuple              # ((name, fill value, dtype), ...) of the result
+    flagged: Callable           # (out, valid) of scanned rows -> their mask
+    run: Callable               # (out, valid, rows, make_scanner) -> the column arrays [n_var], read at rows
+    ready: Callable = lambda make_scanner: None      # what is refused before any row is scanned
+
+
+def hard_call_input(inp):
+    """An in-memory uint8 / int32 matrix of hard calls as 2-bit rows (``aggregate.reduce_hard_calls``), else ``inp``."""
+    if inp.kind == "dosage" and inp.in_mem:
+        ds = np.asarray(inp.ds_all)
+        if ds.ndim == 2 and ds.dtype in (np.uint8, np.int32):
+            inp = aggregate.reduce_hard_calls(dataclasses.replace(inp, ds_all=ds, ds_dtype=ds.dtype))
+    return inp
+
+
+def valid_rows(rows, valid) -> np.ndarray:
+    """Row indices as a pass takes them: unique and ascending, the valid ones."""
+    rows = np.unique(np.asarray(rows, dtype=np.int64))
+    return rows[np.asarray(valid)[rows] != 0]
+
+
+def hard_call_batches(inp, out: np.ndarray, rows: np.ndarray):
+    """Batches of ``FIRTH_BATCH_BYTES`` of the 2-bit rows ``rows`` -> (idx, packed rows, tables from ``AF.alt``, flip)."""
+    per = max(1, FIRTH_BATCH_BYTES // max(1, (inp.n_samp + 3) // 4))
+    for a in range(0, rows.size, per):
+        idx = rows[a:a + per]
+        lut, flip = firth_tables(out[idx, 0])
+        yield idx, inp.packed_rows_at(idx), lut, flip
+
+
 def firth_input(inp, scanner_cls):
     """The opened input of a driver call as the Firth pass takes it: hard calls as 2-bit rows -- as they are, or an
     in-memory uint8 / int32 matrix that holds 0, 1, 2 and the missing code only as the rows it means
     (``aggregate.reduce_hard_calls``); any other input -- a dosage node, a file of dosages only, a matrix of other
     values -- as dosage rows of the type the scan gives them (uint8, int32 for other integers, else float64), refused
     where ``scanner_cls`` has no ``dosage_block``."""
-    if inp.kind == "dosage" and inp.in_mem:
-        ds = np.asarray(inp.ds_all)
-        if ds.ndim == 2 and ds.dtype in (np.uint8, np.int32):
-            inp = aggregate.reduce_hard_calls(dataclasses.replace(inp, ds_all=ds, ds_dtype=ds.dtype))
+    inp = hard_call_input(inp)
     if inp.kind == "packed":
         return inp
     if not hasattr(scanner_cls, "dosage_block"):
@@ -69,14 +100,10 @@ def firth_input(inp, scanner_cls):
 def dosage_route(inp, make_scanner) -> bool:
     """Dosage input, before any row is scanned: the scanner's dosage block must have ``firth`` (else
     ``NotImplementedError``) -> whether a stored node goes to it in its file form (the block has ``load_packed``)."""
-    sc = make_scanner()
-    try:
-        with sc.dosage_block(inp.ds_dtype, 1) as blk:
-            if not hasattr(blk, "firth"):
-                raise NotImplementedError(NO_DOSAGE)
-            return inp.kind == "stored" and hasattr(blk, "load_packed")
-    finally:
-        sc.close()
+    with contextlib.closing(make_scanner()) as sc, sc.dosage_block(inp.ds_dtype, 1) as blk:
+        if not hasattr(blk, "firth"):
+            raise NotImplementedError(NO_DOSAGE)
+        return inp.kind == "stored" and hasattr(blk, "load_packed")
 
 
 def firth_pass(inp, out: np.ndarray, valid: np.ndarray, rows, make_scanner: Callable, maxit: int = 50, stored: bool = False):
@@ -89,8 +116,7 @@ def firth_pass(inp, out: np.ndarray, valid: np.ndarray, rows, make_scanner: Call
     n_var = out.shape[0]
     beta, se = np.full(n_var, np.nan), np.full(n_var, np.nan)
     cvg = np.zeros(n_var, dtype=bool)
-    rows = np.unique(np.asarray(rows, dtype=np.int64))
-    rows = rows[np.asarray(valid)[rows] != 0]
+    rows = valid_rows(rows, valid)
     if rows.size == 0:
         return beta, se, cvg
 
@@ -99,14 +125,10 @@ def firth_pass(inp, out: np.ndarray, valid: np.ndarray, rows, make_scanner: Call
         se[idx] = o4[:, 1]
         cvg[idx] = o4[:, 3] == 1
 
-    sc = make_scanner()
-    try:
+    with contextlib.closing(make_scanner()) as sc:
         if inp.kind == "packed":
-            per = max(1, FIRTH_BATCH_BYTES // max(1, (inp.n_samp + 3) // 4))
-            for a in range(0, rows.size, per):
-                idx = rows[a:a + per]
-                lut, flip = firth_tables(out[idx, 0])
-                put(idx, flip, np.asarray(sc.firth_2bit(inp.packed_rows_at(idx), lut, int(maxit))))
+            for idx, packed, lut, flip in hard_call_batches(inp, out, rows):
+                put(idx, flip, np.asarray(sc.firth_2bit(packed, lut, int(maxit))))
         else:
             make = getattr(sc, "dosage_block", None)
             if make is None:
@@ -122,6 +144,16 @@ def firth_pass(inp, out: np.ndarray, valid: np.ndarray, rows, make_scanner: Call
                     flip, mean = aggregate.flip_mean(n, s)
                     o4 = np.asarray(blk.firth(np.arange(idx.size, dtype=np.int32), flip, mean, int(maxit)))
                     put(idx, flip != 0, o4)
-    finally:
-        sc.close()
     return beta, se, cvg
+
+
+def follow_up(inp, scanner_cls, pval: float, maxit: int) -> FollowUp:
+    """``seqAssocGLMM_SPA(firth_pval=, firth_maxit=)``: the Firth pass of every valid row with ``pval <= firth_pval``.
+    Input that ``scanner_cls`` cannot serve is refused here, a dosage block without ``firth`` by ``ready``."""
+    inp, stored = firth_input(inp, scanner_cls), []           # stored: what ready appends, dosage_route's answer
+    return FollowUp(
+        f"    p-value threshold for Firth effect sizes: {pval}",
+        (("beta.firth", np.nan, np.float64), ("SE.firth", np.nan, np.float64), ("cvg.firth", False, bool)),
+        lambda out, valid: (valid != 0) & (out[:, 5] <= pval),
+        lambda out, valid, rows, make_scanner: firth_pass(inp, out, valid, rows, make_scanner, maxit, stored[0]),
+        lambda make_scanner: stored.append(inp.kind != "packed" and dosage_route(inp, make_scanner)))
