@@ -383,6 +383,34 @@ int sgx_exact_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_varian
 int sgx_exact_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_per_variant, size_t n_variants,
 	const double *lut_dev, int max_mac, double *out4_dev);
 
+/* Pseudo-variants of groups of 2-bit rows: what SKAT and SKAT-O put in the place of a unit's ultra-rare variants
+ * (saigegds_amd/aggregate.py, collapse_mac=; nothing of this is in the reference).  Group g has the entries
+ * e in [grp_ptr[g], grp_ptr[g+1]) = rows var_idx[e] of `packed`, each with a byte flip[e].  An entry's minor-allele dosage
+ * of sample i is its code, 2 - code where flip[e] != 0, and 0 where the code is 3 (missing).  Per group:
+ *   out_rows[g]     a 2-bit row of bytes_per_variant bytes: code of sample i = the largest dosage over the group's entries
+ *                   (codes 0, 1, 2 only); the fields at and beyond n_samp and the bytes beyond ceil(n_samp / 4) are 0,
+ *                   whatever the input rows hold there and whatever the flips
+ *   counts[2g]      samples with code 1        counts[2g + 1]   samples with code 2
+ * so that out_rows is a source of sgx_scan_2bit, sgx_skat_2bit and the other entries like any row.  A group of 0 entries
+ * gives an all-zero row and zero counts; a row may be in any number of groups.
+ *   sgx_collapse_2bit      rows, groups and results in HOST memory; the rows cross PCIe once in the chunks of the
+ *                          host-buffer scans.  Synchronous; a thin wrapper around the next entry: same kernel, same bits.
+ *   sgx_collapse_2bit_dev  everything in DEVICE memory: rows and out_rows at stride and alignment of sgx_scan_2bit_dev
+ *                          (out_rows at the rows' stride; the two must not overlap), grp_ptr_dev 8-byte aligned,
+ *                          var_idx_dev and counts_dev 4-byte.  grp_ptr_dev and var_idx_dev are copied back and checked
+ *                          first, which waits for what the handle's stream already holds; the kernel is then queued on
+ *                          that stream and the results are readable after sgx_sync().
+ * Integer work only (bit operations on whole words, popcounts, integer atomics for the counts): a group's row and counts
+ * depend on its entries' rows and flips alone -- not on the other groups, their order, the grid or the chunks.
+ * n_groups = 0 succeeds and does nothing.  A NULL buffer, grp_ptr[0] != 0 or grp_ptr not ascending, a variant index
+ * outside [0, n_variants), bytes_per_variant < ceil(n_samp / 4), or a bad device stride or alignment returns SGX_EINVAL
+ * and launches nothing; the handle stays usable. */
+int sgx_collapse_2bit(sgx_handle *h, const uint8_t *packed, size_t bytes_per_variant, size_t n_variants, size_t n_groups,
+	const int64_t *grp_ptr, const int32_t *var_idx, const uint8_t *flip, uint8_t *out_rows, int32_t *counts);
+int sgx_collapse_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes_per_variant, size_t n_variants,
+	size_t n_groups, const int64_t *grp_ptr_dev, const int32_t *var_idx_dev, const uint8_t *flip_dev,
+	uint8_t *out_rows_dev, int32_t *counts_dev);
+
 /* Aggregate tests on dosage input: the INTSXP / REALSXP branches of ds_mat_mafmac and ds_mat_burden
  * (src/saige_main.cpp:485-610), which the R drivers reach with .dsnode(gdsfile, dsnode) for imputed
  * data (R/assoc_aggregate.r:89,351,606).  A batch of dosage rows (u8: 0xFF = missing; i32: INT_MIN =

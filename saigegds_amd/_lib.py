@@ -209,6 +209,8 @@ def _abi():
         "sgx_ds_block_cond_kmat_set": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp, ci, dp, vp, vp, vp]),
         "sgx_ds_block_cond_kmat": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sgx_skato_spectra": (ci, [vp, sz, vp, vp, sz, vp, vp, vp]),
+        "sgx_collapse_2bit": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
+        "sgx_collapse_2bit_dev": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
     }
 
 
@@ -598,6 +600,28 @@ class Scanner(_Handle):
         """``exact_2bit`` on rows, tables and results in device memory (``sgx_exact_2bit_dev``; asynchronous, sync()
         before reading)."""
         self._out4_2bit_dev("exact_2bit_dev", packed_ptr, bpv, m, lut_ptr, max_mac, out4_ptr)
+
+    def collapse_2bit(self, packed: np.ndarray, grp_ptr, var_idx, flip):
+        """The pseudo-variant of every group of 2-bit rows (CSR ``grp_ptr`` / ``var_idx`` over the rows of ``packed``, one
+        flip byte per entry; ``sgx_collapse_2bit``): per sample the largest minor-allele dosage over the
+        group's rows (the code, 2 - code where flipped, 0 where missing) -> (rows [n_groups, bpv] uint8 with codes 0, 1,
+        2 and zero padding, counts [n_groups, 2] int32: samples with code 1 and with code 2)."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint8)
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        grp_ptr, var_idx, n_groups, _, _ = _unit_args("collapse_2bit", grp_ptr, var_idx, [(flip, ())], packed.ndim == 2)
+        rows, counts = np.zeros((n_groups, packed.shape[1]), dtype=np.uint8), np.zeros((n_groups, 2), dtype=np.int32)
+        if var_idx.size:                              # (groups without an entry: the zeros above)
+            check(self._L.sgx_collapse_2bit(self._h, packed.ctypes.data, packed.shape[1], packed.shape[0], n_groups,
+                                            grp_ptr.ctypes.data, var_idx.ctypes.data, flip.ctypes.data, rows.ctypes.data,
+                                            counts.ctypes.data))
+        return rows, counts
+
+    def collapse_2bit_dev(self, packed_ptr: int, bpv: int, m: int, n_groups: int, grp_ptr_ptr: int, var_idx_ptr: int,
+                          flip_ptr: int, out_rows_ptr: int, counts_ptr: int):
+        """``collapse_2bit`` on rows, groups and results in device memory (``sgx_collapse_2bit_dev``: the groups are
+        checked on the host first, the kernel is asynchronous; sync() before reading)."""
+        check(self._L.sgx_collapse_2bit_dev(self._h, packed_ptr, bpv, m, n_groups, grp_ptr_ptr, var_idx_ptr, flip_ptr,
+                                            out_rows_ptr, counts_ptr))
 
     def dosage_block(self, dtype, max_variants: int) -> "DosageBlock":
         """Device storage for a batch of dosage rows of the aggregate tests (``DosageBlock`` below)."""

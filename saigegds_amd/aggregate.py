@@ -170,6 +170,9 @@ class _Prepared:
     valid: np.ndarray = None                # its valid flags
     burden: Dict[str, Any] = None           # column kind -> (burden rows [n_units, n_weights, 8], valid)
     skat: List[SkatStep] = None             # the SKAT driver: the device step of every batch of units
+    collapse_mac: float = float("nan")      # SKAT / SKAT-O: variants up to this mac become one pseudo-variant a unit (NaN: off)
+    n_collapsed: np.ndarray = None          # per unit: the variants its pseudo-variant replaces, and
+    pseudo: np.ndarray = None               # its row of the per-variant arrays (appended to them; -1: none)
 
 
 DS_BUDGET = 1 << 30      # bytes of dosage rows resident on the device per batch of units
@@ -231,7 +234,9 @@ def variant_stats(n, s, out, valid):
 #   truncated `int sum` of ds_mat_burden, and the scan table of the rows;
 # burden(grp_ptr, var_idx, flip, mean, W): groups (CSR over rows of bv) x the columns of W ([entries, n_cols], NaN =
 #   entry not in that column) -> (burden rows [groups * n_cols, 8] or [groups, n_cols, 8], valid);
-# skat(unit_ptr, var_idx, flip, mean) -> (score [entries], cov per unit, PCG steps per entry or None).
+# skat(unit_ptr, var_idx, flip, mean) -> (score [entries], cov per unit, PCG steps per entry or None);
+# collapse(grp_ptr, var_idx, flip): groups (CSR over the resident rows) -> what load returns, for one pseudo-variant per
+#   group; their rows are resident after the batch's own from then on.  None: the backend has none.
 
 @contextlib.contextmanager
 def _packed_rows(pr: _Prepared, used, kmat=None):
@@ -240,15 +245,24 @@ def _packed_rows(pr: _Prepared, used, kmat=None):
     sc, nw = pr.sc, pr.wbeta.shape[1]
     packed = pr.inp.packed_rows_at(used - 1)
 
-    def load(bv):
-        out, valid = sc.scan_2bit(packed)
+    def scan(rows):
+        out, valid = sc.scan_2bit(rows)
         ok = valid != 0
         n = np.where(ok, out[:, 2], 0).astype(np.float64)
         s = np.where(ok, np.rint(out[:, 0] * 2 * n), 0.0)           # RAW branch: s = sum of codes
         if not ok.all():    # a variant rejected by the scan's filter (monomorphic: maf = 0) still has counts: from the host
-            codes = unpack_dosage_2bit(packed[~ok], pr.inp.n_samp).astype(np.int64)
+            codes = unpack_dosage_2bit(rows[~ok], pr.inp.n_samp).astype(np.int64)
             n[~ok], s[~ok] = (codes != 3).sum(axis=1), np.where(codes != 3, codes, 0).sum(axis=1)
         return n, s, s.astype(np.int64), out, valid                 # integer codes: nothing to truncate
+
+    def load(bv):
+        return scan(packed)
+
+    def collapse(grp_ptr, var_idx, flip):
+        nonlocal packed
+        rows, _ = sc.collapse_2bit(packed, grp_ptr, var_idx, flip)
+        packed = np.concatenate([packed, rows])                     # burden and skat below read the longer matrix
+        return scan(rows)
 
     def burden(grp_ptr, var_idx, flip, mean, W):
         ng = len(grp_ptr) - 1
@@ -273,7 +287,8 @@ def _packed_rows(pr: _Prepared, used, kmat=None):
         with ExplicitGrmOperator(mat) as op:
             return sc.skat_kmat(op, packed, unit_ptr, var_idx, lut, w, pr.sm.tau, maxiter=maxiter, tol=tol)
 
-    yield SimpleNamespace(batches=[list(range(len(pr.index)))], load=load, burden=burden, skat=skat)
+    yield SimpleNamespace(batches=[list(range(len(pr.index)))], load=load, burden=burden, skat=skat,
+                          collapse=collapse if hasattr(sc, "collapse_2bit") else None)
 
 
 _NO_DOSAGE_KMAT = "SKAT with 'grm_mat' on dosage input is not implemented."
@@ -325,7 +340,7 @@ def _dosage_rows(pr: _Prepared, used, stored, budget, kmat=None):
 
             def skat(*a):
                 return blk.skat_kmat(op, *a, w, pr.sm.tau, maxiter=maxiter, tol=tol)
-        yield SimpleNamespace(batches=batches, load=load, burden=burden, skat=skat)
+        yield SimpleNamespace(batches=batches, load=load, burden=burden, skat=skat, collapse=None)
 
 
 SkatStep = collections.namedtuple("SkatStep", "kept unit_ptr var_idx flip mean score cov n_iter")
@@ -344,6 +359,40 @@ def skat_step(pr: _Prepared, skat, rows, bv) -> SkatStep:
     var_idx = np.searchsorted(bv, rows_k).astype(np.int32)
     flip, mean = flip_mean(pr.n[rows_k], pr.s[rows_k])
     return SkatStep(kept, unit_ptr, var_idx, flip, mean, *skat(unit_ptr, var_idx, flip, mean))
+
+
+def check_collapse_mac(collapse_mac) -> float:
+    """``collapse_mac`` of the SKAT drivers: NaN (off) or a number of at least 1."""
+    if not _is_num(collapse_mac):
+        raise TypeError("is.numeric(collapse.mac) is not TRUE")
+    collapse_mac = float(collapse_mac)
+    if not (math.isnan(collapse_mac) or collapse_mac >= 1):
+        raise ValueError("'collapse_mac' should be NaN (no collapsing) or at least 1.")
+    return collapse_mac
+
+
+def collapse_step(pr: _Prepared, collapse, bt, rows, bv):
+    """The ultra-rare variants of the units ``bt`` become one pseudo-variant a unit, before ``skat_step``:
+    of a unit's variants in the test (valid, mac > 0) those with mac <= pr.collapse_mac are its set U; where U is not
+    empty the backend's ``collapse`` makes the row of per-sample maxima of U's minor-allele dosages -- the flip is the
+    scan's own, ``flip_mean`` -- and scans it.  The pseudo-variants get rows of the per-variant arrays after all others
+    (pr.pseudo[u]; pr.n_collapsed[u] = |U|) and take U's place at the end of the unit -> (rows, bv) for ``skat_step``."""
+    rare = (pr.valid != 0) & (pr.mac > 0) & (pr.mac <= pr.collapse_mac)
+    U = [r[rare[r]] for r in rows]
+    sizes = np.array([u.size for u in U])
+    pr.n_collapsed[bt] = sizes
+    if not sizes.any():
+        return rows, bv
+    ent = np.concatenate(U)
+    grp_ptr = np.concatenate([[0], np.cumsum(sizes[sizes > 0])]).astype(np.int64)
+    n, s, _, out, valid = collapse(grp_ptr, np.searchsorted(bv, ent).astype(np.int32), flip_mean(pr.n[ent], pr.s[ent])[0])
+    new = pr.n.size + np.arange(n.size)
+    maf, mac, pval = variant_stats(n.astype(np.float64), s, out, valid)
+    for nm, x in (("n", n), ("s", s), ("out", out), ("valid", valid), ("maf", maf), ("mac", mac), ("pval", pval)):
+        setattr(pr, nm, np.concatenate([getattr(pr, nm), x]))
+    pr.pseudo[np.asarray(bt)[sizes > 0]] = new
+    own = iter(new)
+    return [np.append(r[~rare[r]], next(own)) if k else r for r, k in zip(rows, sizes)], np.concatenate([bv, new])
 
 
 def _burden_entries(pr: _Prepared, rows, bv, n, st, kinds, burden_mac):
@@ -381,16 +430,22 @@ def _burden_entries(pr: _Prepared, rows, bv, n, st, kinds, burden_mac):
 
 def _run(pr: _Prepared, kinds=(), burden_mac=float("nan"), skat=False):
     """The device side of a driver call, per batch of units of the rows backend: load the batch's distinct variants,
-    fill the per-variant arrays, then SKAT's step (``skat``: pr.skat gets one ``SkatStep`` per batch) and one burden call
+    fill the per-variant arrays, then SKAT's step (``skat``: pr.skat gets one ``SkatStep`` per batch; with pr.collapse_mac
+    after ``collapse_step``, which appends the pseudo-variants to the per-variant arrays) and one burden call
     with every column of the driver (``kinds``: pr.burden[kind] = (rows [n_units, n_weights, 8], valid))."""
     nu, nw, nv = len(pr.index), pr.wbeta.shape[1], np.unique(np.concatenate(pr.index)).size
     pr.n, pr.s, pr.out, pr.valid = np.zeros(nv), np.zeros(nv), np.full((nv, 8), np.nan), np.zeros(nv, dtype=np.uint8)
     pr.maf, pr.mac, pr.pval = np.full(nv, np.nan), np.full(nv, np.nan), np.full(nv, np.nan)
     rows_out, rows_valid = np.full((nu, len(kinds) * nw, 8), np.nan), np.zeros((nu, len(kinds) * nw), dtype=np.uint8)
     pr.skat = [] if skat else None
+    collapsing = skat and not math.isnan(pr.collapse_mac)
+    if collapsing:
+        pr.n_collapsed, pr.pseudo = np.zeros(nu, dtype=np.int64), np.full(nu, -1, dtype=np.int64)
     with pr.backend as be:
         if skat and be.skat is None:
             raise NotImplementedError("SKAT on dosage input is not implemented.")
+        if collapsing and be.collapse is None:
+            raise NotImplementedError("'collapse_mac' needs a scanner with collapse_2bit.")
         for bt in be.batches:
             rows = [pr.index[u] for u in bt]
             bv = np.unique(np.concatenate(rows))                    # rows of the per-variant arrays
@@ -399,7 +454,7 @@ def _run(pr: _Prepared, kinds=(), burden_mac=float("nan"), skat=False):
             pr.n[bv], pr.s[bv], pr.out[bv], pr.valid[bv] = n, s, out, valid
             pr.maf[bv], pr.mac[bv], pr.pval[bv] = variant_stats(n, s, out, valid)
             if skat:
-                pr.skat.append(skat_step(pr, be.skat, rows, bv))
+                pr.skat.append(skat_step(pr, be.skat, *(collapse_step(pr, be.collapse, bt, rows, bv) if collapsing else (rows, bv))))
             if kinds:
                 ob, vb = be.burden(*_burden_entries(pr, rows, bv, n, st, kinds, burden_mac))
                 rows_out[bt], rows_valid[bt] = ob.reshape(len(bt), -1, 8), vb.reshape(len(bt), -1)
@@ -407,19 +462,22 @@ def _run(pr: _Prepared, kinds=(), burden_mac=float("nan"), skat=False):
 
 
 def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, scanner_factory=None, dsnode="",
-             ds_budget=None, kmat=None) -> _Prepared:
+             ds_budget=None, kmat=None, collapse_mac=float("nan")) -> _Prepared:
     """Common head of the set-test drivers (R/assoc_aggregate.r:55-150): checks, sample matching, the model, the scanner
     and the rows backend of the input (and what the reference prints about the units).  Nothing has gone to the device
-    yet: ``_run`` does that."""
+    yet: ``_run`` does that.  ``collapse_mac`` (SKAT and SKAT-O; what ``check_collapse_mac`` returned)
+    other than NaN needs hard calls: dosage input is refused here, before the scanner is made."""
     if verbose:
         print(what)
-    pr = _Prepared(_Units(units), _check_beta(wbeta))
+    pr = _Prepared(_Units(units), _check_beta(wbeta), collapse_mac=collapse_mac)
     for nm, v in (("spa.pval", spa_pval), ("var.ratio", var_ratio)):
         if not _is_num(v):
             raise TypeError(f"is.numeric({nm}) is not TRUE")
     mod: NullModel = load_modobj(modobj, verbose)
     no_loco(mod, what.rstrip(":"))
     pr.inp = inp = reduce_hard_calls(open_scan_input(gdsfile, mod, dsnode, verbose))
+    if inp.kind != "packed" and not math.isnan(pr.collapse_mac):
+        raise NotImplementedError("'collapse_mac' on dosage input is not implemented.")
     used = np.unique(np.concatenate(pr.units.index))
     if used.size == 0 or used.min() < 1 or used.max() > inp.n_var:
         raise ValueError("No variant in the genotypic data set!")
@@ -459,6 +517,14 @@ def _summary_cols(pr: _Prepared) -> Dict[str, Any]:
     for k, nm in enumerate(("maf.avg", "maf.sd", "maf.min", "maf.max", "mac.avg", "mac.sd", "mac.min", "mac.max")):
         ans[nm] = st[:, k]
     return ans
+
+
+def _collapse_cols(pr: _Prepared, ans: Dict[str, Any]):
+    """The two columns of a call with ``collapse_mac``: ``n.collapsed``, the variants a unit's pseudo-variant replaces,
+    and ``mac.collapsed``, the pseudo-variant's minor allele count (NaN: the unit has none)."""
+    if pr.n_collapsed is not None:
+        ans["n.collapsed"] = pr.n_collapsed
+        ans["mac.collapsed"] = np.where(pr.pseudo >= 0, pr.mac[pr.pseudo], np.nan)
 
 
 def _row_result(o, ok, n_snp, summac_thr):

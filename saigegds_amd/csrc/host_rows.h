@@ -36,6 +36,18 @@ static int rows_2bit_host(sgx_handle *h, const uint8_t *packed, size_t bpv, size
 	return SGX_OK;
 }
 
+// All n 2-bit rows of a grouped call (sgx_skat_2bit, sgx_skat_kmat_2bit, sgx_collapse_2bit: an entry may name any row)
+// from host memory to dst at the device stride, queued on st in the chunks of the host-buffer scans.
+static int rows_2bit_upload(const sgx_handle *h, uint8_t *dst, size_t dbpv, const uint8_t *packed, size_t bpv, size_t n, hipStream_t st)
+{
+	const size_t rchunk = scan_chunk(h, dbpv, n);
+	for (size_t off = 0; off < n; off += rchunk) {
+		const int rc = copy_rows_h2d(dst + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n - off), st);
+		if (rc) return rc;
+	}
+	return SGX_OK;
+}
+
 // the head of the checks of the entries for binary traits; what: "the Firth fit", "the exact test"
 static int binary_check(const sgx_handle *h, const char *who, const char *what)
 {

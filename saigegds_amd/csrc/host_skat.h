@@ -181,11 +181,8 @@ static int skat_2bit_host(sgx_handle *h, const uint8_t *packed, size_t bpv, size
 	const auto s_til = tl.add(pl.tiles.size(), pl.tiles.data());
 	rc = grow(h->stage_pk, tl.bytes());
 	if (rc) return rc;
-	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
-	for (size_t off = 0; off < n_variants; off += rchunk) {
-		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), h->stream);
-		if (rc) return rc;
-	}
+	rc = rows_2bit_upload(h, h->stage_pk, dbpv, packed, bpv, n_variants, h->stream);
+	if (rc) return rc;
 	rc = tabs_upload(h->stage_pk, h->stream, s_idx, s_lut, s_til);
 	if (rc) return rc;
 

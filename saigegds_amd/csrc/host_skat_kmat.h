@@ -363,11 +363,8 @@ extern "C" int sgx_skat_kmat_2bit(sgx_handle *h, sgx_kmat *km, const uint8_t *pa
 	rc = dev_room(h->stage_pk, tl.bytes(), "the rows", who);
 	if (!rc) rc = skk_unit_room(who, h, (size_t)m_max);
 	if (rc) return rc;
-	const size_t rchunk = scan_chunk(h, dbpv, n_variants);
-	for (size_t off = 0; off < n_variants; off += rchunk) {
-		rc = copy_rows_h2d(h->stage_pk + off * dbpv, dbpv, packed + off * bpv, bpv, std::min(rchunk, n_variants - off), st);
-		if (rc) return rc;
-	}
+	rc = rows_2bit_upload(h, h->stage_pk, dbpv, packed, bpv, n_variants, st);
+	if (rc) return rc;
 	rc = tabs_upload(h->stage_pk, st, s_idx, s_lut);
 	if (rc) return rc;
 	SkkSrc src;

@@ -90,6 +90,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_firth_ds.h"
 #include "kern_exact.h"
 #include "kern_eig.h"
+#include "kern_collapse.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -119,3 +120,4 @@ static int fail(int code, const char *fmt, ...)
 #include "host_firth.h"
 #include "host_exact.h"
 #include "host_skato.h"
+#include "host_collapse.h"

@@ -18,7 +18,9 @@ Hard calls are one batch: one ``sgx_scan_2bit`` and one ``sgx_skat_2bit`` for al
 ``annotation/format/DS``, or a ``GenotypeSource(dosage=...)`` that does not reduce to hard calls) is cut into batches
 that fit the device: the rows of a batch go to a resident ``DosageBlock`` once, ``blk.scan()`` gives the per-variant
 table and ``blk.skat()`` (``sgx_ds_block_skat``) ``S`` and ``Phi`` of the batch's units -- with ``grm_mat=``
-``blk.skat_kmat()`` (``sgx_ds_block_skat_kmat``) on one operator for all batches.
+``blk.skat_kmat()`` (``sgx_ds_block_skat_kmat``) on one operator for all batches.  With ``collapse_mac=``
+(hard calls only) ``aggregate.collapse_step`` runs between steps 1 and 2: one ``sgx_collapse_2bit`` makes a
+pseudo-variant of every unit's ultra-rare variants, one more ``sgx_scan_2bit`` scans them.
 """
 from __future__ import annotations
 
@@ -27,7 +29,7 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .aggregate import AggrParamBeta, _dbeta, _prepare, _run, _save, _summary_cols
+from .aggregate import AggrParamBeta, _collapse_cols, _dbeta, _prepare, _run, _save, _summary_cols, check_collapse_mac
 from .assoc import GenotypeSource
 
 LAMBDA_DROP = 1e-10      # eigenvalues at or below this fraction of the largest one are dropped
@@ -191,7 +193,7 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
                          var_ratio: float = float("nan"), res_savefn: str = "", res_compress: str = "LZMA",
                          parallel=False, verbose: bool = True, verbose_maf: bool = True,
                          scanner_factory=None, ds_budget: Optional[int] = None, grm_mat=None, tol_pcg: float = 1e-5,
-                         maxiter_pcg: int = 500) -> Dict[str, Any]:
+                         maxiter_pcg: int = 500, collapse_mac: float = float("nan")) -> Dict[str, Any]:
     """SKAT per unit and weight set (not in the reference; arguments as ``seqAssocGLMM_spaBurden``), on hard calls or
     on dosages (``dsnode``, or a file without ``genotype/data``, or an in-memory dosage matrix that is float64 or holds
     more than hard calls; ``ds_budget``: bytes of resident dosage rows per batch of units).
@@ -219,7 +221,18 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
     PCG step count of the unit.  Dosage input takes ``sgx_ds_block_skat_kmat`` per batch with the scan's
     own mean and flip.  Refused before any row is read: dosage input on a scanner without ``dosage_block`` or whose block
     has no ``skat_kmat`` (``NotImplementedError``; the scanner is closed), a LOCO model, ``parallel`` other than one GPU
-    (``ValueError``)."""
+    (``ValueError``).
+
+    ``collapse_mac`` (NaN: off, the default; else a number of at least 1, ``ValueError`` below that and ``TypeError`` for
+    what is no number; hard calls only: dosage input is refused with ``NotImplementedError`` before any row is read, and
+    so is a scanner without ``collapse_2bit``, which is closed): the step of SAIGE-GENE+, DESIGN.md 8m.  Of a unit's
+    variants in the test those with ``mac <= collapse_mac`` are replaced by one pseudo-variant, placed last: per sample
+    the largest minor-allele dosage over them (the code, 2 - code where the scan flips the row, 0 where missing), made
+    for all units by one ``sgx_collapse_2bit`` and then scanned, weighted by its own maf and entered into ``S``, ``Phi``
+    (or ``Phi^K``) and the SPA scaling like any variant.  ``n.var`` counts the entries after collapsing; two more
+    columns appear: ``n.collapsed`` (the variants replaced) and ``mac.collapsed`` (the pseudo-variant's minor allele
+    count, NaN where nothing was replaced).  The summary columns keep describing the unit's original variants."""
+    collapse_mac = check_collapse_mac(collapse_mac)
     if not isinstance(dsnode, str):
         raise TypeError("is.character(dsnode) is not TRUE")
     if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
@@ -229,7 +242,7 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
         gdsfile, aligned, aligned_w = _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat)
         kmat = (aligned, aligned_w, maxiter_pcg, tol_pcg)
     pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT analysis:", scanner_factory,
-                  dsnode, ds_budget, kmat)
+                  dsnode, ds_budget, kmat, collapse_mac)
     try:
         _run(pr, skat=True)
     finally:
@@ -246,6 +259,7 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
                 n_iter.append(int(st.n_iter[a:b].max()) if r.size else 0)
     Q, P = _unit_tests(pr, kept, S.__getitem__, Phi.__getitem__)
     ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
+    _collapse_cols(pr, ans)
     if kmat is not None:
         ans["n.iter"] = np.array(n_iter, dtype=np.int64)
     for i, nm in enumerate(pr.wb_colnm):

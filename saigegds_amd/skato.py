@@ -19,7 +19,7 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .aggregate import AggrParamBeta, _dbeta, _prepare, _run, _save, _summary_cols
+from .aggregate import AggrParamBeta, _collapse_cols, _dbeta, _prepare, _run, _save, _summary_cols, check_collapse_mac
 from .assoc import GenotypeSource
 from .skat import LAMBDA_DROP, LIMIT_T, _check_grm_mat, _h_u, pchisq_mix, spa_scale
 
@@ -235,7 +235,7 @@ def seqAssocGLMM_spaSKATO(gdsfile, modobj, units, wbeta=AggrParamBeta, rho=RHO_D
                           spa_pval: float = 0.05, var_ratio: float = float("nan"), res_savefn: str = "",
                           res_compress: str = "LZMA", parallel=False, verbose: bool = True, verbose_maf: bool = True,
                           scanner_factory=None, ds_budget: Optional[int] = None, grm_mat=None, tol_pcg: float = 1e-5,
-                          maxiter_pcg: int = 500) -> Dict[str, Any]:
+                          maxiter_pcg: int = 500, collapse_mac: float = float("nan")) -> Dict[str, Any]:
     """SKAT-O per unit and weight set (not in the reference; arguments as ``seqAssocGLMM_spaSKAT`` plus the grid
     ``rho``: non-empty, within [0, 1], strictly increasing, else ``ValueError``).
 
@@ -249,9 +249,12 @@ def seqAssocGLMM_spaSKATO(gdsfile, modobj, units, wbeta=AggrParamBeta, rho=RHO_D
     Columns: those of the burden driver's summary, ``n.var``, ``n.iter`` (only with ``grm_mat``), then ``pval``,
     ``pval.SKAT`` (``seqAssocGLMM_spaSKAT``'s ``pval``), ``pval.burden`` (the chi-square of ``(sum s)^2`` on one degree of
     freedom under the same covariance), ``rho.min`` and ``Q`` (SKAT's, ``sum w_j^2 S_j^2``), with the suffix ``.b<a>_<b>``
-    where there is more than one weight set.  A unit with no variant left gives NaN."""
+    where there is more than one weight set.  A unit with no variant left gives NaN.  ``collapse_mac``: as for
+    ``seqAssocGLMM_spaSKAT`` (the same code), with its columns ``n.collapsed`` and ``mac.collapsed``
+    after ``n.var``."""
     from ._lib import SKATO_MAX_M
     rho = check_rho(rho)
+    collapse_mac = check_collapse_mac(collapse_mac)
     if not isinstance(dsnode, str):
         raise TypeError("is.character(dsnode) is not TRUE")
     if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
@@ -261,7 +264,7 @@ def seqAssocGLMM_spaSKATO(gdsfile, modobj, units, wbeta=AggrParamBeta, rho=RHO_D
         gdsfile, aligned, aligned_w = _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat)
         kmat = (aligned, aligned_w, maxiter_pcg, tol_pcg)
     pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT-O analysis:", scanner_factory,
-                  dsnode, ds_budget, kmat)
+                  dsnode, ds_budget, kmat, collapse_mac)
     try:
         _run(pr, skat=True)
         kept, n_iter, prob = [], [], []                     # prob: (unit, weight column, s, A, Q of SKAT)
@@ -299,6 +302,7 @@ def seqAssocGLMM_spaSKATO(gdsfile, modobj, units, wbeta=AggrParamBeta, rho=RHO_D
         for c, key in (("pval", "pval"), ("pval.SKAT", "p.SKAT"), ("pval.burden", "p.burden"), ("rho.min", "rho.min")):
             cols[c][u, i] = res[key]
     ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
+    _collapse_cols(pr, ans)
     if kmat is not None:
         ans["n.iter"] = np.array(n_iter, dtype=np.int64)
     for i, nm in enumerate(pr.wb_colnm):
