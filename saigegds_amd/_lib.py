@@ -294,16 +294,22 @@ class _Handle:
         self.close()
 
 
+def _csr_ptr(what: str, msg: str, ptr, var_idx: np.ndarray, entries, ok: bool = True):
+    """The shape checks of a CSR ``ptr`` over the entries ``var_idx`` (``entries``: the per-entry arrays, each with the
+    shape of one entry; ``ok``: the caller's own condition) -> (ptr int64, the number of its groups)."""
+    ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+    n = ptr.size - 1
+    if not ok or any(a.shape != (var_idx.size,) + one for a, one in entries) or n < 0 or ptr[-1] != var_idx.size:
+        raise ValueError(f"{what}: {msg}")
+    return ptr, n
+
+
 def _unit_args(what: str, unit_ptr, var_idx, entries, ok: bool = True):
-    """Checks of the set tests' units (CSR ``unit_ptr`` / ``var_idx`` over rows; ``entries``: the per-entry arrays,
-    each with the shape of one entry; ``ok``: the caller's own condition) -> (unit_ptr int64, var_idx int32, n_units,
-    the units' sizes m, the offsets of their m x m matrices in one buffer)."""
-    unit_ptr = np.ascontiguousarray(unit_ptr, dtype=np.int64)
+    """Checks of the set tests' units (CSR ``unit_ptr`` / ``var_idx`` over rows; ``entries`` and ``ok`` as for
+    ``_csr_ptr``) -> (unit_ptr int64, var_idx int32, n_units, the units' sizes m, the offsets of their m x m matrices in
+    one buffer)."""
     var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
-    n_units = unit_ptr.size - 1
-    if not ok or var_idx.ndim != 1 or any(a.shape != var_idx.shape + one for a, one in entries) or n_units < 0 \
-            or unit_ptr[-1] != var_idx.size:
-        raise ValueError(f"{what}: inconsistent CSR / table shapes")
+    unit_ptr, n_units = _csr_ptr(what, "inconsistent CSR / table shapes", unit_ptr, var_idx, entries, ok and var_idx.ndim == 1)
     sizes = np.diff(unit_ptr)
     if (sizes < 0).any():
         raise ValueError(f"{what}: unit_ptr not ascending")
@@ -385,33 +391,23 @@ class Scanner(_Handle):
                                     valid.ctypes.data))
         return out, valid
 
-    def scan_u8(self, dosage: np.ndarray):
-        dosage = np.ascontiguousarray(dosage, dtype=np.uint8)
+    def _scan_dosage(self, dosage, dtype, entry: str):
+        dosage = np.ascontiguousarray(dosage, dtype=dtype)
         if dosage.ndim != 2 or dosage.shape[1] != self.n:
             raise ValueError(f"Invalid length of dosages: {dosage.shape[-1]}.")
         out, valid = self._out(dosage.shape[0])
-        check(self._L.sgx_scan_u8(self._h, dosage.ctypes.data, dosage.shape[0], out.ctypes.data,
-                                  valid.ctypes.data))
+        check(getattr(self._L, entry)(self._h, dosage.ctypes.data, dosage.shape[0], out.ctypes.data, valid.ctypes.data))
         return out, valid
+
+    def scan_u8(self, dosage: np.ndarray):
+        return self._scan_dosage(dosage, np.uint8, "sgx_scan_u8")
 
     def scan_i32(self, dosage: np.ndarray):
         """INTEGER dosages, NA_INTEGER (-2147483648) = missing (the INTSXP branch of get_ds)."""
-        dosage = np.ascontiguousarray(dosage, dtype=np.int32)
-        if dosage.ndim != 2 or dosage.shape[1] != self.n:
-            raise ValueError(f"Invalid length of dosages: {dosage.shape[-1]}.")
-        out, valid = self._out(dosage.shape[0])
-        check(self._L.sgx_scan_i32(self._h, dosage.ctypes.data, dosage.shape[0], out.ctypes.data,
-                                   valid.ctypes.data))
-        return out, valid
+        return self._scan_dosage(dosage, np.int32, "sgx_scan_i32")
 
     def scan_f64(self, dosage: np.ndarray):
-        dosage = np.ascontiguousarray(dosage, dtype=np.float64)
-        if dosage.ndim != 2 or dosage.shape[1] != self.n:
-            raise ValueError(f"Invalid length of dosages: {dosage.shape[-1]}.")
-        out, valid = self._out(dosage.shape[0])
-        check(self._L.sgx_scan_f64(self._h, dosage.ctypes.data, dosage.shape[0], out.ctypes.data,
-                                   valid.ctypes.data))
-        return out, valid
+        return self._scan_dosage(dosage, np.float64, "sgx_scan_f64")
 
     def scan_packed(self, raw: np.ndarray, cls, scale: float, offset: float, sel=None):
         """Packed-real dosage rows as the file stores them (``sgx_scan_packed``): ``raw`` [m, n_file_samp] integers
@@ -442,12 +438,10 @@ class Scanner(_Handle):
         """Burden rows (CSR over the rows of ``packed``, one 4-entry table per entry), then the
         single-variant test on each row (``sgx_burden_2bit``)."""
         packed = np.ascontiguousarray(packed, dtype=np.uint8)
-        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
         var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
         lut = np.ascontiguousarray(lut, dtype=np.float64)
-        n_rows = row_ptr.size - 1
-        if packed.ndim != 2 or lut.shape != (var_idx.size, 4) or n_rows < 0 or (n_rows >= 0 and row_ptr[-1] != var_idx.size):
-            raise ValueError("burden_2bit: inconsistent CSR / table shapes")
+        row_ptr, n_rows = _csr_ptr("burden_2bit", "inconsistent CSR / table shapes", row_ptr, var_idx, [(lut, (4,))],
+                                   packed.ndim == 2)
         out, valid = self._out(n_rows)
         check(self._L.sgx_burden_2bit(self._h, packed.ctypes.data, packed.shape[1], packed.shape[0], n_rows,
                                       row_ptr.ctypes.data, var_idx.ctypes.data, lut.ctypes.data,
@@ -770,15 +764,12 @@ class DosageBlock(_Handle):
     def burden(self, grp_ptr, var_idx, flip, w, mw):
         """Burden rows of the groups (CSR over the block's rows) x the columns of ``w`` / ``mw`` ([entries, n_cols],
         NaN weight = entry not in that column), then the single-variant test -> (out [groups * n_cols, 8], valid)."""
-        grp_ptr = np.ascontiguousarray(grp_ptr, dtype=np.int64)
         var_idx = np.ascontiguousarray(var_idx, dtype=np.int32)
         flip = np.ascontiguousarray(flip, dtype=np.uint8)
         w = np.ascontiguousarray(w, dtype=np.float64)
         mw = np.ascontiguousarray(mw, dtype=np.float64)
-        ng = grp_ptr.size - 1
-        if w.ndim != 2 or w.shape != mw.shape or w.shape[0] != var_idx.size or flip.shape != var_idx.shape or ng < 0 \
-                or grp_ptr[-1] != var_idx.size:
-            raise ValueError("DosageBlock.burden: inconsistent group / weight shapes")
+        grp_ptr, ng = _csr_ptr("DosageBlock.burden", "inconsistent group / weight shapes", grp_ptr, var_idx,
+                               [(w, w.shape[1:]), (mw, w.shape[1:])], w.ndim == 2 and flip.shape == var_idx.shape)
         nc = w.shape[1]
         out, valid = self._sc._out(ng * nc)
         check(self._L.sgx_dsblock_burden(self._sc._h, self._b, ng, grp_ptr.ctypes.data, var_idx.ctypes.data,

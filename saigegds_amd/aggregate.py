@@ -39,6 +39,7 @@ import numpy as np
 from ._lib import Scanner
 from .assoc import PackedRows, ScanInput, _is_num, open_scan_input
 from .gds import pack_dosage_2bit, unpack_dosage_2bit
+from .kmat import NO_DOSAGE_KMAT
 from .nullmod import NullModel, ScanModel, init_nullmod, load_modobj, no_loco
 
 # AggrParamBeta, R/assoc_aggregate.r:18-19: columns (shape1, shape2) = (1,1) and (1,25)
@@ -240,8 +241,8 @@ def variant_stats(n, s, out, valid):
 
 @contextlib.contextmanager
 def _packed_rows(pr: _Prepared, used, kmat=None):
-    """2-bit rows: one batch with every unit.  ``kmat`` = (matrix, weights, maxiter, tol): SKAT's covariance on the
-    explicit GRM (``sgx_skat_kmat_2bit``) instead of ``sgx_skat_2bit``."""
+    """2-bit rows: one batch with every unit.  ``kmat`` (a ``KmatSolve``): SKAT's covariance on the explicit GRM
+    (``sgx_skat_kmat_2bit``) instead of ``sgx_skat_2bit``."""
     sc, nw = pr.sc, pr.wbeta.shape[1]
     packed = pr.inp.packed_rows_at(used - 1)
 
@@ -282,16 +283,11 @@ def _packed_rows(pr: _Prepared, used, kmat=None):
         lut = dosage_tables(flip, mean)
         if kmat is None:
             return (*sc.skat_2bit(packed, unit_ptr, var_idx, lut), None)
-        from ._lib import ExplicitGrmOperator
-        mat, w, maxiter, tol = kmat
-        with ExplicitGrmOperator(mat) as op:
-            return sc.skat_kmat(op, packed, unit_ptr, var_idx, lut, w, pr.sm.tau, maxiter=maxiter, tol=tol)
+        with kmat.operator(sc) as op:
+            return sc.skat_kmat(op, packed, unit_ptr, var_idx, lut, *kmat.args)
 
     yield SimpleNamespace(batches=[list(range(len(pr.index)))], load=load, burden=burden, skat=skat,
                           collapse=collapse if hasattr(sc, "collapse_2bit") else None)
-
-
-_NO_DOSAGE_KMAT = "SKAT with 'grm_mat' on dosage input is not implemented."
 
 
 @contextlib.contextmanager
@@ -300,8 +296,8 @@ def _dosage_rows(pr: _Prepared, used, stored, budget, kmat=None):
     larger than that is a batch of its own); one ``DosageBlock`` of the largest batch's size, one upload per batch.  A
     variant that two batches share (sliding windows) is loaded in both.  ``skat`` is None where the block has none.
     ``kmat`` (as for ``_packed_rows``): ``skat`` is the block's ``skat_kmat`` (``sgx_ds_block_skat_kmat``) on one operator
-    for all batches -- the scanner's ``grm_operator`` where it has one (the tests' stand-ins); a scanner without
-    ``dosage_block`` or a block without ``skat_kmat`` is refused before any row is read."""
+    for all batches; a scanner without ``dosage_block`` or a block without ``skat_kmat`` is refused before any row is
+    read."""
     read_rows, dtype = pr.inp.dosage_reader(stored), pr.inp.ds_dtype
     row_bytes = ds_row_bytes(dtype, pr.sm.n)
     batches, cur, seen = [], [], set()
@@ -315,7 +311,7 @@ def _dosage_rows(pr: _Prepared, used, stored, budget, kmat=None):
     batches.append(cur)
     cap = max(np.unique(np.concatenate([pr.index[u] for u in bt])).size for bt in batches)
     if kmat is not None and not hasattr(pr.sc, "dosage_block"):
-        raise NotImplementedError(_NO_DOSAGE_KMAT)
+        raise NotImplementedError(NO_DOSAGE_KMAT.format("SKAT"))
     with contextlib.ExitStack() as stack:
         blk = stack.enter_context(pr.sc.dosage_block(dtype, cap))
 
@@ -331,19 +327,14 @@ def _dosage_rows(pr: _Prepared, used, stored, budget, kmat=None):
             skat = (lambda *a: (*blk.skat(*a), None)) if hasattr(blk, "skat") else None
         else:
             if not hasattr(blk, "skat_kmat"):
-                raise NotImplementedError(_NO_DOSAGE_KMAT)
-            mat, w, maxiter, tol = kmat
-            make_op = getattr(pr.sc, "grm_operator", None)
-            if make_op is None:
-                from ._lib import ExplicitGrmOperator as make_op
-            op = stack.enter_context(make_op(mat))
-
-            def skat(*a):
-                return blk.skat_kmat(op, *a, w, pr.sm.tau, maxiter=maxiter, tol=tol)
+                raise NotImplementedError(NO_DOSAGE_KMAT.format("SKAT"))
+            op = stack.enter_context(kmat.operator(pr.sc))
+            skat = lambda *a: blk.skat_kmat(op, *a, *kmat.args)      # noqa: E731
         yield SimpleNamespace(batches=batches, load=load, burden=burden, skat=skat, collapse=None)
 
 
 SkatStep = collections.namedtuple("SkatStep", "kept unit_ptr var_idx flip mean score cov n_iter")
+NO_DOSAGE_SKAT = "SKAT on dosage input is not implemented."
 
 
 def skat_step(pr: _Prepared, skat, rows, bv) -> SkatStep:
@@ -443,7 +434,7 @@ def _run(pr: _Prepared, kinds=(), burden_mac=float("nan"), skat=False):
         pr.n_collapsed, pr.pseudo = np.zeros(nu, dtype=np.int64), np.full(nu, -1, dtype=np.int64)
     with pr.backend as be:
         if skat and be.skat is None:
-            raise NotImplementedError("SKAT on dosage input is not implemented.")
+            raise NotImplementedError(NO_DOSAGE_SKAT)
         if collapsing and be.collapse is None:
             raise NotImplementedError("'collapse_mac' needs a scanner with collapse_2bit.")
         for bt in be.batches:

@@ -28,6 +28,7 @@ input the same two steps are the block's ``cond_kmat_set`` and ``
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import math
 import re
@@ -38,6 +39,7 @@ import numpy as np
 from . import aggregate
 from .assoc import (BLOCK_SIZE, GenotypeSource, ScanInput, _open_source, _pretty, assemble_result,
                     check_scan_args, finish_result, open_scan_input, require_device)
+from .kmat import NO_DOSAGE_KMAT, KmatSolve
 from .nullmod import ModelError, NullModel, init_nullmod, load_modobj, no_loco
 from .skat import aligned_grm_mat, spa_scale
 
@@ -110,31 +112,47 @@ def _tables(af, valid):
 
 
 _NO_DOSAGE = "Conditional analysis on dosage input is not implemented."
-_NO_DOSAGE_KMAT = "Conditional analysis with 'grm_mat' on dosage input is not implemented."
+_NO_DOSAGE_KMAT = NO_DOSAGE_KMAT.format("Conditional analysis")
+
+# a route's result (res: _scan_hard); n_iter: the PCG steps of every row's column, None without ``grm_mat``
+CondScan = collections.namedtuple("CondScan", "res out_c S_C Phi_CC n_iter")
 
 
-def _check_set(cond_ids, out_c, valid_c):
+def _set_phase(sc, cond_ids, thresholds, scan_set, install):
+    """The conditioning set of every route, at thresholds 0 / 0 / 1: ``scan_set()`` -> (its scan table, valid flags, what
+    ``install`` needs), the check of the set, ``install(out_c, ...)`` -> (S_C, Phi_CC, ...); the call's thresholds return."""
+    sc.set_thresholds(0.0, 0.0, 1.0, thresholds[3])
+    out_c, valid_c, *more = scan_set()
     for k, v in enumerate(cond_ids):
         if not valid_c[k] or not out_c[k, 1] > 0:
             raise ValueError(f"`condition`: variant {v!r} has no valid genotype or is monomorphic.")
+    S_C, Phi_CC = install(out_c, *more)[:2]
+    sc.set_thresholds(*thresholds)
+    return out_c, S_C, Phi_CC
 
 
-def _scan_hard(sc, inp: ScanInput, cidx, cond_ids, thresholds):
-    """The hard-call route: 2-bit rows -> (res [n_var, 8 + 3 + C]: the scan table, valid, S_j, Phi_jj, Phi_jC; the
-    set's scan table, S_C, Phi_CC)."""
+def _set_2bit(sc, inp: ScanInput, cidx, cond_ids, thresholds, install):
+    """``_set_phase`` of the two hard-call routes: ``install(rows_c, lut_c)`` is ``cond_set`` or ``cond_kmat_set``."""
+    import torch
+    nb = (inp.n_samp + 3) // 4
+
+    def scan_set():
+        rows_c = np.ascontiguousarray(np.concatenate([inp.packed_rows(i, i + 1)[:, :nb] for i in cidx]))
+        return (*sc.scan_2bit(rows_c), rows_c)
+
+    def put(out_c, rows_c):
+        return install(rows_c, _tables(torch.from_numpy(out_c[:, 0].copy()), torch.ones(len(cidx), dtype=torch.bool)).numpy())
+    return _set_phase(sc, cond_ids, thresholds, scan_set, put)
+
+
+def _scan_hard(sc, inp: ScanInput, cidx, cond_ids, thresholds) -> CondScan:
+    """The hard-call route: 2-bit rows, resident on the device per block -> res [n_var, 8 + 3 + C]: the scan table, valid,
+    S_j, Phi_jj, Phi_jC; the set's scan table, S_C, Phi_CC."""
     import torch
     n_samp, n_var, read_rows = inp.n_samp, inp.n_var, inp.packed_rows
     dev = torch.device(getattr(sc, "torch_device", "cuda"))
     nb = (n_samp + 3) // 4
-
-    # the conditioning set
-    sc.set_thresholds(0.0, 0.0, 1.0, thresholds[3])
-    rows_c = np.ascontiguousarray(np.concatenate([read_rows(i, i + 1)[:, :nb] for i in cidx]))
-    out_c, valid_c = sc.scan_2bit(rows_c)
-    _check_set(cond_ids, out_c, valid_c)
-    lut_c = _tables(torch.from_numpy(out_c[:, 0].copy()), torch.ones(len(cidx), dtype=torch.bool)).numpy()
-    S_C, Phi_CC = sc.cond_set(rows_c, lut_c)
-    sc.set_thresholds(*thresholds)
+    out_c, S_C, Phi_CC = _set_2bit(sc, inp, cidx, cond_ids, thresholds, sc.cond_set)
 
     # the scan, by blocks
     C = len(cidx)
@@ -161,30 +179,19 @@ def _scan_hard(sc, inp: ScanInput, cidx, cond_ids, thresholds):
         sc.sync()
         res[off:end] = torch.cat([out8, valid.to(torch.float64)[:, None], score[:, None], var[:, None], cov],
                                  dim=1).cpu().numpy()              # the one download
-    return res, out_c, S_C, Phi_CC
+    return CondScan(res, out_c, S_C, Phi_CC, None)
 
 
-def _scan_kmat(sc, inp: ScanInput, cidx, cond_ids, thresholds, kmat):
-    """The hard-call route on an explicit GRM: what ``_scan_hard`` returns with ``Phi^K`` for ``Phi``, and the PCG steps
-    of every row's column.  ``kmat`` = (matrix, weights, tau, maxiter, tol)."""
+def _scan_kmat(sc, inp: ScanInput, cidx, cond_ids, thresholds, kmat: KmatSolve) -> CondScan:
+    """The hard-call route on an explicit GRM: ``Phi^K`` for ``Phi``, the rows from host memory per block."""
     import torch
     n_samp, n_var, read_rows = inp.n_samp, inp.n_var, inp.packed_rows
     nb = (n_samp + 3) // 4
-    mat, w, tau, maxiter, tol = kmat
-    make_op = getattr(sc, "grm_operator", None)
-    if make_op is None:
-        from ._lib import ExplicitGrmOperator as make_op
-    C = len(cidx)
-    res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
+    res = np.empty((n_var, 8 + 3 + len(cidx)), dtype=np.float64)
     n_iter = np.zeros(n_var, dtype=np.int64)
-    with make_op(mat) as op:
-        sc.set_thresholds(0.0, 0.0, 1.0, thresholds[3])
-        rows_c = np.ascontiguousarray(np.concatenate([read_rows(i, i + 1)[:, :nb] for i in cidx]))
-        out_c, valid_c = sc.scan_2bit(rows_c)
-        _check_set(cond_ids, out_c, valid_c)
-        lut_c = _tables(torch.from_numpy(out_c[:, 0].copy()), torch.ones(C, dtype=torch.bool)).numpy()
-        S_C, Phi_CC, _ = sc.cond_kmat_set(op, rows_c, lut_c, w, tau, maxiter, tol)
-        sc.set_thresholds(*thresholds)
+    with kmat.operator(sc) as op:
+        out_c, S_C, Phi_CC = _set_2bit(sc, inp, cidx, cond_ids, thresholds,
+                                       lambda rows_c, lut_c: sc.cond_kmat_set(op, rows_c, lut_c, *kmat.args))
         for off in range(0, n_var, BLOCK_SIZE):
             end = min(n_var, off + BLOCK_SIZE)
             rows = np.ascontiguousarray(read_rows(off, end)[:, :nb])
@@ -193,17 +200,13 @@ def _scan_kmat(sc, inp: ScanInput, cidx, cond_ids, thresholds, kmat):
             score, var, cov, it = sc.cond_kmat(op, rows, lut)      # a row that failed the thresholds: NaN table, no solve
             res[off:end, :8], res[off:end, 8], res[off:end, 9], res[off:end, 10], res[off:end, 11:] = out8, valid, score, var, cov
             n_iter[off:end] = it
-    return res, out_c, S_C, Phi_CC, n_iter
+    return CondScan(res, out_c, S_C, Phi_CC, n_iter)
 
 
-def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds, kmat=None):
-    """The dosage route: what ``_scan_hard`` returns, from resident dosage blocks -- with ``kmat`` (as for ``_scan_kmat``)
-    what ``_scan_kmat`` returns: the set by the block's ``cond_kmat_set``, the rows by its ``cond_kmat``, on one operator
-    (the scanner's ``grm_operator`` where it has one).  A row that failed the thresholds gets a NaN mean there: no solve."""
+def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds, kmat: Optional[KmatSolve] = None) -> CondScan:
+    """The dosage route, from resident dosage blocks -- with ``kmat`` the set by the block's ``cond_kmat_set`` and the rows
+    by its ``cond_kmat``, on one operator.  A row that failed the thresholds gets a NaN mean there: no solve."""
     read_rows, ds_dtype, n_samp, n_var = inp.dosage_reader(stored), inp.ds_dtype, inp.n_samp, inp.n_var
-
-    def load(blk, v0):
-        return aggregate.load_rows(blk, read_rows(v0))
 
     refusal = _NO_DOSAGE if kmat is None else _NO_DOSAGE_KMAT
     make = getattr(sc, "dosage_block", None)
@@ -212,36 +215,31 @@ def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds, kmat=No
     C = len(cidx)
     order = np.argsort(cidx)                           # the readers take ascending indices
     rank = np.argsort(order).astype(np.int32)          # conditioning variant k is row rank[k] of its block
-    n_iter = np.zeros(n_var, dtype=np.int64)
+    n_iter = None if kmat is None else np.zeros(n_var, dtype=np.int64)
     with contextlib.ExitStack() as stack:
         blk = stack.enter_context(make(ds_dtype, C))
         if not hasattr(blk, "cond" if kmat is None else "cond_kmat"):
             raise NotImplementedError(refusal)
-        op = None
-        if kmat is not None:
-            mat, w, tau, maxiter, tol = kmat
-            make_op = getattr(sc, "grm_operator", None)
-            if make_op is None:
-                from ._lib import ExplicitGrmOperator as make_op
-            op = stack.enter_context(make_op(mat))
-        sc.set_thresholds(0.0, 0.0, 1.0, thresholds[3])
-        n, s, _ = load(blk, np.asarray(cidx, dtype=np.int64)[order])
-        out_c, valid_c = blk.scan()
-        out_c, valid_c = out_c[rank], valid_c[rank]
-        _check_set(cond_ids, out_c, valid_c)
-        fl, mean = aggregate.flip_mean(n, s)
-        if kmat is None:
-            S_C, Phi_CC = blk.cond_set(rank, fl[rank], mean[rank])
-        else:
-            S_C, Phi_CC, _ = blk.cond_kmat_set(op, rank, fl[rank], mean[rank], w, tau, maxiter, tol)
-        sc.set_thresholds(*thresholds)
+        op = None if kmat is None else stack.enter_context(kmat.operator(sc))
+
+        def scan_set():
+            n, s, _ = aggregate.load_rows(blk, read_rows(np.asarray(cidx, dtype=np.int64)[order]))
+            out_c, valid_c = blk.scan()
+            return out_c[rank], valid_c[rank], n, s
+
+        def install(out_c, n, s):
+            fl, mean = aggregate.flip_mean(n, s)
+            if kmat is None:
+                return blk.cond_set(rank, fl[rank], mean[rank])
+            return blk.cond_kmat_set(op, rank, fl[rank], mean[rank], *kmat.args)
+        out_c, S_C, Phi_CC = _set_phase(sc, cond_ids, thresholds, scan_set, install)
         blk.close()                                    # the set is the scanner's: the rows' block takes the memory
         per = int(max(1, min(n_var, aggregate.DS_BUDGET // aggregate.ds_row_bytes(ds_dtype, n_samp))))
         res = np.empty((n_var, 8 + 3 + C), dtype=np.float64)
         blk = stack.enter_context(make(ds_dtype, per))
         for off in range(0, n_var, per):
             end = min(n_var, off + per)
-            n, s, _ = load(blk, np.arange(off, end, dtype=np.int64))      # the one upload
+            n, s, _ = aggregate.load_rows(blk, read_rows(np.arange(off, end, dtype=np.int64)))      # the one upload
             out8, valid = blk.scan()
             fl, mean = aggregate.flip_mean(n, s)
             if kmat is None:
@@ -249,7 +247,7 @@ def _scan_dosage(sc, inp: ScanInput, stored, cidx, cond_ids, thresholds, kmat=No
             else:
                 score, var, cov, n_iter[off:end] = blk.cond_kmat(op, fl, np.where(valid != 0, mean, np.nan))
             res[off:end, :8], res[off:end, 8], res[off:end, 9], res[off:end, 10], res[off:end, 11:] = out8, valid, score, var, cov
-    return (res, out_c, S_C, Phi_CC) if kmat is None else (res, out_c, S_C, Phi_CC, n_iter)
+    return CondScan(res, out_c, S_C, Phi_CC, n_iter)
 
 
 def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("nan"), mac: float = 10,
@@ -338,20 +336,18 @@ def seqAssocGLMM_SPA_cond(gdsfile, modobj: Any, condition, maf: float = float("n
     sc = scanner_factory(mobj)
     try:
         thresholds = (float(maf), float(mac), float(missing), float(spa_pval))
-        n_iter = None
-        if kmat_w is not None:
-            kmat = (*kmat_w, np.asarray(mobj.tau, dtype=np.float64), int(maxiter_pcg), float(tol_pcg))
-            if inp.kind == "packed":
-                res, out_c, S_C, Phi_CC, n_iter = _scan_kmat(sc, inp, cidx, cond_ids, thresholds, kmat)
-            else:
-                res, out_c, S_C, Phi_CC, n_iter = _scan_dosage(sc, inp, stored, cidx, cond_ids, thresholds, kmat)
-        elif inp.kind == "packed":
-            res, out_c, S_C, Phi_CC = _scan_hard(sc, inp, cidx, cond_ids, thresholds)
+        kmat = None if kmat_w is None else KmatSolve(*kmat_w, np.asarray(mobj.tau, dtype=np.float64), int(maxiter_pcg),
+                                                     float(tol_pcg))
+        if inp.kind != "packed":
+            scan = _scan_dosage(sc, inp, stored, cidx, cond_ids, thresholds, kmat)
+        elif kmat is None:
+            scan = _scan_hard(sc, inp, cidx, cond_ids, thresholds)
         else:
-            res, out_c, S_C, Phi_CC = _scan_dosage(sc, inp, stored, cidx, cond_ids, thresholds)
+            scan = _scan_kmat(sc, inp, cidx, cond_ids, thresholds, kmat)
     finally:
         sc.close()
 
+    res, out_c, S_C, Phi_CC, n_iter = scan
     x = res[:, 8] != 0
     if verbose:
         print(f"# of variants after filtering by MAF, MAC and missing thresholds: {_pretty(int(x.sum()))}")

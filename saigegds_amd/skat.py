@@ -29,8 +29,11 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .aggregate import AggrParamBeta, _collapse_cols, _dbeta, _prepare, _run, _save, _summary_cols, check_collapse_mac
-from .assoc import GenotypeSource
+from .aggregate import (NO_DOSAGE_SKAT, AggrParamBeta, _collapse_cols, _dbeta, _prepare, _run, _save, _summary_cols,
+                        check_collapse_mac)
+from .assoc import GenotypeSource, _open_source, open_scan_input
+from .kmat import KmatSolve
+from .nullmod import load_modobj, no_loco
 
 LAMBDA_DROP = 1e-10      # eigenvalues at or below this fraction of the largest one are dropped
 SERIES_X = 0.05          # |2 t lambda_k| below which a term's functions are summed as power series
@@ -145,19 +148,33 @@ def spa_scale(o, S, var, spa_pval: float) -> np.ndarray:
     return d
 
 
+def device_units(pr):
+    """pr.skat, the device step of a batch of units each -> per unit in the units' order (``kept``: its variants in the
+    test as rows of pr.out / pr.maf, their scores and covariance, its largest PCG step count; None without ``grm_mat``)."""
+    for st in pr.skat:
+        for k, (r, a, b) in enumerate(zip(st.kept, st.unit_ptr, st.unit_ptr[1:])):
+            yield r, st.score[a:b], st.cov[k], None if st.n_iter is None else (int(st.n_iter[a:b].max()) if r.size else 0)
+
+
+def unit_walk(pr, units=None):
+    """The walk over the units of a call (``units``: what ``device_units`` gives, the default) -> per unit (its number,
+    ``kept``, ``S`` and ``Phi`` as float64, ``n_iter``); binary traits: ``Phi`` with the SPA scaling (``spa_scale``)."""
+    for u, (r, S, phi, n_iter) in enumerate(device_units(pr) if units is None else units):
+        S, phi = np.asarray(S, dtype=np.float64), np.array(phi, dtype=np.float64)
+        if pr.binary and r.size:
+            sd = np.sqrt(spa_scale(pr.out[r], S, np.diag(phi), pr.sm.spa_pval))
+            phi = phi * sd[:, None] * sd[None, :]
+        yield u, r, S, phi, n_iter
+
+
 def _unit_tests(pr, kept, S_of, phi_of):
     """Step 3 of the flow for every unit: ``kept[u]`` the unit's variants (rows of pr.out / pr.maf), ``S_of(u)`` and
     ``phi_of(u)`` their score statistics and covariance -> (Q, pval), [n_units, n_weights] each."""
     nu, nw = len(kept), pr.wbeta.shape[1]
     Q, P = np.full((nu, nw), np.nan), np.full((nu, nw), np.nan)
-    for u, r in enumerate(kept):
+    for u, r, S, phi, _ in unit_walk(pr, ((r, S_of(u), phi_of(u), None) for u, r in enumerate(kept))):
         if r.size == 0:
             continue
-        S = np.asarray(S_of(u), dtype=np.float64)
-        phi = np.array(phi_of(u), dtype=np.float64)
-        if pr.binary:
-            sd = np.sqrt(spa_scale(pr.out[r], S, np.diag(phi), pr.sm.spa_pval))
-            phi = phi * sd[:, None] * sd[None, :]
         for i, (a, b) in enumerate(pr.wbeta.T):
             w = _dbeta(pr.maf[r], a, b)
             Q[u, i] = float(np.sum(w * w * S * S))
@@ -174,19 +191,44 @@ def aligned_grm_mat(grm_mat, inp, mod):
     return _align_grm_mat(grm_mat, inp.sample_id()), np.ascontiguousarray(np.asarray(mod.V, dtype=np.float64)[inp.ii])
 
 
-def _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat):
-    """The refusals of ``seqAssocGLMM_spaSKAT(grm_mat=)`` that need no scanner, before any row is read -> (the opened
-    source, the matrix of the scan's samples in the scan's order, the model's weights V in that order).  Dosage input
-    is refused only where the scanner cannot serve it (``aggregate._dosage_rows``)."""
-    from .assoc import _open_source, open_scan_input
-    from .nullmod import load_modobj, no_loco
-    if not (parallel is False or parallel is None or (isinstance(parallel, (int, np.integer)) and int(parallel) in (0, 1))):
-        raise ValueError("SKAT with 'grm_mat' runs on one GPU: 'parallel' should be FALSE or 1.")
-    mod = load_modobj(modobj, False)
-    no_loco(mod, "SAIGE SKAT analysis")
-    src = _open_source(gdsfile, False)          # opened once: the driver goes on with this object
-    inp = open_scan_input(src, mod, dsnode, False)
-    return (src, *aligned_grm_mat(grm_mat, inp, mod))
+def prepare_skat(what, gdsfile, modobj, units, wbeta, dsnode, spa_pval, var_ratio, parallel, verbose, scanner_factory,
+                 ds_budget, grm_mat, tol_pcg, maxiter_pcg, collapse_mac):
+    """The head of the SKAT and SKAT-O drivers (``what``: the title a verbose call prints) -> the prepared call.  What
+    ``grm_mat=`` refuses without a scanner comes before any row is read (dosage input only where the scanner cannot serve
+    it: ``aggregate._dosage_rows``); the solve's tau is the model's, which ``init_nullmod`` hands on as it is."""
+    collapse_mac = check_collapse_mac(collapse_mac)
+    if not isinstance(dsnode, str):
+        raise TypeError("is.character(dsnode) is not TRUE")
+    if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
+        raise NotImplementedError(NO_DOSAGE_SKAT)
+    kmat = None
+    if grm_mat is not None:
+        if not (parallel is False or parallel is None or (isinstance(parallel, (int, np.integer)) and int(parallel) in (0, 1))):
+            raise ValueError("SKAT with 'grm_mat' runs on one GPU: 'parallel' should be FALSE or 1.")
+        mod = load_modobj(modobj, False)
+        no_loco(mod, "SAIGE SKAT analysis")
+        gdsfile = _open_source(gdsfile, False)          # opened once: _prepare goes on with this object
+        inp = open_scan_input(gdsfile, mod, dsnode, False)
+        kmat = KmatSolve(*aligned_grm_mat(grm_mat, inp, mod), np.asarray(mod.tau, dtype=np.float64), maxiter_pcg, tol_pcg)
+    return _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, scanner_factory, dsnode, ds_budget,
+                    kmat, collapse_mac)
+
+
+def finish_skat(pr, kept, n_iter, cols, res_savefn, res_compress, verbose) -> Dict[str, Any]:
+    """The tail of the SKAT and SKAT-O drivers: the summary columns, ``n.var``, those of ``collapse_mac``, ``n.iter`` (the
+    walk's ``n_iter`` per unit), then per weight set the columns ``cols`` (name -> [n_units, n_weights], in the result's
+    order; suffix ``.b<a>_<b>`` with more than one weight set); saves the result where asked."""
+    ans = _summary_cols(pr)
+    ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
+    _collapse_cols(pr, ans)
+    if n_iter[0] is not None:
+        ans["n.iter"] = np.array(n_iter, dtype=np.int64)
+    for i, nm in enumerate(pr.wb_colnm):
+        sfx = f".{nm}" if len(pr.wb_colnm) > 1 else ""
+        for c, x in cols.items():
+            ans[c + sfx] = x[:, i]
+    _save(ans, res_savefn, res_compress, verbose)
+    return ans
 
 
 def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: str = "", spa_pval: float = 0.05,
@@ -232,38 +274,12 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
     (or ``Phi^K``) and the SPA scaling like any variant.  ``n.var`` counts the entries after collapsing; two more
     columns appear: ``n.collapsed`` (the variants replaced) and ``mac.collapsed`` (the pseudo-variant's minor allele
     count, NaN where nothing was replaced).  The summary columns keep describing the unit's original variants."""
-    collapse_mac = check_collapse_mac(collapse_mac)
-    if not isinstance(dsnode, str):
-        raise TypeError("is.character(dsnode) is not TRUE")
-    if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
-        raise NotImplementedError("SKAT on dosage input is not implemented.")
-    kmat = None
-    if grm_mat is not None:
-        gdsfile, aligned, aligned_w = _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat)
-        kmat = (aligned, aligned_w, maxiter_pcg, tol_pcg)
-    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT analysis:", scanner_factory,
-                  dsnode, ds_budget, kmat, collapse_mac)
+    pr = prepare_skat("SAIGE SKAT analysis:", gdsfile, modobj, units, wbeta, dsnode, spa_pval, var_ratio, parallel, verbose,
+                      scanner_factory, ds_budget, grm_mat, tol_pcg, maxiter_pcg, collapse_mac)
     try:
         _run(pr, skat=True)
     finally:
         pr.sc.close()
-    ans = _summary_cols(pr)
-    kept, S, Phi, n_iter = [], [], [], []
-    for st in pr.skat:                                  # a batch of units each, in the units' order
-        for k, r in enumerate(st.kept):
-            a, b = st.unit_ptr[k], st.unit_ptr[k + 1]
-            kept.append(r)
-            S.append(st.score[a:b])
-            Phi.append(st.cov[k])
-            if kmat is not None:
-                n_iter.append(int(st.n_iter[a:b].max()) if r.size else 0)
-    Q, P = _unit_tests(pr, kept, S.__getitem__, Phi.__getitem__)
-    ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
-    _collapse_cols(pr, ans)
-    if kmat is not None:
-        ans["n.iter"] = np.array(n_iter, dtype=np.int64)
-    for i, nm in enumerate(pr.wb_colnm):
-        sfx = f".{nm}" if len(pr.wb_colnm) > 1 else ""
-        ans["Q" + sfx], ans["pval" + sfx] = Q[:, i], P[:, i]
-    _save(ans, res_savefn, res_compress, verbose)
-    return ans
+    kept, S, Phi, n_iter = zip(*device_units(pr))
+    Q, P = _unit_tests(pr, kept, S.__getitem__, Phi.__getitem__)      # (the walk scales Phi: it gets the device's own)
+    return finish_skat(pr, kept, n_iter, {"Q": Q, "pval": P}, res_savefn, res_compress, verbose)

@@ -19,9 +19,8 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from .aggregate import AggrParamBeta, _collapse_cols, _dbeta, _prepare, _run, _save, _summary_cols, check_collapse_mac
-from .assoc import GenotypeSource
-from .skat import LAMBDA_DROP, LIMIT_T, _check_grm_mat, _h_u, pchisq_mix, spa_scale
+from .aggregate import AggrParamBeta, _dbeta, _run
+from .skat import LAMBDA_DROP, LIMIT_T, _h_u, finish_skat, pchisq_mix, prepare_skat, unit_walk
 
 RHO_DEFAULT = (0, 0.01, 0.04, 0.09, 0.25, 0.5, 1)
 RHO_CAP = 0.999          # a grid of more than one value takes a value above this as this
@@ -254,37 +253,19 @@ def seqAssocGLMM_spaSKATO(gdsfile, modobj, units, wbeta=AggrParamBeta, rho=RHO_D
     after ``n.var``."""
     from ._lib import SKATO_MAX_M
     rho = check_rho(rho)
-    collapse_mac = check_collapse_mac(collapse_mac)
-    if not isinstance(dsnode, str):
-        raise TypeError("is.character(dsnode) is not TRUE")
-    if dsnode != "" and isinstance(gdsfile, GenotypeSource) and gdsfile.packed is not None:
-        raise NotImplementedError("SKAT on dosage input is not implemented.")
-    kmat = None
-    if grm_mat is not None:
-        gdsfile, aligned, aligned_w = _check_grm_mat(gdsfile, modobj, dsnode, parallel, grm_mat)
-        kmat = (aligned, aligned_w, maxiter_pcg, tol_pcg)
-    pr = _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, "SAIGE SKAT-O analysis:", scanner_factory,
-                  dsnode, ds_budget, kmat, collapse_mac)
+    pr = prepare_skat("SAIGE SKAT-O analysis:", gdsfile, modobj, units, wbeta, dsnode, spa_pval, var_ratio, parallel, verbose,
+                      scanner_factory, ds_budget, grm_mat, tol_pcg, maxiter_pcg, collapse_mac)
     try:
         _run(pr, skat=True)
         kept, n_iter, prob = [], [], []                     # prob: (unit, weight column, s, A, Q of SKAT)
-        for st in pr.skat:                                  # a batch of units each, in the units' order
-            for k, r in enumerate(st.kept):
-                a, b = st.unit_ptr[k], st.unit_ptr[k + 1]
-                u = len(kept)
-                kept.append(r)
-                if kmat is not None:
-                    n_iter.append(int(st.n_iter[a:b].max()) if r.size else 0)
-                if r.size == 0:
-                    continue
-                S = np.asarray(st.score[a:b], dtype=np.float64)
-                phi = np.array(st.cov[k], dtype=np.float64)
-                if pr.binary:
-                    sd = np.sqrt(spa_scale(pr.out[r], S, np.diag(phi), pr.sm.spa_pval))
-                    phi = phi * sd[:, None] * sd[None, :]
-                for i, (wa, wb) in enumerate(pr.wbeta.T):
-                    w = _dbeta(pr.maf[r], wa, wb)
-                    prob.append((u, i, w * S, phi * w[:, None] * w[None, :], float(np.sum(w * w * S * S))))
+        for u, r, S, phi, it in unit_walk(pr):
+            kept.append(r)
+            n_iter.append(it)
+            if r.size == 0:
+                continue
+            for i, (wa, wb) in enumerate(pr.wbeta.T):
+                w = _dbeta(pr.maf[r], wa, wb)
+                prob.append((u, i, w * S, phi * w[:, None] * w[None, :], float(np.sum(w * w * S * S))))
         spectra = [None] * len(prob)
         dev = [j for j, p in enumerate(prob) if p[2].size <= SKATO_MAX_M and np.all(np.isfinite(p[3]))]
         if dev and hasattr(pr.sc, "skato_spectra"):
@@ -293,7 +274,6 @@ def seqAssocGLMM_spaSKATO(gdsfile, modobj, units, wbeta=AggrParamBeta, rho=RHO_D
                 spectra[j] = x
     finally:
         pr.sc.close()
-    ans = _summary_cols(pr)
     nu, nw = len(kept), pr.wbeta.shape[1]
     cols = {c: np.full((nu, nw), np.nan) for c in ("pval", "pval.SKAT", "pval.burden", "rho.min", "Q")}
     for (u, i, s, A, q0), sp in zip(prob, spectra):
@@ -301,13 +281,4 @@ def seqAssocGLMM_spaSKATO(gdsfile, modobj, units, wbeta=AggrParamBeta, rho=RHO_D
         cols["Q"][u, i] = q0
         for c, key in (("pval", "pval"), ("pval.SKAT", "p.SKAT"), ("pval.burden", "p.burden"), ("rho.min", "rho.min")):
             cols[c][u, i] = res[key]
-    ans["n.var"] = np.array([k.size for k in kept], dtype=np.int64)
-    _collapse_cols(pr, ans)
-    if kmat is not None:
-        ans["n.iter"] = np.array(n_iter, dtype=np.int64)
-    for i, nm in enumerate(pr.wb_colnm):
-        sfx = f".{nm}" if len(pr.wb_colnm) > 1 else ""
-        for c in ("pval", "pval.SKAT", "pval.burden", "rho.min", "Q"):
-            ans[c + sfx] = cols[c][:, i]
-    _save(ans, res_savefn, res_compress, verbose)
-    return ans
+    return finish_skat(pr, kept, n_iter, cols, res_savefn, res_compress, verbose)
