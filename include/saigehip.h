@@ -565,8 +565,8 @@ int sgx_quantize_packed(const void *raw, int cls, size_t n_file_samp, double sca
  * (1..4: successive sgx_scan_block / sgx_scan_2bit_dev calls go round-robin over that many streams with
  * their own workspace, so the SPA stage of one block runs under the score stage of the next; call
  * sgx_sync() before reading any output), "pipe_mb" (MiB of input rows per chunk of a host-buffer scan;
- * 0 = default 512), "spa_abl" (diagnostic bits; 512: the SPA kernels scan the rows of a block instead of
- * walking its carrier lists), "three_plane" (-1 automatic -- row-major calls take the three-plane form of the
+ * 0 = default 512), "spa_scan_rows" (0 / 1: the per-variant SPA kernels scan the rows of a block instead of
+ * walking its carrier lists, as they do for row-major input), "three_plane" (-1 automatic -- row-major calls take the three-plane form of the
  * contraction kernel for models of up to four B fragments (K <= 3 binary, any quantitative K <= 2) and otherwise once
  * more than ~0.5 % of the genotypes are missing, resident blocks by the census of their load; 0 / 1: never / always), "guard_exp" (x: the fixed-point guard at 10^-x instead of 2e-11; 0 = off, 300 = every
  * variant through the FP64 kernel).  Results never depend on them beyond rounding (1e-12). */

@@ -9,7 +9,7 @@ extern "C" int sgx_set_option(sgx_handle *h, const char *name, long long value)
 	else if (n == "force_dense") h->force_dense = value != 0;
 	else if (n == "spa_exact") h->force_exact = value != 0;
 	else if (n == "pipe_mb") { if (value < 0 || value > 65536) return fail(SGX_EINVAL, "pipe_mb out of range"); h->pipe_bytes = (size_t)value << 20; return SGX_OK; }
-	else if (n == "spa_abl") h->spa_abl = (int)value;
+	else if (n == "spa_scan_rows") h->spa_scan_rows = value != 0;
 	else if (n == "guard_exp") { if (value < 0 || value > 300) return fail(SGX_EINVAL, "guard_exp must be 0..300"); h->guard_tol = std::pow(10.0, -(double)value); }
 	else if (n == "three_plane") { if (value < -1 || value > 1) return fail(SGX_EINVAL, "three_plane must be -1 (automatic), 0 or 1"); h->dense_opt = (int)value; return SGX_OK; }
 	else if (n == "lanes") {
@@ -26,7 +26,7 @@ extern "C" int sgx_set_option(sgx_handle *h, const char *name, long long value)
 			for (int g = 0; g < MF_MAXG; g++) { t->mf[g] = h->mf[g]; t->mf_nbfv[g] = h->mf_nbfv[g]; }
 			t->owner = h;
 			t->force_dense = h->force_dense; t->force_v1 = h->force_v1; t->force_exact = h->force_exact;
-			t->spa_abl = h->spa_abl; t->guard_tol = h->guard_tol;
+			t->spa_scan_rows = h->spa_scan_rows; t->guard_tol = h->guard_tol;
 			rc = set_dev(t.get());
 			if (!rc) rc = alloc_workspace(t.get());
 			if (rc) return rc;
@@ -81,13 +81,6 @@ static int sync_lane(sgx_handle *h)
 			if (h->form != FORM_THREE && (frac > SGX_DENSE_ON || over)) p->dense_mode = true;
 			else if (h->form == FORM_THREE && frac < SGX_DENSE_OFF) p->dense_mode = false;
 		}
-#ifdef SPA5_PROF
-		fprintf(stderr, "routing: tier A %d, tier B %d (of them handed on by A: %d), per-variant kernels %d (series list %d, exact list %d), dense %d\n",
-			h->h_counters[0], h->h_counters[7], h->h_counters[6], h->h_counters[5], h->h_counters[3], h->h_counters[4], h->h_counters[2]);
-		fprintf(stderr, "spa5 phases (10 ns ticks summed over variants): series kernel %d variants: stage %d count %d index %d gather %d series %d (sweep %d sum %d solve %d) | exact kernel %d variants: stage %d count %d index %d gather %d - sweeps %d\n",
-			h->h_counters[3], h->h_counters[8], h->h_counters[9], h->h_counters[10], h->h_counters[11], h->h_counters[12], h->h_counters[13], h->h_counters[14], h->h_counters[15],
-			h->h_counters[4], h->h_counters[16], h->h_counters[17], h->h_counters[18], h->h_counters[19], h->h_counters[21]);
-#endif
 		float a = 0, b = 0, c = 0;
 		(void)hipEventElapsedTime(&a, h->ev[0], h->ev[1]);
 		(void)hipEventElapsedTime(&b, h->ev[1], h->ev[2]);

@@ -46,17 +46,24 @@ static const void *spa4_moments_fn()
 	else return (const void *)spa4_moments_ds<KK, NCX, INPUT>;
 }
 
+// the exact dense pass (spa_kernel, kern_spa.h) over counters[slot] variants of a call of M: the records of `list`, or,
+// without one, the records in order
+template <int KK, int INPUT>
+static void launch_dense(sgx_handle *h, RowsRef rr, size_t M, int slot, const int *list, double *out8)
+{
+	const dim3 sgrid((unsigned)std::min<size_t>(M, (size_t)h->spa_grid));
+	hipLaunchKernelGGL((spa_kernel<KK, 512, INPUT>), sgrid, dim3(512), 0, h->stream, rr,
+		h->md, h->recs, h->counters, slot, list, h->scratch, h->scratch_stride, out8);
+}
+
 // the SPA stage's launches for K = KK (launch_spa)
 template <int KK, int INPUT>
 static int launch_spa_k(sgx_handle *h, RowsRef rr, size_t M, double *out8, bool lazy_dense)
 {
 	const DevModel &md = h->md;
-	constexpr int PB = 512;
 	hipStream_t st = h->stream;
-	const dim3 sgrid((unsigned)std::min<size_t>(M, (size_t)h->spa_grid));
 	if (h->force_v1 && INPUT != IN_2BIT) {
-		hipLaunchKernelGGL((spa_kernel<KK, PB, INPUT>), sgrid, dim3(PB), 0, st, rr,
-			md, h->recs, h->counters, 0, (const int *)nullptr, h->scratch, h->scratch_stride, out8);
+		launch_dense<KK, INPUT>(h, rr, M, 0, nullptr, out8);
 		return SGX_OK;
 	}
 	// series SPA stage (kern_spa4.h): rounds of at most vcap4 flagged variants; tier A (short series), then tier B
@@ -80,12 +87,11 @@ static int launch_spa_k(sgx_handle *h, RowsRef rr, size_t M, double *out8, bool 
 		HIPCHK(hipFuncSetAttribute((const void *)spa5_kernel<KK, INPUT, 1, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l5));
 		h->spa5_attr_set[INPUT] = true;
 	}
-	const int fx5 = (h->force_exact ? 1 : 0) | (h->spa_abl & ~1);
 	auto moments = [&](auto ncx, int tier, int rd) {
 		constexpr int NCX = decltype(ncx)::value;
 		if constexpr (INPUT == IN_2BIT)
 			hipLaunchKernelGGL((spa4_moments<KK, NCX>), dim3((unsigned)h->n_cu), dim3(WAVE * spa4_waves(KK)), fl, st, rr, md, h->nseg,
-				tier, btop, rd * h->vcap4, h->vcap4, h->recs, h->counters, h->seg4, h->spa_abl, h->cur5 + 2);
+				tier, btop, rd * h->vcap4, h->vcap4, h->recs, h->counters, h->seg4, h->cur5 + 2);
 		else
 			hipLaunchKernelGGL((spa4_moments_ds<KK, NCX, INPUT>), dim3((unsigned)h->n_cu), dim3(WAVE * spa4_waves(KK)), fl, st,
 				(const void *)rr.base, rr.bpv, md, h->nseg, tier, btop, rd * h->vcap4, h->vcap4, h->recs, h->counters, h->seg4, h->cur5 + 2);
@@ -95,23 +101,22 @@ static int launch_spa_k(sgx_handle *h, RowsRef rr, size_t M, double *out8, bool 
 	for (int rd = 0; rd < nround; rd++) moments(std::integral_constant<int, SPA4_NCA>(), 0, rd);
 	for (int rd = 0; rd < nround; rd++) moments(std::integral_constant<int, SPA4_NCB>(), 1, rd);
 	// (genotype blocks carry the carrier lists of the rare variants, rr.cptr: the kernels walk those instead of scanning
-	// the row; spa_abl & 512 makes them scan, as for row-major input)
-	const int only5 = (INPUT == IN_2BIT && rr.cptr != nullptr && (h->spa_abl & 512)) ? 2 : 0;
+	// the row; the "spa_scan_rows" hook makes them scan, as for row-major input)
 	const size_t ws5 = spa5_wg_bytes(md.N);
 	auto spa5 = [&](auto threads, int nwg) {
 		constexpr int T5 = decltype(threads)::value;
 		if constexpr (T5 == 512 || INPUT == IN_2BIT) {     // (the 128-thread forms: 2-bit rows only)
 			hipLaunchKernelGGL((spa5_kernel<KK, INPUT, 0, T5>), dim3((unsigned)nwg), dim3(T5), l5, st, rr, md, h->recs, h->counters,
-				h->fb_spa2, h->fb_x2, h->cur5, h->fallback, h->scr5, out8, h->force_dense ? 1 : 0, fx5, l5, only5, ws5, 3);
+				h->fb_spa2, h->fb_x2, h->cur5, h->fallback, h->scr5, out8, h->force_dense ? 1 : 0, h->force_exact ? 1 : 0, l5,
+				h->spa_scan_rows, ws5, 3);
 			hipLaunchKernelGGL((spa5_kernel<KK, INPUT, 1, T5>), dim3((unsigned)nwg), dim3(T5), l5, st, rr, md, h->recs, h->counters,
-				h->fb_x2, h->fb_x2, h->cur5 + 1, h->fallback, h->scr5, out8, h->force_dense ? 1 : 0, fx5, l5, only5, ws5, 4);
+				h->fb_x2, h->fb_x2, h->cur5 + 1, h->fallback, h->scr5, out8, h->force_dense ? 1 : 0, h->force_exact ? 1 : 0, l5,
+				h->spa_scan_rows, ws5, 4);
 		}
 	};
 	if (small5) spa5(std::integral_constant<int, 128>(), h->nwg5);
 	else spa5(std::integral_constant<int, 512>(), h->n_cu);
-	if (!lazy_dense)
-		hipLaunchKernelGGL((spa_kernel<KK, PB, INPUT>), sgrid, dim3(PB), 0, st, rr,
-			md, h->recs, h->counters, 2, h->fallback, h->scratch, h->scratch_stride, out8);
+	if (!lazy_dense) launch_dense<KK, INPUT>(h, rr, M, 2, h->fallback, out8);
 	return SGX_OK;
 }
 
@@ -140,10 +145,8 @@ static int launch_spa(sgx_handle *h, RowsRef rr, size_t M, double *out8, bool la
 // the dense pass a lazy call left out, for the variants on its fallback list (counters[2] of that call)
 static int launch_pending_dense(sgx_handle *h)
 {
-	const dim3 sgrid((unsigned)std::min<size_t>(h->pend_dense.M, (size_t)h->spa_grid));
 	with_k(h->md.K, [&](auto kk) {
-		hipLaunchKernelGGL((spa_kernel<decltype(kk)::value, 512, IN_2BIT>), sgrid, dim3(512), 0, h->stream, h->pend_dense.rr, h->md,
-			h->recs, h->counters, 2, h->fallback, h->scratch, h->scratch_stride, h->pend_dense.out8);
+		launch_dense<decltype(kk)::value, IN_2BIT>(h, h->pend_dense.rr, h->pend_dense.M, 2, h->fallback, h->pend_dense.out8);
 	});
 	HIPCHK(hipGetLastError());
 	return SGX_OK;

@@ -81,7 +81,7 @@ struct sgx_handle {
 	bool spa5_attr_set[3] = {false, false, false};
 	bool mom_attr_set[3] = {false, false, false};   // per input type: the moments kernels' dynamic LDS size has been raised
 	DevBuf<uint8_t> scr5; DevBuf<int> cur5; int nwg5 = 0;   // spa5_kernel: per-workgroup lists, queue cursor
-	int spa_abl = 0;                  // timing experiments (wrong results)
+	bool spa_scan_rows = false;       // test hook: the per-variant kernels scan a block's rows instead of walking its carrier lists
 	bool force_exact = false;         // test hook: every SPA variant takes the exact exp/log kernels
 	// exact-integer MFMA score path (mf_fixed.h, kern_score3.h)
 	bool mf_ok = false;

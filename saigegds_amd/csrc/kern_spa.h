@@ -125,6 +125,17 @@ __device__ double saddle_prob_fast(double t, double k2s, double q, double NAmu, 
 	return pval;
 }
 
+// How Saddle_Prob_Fast ends (SPATest.cpp:362-373) once both root searches are through.  p1, p2: the two tail
+// probabilities, read only when both searches converged; pn_in: the p-value without the adjustment.
+__device__ __forceinline__ double spa_two_roots(double p1, double p2, bool both_converged, double pn_in, bool &converged)
+{
+	converged = both_converged;
+	if (!both_converged) return pn_in;
+	const double pval = fabs(p1) + fabs(p2);
+	// :368-371: the cutoff doubles until |z| < cutoff, the roots do not change, so the loop always ends in pval_noadj
+	return (pval != 0 && pn_in / pval > 1000) ? pn_in : pval;
+}
+
 template <int K, int BLOCK, int INPUT>
 __global__ void __launch_bounds__(BLOCK)
 spa_kernel(RowsRef rr, DevModel md,
@@ -211,17 +222,12 @@ spa_kernel(RowsRef rr, DevModel md,
 			double k2r1, k2r2;
 			const double root1 = getroot_fast<BLOCK>(g_pos, g_neg, qtilde, NAmu, NAsigma, nnz, gl, ml, sh, conv1, k2r1);
 			const double root2 = getroot_fast<BLOCK>(g_pos, g_neg, qinv, NAmu, NAsigma, nnz, gl, ml, sh, conv2, k2r2);
+			double p1 = 0, p2 = 0;
 			if (conv1 && conv2) {
-				const double p1 = saddle_prob_fast<BLOCK>(root1, k2r1, qtilde, NAmu, NAsigma, nnz, gl, ml, sh);
-				const double p2 = saddle_prob_fast<BLOCK>(root2, k2r2, qinv, NAmu, NAsigma, nnz, gl, ml, sh);
-				pval = fabs(p1) + fabs(p2);
-				// SPATest.cpp:368-371: the cutoff doubles until |z| < cutoff, the
-				// roots do not change, so the loop always ends in pval_noadj
-				if (pval != 0 && pn_in / pval > 1000) pval = pn_in;
-			} else {
-				pval = pn_in;
-				converged = false;
+				p1 = saddle_prob_fast<BLOCK>(root1, k2r1, qtilde, NAmu, NAsigma, nnz, gl, ml, sh);
+				p2 = saddle_prob_fast<BLOCK>(root2, k2r2, qinv, NAmu, NAsigma, nnz, gl, ml, sh);
 			}
+			pval = spa_two_roots(p1, p2, conv1 && conv2, pn_in, converged);
 		}
 		if (pval == 0 && r.p_noadj > 0) { pval = r.p_noadj; converged = false; }
 		if (tid == 0) {

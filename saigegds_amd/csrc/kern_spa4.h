@@ -51,10 +51,7 @@
 // as a whole is ~2 % faster on two lanes (same box, C3: 2.55 -> 2.50 ms per step; K = 5: 3.42 -> 3.29).  With
 // many covariates a wave's state (c[K], a table row per carrier in flight) does not fit 168 registers at
 // three waves anyway: K = 13 ran 2.56 ms at 8 waves and 3.24 at 12.
-#ifndef SPA4_WAVES_LOWK
-#define SPA4_WAVES_LOWK 8
-#endif
-__host__ __device__ constexpr int spa4_waves(int K) { return K <= 8 ? SPA4_WAVES_LOWK : 8; }
+__host__ __device__ constexpr int spa4_waves(int) { return 8; }
 #define SPA4_NCA 12              /* cumulants carried for the variants of tier A (small g t: most carriers) */
 #define SPA4_NCB SPA4_NC         /* ... of tier B */
 #define SPA4_NSMAX (SPA4_NC + 5) /* partial sums per (variant, segment) of the wider tier */
@@ -204,13 +201,40 @@ __device__ __forceinline__ void spa4_queue_done(int *cursor)
 	}
 }
 
+// One carrier of a (variant, segment) into its sums: x = the carrier's table row (X row, then mu), G its dosage.
+// acc: 0 sum mu*G, 1 sum b, 2 sum max(adj,0), 3 sum min(adj,0), 4 sum adj*mu, 5 sum adj^2 mu(1-mu), 6.. kappa'_3..NC;
+// max |adj| apart.
+// History: a switch "no cumulant terms" (ablation bit 1) was a build option, not a run-time test:
+// tested at run time it is a scalar branch per carrier that cuts the carrier's arithmetic into three scheduling
+// regions (measured both ways: nothing, tools/README.md).  Commit 43cdecf is the last that has it.
+template <int K, int NC>
+__device__ __forceinline__ void spa4_carrier(const double *x, double G, const double (&c)[K], double inv, double ts,
+	double *acc, double &gmax)
+{
+	double bb = 0;
+#pragma unroll
+	for (int a = 0; a < K; a++) bb = fma(x[a], c[a], bb);
+	const double mui = x[K];
+	const double adj = (G - bb) * inv;
+	const double u = mui * (1 - mui);
+	acc[0] = fma(mui, G, acc[0]);
+	acc[1] += bb;
+	acc[2] += fmax(adj, 0.0); acc[3] += fmin(adj, 0.0);      // (two selects of a 64-bit pair each way cost seven instructions)
+	acc[4] = fma(adj, mui, acc[4]);
+	acc[5] = fma(adj * adj, u, acc[5]);
+	spa4_max_abs(gmax, adj);
+	spa4_cum_terms<NC>(adj * ts, u, 1 - 2 * mui, &acc[6]);
+}
+
 // One workgroup per CU.  Item = (sample segment, slice of SPA4_VPER flagged variants): the segment's X
 // rows and mu and the slice's parameters are staged in LDS; one wave per variant, a lane owns SEG/64
 // consecutive samples of the segment and walks its carriers in lock step with the other lanes.
+// History: the kernel took an argument of timing bits with wrong results (no row loads, no carrier work, everything
+// through the leftover queue; tools/README.md has what they measured).  Commit 43cdecf is the last that has them.
 template <int K, int NC>
 __global__ void __launch_bounds__(WAVE * spa4_waves(K))
 spa4_moments(RowsRef rr, DevModel md, int nseg, int tier, int btop, int v0, int vcap,
-	const SpaRec *__restrict__ recs, const int *__restrict__ counters, double *__restrict__ segpart, int abl, int *__restrict__ cursor)
+	const SpaRec *__restrict__ recs, const int *__restrict__ counters, double *__restrict__ segpart, int *__restrict__ cursor)
 {
 	constexpr int SEG = spa_seg(K), KP = (K + 2) & ~1, NS = NC + 5;
 	constexpr int LDW = SEG / 16 / WAVE > 0 ? SEG / 16 / WAVE : 1;     // dwords (of 16 samples) per lane
@@ -227,6 +251,8 @@ spa4_moments(RowsRef rr, DevModel md, int nseg, int tier, int btop, int v0, int 
 	// the (segment, slice) items in segment-major order, pulled off a queue (cursor[0]): the items differ in
 	// weight (carriers per slice) and a static share left workgroups idle behind the slowest; the workgroups
 	// running at any moment work on the same few segments, so the tables they restage come from L2
+	// (this prologue of an item is written out again in spa4_moments_ds: shared, it cost that kernel 19-38
+	// instructions and scalar spills, and this one scratch at sixteen cumulants)
 	const int vper = spa4_slice(nflag, nseg, gridDim.x, spa4_waves(K));
 	const int nslice = (nflag + vper - 1) / vper;
 	const int nitem = nseg * nslice;
@@ -237,7 +263,7 @@ spa4_moments(RowsRef rr, DevModel md, int nseg, int tier, int btop, int v0, int 
 	int samp0 = 0;                                                                // first sample of the lane
 	auto load_row = [&](int vl) -> uint4 {                                      // .x .. of the first LDW are used
 		uint4 w = make_uint4(0u, 0u, 0u, 0u);
-		if (mine && !(abl & 16)) {
+		if (mine) {
 			const uint8_t *p = rr.base + rr_piece(rr, (size_t)pj[vl], row_off >> 4) + (row_off & 15);
 			if (LDW == 4) w = *reinterpret_cast<const uint4 *>(p);
 			else if (LDW == 2) { const uint2 t = *reinterpret_cast<const uint2 *>(p); w.x = t.x; w.y = t.y; }
@@ -287,9 +313,7 @@ spa4_moments(RowsRef rr, DevModel md, int nseg, int tier, int btop, int v0, int 
 #pragma unroll
 			for (int a = 0; a < K; a++) c[a] = pd[(2 + a) * SPA4_VPER + vl];
 			const double *lut = pd + (2 + K) * SPA4_VPER + vl;       // dosage of code k at lut[k * VPER]
-			// 0 sum mu*G, 1 sum b, 2 sum max(adj,0), 3 sum min(adj,0), 4 sum adj*mu, 5 sum adj^2 mu(1-mu),
-			// 6.. kappa'_3..NC; max |adj| apart
-			double acc[NS - 1], gmax = 0;
+			double acc[NS - 1], gmax = 0;                            // spa4_carrier
 #pragma unroll
 			for (int a = 0; a < NS - 1; a++) acc[a] = 0;
 			// carrier masks: bit b of lo -> dword (b & 1), sample b >> 1 of it; hi the same for dwords 2, 3
@@ -298,7 +322,6 @@ spa4_moments(RowsRef rr, DevModel md, int nseg, int tier, int btop, int v0, int 
 				return (mine && k < LDW) ? nz_fields((w ^ zx) & keep_mask(N - samp0 - 16 * k)) : 0u;
 			};
 			uint32_t lo = nzm(wd0, 0) | (nzm(wd1, 1) << 1), hi = nzm(wd2, 2) | (nzm(wd3, 3) << 1);
-			if (abl & 4) lo = hi = 0;
 			// Software pipeline: the table row and the dosage of a lane's next carrier are read from
 			// LDS before the arithmetic of the current one, into the other of two register sets.  The reads
 			// are UNCONDITIONAL (a lane without a carrier left reads its first sample's row and uses nothing
@@ -325,34 +348,15 @@ spa4_moments(RowsRef rr, DevModel md, int nseg, int tier, int btop, int v0, int 
 				for (int a = 0; a <= K; a++) cr.x[a] = x[a];
 				cr.G = lut[code * SPA4_VPER];
 			};
-			auto work = [&](const Car &cr) {
-				double bb = 0;
-#pragma unroll
-				for (int a = 0; a < K; a++) bb = fma(cr.x[a], c[a], bb);
-				const double mui = cr.x[K], G = cr.G;
-				const double adj = (G - bb) * inv;
-				const double u = mui * (1 - mui);
-				acc[0] = fma(mui, G, acc[0]);
-				acc[1] += bb;
-				acc[2] += fmax(adj, 0.0); acc[3] += fmin(adj, 0.0);      // (two selects of a 64-bit pair each way cost seven instructions)
-				acc[4] = fma(adj, mui, acc[4]);
-				acc[5] = fma(adj * adj, u, acc[5]);
-				spa4_max_abs(gmax, adj);
-				// (ablation bit 1, "no cumulant terms", is a build option: tested at run time it is a scalar branch
-				// per carrier that cuts the carrier's arithmetic into three scheduling regions)
-#ifdef SPA4_ABLATE_TERMS
-				if (!(abl & 1))
-#endif
-				spa4_cum_terms<NC>(adj * ts, u, 1 - 2 * mui, &acc[6]);
-			};
+			auto work = [&](const Car &cr) { spa4_carrier<K, NC>(cr.x, cr.G, c, inv, ts, acc, gmax); };
 			// A lane owns 64 samples, so the lanes' carrier counts differ (binomial): walking them in lock
 			// step to the largest count would leave ~40 % of the lane-steps empty.  Instead: T =
 			// ceil(mean count) lock-step rounds, then whatever the busier lanes have left goes through
-			// the wave's LDS queue and is shared out evenly, 64 carriers a round.  (abl & 256: everything
-			// the queue holds goes through it -- measured, no faster: filling the queue costs what the
-			// idle lane-steps do.)
+			// the wave's LDS queue and is shared out evenly, 64 carriers a round.  (History: with no lock-step
+			// rounds, everything the queue holds going through it -- measured, no faster: filling the queue
+			// costs what the idle lane-steps do.)
 			const int ctot = wave_total_i(__popc(lo) + __popc(hi));
-			const int T = (abl & 256) ? max(0, (ctot - spa4_qcap(K) + WAVE - 1) / WAVE) : (ctot + WAVE - 1) / WAVE;
+			const int T = (ctot + WAVE - 1) / WAVE;
 			// exactly T fetches, none of them inside a branch of the loop body
 			Car ca, cb;
 			ca.ok = cb.ok = false;
@@ -444,7 +448,7 @@ spa4_moments_ds(const void *__restrict__ rows, size_t row_bytes, DevModel md, in
 	const int nitem = nseg * nslice;
 	__shared__ int sh_it;
 	int seg = -1;
-	for (;;) {
+	for (;;) {                               // (the prologue of an item as in spa4_moments)
 		__syncthreads();                     // the previous item's readers are done
 		if (tid == 0) sh_it = atomicAdd(cursor, 1);
 		__syncthreads();
@@ -496,27 +500,13 @@ spa4_moments_ds(const void *__restrict__ rows, size_t row_bytes, DevModel md, in
 			for (int j = 0; j < nstep; j++) {
 				const double G = gn;
 				if (j + 1 < nstep) gn = dosage(j + 1);
-				if (G != 0) {
-					const double *x = tab + (size_t)(j * WAVE + lane) * KP;
-					double bb = 0;
-#pragma unroll
-					for (int a = 0; a < K; a++) bb = fma(x[a], c[a], bb);
-					const double mui = x[K];
-					const double adj = (G - bb) * inv;
-					const double u = mui * (1 - mui);
-					acc[0] = fma(mui, G, acc[0]);
-					acc[1] += bb;
-					acc[2] += fmax(adj, 0.0); acc[3] += fmin(adj, 0.0);      // (two selects of a 64-bit pair each way cost seven instructions)
-					acc[4] = fma(adj, mui, acc[4]);
-					acc[5] = fma(adj * adj, u, acc[5]);
-					spa4_max_abs(gmax, adj);
-					spa4_cum_terms<NC>(adj * ts, u, 1 - 2 * mui, &acc[6]);
-				}
+				if (G != 0) spa4_carrier<K, NC>(tab + (size_t)(j * WAVE + lane) * KP, G, c, inv, ts, acc, gmax);
 			}
 			const int idx = wave_reduce_scatter(acc, lane);
 			gmax = wave_max_nonneg_to_last(gmax);
 			// [variant][segment][NS]: the sums of a (variant, segment) leave in one store, and spa4_solve reads a
-			// variant's segments as one contiguous run
+			// variant's segments as one contiguous run (written out here as in spa4_moments: as one function the
+			// store cost this kernel 1-8 instructions and two scalar spills)
 			const size_t base = ((size_t)(vb + vl) * nseg + seg) * NS;
 			if (!(lane & (NS - 1 > 16 ? 1 : 3)) && idx < NS - 1) segpart[base + idx] = acc[0];
 			if (lane == WAVE - 1) segpart[base + (NS - 1)] = gmax;
@@ -621,7 +611,8 @@ __device__ __forceinline__ void spa4_solve_one(const DevModel &md, int nseg, int
 	// Lanes 0 and 1 go on with identical values: each runs one of the two root searches (q and 2 m1 - q),
 	// lane 0 collects and writes.
 	if (lane > 1) return;
-	// scalars of saige_main.cpp:369-381
+	// scalars of saige_main.cpp:369-381 (written out again in spa5_kernel: filled through one struct, that kernel's
+	// 128-thread exact form took two registers more)
 	const double inv = 1 / sqrt(r.AC2);
 	double xmu_c = 0, xsum_c = 0;
 #pragma unroll
@@ -668,15 +659,8 @@ __device__ __forceinline__ void spa4_solve_one(const DevModel &md, int nseg, int
 		}
 		return;
 	}
-	double pval;
-	bool converged = true;
-	if ((st_mine & 2) && (st_other & 2)) {
-		pval = fabs(p_mine) + fabs(p_other);
-		if (pval != 0 && pn_in / pval > 1000) pval = pn_in;   // SPATest.cpp:368-371
-	} else {
-		pval = pn_in;
-		converged = false;
-	}
+	bool converged;
+	const double pval = spa_two_roots(p_mine, p_other, (st_mine & 2) && (st_other & 2), pn_in, converged);
 	spa_write_row(r, Tstat, var1, pval, converged, out8);
 }
 
@@ -741,17 +725,14 @@ __device__ __noinline__ int spa5_series_solve(const double *arg, const SpaRec *_
 	const double pn_in = arg[NC + 7], Tstat = arg[NC + 8], var1 = arg[NC + 9];
 	RootState s1, s2;
 	if (!spa4_root(S, xmax, qtilde, NAmu, NAsigma, s1) || !spa4_root(S, xmax, qinv, NAmu, NAsigma, s2)) return 0;
-	double pval;
-	bool converged = true;
-	if (s1.converged && s2.converged) {
-		const double p1 = lugannani_rice(s1.root, s1.Kcur, s1.K2cur, qtilde, NAmu, NAsigma);
-		const double p2 = lugannani_rice(s2.root, s2.Kcur, s2.K2cur, qinv, NAmu, NAsigma);
-		pval = fabs(p1) + fabs(p2);
-		if (pval != 0 && pn_in / pval > 1000) pval = pn_in;   // SPATest.cpp:368-371
-	} else {
-		pval = pn_in;
-		converged = false;
+	const bool both = s1.converged && s2.converged;
+	double p1 = 0, p2 = 0;
+	if (both) {
+		p1 = lugannani_rice(s1.root, s1.Kcur, s1.K2cur, qtilde, NAmu, NAsigma);
+		p2 = lugannani_rice(s2.root, s2.Kcur, s2.K2cur, qinv, NAmu, NAsigma);
 	}
+	bool converged;
+	const double pval = spa_two_roots(p1, p2, both, pn_in, converged);
 	const SpaRec rr = *rec;
 	spa_write_row(rr, Tstat, var1, pval, converged, out8);
 	return 1;
@@ -764,18 +745,11 @@ __device__ __noinline__ int spa5_series_solve(const double *arg, const SpaRec *_
 template <int BLOCK>
 __device__ __forceinline__ bool spa5_series(const double2 *__restrict__ glist, int nnz, double ts, double xmax,
 	double k1, double k2, double qtilde, double qinv, double NAmu, double NAsigma, double pn_in,
-	double Tstat, double var1, const SpaRec *__restrict__ rec, double *__restrict__ out8, double *sh, int *sh_flag, int *prof = nullptr)
+	double Tstat, double var1, const SpaRec *__restrict__ rec, double *__restrict__ out8, double *sh, int *sh_flag)
 {
 	constexpr int NC = SPA4_NCB;
 	double kp[NC - 1];                 // kappa'_3..NC, and max |adj| in the last slot
-#ifdef SPA5_PROF
-	long long tp_ = wall_clock64();
-#define SPA5_TS(ph) do { if (threadIdx.x == 0) { const long long now_ = wall_clock64(); atomicAdd(&prof[ph], (int)(now_ - tp_)); tp_ = now_; } } while (0)
-#else
-#define SPA5_TS(ph) do { } while (0)
-#endif
 	spa5_cum_sweep<BLOCK>(glist, nnz, ts, kp);
-	SPA5_TS(0);
 	// Only thread 0 needs the totals: a reduce-scatter inside each wave (wave_reduce_scatter: ~NC shuffles
 	// instead of 6 NC), the waves' partial sums through LDS, NC - 2 threads add them up
 	constexpr int NWV = BLOCK / WAVE;
@@ -798,7 +772,6 @@ __device__ __forceinline__ bool spa5_series(const double2 *__restrict__ glist, i
 		arg[threadIdx.x] = t;
 	}
 	__syncthreads();
-	SPA5_TS(1);
 	if (threadIdx.x == 0) {
 		for (int w = 0; w < NWV; w++) gmax = fmax(gmax, part[(NC - 2) * NWV + w]);
 		// the scalar part as a call: its registers (two root searches on sixteen cumulants) stay out of
@@ -808,7 +781,6 @@ __device__ __forceinline__ bool spa5_series(const double2 *__restrict__ glist, i
 		arg[NC + 7] = pn_in; arg[NC + 8] = Tstat; arg[NC + 9] = var1;
 		*sh_flag = spa5_series_solve(arg, rec, out8);
 	}
-	SPA5_TS(2);
 	__syncthreads();
 	const bool done = *sh_flag != 0;
 	__syncthreads();                   // sh and the flag are free again
@@ -820,24 +792,21 @@ __device__ __forceinline__ bool spa5_series(const double2 *__restrict__ glist, i
 // BLOCK: 512 threads per variant, or 128 where the packed row is short enough for four workgroups per CU
 // (small N: the kernel is bound by the number of variants in flight, not by the work in one).
 // Registers: the 512-thread form is two waves per SIMD at up to 256 registers -- one workgroup per CU then holds
-// the CU's whole register file while it waits on its ~10 dependent phases.  Capped at 128 (SPA5_REG_WAVES 4) half
+// the CU's whole register file while it waits on its ~10 dependent phases.  Capped at 128 (four waves per SIMD) half
 // of every register file would stay free for the other lane's small kernels, but the kernel spills and the
 // SPA stage alone goes from 1.26 to 1.65 ms (C3 2.24 -> 2.53-2.57 ms per step): measured, not adopted.
-#ifndef SPA5_REG_WAVES
-#define SPA5_REG_WAVES 2
-#endif
-#define SPA5_WAVES_PER_SIMD(BLOCK) ((BLOCK) == 512 ? SPA5_REG_WAVES : ((BLOCK) / 64 + 3) / 4)
-#ifdef SPA5_PROF   /* phase times of spa5_kernel in 10-ns ticks -> counters[8 + 8 MODE + phase] (diagnostic build only) */
-#define SPA5_T(ph) do { if (tid == 0) { const long long now_ = wall_clock64(); atomicAdd(&counters[8 + 8 * MODE + (ph)], (int)(now_ - tprev_)); tprev_ = now_; } } while (0)
-#else
-#define SPA5_T(ph) do { } while (0)
-#endif
+__host__ __device__ constexpr int spa5_waves_per_simd(int BLOCK) { return BLOCK == 512 ? 2 : (BLOCK / 64 + 3) / 4; }
+// force_exact (test hook "spa_exact"): MODE 0 hands every variant on to MODE 1.  scan_rows (test hook "spa_scan_rows"):
+// the block's carrier lists (rr.cptr) are not used, every variant scans its row as for row-major input.
+// History: force_exact also carried timing bits with wrong results (no list building, no exact sweeps), and a
+// diagnostic build summed clock stamps per phase into spare counters; tools/README.md has what both
+// showed.  Commit 43cdecf is the last that has them.
 template <int K, int INPUT, int MODE, int BLOCK>
-__global__ void __launch_bounds__(BLOCK, SPA5_WAVES_PER_SIMD(BLOCK))
+__global__ void __launch_bounds__(BLOCK, spa5_waves_per_simd(BLOCK))
 spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 	int *__restrict__ counters, const int *__restrict__ todo, int *__restrict__ todo_next, int *__restrict__ cursor,
 	int *__restrict__ fb_dense, uint8_t *__restrict__ scratch, double *__restrict__ out8, int force_dense, int force_exact,
-	size_t lds_row_bytes, int only, size_t wg_stride, int nslot)
+	size_t lds_row_bytes, bool scan_rows, size_t wg_stride, int nslot)
 {
 	constexpr int KP = (K + 2) & ~1, NW = BLOCK / WAVE;
 	extern __shared__ __attribute__((aligned(16))) uint8_t fill_smem[];
@@ -848,7 +817,6 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 	__shared__ int sh_vi, sh_v;
 	__shared__ SpaRec sh_rec;
 	const int N = md.N, tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
-	// only = 2: the block's carrier lists (rr.cptr) are not used (diagnostic: every variant scans its row); 0: used
 	double2 *glist = reinterpret_cast<double2 *>(scratch + (size_t)blockIdx.x * wg_stride);
 	uint32_t *ilist = reinterpret_cast<uint32_t *>(glist + (((size_t)N + 63) & ~(size_t)63));
 	// length of the list: counters[3] / [4], or a copy taken when the list was complete (a launch that runs
@@ -877,9 +845,6 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 		__syncthreads();
 		const int vi = sh_vi;
 		if (vi >= 2 * ntodo) break;
-#ifdef SPA5_PROF
-		long long tprev_ = wall_clock64();
-#endif
 		const bool big_round = vi < ntodo;
 		const int v = sh_v;
 		const SpaRec &r = sh_rec;
@@ -889,7 +854,7 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 		const double lut0 = r.lut[0], lut1 = r.lut[1], lut2 = r.lut[2], lut3 = r.lut[3];
 		// The block's carrier list of the variant, when it has one for this orientation: sample | code << 30 in
 		// ascending order, r.nnz entries -- what the three phases below build from the row otherwise.
-		const bool listed = INPUT == IN_2BIT && only != 2 && rr.cptr != nullptr && rr.corient[r.j] == (r.minus ? 2 : 1);
+		const bool listed = INPUT == IN_2BIT && !scan_rows && rr.cptr != nullptr && rr.corient[r.j] == (r.minus ? 2 : 1);
 		const uint32_t *il = listed ? rr.cidx + rr.cptr[r.j] : ilist;
 		int nnz = listed ? r.nnz : 0;
 		if (!listed) {
@@ -910,7 +875,6 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 				}
 				__syncthreads();
 			}
-			SPA5_T(0);
 			auto masks = [&](int p, uint32_t (&ww)[4], uint32_t (&z)[4]) -> int {
 				int cnt = 0;
 				if (INPUT == IN_2BIT) {
@@ -941,7 +905,6 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 			int o_w = 0;
 	#pragma unroll
 			for (int w = 0; w < NW; w++) { if (w < wid) o_w += shi[w]; nnz += shi[w]; }
-			SPA5_T(1);
 			for (int it = 0; it < per; it += WAVE) {
 				uint32_t ww[4], z[4];
 				const int p = wid * per + it + lane;
@@ -978,7 +941,6 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 				}
 			}
 			__syncthreads();                         // publishes the index list to the workgroup
-			SPA5_T(2);
 		}
 		// ---- (adj, mu) list + carrier sums (kern_spa2.h)
 		const double inv = 1 / sqrt(r.AC2);
@@ -989,7 +951,7 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 		// (UNG independent index reads, then UNG independent row gathers per thread and step: the loop is
 		// bound by the two global latencies in a row, not by its arithmetic)
 		constexpr int UNG = K <= 4 ? 4 : 2;
-		for (int k0 = tid; k0 < ((force_exact & 128) ? 0 : nnz); k0 += UNG * BLOCK) {
+		for (int k0 = tid; k0 < nnz; k0 += UNG * BLOCK) {
 			uint32_t e[UNG];
 			double xv[UNG][KP];
 #pragma unroll
@@ -1024,8 +986,7 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 			}
 		}
 		block_sum<6, BLOCK>(a6, sh);        // its barriers also publish the list
-		SPA5_T(3);
-		// ---- scalars of saige_main.cpp:369-381, then Saddle_Prob_Fast
+		// ---- scalars of saige_main.cpp:369-381 (as in spa4_solve_one; see there), then Saddle_Prob_Fast
 		double xmu_c = 0, xsum_c = 0;
 #pragma unroll
 		for (int a = 0; a < K; a++) { xmu_c = fma(md.Xmu[a], c[a], xmu_c); xsum_c = fma(md.Xsum[a], c[a], xsum_c); }
@@ -1050,11 +1011,10 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 			const double NAmu = m1 - a6[4], NAsigma = var2 - a6[5];
 			if (MODE == 0) {
 				// the series: one sweep over the list instead of one per Newton step
-				if ((force_exact & 1) || !spa5_series<BLOCK>(glist, nnz, r.tscale, md.spa_xmax, a6[4], a6[5], qtilde, qinv, NAmu, NAsigma,
-						pn_in, Tstat, var1, &sh_rec, out8, sh, &sh_flag, counters + 13)) {
+				if (force_exact || !spa5_series<BLOCK>(glist, nnz, r.tscale, md.spa_xmax, a6[4], a6[5], qtilde, qinv, NAmu, NAsigma,
+						pn_in, Tstat, var1, &sh_rec, out8, sh, &sh_flag)) {
 					if (tid == 0) todo_next[atomicAdd(&counters[4], 1)] = v;     // on to the exact exp/log sweeps
 				}
-				SPA5_T(4);
 				continue;
 			}
 			RootState s1, s2;
@@ -1075,14 +1035,16 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 				}
 				block_sum<6, BLOCK>(sv, sh);
 			};
-			while ((s1.active || s2.active) && !(force_exact & 64)) {
+			while (s1.active || s2.active) {
 				const bool a1 = s1.active, a2 = s2.active, k1w = s1.want_k, k2w = s2.want_k;
 				double sv[6];
 				sweep(a1, a2, k1w, k2w, s1.tnew, s2.tnew, sv);
 				if (a1) root_feed(s1, sv[0], sv[1], NAmu, NAsigma, sv[2], k1w);
 				if (a2) root_feed(s2, sv[3], sv[4], NAmu, NAsigma, sv[5], k2w);
 			}
-			if (s1.converged && s2.converged) {
+			const bool both = s1.converged && s2.converged;
+			double p1 = 0, p2 = 0;
+			if (both) {
 				if (!(s1.k_ok && s2.k_ok)) {
 					// a search ended at a point evaluated without Korg (root_step's guess was wrong)
 					double sv[6];
@@ -1090,16 +1052,11 @@ spa5_kernel(RowsRef rr, DevModel md, const SpaRec *__restrict__ recs,
 					if (!s1.k_ok) s1.Kcur = sv[2];
 					if (!s2.k_ok) s2.Kcur = sv[5];
 				}
-				const double p1 = lugannani_rice(s1.root, s1.Kcur, s1.K2cur, qtilde, NAmu, NAsigma);
-				const double p2 = lugannani_rice(s2.root, s2.Kcur, s2.K2cur, qinv, NAmu, NAsigma);
-				pval = fabs(p1) + fabs(p2);
-				if (pval != 0 && pn_in / pval > 1000) pval = pn_in;   // SPATest.cpp:368-371
-			} else {
-				pval = pn_in;
-				converged = false;
+				p1 = lugannani_rice(s1.root, s1.Kcur, s1.K2cur, qtilde, NAmu, NAsigma);
+				p2 = lugannani_rice(s2.root, s2.Kcur, s2.K2cur, qinv, NAmu, NAsigma);
 			}
+			pval = spa_two_roots(p1, p2, both, pn_in, converged);
 		}
 		if (tid == 0) spa_write_row(r, Tstat, var1, pval, converged, out8);
-		SPA5_T(5);
 	}
 }

@@ -346,7 +346,7 @@ def _scan_block(sc, blk, m):
 def test_block_carrier_lists_equal_row_scans():
     """Resident genotype blocks list the carriers of the rare variants (both orientations: 10 % of the synthetic
     variants have the alt allele as the major one); the per-variant SPA kernels walk those lists.  Same rows when
-    the lists are ignored ("spa_abl" 512: every variant scans its row), from the row-major call (which never has
+    the lists are ignored ("spa_scan_rows": every variant scans its row), from the row-major call (which never has
     lists), when the block's list is too small for all of them (clist_avg: the later variants go unlisted), and
     through the exact sweeps."""
     from saigegds_amd._lib import Block
@@ -359,10 +359,10 @@ def test_block_carrier_lists_equal_row_scans():
         base, valid = _scan_block(sc, blk, 1200)
         assert sc.stats()["n_spa"] > 30
         assert_table_close(base, valid, ref, ref_valid, what="carrier lists")
-        sc.set_option("spa_abl", 512)
+        sc.set_option("spa_scan_rows", 1)
         rows, _ = _scan_block(sc, blk, 1200)
         np.testing.assert_allclose(rows[v][:, 3:7], base[v][:, 3:7], rtol=1e-11)
-        sc.set_option("spa_abl", 0)
+        sc.set_option("spa_scan_rows", 0)
         direct, valid = sc.scan_2bit(packed)
         assert_table_close(direct, valid, ref, ref_valid, what="row-major call")
         np.testing.assert_allclose(direct[v][:, 3:7], base[v][:, 3:7], rtol=1e-11)

@@ -83,7 +83,7 @@ def test_series_tiers_against_the_oracle(n, m, k):
 def test_series_tiers_from_a_resident_block(k):
     """The same rows resident in a Block: the cumulant pass reads block rows, and spa5_kernel walks the block's carrier
     lists of up to 8192 entries (those over SPA5_BIG = 2048 in its first round) -- or scans the rows where the lists
-    are ignored ("spa_abl" 512) or too small for the later variants (clist_avg)."""
+    are ignored ("spa_scan_rows") or too small for the later variants (clist_avg)."""
     from saigegds_amd._lib import Block
     n, m = S.N_SERIES, 96
     sm, packed, ref, ref_valid, nflag = _case(n, m, k)
@@ -103,9 +103,9 @@ def test_series_tiers_from_a_resident_block(k):
         _check(base, valid, ref, ref_valid, what)
         assert st["n_spa"] == nflag, (what, st, nflag)
         _same(base, direct, ref_valid, what + " against the row-major call")
-        sc.set_option("spa_abl", 512)
+        sc.set_option("spa_scan_rows", 1)
         out, valid = _scan_block(sc, blk, m)
-        sc.set_option("spa_abl", 0)
+        sc.set_option("spa_scan_rows", 0)
         _check(out, valid, ref, ref_valid, what + ", lists ignored")
         _same(out, direct, ref_valid, what + ", lists ignored, against the row-major call")
         # 300 entries per variant: 28 800 in all, and the rare rows have 300 .. 6 700 carriers each

@@ -69,7 +69,7 @@ def test_twelve_fragments_block_and_rows_give_the_same_table():
         sc.load_block(blk, packed)
         o2 = torch.full((700, 8), -1.0, dtype=torch.float64, device=dev)
         v2 = torch.zeros(700, dtype=torch.uint8, device=dev)
-        sc.set_option("spa_abl", 512)            # the SPA kernels scan the rows, as the row-major call does
+        sc.set_option("spa_scan_rows", 1)         # the SPA kernels scan the rows, as the row-major call does
         sc.scan_block(blk, o2.data_ptr(), v2.data_ptr())
         sc.sync()
     assert np.array_equal(valid, v2.cpu().numpy())
