@@ -492,6 +492,27 @@ int sgx_collapse_2bit_dev(sgx_handle *h, const uint8_t *packed_dev, size_t bytes
  *                       succeeds and does nothing.  A NULL handle, block or buffer, a twin handle, a quantitative-trait
  *                       handle, maxit < 1, nothing loaded, an index outside the loaded rows or a block / handle mismatch
  *                       returns SGX_EINVAL and launches nothing; handle and block stay usable.
+ *   sgx_ds_block_collapse  the pseudo-variants of sgx_collapse_2bit for groups of resident rows (not in the
+ *                       reference).  Group g has the entries [grp_ptr[g], grp_ptr[g+1]) = rows var_idx[e] of the block,
+ *                       in [0, rows loaded), each with a byte flip[e]; HOST tables.  Its row holds, per sample,
+ *                           top = 0;  for every entry: v = missing(x) ? 0 : (flip[e] ? 2 - x : x);  if (v > top) top = v
+ *                       with x = row var_idx[e] at that sample: u8 rows in integer arithmetic (0xFF missing; a value
+ *                       above 2 in a flipped row is negative and never enters), rows held as doubles (i32 and f64
+ *                       blocks) with one rounded subtraction (non-finite missing; negative values, -0.0 and NaN never
+ *                       enter) -- a strict maximum from +0.0, so the order of the entries and repeats change no bit, and
+ *                       a group's row depends on its entries' rows and flips alone.  A row of hard calls gives the row
+ *                       of sgx_collapse_2bit.  A group of 0 entries gives a row of zeros; no value of a pseudo-row is
+ *                       missing.  The n_groups rows are appended to the block in its resident form (rows loaded += n_groups;
+ *                       the next load resets the block) and are rows like any other to every sgx_dsblock_* /
+ *                       sgx_ds_block_* entry from then on.  n_valid, sum, sum_trunc [n_groups]: what sgx_dsblock_load
+ *                       returns for such rows (the same kernel); out8 [n_groups * 8], valid [n_groups]: what
+ *                       sgx_dsblock_scan returns for a block of exactly these rows (the same launches); out_rows (may be
+ *                       NULL): the rows themselves, n_groups * n_samp bytes (u8) or doubles.  sgx_stats after the call
+ *                       are the scan's, with ms_kernel the time of the collapse kernel alone.  n_groups = 0 succeeds and
+ *                       does nothing.  A NULL handle, block or buffer (but out_rows), a twin handle, nothing loaded,
+ *                       grp_ptr[0] != 0 or a descending grp_ptr, an index outside the loaded rows, more rows than the
+ *                       block was created for, or a block / handle mismatch returns SGX_EINVAL and launches nothing;
+ *                       handle and block stay usable.
  * All of them are synchronous; block and handle must be on the same device and have the same n_samp. */
 #define SGX_DS_U8  0
 #define SGX_DS_I32 1
@@ -505,6 +526,9 @@ int  sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosage, size_t 
 int  sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const void *raw, int cls, size_t n_file_samp,
 	double scale, double offset, const int32_t *sel, size_t n_variants,
 	int32_t *n_valid, double *sum, int64_t *sum_trunc);
+int  sgx_ds_block_collapse(sgx_handle *h, sgx_dsblock *b, size_t n_groups, const int64_t *grp_ptr,
+	const int32_t *var_idx, const uint8_t *flip, int32_t *n_valid, double *sum, int64_t *sum_trunc,
+	double *out8, uint8_t *valid, void *out_rows);
 int  sgx_ds_block_skat(sgx_handle *h, const sgx_dsblock *b, size_t n_units, const int64_t *unit_ptr,
 	const int32_t *var_idx, const uint8_t *flip, const double *mean, double *score, double *cov);
 int  sgx_ds_block_cond_set(sgx_handle *h, const sgx_dsblock *b, size_t n_cond, const int32_t *var_idx,

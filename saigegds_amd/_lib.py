@@ -211,6 +211,7 @@ def _abi():
         "sgx_skato_spectra": (ci, [vp, sz, vp, vp, sz, vp, vp, vp]),
         "sgx_collapse_2bit": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
         "sgx_collapse_2bit_dev": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
+        "sgx_ds_block_collapse": (ci, [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
 
 
@@ -356,6 +357,7 @@ class Scanner(_Handle):
     """One model resident on one GPU (an ``sgx_handle``)."""
 
     _free = "sgx_free"
+    ds_collapse = True      # its dosage blocks have ``collapse``: what ``collapse_mac=`` on dosage input asks of a scanner class
 
     def __init__(self, sm, device: int = 0):
         L = load()
@@ -776,6 +778,23 @@ class DosageBlock(_Handle):
                                          flip.ctypes.data, nc, w.ctypes.data, mw.ctypes.data, out.ctypes.data,
                                          valid.ctypes.data))
         return out, valid
+
+    def collapse(self, grp_ptr, var_idx, flip, return_rows: bool = False):
+        """One pseudo-variant per group of resident rows (CSR ``grp_ptr`` / ``var_idx`` over the block's rows, one flip
+        byte per entry; ``sgx_ds_block_collapse``): per sample the largest minor-allele dosage over the
+        group's entries (2 - x where ``flip``, 0 where missing), appended to the block as rows ``n_variants ..`` in the
+        block's resident form -> (n_valid, sum, sum_trunc: what ``load`` returns for them; out [groups, 8], valid: what
+        ``scan`` returns for them[; rows [groups, N]: uint8 for a uint8 block, else float64])."""
+        flip = np.ascontiguousarray(flip, dtype=np.uint8)
+        grp_ptr, var_idx, ng, _, _ = _unit_args("DosageBlock.collapse", grp_ptr, var_idx, [(flip, ())])
+        nv, sm, st = np.empty(ng, dtype=np.int32), np.empty(ng, dtype=np.float64), np.empty(ng, dtype=np.int64)
+        out, valid = self._sc._out(ng)
+        rows = np.empty((ng, self.n), dtype=np.uint8 if self.dtype == np.uint8 else np.float64) if return_rows else None
+        check(self._L.sgx_ds_block_collapse(self._sc._h, self._b, ng, grp_ptr.ctypes.data, var_idx.ctypes.data,
+                                            flip.ctypes.data, nv.ctypes.data, sm.ctypes.data, st.ctypes.data,
+                                            out.ctypes.data, valid.ctypes.data, None if rows is None else rows.ctypes.data))
+        self.n_variants += ng
+        return (nv, sm, st, out, valid, rows) if return_rows else (nv, sm, st, out, valid)
 
     def skat(self, unit_ptr, var_idx, flip, mean):
         """Score statistics and their covariance per unit (CSR over the block's rows; per entry ``flip`` and the mean

@@ -297,23 +297,29 @@ def _dosage_rows(pr: _Prepared, used, stored, budget, kmat=None):
     variant that two batches share (sliding windows) is loaded in both.  ``skat`` is None where the block has none.
     ``kmat`` (as for ``_packed_rows``): ``skat`` is the block's ``skat_kmat`` (``sgx_ds_block_skat_kmat``) on one operator
     for all batches; a scanner without ``dosage_block`` or a block without ``skat_kmat`` is refused before any row is
-    read."""
+    read.  With pr.collapse_mac every unit of a batch counts one more resident row, its pseudo-variant, and the block has
+    room for them after the batch's own rows (``collapse``: the block's, ``sgx_ds_block_collapse``); a block without
+    ``collapse`` is refused before any row is read."""
     read_rows, dtype = pr.inp.dosage_reader(stored), pr.inp.ds_dtype
     row_bytes = ds_row_bytes(dtype, pr.sm.n)
+    extra = 0 if math.isnan(pr.collapse_mac) else 1                # resident rows a unit adds of its own: its pseudo-variant
     batches, cur, seen = [], [], set()
     for u, r in enumerate(pr.index):
         new = set(r.tolist()) - seen
-        if cur and (len(seen) + len(new)) * row_bytes > budget:
+        if cur and (len(seen) + len(new) + extra * (len(cur) + 1)) * row_bytes > budget:
             batches.append(cur)
             cur, seen, new = [], set(), set(r.tolist())
         cur.append(u)
         seen |= new
     batches.append(cur)
     cap = max(np.unique(np.concatenate([pr.index[u] for u in bt])).size for bt in batches)
+    cap += extra * max(len(bt) for bt in batches)
     if kmat is not None and not hasattr(pr.sc, "dosage_block"):
         raise NotImplementedError(NO_DOSAGE_KMAT.format("SKAT"))
     with contextlib.ExitStack() as stack:
         blk = stack.enter_context(pr.sc.dosage_block(dtype, cap))
+        if extra and not hasattr(blk, "collapse"):
+            raise NotImplementedError(NO_DOSAGE_COLLAPSE)
 
         def load(bv):
             n, s, st = load_rows(blk, read_rows(used[bv] - 1))
@@ -330,11 +336,12 @@ def _dosage_rows(pr: _Prepared, used, stored, budget, kmat=None):
                 raise NotImplementedError(NO_DOSAGE_KMAT.format("SKAT"))
             op = stack.enter_context(kmat.operator(pr.sc))
             skat = lambda *a: blk.skat_kmat(op, *a, *kmat.args)      # noqa: E731
-        yield SimpleNamespace(batches=batches, load=load, burden=burden, skat=skat, collapse=None)
+        yield SimpleNamespace(batches=batches, load=load, burden=burden, skat=skat, collapse=getattr(blk, "collapse", None))
 
 
 SkatStep = collections.namedtuple("SkatStep", "kept unit_ptr var_idx flip mean score cov n_iter")
 NO_DOSAGE_SKAT = "SKAT on dosage input is not implemented."
+NO_DOSAGE_COLLAPSE = "'collapse_mac' on dosage input needs a dosage block with collapse."
 
 
 def skat_step(pr: _Prepared, skat, rows, bv) -> SkatStep:
@@ -457,7 +464,8 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
     """Common head of the set-test drivers (R/assoc_aggregate.r:55-150): checks, sample matching, the model, the scanner
     and the rows backend of the input (and what the reference prints about the units).  Nothing has gone to the device
     yet: ``_run`` does that.  ``collapse_mac`` (SKAT and SKAT-O; what ``check_collapse_mac`` returned)
-    other than NaN needs hard calls: dosage input is refused here, before the scanner is made."""
+    other than NaN on dosage input needs a scanner whose dosage blocks collapse: the factory (``Scanner`` when None) must
+    be a class that says so (``ds_collapse = True``); anything else is refused here, before the scanner is made."""
     if verbose:
         print(what)
     pr = _Prepared(_Units(units), _check_beta(wbeta), collapse_mac=collapse_mac)
@@ -468,7 +476,9 @@ def _prepare(gdsfile, modobj, units, wbeta, spa_pval, var_ratio, verbose, what, 
     no_loco(mod, what.rstrip(":"))
     pr.inp = inp = reduce_hard_calls(open_scan_input(gdsfile, mod, dsnode, verbose))
     if inp.kind != "packed" and not math.isnan(pr.collapse_mac):
-        raise NotImplementedError("'collapse_mac' on dosage input is not implemented.")
+        fac = Scanner if scanner_factory is None else scanner_factory
+        if not (isinstance(fac, type) and getattr(fac, "ds_collapse", False)):
+            raise NotImplementedError("'collapse_mac' on dosage input is not implemented.")
     used = np.unique(np.concatenate(pr.units.index))
     if used.size == 0 or used.min() < 1 or used.max() > inp.n_var:
         raise ValueError("No variant in the genotypic data set!")

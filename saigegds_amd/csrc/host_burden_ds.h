@@ -58,20 +58,21 @@ static int dsblock_check(sgx_handle *h, const sgx_dsblock *b, const char *who)
 	return SGX_OK;
 }
 
-// ds_stats_kernel on the M rows just put into the block, the counts to the caller; the block is loaded when they are back
-static int dsblock_counts(sgx_handle *h, sgx_dsblock *b, size_t M, int32_t *n_valid, double *sum, int64_t *sum_trunc)
+// ds_stats_kernel on the m rows just put into the block from row `first` on, their counts to the caller; the block holds
+// first + m rows when they are back
+static int dsblock_counts(sgx_handle *h, sgx_dsblock *b, size_t first, size_t m, int32_t *n_valid, double *sum, int64_t *sum_trunc)
 {
 	with_ds_rows(b->dtype, b->rows.p, [&](auto *rows, auto t) {
-		hipLaunchKernelGGL((ds_stats_kernel<decltype(t)>), dim3((unsigned)M), dim3(256), 0, h->stream,
-			rows, b->N, b->d_nv, b->d_sum, b->d_trunc);
+		hipLaunchKernelGGL((ds_stats_kernel<decltype(t)>), dim3((unsigned)m), dim3(256), 0, h->stream,
+			rows + first * (size_t)b->N, b->N, b->d_nv.p + first, b->d_sum.p + first, b->d_trunc.p + first);
 	});
 	HIPCHK(hipGetLastError());
 	static_assert(sizeof(long long) == sizeof(int64_t), "sum_trunc");
-	HIPCHK(hipMemcpyAsync(n_valid, b->d_nv, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(hipMemcpyAsync(sum, b->d_sum, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-	HIPCHK(hipMemcpyAsync(sum_trunc, b->d_trunc, M * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(n_valid, b->d_nv.p + first, m * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(sum, b->d_sum.p + first, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(sum_trunc, b->d_trunc.p + first, m * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(hipStreamSynchronize(h->stream));
-	b->M = M;
+	b->M = first + m;
 	return SGX_OK;
 }
 
@@ -108,7 +109,7 @@ extern "C" int sgx_dsblock_load(sgx_handle *h, sgx_dsblock *b, const void *dosag
 			});
 		if (rc) return rc;
 	}
-	return dsblock_counts(h, b, M, n_valid, sum, sum_trunc);
+	return dsblock_counts(h, b, 0, M, n_valid, sum, sum_trunc);
 }
 
 // The same block from packed-real rows as the file stores them (kern_unpack.h): raw chunks land in the pipeline's two
@@ -139,7 +140,30 @@ extern "C" int sgx_ds_block_load_packed(sgx_handle *h, sgx_dsblock *b, const voi
 			return launch_unpack(h->stream, src, h->pipe_raw[k], b->N, m, reinterpret_cast<double *>(b->rows + off * b->row_bytes));
 		});
 	if (rc) return rc;
-	return dsblock_counts(h, b, M, n_valid, sum, sum_trunc);
+	return dsblock_counts(h, b, 0, M, n_valid, sum, sum_trunc);
+}
+
+// Single-variant test of the m resident rows from row `first` on, in scan_chunk's chunks, on a lane that begin_call
+// made ready: a call's launches depend on m alone, not on where the rows lie in the block
+static int dsblock_scan_rows(sgx_handle *h, const sgx_dsblock *b, size_t first, size_t m, double *out8, uint8_t *valid)
+{
+	const size_t N = (size_t)b->N;
+	const size_t per_row = b->dtype == SGX_DS_U8 ? N : b->dtype == SGX_DS_I32 ? N * (sizeof(int32_t) + sizeof(double)) : N * sizeof(double);
+	const size_t chunk = scan_chunk(h, per_row, m);
+	int rc = ensure_stage(h, 0, chunk);
+	if (rc) return rc;
+	rc = ensure_recs(h, chunk);
+	if (rc) return rc;
+	sgx_stats total{};
+	for (size_t off = 0; off < m; off += chunk) {
+		const size_t mc = std::min(chunk, m - off);
+		const uint8_t *rows = b->rows + (first + off) * b->row_bytes;
+		if (b->dtype == SGX_DS_U8) rc = scan_staged<IN_U8>(h, rows, b->row_bytes, mc, out8 + off * 8, valid + off, total);
+		else rc = scan_staged<IN_F64>(h, rows, b->row_bytes, mc, out8 + off * 8, valid + off, total);
+		if (rc) return rc;
+	}
+	h->stats = total;
+	return SGX_OK;
 }
 
 // Single-variant test of every resident row, in scan_chunk's chunks: results equal sgx_scan_u8 / _i32 / _f64 on rows
@@ -154,23 +178,7 @@ extern "C" int sgx_dsblock_scan(sgx_handle *h, const sgx_dsblock *b, double *out
 	if (b->M == 0) return fail(SGX_EINVAL, "sgx_dsblock_scan: nothing loaded");
 	rc = begin_call(h);
 	if (rc) return rc;
-	const size_t N = (size_t)b->N, M = b->M;
-	const size_t per_row = b->dtype == SGX_DS_U8 ? N : b->dtype == SGX_DS_I32 ? N * (sizeof(int32_t) + sizeof(double)) : N * sizeof(double);
-	const size_t chunk = scan_chunk(h, per_row, M);
-	rc = ensure_stage(h, 0, chunk);
-	if (rc) return rc;
-	rc = ensure_recs(h, chunk);
-	if (rc) return rc;
-	sgx_stats total{};
-	for (size_t off = 0; off < M; off += chunk) {
-		const size_t m = std::min(chunk, M - off);
-		const uint8_t *rows = b->rows + off * b->row_bytes;
-		if (b->dtype == SGX_DS_U8) rc = scan_staged<IN_U8>(h, rows, b->row_bytes, m, out8 + off * 8, valid + off, total);
-		else rc = scan_staged<IN_F64>(h, rows, b->row_bytes, m, out8 + off * 8, valid + off, total);
-		if (rc) return rc;
-	}
-	h->stats = total;
-	return SGX_OK;
+	return dsblock_scan_rows(h, b, 0, b->M, out8, valid);
 }
 
 template <typename T>

@@ -91,6 +91,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_exact.h"
 #include "kern_eig.h"
 #include "kern_collapse.h"
+#include "kern_collapse_ds.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -121,3 +122,4 @@ static int fail(int code, const char *fmt, ...)
 #include "host_exact.h"
 #include "host_skato.h"
 #include "host_collapse.h"
+#include "host_collapse_ds.h"

@@ -19,8 +19,9 @@ Hard calls are one batch: one ``sgx_scan_2bit`` and one ``sgx_skat_2bit`` for al
 that fit the device: the rows of a batch go to a resident ``DosageBlock`` once, ``blk.scan()`` gives the per-variant
 table and ``blk.skat()`` (``sgx_ds_block_skat``) ``S`` and ``Phi`` of the batch's units -- with ``grm_mat=``
 ``blk.skat_kmat()`` (``sgx_ds_block_skat_kmat``) on one operator for all batches.  With ``collapse_mac=``
-(hard calls only) ``aggregate.collapse_step`` runs between steps 1 and 2: one ``sgx_collapse_2bit`` makes a
-pseudo-variant of every unit's ultra-rare variants, one more ``sgx_scan_2bit`` scans them.
+ ``aggregate.collapse_step`` runs between steps 1 and 2: one ``sgx_collapse_2bit`` makes a pseudo-variant
+of every unit's ultra-rare variants, one more ``sgx_scan_2bit`` scans them; on dosage input one ``blk.collapse()``
+(``sgx_ds_block_collapse``) per batch appends them to the resident block, counted and scanned.
 """
 from __future__ import annotations
 
@@ -266,12 +267,16 @@ def seqAssocGLMM_spaSKAT(gdsfile, modobj, units, wbeta=AggrParamBeta, dsnode: st
     (``ValueError``).
 
     ``collapse_mac`` (NaN: off, the default; else a number of at least 1, ``ValueError`` below that and ``TypeError`` for
-    what is no number; hard calls only: dosage input is refused with ``NotImplementedError`` before any row is read, and
-    so is a scanner without ``collapse_2bit``, which is closed): the step of SAIGE-GENE+, DESIGN.md 8m.  Of a unit's
-    variants in the test those with ``mac <= collapse_mac`` are replaced by one pseudo-variant, placed last: per sample
-    the largest minor-allele dosage over them (the code, 2 - code where the scan flips the row, 0 where missing), made
-    for all units by one ``sgx_collapse_2bit`` and then scanned, weighted by its own maf and entered into ``S``, ``Phi``
-    (or ``Phi^K``) and the SPA scaling like any variant.  ``n.var`` counts the entries after collapsing; two more
+    what is no number; a scanner without ``collapse_2bit`` is refused with ``NotImplementedError`` and closed): the step
+    of SAIGE-GENE+, DESIGN.md 8m.  Of a unit's variants in the test those with ``mac <= collapse_mac`` are replaced by
+    one pseudo-variant, placed last: per sample the largest minor-allele dosage over them (the code, 2 - code where the
+    scan flips the row, 0 where missing), made for all units by one ``sgx_collapse_2bit`` and then scanned, weighted by
+    its own maf and entered into ``S``, ``Phi`` (or ``Phi^K``) and the SPA scaling like any variant.  On dosage input
+    ``mac`` is the real ``min(s, 2n - s)``, the maximum is over the dosages themselves (2 - x where flipped, 0 where
+    missing; strictly ``v > top`` from +0.0) and the pseudo-rows are appended to the resident block by one
+    ``sgx_ds_block_collapse`` per batch, each unit counting one more resident row against ``ds_budget``; that needs a
+    scanner class that declares ``ds_collapse`` (``Scanner`` does): any other ``scanner_factory`` is refused with
+    ``NotImplementedError`` before a scanner is made, a dosage block without ``collapse`` before any row is read.  ``n.var`` counts the entries after collapsing; two more
     columns appear: ``n.collapsed`` (the variants replaced) and ``mac.collapsed`` (the pseudo-variant's minor allele
     count, NaN where nothing was replaced).  The summary columns keep describing the unit's original variants."""
     pr = prepare_skat("SAIGE SKAT analysis:", gdsfile, modobj, units, wbeta, dsnode, spa_pval, var_ratio, parallel, verbose,

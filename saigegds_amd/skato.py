@@ -249,8 +249,8 @@ def seqAssocGLMM_spaSKATO(gdsfile, modobj, units, wbeta=AggrParamBeta, rho=RHO_D
     ``pval.SKAT`` (``seqAssocGLMM_spaSKAT``'s ``pval``), ``pval.burden`` (the chi-square of ``(sum s)^2`` on one degree of
     freedom under the same covariance), ``rho.min`` and ``Q`` (SKAT's, ``sum w_j^2 S_j^2``), with the suffix ``.b<a>_<b>``
     where there is more than one weight set.  A unit with no variant left gives NaN.  ``collapse_mac``: as for
-    ``seqAssocGLMM_spaSKAT`` (the same code), with its columns ``n.collapsed`` and ``mac.collapsed``
-    after ``n.var``."""
+    ``seqAssocGLMM_spaSKAT`` (the same code; hard calls and dosage input alike), with its columns
+    ``n.collapsed`` and ``mac.collapsed`` after ``n.var``."""
     from ._lib import SKATO_MAX_M
     rho = check_rho(rho)
     pr = prepare_skat("SAIGE SKAT-O analysis:", gdsfile, modobj, units, wbeta, dsnode, spa_pval, var_ratio, parallel, verbose,
