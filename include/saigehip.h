@@ -583,6 +583,42 @@ int sgx_quantize_packed(const void *raw, int cls, size_t n_file_samp, double sca
 	uint8_t *packed_out, size_t out_stride,
 	int32_t *n_valid, int32_t *allele_sum, int32_t *ds_valid, double *ds_sum);
 
+/* Pairwise LD of 2-bit rows, the kernel under seqFitLDpruning.  For rows x, y (code = alt-allele count,
+ * 3 = missing) and the samples called in BOTH, six non-negative integers describe the pair:
+ *     n = #both called   sx = sum x   sy = sum y   sxx = sum x^2   syy = sum y^2   sxy = sum x y
+ * and with c = n sxy - sx sy, vx = n sxx - sx^2, vy = n syy - sy^2 in int64 (exact for n_samp < 2^29) the correlation is
+ * r = c / sqrt(vx vy).  The pair is IN LD at t2 = t^2 iff  vx > 0 && vy > 0 && (double)c*(double)c > t2*((double)vx*(double)vy)
+ * (strict: a tie is not in LD).  All sums are integer accumulations on the matrix cores: a pair's sums depend on its two
+ * rows alone, and neither the 2-bit fields at and beyond n_samp in the last byte nor the bytes beyond ceil(n_samp/4)
+ * enter them, whatever they hold.
+ *
+ * A handle needs no model.  It holds a resident BLOCK of up to SGX_LD_BLOCK candidate rows and a WINDOW of kept rows, a
+ * ring that grows by doubling up to window_bytes (0 = 8 GiB).  Every entry is synchronous.  After SGX_EINVAL (a NULL
+ * buffer, a row count over its cap, bytes_per_variant < ceil(n_samp/4)) or SGX_ENOMEM (the window over its budget, no
+ * device memory) the handle stays usable and the window is as it was: sgx_ld_window_push changes its length and its
+ * first row only once the append is done.  After SGX_EHIP (the device itself failed) the rows of the window are
+ * undefined: reset it.
+ *   sgx_ld_counts_2bit   host rows a[ma], b[mb] (bytes_per_variant stride, at most SGX_LD_MAX_ROWS each) ->
+ *                        out[ma][mb][6] = (n, sx, sy, sxx, syy, sxy), x the row of a.  Touches neither block nor window.
+ *   sgx_ld_block_2bit    uploads mb <= SGX_LD_BLOCK candidate rows as the block; flags[mb][W + mb], one byte per pair,
+ *                        1 = in LD: columns 0..W-1 are the W window rows, oldest first, columns W.. the block's own
+ *                        rows, of which only j < i is defined.  The sums stay on the device.
+ *   sgx_ld_window_push   drops the oldest drop_oldest window rows, then appends the block's rows keep_idx[0..n_keep)
+ *                        (ascending), device to device.
+ *   sgx_ld_window_reset  empties the window (its memory is kept).   sgx_ld_window_len: its rows (-1: NULL handle).
+ *   sgx_ld_kernel_ms     HIP-event time of the kernels of the last counts / block call. */
+#define SGX_LD_BLOCK     256
+#define SGX_LD_MAX_ROWS 4096
+typedef struct sgx_ld sgx_ld;
+int  sgx_ld_create(int device, int32_t n_samp, size_t bytes_per_variant, size_t window_bytes, sgx_ld **out);
+void sgx_ld_free(sgx_ld *l);
+int  sgx_ld_counts_2bit(sgx_ld *l, const uint8_t *a, size_t ma, const uint8_t *b, size_t mb, int32_t *out);
+int  sgx_ld_block_2bit(sgx_ld *l, const uint8_t *rows, size_t mb, double t2, uint8_t *flags);
+int  sgx_ld_window_push(sgx_ld *l, const int32_t *keep_idx, size_t n_keep, size_t drop_oldest);
+int  sgx_ld_window_reset(sgx_ld *l);
+int64_t sgx_ld_window_len(const sgx_ld *l);
+int  sgx_ld_kernel_ms(sgx_ld *l, double *ms);
+
 /* Tuning / test hooks (per handle; there are no process-wide switches): "spa_exact" (every flagged variant
  * through the exact exp/log SPA kernel instead of the cumulant series), "force_dense" (exact g_pos/g_neg
  * pass for every SPA variant), "score_v1" (FP64 gather score kernel instead of the MFMA path), "lanes"

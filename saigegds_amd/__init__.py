@@ -11,6 +11,8 @@ Public surface (mirrors the reference's R API for this path):
     seqFitDenseGRM, seqFitSparseGRM  the explicit GRM, dense and thresholded (not in the reference)
     load_grm, ExplicitGrmOperator    read it back; the operator seqFitNullGLMM_SPA(grm_mat=) fits on
     exact_pass, EXACT_MAX_MAC  exact p-values of ultra-rare rows, seqAssocGLMM_SPA(exact_mac=) (not in the reference)
+    seqFitLDpruning    LD pruning of the GRM markers, the vignette's first step (upstream 2.x)
+    ld_counts_2bit, ld_corr  the pairwise LD sums of 2-bit rows on the device, and r from them
     seqSAIGE_LoadPval  load saved association results     (R/saige_main.r:164-215)
 The compute lives in libsaigehip.so (include/saigehip.h); there is no CPU path.
 """
@@ -24,7 +26,8 @@ from .skat import pchisq_mix, seqAssocGLMM_spaSKAT  # noqa: F401
 from .skato import pchisq_mix_vec, seqAssocGLMM_spaSKATO, skato_pvalue  # noqa: F401
 from .cond import cond_tests, seqAssocGLMM_SPA_cond  # noqa: F401
 from .grm import SparseGRM, load_grm, seqFitDenseGRM, seqFitSparseGRM  # noqa: F401
-from ._lib import ExplicitGrmOperator  # noqa: F401
+from ._lib import ExplicitGrmOperator, ld_corr, ld_counts_2bit  # noqa: F401
+from .ldprune import seqFitLDpruning  # noqa: F401
 from .results import seqSAIGE_LoadPval  # noqa: F401
 from .exact import EXACT_MAX_MAC, exact_pass  # noqa: F401
 

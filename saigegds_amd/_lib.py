@@ -21,6 +21,8 @@ ENOSPACE = -5         # SGX_ENOSPACE: sgx_grm_sparse found more entries than the
 SKAT_MAX_VARIANTS = 4096   # SGX_SKAT_MAX_VARIANTS: entries of one unit of sgx_skat_2bit
 SKATO_MAX_M = 256     # SGX_SKATO_MAX_M: order of one matrix of sgx_skato_spectra
 COND_MAX = 16         # SGX_COND_MAX: conditioning variants of one sgx_cond_set
+LD_BLOCK = 256        # SGX_LD_BLOCK: candidate rows of one sgx_ld_block_2bit call
+LD_MAX_ROWS = 4096    # SGX_LD_MAX_ROWS: rows a side of one sgx_ld_counts_2bit call
 DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
 DS_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float64): 2}   # SGX_DS_U8 / _I32 / _F64
 # SGX_PR_*: the GDS classes whose rows cross PCIe as stored (sgx_scan_packed) and the numpy type of their values
@@ -212,6 +214,14 @@ def _abi():
         "sgx_collapse_2bit": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
         "sgx_collapse_2bit_dev": (ci, [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
         "sgx_ds_block_collapse": (ci, [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sgx_ld_create": (ci, [ci, i32, sz, sz, pvp]),
+        "sgx_ld_free": (None, [vp]),
+        "sgx_ld_counts_2bit": (ci, [vp, vp, sz, vp, sz, vp]),
+        "sgx_ld_block_2bit": (ci, [vp, vp, sz, dp, vp]),
+        "sgx_ld_window_push": (ci, [vp, vp, sz, sz]),
+        "sgx_ld_window_reset": (ci, [vp]),
+        "sgx_ld_window_len": (C.c_int64, [vp]),
+        "sgx_ld_kernel_ms": (ci, [vp, ptr(dp)]),
     }
 
 
@@ -951,6 +961,88 @@ def geno_stats_2bit(packed: np.ndarray, n_samp: int, device: int = 0):
     check(L.sgx_geno_stats_2bit(packed.ctypes.data, packed.shape[1], int(n_samp), m, int(device),
                                 nv.ctypes.data, sm.ctypes.data))
     return nv, sm
+
+
+class LdEngine(_Handle):
+    """The LD handle of the library (``sgx_ld``) for rows of ``n_samp`` samples at ``bytes_per_variant``
+    stride: a resident block of up to ``LD_BLOCK`` candidate rows and a window of kept rows (a ring of at most
+    ``window_bytes``; 0: the library's default).  What seqFitLDpruning drives; needs no model."""
+
+    _free = "sgx_ld_free"
+
+    def __init__(self, n_samp: int, bytes_per_variant: int, device: int = 0, window_bytes: int = 0):
+        self.n_samp, self.bpv = int(n_samp), int(bytes_per_variant)
+        h = C.c_void_p()
+        check(self._L.sgx_ld_create(int(device), self.n_samp, self.bpv, int(window_bytes), C.byref(h)))
+        self._h = h
+
+    def _rows(self, rows) -> np.ndarray:
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        if rows.ndim != 2 or rows.shape[1] != self.bpv:
+            raise ValueError(f"LdEngine: rows must be [m, {self.bpv}] uint8")
+        return rows
+
+    def counts(self, a, b) -> np.ndarray:
+        """int32 [ma, mb, 6] = (n, sx, sy, sxx, syy, sxy) of every pair (row of ``a``: x, row of ``b``: y)."""
+        a, b = self._rows(a), self._rows(b)
+        out = np.zeros((a.shape[0], b.shape[0], 6), dtype=np.int32)
+        check(self._L.sgx_ld_counts_2bit(self._h, a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], out.ctypes.data))
+        return out
+
+    def block(self, rows, t2: float) -> np.ndarray:
+        """Uploads the candidate rows -> uint8 [mb, W + mb], 1 = in LD at ``t2``: the W window rows oldest first, then
+        the block's own rows (only j < i defined)."""
+        rows = self._rows(rows)
+        flags = np.zeros((rows.shape[0], self.window_len + rows.shape[0]), dtype=np.uint8)
+        check(self._L.sgx_ld_block_2bit(self._h, rows.ctypes.data, rows.shape[0], float(t2), flags.ctypes.data))
+        return flags
+
+    def push(self, keep_idx, drop_oldest: int = 0):
+        """Drops the oldest ``drop_oldest`` window rows, then appends the block's rows ``keep_idx`` (ascending).  A
+        window over the byte budget raises MemoryError."""
+        idx = np.ascontiguousarray(keep_idx, dtype=np.int32).reshape(-1)
+        rc = self._L.sgx_ld_window_push(self._h, idx.ctypes.data if idx.size else None, idx.size, int(drop_oldest))
+        if rc == -3:                                   # SGX_ENOMEM
+            raise MemoryError(self._L.sgx_last_error().decode("utf-8", "replace"))
+        check(rc)
+
+    def reset(self):
+        check(self._L.sgx_ld_window_reset(self._h))
+
+    @property
+    def window_len(self) -> int:
+        return int(self._L.sgx_ld_window_len(self._h))
+
+    def kernel_ms(self) -> float:
+        ms = C.c_double()
+        check(self._L.sgx_ld_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+
+def ld_counts_2bit(packed_a, packed_b, n_samp: int, device: int = 0) -> np.ndarray:
+    """The six LD sums of every pair of 2-bit rows, on the GPU: int32 [ma, mb, 6] = (n, sx, sy, sxx, syy, sxy) over the
+    samples called in both rows (``sgx_ld_counts_2bit``); the two matrices share their row stride."""
+    a = np.ascontiguousarray(packed_a, dtype=np.uint8)
+    b = np.ascontiguousarray(packed_b, dtype=np.uint8)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("ld_counts_2bit: two [m, stride] uint8 matrices of one stride")
+    out = np.zeros((a.shape[0], b.shape[0], 6), dtype=np.int32)
+    with LdEngine(n_samp, a.shape[1], device=device) as eng:
+        for i in range(0, a.shape[0], LD_MAX_ROWS):
+            for j in range(0, b.shape[0], LD_MAX_ROWS):
+                out[i:i + LD_MAX_ROWS, j:j + LD_MAX_ROWS] = eng.counts(a[i:i + LD_MAX_ROWS], b[j:j + LD_MAX_ROWS])
+    return out
+
+
+def ld_corr(counts) -> np.ndarray:
+    """The six sums [..., 6] -> r = c / sqrt(vx vy) with c = n sxy - sx sy, vx = n sxx - sx^2, vy = n syy - sy^2 in
+    int64; NaN where vx vy == 0.  numpy, no GPU."""
+    s = np.asarray(counts).astype(np.int64)
+    n, sx, sy, sxx, syy, sxy = (s[..., k] for k in range(6))
+    c, vx, vy = n * sxy - sx * sy, n * sxx - sx * sx, n * syy - sy * sy
+    den = np.sqrt(vx.astype(np.float64) * vy.astype(np.float64))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(den > 0, c.astype(np.float64) / den, np.nan)
 
 
 def quantize_packed(raw, cls, scale, offset, n_samp: int, sel=None, device: int = 0, chunk_bytes: int = 0):

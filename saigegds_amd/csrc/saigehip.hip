@@ -92,6 +92,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_eig.h"
 #include "kern_collapse.h"
 #include "kern_collapse_ds.h"
+#include "kern_ld.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -123,3 +124,4 @@ static int fail(int code, const char *fmt, ...)
 #include "host_skato.h"
 #include "host_collapse.h"
 #include "host_collapse_ds.h"
+#include "host_ld.h"

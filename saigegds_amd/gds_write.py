@@ -270,13 +270,24 @@ def write_seqarray_alleles(fn: str, alleles: np.ndarray, sample_id: Optional[Seq
 
 
 def write_seqarray_genotypes(fn: str, packed: np.ndarray, n_samp: int, sample_id: Optional[Sequence[str]] = None,
-                             compress: str = "none", chromosome: str = "1", ra_block: int = _RA_BLOCK):
+                             compress: str = "none", chromosome="1", ra_block: int = _RA_BLOCK, variant_id=None,
+                             position=None, allele=None):
     """A SeqArray-style genotype file from 2-bit dosage rows (``packed``: [M, >= ceil(N / 4)], code = alt-allele
     count, 3 = missing): sample.id, variant.id, position, chromosome, allele, genotype/data (dBit2
     [variant, sample, ploidy]) and genotype/@data -- what seqAssocGLMM_SPA reads (R/assoc_single.r:116-144).
-    The test and benchmark generator; dosage d is stored as alleles (1, 0) / (1, 1), missing as (3, 3)."""
+    The test and benchmark generator; dosage d is stored as alleles (1, 0) / (1, 1), missing as (3, 3).
+    ``variant_id`` (default 1..M), ``position`` (default 100, 200, ...), ``allele`` (default "A,C") and a per-variant
+    list for ``chromosome`` carry the variants' own annotation (seqFitLDpruning's export)."""
     packed = np.ascontiguousarray(packed, dtype=np.uint8)
     M = packed.shape[0]
+    per_variant = {}
+    for name, v in (("variant_id", variant_id), ("position", position), ("allele", allele),
+                    ("chromosome", None if isinstance(chromosome, str) else chromosome)):
+        if v is not None:
+            v = [str(x) for x in v] if name in ("allele", "chromosome") else np.asarray(v)
+            if len(v) != M:
+                raise ValueError(f"write_seqarray_genotypes: '{name}' should have one entry per variant ({M}).")
+            per_variant[name] = v
     nb = (n_samp + 3) // 4
     # one packed byte (4 dosage codes) -> 16 bits (4 samples x 2 alleles x 2 bits)
     nib = np.array([0b0000, 0b0001, 0b0101, 0b1111], dtype=np.uint16)
@@ -296,10 +307,10 @@ def write_seqarray_genotypes(fn: str, packed: np.ndarray, n_samp: int, sample_id
     w.put_attr("FileFormat", "SEQ_ARRAY")
     sid = [f"s{i + 1}" for i in range(n_samp)] if sample_id is None else [str(x) for x in sample_id]
     w.add("sample.id", sid, "none")
-    w.add("variant.id", np.arange(1, M + 1), "none")
-    w.add("position", np.arange(1, M + 1) * 100, "none")
-    w.add("chromosome", [chromosome] * M, "none")
-    w.add("allele", ["A,C"] * M, "none")
+    w.add("variant.id", per_variant.get("variant_id", np.arange(1, M + 1)), "none")
+    w.add("position", per_variant.get("position", np.arange(1, M + 1) * 100), "none")
+    w.add("chromosome", per_variant.get("chromosome", [chromosome] * M), "none")
+    w.add("allele", per_variant.get("allele", ["A,C"] * M), "none")
     w.add("genotype/data", raw, compress, cls="dBit2", dims=(M, n_samp, 2), ra_block=ra_block)
     w.add("genotype/@data", np.ones(M, dtype=np.uint8).tobytes(), "none", cls="dUInt8", dims=(M,))
     w.close()
