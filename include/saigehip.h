@@ -50,6 +50,7 @@ extern "C" {
 #define SGX_ENOMEM     -3   /* allocation failed                               */
 #define SGX_ENODEV     -4   /* no usable gfx950 device                         */
 #define SGX_ENOSPACE   -5   /* output buffer too small: the needed size is returned */
+#define SGX_ERANK      -6   /* sgx_grm_pca: the block of vectors lost rank     */
 
 #define SGX_MAX_COEFF  16   /* K = nrow(XV) supported by the compiled kernels  */
 #define SGX_TRAIT_BINARY 0
@@ -750,6 +751,46 @@ int  sgx_grm_dense(sgx_grm *g, int32_t i0, int32_t ni, int32_t j0, int32_t nj, d
 int  sgx_grm_dense_kernel_ms(sgx_grm *g, double *ms_out);
 int  sgx_grm_sparse(sgx_grm *g, double cutoff, size_t cap, int32_t *i_out, int32_t *j_out, double *v_out,
 	size_t *n_out, sgx_grm_sparse_stats *stats);
+
+/* The marker side of the product, and the top principal components of K (not in the reference, which leaves PCA to
+ * SNPRelate's dense N x N route).
+ *   sgx_grm_marker_dots(_dev)  Out[c * ldo + v] = dot_v = sum_i G[v, i] B[i, c]: pass 1 of sgx_grm_crossprod_multi (the same
+ *                   launches, so the bits the product uses internally), copied out before it becomes x_v.  B as for the
+ *                   products (k columns, ldb >= N), ldo >= n_markers; host / device pointers, the _dev form asynchronous
+ *                   until sgx_grm_sync.  Marker groups are ignored.  The products' results do not change by a call.
+ *   sgx_grm_pca     block subspace iteration with Rayleigh-Ritz on n_block vectors from Q0 (host, [n_block][ld0]): the
+ *                   block is orthonormalised by CholeskyQR twice, Y = K Q by sgx_grm_crossprod_multi_dev, H = Q'Y is
+ *                   symmetrised and diagonalised by a cyclic Jacobi routine on the host, U = Q V, W = Y V,
+ *                   r_c = |W_c - theta_c U_c|; it stops when r_c <= tol theta_1 for all c < n_pc or after max_iter
+ *                   rounds (not an error: stats->n_converged counts the leading components that met tol), else W is the
+ *                   next block.  eigval / resid [n_pc], vec [n_pc][ldv] (unit vectors, the entry of largest magnitude
+ *                   positive, the lowest index on ties), loading (or NULL) [n_pc][ldl]: dot_v(U_c) / sqrt(M theta_c),
+ *                   the unit left singular vector of G / sqrt(M), 0 where theta_c <= 0.  Everything N-sized stays on
+ *                   the device; the bits of the outputs depend on the genotypes and on Q0 only.
+ *                   SGX_ERANK (no output written, the handle stays usable): a Cholesky pivot <= n_block 2^-52 of the
+ *                   largest diagonal entry -- the block's vectors are dependent, K has fewer directions than n_block.
+ *                   SGX_EINVAL (nothing launched): n_pc < 1, n_block < n_pc, n_block > SGX_GRM_MAX_RHS or > N,
+ *                   ld0 or ldv < N, ldl < n_markers with loading, a NULL Q0 / eigval / resid / vec, tol not finite or
+ *                   < 0, max_iter < 1.
+ *   sgx_grm_ts_gram / sgx_grm_ts_apply   the block kernels under the solver alone, on host arrays of any row count n
+ *                   (column c at base + c * ld, ld >= n, 1 <= columns <= SGX_GRM_MAX_RHS): C[a * Lb + b] = sum_i
+ *                   A[i, a] B[i, b] on the FP64 matrix cores, in slabs of SGX_TS_SLAB rows added in slab order, the bits
+ *                   of C[a][b] a function of columns a, b and n only; Out[:, c] = sum_a A[:, a] T[a * Lc + c], one
+ *                   fused multiply-add chain in ascending a.  Rows >= n of a column are never read or written.  For tests.
+ * The scratch of all of them is allocated on first use and freed by sgx_grm_free. */
+#define SGX_TS_SLAB 1024
+/* af_out / inv_out [n_markers]: the allele frequency and 1 / sqrt(2 af (1 - af)) (0: monomorphic) the operator
+ * standardises a marker with; what a projection of other samples onto the loadings has to repeat */
+int  sgx_grm_marker_table(sgx_grm *g, double *af_out, double *inv_out);
+typedef struct { int32_t iters; int32_t n_converged; double ms_products, ms_block; } sgx_grm_pca_stats;
+int  sgx_grm_marker_dots(sgx_grm *g, const double *B, size_t ldb, int k, double *Out, size_t ldo);
+int  sgx_grm_marker_dots_dev(sgx_grm *g, const double *B_dev, size_t ldb, int k, double *Out_dev, size_t ldo);
+int  sgx_grm_pca(sgx_grm *g, int n_pc, int n_block, const double *Q0, size_t ld0, int max_iter, double tol,
+	double *eigval, double *resid, double *vec, size_t ldv, double *loading, size_t ldl, sgx_grm_pca_stats *stats);
+int  sgx_grm_ts_gram(sgx_grm *g, int32_t n, const double *A, size_t lda, int La, const double *B, size_t ldb, int Lb,
+	double *C);
+int  sgx_grm_ts_apply(sgx_grm *g, int32_t n, const double *A, size_t lda, int La, const double *T, int Lc,
+	double *Out, size_t ldo);
 
 /* Operator of an explicit symmetric matrix K [n][n] resident on one device: the null-model fit on the matrix
  * sgx_grm_sparse / sgx_grm_dense made (SAIGE's useSparseGRMtoFitNULL, upstream SAIGEgds 2.x grm.mat=; not in the

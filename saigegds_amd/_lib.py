@@ -22,6 +22,8 @@ SKAT_MAX_VARIANTS = 4096   # SGX_SKAT_MAX_VARIANTS: entries of one unit of sgx_s
 SKATO_MAX_M = 256     # SGX_SKATO_MAX_M: order of one matrix of sgx_skato_spectra
 COND_MAX = 16         # SGX_COND_MAX: conditioning variants of one sgx_cond_set
 LD_BLOCK = 256        # SGX_LD_BLOCK: candidate rows of one sgx_ld_block_2bit call
+TS_SLAB = 1024        # SGX_TS_SLAB: rows per partial of the tall-skinny Gram kernel (GrmOperator.ts_gram)
+ERANK = -6            # SGX_ERANK: sgx_grm_pca's block of vectors lost rank
 LD_MAX_ROWS = 4096    # SGX_LD_MAX_ROWS: rows a side of one sgx_ld_counts_2bit call
 DS_MAX_COLS = 64      # SGX_DS_MAX_COLS: weight columns of one sgx_dsblock_burden call
 DS_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.int32): 1, np.dtype(np.float64): 2}   # SGX_DS_U8 / _I32 / _F64
@@ -78,6 +80,14 @@ class SgxError(RuntimeError):
         self.code = code
 
 
+class PcaRankError(ValueError):
+    """What an operator's ``pca`` raises when its block of vectors loses rank; ``seqFitPCA`` catches this type."""
+
+
+class SgxRankError(SgxError, PcaRankError):
+    """``sgx_grm_pca``: the block of vectors lost rank (SGX_ERANK)."""
+
+
 class SgxModel(C.Structure):
     _fields_ = [
         ("n_samp", C.c_int32), ("n_coeff", C.c_int32), ("trait", C.c_int32), ("reserved", C.c_int32),
@@ -111,6 +121,10 @@ class SgxGrmSparseStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+class SgxGrmPcaStats(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("n_converged", C.c_int32), ("ms_products", C.c_double), ("ms_block", C.c_double)]
 
 
 def _abi():
@@ -171,6 +185,12 @@ def _abi():
         "sgx_grm_dense": (ci, [vp, i32, i32, i32, i32, vp, sz]),
         "sgx_grm_dense_kernel_ms": (ci, [vp, ptr(dp)]),
         "sgx_grm_sparse": (ci, [vp, dp, sz, vp, vp, vp, ptr(sz), ptr(SgxGrmSparseStats)]),
+        "sgx_grm_marker_table": (ci, [vp, vp, vp]),
+        "sgx_grm_marker_dots": (ci, [vp, vp, sz, ci, vp, sz]),
+        "sgx_grm_marker_dots_dev": (ci, [vp, vp, sz, ci, vp, sz]),
+        "sgx_grm_pca": (ci, [vp, ci, ci, vp, sz, ci, dp, vp, vp, vp, sz, vp, sz, ptr(SgxGrmPcaStats)]),
+        "sgx_grm_ts_gram": (ci, [vp, i32, vp, sz, ci, vp, sz, ci, vp]),
+        "sgx_grm_ts_apply": (ci, [vp, i32, vp, sz, ci, vp, ci, vp, sz]),
         "sgx_kmat_init_csr": (ci, [i32, vp, vp, vp, ci, pvp]),
         "sgx_kmat_init_dense": (ci, [vp, sz, i32, ci, pvp]),
         "sgx_kmat_free": (None, [vp]),
@@ -1200,6 +1220,68 @@ class GrmOperator(_Operator):
             k = int(n_out.value)
             res = (i[:k].copy(), j[:k].copy(), x[:k].copy())
             return res + (st.as_dict(),) if return_stats else res
+
+    # -- the marker side of the product and the principal components of K (sgx_grm_marker_dots / sgx_grm_pca)
+    def marker_table(self):
+        """(af, inv) per marker: the allele frequency and 1 / sqrt(2 af (1 - af)) the operator standardises with."""
+        af, inv = np.empty(self.m, dtype=np.float64), np.empty(self.m, dtype=np.float64)
+        check(self._L.sgx_grm_marker_table(self._h, af.ctypes.data, inv.ctypes.data))
+        return af, inv
+
+    def marker_dots(self, B: np.ndarray) -> np.ndarray:
+        """dot_v = sum_i G[v, i] b_i for every row b of B ([k, N] -> [k, M]): pass 1 of the product, as an output."""
+        B = self._rhs(B)
+        out = np.empty((B.shape[0], self.m), dtype=np.float64)
+        for j0, k in self._batches(B.shape[0]):
+            check(self._L.sgx_grm_marker_dots(self._h, B[j0].ctypes.data, self.n, k, out[j0].ctypes.data, self.m))
+        return out
+
+    def pca(self, n_pc: int, Q0: np.ndarray, max_iter: int = 100, tol: float = 1e-6, loadings: bool = False) -> dict:
+        """The top ``n_pc`` eigenpairs of K by block subspace iteration from the rows of ``Q0`` ([n_block, N]) ->
+        dict of ``eigval`` [n_pc], ``resid`` [n_pc] (|K u - theta u|), ``vec`` [n_pc, N], ``loading`` ([n_pc, M], or
+        None), ``iters``, ``n_converged``, ``ms_products``, ``ms_block``.  A block that loses rank raises
+        ``SgxRankError`` (a ValueError); not converging within ``max_iter`` is for the caller to read off ``resid``."""
+        Q0 = self._rhs(Q0)
+        n_pc, L = int(n_pc), Q0.shape[0]
+        k = max(n_pc, 1)
+        eigval, resid = np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.float64)
+        vec = np.zeros((k, self.n), dtype=np.float64)
+        load_ = np.zeros((k, self.m), dtype=np.float64) if loadings else None
+        st = SgxGrmPcaStats()
+        rc = self._L.sgx_grm_pca(self._h, n_pc, L, Q0.ctypes.data, self.n, int(max_iter), float(tol), eigval.ctypes.data,
+                                 resid.ctypes.data, vec.ctypes.data, self.n, None if load_ is None else load_.ctypes.data,
+                                 self.m, C.byref(st))
+        if rc == ERANK:
+            raise SgxRankError(rc, self._L.sgx_last_error().decode("utf-8", "replace"))
+        check(rc)
+        return {"eigval": eigval, "resid": resid, "vec": vec, "loading": load_, "iters": int(st.iters),
+                "n_converged": int(st.n_converged), "ms_products": float(st.ms_products), "ms_block": float(st.ms_block)}
+
+    def ts_gram(self, A: np.ndarray, B: Optional[np.ndarray] = None, n: Optional[int] = None) -> np.ndarray:
+        """C[a, b] = sum_{i < n} A[a, i] B[b, i] by the block Gram kernel (``sgx_grm_ts_gram``; for tests): A [La, ld],
+        B [Lb, ld'] (None: A itself), n rows (default: the whole rows).  Entries beyond n are never read."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        B = A if B is None else np.ascontiguousarray(B, dtype=np.float64)
+        if A.ndim != 2 or B.ndim != 2:
+            raise ValueError("ts_gram: two [L, ld] arrays")
+        n = int(min(A.shape[1], B.shape[1]) if n is None else n)
+        out = np.empty((A.shape[0], B.shape[0]), dtype=np.float64)
+        check(self._L.sgx_grm_ts_gram(self._h, n, A.ctypes.data, A.shape[1], A.shape[0], B.ctypes.data, B.shape[1],
+                                      B.shape[0], out.ctypes.data))
+        return out
+
+    def ts_apply(self, A: np.ndarray, T: np.ndarray, n: Optional[int] = None, fill: float = 0.0) -> np.ndarray:
+        """Out[c, i] = sum_a A[a, i] T[a, c] for i < n by the block kernel (``sgx_grm_ts_apply``; for tests): A [La, ld],
+        T [La, Lc] -> [Lc, ld], whose entries beyond n keep ``fill``."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if A.ndim != 2 or T.ndim != 2 or T.shape[0] != A.shape[0]:
+            raise ValueError("ts_apply: A [La, ld] and T [La, Lc]")
+        n = int(A.shape[1] if n is None else n)
+        out = np.full((T.shape[1], A.shape[1]), fill, dtype=np.float64)
+        check(self._L.sgx_grm_ts_apply(self._h, n, A.ctypes.data, A.shape[1], A.shape[0], T.ctypes.data, T.shape[1],
+                                       out.ctypes.data, A.shape[1]))
+        return out
 
     def crossprod(self, b: np.ndarray) -> np.ndarray:
         b = np.ascontiguousarray(b, dtype=np.float64)

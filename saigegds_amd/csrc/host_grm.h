@@ -41,6 +41,10 @@ struct sgx_grm {
 	DevBuf<GdTile> gd_list;
 	DevBuf<int> gd_i, gd_j; DevBuf<double> gd_v;
 	double gd_ms_kernel = 0;               // the kernels' time over the last sgx_grm_dense call
+	// marker-side output and principal components (host_pca.h): scratch allocated on first use
+	DevBuf<double> md_out;                 // [k][M]: dot_v of k columns
+	DevBuf<double> ts_part, ts_C, ts_T;    // ts_gram partials [slabs][64][64], its result and the matrix of ts_apply [64][64]
+	DevBuf<double> pca_X0, pca_X1, pca_Y, pca_W;   // [n_block][N] blocks of sgx_grm_pca
 };
 static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
 static_assert(GRM_MAX_GROUPS == SGX_GRM_MAX_GROUPS, "kern_grm.h and saigehip.h disagree on the group limit");
@@ -135,6 +139,16 @@ extern "C" int sgx_grm_diag(sgx_grm *g, double *diag_out)
 	return SGX_OK;
 }
 
+// the marker table the operator standardises with: af_v and inv_v = 1 / sqrt(2 af_v (1 - af_v)) (0: monomorphic)
+extern "C" int sgx_grm_marker_table(sgx_grm *g, double *af_out, double *inv_out)
+{
+	if (!g || !af_out || !inv_out) return fail(SGX_EINVAL, "sgx_grm_marker_table: NULL argument");
+	HIPCHK(hipSetDevice(g->device));
+	HIPCHK(hipMemcpy(af_out, g->af, g->M * sizeof(double), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(inv_out, g->inv, g->M * sizeof(double), hipMemcpyDeviceToHost));
+	return SGX_OK;
+}
+
 extern "C" int sgx_grm_sync(sgx_grm *g)
 {
 	if (!g) return fail(SGX_EINVAL, "sgx_grm_sync: NULL handle");
@@ -163,6 +177,25 @@ static void grm_contract(sgx_grm *g, int nbfv, const uint8_t *packed, size_t bpv
 	}
 }
 
+// ---- pass 1 up to its exact sums: per marker, over samples; column y of gc (at most GRM_GROUP) in fragment y / 2,
+// limbs 7 (y % 2) ..  Leaves the columns' scales in g->maxb slot 0 and the sums in g->accV, for grm_dot_epilogue
+// (the product) or grm_dot_out_kernel (sgx_grm_marker_dots): both read what the same launches wrote.
+static int grm_pass1_sums(sgx_grm *g, const double *B, size_t ldb, const GrmCols &gc)
+{
+	hipStream_t st = g->stream;
+	const size_t N = (size_t)g->N, M = g->M;
+	const dim3 bl(256);
+	const int nb1 = (gc.n + 1) / 2;
+	HIPCHK(hipMemsetAsync(g->maxb, 0, (size_t)gc.n * 3 * sizeof(unsigned long long), st));
+	hipLaunchKernelGGL(absmax_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, B, ldb, gc, N, 0, g->maxb);
+	HIPCHK(hipMemsetAsync(g->FlN, 0, (size_t)g->ntileN * 16 * (16 * nb1) * 16, st));
+	hipLaunchKernelGGL(limbs_kernel, dim3(512, gc.n), bl, 0, st, B, ldb, gc, N, (size_t)g->ntileN * 256,
+		16 * nb1, 2, 0, g->maxb, 0, g->FlN);
+	HIPCHK(hipMemsetAsync(g->accV, 0, M * 32 * nb1 * sizeof(int), st));
+	grm_contract(g, nb1, g->G, g->bpvN, (int)M, g->FlN, g->ntileN, g->accV);
+	return SGX_OK;
+}
+
 // Out[:, c] = G'(G B[:, c])/M for c in cols (columns at base + c * ld), device vectors
 // (get_crossprod_b_grm, saige_fitnull.cpp:435-536).  A column's result does not depend on the other
 // columns of the call: its limbs, its exact integer sums and its reductions are its own.
@@ -183,15 +216,8 @@ static int grm_matvec_dev(sgx_grm *g, const double *B, size_t ldb, const GrmCols
 		GrmScal sb{};
 		GrmIdx ex{};
 		for (int y = 0; y < gc.n; y++) { gc.c[y] = cols.c[g0 + y]; sb.v[y] = sum_b[g0 + y]; ex.v[y] = excl ? excl[gc.c[y]] : -1; }
-		// ---- pass 1: per marker, over samples; column y in fragment y / 2, limbs 7 (y % 2) ..
 		const int nb1 = (gc.n + 1) / 2;
-		HIPCHK(hipMemsetAsync(g->maxb, 0, (size_t)gc.n * 3 * sizeof(unsigned long long), st));
-		hipLaunchKernelGGL(absmax_kernel, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, B, ldb, gc, N, 0, g->maxb);
-		HIPCHK(hipMemsetAsync(g->FlN, 0, (size_t)g->ntileN * 16 * (16 * nb1) * 16, st));
-		hipLaunchKernelGGL(limbs_kernel, dim3(512, gc.n), bl, 0, st, B, ldb, gc, N, (size_t)g->ntileN * 256,
-			16 * nb1, 2, 0, g->maxb, 0, g->FlN);
-		HIPCHK(hipMemsetAsync(g->accV, 0, M * 32 * nb1 * sizeof(int), st));
-		grm_contract(g, nb1, g->G, g->bpvN, (int)M, g->FlN, g->ntileN, g->accV);
+		if ((rc = grm_pass1_sums(g, B, ldb, gc))) return rc;
 		if (excl)
 			hipLaunchKernelGGL(grm_dot_epilogue<true>, dim3(GRM_RED_BLOCKS, gc.n), bl, 0, st, M, nb1, g->accV, g->maxb, sb,
 				g->af, g->inv, g->l0, g->xv, g->gv, g->pw.part, g->grp, ex);
@@ -286,6 +312,60 @@ extern "C" int sgx_grm_crossprod_multi_dev(sgx_grm *g, const double *B_dev, size
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(g->device));
 	return grm_matvec_dev(g, B_dev, ldb, pcg_cols_iota(k), Out_dev, ldb);
+}
+
+// ---- the marker side of the product as an output: Out[c][v] = dot_v of column c = sum_i G[v, i] B[i, c], device
+// vectors (Out row c at Out + c * ldo).  The launches of pass 1 of grm_matvec_dev, group by group; the epilogue's place
+// is taken by grm_dot_out_kernel.  Marker groups are ignored.
+static int grm_marker_dots_run(sgx_grm *g, const double *B, size_t ldb, int k, double *Out, size_t ldo)
+{
+	const GrmCols cols = pcg_cols_iota(k);
+	double sum_b[GRM_MAX_RHS];
+	int rc = pcg_sum(&g->pw, B, nullptr, ldb, cols, sum_b);
+	if (rc) return rc;
+	for (int g0 = 0; g0 < k; g0 += GRM_GROUP) {
+		GrmCols gc{};
+		gc.n = std::min(GRM_GROUP, k - g0);
+		GrmScal sb{};
+		for (int y = 0; y < gc.n; y++) { gc.c[y] = cols.c[g0 + y]; sb.v[y] = sum_b[g0 + y]; }
+		if ((rc = grm_pass1_sums(g, B, ldb, gc))) return rc;
+		hipLaunchKernelGGL(grm_dot_out_kernel, dim3(GRM_RED_BLOCKS, gc.n), dim3(256), 0, g->stream, g->M, (gc.n + 1) / 2,
+			g->accV, g->maxb, sb, g->inv, g->l0, Out, ldo, gc);
+		HIPCHK(hipGetLastError());
+	}
+	return SGX_OK;
+}
+
+static int grm_marker_dots_args(const char *fn, sgx_grm *g, const void *B, size_t ldb, int k, const void *Out, size_t ldo)
+{
+	int rc = grm_multi_args(fn, g, B, ldb, k, Out);
+	if (rc) return rc;
+	if (ldo < g->M) return fail(SGX_EINVAL, "%s: ldo=%zu < M=%zu", fn, ldo, g->M);
+	return SGX_OK;
+}
+
+extern "C" int sgx_grm_marker_dots_dev(sgx_grm *g, const double *B_dev, size_t ldb, int k, double *Out_dev, size_t ldo)
+{
+	int rc = grm_marker_dots_args("sgx_grm_marker_dots_dev", g, B_dev, ldb, k, Out_dev, ldo);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(g->device));
+	return grm_marker_dots_run(g, B_dev, ldb, k, Out_dev, ldo);
+}
+
+extern "C" int sgx_grm_marker_dots(sgx_grm *g, const double *B, size_t ldb, int k, double *Out, size_t ldo)
+{
+	int rc = grm_marker_dots_args("sgx_grm_marker_dots", g, B, ldb, k, Out, ldo);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(g->device));
+	HIPCHK(pcg_reserve(&g->pw, k));
+	HIPCHK(g->md_out.reserve((size_t)k * g->M));
+	const size_t N = (size_t)g->N, M = g->M;
+	HIPCHK(pcg_copy_cols(&g->pw, g->pw.B, B, ldb, k, hipMemcpyHostToDevice));
+	if ((rc = grm_marker_dots_run(g, g->pw.B, N, k, g->md_out, M))) return rc;
+	HIPCHK(hipMemcpy2DAsync(Out, ldo * sizeof(double), g->md_out, M * sizeof(double), M * sizeof(double), (size_t)k,
+		hipMemcpyDeviceToHost, g->stream));
+	HIPCHK(hipStreamSynchronize(g->stream));
+	return SGX_OK;
 }
 
 // PCG_diag_sigma (saige_fitnull.cpp:581-614) on the implicit GRM: the loop is pcg_run (host_pcg.h).

@@ -432,6 +432,32 @@ dot_partial_kernel(const double *__restrict__ A, const double *__restrict__ B, s
 	if (threadIdx.x == 0) out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
 }
 
+// dot_v of one marker and column from the exact sums of a pass-1 launch with nbfv fragments (a: the column's
+// first limb of the marker's row of acc); the one statement of it, for the product and for grm_dot_out_kernel
+__device__ __forceinline__ double grm_dot_value(const int *__restrict__ a, int nbfv, int e, double sb, double l0v, double invv)
+{
+	const HiLo V = mf_limbs(a), T3 = mf_limbs(a + 16 * nbfv);
+	const double t3 = ldexp(hl_to_double(T3), -e);
+	const double vw = ldexp(hl_to_double(hl_axpy(-3, T3, V)), -e);     // sum over codes 1,2 of code*b
+	return l0v * (sb - t3) + invv * vw;
+}
+
+// ---- dot_v itself, per column y of a pass-1 launch: Out[cols.c[y]][v] = sum_i G[v, i] b_i (sgx_grm_marker_dots);
+// the sums, the scale and the expression are those grm_dot_epilogue turns into x_v
+__global__ void __launch_bounds__(256)
+grm_dot_out_kernel(size_t M, int nbfv, const int *__restrict__ acc, const unsigned long long *__restrict__ maxb,
+	GrmScal sum_b, const double *__restrict__ inv, const double *__restrict__ l0, double *__restrict__ Out, size_t ldo,
+	GrmCols cols)
+{
+	const int y = blockIdx.y;
+	const int stride = 32 * nbfv, col = 16 * (y >> 1) + MF_NLIMB * (y & 1);
+	const int e = limb_scale(maxb[3 * y]);
+	const double sb = sum_b.v[y];
+	double *__restrict__ o = Out + (size_t)cols.c[y] * ldo;
+	for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < M; v += (size_t)gridDim.x * blockDim.x)
+		o[v] = grm_dot_value(acc + v * stride + col, nbfv, e, sb, l0[v], inv[v]);
+}
+
 // ---- pass-1 epilogue: dot_v -> x_v, gam_v, and the C0 partial sums, per column y of a pass-1 launch
 // with nbfv fragments (two columns per fragment); x_v, gam_v -> XV / GV row y (stride M),
 // C0 partials -> c0_partial[y * gridDim.x + blockIdx.x]
@@ -454,11 +480,7 @@ grm_dot_epilogue(size_t M, int nbfv, const int *__restrict__ acc, const unsigned
 	double *__restrict__ gv = GV + (size_t)y * M;
 	double c0[1] = {0};
 	for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < M; v += (size_t)gridDim.x * blockDim.x) {
-		const int *a = acc + v * stride + col;
-		const HiLo V = mf_limbs(a), T3 = mf_limbs(a + 16 * nbfv);
-		const double t3 = ldexp(hl_to_double(T3), -e);
-		const double vw = ldexp(hl_to_double(hl_axpy(-3, T3, V)), -e);     // sum over codes 1,2 of code*b
-		const double dot = l0[v] * (sb - t3) + inv[v] * vw;
+		const double dot = grm_dot_value(acc + v * stride + col, nbfv, e, sb, l0[v], inv[v]);
 		const double x = dot * inv[v];
 		if constexpr (LOCO) {
 			if (ex >= 0 && grp[v] == ex) { xv[v] = 0; gv[v] = 0; continue; }
