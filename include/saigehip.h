@@ -792,6 +792,35 @@ int  sgx_grm_ts_gram(sgx_grm *g, int32_t n, const double *A, size_t lda, int La,
 int  sgx_grm_ts_apply(sgx_grm *g, int32_t n, const double *A, size_t lda, int La, const double *T, int Lc,
 	double *Out, size_t ldo);
 
+/* KING-robust kinship of the handle's samples over its markers (not in the reference, which leaves relatedness to
+ * SNPRelate's snpgdsIBDKING).  No allele frequency enters, so population structure does not inflate it.
+ * Five int32 counts per pair (i, j), over the markers v < n_markers where both samples are called (code != 3):
+ *     nn both called    hi code_i == 1    hj code_j == 1    hh both == 1    ibs0 codes (0, 2) or (2, 0)
+ * and from them, with D = (hi + hj - 2 hh) + 4 ibs0 and mn = min(hi, hj),
+ *     kinship = mn > 0 ? 0.5 - (double)D / (4.0 * (double)mn) : NaN        IBS0 = nn > 0 ? (double)ibs0 / (double)nn : NaN
+ * The counts are exact (int8 matrix-core products, no floating-point sum), so a pair's five integers and the bits of
+ * its kinship depend on the two samples' codes and n_markers only: not on the tile, the rectangle, the cutoff, the
+ * other samples or the call; counts (j, i) are counts (i, j) with hi and hj swapped.  Marker groups are ignored.
+ *   sgx_grm_king_counts  out[q * ni * ld + (i - i0) * ld + (j - j0)] = count q (0 nn, 1 hi, 2 hj, 3 hh, 4 ibs0) of the
+ *                   pair (i, j), i0 <= i < i0 + ni, j0 <= j < j0 + nj: a host buffer of 5 ni ld int32, any rectangle
+ *                   inside [0, N) x [0, N), ld >= nj; entries at columns >= nj of a row are not written.
+ *   sgx_grm_king_pairs   every pair i < j with mn > 0 and kinship >= cutoff (a pair without a heterozygote on either
+ *                   side has no kinship and is never listed), sorted by (i, j): i_out, j_out, kin_out, ibs0_out
+ *                   [cap] and counts_out [cap][5] (or NULL).  *n_out is the number of pairs that exist; if it exceeds
+ *                   cap, SGX_ENOSPACE is returned and the buffers are not written (call again with cap >= *n_out).
+ *                   cutoff must be finite; stats may be NULL.
+ * Both are synchronous.  SGX_EINVAL (nothing launched, nothing written): a NULL buffer, a rectangle outside [0, N),
+ * ld < nj, a non-finite cutoff.  The scratch of both is allocated on first use and freed by sgx_grm_free. */
+typedef struct {
+	int64_t tiles;               /* 64 x 64 workgroup tiles contracted (bj >= bi)               */
+	int64_t pairs;               /* = *n_out                                                    */
+	double ms_kernel;            /* the contraction kernel on the device (HIP events)           */
+	double ms_sort;              /* copy to the host and sort                                   */
+} sgx_grm_king_stats;
+int  sgx_grm_king_counts(sgx_grm *g, int32_t i0, int32_t ni, int32_t j0, int32_t nj, int32_t *out, size_t ld);
+int  sgx_grm_king_pairs(sgx_grm *g, double cutoff, size_t cap, int32_t *i_out, int32_t *j_out, double *kin_out,
+	double *ibs0_out, int32_t *counts_out, size_t *n_out, sgx_grm_king_stats *stats);
+
 /* Operator of an explicit symmetric matrix K [n][n] resident on one device: the null-model fit on the matrix
  * sgx_grm_sparse / sgx_grm_dense made (SAIGE's useSparseGRMtoFitNULL, upstream SAIGEgds 2.x grm.mat=; not in the
  * reference, which has the implicit operator only: DESIGN.md 8f).

@@ -123,6 +123,13 @@ class SgxGrmSparseStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class SgxGrmKingStats(C.Structure):
+    _fields_ = [("tiles", C.c_int64), ("pairs", C.c_int64), ("ms_kernel", C.c_double), ("ms_sort", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SgxGrmPcaStats(C.Structure):
     _fields_ = [("iters", C.c_int32), ("n_converged", C.c_int32), ("ms_products", C.c_double), ("ms_block", C.c_double)]
 
@@ -191,6 +198,8 @@ def _abi():
         "sgx_grm_pca": (ci, [vp, ci, ci, vp, sz, ci, dp, vp, vp, vp, sz, vp, sz, ptr(SgxGrmPcaStats)]),
         "sgx_grm_ts_gram": (ci, [vp, i32, vp, sz, ci, vp, sz, ci, vp]),
         "sgx_grm_ts_apply": (ci, [vp, i32, vp, sz, ci, vp, ci, vp, sz]),
+        "sgx_grm_king_counts": (ci, [vp, i32, i32, i32, i32, vp, sz]),
+        "sgx_grm_king_pairs": (ci, [vp, dp, sz, vp, vp, vp, vp, vp, ptr(sz), ptr(SgxGrmKingStats)]),
         "sgx_kmat_init_csr": (ci, [i32, vp, vp, vp, ci, pvp]),
         "sgx_kmat_init_dense": (ci, [vp, sz, i32, ci, pvp]),
         "sgx_kmat_free": (None, [vp]),
@@ -1065,6 +1074,19 @@ def ld_corr(counts) -> np.ndarray:
         return np.where(den > 0, c.astype(np.float64) / den, np.nan)
 
 
+def king_values(counts):
+    """KING-robust kinship and IBS0 from the five counts [5, ...] (nn, hi, hj, hh, ibs0), the expressions of
+    ``sgx_grm_king_pairs`` in numpy float64 (the same bits): D = (hi + hj - 2 hh) + 4 ibs0, mn = min(hi, hj),
+    kinship = 0.5 - D / (4 mn) (NaN where mn == 0), IBS0 = ibs0 / nn (NaN where nn == 0)."""
+    c = np.asarray(counts).astype(np.int64)
+    nn, hi, hj, hh, ibs0 = (c[k] for k in range(5))
+    D, mn = (hi + hj - 2 * hh) + 4 * ibs0, np.minimum(hi, hj)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        kin = np.where(mn > 0, 0.5 - D.astype(np.float64) / (4.0 * mn.astype(np.float64)), np.nan)
+        ibs = np.where(nn > 0, ibs0.astype(np.float64) / nn.astype(np.float64), np.nan)
+    return kin, ibs
+
+
 def quantize_packed(raw, cls, scale, offset, n_samp: int, sel=None, device: int = 0, chunk_bytes: int = 0):
     """Stored dosage rows -> the 2-bit hard-call rows of the null-model fit and the marker filter's counts, on the GPU
     (``sgx_quantize_packed``): ``raw`` [m, n_file_samp] of class ``cls`` as for ``Scanner.scan_packed``, ``sel``: the
@@ -1219,6 +1241,38 @@ class GrmOperator(_Operator):
             check(rc)
             k = int(n_out.value)
             res = (i[:k].copy(), j[:k].copy(), x[:k].copy())
+            return res + (st.as_dict(),) if return_stats else res
+
+    # -- KING-robust kinship (sgx_grm_king_counts / sgx_grm_king_pairs); marker groups are ignored
+    def king_counts(self, i0: int, ni: int, j0: int, nj: int) -> np.ndarray:
+        """The five counts (nn, hi, hj, hh, ibs0) of the pairs [i0, i0 + ni) x [j0, j0 + nj): int32 [5, ni, nj], over
+        the markers where both samples are called (``king_values`` turns them into kinship and IBS0)."""
+        out = np.empty((5, max(int(ni), 0), max(int(nj), 0)), dtype=np.int32)
+        check(self._L.sgx_grm_king_counts(self._h, int(i0), int(ni), int(j0), int(nj), out.ctypes.data, out.shape[2]))
+        return out
+
+    def king_pairs(self, cutoff: float, cap: Optional[int] = None, return_stats: bool = False):
+        """The pairs i < j with KING-robust kinship >= cutoff -> (i, j, kinship, ibs0, counts [pairs, 5]), sorted by
+        (i, j); the numbers are those of ``king_values(king_counts(...))``.  Retries once with the size the library
+        reports when ``cap`` pairs (default 8 N) do not hold them.  With ``return_stats`` the dict of
+        sgx_grm_king_stats comes sixth."""
+        cap = int(8 * self.n if cap is None else cap)
+        for attempt in (0, 1):
+            i = np.empty(cap, dtype=np.int32)
+            j = np.empty(cap, dtype=np.int32)
+            kin = np.empty(cap, dtype=np.float64)
+            ibs = np.empty(cap, dtype=np.float64)
+            cnt = np.empty((cap, 5), dtype=np.int32)
+            n_out = C.c_size_t(0)
+            st = SgxGrmKingStats()
+            rc = self._L.sgx_grm_king_pairs(self._h, float(cutoff), cap, i.ctypes.data, j.ctypes.data, kin.ctypes.data,
+                                            ibs.ctypes.data, cnt.ctypes.data, C.byref(n_out), C.byref(st))
+            if rc == ENOSPACE and attempt == 0:
+                cap = int(n_out.value)
+                continue
+            check(rc)
+            k = int(n_out.value)
+            res = (i[:k].copy(), j[:k].copy(), kin[:k].copy(), ibs[:k].copy(), cnt[:k].copy())
             return res + (st.as_dict(),) if return_stats else res
 
     # -- the marker side of the product and the principal components of K (sgx_grm_marker_dots / sgx_grm_pca)

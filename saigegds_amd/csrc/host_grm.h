@@ -15,6 +15,7 @@ struct sgx_grm {
 	// (released in reverse order: buffers, events, the stream -- sgx_grm_free waits for the stream first)
 	DevStream stream;
 	DevEvent gd_ev0, gd_ev1;               // host_grm_dense.h: around the kernels of a piece of sgx_grm_dense
+	DevEvent kg_ev0, kg_ev1;               // host_king.h: around the kernel of sgx_grm_king_pairs
 	int N = 0; size_t M = 0;
 	size_t bpvN = 0, bpvM = 0;             // row strides of G (marker-major) and Gt (sample-major)
 	DevBuf<uint8_t> G, Gt;
@@ -45,6 +46,11 @@ struct sgx_grm {
 	DevBuf<double> md_out;                 // [k][M]: dot_v of k columns
 	DevBuf<double> ts_part, ts_C, ts_T;    // ts_gram partials [slabs][64][64], its result and the matrix of ts_apply [64][64]
 	DevBuf<double> pca_X0, pca_X1, pca_Y, pca_W;   // [n_block][N] blocks of sgx_grm_pca
+	// KING-robust kinship (host_king.h): scratch of sgx_grm_king_counts / sgx_grm_king_pairs, allocated on first use
+	DevBuf<int> kg_out;                    // [5][ni][nj] counts of a piece of a rectangle
+	DevBuf<unsigned long long> kg_cnt;     // [1] pairs listed
+	DevBuf<int> kg_i, kg_j, kg_c5;         // the pair list: indices and [pairs][5] counts
+	DevBuf<double> kg_kin, kg_ibs;         // ... kinship and IBS0
 };
 static_assert(GRM_MAX_RHS == SGX_GRM_MAX_RHS, "kern_grm.h and saigehip.h disagree on the column limit");
 static_assert(GRM_MAX_GROUPS == SGX_GRM_MAX_GROUPS, "kern_grm.h and saigehip.h disagree on the group limit");

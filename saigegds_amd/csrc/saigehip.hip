@@ -94,6 +94,7 @@ static int fail(int code, const char *fmt, ...)
 #include "kern_collapse_ds.h"
 #include "kern_ld.h"
 #include "kern_tsblock.h"
+#include "kern_king.h"
 
 // ---------------------------------------------------------------------------
 // host side: one translation unit (every kernel template is instantiated once), in topic files
@@ -117,6 +118,7 @@ static int fail(int code, const char *fmt, ...)
 #include "host_grm.h"
 #include "host_grm_dense.h"
 #include "host_pca.h"
+#include "host_king.h"
 #include "host_kmat.h"
 #include "host_skat_kmat.h"
 #include "host_cond_kmat.h"
